@@ -9,6 +9,13 @@ resident in HBM.  Default workload = BASELINE.json configs[1]: HR-Avenue-shaped 
 17 joints), noise_steps=10, 5 generated samples, inject conditioning, in-kernel Philox noise.
 
   python bench.py [--gpus N --steps K --warmup W] [--config avenue|stc|ubnormal_concat|seq24] [--scaling weak|strong]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (throughput, roofline from this run's own step times).
+--full adds the informational legs that take runs of their own: the CPU baseline, the AUC next to the reference-noise AUC,
+the sustained and end-to-end runs, the PCIe-inclusive rate and the shader clock / power reading.  --dump-outputs DIR writes
+the window scores of the last timed step to DIR/window_scores.npy (float32; inputs and noise seeds are fixed, so two builds
+compare output for output).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks (one per GPU,
 torch.distributed.run on 127.0.0.1 with a free port); started under torch.distributed.run it uses the ranks it is given.
@@ -572,11 +579,18 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for the cpu_baseline sample (all threads + one thread)")
     ap.add_argument("--dist-backend", default="nccl", help="'nccl' (= RCCL over xGMI, the default) or 'gloo' (tests that "
                     "place several ranks on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also run the informational legs (cpu_baseline, auc, sustained, e2e, "
+                    "value_incl_h2d, gpu_after_timed_region); each can still be left out with its own --no-* option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step "
+                    "(the 'best'-aggregated score of every window, all ranks) to DIR/window_scores.npy, float32")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 5 if args.config == "seq24" else 200
     if args.warmup is None:
         args.warmup = 2 if args.config == "seq24" else 20
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -710,7 +724,7 @@ def main():
     barrier()
     dt_local = time.perf_counter() - t0
     gpu_after = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         smp = GpuSampler(dev_index, 0.05)
         clk_, pw_ = smp._read()
         gpu_after = {"source": smp.source, "sclk_mhz": round(clk_, 1) if clk_ else None, "socket_power_w": round(pw_, 1) if pw_ else None,
@@ -742,6 +756,13 @@ def main():
         # the roofline then uses the timed region's average time per launch instead
         kern_ms = dt / args.steps * 1e3
     assert torch.isfinite(best).all()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's row of every rank's (steps, per) score block, each cut to that rank's windows
+        last = best.view(world, -1, per)[:, args.steps - 1, :].cpu()
+        counts = rank_info["windows_per_step"] if use_dist else [B]
+        scores_last = torch.cat([last[r, :counts[r]] for r in range(world)]).numpy().astype(np.float32)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "window_scores.npy"), scores_last)
 
     if rank == 0:
         total = B_total * args.steps
@@ -809,24 +830,24 @@ def main():
         if args.ref_value:
             out["scaling_efficiency"] = round(out["value"] / (args.ref_value * (world if args.scaling == "weak" else world)), 4)
             out["ref_value_1gpu"] = args.ref_value
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, cfg, ns, S, args.cpu_budget)
-        if world == 1 and not args.no_extras and not args.no_auc:
+        if world == 1 and extras and not args.no_auc:
             # `AUC vs ref` (BASELINE.json metric), untimed: see auc_vs_ref
             out["auc"] = auc_vs_ref(sc, sd, cfg, ns, S, with_oracle=not args.no_cpu_baseline and S * (ns - 1) <= 64)
-        if world == 1 and not args.no_extras and args.sustained_seconds > 0 and B > 0:
+        if world == 1 and extras and args.sustained_seconds > 0 and B > 0:
             # informational only (never `value`): the same launches back to back for >= --sustained-seconds
             sus_out = torch.zeros(per, device=dev, dtype=torch.float32)
             out["sustained"] = sustained_run(lambda i: sc.score_fused(data, n_samples=S, noise_steps=ns, aggregation="best", seed=5000 + i,
                                                                       first_window_id=lo, out=sus_out[:B]),
                                              args.sustained_seconds, kern_ms, B, flop_per_window, dev_index)
-        if world == 1 and not args.no_extras and args.e2e_windows != 0 and not variant.startswith("rand:"):
+        if world == 1 and extras and args.e2e_windows != 0 and not variant.startswith("rand:"):
             # informational only: the caller's loop around the path (test_step + on_test_epoch_end), about 0.5 s of scoring by default
             n_e2e = args.e2e_windows or int(max(4 * B, min(400_000, 0.5 * out["value"])))
             fpc = 200 if seg_len <= 12 else 300
             per_clip = 3 * (fpc - 5 - seg_len + 1) * int(cfg.get("num_transform", 5))
             out["e2e"] = e2e_run(sd, cfg, ns, S, B, max(1, round(n_e2e / per_clip)), fpc, dev, out["value"])
-        if world == 1 and not use_dist and not args.no_extras:
+        if world == 1 and not use_dist and extras:
             # informational only (never `value`): the same steps fed from pinned HOST windows, the H2D copy inside the timed loop
             n_x = min(args.steps, 10)
             pinned = data_host.pin_memory()

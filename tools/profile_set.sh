@@ -31,13 +31,13 @@ except Exception as e:
 PY
 }
 for c in $CFGS; do
-  timeout 600 python bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 600 python bench.py --config $c --full > $O/bench_$c.json 2> $O/bench_$c.err
   stamp_json $O/bench_$c.json
 done
 if [ -z "$2" ]; then
 # sustained: a TIMED region of >= 10 s for the four BASELINE shapes (value = the sustained rate)
 for c in $CFGS; do
-  timeout 600 python bench.py --config $c --min-seconds 10 --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/sustained_$c.json 2> $O/sustained_$c.err
+  timeout 600 python bench.py --config $c --min-seconds 10 --full --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/sustained_$c.json 2> $O/sustained_$c.err
   stamp_json $O/sustained_$c.json
 done
 # every other frame-count family: one line each (no CPU leg)
@@ -50,7 +50,7 @@ stamp $O/shapes.txt
   for sp in 5 1; do echo -n "avenue B=4096 split=$sp: "; python bench.py --batch 4096 --split $sp --no-cpu-baseline --no-extras | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'clips/s  frac', d['roofline']['frac'])"; done; } > $O/split_ab.txt 2>&1
 stamp $O/split_ab.txt
 # the shipped sample count of the reference's test configs (n_generated_samples: 50)
-timeout 600 python bench.py --samples 50 --steps 20 --warmup 2 --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/bench_avenue_S50.json 2> $O/bench_avenue_S50.err
+timeout 600 python bench.py --samples 50 --steps 20 --warmup 2 --full --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/bench_avenue_S50.json 2> $O/bench_avenue_S50.err
 stamp_json $O/bench_avenue_S50.json
 # in-kernel stage profiles (a -DMCD_PROFILE build of the same sources)
 for c in avenue ubnormal_concat seq24; do

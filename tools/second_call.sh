@@ -7,10 +7,10 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG}2
 mkdir -p $O
 for c in avenue stc ubnormal_concat seq24 concat24 concat32; do
-  timeout 600 python bench.py --config $c > $O/bench_$c.json 2>/dev/null
+  timeout 600 python bench.py --config $c --full > $O/bench_$c.json 2>/dev/null
 done
 for c in avenue seq24; do
-  timeout 600 python bench.py --config $c --min-seconds 60 --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/sustained60_$c.json 2>/dev/null
+  timeout 600 python bench.py --config $c --min-seconds 60 --full --no-cpu-baseline --no-auc --sustained-seconds 0 --e2e-windows 0 > $O/sustained60_$c.json 2>/dev/null
 done
 timeout 1500 python tests/studies/random_sweep.py 2>&1 | grep -v amdgpu.ids > $O/random_sweep.txt
 tail -1 $O/random_sweep.txt
