@@ -3,7 +3,7 @@ plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp
 
     python -m mocodad_amd.build                       # the shipped library (mocodad_amd/libmocodad_hip.so)
     python -m mocodad_amd.build --profile             # + -DMCD_PROFILE -> libmocodad_hip_prof.so (tools/stage_profile.py)
-    python -m mocodad_amd.build --fast-t 3 -o /tmp/x.so -D MCD_STASH=0    # developer build: one trajectory kernel only
+    python -m mocodad_amd.build --fast-t 3 -o /tmp/x.so -D MCD_FAST_TILED=24    # developer build: one trajectory kernel (+ the 24-frame tiled one)
 
 Objects are cached under csrc/_obj/<tag>/ (git-ignored) and rebuilt when a source, the public header or the flag set is newer /
 different; the library is relinked when any object changed."""

@@ -81,19 +81,6 @@ __device__ __forceinline__ float4 load_global4(const float* p) {       // 16-byt
 #ifndef MCD_NWAVES
 #define MCD_NWAVES 8
 #endif
-// Layer 8 (su4.1, 64 -> 32 channels at 12 joints) W-first in score_kernel, like layers 6 and 10: mix(W X) = W mix(X), so the
-// GEMM [W_t ; W_r] X (64 rows x K = 64: as many MFMAs as [W_t | W_r] [Z ; X], 32 rows x K = 128) comes first and the mix runs on
-// the 32 OUTPUT channels instead of the 64 input ones -- half the time-mix FMAs, joint-mix MFMAs and unit overhead of that
-// stage (round 6; the packer of mcd_api.hip packs the layer's weights to match).  0: mix-first as in rounds 1-5 (A/B builds).
-#ifndef MCD_L8_WFIRST
-#define MCD_L8_WFIRST 1
-#endif
-#ifndef MCD_XB32
-#define MCD_XB32 1      // 1: the mixes' X reads of the kernels without a register cap as single ds_read_b32 (mix_stage); 2: + their Z stores
-#endif
-#ifndef MCD_XB32_CAPPED
-#define MCD_XB32_CAPPED 1      // (round 6: +0.7 % at 3 frames, profiles/r06g_t3_variants_ab.txt) 1: the single-read form of the mixes' X reads in the register-capped trajectory kernels too; 2: + the Z stores (equal)
-#endif
 constexpr int NWAVES = MCD_NWAVES;          // waves per workgroup (8; 16 is a tuning experiment)
 constexpr int NTHREADS = NWAVES * 64;
 constexpr int C0 = 2;        // num_coords
@@ -156,29 +143,7 @@ constexpr int PROF_TRACE = 128;                          // time-stamp slots of 
 #endif
 // Everything the instrumentation needs lives in registers of the profiled workgroup (block 0): the timing adds are
 // fire-and-forget LDS atomics, no global memory access, no LDS round trip on the waves' paths.
-// Wave priority by PHASE (MCD_PHPRIO, a tuning experiment): the stages of a pass alternate between latency-bound ones (mixes,
-// resamplers, the tail: short dependent chains, a few instructions per wave) and throughput-bound ones (the channel GEMMs).  Two
-// workgroups share a CU; the issue arbiter picks by priority, then age.  `lat()` / `thr()` are called at the top of the
-// stages: a wave in a latency-bound stage outranks the other workgroup's GEMM waves (it needs few issue slots, but needs them
-// promptly), a GEMM wave takes what is left.  `slice` = the time-slice bit of the alternating scheme (see score_kernel).
-#ifndef MCD_PHPRIO
-#define MCD_PHPRIO 0
-#endif
-struct PhasePrio {
-    int slice;      // 0 / 1, wave-uniform
-    __device__ __forceinline__ void lat() const {
-        if constexpr (MCD_PHPRIO == 1 || MCD_PHPRIO == 3) __builtin_amdgcn_s_setprio(3);
-        else if constexpr (MCD_PHPRIO == 2) { if (slice) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2); }
-        else if constexpr (MCD_PHPRIO == 4) __builtin_amdgcn_s_setprio(0);
-    }
-    __device__ __forceinline__ void thr() const {
-        if constexpr (MCD_PHPRIO == 1 || MCD_PHPRIO == 2) { if (slice) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
-        else if constexpr (MCD_PHPRIO == 3) __builtin_amdgcn_s_setprio(0);
-        else if constexpr (MCD_PHPRIO == 4) __builtin_amdgcn_s_setprio(3);
-    }
-};
 struct Prof {
-    PhasePrio pp;
 #ifdef MCD_PROFILE
     unsigned* acc;               // LDS, PROF_SLOTS words
     unsigned long long tlast;
@@ -207,12 +172,12 @@ struct Prof {
             __hip_atomic_fetch_add(acc + PROF_STAGE + PROF_NW + bidx * PROF_NW + wv, (unsigned)(t1 - t0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         ++bidx;
     }
-    __device__ __forceinline__ void off() { pp.slice = 0; on = false; won = false; acc = nullptr; tlast = 0; bidx = 0; wv = 0; tr = nullptr; tr_on = false; }
+    __device__ __forceinline__ void off() { on = false; won = false; acc = nullptr; tlast = 0; bidx = 0; wv = 0; tr = nullptr; tr_on = false; }
 #else
     __device__ __forceinline__ void trace(int) {}
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void sync() { __syncthreads(); }
-    __device__ __forceinline__ void off() { pp.slice = 0; }
+    __device__ __forceinline__ void off() {}
 #endif
 };
 // workgroup barrier: every scope that synchronises has a `Prof prof` in reach
@@ -522,7 +487,7 @@ struct MixCfg {
     //     unit); 3 per unit at 32 channels (6 units) and 2 at 16 channels (2 + 2 + 2 + 2 + 1) are one round each: +0.9 % and +0.7 %
     //     (3 per unit at 16 channels: +0; profiles/r04ad_t9_mixq_ab.txt)
     //   5 frames, 32 channels: 3 + 2 (4 units) instead of 2 + 2 + 1 (6 units): +1.3 %
-    // and where the lever ends (-DMCD_QC16/32/64 sweep, profiles/r04ae_qc_sweep_ab.txt): 6 frames / 32 channels as 3 + 3: +0.1 %; fewer,
+    // and where the lever ends (a sweep of forced unit sizes, profiles/r04ae_qc_sweep_ab.txt): 6 frames / 32 channels as 3 + 3: +0.1 %; fewer,
     // larger units at 16 channels are slower (7 / 8 frames in pairs -1.3 / -2.3 %, 12 frames in triples -0.5 %)
     static constexpr int measured_qc() {
         // 12 waves per workgroup (the 12-frame kernel, mcd_instances.hpp): 12 units per stage where the frame count allows --
@@ -533,18 +498,7 @@ struct MixCfg {
         if (CIN == 16 && T == 9) return 2;
         return 0;
     }
-    // (tuning builds: -DMCD_QC16= / -DMCD_QC32= / -DMCD_QC64= force the frames per unit of the 16- / 32- / 64-channel mixes)
-#ifndef MCD_QC16
-#define MCD_QC16 0
-#endif
-#ifndef MCD_QC32
-#define MCD_QC32 0
-#endif
-#ifndef MCD_QC64
-#define MCD_QC64 0
-#endif
-    static constexpr int QF = CIN == 16 ? MCD_QC16 : CIN == 32 ? MCD_QC32 : CIN == 64 ? MCD_QC64 : 0;
-    static constexpr int QX = QF > 0 ? QF : measured_qc();
+    static constexpr int QX = measured_qc();
     static constexpr int QC = QX > 0 ? QX : (Q6 > 1 && units_of(Q6) >= NWAVES) ? Q6 : (Q5 > 1 && units_of(Q5) >= NWAVES) ? Q5
                             : (Q4 > 1 && units_of(Q4) >= NWAVES) ? Q4 : units_of(QALL) >= NWAVES ? QALL : units_of(Q2) >= NWAVES ? Q2
                             : 2 * units_of(QALL) > NWAVES ? QALL : 2 * units_of(Q2) > NWAVES ? Q2 : 1;
@@ -610,19 +564,14 @@ struct ChIdx {
 struct ZeroInit { __device__ __forceinline__ float operator()(int, int, int, int) const { return 0.f; } };
 // FORCE (kernels without a register cap): the unit's X reads are pinned in front of its arithmetic (the scheduler otherwise
 // sinks each k-step's reads to their first use and the wave pays an LDS round trip per k-step)
-#ifndef MCD_ALLW_CAPPED
-#define MCD_ALLW_CAPPED 1      // (+1.3 % at 3 frames, +0.9 % at 6: profiles/r05l_capped_ab.txt) tuning: the compile-time "every wave has a unit" of ALLW in the register-capped trajectory kernels too
-#endif
-#ifndef MCD_RS_FULL
-#define MCD_RS_FULL 1          // tuning: resample_stage's FULL
-#endif
 template <int CIN, int V, int T, int NB, bool FORCE = false, bool SCORE = false, class Init, class Store>
 __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_in, const MixCoef<CIN, V, T, NB>& pre,
                                           const float* __restrict__ tqd, const float* __restrict__ af, int wave, int lane,
                                           Init&& init, Store&& store) {
     using M = MixCfg<CIN, V, T, NB>;
     constexpr int KS = M::KS, KP = M::KP, MT = M::MT, CB = M::CB, QC = M::QC, NQ = M::NQ, PER = M::PER;
-    constexpr bool XB32 = (FORCE || (SCORE && MCD_XB32_CAPPED)) && MCD_XB32;
+    // (XB32 in the register-capped trajectory kernels too: +0.7 % at 3 frames, profiles/r06g_t3_variants_ab.txt)
+    constexpr bool XB32 = FORCE || SCORE;
     const int j = lane & 15, g = lane >> 4;
     const int voff_pair = 4 * (g & 1) + (g >> 1);
     // the X values of one unit: x[ks][t] = X[(n, t, joint of (ks, lane group))][channel cb*16 + j]
@@ -729,9 +678,10 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
         MixCoef<CIN, V, T, NB> cur = pre;
         static_for<PER>([&](auto ri) {
             constexpr int rnd = decltype(ri)::value;
-            // (full rounds: every wave has a unit -- said at compile time in the kernels without a register cap; in the condition
+            // (full rounds: every wave has a unit -- said at compile time in the kernels without a register cap and in the trajectory
+            // kernels, the register-capped ones included: +1.3 % at 3 frames, +0.9 % at 6, profiles/r05l_capped_ab.txt; in the condition
             // encoders' instantiations the same shortcut trips an "Unsupported instruction" abort of this compiler's backend)
-            constexpr bool ALLW = (FORCE || (SCORE && MCD_ALLW_CAPPED)) && !M::SAMEQ && M::UNITS == PER * NWAVES;
+            constexpr bool ALLW = (FORCE || SCORE) && !M::SAMEQ && M::UNITS == PER * NWAVES;
             const int u = ALLW ? wave + rnd * NWAVES : M::unit_of(wave, rnd);
             constexpr bool SURE = ALLW;       // (the SAMEQ map's first round gives every wave a unit as well: said too, -0.3 %, profiles/r05n_sameq_ab.txt)
             float xs[KS][T];
@@ -823,7 +773,7 @@ __device__ __forceinline__ void resample_stage(const float* __restrict__ in, int
     // may alias the next unit's reads, so reading inside the unit loop would serialise the units on LDS latency
     float xr[CAPTURE ? 1 : PER][CAPTURE ? 1 : KS] = {};      // (the down-samplers read straight into `skip`)
     // (FULL: every wave has all PER units -- said at compile time, or the conditional reads cost a copy of the whole `skip` array per unit)
-    constexpr bool FULL = MCD_RS_FULL && (CAPTURE || ADD) && UNITS == PER * NWAVES;      // (score_kernel's resamplers; the slab-tiled kernel's fused ones keep the run-time test, see DESIGN)
+    constexpr bool FULL = (CAPTURE || ADD) && UNITS == PER * NWAVES;      // (score_kernel's resamplers; the slab-tiled kernel's fused ones keep the run-time test, see DESIGN)
     // the mix whose unit map SQMAP follows (without SQMAP: a fixed valid instantiation, never used)
     using SM = std::conditional_t<SQMAP, MixCfg<(SQMAP ? C : 32), (SQMAP ? (CAPTURE ? VOUT : VIN) : 12), (SQMAP ? T : 3), (SQMAP ? NB : 2)>, MixCfg<32, 12, 3, 2>>;
     static_assert(!SQMAP || (SM::SAMEQ && UNITS == SM::UNITS && PER == SM::PER && !RC::ALIGNED), "SQMAP: the 12-unit SAMEQ mixes only");
@@ -991,12 +941,6 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
     const float* const p1b = b1 + __mul24(col0, cs1) + 4 * g;
     const float* const p2b = b2 + __mul24(col0, cs2) + 4 * g;
     constexpr int KQ = KQ1 + KQ2;
-#ifndef MCD_PIPE_DEPTH
-#define MCD_PIPE_DEPTH 1
-#endif
-#ifndef MCD_PIPE_SEED
-#define MCD_PIPE_SEED (MCD_NWAVES == 12)      // (12 waves, 168 registers: the seeds with the read-ahead, 16 spilled registers less: +2 % there; 8 waves: -0.4 %)
-#endif
     constexpr int DEPTH0 = KQ < 3 ? KQ : 3;
     // one 16x16 output tile: B fragments (one ds_read_b128 = 4 k-steps) fetched DEPTH0 reads ahead of the MFMAs that consume
     // them -- read right before its use each fragment exposes an LDS round trip per 4 MFMAs on this wave's matrix-pipe stream
@@ -1083,19 +1027,9 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
             epi(ib, col0 + i1 * NG * 16, c0, c[1], col0, ng);
         }
     };
-#ifndef MCD_GEMM_PIPE
-#define MCD_GEMM_PIPE 1
-#endif
-#ifndef MCD_GEMM_PIPE1
-#define MCD_GEMM_PIPE1 0
-#endif
-    constexpr bool PIPE = (DUAL || MCD_GEMM_PIPE1) && MAXN >= 2 && !HASPRE && MCD_GEMM_PIPE;
+    constexpr bool PIPE = DUAL && MAXN >= 2 && !HASPRE;
     constexpr int PW = DUAL ? 2 : 1;                      // tiles per pipeline step
-#ifndef MCD_PIPE_DEPTH_LONG
-#define MCD_PIPE_DEPTH_LONG MCD_PIPE_DEPTH
-#endif
-    constexpr int PD = KQ >= 8 ? MCD_PIPE_DEPTH_LONG : MCD_PIPE_DEPTH;      // (K = 128: 32 weight registers per wave)
-    constexpr int DEPTH = PIPE ? (KQ < PD ? KQ : PD) : DEPTH0;
+    constexpr int DEPTH = PIPE ? 1 : DEPTH0;              // (the pipeline reads one fragment ahead)
     if constexpr (PIPE) {
         // The pairs of a wave as ONE software pipeline: a pair's first DEPTH B fragments (and identity-residual seeds) are read
         // under the previous pair's last MFMAs, and a pair's epilogue is issued behind the NEXT pair's first k-group -- between
@@ -1103,7 +1037,6 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
         // Buffers and accumulators alternate by the pair's parity (compile-time indices: no copies).  Tile slots past the
         // wave's last tile are read like the others (never used; LDS reads past the allocation return 0) so that the stream has
         // no branches.
-        constexpr bool PIN = DUAL || MCD_GEMM_PIPE1 == 2;  // (under the register cap the order is left to the scheduler)
         constexpr int NP = (MAXN + PW - 1) / PW;
         const int nv = (NT - ng + NG - 1) / NG;           // this wave's tiles (wave-uniform)
         float4 bufs[2][2][DEPTH];
@@ -1119,7 +1052,8 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
                 constexpr int i0 = PW * p, i1 = (PW == 2 && i0 + 1 < MAXN) ? i0 + 1 : i0;
                 bufs[p & 1][0][d] = rdt(i0, dd);
                 if constexpr (i1 != i0) bufs[p & 1][1][d] = rdt(i1, dd);
-                if constexpr (IDRES && d == DEPTH - 1 && MCD_PIPE_SEED) {
+                // (12 waves, 168 registers: the seeds with the read-ahead, 16 spilled registers less: +2 % there; 8 waves: -0.4 %)
+                if constexpr (IDRES && d == DEPTH - 1 && NWAVES == 12) {
                     seed[p & 1][0] = *reinterpret_cast<const float4*>(p2b + i0 * NG * 16 * cs2 - 4 * g + c0);
                     if constexpr (i1 != i0) seed[p & 1][1] = *reinterpret_cast<const float4*>(p2b + i1 * NG * 16 * cs2 - 4 * g + c0);
                 }
@@ -1137,7 +1071,7 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
             for (int h = 0; h < N; ++h) {
                 c[h] = f32x4{cinit.x, cinit.y, cinit.z, cinit.w};
                 if (IDRES) {
-                    if constexpr (!MCD_PIPE_SEED) seed[p & 1][h] = *reinterpret_cast<const float4*>(p2b + (h ? i1 : i0) * NG * 16 * cs2 - 4 * g + c0);
+                    if constexpr (NWAVES != 12) seed[p & 1][h] = *reinterpret_cast<const float4*>(p2b + (h ? i1 : i0) * NG * 16 * cs2 - 4 * g + c0);
                     c[h] = f32x4{seed[p & 1][h].x, seed[p & 1][h].y, seed[p & 1][h].z, seed[p & 1][h].w};
                 }
             }
@@ -1152,7 +1086,7 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
                 } else if constexpr (N == PW) {           // (a short step is the wave's last)
                     fetch(std::integral_constant<int, p + 1>{}, std::integral_constant<int, kq + DEPTH - KQ>{});
                 }
-                if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 c[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kq].x, u[0].x, c[0], 0, 0, 0);
                 if constexpr (N == 2) c[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kq].x, u[1].x, c[1], 0, 0, 0);
                 c[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kq].y, u[0].y, c[0], 0, 0, 0);
@@ -1162,9 +1096,9 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
                 c[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kq].w, u[0].w, c[0], 0, 0, 0);
                 if constexpr (N == 2) c[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kq].w, u[1].w, c[1], 0, 0, 0);
                 if constexpr (kq == 0 && p > 0) {         // the previous pair's epilogue, behind this pair's first k-group
-                    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);
                     epi_pair(std::integral_constant<int, p - 1>{}, std::integral_constant<int, PW>{});
-                    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             });
             // the wave's last pair runs its epilogue itself; the others leave it to the pair behind them
@@ -1234,7 +1168,6 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
     float4 afr[KQ1 + KQ2];
     const int trs = 8 + 8 * ((prof_id - 32) / 3);      // trace slots of this layer (profile builds)
     prof.trace(trs + 0);
-    prof.pp.lat();
     const float* bias = wb + lw.bias;
     float4 bcur;
     if (pre_afr != nullptr) {
@@ -1247,10 +1180,7 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
         // latency hides behind the mix as well)
         bcur = load_global4(bias + (wave % MT) * 16 + 4 * (lane >> 4));
     }
-#ifndef MCD_MIX_FORCE
-#define MCD_MIX_FORCE 1
-#endif
-    mix_stage<CIN, V, T, NB, (FORCE && MCD_MIX_FORCE), HASEMB>(in, CSX, mc, wb + lw.tq, wb + lw.am, wave, lane,
+    mix_stage<CIN, V, T, NB, FORCE, HASEMB>(in, CSX, mc, wb + lw.tq, wb + lw.am, wave, lane,
                              ZeroInit{},
                              [&](int n, int q, int w, ChIdx c, auto v) {
                                  // joint w's row, the lane's channels: the unit's part of the address on the scalar unit, the lane's
@@ -1268,7 +1198,6 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
     // 3 frames +1.1 %: profiles/r03k_prebar_ab.txt).
     pre_gemm();
     bsync();
-    prof.pp.thr();
     prof.trace(trs + 2);
     prof.mark(prof_id);
     const float slope = lw.slope;
@@ -1353,7 +1282,6 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
 #endif
     prof.trace(trs + 5);
     bsync();
-    prof.pp.lat();
     prof.trace(trs + 6);
     prof.mark(prof_id + 1);
 }
@@ -1462,7 +1390,7 @@ struct Plan {
     static constexpr int UP3_out = 0;
     static constexpr int L7_in = 0, L7_z = s64b, L7_out = 2 * s64b;
     static constexpr int L8_in = 2 * s64b, L8_z = 0, L8_out = s64b;
-    static constexpr int L8_p = 0;              // W-first layer 8 (MCD_L8_WFIRST): P = [P_t | P_r] [P12][68] where z was; the layer's output replaces P_r
+    static constexpr int L8_p = 0;              // W-first layer 8: P = [P_t | P_r] [P12][68] where z was; the layer's output replaces P_r
     static constexpr int UP2_out = cmax(s64b + s32b, 2 * s32a);      // behind layer 8's output and layer 9's (z, out)
     static constexpr int L9_in = UP2_out, L9_z = 0, L9_out = s32a;
     static constexpr int L10_in = s32a, L10_p = 2 * s32a;

@@ -3,18 +3,6 @@
 #pragma once
 #include "mcd_device.hpp"
 
-// kernels with at most this many waves per SIMD get the latency-side forms (two GEMM tiles in flight, pinned read-ahead, resampler
-// units advancing together, coefficient fetches two stages ahead): 2 = the shapes without a register cap; 3 with the 12-wave tuning build
-#ifndef MCD_LOWOCC
-#define MCD_LOWOCC (MCD_NWAVES == 12 ? 3 : 2)
-#endif
-#ifndef MCD_NO_EARLY2
-#define MCD_NO_EARLY2 0
-#endif
-#ifndef MCD_RS_ILP
-#define MCD_RS_ILP 1
-#endif
-
 namespace mcd {
 
 // ------------------------------------------------------------------------------------------------
@@ -261,32 +249,17 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         }
     };
     // U-Net skip tensors d1 / d2, register-resident between the down- and the up-samplers
+    // (round 5: none is parked in private memory by hand any more -- d2 / d1 of the 6-frame kernel: +1.7 % without)
     using RS1 = RsCfg<32, 17, 12, T, NB, true>;
     using RS2 = RsCfg<64, 12, 10, T, NB, true>;
     float skip1[RS1::PER * RS1::SK];
     float skip2[RS2::PER * RS2::SK];
-    // 6 frames under the 128-VGPR cap (two workgroups per CU): d2 does not fit beside the 128-channel layers' fragments and
-    // the register allocator spilled it where it was read (before its own use) and reloaded it in front of every consumer.
-    // Parked in private memory by hand instead -- stored after down2 has used it, fetched back in front of the barrier
-    // that precedes up3, whose MFMAs run before the skip values are added: the round trip is off the critical path.
-#ifndef MCD_STASH
-#define MCD_STASH 0      // (round 5: nothing is hand-parked any more; bit 0 / 1: d2 / d1 of the 6-frame kernel, +1.7 % without)
-#endif
-#ifndef MCD_T6_LOWO
-#define MCD_T6_LOWO 0       // (round 6: off again -- with layer 8 W-first, the single-read mixes and the swapped-operand fragments in, the
-#endif                      //  plain forms are +1.2 .. 1.4 % at 6 frames, profiles/r06j_switch_sweep_ab.txt; round 5 had measured +1.1 % WITH it)
-#ifndef MCD_RELAUNDER_UP
-#define MCD_RELAUNDER_UP 1      // 0: off, 1: the register-capped kernels that spilled (see the step loop), 7: every kernel (A/B)
-#endif
-    // LOWO: the stage forms of the kernels with registers to spare -- pinned X reads in the mixes (FORCE), the pipelined GEMM's
-    // read-ahead, interleaved resampler units.  The 6-frame kernel joined them in round 5 (114 of its 128 registers once the
-    // up path derives its addresses again, see the step loop): +1.1 %; 3 frames -5 %, 5 frames +0.3 % (profiles/r05u_lowocc4_ab.txt)
-    constexpr bool LOWO = MINW <= MCD_LOWOCC || (MCD_T6_LOWO && T == 6 && NB == 1 && MINW >= 4);
-    constexpr bool STASH2 = !LT && ((MINW >= 4 && ((T == 6 && (MCD_STASH & 1)) || (T == 3 && (MCD_STASH & 4)))) || (MINW == 3 && (MCD_STASH & 32)));
-    constexpr bool STASH1 = !LT && ((MINW >= 4 && ((T == 6 && (MCD_STASH & 2)) || (T == 3 && (MCD_STASH & 8)))) || (MINW == 3 && (MCD_STASH & 16)));
-    float stash1_mem[STASH1 ? RS1::PER * RS1::SK : 1];
-    float stash2_mem[STASH2 ? RS2::PER * RS2::SK : 1];
-    typedef float __attribute__((address_space(5))) priv_float;         // (explicit private address space: scratch_*, not flat_*)
+    // LOWO: the stage forms of the kernels with registers to spare, at most 2 waves per SIMD (3 in the 12-wave build) -- pinned X
+    // reads in the mixes (FORCE), the pipelined GEMM's read-ahead, interleaved resampler units, coefficient fetches two stages ahead.
+    // The 6-frame kernel joined them in round 5 (114 of its 128 registers once the up path derives its addresses again, see the step
+    // loop): +1.1 %; 3 frames -5 %, 5 frames +0.3 % (profiles/r05u_lowocc4_ab.txt).  Round 6 took it out again: with layer 8 W-first,
+    // the single-read mixes and the swapped-operand fragments in, the plain forms are +1.2 .. 1.4 % there (profiles/r06j_switch_sweep_ab.txt)
+    constexpr bool LOWO = MINW <= (NWAVES == 12 ? 3 : 2);
 
     const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
     const int i_last = P.mode == 1 ? P.step_single : 1;
@@ -355,10 +328,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     // WEARLY: every layer's GEMM weight fragments are fetched at the end of the stage in front of the layer (see LayerAfr).
     // 3 / 4 frames only: +0.5 % there, nothing at 6 frames, -0.9 % at 12 (profiles/r03l_wearly_ab.txt) -- the larger shapes'
     // GEMM stages end with the other prefetches (EARLY2) already
-#ifndef MCD_WEARLY
-#define MCD_WEARLY 1
-#endif
-    constexpr bool WEARLY = T <= 4 && MCD_WEARLY;
+    constexpr bool WEARLY = T <= 4;
     LAfr<0> A0;
     if constexpr (WEARLY) load_lafr<0>(A0, P.wbuf, wave, lane);
     for (int sidx = i_first; sidx >= i_last; --sidx) {
@@ -386,11 +356,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                 unsigned hwid;
                 asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
                 const unsigned slice = (unsigned)(__builtin_amdgcn_s_memrealtime() >> sh);
-                prof.pp.slice = (int)(((hwid >> 16) ^ slice) & 1u);
-                if constexpr (MCD_PHPRIO == 0) {
-                    if (prof.pp.slice) __builtin_amdgcn_s_setprio(1);
-                    else __builtin_amdgcn_s_setprio(0);
-                }
+                if (((hwid >> 16) ^ slice) & 1u) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
             }
         }
         // ---- step prologue: this step's noise z (layer 0's mix coefficients were fetched at the end of the previous pass)
@@ -447,15 +414,12 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         // each SIMD only waits): the resampler is too short to cover 36 loads per wave, and issued at its top they delayed its
         // MFMAs by ~2 k cycles
         // (6 frames: +1 % on top of the pre-barrier placement; 3 frames: -0.3 %, the 128-register budget has no room for it)
-#ifndef MCD_EARLY2_ALL
-#define MCD_EARLY2_ALL 0       // tuning: EARLY2 in every kernel
-#endif
-        constexpr bool EARLY2 = (LOWO && !MCD_NO_EARLY2) || T == 6 || MCD_EARLY2_ALL;
+        constexpr bool EARLY2 = LOWO || T == 6;
         LMix<1, T, NB> mc1;
         // layer 0 reads the chain state XT[col][4] in place (x in channels 0,1): its lanes' channels 2..15 are then other
         // columns' coordinates -- finite, and multiplied by the zero-padded K rows of the layer's weights -- so no 16-channel
         // copy of x has to be zeroed and rewritten every pass
-        LAfr<1> A1; LAfr<2> A2; LAfr<3> A3; LAfr<4> A4; LAfr<5> A5; LAfr<7> A7; LAfr<8> A8; LAfr<9> A9;
+        LAfr<1> A1; LAfr<2> A2; LAfr<3> A3; LAfr<4> A4; LAfr<5> A5; LAfr<7> A7; LAfr<9> A9;
         auto wearly = [&](auto& A, auto lc) { if constexpr (WEARLY) load_lafr<decltype(lc)::value>(A, wb, wave, lane); };
 #define MCD_LC(l) std::integral_constant<int, l>{}
         layer_std<0, T, NB, LOWO, 4>(wb, mc0, XT, RG + PL::L0_z, RG + PL::L0_out, EMB, wave, lane, prof,
@@ -482,14 +446,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         lt_inject(11, RG + PL::L2_out, 36, 32, 17);
         if constexpr (!EARLY2) mix_early(mc3, 3);
         // (SQ12: down1 / up2 take their units in the order of layer 8's W-first mix, so that up2 follows that mix without a barrier)
-        constexpr bool SQ12 = MCD_L8_WFIRST && !LT && MixCfg<32, 12, T, NB>::SAMEQ;
-        resample_stage<32, 17, 12, T, NB, true, false, (LOWO && MCD_RS_ILP), SQ12>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc1, skip1, wave, lane);  // down1 (captures d1)
-        if constexpr (STASH1) {
-            priv_float* sp = (priv_float*)stash1_mem;
-            asm volatile("" : "+v"(sp));
-#pragma unroll
-            for (int i = 0; i < RS1::PER * RS1::SK; ++i) sp[i] = skip1[i];
-        }
+        constexpr bool SQ12 = !LT && MixCfg<32, 12, T, NB>::SAMEQ;
+        resample_stage<32, 17, 12, T, NB, true, false, LOWO, SQ12>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc1, skip1, wave, lane);  // down1 (captures d1)
         wearly(A3, MCD_LC(3));
         bsync();
         STAGE(5);
@@ -509,13 +467,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         lt_dump(4, RG + PL::L4_out, 68, 64, 12);
         lt_inject(12, RG + PL::L4_out, 68, 64, 12);
         if constexpr (!EARLY2) mix_early(mc5, 5);
-        resample_stage<64, 12, 10, T, NB, true, false, (LOWO && MCD_RS_ILP)>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc2, skip2, wave, lane);  // down2 (captures d2)
-        if constexpr (STASH2) {
-            priv_float* sp = (priv_float*)stash2_mem;
-            asm volatile("" : "+v"(sp));            // opaque: the array stays in memory, plain (cached) scratch accesses
-#pragma unroll
-            for (int i = 0; i < RS2::PER * RS2::SK; ++i) sp[i] = skip2[i];
-        }
+        resample_stage<64, 12, 10, T, NB, true, false, LOWO>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc2, skip2, wave, lane);  // down2 (captures d2)
         // wave-aligned units: the layer-5 mix reads only what this wave just wrote -> no barrier (see RsCfg::ALIGNED)
         constexpr bool FUSE64 = RS2::ALIGNED && MixCfg<64, 10, T, NB>::QC == T && MixCfg<64, 10, T, NB>::UNITS == NWAVES;
         wearly(A5, MCD_LC(5));
@@ -541,7 +493,6 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             lt_dump(5, RG + PL::L5_out, 132, 128, 10);
             lt_inject(6, RG + PL::L6_in, 132, 128, 10);
             float* Pb = RG + PL::L6_p;
-            prof.pp.thr();
             if constexpr (!EARLY2) mc6.load(wb + lw.tq, wb + lw.am, wave, lane);
             auto epi6 = [&](auto ti, int col, int c0, f32x4 acc, int col0, int) {
                 constexpr int STEP = Tiling<8, NT>::NG * 16 * 132;
@@ -555,7 +506,6 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             }
             if constexpr (EARLY2) { rs_early(rc3, 2); mix_early(mc7, 7); }      // up3's fragments, layer 7's mix coefficients
             bsync();
-            prof.pp.lat();
             STAGE(10);
             const float slope6 = lw.slope;
             const float pinf6 = prelu_bound(slope6);
@@ -578,13 +528,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                                          lds_store4(lds_addr(pp), r0[0], r0[1], r1[0], r1[1]);
                                      });
         }
-        if constexpr (STASH2) {
-            const priv_float* sp = (const priv_float*)stash2_mem;
-            asm volatile("" : "+v"(sp));
-#pragma unroll
-            for (int i = 0; i < RS2::PER * RS2::SK; ++i) skip2[i] = sp[i];
-        }
-        if constexpr (MCD_RELAUNDER_UP == 7 || (MCD_RELAUNDER_UP && (MINW == 3 || (MINW >= 4 && T >= 5)))) {
+        if constexpr (MINW == 3 || (MINW >= 4 && T >= 5)) {
             // The register-capped kernels (twelve waves: 168 registers; two workgroups per CU: 128): per-lane LDS addresses of the
             // down path that the up path's stages compute again -- the B-operand address of the 17-joint GEMMs (layers 2 and 9), a
             // mix's store address (layers 1 and 8) -- were kept live across the 128-channel layers, i.e. SPILLED there (all 11
@@ -609,7 +553,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         }
         // ---- up path
         if constexpr (!EARLY2) mix_early(mc7, 7);
-        resample_stage<64, 10, 12, T, NB, false, true, (LOWO && MCD_RS_ILP)>(RG + PL::L6_p + 64, 132, RG + PL::UP3_out, 68, rc3, skip2, wave, lane);  // up3 (+ d2)
+        resample_stage<64, 10, 12, T, NB, false, true, LOWO>(RG + PL::L6_p + 64, 132, RG + PL::UP3_out, 68, rc3, skip2, wave, lane);  // up3 (+ d2)
         wearly(A7, MCD_LC(7));
         // (up3 and layer 7's mix are both wave-aligned at 3 frames x 2 chains, and this barrier was removed in round 6 for +0.3 % --
         // and put back: layer 7's z region [s64b, 2 s64b) overlaps layer 6's P region, which slower waves are still READING in up3;
@@ -619,20 +563,14 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         STAGE(12);
         lt_dump(13, RG + PL::UP3_out, 68, 64, 12);
         lt_inject(7, RG + PL::L7_in, 68, 64, 12);
-        LMix<8, T, NB> mc8;
         RsCoef<32, 12, 17, T, NB, false> rc4;
         LMix<9, T, NB> mc9;
-        auto stash1_back = [&] {
-            if constexpr (STASH1) {
-                const priv_float* sp = (const priv_float*)stash1_mem;
-                asm volatile("" : "+v"(sp));
-#pragma unroll
-                for (int i = 0; i < RS1::PER * RS1::SK; ++i) skip1[i] = sp[i];
-            }
-        };
-        if constexpr (MCD_L8_WFIRST) {
+        {
             // ---- su4.0, then su4.1 (64 -> 32) W-first: P = [W_t ; W_r] X (64 rows), then out = PReLU(mix(P_t) + P_r + b) + e on the 32
             //      output channels, in place of P_r; up2 reads it from there (row stride 68)
+            // (round 6: mix(W X) = W mix(X), so the GEMM [W_t ; W_r] X -- 64 rows x K = 64: as many MFMAs as [W_t | W_r] [Z ; X], 32 rows
+            // x K = 128 -- comes first and the mix runs on the 32 output channels instead of the 64 input ones: half the time-mix FMAs,
+            // joint-mix MFMAs and unit overhead of the mix-first form; the packer of mcd_api.hip packs the layer's weights to match)
             constexpr int NT = PL::P12 / 16;
             constexpr int COLS = NB * T * 12;
             const LayerW lw = layer_w(wb, 8);
@@ -647,7 +585,6 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             lt_dump(7, RG + PL::L7_out, 68, 64, 12);
             lt_inject(8, RG + PL::L8_in, 68, 64, 12);
             float* Pb = RG + PL::L8_p;
-            prof.pp.thr();
             if constexpr (!EARLY2) mc8w.load(wb + lw.tq, wb + lw.am, wave, lane);
             auto epi8 = [&](auto ti, int col, int c0, f32x4 acc, int col0, int) {
                 constexpr int STEP = Tiling<4, NT>::NG * 16 * 68;
@@ -660,9 +597,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                 gemm_tiles<4, NT, 4, 0, false, LOWO>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, mi);
             }
             if constexpr (EARLY2) { rs_early(rc4, 3); mix_early(mc9, 9); }      // up2's fragments, layer 9's mix coefficients
-            stash1_back();
             bsync();
-            prof.pp.lat();
             prof.mark(32 + 3 * 8 + 1);                                          // (the tool's "gemm" column of layer 8)
             const float slope8 = lw.slope;
             const float pinf8 = prelu_bound(slope8);
@@ -689,24 +624,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             lt_dump(8, RG + PL::L8_p + 32, 68, 32, 12);
             lt_inject(14, RG + PL::L8_p + 32, 68, 32, 12);
             if constexpr (!EARLY2) mix_early(mc9, 9);
-            resample_stage<32, 12, 17, T, NB, false, true, (LOWO && MCD_RS_ILP), SQ12>(RG + PL::L8_p + 32, 68, RG + PL::UP2_out, 36, rc4, skip1, wave, lane);  // up2 (+ d1)
-        } else {
-        layer_std<7, T, NB, LOWO>(wb, mc7, RG + PL::L7_in, RG + PL::L7_z, RG + PL::L7_out, EMB, wave, lane, prof,
-                            [&] { mix_early(mc8, 8); }, [&] { wearly(A8, MCD_LC(8)); }, WEARLY ? &A7 : nullptr);     // su4.0
-        STAGE(13);
-        lt_dump(7, RG + PL::L7_out, 68, 64, 12);
-        lt_inject(8, RG + PL::L8_in, 68, 64, 12);
-        layer_std<8, T, NB, LOWO>(wb, mc8, RG + PL::L8_in, RG + PL::L8_z, RG + PL::L8_out, EMB, wave, lane, prof,
-                            [&] { rs_early(rc4, 3); },
-                            [&] {
-                                if constexpr (EARLY2) mix_early(mc9, 9);
-                                stash1_back();
-                            }, WEARLY ? &A8 : nullptr);                                            // su4.1
-        STAGE(14);
-        lt_dump(8, RG + PL::L8_out, 36, 32, 12);
-        lt_inject(14, RG + PL::L8_out, 36, 32, 12);
-        if constexpr (!EARLY2) mix_early(mc9, 9);
-        resample_stage<32, 12, 17, T, NB, false, true, (LOWO && MCD_RS_ILP)>(RG + PL::L8_out, 36, RG + PL::UP2_out, 36, rc4, skip1, wave, lane);  // up2 (+ d1)
+            resample_stage<32, 12, 17, T, NB, false, true, LOWO, SQ12>(RG + PL::L8_p + 32, 68, RG + PL::UP2_out, 36, rc4, skip1, wave, lane);  // up2 (+ d1)
         }
         wearly(A9, MCD_LC(9));
         bsync();

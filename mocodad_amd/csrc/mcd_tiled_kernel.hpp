@@ -17,7 +17,7 @@ namespace mcd {
 //   GEMM   gemm_part: z . W_t + x . W_r (or + x) of the part into register accumulators (<= 80 per lane); layers with 64 or
 //          128 input channels sum their 2 or 4 parts there; one epilogue (bias, PReLU, embedding) -> slab
 //   layers at 17 joints (32 input channels, X = 78 KB at 32 frames) take their frames in two groups so that X + z fit
-//   layer 6 runs mix-first here (the specialised kernels run it W-first); layer 10 W-first on plain FMAs + mix_long
+//   layer 6 runs mix-first here (the specialised kernels run it W-first); layer 10 W-first on the matrix cores + mix_long
 //   hand-overs: no layer waits for the slab.  A layer's epilogue writes what the next layer reads first straight into LDS --
 //          its first 32-channel part (3->4, 5->6, 7->8; the whole output across the 17-joint layers 0->1->2, 9->10, group 0's
 //          accumulators held back until group 1's time mix has read the old rows), or the next layer's resampler input (all of
@@ -44,48 +44,20 @@ __host__ __device__ constexpr int tl_ra_floats(int TP) {
 }
 // 24 frames: the LDS has room (29 KB of the 43 KB the plan leaves) for the SECOND chunk of a resampler's input as well, behind
 // the layers whose output all 32 channels of the next layer's fused resampler read (2 -> down1 -> 3, 8 -> up2 -> 9): both chunks are
-// handed over in LDS and layers 3 / 9 start without the store -> barrier -> load round trip through the slab (MCD_TL_EX)
-#ifndef MCD_TL_EX
-#define MCD_TL_EX 1
-#endif
+// handed over in LDS and layers 3 / 9 start without the store -> barrier -> load round trip through the slab (+0.9 %, profiles/r05z_tiled24_ex_ab.txt)
 // (+ 4 pad rows: the 17-joint resampler's last k-step reads joints 16 .. 19 of the chunk's last frame -- zero coefficients on finite values)
-__host__ __device__ constexpr int tl_ex_floats(int TF) { return (MCD_TL_EX && TF == 24) ? (tl_fc(TF) * 17 + 4) * 36 : 0; }
+__host__ __device__ constexpr int tl_ex_floats(int TF) { return TF == 24 ? (tl_fc(TF) * 17 + 4) * 36 : 0; }
 __host__ __device__ constexpr int tl_qc(int TP) { return TP % 3 == 0 ? 3 : 4; }     // output frames per mix unit (6 at 24 frames: 108 coefficient registers, spills)
 __host__ __device__ constexpr long long tl_slab_floats(int TP) {
     // A0, A1 (ping-pong, up to 128 ch x 10 joints), the skips D1, D2 -- each with 16 rows of padding behind it
     return (long long)2 * (TP * 10 + 16) * 132 + (long long)(TP * 17 + 16) * 36 + (long long)(TP * 12 + 16) * 68;
 }
 
-#ifndef MCD_TL_DENSE
-#define MCD_TL_DENSE 0     // 1: slab rows of exactly C floats (every 64-byte chunk of a row aligned); 0: C + 4 like the LDS rows
-#endif
 // row stride of a C-channel tensor in the SLAB.  The + 4 of the LDS row strides (cs_of) serves the LDS banks; in global memory it
 // puts a 32-channel part of a row (128 bytes) across two 128-byte lines.  Dense rows were measured: 24 frames +0.1 %, 32 frames
 // -2.2 % (power-of-two row strides; profiles/r05y_tiled_dense_rows_ab.txt) -- the padded stride stays
-__host__ __device__ constexpr int ss_of(int c) { return MCD_TL_DENSE ? c : c + 4; }
-// cross-layer prefetches in front of a layer's last channel GEMM (see `layer`), per frame-count class: bit 0 the next layer's first
-// time-mix fragments, bit 1 the fragments of the resampler fused into the next layer, bit 2 the skip rows of layers 7 / 9.
-// Measured per shape (profiles/r05z_tiled24_*_ab.txt, r05zb_tiled_pre_shapes_ab.txt): they hold registers across the GEMM
-#ifndef MCD_TL_PRE16
-#define MCD_TL_PRE16 7
-#endif
-#ifndef MCD_TL_PRE24
-#define MCD_TL_PRE24 7
-#endif
-#ifndef MCD_TL_PRE32
-#define MCD_TL_PRE32 7      // (32 frames: -0.8 .. -2 % while layer 5 held 80 accumulators per lane; +1.5 % since it runs on twelve waves, profiles/r05zj_tiled32_pre_w2_ab.txt)
-#endif
-__host__ __device__ constexpr int tl_pre(int TF) { return TF <= 16 ? MCD_TL_PRE16 : TF == 24 ? MCD_TL_PRE24 : MCD_TL_PRE32; }
-#ifndef MCD_TL_L5_W2
-#define MCD_TL_L5_W2 1
-#endif
+__host__ __device__ constexpr int ss_of(int c) { return c + 4; }
 template <class T> struct TlType { using type = T; };
-#ifndef MCD_TL_L10_MFMA
-#define MCD_TL_L10_MFMA 1
-#endif
-#ifndef MCD_TL_LATE
-#define MCD_TL_LATE 1      // the next part's slab loads go out right before the current part's channel GEMM (see `layer`)
-#endif
 // cooperative copies between the slab and LDS, `ch` channels (multiple of 4) from channel ch0 of `rows` rows
 __device__ __forceinline__ void tl_g2l(float* dst, int ds, const float* src, int ss, int ch0, int ch, int rows) {
     const int q = ch >> 2;
@@ -106,8 +78,9 @@ struct TlStage {
     __device__ __forceinline__ void issue(int tid, const float* src, int ss, int ch0) {
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            const int u0 = tid + i * NTHREADS, u = (MCD_TL_LATE && u0 >= ROWS * Q) ? ROWS * Q - 1 : u0;
-            if (MCD_TL_LATE || u < ROWS * Q) { const int r = u / Q, c = (u - r * Q) * 4; v[i] = load_global4(src + (size_t)r * ss + ch0 + c); }
+            const int u0 = tid + i * NTHREADS, u = u0 >= ROWS * Q ? ROWS * Q - 1 : u0;
+            const int r = u / Q, c = (u - r * Q) * 4;
+            v[i] = load_global4(src + (size_t)r * ss + ch0 + c);
         }
     }
     __device__ __forceinline__ void commit(int tid, float* dst, int ds) const {
@@ -507,9 +480,6 @@ __device__ __forceinline__ void gemm_part(const float4 (&a)[NA], const float* __
 
 // profile builds (tools/tiled_stage_profile.py): lane 0 of waves 0 and 7 of workgroup 0 add the cycles since their previous
 // mark to slot 2048 (+ 64 for wave 7) + id of the profile buffer
-#ifndef MCD_TL_ONECHUNK
-#define MCD_TL_ONECHUNK 1
-#endif
 #ifdef MCD_PROFILE
 // ... and lane 0 of EVERY wave of workgroup 0 stamps the events of ONE pass (the third of its first chain): event e of wave w at
 // slot 4096 + 16 e + w, the event's id at 4096 + 8192 + e (TLTR: a trace-only event)
@@ -713,15 +683,17 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
             // (layers 4 / 2), so their loads go out in front of the PREVIOUS layer's last channel GEMM instead of at the layer's start
             // ... and the next layer's first time-mix fragments likewise: fetched behind a layer's own epilogue they wait for the
             // epilogue's slab stores to be acknowledged (stores count in vmcnt too, and everything returns in order)
-            constexpr bool TQPRE = (tl_pre(TF) & 1) && !LT;
+            // (these cross-layer prefetches hold registers across the GEMM; measured per shape: profiles/r05z_tiled24_*_ab.txt,
+            // r05zb_tiled_pre_shapes_ab.txt; at 32 frames +1.5 % since layer 5 runs on twelve waves, profiles/r05zj_tiled32_pre_w2_ab.txt)
+            constexpr bool TQPRE = !LT;
             float tqx[TP / 4];
-            constexpr bool RCPRE = (tl_pre(TF) & 2) && !LT;      // ... and the fragments of the resampler fused into the next layer
+            constexpr bool RCPRE = !LT;      // ... and the fragments of the resampler fused into the next layer
             constexpr int FCX = tl_fc(TF);
             RsCoef<32, 17, 12, FCX, 1, false> rcx3;
             RsCoef<32, 12, 10, FCX, 1, false> rcx5;
             RsCoef<32, 10, 12, FCX, 1, false> rcx7;
             RsCoef<32, 12, 17, FCX, 1, false> rcx9;
-            constexpr bool SKPRE = (tl_pre(TF) & 4) && !LT && !COND;
+            constexpr bool SKPRE = !LT && !COND;
             TlStage<SKPRE ? TF * 12 : 1, 32> sk7;
             TlStage<SKPRE ? TF * 17 : 1, 32> sk9;
             auto layer = [&](auto lc, auto rsc, const float* xin, bool xin_lds, float* xout, const float* skip) {
@@ -806,8 +778,8 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                 // resampled input: a chunk of the resampler's input rows -- or, behind a layer that hands its output over in LDS (HIR: the
                 // z region holds the resampler's input of ALL frames), every later 32-channel part whole as well: its loads are issued a
                 // whole part ahead, where a part's second chunk was fetched under the first chunk's 300-cycle resampling (its latency
-                // to the slab exposed, plus two barriers per chunk)
-                constexpr bool ONE = HIR && MCD_TL_ONECHUNK;
+                // to the slab exposed, plus two barriers per chunk; profiles/r05q_tiled_onechunk_ab.txt)
+                constexpr bool ONE = HIR;
                 TlStage<RSI >= 0 ? (ONE ? NFC * IR : IR) : 1, 32> si;
                 RsCoef<32, VIN, V, TL_FC, 1, false> rc_own;
                 auto& rc = [&]() -> auto& {
@@ -819,21 +791,19 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                     static_assert(!HIC || (NH == 1 && NFC == 2), "");
                     // Vector-memory loads return IN ORDER: a wait for any load also waits for every older one.  The slab loads are the
                     // slow ones (the slabs of an XCD's workgroups are 13 MB against 4 MB of L2), so nothing that is needed early may
-                    // be issued behind them: the coefficient fetches go first, and (MCD_TL_LATE) a later part's slab loads only go out
+                    // be issued behind them: the coefficient fetches go first, and a later part's slab loads only go out
                     // right before the current part's channel GEMM -- the mix stages fetch their later units' coefficients in place
                     // and wait for them with vmcnt(0); issued in front of the mixes, as they were, the slab loads' whole latency sat
-                    // in every time mix.
-                    if constexpr (MCD_TL_LATE && !RCPRE) rc.load(wb + Nl->rsw[RSI], wb + Nl->rsw[RSI] + ((V + 15) / 16) * ((VIN + 3) / 4) * 64, lane);
+                    // in every time mix (profiles/r05q_tiled_late_prefetch_ab.txt).
+                    if constexpr (!RCPRE) rc.load(wb + Nl->rsw[RSI], wb + Nl->rsw[RSI] + ((V + 15) / 16) * ((VIN + 3) / 4) * 64, lane);
                     static_assert(!HIC2 || (IR + 4) * 36 <= EXF, "");
                     if constexpr (HIC2) { }                                                   // (both chunks are in LDS already)
                     else if constexpr (HIC) si.issue(tid, xin + (size_t)IR * CSI, CSI, 0);      // (chunk 0 is in the z region already)
-                    else if constexpr (!(MCD_TL_LATE && HIR)) si.issue(tid, xin, CSI, HIR ? CINV : 0);   // (HIR: part 0 is in the z region already, all chunks of it)
-                    if constexpr (!MCD_TL_LATE && !RCPRE) rc.load(wb + Nl->rsw[RSI], wb + Nl->rsw[RSI] + ((V + 15) / 16) * ((VIN + 3) / 4) * 64, lane);
+                    else if constexpr (!HIR) si.issue(tid, xin, CSI, 0);   // (HIR: part 0 is in the z region already, all chunks of it)
                     static_assert(RSI < 0 || HIC || HIR, "");
                 } else if (!xin_lds && !HI17) {
                     static_assert(!HI || (RSI < 0 && NH >= 2), "");
-                    static_assert(!MCD_TL_LATE || HI || HI17 || L == 0, "a plain layer's first part comes through LDS (hand-over), the later ones are fetched behind the GEMMs");
-                    if constexpr (!MCD_TL_LATE) sx.issue(tid, xin, CSI, HI ? CINV : 0);
+                    static_assert(HI || HI17 || L == 0, "a plain layer's first part comes through LDS (hand-over), the later ones are fetched behind the GEMMs");
                 }
                 float tqa[TP / 4], aja[(V + 15) / 16][(V + 3) / 4];     // the first units' mix coefficients, a stage ahead
                 if constexpr (TQPRE && L > 0) {
@@ -866,7 +836,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                 // the n-tiles wave / 4 + 3 i: 2 x 5 / 2 x 7 accumulators, the part's weight fragments (2 x 4 float4) fetched per part.
                 // 32 frames: 106 -> 58 spilled registers, 0.473 .. 0.517 run to run -> a steady 0.518 .. 0.520 (the spill traffic made
                 // the kernel erratic; profiles/r05zi_tiled32_l5w2_ab2.txt).  24 frames: 16 -> 0 spilled registers and -1.1 %: off there.
-                constexpr bool W2 = MCD_TL_L5_W2 && TF == 32 && L == 5 && MT == 8 && NWAVES == 12 && FS == 1 && RES && NH == 2;
+                constexpr bool W2 = TF == 32 && L == 5 && MT == 8 && NWAVES == 12 && FS == 1 && RES && NH == 2;
                 using TI2 = Tiling<4, NT>;
                 static_assert(!W2 || (TI2::NG == 3 && !HOR && !HOC && !HO17), "");
                 float4 aq2[W2 ? 2 : 1][W2 ? 2 * KH : 1];
@@ -905,7 +875,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                             si.commit(tid, ZA, CSZ);
                             TLXMARK(1);
                             __syncthreads();
-                            if constexpr (h + 1 < NH && !MCD_TL_LATE) si.issue(tid, xin, CSI, (h + 1) * CINV);
 #pragma unroll
                             for (int fc = 0; fc < NFC; ++fc)
                                 resample_stage<32, VIN, V, TL_FC, 1, false, false, true>(ZA + fc * IR * CSZ, CSZ, XA + fc * OR * CSV, CSV, rc, nosk, wave, lane);
@@ -922,7 +891,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                                     TLXMARK(1);
                                     __syncthreads();
                                     if (!HIC && fc + 1 < NFC) si.issue(tid, xin + (size_t)(fc + 1) * IR * CSI, CSI, h * CINV);
-                                    else if constexpr (h + 1 < NH && !MCD_TL_LATE) si.issue(tid, xin, CSI, (h + 1) * CINV);
                                 }
                                 resample_stage<32, VIN, V, TL_FC, 1, false, false, true>(ZA, CSZ, XA + fc * OR * CSV, CSV, rc, nosk, wave, lane);
                             }
@@ -940,7 +908,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                                 }
                             }
                             TLXMARK(1);
-                            if constexpr (h + 1 < NH && !MCD_TL_LATE) sx.issue(tid, skip, CSI, (h + 1) * CINV);
                         }
                         Xl = XA;
                     } else if (HI17) {
@@ -951,7 +918,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                             TLXMARK(0);
                             sx.commit(tid, XA, CSV);
                             TLXMARK(1);
-                            if constexpr (h + 1 < NH && !MCD_TL_LATE) sx.issue(tid, xin, CSI, (h + 1) * CINV);
                         }
                         Xl = XA;
                     }
@@ -1073,7 +1039,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                             TLMARK(4 * L + 1);
                             __syncthreads();
                             TLMARK(4 * L + 2);
-                            if constexpr (MCD_TL_LATE && h + 1 < NH) {      // the next part's slab loads: in flight behind this part's GEMM
+                            if constexpr (h + 1 < NH) {      // the next part's slab loads: in flight behind this part's GEMM
                                 if (fg == FS - 1) {
                                     if constexpr (RSI >= 0) {
                                         si.issue(tid, xin, CSI, (h + 1) * CINV);
@@ -1148,7 +1114,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
             layer(TL_C(9), TL_C(3), A1, false, A0, D1);                     // up2 + d1 on the way in
             }
             TLMARK(61);
-            if (!COND && (!LT || P.lt_stage == 10)) {   // ---- layer 10 (32 -> 2) W-first on plain FMAs: P4[col][r] = sum_k W4[r][k] X[col][k]  (P_t 0,1 ; P_r 2,3)
+            if (!COND && (!LT || P.lt_stage == 10)) {   // ---- layer 10 (32 -> 2) W-first on the matrix cores: P4[col][r] = sum_k W4[r][k] X[col][k]  (P_t 0,1 ; P_r 2,3)
                 int tid = tid0;
                 asm volatile("" : "+v"(tid));
                 const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1159,15 +1125,9 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                     }
                     __syncthreads();
                 }
-#ifndef MCD_TL_QC10
-#define MCD_TL_QC10 2
-#endif
-                // (16 frames: two output frames per unit -- 8 units, every wave busy -- instead of four in 4 units)
-                // (24 frames on twelve waves: two output frames per unit as well -- 12 units, every wave busy -- instead of three in 8)
-#ifndef MCD_TL_QC10_24
-#define MCD_TL_QC10_24 0      // (2: 12 units of two frames -- measured 0, profiles/r05z_tiled24_qc10_ab.txt)
-#endif
-                constexpr int QC10 = TF <= 16 ? MCD_TL_QC10 : (TF == 24 && NWAVES == 12) ? MCD_TL_QC10_24 : 0;
+                // (16 frames: two output frames per unit -- 8 units, every wave busy -- instead of four in 4 units; 24 frames on twelve
+                // waves as 12 units of two frames: measured 0, profiles/r05z_tiled24_qc10_ab.txt)
+                constexpr int QC10 = TF <= 16 ? 2 : 0;
                 MixLongCoef<16, 17, TP, NB, QC10> mc10;      // (the mix's first coefficients: in flight behind the product)
                 mc10.load(wb + Ns->tq[10], wb + Ns->am[10], wave, lane);
                 // P4[col][0 .. 3] = [W_t; W_r] (4 x 32) . X[col][0 .. 31].  Round 4 ran it as plain FMAs per column (a 16-row MFMA tile is 3/4
@@ -1175,7 +1135,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                 // 5 % of a pass; from LDS at wave-uniform addresses it is LDS-bound (40 ds_read_b128 per column on 7 of the 12 waves:
                 // 1.6 % of a pass).  On the matrix cores the padding is free -- 26 tiles x 8 MFMAs at 24 frames -- and a tile costs two
                 // B-operand reads: A = the weights' rows 0 .. 3 (zero rows below), K in the order (16 jj + 4 g + r) for both operands.
-#if MCD_TL_L10_MFMA
                 {
                     const int j = lane & 15, g = lane >> 4;
                     float4 af[2];
@@ -1197,23 +1156,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                         if (g == 0 && nt * 16 + j < R17) *reinterpret_cast<float4*>(P4 + (nt * 16 + j) * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
                     }
                 }
-#else
-                for (int col = tid; col < R17; col += NTHREADS) {
-                    const float* xp = RA + col * 36;          // layer 9's output, handed over in LDS
-                    float a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const float4 x = *reinterpret_cast<const float4*>(xp + 4 * q);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float4 w = *reinterpret_cast<const float4*>(W4L + r * 32 + 4 * q);
-                            a[r] = fmaf(w.x, x.x, a[r]); a[r] = fmaf(w.y, x.y, a[r]);
-                            a[r] = fmaf(w.z, x.z, a[r]); a[r] = fmaf(w.w, x.w, a[r]);
-                        }
-                    }
-                    *reinterpret_cast<float4*>(P4 + col * 4) = make_float4(a[0], a[1], a[2], a[3]);
-                }
-#endif
                 __syncthreads();
                 TLMARK(55);                            // layer 10: W-first product
                 // its 2-channel mix (16-channel block view of P4: channels 2..15 are the next columns' values, never stored)
