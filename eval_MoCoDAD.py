@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from mocodad_amd.data import synthetic  # noqa: E402
+from mocodad_amd.data.trajectories import check_supported, load_dataset  # noqa: E402
 from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
 from mocodad_amd.parallel import WindowShard  # noqa: E402
 from mocodad_amd.utils.argparser import load_config  # noqa: E402
@@ -43,6 +44,11 @@ def main():
     args = load_config(cli.config)
     if hasattr(args, "diffusion_on_latent"):
         raise NotImplementedError("the latent-diffusion variant (MoCoDADlatent) is outside the accelerated path")
+    if not cli.synthetic:
+        try:
+            check_supported(args)        # (before any GPU call)
+        except ValueError as e:
+            raise SystemExit(f"eval_MoCoDAD.py: {e}") from None
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -82,8 +88,12 @@ def main():
         synthetic.write_gt(gt_dir, gts)
         args.gt_path = gt_dir
     else:
-        raise SystemExit("dataset files are read by the reference's own pipeline (utils/dataset.py); "
-                         "pass --synthetic N here, or feed your DataLoader's batches to MoCoDAD.test_step")
+        # the dataset of the YAML paths: CSVs parsed on the host, normalised into the trajectory buffer on the device
+        tw, load_t = load_dataset(args, dev)
+        data, trans, meta, frames = tw, tw.trans.long(), tw.meta, tw.frames
+        if rank == 0:
+            print(f"dataset: {tw.n_samples} windows x {tw.num_transform} transforms from {args.data_dir}  load: parse "
+                  f"{load_t['parse']:.3f}s  upload+normalise {load_t['normalise']:.3f}s")
 
     torch.manual_seed(int(getattr(args, "seed", 0)))      # without a checkpoint every rank must draw the same weights
     model = MoCoDAD(args).to(dev)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 4
+#define MCD_ABI_VERSION 5
 
 enum {
     MCD_OK = 0,
@@ -241,6 +241,15 @@ int mcd_aggregate(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_join
  * row (one per (transform, clip, person)), out (n_rows, n_frames) pre-zeroed by the callee. */
 int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* row, int64_t n, int32_t seg_len,
                     int32_t n_rows, int32_t n_frames, float* out, void* stream);
+
+/* Replaces: Trajectory._from_image_to_centre_bounding_box + compute_bounding_box (utils/data.py:11-43,165-186)
+ * and scale_trajectories_robust (utils/data.py:350-359).  raw (n_frames, 34) f32 = the CSV columns 1..34
+ * (x1,y1,...,x17,y17); out (n_frames, 2, 17) f32 = the frame-major buffer layout of mcd_window_view_t.
+ * center/scale: device (34,) f64 in the CSV's interleaved feature order, or both NULL = no robust scaling.
+ * Bit-exact to the reference under NumPy >= 2 (fp32 box arithmetic, round-half-even box sides; the scaler's subtraction and
+ * division in float64, rounded to fp32 after each).  PRECONDITION: `raw` is finite (the Python wrapper checks it). */
+int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float vid_h,
+                        const double* center, const double* scale, float* out, void* stream);
 
 /* Frame-score assembly after the path, whole: replaces the (transform, clip, person) loops of
  * MoCoDAD.post_processing (mocodad.py:362-425) with compute_var_matrix + np.nanmax (eval_utils.py:27-34, mocodad.py:392-393),

@@ -14,7 +14,7 @@ LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
 COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class Tensor(C.Structure):
@@ -71,6 +71,8 @@ _SIGS = {
     "mcd_frame_scores_workspace_bytes": (C.c_int64, [C.POINTER(FrameCfg)]),
     "mcd_frame_scores": (C.c_int, [C.POINTER(FrameCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_normalize_poses": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
     "mcd_last_error": (C.c_char_p, []),
     "mcd_abi_version": (C.c_int32, []),
 }

@@ -6,6 +6,7 @@
 //   score_generic_kernel        plain-FMA runtime-shape trajectory kernel: the CROSS-CHECK of the MFMA kernels (MCD_OPT_GENERIC_UNET)
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
 //   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
+//   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
 // The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
@@ -579,6 +580,59 @@ __global__ void scatter_max_kernel(const float* __restrict__ scores, const int* 
     if (f < 0 || f >= n_frames) return;
     // non-negative floats order like their bit patterns
     atomicMax(reinterpret_cast<int*>(out + (size_t)row[i] * n_frames + f), __float_as_int(fmaxf(scores[i], 0.f)));
+}
+
+// Per-frame pose normalisation of the dataset loader (utils/data.py:11-43,165-186 + 350-359), one thread per frame, in the
+// reference's own precision (NumPy >= 2 scalar rules, DESIGN.md "Dataset loading"): the box, its margin and the clip in fp32,
+// round-half-even to int, (x - centre) / size correctly rounded in fp32 (computed in double and rounded once: exact, 53 >= 2*24+2),
+// then sklearn's RobustScaler.transform, which runs x - center_ and / scale_ in float64 and rounds to fp32 after each.
+// raw (n, 34) = x1,y1,...,x17,y17; out (n, 2, 17).
+__global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __restrict__ raw, long long n, float vid_w, float vid_h,
+                                                              const double* __restrict__ center, const double* __restrict__ scale,
+                                                              float* __restrict__ out) {
+#pragma clang fp contract(off)      // the margin is 0.1 * (r - l + 1), then l - margin: two roundings, never an FMA
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const float* r = raw + f * 34;
+    float* o = out + f * 34;
+    float v[34];
+    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    for (int k = 0; k < 34; k += 2) {
+        v[k] = r[k]; v[k + 1] = r[k + 1];
+        if (v[k] != 0.f) { xmin = fminf(xmin, v[k]); xmax = fmaxf(xmax, v[k]); }
+        if (v[k + 1] != 0.f) { ymin = fminf(ymin, v[k + 1]); ymax = fmaxf(ymax, v[k + 1]); }
+    }
+    if (xmin > xmax || ymin > ymax) {
+        // all joints missing, or no non-zero x (y): box (0, 0, 0, 0), zero width and height -> the frame is all zeros
+        for (int k = 0; k < 34; ++k) v[k] = 0.f;
+    } else {
+        const float ew = 0.1f * ((xmax - xmin) + 1.f), eh = 0.1f * ((ymax - ymin) + 1.f);
+        const float wm1 = vid_w - 1.f, hm1 = vid_h - 1.f;
+        const int L = (int)rintf(fminf(fmaxf(xmin - ew, 0.f), wm1)), R = (int)rintf(fminf(fmaxf(xmax + ew, 0.f), wm1));
+        const int T = (int)rintf(fminf(fmaxf(ymin - eh, 0.f), hm1)), B = (int)rintf(fminf(fmaxf(ymax + eh, 0.f), hm1));
+        const double cx = 0.5 * (double)(L + R), cy = 0.5 * (double)(T + B);
+        const double w = (double)(R - L), h = (double)(B - T);
+        for (int k = 0; k < 34; k += 2) {
+            // missing joints (0) take the centre, which the subtraction then removes
+            const float dx = (float)((double)(v[k] == 0.f ? (float)cx : v[k]) - cx);
+            const float dy = (float)((double)(v[k + 1] == 0.f ? (float)cy : v[k + 1]) - cy);
+            v[k] = w != 0.0 ? (float)((double)dx / w) : 0.f;
+            v[k + 1] = h != 0.0 ? (float)((double)dy / h) : 0.f;
+        }
+    }
+    for (int k = 0; k < 34; ++k) {
+        float t = v[k];
+        if (center) {
+            // exact zeros are NaN (missing) for the scaler and come back as 0, as does any other NaN of the transform
+            if (t == 0.f) t = 0.f;
+            else {
+                t = (float)((double)t - center[k]);
+                t = (float)((double)t / scale[k]);
+                if (t != t) t = 0.f;
+            }
+        }
+        o[(k & 1) * 17 + (k >> 1)] = t;
+    }
 }
 
 
@@ -1724,6 +1778,21 @@ int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* r
     const long long total = (long long)n * seg_len;
     hipLaunchKernelGGL(scatter_max_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, scores, frames, row,
                        (long long)n, seg_len, n_frames, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float vid_h, const double* center,
+                        const double* scale, float* out, void* stream) {
+    if (n_frames < 0) return fail(MCD_EINVAL, "n_frames < 0");
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    if (n_frames == 0) return MCD_OK;
+    if (!raw || !out) return fail(MCD_EINVAL, "null argument");
+    const long long blocks = (n_frames + 255) / 256;
+    if (blocks > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many frames for one launch");
+    hipLaunchKernelGGL(normalize_poses_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw,
+                       (long long)n_frames, vid_w, vid_h, center, scale, out);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }

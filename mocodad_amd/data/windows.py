@@ -84,6 +84,42 @@ class TrajectoryWindows:
         self.frames = torch.from_numpy(np.stack(frames).astype(np.int32)).repeat(nt, 1) if n else torch.zeros(0, seg_len, dtype=torch.int32)
         self.affine = affine_table(nt)
 
+    @classmethod
+    def from_buffer(cls, buffer: torch.Tensor, row_offsets, frame_ids, keys: List[Tuple[int, int, int]], seg_len: int,
+                    num_transform: int = 1, seg_stride: int = 1) -> "TrajectoryWindows":
+        """Windows of trajectories already in a (device) buffer, with the frame ids of their rows: the form the dataset loader
+        (data/trajectories.py) builds.  buffer: flat fp32, frame-major (rows, C, V); trajectory i = rows
+        row_offsets[i] .. row_offsets[i+1] with key keys[i] = (scene, clip, person), keys in ascending order; frame_ids (rows,):
+        the frame column of each row, gaps included, so that meta = [scene, clip, person, frame_ids[start]] and a window's frames
+        are frame_ids[start : start + seg_len] (utils/preprocessing.py:14-86)."""
+        off = np.asarray(row_offsets, dtype=np.int64)
+        fid = np.asarray(frame_ids, dtype=np.int64)
+        if off.shape != (len(keys) + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or fid.shape != (int(off[-1]),):
+            raise ValueError("row_offsets must be (n_trajectories + 1,) ascending from 0, frame_ids one per row")
+        if list(keys) != sorted(keys):
+            raise ValueError("trajectories must be in ascending (scene, clip, person) order")
+        if buffer.numel() != int(off[-1]) * N_COORDS * N_JOINTS:
+            raise ValueError(f"buffer holds {buffer.numel()} floats, the row offsets describe {int(off[-1])} rows")
+        self = cls.__new__(cls)
+        self.seg_len, self.num_transform = seg_len, max(1, num_transform)
+        lens = np.diff(off)
+        nw = np.where(lens >= seg_len, (lens - seg_len) // seg_stride + 1, 0)
+        traj = np.repeat(np.arange(len(keys)), nw)
+        step = np.arange(int(nw.sum()), dtype=np.int64) - np.repeat(np.cumsum(nw) - nw, nw)
+        start = off[:-1][traj] + step * seg_stride                                  # first row of every window
+        k = np.asarray(keys, dtype=np.int64).reshape(-1, 3)
+        meta = np.concatenate([k[traj], fid[start][:, None]], axis=1)
+        frames = fid[start[:, None] + np.arange(seg_len)].astype(np.int32)
+        n, nt = len(start), self.num_transform
+        self.buffer = buffer
+        self.n_samples = n
+        self.base = torch.from_numpy(start * N_COORDS * N_JOINTS).repeat(nt)
+        self.trans = torch.arange(nt, dtype=torch.int32).repeat_interleave(n)
+        self.meta = torch.from_numpy(meta).reshape(-1, 4).repeat(nt, 1)
+        self.frames = torch.from_numpy(frames).reshape(-1, seg_len).repeat(nt, 1)
+        self.affine = affine_table(nt).to(buffer.device)
+        return self
+
     def __len__(self):
         return int(self.base.shape[0])
 

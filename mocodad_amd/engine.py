@@ -347,6 +347,55 @@ class HipScorer:
         return out
 
 
+def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, device=None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dataset loader step (mcd_normalize_poses): raw (n_frames, 34) fp32 pose rows as read from the CSVs (x1,y1,...,x17,y17;
+    host array or tensor on any device) -> (n_frames, 2, 17) fp32 on `device`: bounding-box-centre coordinates
+    (utils/data.py:11-43,165-186) and, when center / scale (34,) are given, the RobustScaler transform (utils/data.py:350-359)
+    with the fitted statistics in the CSV's interleaved feature order.  `out`: an (n_frames, 2, 17) fp32 device view to write
+    into instead (e.g. a slice of a larger trajectory buffer)."""
+    L = _lib.lib()
+    if not torch.cuda.is_available():
+        raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
+    if (center is None) != (scale is None):
+        raise ValueError("center and scale go together (both None = no robust scaling)")
+    dev = torch.device(device if device is not None else (out.device if out is not None else f"cuda:{torch.cuda.current_device()}"))
+    if torch.is_tensor(raw) and raw.device.type == "cuda":
+        raw = raw.to(dev, torch.float32).contiguous()
+        finite = (not raw.numel()) or bool(torch.isfinite(raw).all().item())
+    else:
+        raw_h = np.ascontiguousarray(raw.numpy() if torch.is_tensor(raw) else raw, dtype=np.float32)
+        finite = bool(np.isfinite(raw_h).all())
+        raw = None
+    shape = tuple((raw if raw is not None else raw_h).shape)
+    if len(shape) != 2 or shape[1] != 34:
+        raise ValueError(f"raw pose rows must be (n_frames, 34) = x1,y1,...,x17,y17, got {shape}")
+    if not finite:
+        raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+    w, h = (float(np.float32(v)) for v in vid_res)
+    if not (np.isfinite(w) and np.isfinite(h)):
+        raise ValueError(f"vid_res must be finite, got {tuple(vid_res)}")
+    stats = []
+    for name, a in (("center", center), ("scale", scale)):
+        if a is None:
+            continue
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.shape != (34,):
+            raise ValueError(f"{name} must hold 34 features, got shape {a.shape}")
+        stats.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
+    n = shape[0]
+    if out is None:
+        out = torch.empty(n, 2, 17, device=dev, dtype=torch.float32)
+    elif out.shape != (n, 2, 17) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous (n_frames, 2, 17) fp32 tensor on the device")
+    with torch.cuda.device(dev):
+        if raw is None:
+            raw = torch.from_numpy(raw_h).to(dev)
+        c, s = (stats[0], stats[1]) if stats else (None, None)
+        _lib.check(L.mcd_normalize_poses(_ptr(raw), n, w, h, _ptr(c), _ptr(s), _ptr(out), _stream()))
+    return out
+
+
 class FrameScoreAssembler:
     """Window scores -> per-frame anomaly scores on the device (mcd_frame_scores): the whole of the reference's
     post_processing loops (mocodad.py:362-425) except roc_auc_score.  Built once per dataset from the ground-truth masks."""
