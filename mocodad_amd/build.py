@@ -5,6 +5,10 @@ plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp
     python -m mocodad_amd.build --profile             # + -DMCD_PROFILE -> libmocodad_hip_prof.so (tools/stage_profile.py)
     python -m mocodad_amd.build --fast-t 3 -o /tmp/x.so -D MCD_FAST_TILED=24    # developer build: one trajectory kernel (+ the 24-frame tiled one)
 
+The instance tables of csrc/mcd_instances.hpp say which kernels exist and in which unit; a unit is selected with -DMCD_INST_UNIT_<n>.
+A developer build (-DMCD_FAST_T) makes the header reduce the tables to the requested rows in unit 1; this script only adds the
+shipped NB / MINW / unit flags of that frame count (shipped_shape) unless the command line gives others.
+
 Objects are cached under csrc/_obj/<tag>/ (git-ignored) and rebuilt when a source, the public header or the flag set is newer /
 different; the library is relinked when any object changed."""
 import argparse
@@ -124,7 +128,7 @@ def build_library(out: str = DEFAULT_OUT, defines: Iterable[str] = (), extra_fla
     units = [1] if fast else list(range(1, n_units() + 1))
     jobs_l = [("mcd_api.o", os.path.join(CSRC, "mcd_api.hip"), [])]
     uf = {} if fast else {u: usable_flags(f) for u, f in unit_flags().items()}      # (developer builds: command line / main())
-    jobs_l += [(f"mcd_inst_{u}.o", os.path.join(CSRC, "mcd_inst.hip"), [f"-DMCD_INST_UNIT={u}"] + uf.get(u, [])) for u in units]
+    jobs_l += [(f"mcd_inst_{u}.o", os.path.join(CSRC, "mcd_inst.hip"), [f"-DMCD_INST_UNIT_{u}"] + uf.get(u, [])) for u in units]
     todo = [(o, s, f) for o, s, f in jobs_l
             if force or not os.path.exists(os.path.join(obj_dir, o)) or os.path.getmtime(os.path.join(obj_dir, o)) < newest(s)]
     t0 = time.perf_counter()

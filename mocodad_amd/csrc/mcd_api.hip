@@ -1,6 +1,7 @@
 // mcd_api.hip — host side of libmocodad_hip.so: the C ABI of include/mocodad_hip.h, the weight packer (BatchNorm folding, MFMA
-// fragment order), dispatch to the kernel instantiations of mcd_inst.hip (declared `extern template` in mcd_launch.hpp), and the
-// kernels that are not templates:
+// fragment order), dispatch to the kernel instantiations of mcd_inst.hip (declared `extern template` in mcd_launch.hpp; every
+// switch over frame counts is an expansion of the tables of mcd_instances.hpp, and which kernel family serves a handle is decided
+// by unet_route() / cond_route() alone: entry points, launches and workspace sizing ask them), and the kernels that are not templates:
 //   cond_encode_kernel          STSE.encode for any channel list / 21 .. 31 condition frames   models/stsae/stsae.py:59-92
 //   cond_unet_generic_kernel    'E_unet' condition encoder at any frame count (cross-check)    models/stsae/stsae_unet.py:62-146
 //   score_generic_kernel        plain-FMA runtime-shape trajectory kernel: the CROSS-CHECK of the MFMA kernels (MCD_OPT_GENERIC_UNET)
@@ -10,6 +11,7 @@
 // The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
+#include <algorithm>
 #include "mcd_launch.hpp"
 
 #if MCD_NWAVES != 8 && !defined(MCD_FAST_T)      // (developer builds pass one flag set to every file)
@@ -858,49 +860,31 @@ int pack_gemm_frags(Builder& B, int M, int K, F&& w) {
 
 namespace {
 
-int launch_score(const mcd_weights* w, int T, ScoreParams& P, hipStream_t st, bool* fused = nullptr) {
-    P.force_split = w->opt[MCD_OPT_SPLIT];
-    P.phase = w->opt[MCD_OPT_PHASE];
-#if defined(MCD_FAST_T)     // developer builds: one instantiation only (mcd_launch.hpp)
-    if (T != MCD_FAST_T) return fail(MCD_EUNSUPPORTED, "fast build");
-    return launch_score_t<MCD_FAST_T, MCD_FAST_NB, MCD_FAST_MINW>(P, st, fused);
-#else
-#ifdef MCD_TUNING_VARIANTS  // alternative workgroup shapes (MCD_OPT_VARIANT), developer builds only
-    const int variant = w->opt[MCD_OPT_VARIANT];
-    if (T == 3 && variant == 1) return launch_score_t<3, 4, 2>(P, st, fused);   // 4 chains / WG, 1 WG per CU
-    if (T == 3 && variant == 3) return launch_score_t<3, 1, 4>(P, st, fused);   // 1 chain / WG (tuning variant)
-    if (T == 3 && variant == 2) return launch_score_t<3, 2, 2>(P, st, fused);   // the default shape without the register cap
-    if (T == 6 && variant == 1) return launch_score_t<6, 2, 2>(P, st, fused);   // 2 chains / WG, 1 WG per CU (no register cap)
-#else
-    if (w->opt[MCD_OPT_VARIANT] != 0) return fail(MCD_EUNSUPPORTED, "MCD_OPT_VARIANT needs a -DMCD_TUNING_VARIANTS build");
-#endif
-    switch (T) {
-        case 3: return launch_score_t<3, 2, 4>(P, st, fused);                 // 2 chains / WG, 2 WGs per CU (<= 128 VGPRs)
-        case 6: return launch_score_t<6, 1, 4>(P, st, fused);                 // 1 chain / WG, 2 WGs per CU
-        case 12: return launch_score_t<12, 1, 3>(P, st, fused);               // 1 chain / WG of 12 waves, 1 WG per CU (168 registers; mcd_instances.hpp)
-        case 4: return launch_score_t<4, 1, 4>(P, st, fused);                 // e.g. seg_len 8 split in halves
-        case 5: return launch_score_t<5, 1, 4>(P, st, fused);                 // e.g. seg_len 10 split in halves (1 chain / WG, 2 WGs per CU: +4.7 % over <5,2,2>, profiles/r04r_t5_shape_ab.txt)
-        case 8: return launch_score_t<8, 1, 2>(P, st, fused);                 // e.g. seg_len 8 concat / seg_len 12 with 4 condition frames
-        case 10: return launch_score_t<10, 1, 3>(P, st, fused);               // e.g. seg_len 20 split in halves / seg_len 10 concat
-        case 7: return launch_score_t<7, 1, 2>(P, st, fused);                 // odd frame counts: one output frame per mix unit
-        case 9: return launch_score_t<9, 1, 3>(P, st, fused);                 // (12 waves, like 12 frames)
-        case 11: return launch_score_t<11, 1, 3>(P, st, fused);
-        case 1: return launch_score_t<1, 4, 4>(P, st, fused);                 // (4 chains / WG, 2 WGs per CU)
-        case 2: return launch_score_t<2, 2, 4>(P, st, fused);                 // e.g. seg_len 4 split in halves (2 chains / WG, 2 WGs per CU: every mix is one round of units; +31 % over <2,3,4>, profiles/r04aa_t2_nb_ab.txt)
-        default: return fail(MCD_EUNSUPPORTED, "U-Net frame count " + std::to_string(T) + " not instantiated (supported: 1 .. 12)");
+// Dispatch to the launchers of mcd_inst.hip is generated from the tables of mcd_instances.hpp (this file only CALLS launchers).
+// score_kernel<T, ...>: the production form (or, in a build that holds tuning variants, the workgroup shape MCD_OPT_VARIANT
+// names); layer_test: the form behind mcd_layer_forward
+int launch_score(const mcd_weights* w, int T, ScoreParams& P, hipStream_t st, bool* fused = nullptr, bool layer_test = false) {
+    if (!layer_test) {
+        P.force_split = w->opt[MCD_OPT_SPLIT];
+        P.phase = w->opt[MCD_OPT_PHASE];
+        const int variant = w->opt[MCD_OPT_VARIANT];
+        if (variant != 0 && !score_has_variants()) return fail(MCD_EUNSUPPORTED, "MCD_OPT_VARIANT needs a -DMCD_TUNING_VARIANTS build");
+#define MCD_CASE(unit, V, T_, NB, MINW) if (T == T_ && variant == V) return launch_score_t<T_, NB, MINW>(P, st, fused);
+        MCD_SCORE_VARIANT_INSTANCES(MCD_CASE)
+#undef MCD_CASE
     }
-#endif
+    switch (layer_test ? -T : T) {
+#define MCD_CASE(unit, T_, NB, MINW, LT) case (LT ? -T_ : T_): return launch_score_t<T_, NB, MINW, LT>(P, st, fused);
+        MCD_SCORE_INSTANCES(MCD_CASE)
+#undef MCD_CASE
+        default: break;
+    }
+    if (layer_test) return fail(MCD_EUNSUPPORTED, "mcd_layer_forward: no layer-test kernel for " + std::to_string(T) + " U-Net frames (the LT rows of mcd_instances.hpp)");
+    return fail(MCD_EUNSUPPORTED, "U-Net frame count " + std::to_string(T) + " not instantiated (MCD_SCORE_INSTANCES, mcd_instances.hpp)");
 }
 
-}  // namespace
-
-namespace {
 // T_c -> NB of the MFMA condition encoders (the chains-per-workgroup of the trajectory kernels' LDS plans)
-#ifdef MCD_FAST_T
-#define MCD_COND_CASE(fn, unit, T, NB) case T: if (T == MCD_FAST_T && NB == MCD_FAST_NB) return fn<MCD_FAST_T, MCD_FAST_NB>(w, data, fi, seg_len, emb, B, st); break;
-#else
 #define MCD_COND_CASE(fn, unit, T, NB) case T: return fn<T, NB>(w, data, fi, seg_len, emb, B, st);
-#endif
 int launch_cond_fast(const mcd_weights* w, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, hipStream_t st) {
     switch (w->cond.Tc) {
 #define MCD_CASE(unit, T, NB) MCD_COND_CASE(launch_cond_fast_t, unit, T, NB)
@@ -909,14 +893,6 @@ int launch_cond_fast(const mcd_weights* w, const DataView& data, const FrameIdx&
         default: break;
     }
     return fail(MCD_EUNSUPPORTED, "cond_fast: frame count not instantiated");
-}
-// frame counts the MFMA 'E_unet' encoder is instantiated for (the trajectory kernel's LDS plans)
-bool cond_unet_has_kernel(int Tc) {
-#ifdef MCD_FAST_T
-    return Tc == MCD_FAST_T;
-#else
-    return Tc >= 1 && Tc <= 12;
-#endif
 }
 int launch_cond_unet(const mcd_weights* w, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, hipStream_t st) {
     switch (w->cond.Tc) {
@@ -954,28 +930,16 @@ int launch_score_tiled(const mcd_weights* w, const ScoreParams& P, const FrameMa
     HIP_TRY(hipGetDevice(&dev));
     if (dev != w->device) return fail(MCD_EINVAL, "the current device is not the handle's device (the workspace slabs are sized for it)");
     const int wgs = tiled_wgs(w, P.n_chains, w->tiled_tp);
-#ifdef MCD_FAST_T
-#ifdef MCD_FAST_TILED
-    if (w->tiled_tp == MCD_FAST_TILED) return launch_score_tiled_t<MCD_FAST_TILED, tl_nb(MCD_FAST_TILED)>(w, P, M, scratch, wgs, st);
-#endif
-    (void)wgs; (void)layer_test;
-    return fail(MCD_EUNSUPPORTED, "fast build");
-#else
     switch (layer_test ? -w->tiled_tp : w->tiled_tp) {
 #define MCD_CASE(unit, TP, NB, LT) case (LT ? -TP : TP): return launch_score_tiled_t<TP, NB, LT>(w, P, M, scratch, wgs, st);
         MCD_TILED_INSTANCES(MCD_CASE)
 #undef MCD_CASE
         default: return fail(MCD_EUNSUPPORTED, "tiled kernel: frame count");
     }
-#endif
 }
-// plain condition encoder (any channel list; 21 .. 31 condition frames of the shipped one).  scratch: cond_plain_scratch_bytes()
-// of global memory when three LDS buffers do not fit (W.gmode), else unused
+// plain condition encoder (any channel list; 21 .. 31 condition frames of the shipped one).  scratch: cond_scratch_bytes() of
+// global memory when three LDS buffers do not fit (W.gmode), else unused
 constexpr int CE_MAX_WGS = 512;
-int64_t cond_plain_scratch_bytes(const mcd_weights* w, int64_t B) {
-    if (!w->has_cond || w->cond_unet || !w->cond.gmode) return 0;
-    return (B < CE_MAX_WGS ? B : CE_MAX_WGS) * (int64_t)w->cond.cmax * w->cond.Tc * 17 * 4;
-}
 int launch_cond_plain(const mcd_weights* w, const float* cond_data, int B, float* emb, float* scratch, hipStream_t st) {
     const bool g = w->cond.gmode != 0;
     if (g && !scratch) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes) for this many condition frames");
@@ -986,15 +950,80 @@ int launch_cond_plain(const mcd_weights* w, const float* cond_data, int B, float
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
-// the condition encoders that read the condition frames straight from the window view: the MFMA kernels for the frame
-// counts they are instantiated for, the runtime-shape 'E_unet' kernel otherwise (scratch: gen_scratch_bytes(B, Tc))
-int launch_cond_mfma(const mcd_weights* w, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, float* scratch,
+// Which kernel family serves a handle, decided here and nowhere else: the entry points, the launches and the workspace sizing
+// below all ask these two functions.
+enum UnetRoute { UNET_KERNEL, UNET_TILED, UNET_GENERIC };      // score_kernel<T,...> | score_tiled_kernel | score_generic_kernel
+UnetRoute unet_route(const mcd_weights* w, bool honour_option = true) {
+    if (honour_option && w->opt[MCD_OPT_GENERIC_UNET]) return UNET_GENERIC;
+    return w->fast_unet ? UNET_KERNEL : w->tiled_tp ? UNET_TILED : UNET_GENERIC;
+}
+enum CondRoute {
+    COND_NONE,              // the model has no condition encoder
+    COND_INKERNEL,          // shipped architecture, inside the trajectory kernel
+    COND_FAST,              // ... as its own launch: cond_fast_kernel
+    COND_UNET,              // 'E_unet': cond_unet_kernel
+    COND_TILED,             // 'E_unet' at a frame count of the slab-tiled kernel: its COND form
+    COND_UNET_GENERIC,      // 'E_unet', runtime-shape kernel (any frame count; MCD_OPT_COND_GENERIC)
+    COND_PLAIN,             // cond_encode_kernel: any channel list / frame count, activations in LDS
+    COND_PLAIN_SCRATCH      // ... with its third buffer in global scratch (cond.gmode)
+};
+// whole_windows: the caller runs score_kernel with workgroups that own whole windows (split == 1) and as many condition frames
+// as U-Net frames -- the shipped encoder then runs inside that kernel (otherwise every workgroup of a window would repeat it)
+CondRoute cond_route(const mcd_weights* w, bool whole_windows = false) {
+    if (!w->has_cond) return COND_NONE;
+    const bool generic = w->opt[MCD_OPT_COND_GENERIC] != 0;
+    if (w->cond_unet) {
+        if (generic) return COND_UNET_GENERIC;
+        return cond_unet_has_kernel(w->cond.Tc) ? COND_UNET : w->tiled_cond_tp ? COND_TILED : COND_UNET_GENERIC;
+    }
+    if (w->cond_fast && !generic) return whole_windows ? COND_INKERNEL : COND_FAST;
+    return w->cond.gmode ? COND_PLAIN_SCRATCH : COND_PLAIN;
+}
+// global scratch a route needs for `chains` trajectories / `B` windows: what its launch below is given, and what the sizing
+// entry points reserve
+int64_t unet_scratch_bytes(const mcd_weights* w, UnetRoute r, int64_t chains) {
+    switch (r) {
+        case UNET_TILED: return w->tiled_tp ? tiled_scratch_bytes(w, chains, w->tiled_tp) : 0;
+        case UNET_GENERIC: return gen_scratch_bytes(chains, w->cfg.t_unet);
+        default: return 0;
+    }
+}
+int64_t cond_scratch_bytes(const mcd_weights* w, CondRoute r, int64_t B) {
+    switch (r) {
+        case COND_TILED: return w->cond_unet && w->tiled_cond_tp ? tiled_scratch_bytes(w, B, w->tiled_cond_tp) : 0;
+        case COND_UNET_GENERIC: return w->cond_unet ? gen_scratch_bytes(B, w->cond.Tc) : 0;
+        case COND_PLAIN_SCRATCH:
+            return w->has_cond && !w->cond_unet && w->cond.gmode ? (B < CE_MAX_WGS ? B : CE_MAX_WGS) * (int64_t)w->cond.cmax * w->cond.Tc * 17 * 4 : 0;
+        default: return 0;
+    }
+}
+// The sizing entry points return an UPPER BOUND over the options, not the need of the route that would run now (callers size
+// once and reuse): a handle without a specialised U-Net kernel reserves for both of its routes, an 'E_unet' handle for the
+// slab-tiled and the runtime-shape encoder even while cond_unet_kernel serves it, and the plain encoder's scratch whenever
+// cond.gmode is set.
+int64_t unet_ws_bytes(const mcd_weights* w, int64_t chains) {
+    if (!w->fast_unet) return std::max(unet_scratch_bytes(w, UNET_TILED, chains), unet_scratch_bytes(w, UNET_GENERIC, chains));
+    return unet_scratch_bytes(w, unet_route(w), chains);
+}
+int64_t cond_ws_bytes(const mcd_weights* w, int64_t B) {
+    return std::max({cond_scratch_bytes(w, COND_TILED, B), cond_scratch_bytes(w, COND_UNET_GENERIC, B), cond_scratch_bytes(w, COND_PLAIN_SCRATCH, B)});
+}
+
+int launch_unet(const mcd_weights* w, UnetRoute r, ScoreParams& P, const FrameMaps& M, float* scratch, hipStream_t st, bool* fused = nullptr) {
+    switch (r) {
+        case UNET_KERNEL: return launch_score(w, w->cfg.t_unet, P, st, fused);
+        case UNET_TILED: return launch_score_tiled(w, P, M, scratch, st);
+        default: return launch_score_generic(w, P, M, scratch, st);
+    }
+}
+// the condition encoders that read the condition frames straight from the window view (scratch: cond_scratch_bytes(w, r, B))
+int launch_cond_view(const mcd_weights* w, CondRoute r, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, float* scratch,
                      hipStream_t st) {
-    if (!w->cond_unet) return launch_cond_fast(w, data, fi, seg_len, emb, B, st);
+    if (r == COND_FAST) return launch_cond_fast(w, data, fi, seg_len, emb, B, st);
+    if (r == COND_UNET) return launch_cond_unet(w, data, fi, seg_len, emb, B, st);
     const int Tc = w->cond.Tc;
-    if (cond_unet_has_kernel(Tc) && !w->opt[MCD_OPT_COND_GENERIC]) return launch_cond_unet(w, data, fi, seg_len, emb, B, st);
     if (!scratch) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes) for the runtime-shape condition encoder");
-    if (w->tiled_cond_tp && !w->opt[MCD_OPT_COND_GENERIC]) {      // 13 .. 32 condition frames: the slab-tiled MFMA stages, one window per "chain"
+    if (r == COND_TILED) {      // the slab-tiled MFMA stages, one window per "chain"
         ScoreParams P;
         memset(&P, 0, sizeof(P));
         P.wbuf = w->dbuf; P.dv = data; P.seg_len = seg_len; P.B = B; P.S = 1; P.n_chains = B; P.ns = 2; P.eps_out = emb;
@@ -1003,16 +1032,10 @@ int launch_cond_mfma(const mcd_weights* w, const DataView& data, const FrameIdx&
         for (int t = 0; t < Tc; ++t) M.src_frame[t] = fi.idx[t];
         const int wgs = tiled_wgs(w, B, w->tiled_cond_tp);
         switch (w->tiled_cond_tp) {
-#ifdef MCD_FAST_T
-#ifdef MCD_FAST_TILED_COND
-            case MCD_FAST_TILED_COND: return launch_score_tiled_t<MCD_FAST_TILED_COND, tl_nb(MCD_FAST_TILED_COND), false, true>(w, P, M, scratch, wgs, st);
-#endif
-#else
 #define MCD_CASE(unit, TP, NB) case TP: return launch_score_tiled_t<TP, NB, false, true>(w, P, M, scratch, wgs, st);
             MCD_TILED_COND_INSTANCES(MCD_CASE)
 #undef MCD_CASE
-#endif
-            default: break;      // (developer builds without this instantiation: the runtime-shape kernel below)
+            default: return fail(MCD_EUNSUPPORTED, "tiled condition encoder: frame count");
         }
     }
     const int wgs = B < GEN_MAX_WGS ? B : GEN_MAX_WGS;
@@ -1060,7 +1083,7 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
     if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
     const int T = cfg->t_unet;
     if (T < 1 || T > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "U-Net frame count must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    const bool fast_unet = T >= 1 && T <= 12;     // the instantiated score_kernel<T,...>
+    const bool fast_unet = score_has_kernel(T);     // the instantiated score_kernel<T,...>
     GenNet G;
     memset(&G, 0, sizeof(G));
     GenCond GC;
@@ -1151,11 +1174,11 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
         for (int vo = 0; vo < vout; ++vo) B.buf[G.rs_b[r] + vo] = (float)f.b[vo];
     }
     G.we = U.we; G.be = U.be;
-    // tables of score_tiled_kernel (12 < T <= 32): mix coefficients for the padded frame count, non-capture resampler packs;
+    // tables of score_tiled_kernel (frame counts without a score_kernel, up to its largest padded one): mix coefficients for the padded frame count, non-capture resampler packs;
     // GEMM fragments, biases, slopes and the embedding Linear are the specialised kernels' own
     TiledNet TN;
     memset(&TN, 0, sizeof(TN));
-    const int tiled_tp = (T > 12 && T <= 32) ? (T <= 16 ? 16 : T <= 24 ? 24 : 32) : 0;
+    const int tiled_tp = fast_unet ? 0 : tiled_tp_for(T);
     if (tiled_tp) {
         for (int l = 0; l < NLAYERS; ++l) {
             const LDesc D = layer_desc(l);
@@ -1262,8 +1285,8 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
         utab[TABC_ULW] = B.alloc(F * EDIM); memcpy(&B.buf[utab[TABC_ULW]], lw, sizeof(float) * F * EDIM);
         utab[TABC_ULB] = B.alloc(EDIM); memcpy(&B.buf[utab[TABC_ULB]], lb, sizeof(float) * EDIM);
         GC.lw = utab[TABC_ULW]; GC.lb = utab[TABC_ULB];
-        if (Tc > 12) {      // the slab-tiled MFMA stages: mix tables for the padded frame count; GEMM fragments, biases, slopes as above
-            tiled_cond_tp = Tc <= 16 ? 16 : Tc <= 24 ? 24 : 32;
+        tiled_cond_tp = cond_unet_has_kernel(Tc) ? 0 : tiled_cond_tp_for(Tc);
+        if (tiled_cond_tp) {      // the slab-tiled MFMA stages: mix tables for the padded frame count; GEMM fragments, biases, slopes as above
             for (int l = 0; l < 7; ++l) {
                 const std::string p = std::string("condition_encoder.") + unames[l];
                 if (!pack_mix_mfma(tm, p, Tc, uv[l], B, TNc.tq[l], TNc.am[l], tiled_cond_tp)) return fail(MCD_EMISSING, tm.missing);
@@ -1322,10 +1345,7 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
         Cw.lb = B.alloc(EDIM); memcpy(&B.buf[Cw.lb], lb, sizeof(float) * EDIM);
         // fast path (cond_fast_kernel): the shipped architecture at a frame count the MFMA stages are instantiated for
         cond_fast = Cw.n_layers == 4 && Cw.cout[0] == 32 && Cw.cout[1] == 16 && Cw.cout[2] == 32 && Cw.cout[3] == 32 &&
-                    Cw.Tc >= 1 && Cw.Tc <= MCD_COND_FAST_MAX_T;
-#ifdef MCD_FAST_T
-        cond_fast = cond_fast && Cw.Tc == MCD_FAST_T;     // (developer builds hold one frame count; the rest takes the plain encoder)
-#endif
+                    cond_fast_has_kernel(Cw.Tc);
         if (cond_fast) {
             int cinr = C0;
             for (int l = 0; l < 4; ++l) {
@@ -1414,27 +1434,23 @@ int mcd_cond_encode(const mcd_weights_t* w, const float* cond_data, int32_t n_wi
     if (!w->has_cond) return fail(MCD_EINVAL, "model has no condition encoder");
     if (n_windows <= 0) return MCD_OK;
     if (!cond_data || !emb_out) return fail(MCD_EINVAL, "null argument");
-    if (w->cond_unet || (w->cond_fast && !w->opt[MCD_OPT_COND_GENERIC])) {
-        FrameIdx fi;
-        for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = k;
-        DataView dv;
-        memset(&dv, 0, sizeof(dv));
-        dv.data = cond_data;
-        if (w->cond_unet && !cond_unet_has_kernel(w->cond.Tc))
-            return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: the 'E_unet' encoder at this frame count needs scratch memory; use mcd_score");
-        return launch_cond_mfma(w, dv, fi, w->cond.Tc, emb_out, n_windows, nullptr, (hipStream_t)stream);
-    }
-    if (w->cond.gmode) return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: this many condition frames need scratch memory; use mcd_score");
-    return launch_cond_plain(w, cond_data, n_windows, emb_out, nullptr, (hipStream_t)stream);
+    const CondRoute route = cond_route(w);
+    if (w->cond_unet && !cond_unet_has_kernel(w->cond.Tc))
+        return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: the 'E_unet' encoder at this frame count needs scratch memory; use mcd_score");
+    if (route == COND_PLAIN_SCRATCH) return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: this many condition frames need scratch memory; use mcd_score");
+    if (route == COND_PLAIN) return launch_cond_plain(w, cond_data, n_windows, emb_out, nullptr, (hipStream_t)stream);
+    FrameIdx fi;
+    for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = k;
+    DataView dv;
+    memset(&dv, 0, sizeof(dv));
+    dv.data = cond_data;
+    return launch_cond_view(w, route, dv, fi, w->cond.Tc, emb_out, n_windows, nullptr, (hipStream_t)stream);
 }
 
 // scratch of the single-pass entries: the slabs of the slab-tiled kernel (13 .. 32 U-Net frames) or of the runtime-shape kernel
 int64_t mcd_pass_workspace_bytes(const mcd_weights_t* w, int32_t n_windows) {
     if (!w || n_windows <= 0) return 0;
-    int64_t b = 0;
-    if (!w->fast_unet || w->opt[MCD_OPT_GENERIC_UNET]) b = gen_scratch_bytes(n_windows, w->cfg.t_unet);
-    if (!w->fast_unet && w->tiled_tp) { const int64_t t = tiled_scratch_bytes(w, n_windows, w->tiled_tp); if (t > b) b = t; }
-    return b;
+    return unet_ws_bytes(w, n_windows);
 }
 
 int mcd_unet_forward(const mcd_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
@@ -1449,13 +1465,11 @@ int mcd_unet_forward(const mcd_weights_t* w, const float* x, const float* cond, 
     P.B = n_windows; P.S = 1; P.ns = t + 1; P.seg_len = w->cfg.t_unet; P.n_corrupt = w->cfg.t_unet; P.fixed_mask = 0;
     P.mode = 1; P.step_single = t; P.n_chains = n_windows;
     hipStream_t st = (hipStream_t)stream;
-    if (w->fast_unet && !w->opt[MCD_OPT_GENERIC_UNET]) return launch_score(w, w->cfg.t_unet, P, st);
-    // 13 .. 32 frames: the slab-tiled kernel in single-pass mode; MCD_OPT_GENERIC_UNET: the runtime-shape kernel
-    if (!workspace) return fail(MCD_EINVAL, "workspace required (mcd_pass_workspace_bytes)");
+    const UnetRoute route = unet_route(w);      // (the slab-tiled and the runtime-shape kernel in single-pass mode)
+    if (route != UNET_KERNEL && !workspace) return fail(MCD_EINVAL, "workspace required (mcd_pass_workspace_bytes)");
     FrameMaps M;
     memset(&M, 0, sizeof(M));
-    if (w->tiled_tp && !w->opt[MCD_OPT_GENERIC_UNET]) return launch_score_tiled(w, P, M, reinterpret_cast<float*>(workspace), st);
-    return launch_score_generic(w, P, M, reinterpret_cast<float*>(workspace), st);
+    return launch_unet(w, route, P, M, reinterpret_cast<float*>(workspace), st);
 }
 
 int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, const float* skip, const float* emb, int32_t n_windows,
@@ -1471,11 +1485,9 @@ int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, con
     P.mode = 1; P.step_single = 0; P.n_chains = n_windows;
     P.lt_stage = stage; P.lt_in = x; P.lt_out = out; P.lt_skip = skip;
     P.x_in = stage == 0 ? x : nullptr;     // layer 0 reads the chain state itself; the other stages start from x = 0
-#ifdef MCD_FAST_T
-    return fail(MCD_EUNSUPPORTED, "fast build");
-#else
     hipStream_t st = (hipStream_t)stream;
-    if (w->tiled_tp) {      // 13 .. 32 frames: the joint resamplers are fused into layers 3, 5, 7, 9 (no stages of their own)
+    // the stage code of the MFMA kernels, whatever MCD_OPT_GENERIC_UNET says
+    if (unet_route(w, false) == UNET_TILED) {      // 13 .. 32 frames: the joint resamplers are fused into layers 3, 5, 7, 9 (no stages of their own)
         if (stage > 10) return fail(MCD_EUNSUPPORTED, "13 .. 32 U-Net frames: the joint resamplers are part of stages 3, 5, 7, 9");
         if (skip && stage != 7 && stage != 9) return fail(MCD_EINVAL, "skip tensor: stages 7 (d2) and 9 (d1) only");
         if (!workspace) return fail(MCD_EINVAL, "workspace required (mcd_pass_workspace_bytes)");
@@ -1484,18 +1496,7 @@ int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, con
         return launch_score_tiled(w, P, M, reinterpret_cast<float*>(workspace), st, true);
     }
     if (skip) return fail(MCD_EINVAL, "skip tensor: only the fused stages of 13 .. 32 U-Net frames take one");
-    switch (w->cfg.t_unet) {
-        case 3: return launch_score_t<3, 2, 4, true>(P, st, nullptr);
-        case 6: return launch_score_t<6, 1, 4, true>(P, st, nullptr);
-        case 12: return launch_score_t<12, 1, 3, true>(P, st, nullptr);      // (the template arguments and unit flags of the production kernels)
-        case 5: return launch_score_t<5, 1, 4, true>(P, st, nullptr);
-        case 7: return launch_score_t<7, 1, 2, true>(P, st, nullptr);
-        case 9: return launch_score_t<9, 1, 3, true>(P, st, nullptr);
-        case 10: return launch_score_t<10, 1, 3, true>(P, st, nullptr);
-        case 11: return launch_score_t<11, 1, 3, true>(P, st, nullptr);
-        default: return fail(MCD_EUNSUPPORTED, "mcd_layer_forward is instantiated for 3, 5, 6, 7, 9, 10, 11, 12 and 13 .. 32 U-Net frames");
-    }
-#endif
+    return launch_score(w, w->cfg.t_unet, P, st, nullptr, true);      // (the layer-test forms: the template arguments and unit flags of the production kernels)
 }
 
 __global__ void philox_noise_kernel(unsigned long long seed, long long first_window, int B, int S, int K, int Tx, float* __restrict__ out) {
@@ -1544,7 +1545,7 @@ static int64_t ws_cond_bytes(const mcd_weights* w, int64_t B) {
 int32_t mcd_plan_split(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
     if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
     if (cfg->n_windows <= 0) return 1;
-    if (!w->fast_unet || w->opt[MCD_OPT_GENERIC_UNET]) return 0;
+    if (unet_route(w) != UNET_KERNEL) return 0;
     ScoreParams P;
     memset(&P, 0, sizeof(P));
     P.B = cfg->n_windows; P.S = cfg->n_samples; P.ns = cfg->noise_steps; P.mode = 0; P.plan_only = 1;
@@ -1554,17 +1555,9 @@ int32_t mcd_plan_split(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
 
 int64_t mcd_score_workspace_bytes(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
     if (!w || !cfg) return 0;
-    // condition embeddings (B,16) + gathered condition frames (B,C,Tc,V); then the scratch slabs of the runtime-shape kernels
-    // (frame counts without a specialised instantiation, or MCD_OPT_GENERIC_UNET / MCD_OPT_COND_GENERIC)
-    int64_t gen = 0;
-    if (!w->fast_unet || w->opt[MCD_OPT_GENERIC_UNET]) gen = gen_scratch_bytes((int64_t)cfg->n_windows * cfg->n_samples, w->cfg.t_unet);
-    if (!w->fast_unet && w->tiled_tp) {
-        const int64_t g3 = tiled_scratch_bytes(w, (int64_t)cfg->n_windows * cfg->n_samples, w->tiled_tp);
-        if (g3 > gen) gen = g3;
-    }
-    if (w->cond_unet) { const int64_t g2 = gen_scratch_bytes(cfg->n_windows, w->cond.Tc); if (g2 > gen) gen = g2; }
-    if (w->cond_unet && w->tiled_cond_tp) { const int64_t g5 = tiled_scratch_bytes(w, cfg->n_windows, w->tiled_cond_tp); if (g5 > gen) gen = g5; }
-    { const int64_t g4 = cond_plain_scratch_bytes(w, cfg->n_windows); if (g4 > gen) gen = g4; }
+    // condition embeddings (B,16) + gathered condition frames (B,C,Tc,V); then the scratch slabs of the slab-tiled and the
+    // runtime-shape kernels (one region: the condition encoder has finished with it when the trajectories start)
+    const int64_t gen = std::max(unet_ws_bytes(w, (int64_t)cfg->n_windows * cfg->n_samples), cond_ws_bytes(w, cfg->n_windows));
     return ws_cond_bytes(w, cfg->n_windows) + ws_loss_bytes(cfg->n_windows, cfg->n_samples) + gen;
 }
 
@@ -1613,7 +1606,7 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     if (rnd && !(view && view->cond_mask)) return fail(MCD_EINVAL, "random_imp needs mcd_window_view_t.cond_mask");
     const int tf = keeps_cond ? cfg->n_cond : 0;
     if (tf + cfg->n_corrupt != Tu) return fail(MCD_EINVAL, "frame split does not match the packed U-Net (t_unet)");
-    const bool generic = !w->fast_unet || w->opt[MCD_OPT_GENERIC_UNET] != 0;      // runtime-shape kernel
+    const UnetRoute route = unet_route(w);
     if (strat == MCD_STRATEGY_INJECT && cfg->n_cond != w->cfg.t_cond) return fail(MCD_EINVAL, "n_cond does not match the packed condition encoder");
     hipStream_t st = (hipStream_t)stream;
     ScoreParams P;
@@ -1669,7 +1662,7 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     float* ws_loss = wsb ? reinterpret_cast<float*>(wsb + ws_cond_bytes(w, B)) : nullptr;
     float* gen_scratch = wsb ? reinterpret_cast<float*>(wsb + ws_cond_bytes(w, B) + ws_loss_bytes(B, S)) : nullptr;
     P.loss_out = loss_all ? loss_all : ws_loss;       // (skipped by a fused launch when the caller did not ask for it)
-    if (!generic) {           // how the call is cut into workgroups (decides where the condition encoder runs)
+    if (route == UNET_KERNEL) {           // how the call is cut into workgroups (decides where the condition encoder runs)
         P.plan_only = 1;
         const int rc = launch_score(w, Tu, P, st);
         if (rc != MCD_OK) return rc;
@@ -1677,16 +1670,10 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     }
     auto score = [&]() -> int {
         bool fused = false;
-        int rc;
-        if (!generic) {
-            P.loss_out_optional = loss_all == nullptr;
-            rc = launch_score(w, Tu, P, st, &fused);
-        } else {
-            if (!workspace) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes) for the runtime-shape kernel");
-            // 12 < T <= 32: the MFMA kernel over an L2-resident slab; everything else (and MCD_OPT_GENERIC_UNET): plain FMAs
-            if (w->tiled_tp && !w->opt[MCD_OPT_GENERIC_UNET]) rc = launch_score_tiled(w, P, M, gen_scratch, st);
-            else rc = launch_score_generic(w, P, M, gen_scratch, st);
-        }
+        if (route == UNET_KERNEL) P.loss_out_optional = loss_all == nullptr;
+        else if (!workspace) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes) for the runtime-shape kernel");
+        // UNET_TILED: the MFMA kernel over an L2-resident slab; UNET_GENERIC: plain FMAs
+        const int rc = launch_unet(w, route, P, M, gen_scratch, st, &fused);
         if (rc != MCD_OK || aggr == 0 || fused) return rc;
         AggrParams A;        // the workgroups did not see all samples of their windows: aggregate the (B,S) losses afterwards
         memset(&A, 0, sizeof(A));
@@ -1694,33 +1681,27 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
         A.seg_len = cfg->seg_len; A.strategy = aggr; A.loss_fn = cfg->loss_fn; A.q = quantile;
         return launch_aggregate(A, st);
     };
-    if (strat == MCD_STRATEGY_INJECT) {
-        // the shipped encoder with as many condition frames as the U-Net has frames runs inside the trajectory kernel when
-        // its workgroups own whole windows (otherwise every workgroup of a window would repeat it: its own launch then)
-        if (!generic && P.split == 1 && w->cond_fast && !w->opt[MCD_OPT_COND_GENERIC] && cfg->n_cond == Tu && Tu <= 12) {
-            P.cond_inkernel = 1;
-            for (int k = 0; k < Tu; ++k) P.cond_idx[k] = cfg->cond_idx[k];
-            return score();
-        }
+    // (strategy inject <=> the handle has a condition encoder)
+    const CondRoute croute = cond_route(w, route == UNET_KERNEL && P.split == 1 && cfg->n_cond == Tu);
+    if (croute == COND_INKERNEL) {
+        P.cond_inkernel = 1;
+        for (int k = 0; k < Tu; ++k) P.cond_idx[k] = cfg->cond_idx[k];
+    } else if (croute != COND_NONE) {
         if (!workspace) return fail(MCD_EINVAL, "workspace required for this condition encoder");
         float* emb = reinterpret_cast<float*>(workspace);
-        float* cbuf = emb + (size_t)B * EDIM + 16;
-        const int Tc = cfg->n_cond;
-        if (w->cond_unet || (w->cond_fast && !w->opt[MCD_OPT_COND_GENERIC])) {
-            FrameIdx fi;
-            for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = cfg->cond_idx[k];
-            int rc = launch_cond_mfma(w, P.dv, fi, cfg->seg_len, emb, B, gen_scratch, st);
-            if (rc != MCD_OK) return rc;
-            P.cond_emb = emb;
-            return score();
-        }
-        const int total = B * C0 * Tc * 17;
         FrameIdx fi;
         for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = cfg->cond_idx[k];
-        hipLaunchKernelGGL(gather_frames_kernel, dim3((total + 255) / 256), dim3(256), 0, st, P.dv, cbuf, B, C0, cfg->seg_len,
-                           17, Tc, fi);
-        HIP_TRY(hipGetLastError());
-        int rc = launch_cond_plain(w, cbuf, B, emb, gen_scratch, st);
+        int rc;
+        if (croute == COND_PLAIN || croute == COND_PLAIN_SCRATCH) {      // this encoder reads gathered frames
+            float* cbuf = emb + (size_t)B * EDIM + 16;
+            const int Tc = cfg->n_cond, total = B * C0 * Tc * 17;
+            hipLaunchKernelGGL(gather_frames_kernel, dim3((total + 255) / 256), dim3(256), 0, st, P.dv, cbuf, B, C0, cfg->seg_len,
+                               17, Tc, fi);
+            HIP_TRY(hipGetLastError());
+            rc = launch_cond_plain(w, cbuf, B, emb, gen_scratch, st);
+        } else {
+            rc = launch_cond_view(w, croute, P.dv, fi, cfg->seg_len, emb, B, gen_scratch, st);
+        }
         if (rc != MCD_OK) return rc;
         P.cond_emb = emb;
     }

@@ -1,14 +1,20 @@
 // mcd_instances.hpp — every kernel instantiation of libmocodad_hip.so and the translation unit that holds it.
 //
 // The library is built from mcd_api.hip (C ABI, packers, dispatch, the runtime-shape kernels) plus mcd_inst.hip compiled once
-// per unit with -DMCD_INST_UNIT=<n>: a unit explicitly instantiates the launcher templates of its rows (and with them the
+// per unit with -DMCD_INST_UNIT_<n>: a unit explicitly instantiates the launcher templates of its rows (and with them the
 // kernels); every other translation unit sees them as `extern template` and compiles none of that device code.  The units
 // build in parallel (mocodad_amd/build.py); their number and the assignment below only balance compile times.
+// These tables are the ONLY list: the instantiations (mcd_inst.hip), the `extern template` declarations (mcd_launch.hpp), the
+// dispatch switches (mcd_api.hip) and the "is there a kernel for this frame count" predicates at the end of this file all
+// expand them.  A new frame count or workgroup shape is a row here (and, for a new unit, MCD_INST_UNITS); nothing else.
 //   X(unit, T_u, NB, MINW, LT)   score_kernel<T_u, NB, MINW, LT>      (LT: the layer-test form behind mcd_layer_forward)
+//   X(unit, variant, T_u, NB, MINW)  ... an alternative workgroup shape of T_u frames, taken when MCD_OPT_VARIANT == variant
 //   X(unit, T_c, NB)             cond_fast_kernel / cond_unet_kernel<T_c, NB>
 //   X(unit, TP, NB, LT)          score_tiled_kernel<TP, NB, LT>
 //   X(unit, TP, NB)              score_tiled_kernel<TP, NB, false, true>: the 'E_unet' condition encoder at 13 .. 32 condition frames
 #pragma once
+
+#ifndef MCD_FAST_T      // the shipped library
 
 #define MCD_INST_UNITS 25
 
@@ -28,24 +34,29 @@
 #define MCD_UNIT_FLAGS_15 "-DMCD_NWAVES=12"     // LT of the slab-tiled kernel at 24 frames (= unit 11)
 #define MCD_UNIT_FLAGS_16 "-DMCD_NWAVES=12"     // ... and at 32 frames (= unit 12)
 
-#ifdef MCD_TUNING_VARIANTS      // alternative workgroup shapes (MCD_OPT_VARIANT): developer builds only
-#define MCD_SCORE_VARIANT_INSTANCES(X) X(1, 3, 4, 2, false) X(1, 3, 1, 4, false) X(1, 3, 2, 2, false) X(2, 6, 2, 2, false)
+#ifdef MCD_TUNING_VARIANTS      // alternative workgroup shapes (MCD_OPT_VARIANT, bench.py --variant): developer builds only
+#define MCD_SCORE_VARIANT_INSTANCES(X) \
+    X(1, 1, 3, 4, 2)      /* 4 chains / WG, 1 WG per CU */ \
+    X(1, 3, 3, 1, 4)      /* 1 chain / WG */ \
+    X(1, 2, 3, 2, 2)      /* the default shape without the register cap */ \
+    X(2, 1, 6, 2, 2)      /* 2 chains / WG, 1 WG per CU (no register cap) */
 #else
 #define MCD_SCORE_VARIANT_INSTANCES(X)
 #endif
 
 #define MCD_SCORE_INSTANCES(X) \
     X(1, 3, 2, 4, false)  /* HR-Avenue / HR-STC: 2 chains per workgroup, 2 workgroups per CU (<= 128 VGPRs) */ \
-    X(1, 1, 4, 4, false) X(1, 2, 2, 4, false) \
-    X(2, 6, 1, 4, false)  /* concat over 6 frames */ \
-    X(2, 4, 1, 4, false) \
+    X(1, 1, 4, 4, false)  /* (4 chains / WG, 2 WGs per CU) */ \
+    X(1, 2, 2, 4, false)  /* e.g. seg_len 4 split in halves (2 chains / WG, 2 WGs per CU: every mix is one round of units; +31 % over <2,3,4>, profiles/r04aa_t2_nb_ab.txt) */ \
+    X(2, 6, 1, 4, false)  /* concat over 6 frames: 1 chain / WG, 2 WGs per CU */ \
+    X(2, 4, 1, 4, false)  /* e.g. seg_len 8 split in halves */ \
     X(3, 12, 1, 3, false) /* seg_len 24 split in halves: 1 workgroup of TWELVE waves per CU (unit 3 is compiled with MCD_UNIT_FLAGS_3), 168 registers */ \
-    X(22, 8, 1, 2, false) \
-    X(4, 5, 1, 4, false) X(4, 7, 1, 2, false) \
+    X(22, 8, 1, 2, false) /* e.g. seg_len 8 concat / seg_len 12 with 4 condition frames */ \
+    X(4, 5, 1, 4, false)  /* e.g. seg_len 10 split in halves (1 chain / WG, 2 WGs per CU: +4.7 % over <5,2,2>, profiles/r04r_t5_shape_ab.txt) */ \
+    X(4, 7, 1, 2, false)  /* odd frame counts: one output frame per mix unit */ \
     X(23, 9, 1, 3, false) X(5, 10, 1, 3, false) X(5, 11, 1, 3, false) /* twelve waves as well (unit 5): +3.7 / +0.9 / +0.9 %; 7 and 8 frames measured -1 % / +0.2 %: eight waves */ \
-    X(9, 3, 2, 4, true) X(9, 6, 1, 4, true) X(25, 12, 1, 3, true) X(24, 9, 1, 3, true) \
-    X(13, 5, 1, 4, true) X(13, 7, 1, 2, true) X(25, 10, 1, 3, true) X(25, 11, 1, 3, true) \
-    MCD_SCORE_VARIANT_INSTANCES(X)
+    X(9, 3, 2, 4, true) X(9, 6, 1, 4, true) X(25, 12, 1, 3, true) X(24, 9, 1, 3, true)     /* the layer-test forms: the template arguments of their production twins */ \
+    X(13, 5, 1, 4, true) X(13, 7, 1, 2, true) X(25, 10, 1, 3, true) X(25, 11, 1, 3, true)
 
 #define MCD_COND_FAST_INSTANCES(X) \
     X(7, 1, 4) X(7, 2, 3) X(7, 3, 2) X(7, 4, 2) X(7, 5, 2) X(7, 6, 2) X(7, 7, 1) X(7, 8, 1) X(7, 9, 1) X(7, 10, 1) X(7, 11, 1) X(7, 12, 1) \
@@ -57,3 +68,53 @@
 #define MCD_TILED_INSTANCES(X) X(6, 16, 1, false) X(11, 24, 1, false) X(12, 32, 1, false) X(14, 16, 1, true) X(15, 24, 1, true) X(16, 32, 1, true)
 
 #define MCD_TILED_COND_INSTANCES(X) X(17, 16, 1) X(18, 24, 1) X(19, 32, 1)
+
+#else
+// Developer builds (python -m mocodad_amd.build --fast-t T [-D MCD_FAST_NB= -D MCD_FAST_MINW= -D MCD_FAST_TILED=16|24|32
+// -D MCD_FAST_TILED_COND=16|24|32]): the same tables with only the requested rows, all in unit 1, and one flag set for every
+// file.  Everything generated from the tables follows: such a library answers a frame count it does not hold the way the
+// shipped one answers a frame count IT does not hold.
+#define MCD_INST_UNITS 1
+#ifndef MCD_FAST_NB
+#define MCD_FAST_NB (MCD_FAST_T == 3 ? 2 : 1)
+#endif
+#ifndef MCD_FAST_MINW
+#define MCD_FAST_MINW (MCD_NWAVES == 12 ? 3 : MCD_FAST_T >= 7 ? 2 : 4)
+#endif
+#define MCD_SCORE_INSTANCES(X) X(1, MCD_FAST_T, MCD_FAST_NB, MCD_FAST_MINW, false)
+#define MCD_SCORE_VARIANT_INSTANCES(X)
+#define MCD_COND_FAST_INSTANCES(X) X(1, MCD_FAST_T, MCD_FAST_NB)
+#define MCD_COND_UNET_INSTANCES(X) X(1, MCD_FAST_T, MCD_FAST_NB)
+#ifdef MCD_FAST_TILED
+#define MCD_TILED_INSTANCES(X) X(1, MCD_FAST_TILED, 1, false)
+#else
+#define MCD_TILED_INSTANCES(X)
+#endif
+#ifdef MCD_FAST_TILED_COND
+#define MCD_TILED_COND_INSTANCES(X) X(1, MCD_FAST_TILED_COND, 1)
+#else
+#define MCD_TILED_COND_INSTANCES(X)
+#endif
+#endif  // MCD_FAST_T
+
+// What the tables hold, for the packer and the dispatch of mcd_api.hip (a frame count outside them takes the next more general
+// kernel: slab-tiled, then runtime-shape).
+namespace mcd {
+#define MCD_ROW_IS_T(unit, T, ...) || t == (T)
+#define MCD_ROW_IS_T_LT(unit, T, NB, MINW, LT) || (t == (T) && lt == (LT))
+#define MCD_ROW_TP(unit, TP, NB, LT) if (!(LT) && (TP) >= t && (tp == 0 || (TP) < tp)) tp = (TP);
+#define MCD_ROW_TP_COND(unit, TP, NB) if ((TP) >= t && (tp == 0 || (TP) < tp)) tp = (TP);
+constexpr bool score_has_kernel(int t, bool lt = false) { return false MCD_SCORE_INSTANCES(MCD_ROW_IS_T_LT); }   // score_kernel<t, ..., lt>
+constexpr bool cond_fast_has_kernel(int t) { return false MCD_COND_FAST_INSTANCES(MCD_ROW_IS_T); }
+constexpr bool cond_unet_has_kernel(int t) { return false MCD_COND_UNET_INSTANCES(MCD_ROW_IS_T); }
+// padded frame count of the slab-tiled kernel (and of its COND form) that holds t frames: the smallest one instantiated; 0 = none
+constexpr int tiled_tp_for(int t) { int tp = 0; MCD_TILED_INSTANCES(MCD_ROW_TP) return tp; }
+constexpr int tiled_cond_tp_for(int t) { int tp = 0; MCD_TILED_COND_INSTANCES(MCD_ROW_TP_COND) return tp; }
+#define MCD_ROW_COUNT(...) +1
+constexpr bool score_has_variants() { return (0 MCD_SCORE_VARIANT_INSTANCES(MCD_ROW_COUNT)) > 0; }
+#undef MCD_ROW_IS_T
+#undef MCD_ROW_IS_T_LT
+#undef MCD_ROW_TP
+#undef MCD_ROW_TP_COND
+#undef MCD_ROW_COUNT
+}  // namespace mcd

@@ -1,5 +1,5 @@
 // mcd_launch.hpp — host side shared by the translation units of libmocodad_hip.so: the weights handle, error plumbing and the
-// launcher templates whose explicit instantiations (mcd_inst_*.hip) hold the kernels.
+// launcher templates whose explicit instantiations (mcd_inst.hip, one unit of mcd_instances.hpp per compilation) hold the kernels.
 #pragma once
 #include "mcd_device.hpp"
 #include "mcd_score_kernel.hpp"
@@ -34,9 +34,9 @@ struct mcd_weights {
     bool has_cond;
     bool cond_fast;   // shipped condition-encoder architecture -> cond_fast_kernel
     bool cond_unet;   // 'E_unet' condition encoder -> cond_unet_kernel
-    bool fast_unet;   // a specialised score_kernel<T,...> exists for cfg.t_unet (1 .. 12); otherwise the slab-tiled (13 .. 32) or the runtime-shape kernel
-    mcd::TiledNet tiled;   // tables of score_tiled_kernel (12 < t_unet <= 32), frame count padded to tiled_tp
-    int tiled_tp;     // 16, 24 or 32; 0 = none
+    bool fast_unet;   // a specialised score_kernel<T,...> exists for cfg.t_unet (score_has_kernel); otherwise the slab-tiled or the runtime-shape kernel
+    mcd::TiledNet tiled;   // tables of score_tiled_kernel (t_unet without a score_kernel), frame count padded to tiled_tp
+    int tiled_tp;     // tiled_tp_for(t_unet): 16, 24 or 32; 0 = none
     mcd::TiledNet tiled_cond;   // ... of its COND form: the 'E_unet' condition encoder at 13 .. 32 condition frames
     int tiled_cond_tp;
     mcd::GenNet gen;       // plain (unpacked) folded weights of the U-Net for score_generic_kernel
@@ -144,8 +144,7 @@ int launch_score_t(ScoreParams& P, hipStream_t st, bool* fused) {
 }
 
 
-// largest frame count of the MFMA encoder of the shipped architecture: its four 17-joint layers need 112 floats of LDS per column
-constexpr int MCD_COND_FAST_MAX_T = 20;
+// MFMA encoder of the shipped architecture: its four 17-joint layers need 112 floats of LDS per column (20 frames: 158 KB)
 template <int T, int NB>
 int launch_cond_fast_t(const mcd_weights* w, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, hipStream_t st) {
     constexpr int P17 = ceil16(NB * T * 17);
@@ -196,42 +195,24 @@ int launch_score_tiled_t(const mcd_weights* w, const ScoreParams& P, const Frame
 }
 
 
-// developer builds (-DMCD_FAST_T=3|6|12 [-DMCD_FAST_NB= -DMCD_FAST_MINW= -DMCD_FAST_TILED=16|24|32 -DMCD_FAST_TILED_COND=16|24|32]): one trajectory kernel only
-#ifdef MCD_FAST_T
-#ifndef MCD_FAST_NB
-#define MCD_FAST_NB (MCD_FAST_T == 3 ? 2 : 1)
-#endif
-#ifndef MCD_FAST_MINW
-#define MCD_FAST_MINW (MCD_NWAVES == 12 ? 3 : MCD_FAST_T >= 7 ? 2 : 4)
-#endif
-#endif
-
-// Every instantiation lives in exactly one unit of mcd_inst.hip; everywhere else it is only declared.
-#ifdef MCD_FAST_T
-extern template int launch_score_t<MCD_FAST_T, MCD_FAST_NB, MCD_FAST_MINW, false>(ScoreParams&, hipStream_t, bool*);
-extern template int launch_cond_fast_t<MCD_FAST_T, MCD_FAST_NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
-extern template int launch_cond_unet_t<MCD_FAST_T, MCD_FAST_NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
-#ifdef MCD_FAST_TILED
-extern template int launch_score_tiled_t<MCD_FAST_TILED, tl_nb(MCD_FAST_TILED), false>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
-#endif
-#ifdef MCD_FAST_TILED_COND
-extern template int launch_score_tiled_t<MCD_FAST_TILED_COND, tl_nb(MCD_FAST_TILED_COND), false, true>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
-#endif
-#else
-#define MCD_DECL_SCORE(unit, T, NB, MINW, LT) extern template int launch_score_t<T, NB, MINW, LT>(ScoreParams&, hipStream_t, bool*);
+// Every instantiation lives in exactly one unit of mcd_inst.hip; everywhere else it is only declared.  (A row whose unit no
+// compilation selects would be declared here and defined nowhere: refused.)
+#define MCD_UNIT_OK(unit) static_assert((unit) >= 1 && (unit) <= MCD_INST_UNITS, "mcd_instances.hpp: a row names a unit above MCD_INST_UNITS");
+#define MCD_DECL_SCORE(unit, T, NB, MINW, LT) MCD_UNIT_OK(unit) extern template int launch_score_t<T, NB, MINW, LT>(ScoreParams&, hipStream_t, bool*);
+#define MCD_DECL_VARIANT(unit, variant, T, NB, MINW) MCD_DECL_SCORE(unit, T, NB, MINW, false)
 #define MCD_DECL_COND_FAST(unit, T, NB) \
-    extern template int launch_cond_fast_t<T, NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
+    MCD_UNIT_OK(unit) extern template int launch_cond_fast_t<T, NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
 #define MCD_DECL_COND_UNET(unit, T, NB) \
-    extern template int launch_cond_unet_t<T, NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
+    MCD_UNIT_OK(unit) extern template int launch_cond_unet_t<T, NB>(const mcd_weights*, const DataView&, const FrameIdx&, int, float*, int, hipStream_t);
 #define MCD_DECL_TILED(unit, TP, NB, LT) \
-    extern template int launch_score_tiled_t<TP, NB, LT>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
+    MCD_UNIT_OK(unit) extern template int launch_score_tiled_t<TP, NB, LT>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
+#define MCD_DECL_TILED_COND(unit, TP, NB) \
+    MCD_UNIT_OK(unit) extern template int launch_score_tiled_t<TP, NB, false, true>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
 MCD_SCORE_INSTANCES(MCD_DECL_SCORE)
+MCD_SCORE_VARIANT_INSTANCES(MCD_DECL_VARIANT)
 MCD_COND_FAST_INSTANCES(MCD_DECL_COND_FAST)
 MCD_COND_UNET_INSTANCES(MCD_DECL_COND_UNET)
 MCD_TILED_INSTANCES(MCD_DECL_TILED)
-#define MCD_DECL_TILED_COND(unit, TP, NB) \
-    extern template int launch_score_tiled_t<TP, NB, false, true>(const mcd_weights*, const ScoreParams&, const FrameMaps&, float*, int, hipStream_t);
 MCD_TILED_COND_INSTANCES(MCD_DECL_TILED_COND)
-#endif
 
 }  // namespace mcd

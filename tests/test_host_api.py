@@ -210,7 +210,7 @@ def test_build_is_reproducible_across_output_paths(tmp_path):
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     if probe.returncode != 0:
         pytest.skip("this hipcc cannot target gfx950")
-    flags = B.BASE_FLAGS + ["-DMCD_INST_UNIT=22"]
+    flags = B.BASE_FLAGS + ["-DMCD_INST_UNIT_22"]
     src = os.path.join(B.CSRC, "mcd_inst.hip")
     outs = [str(tmp_path / "a" / "unit.o"), str(tmp_path / "b" / "unit.o.tmp4242")]
     for o in outs:
