@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 5
+#define MCD_ABI_VERSION 6
 
 enum {
     MCD_OK = 0,
@@ -250,6 +250,53 @@ int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* r
  * division in float64, rounded to fp32 after each).  PRECONDITION: `raw` is finite (the Python wrapper checks it). */
 int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float vid_h,
                         const double* center, const double* scale, float* out, void* stream);
+
+/* Live pose streams: the state between two ticks of an online scorer (many tracked people, one new pose row per track per
+ * video frame), in two CALLER-owned device rings.  Replaces, one tick at a time, what the dataset path does once per dataset: the
+ * per-row normalisation of mcd_normalize_poses, the sliding windows over consecutive rows of a trajectory
+ * (utils/preprocessing.py:14-86) and the per-frame maximum over the windows covering a frame (compute_var_matrix + np.nanmax,
+ * eval_utils.py:27-34, mocodad.py:392-393).
+ *   ring          (n_slots, 2 * ring_len, 2, 17) f32 in the frame-major row layout mcd_window_view_t reads with stride_c 17 and stride_t 34.
+ *                 Row r of a track (0-based count of the rows pushed for it) is stored TWICE, at positions r % ring_len and
+ *                 r % ring_len + ring_len: the seg_len rows from row s on are contiguous from position s % ring_len, so a window is
+ *                 one base offset, slot * 2 * ring_len * 34 + (s % ring_len) * 34, and the scoring entries read it as they read a
+ *                 trajectory buffer.
+ *   frame_scores  (n_slots, num_transform, ring_len) f32: cell r % ring_len = running maximum over the windows that cover row r.
+ * A slot is one track; which track owns which slot, its row count and its frame ids are the host's business.  A tick holds AT MOST
+ * ONE row per slot (the kernels use plain loads and stores).  One state is driven from one stream. */
+typedef struct {
+    float* ring;
+    float* frame_scores;
+    int32_t n_slots;
+    int32_t ring_len;      /* L >= seg_len */
+    int32_t seg_len;
+    int32_t num_transform;
+} mcd_stream_state_t;
+
+/* One tick's rows into the rings.  raw (n, 34) f32 as for mcd_normalize_poses, same arithmetic bit for bit (center / scale (34,)
+ * f64 or both NULL; PRECONDITION: finite); desc (n, 3) i32 device = [slot, row index r, emit index j] per row, j = -1 while the
+ * track has fewer than seg_len rows, else its position among the tick's n_emit windows.  Per row: the normalised pose goes to both
+ * ring positions, the row's frame-score cell is zeroed for every transform (which also makes a reused slot start clean), and for
+ * j >= 0 the window descriptors of the window ENDING at row r are written for all transforms, transform-major like the dataset
+ * order (utils/dataset.py:67-71): base_out[t * n_emit + j] (i64 element offsets into `ring`), trans_out[t * n_emit + j] = t --
+ * the `base` / `trans` of a mcd_window_view_t over `ring` for mcd_score_view / mcd_score_fused.  Rows whose slot is out of range
+ * are ignored. */
+int mcd_stream_push(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_emit,
+                    float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
+                    int32_t* trans_out, void* stream);
+
+/* The tick's window scores into the frame-score ring (replaces mocodad.py:392-393 + eval_utils.py:27-34 for the rows in flight).
+ * scores (num_transform * n_emit,) f32 in the order of base_out; win (n_emit, 2) i32 device = [slot, r_last] (the row the window
+ * ends at).  max(score, 0) -- the clamp of mcd_scatter_max -- is taken into the cells of rows r_last - seg_len + 1 .. r_last;
+ * final_out (n_emit, num_transform) f32 = the cell of row r_last - seg_len + 1, which no later window covers: that row's final
+ * frame score. */
+int mcd_stream_frame_scores(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_emit,
+                            float* final_out, void* stream);
+
+/* Tracks being closed: win (n, 2) i32 device = [slot, r_last = index of the track's last row]; out (n, seg_len - 1, num_transform)
+ * f32 = the cells of the still-pending rows r_last - seg_len + 2 .. r_last.  (Tracks of fewer than seg_len rows have no window,
+ * hence no frame score -- the dataset path drops them, utils/preprocessing.py:4-10 -- and are not passed here.) */
+int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream);
 
 /* Frame-score assembly after the path, whole: replaces the (transform, clip, person) loops of
  * MoCoDAD.post_processing (mocodad.py:362-425) with compute_var_matrix + np.nanmax (eval_utils.py:27-34, mocodad.py:392-393),

@@ -14,7 +14,7 @@ LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
 COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class Tensor(C.Structure):
@@ -45,6 +45,11 @@ class FrameCfg(C.Structure):
                 ("clip_out_off", C.c_void_p), ("gauss_weights", C.c_void_p)]
 
 
+class StreamState(C.Structure):
+    _fields_ = [("ring", C.c_void_p), ("frame_scores", C.c_void_p), ("n_slots", C.c_int32), ("ring_len", C.c_int32),
+                ("seg_len", C.c_int32), ("num_transform", C.c_int32)]
+
+
 _SIGS = {
     "mcd_pack_weights": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.c_int32, C.POINTER(C.c_void_p)]),
     "mcd_free_weights": (None, [C.c_void_p]),
@@ -73,6 +78,10 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_normalize_poses": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "mcd_stream_push": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_stream_frame_scores": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcd_stream_flush": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_last_error": (C.c_char_p, []),
     "mcd_abi_version": (C.c_int32, []),
 }

@@ -8,6 +8,8 @@
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
 //   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
+//   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
+//                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
 // The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
@@ -589,14 +591,11 @@ __global__ void scatter_max_kernel(const float* __restrict__ scores, const int* 
 // round-half-even to int, (x - centre) / size correctly rounded in fp32 (computed in double and rounded once: exact, 53 >= 2*24+2),
 // then sklearn's RobustScaler.transform, which runs x - center_ and / scale_ in float64 and rounds to fp32 after each.
 // raw (n, 34) = x1,y1,...,x17,y17; out (n, 2, 17).
-__global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __restrict__ raw, long long n, float vid_w, float vid_h,
-                                                              const double* __restrict__ center, const double* __restrict__ scale,
-                                                              float* __restrict__ out) {
+// normalize_pose_row: one row, written to `o` and, when o2 != nullptr, to `o2` as well (the mirrored copy of a track ring).
+__device__ __forceinline__ void normalize_pose_row(const float* __restrict__ r, float vid_w, float vid_h,
+                                                   const double* __restrict__ center, const double* __restrict__ scale,
+                                                   float* __restrict__ o, float* __restrict__ o2) {
 #pragma clang fp contract(off)      // the margin is 0.1 * (r - l + 1), then l - margin: two roundings, never an FMA
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n) return;
-    const float* r = raw + f * 34;
-    float* o = out + f * 34;
     float v[34];
     float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
     for (int k = 0; k < 34; k += 2) {
@@ -634,7 +633,83 @@ __global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __res
             }
         }
         o[(k & 1) * 17 + (k >> 1)] = t;
+        if (o2) o2[(k & 1) * 17 + (k >> 1)] = t;
     }
+}
+
+__global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __restrict__ raw, long long n, float vid_w, float vid_h,
+                                                              const double* __restrict__ center, const double* __restrict__ scale,
+                                                              float* __restrict__ out) {
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    normalize_pose_row(raw + f * 34, vid_w, vid_h, center, scale, out + f * 34, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Live pose streams (mcd_stream_state_t): the state between two ticks lives in two caller-owned rings.
+//   pose ring  (n_slots, 2 L, 2, 17): row r of a track sits at positions r % L and r % L + L, so the seg_len rows from row s on
+//              are contiguous from position s % L and a window stays ONE base offset of mcd_window_view_t.
+//   score ring (n_slots, num_transform, L): running max, per row and transform, over the windows covering the row.
+// A tick holds at most one row per track, so no two threads of a launch touch the same cell: plain loads and stores.
+// ------------------------------------------------------------------------------------------------
+struct StreamParams {
+    float* ring; float* fs;
+    int n_slots, L, seg_len, nt;
+};
+
+// one thread per pushed row: desc (n, 3) = [slot, row index r, emit index j | -1]
+__global__ __launch_bounds__(256) void stream_push_kernel(StreamParams S, const float* __restrict__ raw, const int* __restrict__ desc,
+                                                          int n, int n_emit, float vid_w, float vid_h,
+                                                          const double* __restrict__ center, const double* __restrict__ scale,
+                                                          long long* __restrict__ base_out, int* __restrict__ trans_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int slot = desc[3 * i], r = desc[3 * i + 1], j = desc[3 * i + 2];
+    if (slot < 0 || slot >= S.n_slots || r < 0) return;        // (a descriptor the host table cannot produce: touch nothing)
+    const int p = r % S.L;
+    float* o = S.ring + ((size_t)slot * 2 * S.L + p) * 34;
+    normalize_pose_row(raw + (size_t)i * 34, vid_w, vid_h, center, scale, o, o + (size_t)S.L * 34);
+    for (int t = 0; t < S.nt; ++t) S.fs[((size_t)slot * S.nt + t) * S.L + p] = 0.f;
+    if (j < 0 || j >= n_emit || r < S.seg_len - 1) return;
+    const long long base = ((long long)slot * 2 * S.L + (r - S.seg_len + 1) % S.L) * 34;
+    for (int t = 0; t < S.nt; ++t) {
+        base_out[(size_t)t * n_emit + j] = base;
+        trans_out[(size_t)t * n_emit + j] = t;
+    }
+}
+
+// one thread per (emitted window j, transform t): win (n_emit, 2) = [slot, r_last]; scores (num_transform * n_emit,) transform-major.
+// The same clamp and zero start as scatter_max_kernel; final_out (n_emit, num_transform) = the cell of row r_last - seg_len + 1,
+// which no later window covers.
+__global__ __launch_bounds__(256) void stream_frame_scores_kernel(StreamParams S, const float* __restrict__ scores,
+                                                                  const int* __restrict__ win, int n_emit,
+                                                                  float* __restrict__ final_out) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_emit * S.nt) return;
+    const int j = u / S.nt, t = u - j * S.nt;
+    const int slot = win[2 * j], r_last = win[2 * j + 1];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
+    const float sc = fmaxf(scores[(size_t)t * n_emit + j], 0.f);
+    float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
+    const int first = r_last - S.seg_len + 1;
+    for (int k = S.seg_len - 1; k >= 0; --k) {
+        float* c = row + (first + k) % S.L;
+        const float m = fmaxf(*c, sc);
+        *c = m;
+        if (k == 0) final_out[u] = m;
+    }
+}
+
+// one thread per (closed track i, pending row k, transform t): the seg_len - 1 cells of rows r_last - seg_len + 2 .. r_last
+__global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const int* __restrict__ win, int n,
+                                                           float* __restrict__ out) {
+    const int pend = S.seg_len - 1;
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n * pend * S.nt) return;
+    const int t = u % S.nt, k = (u / S.nt) % pend, i = u / (S.nt * pend);
+    const int slot = win[2 * i], r_last = win[2 * i + 1];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
+    out[u] = S.fs[((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L];
 }
 
 
@@ -1774,6 +1849,62 @@ int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float v
     if (blocks > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many frames for one launch");
     hipLaunchKernelGGL(normalize_poses_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw,
                        (long long)n_frames, vid_w, vid_h, center, scale, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+static int stream_params(const mcd_stream_state_t* s, StreamParams* P) {
+    if (!s || !s->ring || !s->frame_scores) return fail(MCD_EINVAL, "null stream state");
+    if (s->n_slots <= 0 || s->num_transform <= 0 || s->seg_len <= 0 || s->seg_len > MCD_MAX_FRAMES || s->ring_len < s->seg_len)
+        return fail(MCD_EINVAL, "stream state: need n_slots, num_transform >= 1 and 1 <= seg_len <= ring_len (seg_len <= 32)");
+    if ((int64_t)s->n_slots * 2 * s->ring_len > 0x7fffffffll / 34 || (int64_t)s->n_slots * s->num_transform * s->ring_len > 0x7fffffffll)
+        return fail(MCD_EUNSUPPORTED, "stream rings of more than 2^31 elements");
+    P->ring = s->ring; P->fs = s->frame_scores;
+    P->n_slots = s->n_slots; P->L = s->ring_len; P->seg_len = s->seg_len; P->nt = s->num_transform;
+    return MCD_OK;
+}
+
+int mcd_stream_push(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_emit,
+                    float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
+                    int32_t* trans_out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_params(s, &P)) return rc;
+    if (n < 0 || n_emit < 0 || n_emit > n) return fail(MCD_EINVAL, "need 0 <= n_emit <= n");
+    if (n > s->n_slots) return fail(MCD_EINVAL, "more rows than slots: a tick holds at most one row per track");
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    if (n == 0) return MCD_OK;
+    if (!raw || !desc || (n_emit > 0 && (!base_out || !trans_out))) return fail(MCD_EINVAL, "null argument");
+    hipLaunchKernelGGL(stream_push_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, raw, desc, n,
+                       n_emit, vid_w, vid_h, center, scale, reinterpret_cast<long long*>(base_out), trans_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_frame_scores(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_emit,
+                            float* final_out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_params(s, &P)) return rc;
+    if (n_emit < 0 || n_emit > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n_emit <= n_slots");
+    if (n_emit == 0) return MCD_OK;
+    if (!scores || !win || !final_out) return fail(MCD_EINVAL, "null argument");
+    const long long total = (long long)n_emit * P.nt;
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    hipLaunchKernelGGL(stream_frame_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
+                       scores, win, n_emit, final_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_params(s, &P)) return rc;
+    if (n < 0 || n > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
+    const long long total = (long long)n * (P.seg_len - 1) * P.nt;
+    if (total == 0) return MCD_OK;
+    if (!win || !out) return fail(MCD_EINVAL, "null argument");
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
+    hipLaunchKernelGGL(stream_flush_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, win, n, out);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }

@@ -347,6 +347,21 @@ class HipScorer:
         return out
 
 
+def _scaler_stats(center, scale, dev) -> list:
+    """[center, scale] as (34,) float64 device tensors (the precision sklearn's transform runs in), or [] when both are None."""
+    if (center is None) != (scale is None):
+        raise ValueError("center and scale go together (both None = no robust scaling)")
+    stats = []
+    for name, a in (("center", center), ("scale", scale)):
+        if a is None:
+            continue
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.shape != (34,):
+            raise ValueError(f"{name} must hold 34 features, got shape {a.shape}")
+        stats.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
+    return stats
+
+
 def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, device=None,
                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dataset loader step (mcd_normalize_poses): raw (n_frames, 34) fp32 pose rows as read from the CSVs (x1,y1,...,x17,y17;
@@ -375,14 +390,7 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
     w, h = (float(np.float32(v)) for v in vid_res)
     if not (np.isfinite(w) and np.isfinite(h)):
         raise ValueError(f"vid_res must be finite, got {tuple(vid_res)}")
-    stats = []
-    for name, a in (("center", center), ("scale", scale)):
-        if a is None:
-            continue
-        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-        if a.shape != (34,):
-            raise ValueError(f"{name} must hold 34 features, got shape {a.shape}")
-        stats.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
+    stats = _scaler_stats(center, scale, dev)
     n = shape[0]
     if out is None:
         out = torch.empty(n, 2, 17, device=dev, dtype=torch.float32)
@@ -394,6 +402,62 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
         c, s = (stats[0], stats[1]) if stats else (None, None)
         _lib.check(L.mcd_normalize_poses(_ptr(raw), n, w, h, _ptr(c), _ptr(s), _ptr(out), _stream()))
     return out
+
+
+class StreamRings:
+    """Device state of a live pose stream (mcd_stream_state_t) and the three launches on it; the host half -- which track owns
+    which slot, row counts, frame ids -- is mocodad_amd.stream.TrackTable, the tick that ties them together PoseStream.push.
+      ring          flat (n_slots * 2 * ring_len * 34,) fp32: row r of slot s at positions r % L and r % L + L of its 2 L rows
+      frame_scores  (n_slots, num_transform, ring_len) fp32 running maxima
+    vid_res / center / scale: as for normalize_poses.  All calls are asynchronous on the current stream; one state is driven
+    from one stream."""
+
+    def __init__(self, n_slots: int, seg_len: int, ring_len: int, num_transform: int, vid_res: Sequence[float], center=None,
+                 scale=None, *, device=None):
+        self.L = _lib.lib()
+        if not torch.cuda.is_available():
+            raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
+        self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.n_slots, self.seg_len, self.ring_len, self.num_transform = int(n_slots), int(seg_len), int(ring_len), int(num_transform)
+        self.vid_res = tuple(float(np.float32(v)) for v in vid_res)
+        if len(self.vid_res) != 2 or not all(np.isfinite(self.vid_res)):
+            raise ValueError(f"vid_res must be two finite numbers, got {tuple(vid_res)}")
+        self._stats = _scaler_stats(center, scale, dev)
+        with torch.cuda.device(dev):
+            self.ring = torch.zeros(self.n_slots * 2 * self.ring_len * 34, device=dev, dtype=torch.float32)
+            self.frame_scores_ring = torch.zeros(self.n_slots, self.num_transform, self.ring_len, device=dev, dtype=torch.float32)
+        self._state = _lib.StreamState(ring=self.ring.data_ptr(), frame_scores=self.frame_scores_ring.data_ptr(),
+                                       n_slots=self.n_slots, ring_len=self.ring_len, seg_len=self.seg_len,
+                                       num_transform=self.num_transform)
+
+    def push(self, raw: torch.Tensor, desc: torch.Tensor, n: int, n_emit: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """mcd_stream_push: raw (n, 34) fp32 rows, desc (n, 3) int32 [slot, row index, emit index | -1] (device; any dtype of 4
+        bytes: views of one staging buffer) -> (base (num_transform * n_emit,) int64, trans (same,) int32), transform-major."""
+        nw = self.num_transform * int(n_emit)
+        with torch.cuda.device(self.device):
+            base = torch.empty(nw, device=self.device, dtype=torch.int64)
+            trans = torch.empty(nw, device=self.device, dtype=torch.int32)
+            c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+            _lib.check(self.L.mcd_stream_push(C.byref(self._state), _ptr(raw), _ptr(desc), int(n), int(n_emit), self.vid_res[0],
+                                              self.vid_res[1], _ptr(c), _ptr(s), _ptr(base), _ptr(trans), _stream()))
+        return base, trans
+
+    def frame_scores(self, scores: torch.Tensor, win: torch.Tensor, n_emit: int) -> torch.Tensor:
+        """mcd_stream_frame_scores: scores (num_transform * n_emit,) fp32, win (n_emit, 2) int32 [slot, r_last] ->
+        (n_emit, num_transform) final frame scores of the windows' first rows."""
+        with torch.cuda.device(self.device):
+            final = torch.empty(int(n_emit), self.num_transform, device=self.device, dtype=torch.float32)
+            _lib.check(self.L.mcd_stream_frame_scores(C.byref(self._state), _ptr(scores), _ptr(win), int(n_emit), _ptr(final), _stream()))
+        return final
+
+    def flush(self, win: Optional[torch.Tensor], n: int) -> torch.Tensor:
+        """mcd_stream_flush: win (n, 2) int32 [slot, last row index] of tracks being closed -> (n * (seg_len - 1), num_transform)
+        frame scores of their pending rows, oldest first."""
+        with torch.cuda.device(self.device):
+            out = torch.empty(int(n) * (self.seg_len - 1), self.num_transform, device=self.device, dtype=torch.float32)
+            if out.numel():
+                _lib.check(self.L.mcd_stream_flush(C.byref(self._state), _ptr(win), int(n), _ptr(out), _stream()))
+        return out
 
 
 class FrameScoreAssembler:

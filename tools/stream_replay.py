@@ -1,0 +1,191 @@
+#!/usr/bin/env python3
+"""Replay recorded pose tracks through a PoseStream (mocodad_amd/stream.py) as a live feed and time the ticks.
+
+    python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init               # the split of the YAML paths
+    python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --data-dir tests/golden/dataset \\
+           --dataset-choice HR-STC --no-scaler                                                # the test fixture
+    python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 256 --rows 120
+
+On-disk split: the trajectory CSVs are replayed in frame order, one tick = one frame id across all clips; a track is closed
+after its last row.  The window scores, put back into dataset order, go through the model's own post_processing: the AUC is
+printed.  --synthetic-tracks N: N tracks that all receive a row on every tick (no AUC) -- the load of N tracked people.
+
+Timing (host clock around work that ends in a device synchronise, one warm-up replay, then --reps replays):
+  tick      PoseStream.push of one tick: host table + one H2D copy + mcd_stream_push + the scoring call + mcd_stream_frame_scores
+  baseline  ONE score_fused call on a pre-built WindowBatch of the tick's window count over a trajectory buffer already on the
+            device (what a caller of the dataset path would pay for the same windows if the buffer and the window list cost
+            nothing), timed the same way in the same process, alternating with the stream replay.
+Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
+emitted windows, the range of the per-replay medians (the spread), and the same for the baseline."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from mocodad_amd.data import trajectories as T  # noqa: E402
+from mocodad_amd.data.windows import TrajectoryWindows, WindowBatch  # noqa: E402
+from mocodad_amd.engine import normalize_poses  # noqa: E402
+from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
+from mocodad_amd.stream import PoseStream, ticks_by_frame  # noqa: E402
+from mocodad_amd.utils.argparser import load_config  # noqa: E402
+
+
+def synthetic_tracks(n_tracks, rows, vid_res, seed=0):
+    """n_tracks people walking through the frame for `rows` frames: [((scene, clip, person), frames, poses (rows, 34))]."""
+    rng = np.random.default_rng(seed)
+    W, H = vid_res
+    skel = rng.normal(0, 1, (n_tracks, 1, 17, 2)) * np.array([12.0, 30.0])
+    centre = np.stack([rng.uniform(60, W - 60, n_tracks), rng.uniform(60, H - 60, n_tracks)], 1)[:, None, None, :]
+    walk = np.cumsum(rng.normal(0, 1.5, (n_tracks, rows, 1, 2)), axis=1)
+    p = (centre + walk + skel + rng.normal(0, 0.8, (n_tracks, rows, 17, 2))).clip(1, None).astype(np.float32)
+    fr = np.arange(1, rows + 1, dtype=np.int32)
+    return [((1, 1 + i // 16, i), fr, p[i].reshape(rows, 34)) for i in range(n_tracks)]
+
+
+def stats(per_rep):
+    """per_rep: one array of tick times (s) per replay -> microseconds."""
+    allt = np.concatenate(per_rep) * 1e6
+    med = [float(np.median(r) * 1e6) for r in per_rep]
+    return {"median_us": round(float(np.median(allt)), 1), "p99_us": round(float(np.percentile(allt, 99)), 1),
+            "max_us": round(float(allt.max()), 1), "replay_median_us_min": round(min(med), 1), "replay_median_us_max": round(max(med), 1),
+            "ticks_timed": int(allt.size)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("-c", "--config", required=True)
+    ap.add_argument("--data-dir", default=None, help="overrides data_dir (and test_path = <data-dir>/testing/test_frame_mask)")
+    ap.add_argument("--dataset-choice", default=None)
+    ap.add_argument("--no-scaler", action="store_true", help="bounding-box normalisation only (no fitted RobustScaler at hand)")
+    ap.add_argument("--random-init", action="store_true", help="seeded random-init weights when the checkpoint is missing")
+    ap.add_argument("--synthetic-tracks", type=int, default=0)
+    ap.add_argument("--rows", type=int, default=120, help="rows per synthetic track")
+    ap.add_argument("--ring-len", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
+    cli = ap.parse_args()
+    args = load_config(cli.config)
+    if cli.data_dir:
+        args.data_dir = cli.data_dir
+        args.test_path = args.gt_path = os.path.join(cli.data_dir, "testing", "test_frame_mask")
+    if cli.dataset_choice:
+        args.dataset_choice = cli.dataset_choice
+    if not torch.cuda.is_available():
+        raise SystemExit("stream_replay.py measures on an MI355X: no GPU found (there is no CPU fallback)")
+    dev = torch.device("cuda:0")
+    seg_len, nt, vid_res = int(args.seg_len), int(args.num_transform), tuple(args.vid_res)
+
+    torch.manual_seed(int(getattr(args, "seed", 0)))
+    model = MoCoDAD(args).to(dev)
+    model.save_tensors = False
+    ckpt = os.path.join(args.ckpt_dir, args.load_ckpt)
+    if os.path.exists(ckpt):
+        model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"])
+    elif not cli.random_init:
+        raise SystemExit(f"checkpoint {ckpt} not found (pass --random-init to score with seeded random-init weights)")
+    center, scale = (None, None) if cli.no_scaler or cli.synthetic_tracks else T.load_scaler_stats(args.ckpt_dir)
+
+    if cli.synthetic_tracks:
+        tracks = synthetic_tracks(cli.synthetic_tracks, cli.rows, vid_res, seed=int(getattr(args, "seed", 0)))
+        source = f"synthetic: {cli.synthetic_tracks} tracks x {cli.rows} rows"
+    else:
+        split = str(getattr(args, "split", "test"))
+        files = T.list_trajectory_files(T.trajectories_root(args.data_dir, split))
+        tracks = [(key,) + T.read_trajectory_csv(path) for key, path in files]
+        source = f"{args.data_dir} ({split}): {len(tracks)} track files"
+    size = {k: len(f) for k, f, _ in tracks}
+    ticks, left, n_open, peak = [], dict(size), 0, 0
+    for _, keys, fids, poses in ticks_by_frame(tracks):
+        n_open += sum(left[k] == size[k] for k in keys)
+        peak = max(peak, n_open)
+        for k in keys:
+            left[k] -= 1
+        done = [k for k in keys if left[k] == 0]        # closed right after their last row
+        n_open -= len(done)
+        ticks.append((keys, fids, poses, done))
+    # the dataset path on the same rows: the trajectory buffer + window list the baseline scores from (and the AUC needs)
+    kept = sorted(((k, f, p) for k, f, p in tracks if len(f) >= seg_len), key=lambda t: t[0])
+    off = np.zeros(len(kept) + 1, np.int64)
+    off[1:] = np.cumsum([len(f) for _, f, _ in kept])
+    buf = normalize_poses(np.concatenate([p for _, _, p in kept]), vid_res, center, scale, device=dev)
+    tw = TrajectoryWindows.from_buffer(buf.reshape(-1), off, np.concatenate([f for _, f, _ in kept]), [k for k, _, _ in kept],
+                                       seg_len, nt)
+    n = tw.n_samples
+    sample_of = {tuple(int(v) for v in r): i for i, r in enumerate(tw.meta[:n].numpy())}
+    base_d, trans_d = tw.base.to(dev), tw.trans.to(dev)
+    sc = model.scorer()
+    kw = dict(n_samples=model.n_generated_samples, noise_steps=model.noise_steps, aggregation=model.aggregation_strategy,
+              seed=model.seed, loss_fn=model.loss_name)
+
+    def replay(collect=None):
+        stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=cli.ring_len,
+                            num_transform=nt)
+        times, counts = [], []
+        for keys, fids, poses, done in ticks:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tick = stream.push(keys, fids, poses)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            ne = len(tick.final)
+            if ne:
+                times.append(dt)
+                counts.append(ne * nt)
+                if collect is not None:
+                    idx = np.asarray([t * n + sample_of[tuple(int(v) for v in m)] for t in range(nt) for m in tick.meta[:ne]])
+                    collect[idx] = tick.scores.cpu().numpy()
+            if done:
+                stream.close(done)
+        return np.asarray(times), counts
+
+    def baseline(counts):
+        times = []
+        out = torch.empty(max(counts), device=dev, dtype=torch.float32)
+        for i, c in enumerate(counts):
+            lo = (i * 7) % max(1, len(tw) - c + 1) if c <= len(tw) else 0
+            wb = WindowBatch(tw.buffer, base_d[lo:lo + c], trans_d[lo:lo + c], tw.affine, seg_len)
+            if wb.base.shape[0] != c:                      # (more windows in a tick than the split has: not with these replays)
+                raise SystemExit("baseline: the tick holds more windows than the dataset path built")
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sc.score_fused(wb, first_window_id=lo, out=out[:c], **kw)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        return np.asarray(times)
+
+    scores = np.full(nt * n, np.nan, np.float32)
+    _, counts = replay(scores)                  # warm-up replay (code objects, allocator pools); also the scores for the AUC
+    baseline(counts)
+    assert not np.isnan(scores).any() and sum(counts) == nt * n, "the replay did not emit every window of the dataset path"
+    auc = None
+    if not cli.synthetic_tracks:
+        auc = float(model.post_processing(scores, None, tw.trans.long().numpy(), tw.meta.numpy(), tw.frames.numpy()))
+    t_stream, t_base = [], []
+    for _ in range(cli.reps):                   # alternating: both legs see the same machine state
+        t_stream.append(replay()[0])
+        t_base.append(baseline(counts))
+    res = {"source": source, "ticks": len(ticks), "ticks_with_windows": len(counts), "peak_open_tracks": peak,
+           "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
+           "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
+           "n_samples": int(model.n_generated_samples), "ring_len": cli.ring_len or seg_len, "reps": cli.reps, "auc": auc,
+           "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
+    if auc is not None:
+        print(f"AUC: {auc:.6f}")
+    print(f"tick: median {res['tick']['median_us']} us, p99 {res['tick']['p99_us']} us | baseline score_fused alone: median "
+          f"{res['baseline_score_fused']['median_us']} us, p99 {res['baseline_score_fused']['p99_us']} us")
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(cli.out)), exist_ok=True)
+    with open(cli.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
