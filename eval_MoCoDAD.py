@@ -28,6 +28,14 @@ from mocodad_amd.parallel import WindowShard  # noqa: E402
 from mocodad_amd.utils.argparser import load_config  # noqa: E402
 
 
+def model_class(args):
+    """MoCoDADlatent when the YAML says `diffusion_on_latent: true` (the reference's eval_MoCoDAD.py:45-46), else MoCoDAD."""
+    if getattr(args, "diffusion_on_latent", False):
+        from mocodad_amd.models.mocodad_latent import MoCoDADlatent
+        return MoCoDADlatent
+    return MoCoDAD
+
+
 def main():
     ap = argparse.ArgumentParser(description="MoCoDAD (MI355X)")
     ap.add_argument("-c", "--config", type=str, required=True)
@@ -42,8 +50,7 @@ def main():
     ap.add_argument("--dump-scores", type=str, default=None, help="rank 0 writes the gathered window scores + AUC to this .npz")
     cli = ap.parse_args()
     args = load_config(cli.config)
-    if hasattr(args, "diffusion_on_latent"):
-        raise NotImplementedError("the latent-diffusion variant (MoCoDADlatent) is outside the accelerated path")
+    model_cls = model_class(args)
     if not cli.synthetic:
         try:
             check_supported(args)        # (before any GPU call)
@@ -96,7 +103,7 @@ def main():
                   f"{load_t['parse']:.3f}s  upload+normalise {load_t['normalise']:.3f}s")
 
     torch.manual_seed(int(getattr(args, "seed", 0)))      # without a checkpoint every rank must draw the same weights
-    model = MoCoDAD(args).to(dev)
+    model = model_cls(args).to(dev)
     if cli.synthetic:
         model.dataset_name = "synthetic"      # synthetic clips have their own lengths: no HR-Avenue / UBnormal frame masks
     ckpt = os.path.join(args.ckpt_dir, args.load_ckpt)

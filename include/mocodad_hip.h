@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 6
+#define MCD_ABI_VERSION 7
 
 enum {
     MCD_OK = 0,
@@ -324,6 +324,76 @@ int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* cfg);
  * (the arrays MoCoDAD.post_processing receives, on the device) -> out (sum clip_out_len,) f64 = `pds` of mocodad.py:422. */
 int mcd_frame_scores(const mcd_frame_cfg_t* cfg, const float* scores, const int64_t* trans, const int64_t* meta,
                      const int32_t* frames, int64_t n_windows, int32_t seg_len, void* workspace, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * MoCoDADlatent (models/mocodad_latent.py, stage 'diffusion'): the reverse diffusion runs on a D-dimensional latent code of the
+ * corrupt frames, through a small conditioned MLP.  A latent model has its own handle type: none of the entry points above
+ * takes it.  Two launches per scoring call: encode (condition encoder + the U-Net's down path + to_time_dim) and chain (every
+ * denoiser pass, the DDPM updates, the loss and the aggregation). */
+
+#define MCD_LATENT_MAX_LAYERS 8
+/* Denoiser of models/common/components.py:203-241 as MoCoDADlatent.build_model constructs it (mocodad_latent.py:51-57):
+ * latent_dim = latent_embedding_dim, hidden = hidden_sizes (the last one equals latent_dim).  latent_dim and every hidden size:
+ * a multiple of 16 in 16 .. 128; 1 .. 8 layers; anything else is MCD_EUNSUPPORTED. */
+typedef struct {
+    int32_t latent_dim;
+    int32_t n_layers;
+    int32_t hidden[MCD_LATENT_MAX_LAYERS];
+} mcd_latent_cfg_t;
+
+typedef struct mcd_latent_weights mcd_latent_weights_t;
+
+/* Replaces: load_state_dict + eval() of a diffusion-stage MoCoDADlatent checkpoint (mocodad_latent.py:42-57; eval_MoCoDAD.py:36-38).
+ * Reads model.{st_gcnnsp1a,st_gcnnsd1..3,down1,down2,to_time_dim}.* (STSE_Unet with embeddings, stsae_unet.py:50-154; there is no
+ * up path), condition_encoder.* (encoder and bottleneck; the AE decoder is dead work at evaluation) and
+ * denoiser.{net,cond_layers}.*.  BatchNorm2d / BatchNorm1d are folded into the preceding conv / Linear in double, the matrices
+ * repacked into MFMA fragment order.  cfg: strategy MCD_STRATEGY_INJECT (mocodad_latent.py:32), t_unet = corrupt frames,
+ * t_cond = condition frames, the shipped condition encoder (cond_layers 4, channels 32,16,32,32).  The encode launch is
+ * instantiated for t_unet = t_cond = 3 (every shipped configuration); another count is MCD_EUNSUPPORTED, naming it.  A missing
+ * tensor is MCD_EMISSING with its name -- reported before the device is touched. */
+int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg,
+                            const mcd_latent_cfg_t* latent_cfg, int32_t device, mcd_latent_weights_t** out);
+void mcd_free_latent_weights(mcd_latent_weights_t* w);
+
+/* Bytes of device scratch mcd_latent_score needs for n_windows windows: cond_emb (B,16) and z0 (B,D) between its two launches. */
+int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows);
+
+/* The latent step table: (noise_steps + 1, 4 + emb_dim) -- rows 0 .. ns-1 as for mcd_score (update coefficients of
+ * mocodad_latent.py:117-123 and pos_encoding(i), components.py:244-262), row ns = [0, 0, 0, 0, pos_encoding(-1)]: the constant
+ * time step the encoder is given (mocodad_latent.py:95). */
+
+/* Replaces: _encode_condition + _unet_forward(corrupt_data, t = -1, condition_embedding) (mocodad_latent.py:98-104 ->
+ * STSE_Unet.forward, stsae_unet.py:222-249).  cfg: n_windows, seg_len, noise_steps (locates the table's last row) and the frame
+ * index lists; data / view as for mcd_score_view -> cond_emb_out (B,16), z0_out (B,D). */
+int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                      const float* step_table, float* cond_emb_out, float* z0_out, void* stream);
+
+/* TEST ENTRY.  Replaces: Denoiser.forward (components.py:265-291) for n_rows arbitrary rows at one time step t >= 0 shared by
+ * them: x (N,D), cond (N,16), step_table with at least t + 1 rows -> eps_out (N,D).  Runs the chain kernel's layer code. */
+int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
+                       int32_t n_rows, float* eps_out, void* stream);
+
+/* Replaces: MoCoDADlatent.forward, stage 'diffusion' (mocodad_latent.py:93-127) with the loss-based aggregations of
+ * _aggregation_strategy (mocodad.py:484-516).
+ *   noise        NULL -> in-kernel Philox4x32-10 keyed by (seed, first_window_id + b, s, slot, group of 4 latent elements);
+ *                else (S, max(ns-1,1), B, D): slot 0 = x_T (torch.randn at mocodad_latent.py:109), slot k = the z of step
+ *                i = ns - k (torch.randn_like at :121), in call order
+ *   step_table   the latent step table above
+ *   workspace    mcd_latent_workspace_bytes (required)
+ *   aggregation  MCD_AGGR_ALL (loss_all required, loss_agg unused) or BEST / WORST / MEAN / MEDIAN / QUANTILE -> loss_agg (B,)
+ *   loss_all (B,S), latent_all (B,S,D) generated latents, latent_code (B,D) = z0: optional outputs (NULL = not wanted)
+ * cfg->loss_fn is applied to (generated latent, z0) and averaged over D.  1 .. 1024 samples per call.  Chains are independent:
+ * one whose state becomes non-finite returns a non-finite loss and changes no other chain's result; `best` / `worst` skip it
+ * like the reference's strict comparisons do. */
+int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                     const float* noise, uint64_t seed, int64_t first_window_id, const float* step_table, void* workspace,
+                     int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,
+                     void* stream);
+
+/* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
+ * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121). */
+int mcd_latent_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
+                            int32_t latent_dim, float* noise_out, void* stream);
 
 /* Profiling builds only (-DMCD_PROFILE, tools/stage_profile.py): device buffer of 96 uint64 per-stage cycle accumulators
  * written by workgroup 0 of the trajectory kernel; NULL (the default) disables it.  A no-op in the shipped build. */

@@ -14,7 +14,7 @@ LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
 COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class Tensor(C.Structure):
@@ -43,6 +43,10 @@ class FrameCfg(C.Structure):
                 ("pad_size", C.c_int32), ("frames_shift", C.c_int32), ("gauss_radius", C.c_int32),
                 ("clip_keys", C.c_void_p), ("clip_n_frames", C.c_void_p), ("frame_dst", C.c_void_p), ("clip_out_len", C.c_void_p),
                 ("clip_out_off", C.c_void_p), ("gauss_weights", C.c_void_p)]
+
+
+class LatentCfg(C.Structure):
+    _fields_ = [("latent_dim", C.c_int32), ("n_layers", C.c_int32), ("hidden", C.c_int32 * 8)]
 
 
 class StreamState(C.Structure):
@@ -82,6 +86,17 @@ _SIGS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_stream_frame_scores": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_stream_flush": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcd_pack_latent_weights": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.POINTER(LatentCfg), C.c_int32,
+                                          C.POINTER(C.c_void_p)]),
+    "mcd_free_latent_weights": (None, [C.c_void_p]),
+    "mcd_latent_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32]),
+    "mcd_latent_encode": (C.c_int, [C.c_void_p, C.POINTER(ScoreCfg), C.c_void_p, C.POINTER(WindowView), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "mcd_latent_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcd_latent_score": (C.c_int, [C.c_void_p, C.POINTER(ScoreCfg), C.c_void_p, C.POINTER(WindowView), C.c_void_p, C.c_uint64,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "mcd_latent_philox_noise": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_last_error": (C.c_char_p, []),
     "mcd_abi_version": (C.c_int32, []),
 }

@@ -1,5 +1,5 @@
 """Builds libmocodad_hip.so for gfx950 from mocodad_amd/csrc: mcd_api.hip (C ABI, packers, dispatch, the runtime-shape kernels)
-plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp), compiled in parallel and linked with hipcc.
+plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels), compiled in parallel and linked with hipcc.
 
     python -m mocodad_amd.build                       # the shipped library (mocodad_amd/libmocodad_hip.so)
     python -m mocodad_amd.build --profile             # + -DMCD_PROFILE -> libmocodad_hip_prof.so (tools/stage_profile.py)
@@ -129,6 +129,7 @@ def build_library(out: str = DEFAULT_OUT, defines: Iterable[str] = (), extra_fla
     jobs_l = [("mcd_api.o", os.path.join(CSRC, "mcd_api.hip"), [])]
     uf = {} if fast else {u: usable_flags(f) for u, f in unit_flags().items()}      # (developer builds: command line / main())
     jobs_l += [(f"mcd_inst_{u}.o", os.path.join(CSRC, "mcd_inst.hip"), [f"-DMCD_INST_UNIT_{u}"] + uf.get(u, [])) for u in units]
+    jobs_l += [("mcd_latent.o", os.path.join(CSRC, "mcd_latent.hip"), [])]      # the MoCoDADlatent kernels (developer builds too)
     todo = [(o, s, f) for o, s, f in jobs_l
             if force or not os.path.exists(os.path.join(obj_dir, o)) or os.path.getmtime(os.path.join(obj_dir, o)) < newest(s)]
     t0 = time.perf_counter()

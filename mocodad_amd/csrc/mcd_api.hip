@@ -1952,4 +1952,7 @@ int mcd_frame_scores(const mcd_frame_cfg_t* c, const float* scores, const int64_
 }
 
 }  // extern "C"
+
+// the MoCoDADlatent entry points (packer + calls; their kernels live in mcd_latent.hip)
+#include "mcd_latent_api.hpp"
 #pragma GCC visibility pop

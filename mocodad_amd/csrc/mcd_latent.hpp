@@ -1,0 +1,64 @@
+// mcd_latent.hpp -- what the host side (mcd_latent_api.hpp, inside mcd_api.hip) and the kernels (mcd_latent_kernel.hpp, inside
+// mcd_latent.hip) of the MoCoDADlatent path share: sizes, the packed denoiser's description, launch parameters, launchers.
+#pragma once
+#include "mcd_device.hpp"
+
+namespace mcd {
+
+constexpr int LAT_MAX_LAYERS = 8;
+constexpr int LAT_MAX_DIM = 128;          // D and every hidden size: a multiple of 16 in 16 .. 128
+constexpr int LAT_NC = 32;                // chains (MFMA columns) a workgroup runs at a time: two n-tiles share every A fragment
+constexpr int LAT_WAVES = 4;
+constexpr int LAT_THREADS = LAT_WAVES * 64;
+constexpr int LAT_HS = LAT_MAX_DIM + 4;   // row stride of the activation buffers (4 x odd: conflict-free ds_read_b128)
+constexpr int LAT_MAX_S = 1024;           // per-sample losses of a workgroup's windows kept in LDS
+constexpr int LAT_DOWN_LAYERS = 7;        // sp1a, sd1.0, sd1.1, sd2.0, sd2.1, sd3.0, sd3.1
+constexpr int LAT_EMB = 400;              // emb_off(7): embedding outputs of the seven down-path layers
+constexpr int LAT_ENC_C = 64;             // unet_down_channels[6] of the latent encoder (mocodad_latent.py:55)
+
+// The denoiser in the packed buffer (offsets in floats).  Layer l: out = act(W' h + b') + (W_c e + b_c), act = ReLU behind the
+// folded BatchNorm1d for all but the last layer, e = pos_encoding(i) + cond_emb.  Fragments: pack_gemm_frags order of
+// [W_c | W'] (M = out, K = 16 + in): k-group 0 is the conditioning product, accumulated apart because the ReLU sits between.
+struct LatentNet {
+    int D, n_layers;
+    int in[LAT_MAX_LAYERS], out[LAT_MAX_LAYERS];
+    int wp[LAT_MAX_LAYERS], bias[LAT_MAX_LAYERS], cbias[LAT_MAX_LAYERS];
+};
+
+struct LatentChainParams {
+    const float* wbuf;
+    LatentNet net;
+    const float* cond;        // (B,16); mode 1: (N,16)
+    const float* z0;          // (B,D)
+    const float* noise;       // parity mode: (S, max(ns-1,1), B, D); null: in-kernel Philox
+    const float* step_table;  // (ns + 1, 4 + 16)
+    const float* x_in;        // mode 1: (N,D)
+    float* eps_out;           // mode 1: (N,D)
+    float* loss_agg;          // (B,) or null
+    float* loss_all;          // (B,S) or null
+    float* latent_all;        // (B,S,D) or null
+    float* latent_code;       // (B,D) or null
+    unsigned long long seed;
+    long long first_window;
+    int B, S, ns, wpg;        // wpg: windows per workgroup (all their samples)
+    int mode;                 // 0: chains; 1: one denoiser pass at step_single for B rows
+    int step_single, loss_fn, aggr;
+    float aggr_q;
+};
+
+__host__ __device__ inline int latent_chain_lds_floats(int D, int chains_per_wg) {
+    // HA | HB | X | Z0 | E | CE | RED | column tables | per-sample losses
+    return 2 * LAT_NC * LAT_HS + 2 * LAT_NC * (D + 4) + LAT_NC * 20 + LAT_NC * 16 + LAT_NC * 8 + 2 * LAT_NC + chains_per_wg;
+}
+
+// words of the packed buffer's offset table (mcd_device.hpp) that hold to_time_dim's weight / bias
+constexpr int TAB_LAT_LW = 100, TAB_LAT_LB = 101;
+
+// launchers (mcd_latent.hip holds the kernels; mcd_api.hip only calls these)
+bool latent_encode_has_kernel(int t);
+int launch_latent_encode(int t, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi, int seg_len,
+                         const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st);
+int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
+int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
+
+}  // namespace mcd

@@ -1,0 +1,324 @@
+// mcd_latent_api.hpp — host side of the MoCoDADlatent entry points (include/mocodad_hip.h): the packer and the calls around the
+// launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose packing helpers (TensorMap, fold_conv_bn, pack_mix_mfma,
+// pack_gemm_frags, Builder) it shares; it holds no device code.
+#pragma once
+#include "mcd_latent.hpp"
+
+struct mcd_latent_weights {
+    mcd_model_cfg_t cfg;
+    int device;
+    float* dbuf;
+    size_t n_floats;
+    mcd::LatentNet net;
+};
+
+namespace {
+
+using namespace mcd;
+
+// Linear (out,in) + bias, optionally followed by an eval-mode BatchNorm1d (eps 1e-5): W' = s W, b' = s (b - mu) + beta, in double
+bool fold_linear_bn(TensorMap& tm, const std::string& lin, const std::string& bn, int out, int in, Folded& f) {
+    const float* w = tm.get(lin + ".weight", (int64_t)out * in);
+    const float* b = tm.get(lin + ".bias", out);
+    if (!w || !b) return false;
+    f.w.resize((size_t)out * in); f.b.resize(out);
+    const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
+    if (!bn.empty()) {
+        g = tm.get(bn + ".weight", out); be = tm.get(bn + ".bias", out);
+        mu = tm.get(bn + ".running_mean", out); var = tm.get(bn + ".running_var", out);
+        if (!g || !be || !mu || !var) return false;
+    }
+    for (int o = 0; o < out; ++o) {
+        const double s = g ? (double)g[o] / sqrt((double)var[o] + 1e-5) : 1.0;
+        for (int i = 0; i < in; ++i) f.w[(size_t)o * in + i] = s * (double)w[(size_t)o * in + i];
+        f.b[o] = g ? s * ((double)b[o] - (double)mu[o]) + (double)be[o] : (double)b[o];
+    }
+    return true;
+}
+
+bool latent_dim_ok(int d) { return d >= 16 && d <= LAT_MAX_DIM && d % 16 == 0; }
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+int64_t lat_ws_cond_bytes(int64_t B) { return (B * EDIM * 4 + 255) / 256 * 256; }
+int64_t lat_ws_z0_bytes(int64_t B, int D) { return (B * D * 4 + 255) / 256 * 256; }
+
+int latent_view(const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view, DataView& dv) {
+    memset(&dv, 0, sizeof(dv));
+    dv.data = data;
+    if (view) {
+        if (view->trans && !view->affine) return fail(MCD_EINVAL, "window view: trans given without an affine table");
+        dv.base = reinterpret_cast<const long long*>(view->base); dv.sc = view->stride_c; dv.st = view->stride_t;
+        dv.trans = view->trans; dv.aff = view->affine;
+        if (!view->base) { dv.sc = (long long)cfg->seg_len * 17; dv.st = 17; }
+    }
+    return MCD_OK;
+}
+
+int latent_frames(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, FrameIdx& cond_fi, FrameIdx& fi) {
+    if (cfg->n_corrupt != w->cfg.t_unet || cfg->n_cond != w->cfg.t_cond) return fail(MCD_EINVAL, "frame split does not match the packed model (t_unet / t_cond)");
+    if (cfg->n_cond + cfg->n_corrupt != cfg->seg_len || cfg->seg_len > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "cond/corrupt index lists do not partition seg_len");
+    memset(&cond_fi, 0, sizeof(cond_fi));
+    memset(&fi, 0, sizeof(fi));
+    for (int k = 0; k < cfg->n_cond; ++k) {
+        if (cfg->cond_idx[k] < 0 || cfg->cond_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "cond_idx outside [0, seg_len)");
+        cond_fi.idx[k] = cfg->cond_idx[k];
+    }
+    for (int k = 0; k < cfg->n_corrupt; ++k) {
+        if (cfg->corrupt_idx[k] < 0 || cfg->corrupt_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "corrupt_idx outside [0, seg_len)");
+        fi.idx[k] = cfg->corrupt_idx[k];
+    }
+    return MCD_OK;
+}
+
+int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                       const float* step_table, float* cond_out, float* z0_out, hipStream_t st) {
+    DataView dv;
+    int rc = latent_view(cfg, data, view, dv);
+    if (rc != MCD_OK) return rc;
+    FrameIdx cond_fi, fi;
+    rc = latent_frames(w, cfg, cond_fi, fi);
+    if (rc != MCD_OK) return rc;
+    // row ns of the table: the constant time step -1 the encoder is given (mocodad_latent.py:95)
+    const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
+    return launch_latent_encode(w->cfg.t_unet, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D, cfg->n_windows, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* lcfg,
+                            int32_t device, mcd_latent_weights_t** out) {
+    if (!tensors || !cfg || !lcfg || !out) return fail(MCD_EINVAL, "null argument");
+    if (cfg->num_coords != C0) return fail(MCD_EUNSUPPORTED, "num_coords must be 2");
+    if (cfg->n_joints != 17) return fail(MCD_EUNSUPPORTED, "n_joints must be 17 (the reference U-Net hard-wires 17/12/10 joints)");
+    if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
+    if (cfg->strategy != MCD_STRATEGY_INJECT) return fail(MCD_EINVAL, "the latent model conditions by 'inject' only (mocodad_latent.py:32)");
+    const int T = cfg->t_unet;
+    if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
+        return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
+    if (!latent_encode_has_kernel(T) || cfg->t_cond != T)
+        return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
+                                      " condition frames (instantiated: 3 + 3)");
+    if (cfg->cond_layers != 4 || cfg->cond_channels[0] != 32 || cfg->cond_channels[1] != 16 || cfg->cond_channels[2] != 32 || cfg->cond_channels[3] != 32)
+        return fail(MCD_EUNSUPPORTED, "the latent encode launch runs the shipped condition encoder only (channels [32,16,32], h_dim 32)");
+    const int D = lcfg->latent_dim, NL = lcfg->n_layers;
+    if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
+    if (NL < 1 || NL > LAT_MAX_LAYERS) return fail(MCD_EUNSUPPORTED, "the denoiser has " + std::to_string(NL) + " layers: 1.." + std::to_string(LAT_MAX_LAYERS) + " are supported");
+    for (int l = 0; l < NL; ++l)
+        if (!latent_dim_ok(lcfg->hidden[l])) return fail(MCD_EUNSUPPORTED, "denoiser hidden size " + std::to_string(lcfg->hidden[l]) + ": must be a multiple of 16 in 16..128");
+    if (lcfg->hidden[NL - 1] != D) return fail(MCD_EINVAL, "the last denoiser hidden size must equal latent_embedding_dim (it predicts the latent's noise)");
+
+    TensorMap tm;
+    for (int i = 0; i < n_tensors; ++i) tm.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
+    Builder B;
+    B.alloc(TAB_FLOATS);
+    std::vector<int> tab(TAB_FLOATS, 0);
+    auto set_f = [&](int idx, float v) { memcpy(&tab[idx], &v, sizeof(float)); };
+
+    // ---- the U-Net's down path (stsae_unet.py:182-219) with its embedding Linears
+    static const char* names[LAT_DOWN_LAYERS] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1", "st_gcnnsd3.0", "st_gcnnsd3.1"};
+    const int we_off = B.alloc((size_t)LAT_EMB * EDIM), be_off = B.alloc(LAT_EMB);
+    for (int l = 0; l < LAT_DOWN_LAYERS; ++l) {
+        const LDesc Dl = layer_desc(l);
+        const std::string p = std::string("model.") + names[l];
+        int tq = 0, am = 0;
+        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
+        const int cin = l == 0 ? C0 : Dl.cin, cinp = Dl.cin;
+        Folded ft, fr;
+        if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", Dl.cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
+        if (Dl.res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", Dl.cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
+        const float* sl = tm.get(p + ".prelu.weight", 1);
+        const float* we = tm.get(p + ".emb_layer.1.weight", (int64_t)Dl.cout * EDIM);
+        const float* be = tm.get(p + ".emb_layer.1.bias", Dl.cout);
+        if (!sl || !we || !be) return fail(MCD_EMISSING, tm.missing);
+        memcpy(&B.buf[we_off + (size_t)emb_off(l) * EDIM], we, sizeof(float) * Dl.cout * EDIM);
+        memcpy(&B.buf[be_off + emb_off(l)], be, sizeof(float) * Dl.cout);
+        const int bias = B.alloc(ceil16(Dl.cout));
+        for (int o = 0; o < Dl.cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (Dl.res ? fr.b[o] : 0.0));
+        // every layer mix-first here: [W_t' | W_r'] (layer 6 too, as in cond_unet_kernel)
+        const int wp = pack_gemm_frags(B, ceil16(Dl.cout), cinp * (Dl.res ? 2 : 1), [&](int r, int k) -> double {
+            const bool second = k >= cinp;
+            const int kk = second ? k - cinp : k;
+            if (r >= Dl.cout || kk >= cin) return 0.0;
+            return second ? fr.w[(size_t)r * cin + kk] : ft.w[(size_t)r * cin + kk];
+        });
+        tab[l * F_STRIDE + F_TQ] = tq; tab[l * F_STRIDE + F_AM] = am; tab[l * F_STRIDE + F_WP] = wp; tab[l * F_STRIDE + F_BIAS] = bias;
+        set_f(l * F_STRIDE + F_SLOPE, sl[0]);
+    }
+    tab[TAB_WE] = we_off; tab[TAB_BE] = be_off;
+    static const char* rs_names[2] = {"down1", "down2"};
+    static const int rs_in[2] = {17, 12}, rs_out[2] = {12, 10};
+    for (int r = 0; r < 2; ++r) {
+        Folded f;
+        const std::string p = std::string("model.") + rs_names[r];
+        if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", rs_out[r], rs_in[r], f)) return fail(MCD_EMISSING, tm.missing);
+        const int vin = rs_in[r], vout = rs_out[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
+        const int wf = B.alloc((size_t)MTr * KS * 64), bo = B.alloc(32);
+        for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
+            const int vo = mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
+            B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
+        }
+        for (int vo = 0; vo < vout; ++vo) B.buf[bo + vo] = (float)f.b[vo];
+        tab[TAB_RSW + r] = wf; tab[TAB_RSB + r] = bo;
+    }
+    {
+        const int64_t F = (int64_t)LAT_ENC_C * T * 10;
+        const float* lw = tm.get("model.to_time_dim.weight", F * D);
+        const float* lb = tm.get("model.to_time_dim.bias", D);
+        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
+        tab[TAB_LAT_LW] = B.alloc(F * D); memcpy(&B.buf[tab[TAB_LAT_LW]], lw, sizeof(float) * F * D);
+        tab[TAB_LAT_LB] = B.alloc(D); memcpy(&B.buf[tab[TAB_LAT_LB]], lb, sizeof(float) * D);
+    }
+    // ---- the condition encoder in cond_fast_body's table (the AE decoder is dead work at evaluation and is not read)
+    {
+        const int Tc = cfg->t_cond;
+        int cinr = C0;
+        for (int l = 0; l < 4; ++l) {
+            const int cout = cfg->cond_channels[l], cinp = l == 0 ? 16 : cinr;
+            const std::string p = "condition_encoder.encoder.model_layers." + std::to_string(l);
+            Folded ft, fr;
+            const bool res = cinr != cout;
+            if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", cout, cinr, ft)) return fail(MCD_EMISSING, tm.missing);
+            if (res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", cout, cinr, fr)) return fail(MCD_EMISSING, tm.missing);
+            const float* sl = tm.get(p + ".prelu.weight", 1);
+            if (!sl) return fail(MCD_EMISSING, tm.missing);
+            int tq = 0, am = 0;
+            if (!pack_mix_mfma(tm, p, Tc, 17, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
+            const int wp = pack_gemm_frags(B, ceil16(cout), cinp * (res ? 2 : 1), [&](int r, int k) -> double {
+                const bool second = k >= cinp;
+                const int kk = second ? k - cinp : k;
+                if (r >= cout || kk >= cinr) return 0.0;
+                return second ? fr.w[(size_t)r * cinr + kk] : ft.w[(size_t)r * cinr + kk];
+            });
+            const int bias = B.alloc(ceil16(cout));
+            for (int o = 0; o < cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
+            const int t0 = TABC + l * F_STRIDE;
+            tab[t0 + F_TQ] = tq; tab[t0 + F_AM] = am; tab[t0 + F_WP] = wp; tab[t0 + F_BIAS] = bias;
+            set_f(t0 + F_SLOPE, sl[0]);
+            cinr = cout;
+        }
+        const int64_t F = (int64_t)cinr * Tc * 17;
+        const float* lw = tm.get("condition_encoder.btlnk.weight", F * EDIM);
+        const float* lb = tm.get("condition_encoder.btlnk.bias", EDIM);
+        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
+        tab[TABC + TABC_LW] = B.alloc(F * EDIM); memcpy(&B.buf[tab[TABC + TABC_LW]], lw, sizeof(float) * F * EDIM);
+        tab[TABC + TABC_LB] = B.alloc(EDIM); memcpy(&B.buf[tab[TABC + TABC_LB]], lb, sizeof(float) * EDIM);
+    }
+    // ---- the denoiser (components.py:228-241): Linear -> BatchNorm1d -> ReLU, the last layer a plain Linear; cond_layers apart
+    LatentNet N;
+    memset(&N, 0, sizeof(N));
+    N.D = D; N.n_layers = NL;
+    for (int l = 0; l < NL; ++l) {
+        const int in = l == 0 ? D : lcfg->hidden[l - 1], outc = lcfg->hidden[l];
+        const bool last = l == NL - 1;
+        const std::string p = "denoiser.net." + std::to_string(l), pc = "denoiser.cond_layers." + std::to_string(l);
+        Folded f, fc;
+        if (!fold_linear_bn(tm, last ? p : p + ".0", last ? "" : p + ".1", outc, in, f)) return fail(MCD_EMISSING, tm.missing);
+        if (!fold_linear_bn(tm, pc, "", outc, EDIM, fc)) return fail(MCD_EMISSING, tm.missing);
+        N.in[l] = in; N.out[l] = outc;
+        N.wp[l] = pack_gemm_frags(B, outc, EDIM + in, [&](int r, int k) -> double {
+            return k < EDIM ? fc.w[(size_t)r * EDIM + k] : f.w[(size_t)r * in + (k - EDIM)];
+        });
+        N.bias[l] = B.alloc(outc);
+        N.cbias[l] = B.alloc(outc);
+        for (int o = 0; o < outc; ++o) { B.buf[N.bias[l] + o] = (float)f.b[o]; B.buf[N.cbias[l] + o] = (float)fc.b[o]; }
+    }
+    memcpy(B.buf.data(), tab.data(), sizeof(int) * TAB_FLOATS);
+
+    int prev_dev = 0;
+    HIP_TRY(hipGetDevice(&prev_dev));
+    HIP_TRY(hipSetDevice(device));
+    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_dev};
+    mcd_latent_weights* w = new mcd_latent_weights();
+    w->cfg = *cfg; w->device = device; w->n_floats = B.buf.size(); w->net = N; w->dbuf = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->dbuf), B.buf.size() * sizeof(float));
+    if (e != hipSuccess) { delete w; return fail(MCD_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    e = hipMemcpy(w->dbuf, B.buf.data(), B.buf.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(w->dbuf); delete w; return fail(MCD_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+    *out = w;
+    return MCD_OK;
+}
+
+void mcd_free_latent_weights(mcd_latent_weights_t* w) {
+    if (!w) return;
+    if (w->dbuf) (void)hipFree(w->dbuf);
+    delete w;
+}
+
+int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows) {
+    if (!w || n_windows <= 0) return 0;
+    return lat_ws_cond_bytes(n_windows) + lat_ws_z0_bytes(n_windows, w->net.D);
+}
+
+int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                      const float* step_table, float* cond_emb_out, float* z0_out, void* stream) {
+    if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
+    if (cfg->n_windows <= 0) return MCD_OK;
+    if (!data || !step_table || !cond_emb_out || !z0_out) return fail(MCD_EINVAL, "null argument");
+    if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
+    return latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, (hipStream_t)stream);
+}
+
+int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
+                       int32_t n_rows, float* eps_out, void* stream) {
+    if (!w) return fail(MCD_EINVAL, "null argument");
+    if (n_rows <= 0) return MCD_OK;
+    if (!x || !cond || !step_table || !eps_out) return fail(MCD_EINVAL, "null argument");
+    if (t < 0) return fail(MCD_EINVAL, "t must be >= 0 (step_table needs at least t + 1 rows)");
+    if (!aligned16(x) || !aligned16(eps_out)) return fail(MCD_EINVAL, "x and eps_out must be 16-byte aligned");
+    LatentChainParams P;
+    memset(&P, 0, sizeof(P));
+    P.wbuf = w->dbuf; P.net = w->net; P.cond = cond; P.step_table = step_table; P.x_in = x; P.eps_out = eps_out;
+    P.B = n_rows; P.S = 1; P.ns = t + 1; P.wpg = LAT_NC; P.mode = 1; P.step_single = t;
+    return launch_latent_chain(P, (hipStream_t)stream);
+}
+
+int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                     const float* noise, uint64_t seed, int64_t first_window_id, const float* step_table, void* workspace,
+                     int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,
+                     void* stream) {
+    if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
+    const int B = cfg->n_windows, S = cfg->n_samples, D = w->net.D;
+    if (B <= 0) return MCD_OK;
+    if (!data || !step_table || !workspace) return fail(MCD_EINVAL, "null argument (the workspace of mcd_latent_workspace_bytes is required)");
+    if (aggregation == MCD_AGGR_ALL) {
+        if (!loss_all) return fail(MCD_EINVAL, "null argument");
+    } else {
+        if (!loss_agg) return fail(MCD_EINVAL, "null argument");
+        if (aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST && aggregation != MCD_AGGR_MEAN && aggregation != MCD_AGGR_MEDIAN &&
+            aggregation != MCD_AGGR_QUANTILE)
+            return fail(MCD_EINVAL, "mcd_latent_score aggregates losses (best, worst, mean, median, quantile)");
+        if (aggregation == MCD_AGGR_QUANTILE && !(quantile >= 0.f && quantile <= 1.f)) return fail(MCD_EINVAL, "quantile must be in [0, 1]");
+    }
+    if (S < 1 || cfg->noise_steps < 2) return fail(MCD_EINVAL, "need n_samples >= 1 and noise_steps >= 2");
+    if (S > LAT_MAX_S) return fail(MCD_EUNSUPPORTED, "n_samples " + std::to_string(S) + ": at most " + std::to_string(LAT_MAX_S) + " per call");
+    if ((long long)B * S > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x n_samples exceeds 2^31 - 1: score in smaller batches");
+    if (cfg->loss_fn < MCD_LOSS_SMOOTH_L1 || cfg->loss_fn > MCD_LOSS_MSE) return fail(MCD_EINVAL, "unknown loss_fn");
+    if (noise && !aligned16(noise)) return fail(MCD_EINVAL, "noise must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    float* cond = reinterpret_cast<float*>(workspace);
+    float* z0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + lat_ws_cond_bytes(B));
+    int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, st);
+    if (rc != MCD_OK) return rc;
+    LatentChainParams P;
+    memset(&P, 0, sizeof(P));
+    P.wbuf = w->dbuf; P.net = w->net; P.cond = cond; P.z0 = z0; P.noise = noise; P.step_table = step_table;
+    P.loss_agg = aggregation == MCD_AGGR_ALL ? nullptr : loss_agg; P.loss_all = loss_all; P.latent_all = latent_all; P.latent_code = latent_code;
+    P.seed = seed; P.first_window = first_window_id;
+    P.B = B; P.S = S; P.ns = cfg->noise_steps; P.wpg = S >= LAT_NC ? 1 : LAT_NC / S;
+    P.mode = 0; P.loss_fn = cfg->loss_fn; P.aggr = aggregation; P.aggr_q = quantile;
+    return launch_latent_chain(P, st);
+}
+
+int mcd_latent_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
+                            int32_t latent_dim, float* noise_out, void* stream) {
+    if (n_windows <= 0) return MCD_OK;
+    if (!noise_out) return fail(MCD_EINVAL, "null argument");
+    if (n_samples < 1 || noise_steps < 2 || !latent_dim_ok(latent_dim)) return fail(MCD_EINVAL, "bad sizes");
+    if (!aligned16(noise_out)) return fail(MCD_EINVAL, "noise_out must be 16-byte aligned");
+    const int K = noise_steps > 2 ? noise_steps - 1 : 1;
+    return launch_latent_philox(seed, first_window_id, n_windows, n_samples, K, latent_dim, noise_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,330 @@
+// mcd_latent_kernel.hpp — MoCoDADlatent (models/mocodad_latent.py:69-132, stage 'diffusion'): the two launches of a latent
+// scoring call and their test / replay companions.
+//   latent_encode_kernel<T, NB>   condition encoder + the U-Net's down path with embeddings + to_time_dim -> cond_emb (B,16), z0 (B,D)
+//   latent_chain_kernel           every reverse-diffusion chain of the call: S (ns-1) denoiser passes (components.py:203-291) as
+//                                 v_mfma_f32_16x16x4_f32 products with the chains as the N dimension, the DDPM updates, the loss
+//                                 against z0 and the loss-based aggregation over the samples
+//   latent_philox_kernel          the perf mode's draws in the parity layout
+// The stage functions, the LDS plan and the fragment orders are those of mcd_device.hpp / mcd_score_kernel.hpp, included unchanged.
+#pragma once
+#include "mcd_device.hpp"
+#include "mcd_score_kernel.hpp"
+#include "mcd_latent.hpp"
+
+namespace mcd {
+
+__device__ __forceinline__ f32x4 lat_mfma4(const float4 a, const float4 b, f32x4 acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+    return acc;
+}
+
+__global__ __launch_bounds__(LAT_THREADS) void latent_chain_kernel(const LatentChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int D = P.net.D, XS = D + 4, L = P.net.n_layers;
+    const int per_wg = P.mode == 1 ? LAT_NC : P.wpg * P.S;      // chains of this workgroup
+    float* const HA = smem;
+    float* const HB = HA + LAT_NC * LAT_HS;
+    float* const X = HB + LAT_NC * LAT_HS;        // chain state x[col][D]
+    float* const Z0 = X + LAT_NC * XS;            // latent code of the column's window
+    float* const E = Z0 + LAT_NC * XS;            // pos_encoding(i) + cond_emb [col][20]
+    float* const CE = E + LAT_NC * 20;            // cond_emb [col][16]
+    float* const RED = CE + LAT_NC * 16;          // loss partial sums [col][8]
+    int* const COLB = reinterpret_cast<int*>(RED + LAT_NC * 8);      // window (mode 1: row) of a column, -1 = empty
+    int* const COLS = COLB + LAT_NC;                                 // its sample
+    float* const LOSS = reinterpret_cast<float*>(COLS + LAT_NC);     // [window of the workgroup][S]
+    const int tid = threadIdx.x, lane = tid & 63, n16 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int K = P.ns > 2 ? P.ns - 1 : 1;
+    const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
+    const int i_last = P.mode == 1 ? P.step_single : 1;
+    const int n_chunks = (per_wg + LAT_NC - 1) / LAT_NC;
+
+    for (int chunk = 0; chunk < n_chunks; ++chunk) {
+        // ---- the columns of this pass: chain q of the workgroup = (window q / S, sample q % S); mode 1: row
+        if (tid < LAT_NC) {
+            const int q = chunk * LAT_NC + tid;
+            int b = -1, s = 0;
+            if (P.mode == 1) {
+                b = blockIdx.x * LAT_NC + tid;
+                if (b >= P.B) b = -1;
+            } else if (q < per_wg) {
+                b = blockIdx.x * P.wpg + q / P.S;
+                s = q % P.S;
+                if (b >= P.B) b = -1;
+            }
+            COLB[tid] = b;
+            COLS[tid] = s;
+        }
+        __syncthreads();
+        for (int u = tid; u < LAT_NC * 16; u += LAT_THREADS) {
+            const int col = u >> 4, b = COLB[col];
+            CE[u] = b >= 0 ? P.cond[(size_t)b * EDIM + (u & 15)] : 0.f;
+        }
+        // x_T (slot 0 of the noise layout) or the given rows; z0.  One Philox call = the four normals of an element group.
+        for (int u = tid; u < LAT_NC * (D >> 2); u += LAT_THREADS) {
+            const int col = u / (D >> 2), d0 = (u % (D >> 2)) * 4, b = COLB[col], s = COLS[col];
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            float4 zc = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (b >= 0) {
+                if (P.mode == 1) {
+                    const float4 v = load_global4(P.x_in + (size_t)b * D + d0);
+                    z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+                } else {
+                    if (P.noise) {
+                        const float4 v = load_global4(P.noise + ((size_t)(s * K) * P.B + b) * D + d0);
+                        z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+                    } else {
+                        philox_normal4(P.seed, (unsigned)(d0 >> 2), 0u, (unsigned)s, (unsigned)(P.first_window + b), z);
+                    }
+                    zc = load_global4(P.z0 + (size_t)b * D + d0);
+                }
+            }
+            lds_store4(lds_addr(X + col * XS + d0), z[0], z[1], z[2], z[3]);
+            lds_store4(lds_addr(Z0 + col * XS + d0), zc.x, zc.y, zc.z, zc.w);
+        }
+        __syncthreads();
+
+        for (int step = i_first; step >= i_last; --step) {
+            const float* srow = P.step_table + step * (4 + EDIM);
+            for (int u = tid; u < LAT_NC * 16; u += LAT_THREADS) E[(u >> 4) * 20 + (u & 15)] = srow[4 + (u & 15)] + CE[u];
+            if (L == 1)      // the only layer reads x while its own epilogue rewrites it: from a copy
+                for (int u = tid; u < LAT_NC * D; u += LAT_THREADS) HB[(u / D) * LAT_HS + u % D] = X[(u / D) * XS + u % D];
+            __syncthreads();
+            const float t0 = srow[0], t1 = srow[1], t2 = srow[2];
+            for (int l = 0; l < L; ++l) {
+                const bool last = l == L - 1;
+                const float* in = l == 0 ? (L == 1 ? HB : X) : ((l & 1) ? HA : HB);
+                const int in_s = (l == 0 && L > 1) ? XS : LAT_HS;
+                float* out = (l & 1) ? HB : HA;
+                const int KQh = P.net.in[l] >> 4, KQ = KQh + 1, MT = P.net.out[l] >> 4;
+                const float* wb = P.wbuf;
+                const unsigned in_a = lds_addr(in) + 4u * (unsigned)(n16 * in_s + 4 * g);
+                const unsigned e_a = lds_addr(E) + 4u * (unsigned)(n16 * 20 + 4 * g);
+                for (int mt = wave; mt < MT; mt += LAT_WAVES) {
+                    const float* wp = wb + P.net.wp[l] + ((size_t)mt * KQ * 64 + lane) * 4;
+                    float4 a[LAT_MAX_DIM / 16 + 1];
+#pragma unroll
+                    for (int k = 0; k <= LAT_MAX_DIM / 16; ++k) a[k] = k < KQ ? load_global4(wp + k * 256) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const int c0 = mt * 16 + 4 * g;      // the lane's four output rows
+                    const float4 b1 = load_global4(wb + P.net.bias[l] + c0), bc = load_global4(wb + P.net.cbias[l] + c0);
+                    f32x4 acc[2], accc[2];
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        acc[nt] = f32x4{b1.x, b1.y, b1.z, b1.w};
+                        accc[nt] = lat_mfma4(a[0], lds_load4(e_a + 4u * (unsigned)(nt * 16 * 20)), f32x4{bc.x, bc.y, bc.z, bc.w});
+                    }
+#pragma unroll
+                    for (int k = 1; k <= LAT_MAX_DIM / 16; ++k) {
+                        if (k <= KQh) {
+#pragma unroll
+                            for (int nt = 0; nt < 2; ++nt)
+                                acc[nt] = lat_mfma4(a[k], lds_load4(in_a + 4u * (unsigned)(nt * 16 * in_s + (k - 1) * 16)), acc[nt]);
+                        }
+                    }
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        const int col = nt * 16 + n16;
+                        f32x4 v = acc[nt];
+                        if (!last) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+                        v += accc[nt];
+                        if (!last) {
+                            lds_store4(lds_addr(out + col * LAT_HS + c0), v[0], v[1], v[2], v[3]);
+                        } else if (P.mode == 1) {
+                            const int b = COLB[col];
+                            if (b >= 0) store_global4(P.eps_out + (size_t)b * D + c0, make_float4(v[0], v[1], v[2], v[3]));
+                        } else {
+                            // DDPM update (mocodad_latent.py:117-123); z = 0 at step 1.  The lane's four rows are one element group.
+                            const int b = COLB[col], s = COLS[col];
+                            float z[4] = {0.f, 0.f, 0.f, 0.f};
+                            if (step > 1 && b >= 0) {
+                                const int k = P.ns - step;
+                                if (P.noise) {
+                                    const float4 zv = load_global4(P.noise + ((size_t)(s * K + k) * P.B + b) * D + c0);
+                                    z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+                                } else {
+                                    philox_normal4(P.seed, (unsigned)(c0 >> 2), (unsigned)k, (unsigned)s, (unsigned)(P.first_window + b), z);
+                                }
+                            }
+                            const unsigned xa = lds_addr(X + col * XS + c0);
+                            const float4 x = lds_load4(xa);
+                            lds_store4(xa, t0 * (x.x - t1 * v[0]) + t2 * z[0], t0 * (x.y - t1 * v[1]) + t2 * z[1],
+                                       t0 * (x.z - t1 * v[2]) + t2 * z[2], t0 * (x.w - t1 * v[3]) + t2 * z[3]);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (P.mode == 1) return;
+        // ---- loss of every chain of the pass against its window's latent code: mean over D (mocodad.py:484)
+        {
+            const int col = tid >> 3, part = tid & 7;
+            float sum = 0.f;
+            for (int d = part; d < D; d += 8) sum += loss_elem(X[col * XS + d], Z0[col * XS + d], P.loss_fn);
+            RED[tid] = sum;
+        }
+        __syncthreads();
+        if (tid < LAT_NC && COLB[tid] >= 0) {
+            float sum = 0.f;
+#pragma unroll
+            for (int p = 0; p < 8; ++p) sum += RED[tid * 8 + p];
+            const float loss = sum / (float)D;
+            LOSS[chunk * LAT_NC + tid] = loss;
+            if (P.loss_all) P.loss_all[(size_t)COLB[tid] * P.S + COLS[tid]] = loss;
+        }
+        if (P.latent_all || P.latent_code) {
+            for (int u = tid; u < LAT_NC * D; u += LAT_THREADS) {
+                const int col = u / D, d = u % D, b = COLB[col], s = COLS[col];
+                if (b < 0) continue;
+                if (P.latent_all) P.latent_all[((size_t)b * P.S + s) * D + d] = X[col * XS + d];
+                if (P.latent_code && s == 0) P.latent_code[(size_t)b * D + d] = Z0[col * XS + d];
+            }
+        }
+        __syncthreads();
+    }
+    // ---- aggregation over the samples of every window of the workgroup (mocodad.py:489-516), as aggregate_kernel does it
+    if (P.loss_agg && tid < P.wpg) {
+        const int b = blockIdx.x * P.wpg + tid;
+        if (b < P.B) P.loss_agg[b] = aggregate_losses(LOSS + tid * P.S, P.S, P.aggr, P.aggr_q);
+    }
+}
+
+// The draws of the perf mode in the parity layout (S, max(ns-1,1), B, D): slot 0 = x_T, slot k = z of step ns - k.
+__global__ __launch_bounds__(256) void latent_philox_kernel(unsigned long long seed, long long first_window, int B, int S, int K, int D,
+                                                            float* __restrict__ out) {
+    const long long n = (long long)S * K * B * (D >> 2);
+    const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (u >= n) return;
+    const int grp = (int)(u % (D >> 2));
+    const int b = (int)((u / (D >> 2)) % B);
+    const int k = (int)((u / ((long long)(D >> 2) * B)) % K);
+    const int s = (int)(u / ((long long)(D >> 2) * B * K));
+    float z[4];
+    philox_normal4(seed, (unsigned)grp, (unsigned)k, (unsigned)s, (unsigned)(first_window + b), z);
+    store_global4(out + (((size_t)(s * K + k) * B + b) * D + grp * 4), make_float4(z[0], z[1], z[2], z[3]));
+}
+
+// ------------------------------------------------------------------------------------------------
+// Encode launch: windows b0 .. b0 + NB - 1 of a workgroup.  cond_fast_body (the shipped condition encoder) -> cond_emb; the
+// embeddings Linear(SiLU(pos_encoding(-1) + cond_emb)) of the seven down-path layers; the layers on Plan<T, NB> as in
+// cond_unet_kernel, with the embedding added in the GEMM epilogue as in score_kernel; to_time_dim over the (c,t,v) flattening.
+// Table of the packed buffer: layers 0 .. 6 at l * F_STRIDE (all mix-first [W_t' | W_r']), TAB_WE / TAB_BE = W_e [400][16] / b_e,
+// TAB_RSW / TAB_RSB + 0, 1 = down1 / down2 (non-capturing fragments), TAB_LAT_LW / TAB_LAT_LB = to_time_dim; the condition
+// encoder's table at TABC as cond_fast_body expects it.
+// ------------------------------------------------------------------------------------------------
+
+template <int T, int NB>
+struct LatentEncLds {
+    using PL = Plan<T, NB>;
+    static constexpr int P17 = ceil16(NB * T * 17);
+    static constexpr int H_OFF = 2 * PL::s128;                   // [P10][68] output of the last layer behind its (in, z)
+    static constexpr int WORK = cmax(cmax(PL::R, H_OFF + PL::P10 * 68), P17 * (2 * 20 + 2 * 36));
+    static constexpr int EMB = NB * EMB_STRIDE;
+    static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
+};
+
+template <int T, int NB>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
+                                                                    const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
+                                                                    float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
+    using PL = Plan<T, NB>;
+    using LD = LatentEncLds<T, NB>;
+    constexpr int TV17 = T * 17, COLS17 = NB * TV17, TV10 = T * 10;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const RG = smem;
+    float* const EMB = smem + LD::WORK;
+    float* const CE = EMB + LD::EMB;
+    float* const SEN = CE + NB * EDIM;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b0 = blockIdx.x * NB;
+    Prof prof;
+    prof.off();
+    for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+    __syncthreads();
+    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
+    __syncthreads();
+    const float* wb = wbuf;
+    if (tid < NB * EDIM) {
+        const float e = pe_row[tid % EDIM] + CE[tid];
+        SEN[tid] = e / (1.f + expf(-e));
+    }
+    for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
+    __syncthreads();
+    for (int u = tid; u < COLS17 * C0; u += NTHREADS) {
+        const int c = u % C0, col = u / C0;
+        const int n = col / TV17, t = (col / 17) % T, v = col % 17;
+        const int b = b0 + n < B ? b0 + n : B - 1;
+        RG[PL::L0_in + col * 20 + c] = load_coord(dv, b, c, fi.idx[t], v, seg_len);
+    }
+    {
+        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
+        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
+        for (int o = tid; o < LAT_EMB; o += NTHREADS) {
+            float w[EDIM];
+#pragma unroll
+            for (int k = 0; k < EDIM; ++k) w[k] = we[o * EDIM + k];
+            const float bo = be[o];
+#pragma unroll
+            for (int n = 0; n < NB; ++n) {
+                float a = bo;
+#pragma unroll
+                for (int k = 0; k < EDIM; ++k) a = fmaf(w[k], SEN[n * EDIM + k], a);
+                EMB[n * EMB_STRIDE + o] = a;
+            }
+        }
+    }
+    __syncthreads();
+    float nosk[1] = {0.f};
+    layer_generic<16, 16, 17, true, true, T, NB>(wb, layer_w(wb, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, EMB + emb_off(0), wave, lane, prof, 0);
+    layer_generic<16, 32, 17, true, true, T, NB>(wb, layer_w(wb, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, EMB + emb_off(1), wave, lane, prof, 0);
+    layer_generic<32, 32, 17, false, true, T, NB>(wb, layer_w(wb, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, EMB + emb_off(2), wave, lane, prof, 0);
+    {
+        RsCoef<32, 17, 12, T, NB, false> rc;
+        rc.load(wb + tab_i(wb, TAB_RSW + 0), wb + tab_i(wb, TAB_RSB + 0), lane);
+        resample_stage<32, 17, 12, T, NB, false, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, nosk, wave, lane);
+        __syncthreads();
+    }
+    layer_generic<32, 64, 12, true, true, T, NB>(wb, layer_w(wb, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, EMB + emb_off(3), wave, lane, prof, 0);
+    layer_generic<64, 64, 12, false, true, T, NB>(wb, layer_w(wb, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, EMB + emb_off(4), wave, lane, prof, 0);
+    {
+        RsCoef<64, 12, 10, T, NB, false> rc;
+        rc.load(wb + tab_i(wb, TAB_RSW + 1), wb + tab_i(wb, TAB_RSB + 1), lane);
+        resample_stage<64, 12, 10, T, NB, false, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, nosk, wave, lane);
+        __syncthreads();
+    }
+    layer_generic<64, 128, 10, true, true, T, NB>(wb, layer_w(wb, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, EMB + emb_off(5), wave, lane, prof, 0);
+    layer_generic<128, 64, 10, true, true, T, NB>(wb, layer_w(wb, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6), wave, lane, prof, 0);
+    // to_time_dim: z0[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v.  thread = (j, part of 16), every window of the workgroup
+    constexpr int F = LAT_ENC_C * TV10;
+    const float* H = RG + LD::H_OFF;
+    gfloat* W = as_global(wb + tab_i(wb, TAB_LAT_LW));
+    gfloat* bb = as_global(wb + tab_i(wb, TAB_LAT_LB));
+    for (int u = tid; u < D * 16; u += NTHREADS) {
+        const int part = u & 15, jo = u >> 4;
+        float a[NB];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) a[n] = 0.f;
+        constexpr int NT16 = (TV10 + 15) / 16;
+#pragma unroll 4
+        for (int c = 0; c < LAT_ENC_C; ++c) {
+            float wv[NT16];
+#pragma unroll
+            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV10) ? W[(size_t)jo * F + c * TV10 + i * 16 + part] : 0.f;
+#pragma unroll
+            for (int n = 0; n < NB; ++n)
+#pragma unroll
+                for (int i = 0; i < NT16; ++i) a[n] = fmaf(wv[i], (i * 16 + part < TV10) ? H[(n * TV10 + i * 16 + part) * 68 + c] : 0.f, a[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            const float r = row16_sum(a[n]);
+            if (part == 0 && b0 + n < B) z0_out[(size_t)(b0 + n) * D + jo] = r + bb[jo];
+        }
+    }
+}
+
+}  // namespace mcd

@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .utils.diffusion_utils import step_table
+from .utils.diffusion_utils import latent_step_table, step_table
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -344,6 +344,185 @@ class HipScorer:
         with torch.cuda.device(self.device):
             _lib.check(self.L.mcd_scatter_max(_ptr(scores), _ptr(frames), _ptr(row), scores.numel(), frames.shape[1],
                                               n_rows, n_frames, _ptr(out), _stream()))
+        return out
+
+
+def _pack_tensors(state_dict):
+    """state_dict -> (ctypes array of mcd_tensor_t, count, host copies to keep alive during the call)."""
+    keep = []
+    arr = (_lib.Tensor * len(state_dict))()
+    n = 0
+    for k, v in state_dict.items():
+        if not torch.is_tensor(v) or not v.dtype.is_floating_point:
+            continue
+        h = v.detach().to("cpu", torch.float32).contiguous()
+        keep.append(h)
+        arr[n].name = k.encode()
+        arr[n].data = h.data_ptr()
+        arr[n].numel = h.numel()
+        n += 1
+    return arr, n, keep
+
+
+class LatentScorer:
+    """One packed MoCoDADlatent model (stage 'diffusion') on one GPU: the mcd_latent_* entry points.
+
+    state_dict: the reference's keys ('model.*' without an up path, 'condition_encoder.*', 'denoiser.*').
+    latent_dim / hidden_sizes: latent_embedding_dim and the denoiser's layer widths (the last equals latent_dim)."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
+                 cond_channels: Sequence[int], latent_dim: int, hidden_sizes: Sequence[int], num_coords: int = 2, n_joints: int = 17,
+                 emb_dim: int = 16, device=None):
+        self.L = _lib.lib()
+        self.seg_len = int(seg_len)
+        self.cond_idx = [int(i) for i in cond_idx]
+        self.corrupt_idx = [int(i) for i in corrupt_idx]
+        self.num_coords, self.n_joints, self.emb_dim = num_coords, n_joints, emb_dim
+        self.latent_dim = int(latent_dim)
+        self.hidden_sizes = [int(h) for h in hidden_sizes]
+        self._tables: Dict[int, torch.Tensor] = {}
+        self._ws: Dict[int, torch.Tensor] = {}
+        self._h = None
+        cfg = _lib.ModelCfg()
+        cfg.num_coords, cfg.n_joints, cfg.t_unet, cfg.t_cond = num_coords, n_joints, len(self.corrupt_idx), len(self.cond_idx)
+        cfg.emb_dim, cfg.strategy = emb_dim, _lib.STRATEGY["inject"]
+        if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
+            raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
+        cfg.cond_layers = len(cond_channels)
+        for i, c in enumerate(cond_channels):
+            cfg.cond_channels[i] = int(c)
+        lcfg = _lib.LatentCfg()
+        lcfg.latent_dim, lcfg.n_layers = self.latent_dim, len(self.hidden_sizes)
+        for i, h in enumerate(self.hidden_sizes[:8]):       # (more than 8 layers: the library refuses n_layers)
+            lcfg.hidden[i] = h
+        arr, n, keep = _pack_tensors(state_dict)
+        # sizes and tensor names are checked by the library before it touches a device: those errors need no GPU
+        have_gpu = torch.cuda.is_available()
+        self.device = torch.device(device if device is not None else (f"cuda:{torch.cuda.current_device()}" if have_gpu else "cuda:0"))
+        idx = self.device.index if self.device.index is not None else 0
+        handle = C.c_void_p()
+        _lib.check(self.L.mcd_pack_latent_weights(arr, n, C.byref(cfg), C.byref(lcfg), idx, C.byref(handle)))
+        del keep
+        self._h = handle
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                self.L.mcd_free_latent_weights(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def table(self, noise_steps: int) -> torch.Tensor:
+        t = self._tables.get(noise_steps)
+        if t is None:
+            t = latent_step_table(noise_steps, self.emb_dim).to(self.device)
+            self._tables[noise_steps] = t
+        return t
+
+    def _cfg(self, B: int, S: int, ns: int, loss_fn: str = "smooth_l1") -> "_lib.ScoreCfg":
+        c = _lib.ScoreCfg()
+        c.n_windows, c.n_samples, c.noise_steps, c.seg_len = B, S, ns, self.seg_len
+        c.n_cond, c.n_corrupt = len(self.cond_idx), len(self.corrupt_idx)
+        for i, v in enumerate(self.cond_idx):
+            c.cond_idx[i] = v
+        for i, v in enumerate(self.corrupt_idx):
+            c.corrupt_idx[i] = v
+        c.loss_fn = _lib.LOSS[loss_fn]
+        return c
+
+    def _windows(self, data):
+        """-> (data tensor, WindowView | None, B, keep-alive)"""
+        if hasattr(data, "as_view"):
+            wb = data.to(self.device)
+            if wb.seg_len != self.seg_len:
+                raise ValueError(f"window view has seg_len {wb.seg_len}, model expects {self.seg_len}")
+            view = _lib.WindowView(base=wb.base.data_ptr(), stride_c=wb.stride_c, stride_t=wb.stride_t,
+                                   trans=wb.trans.data_ptr() if wb.trans is not None else None,
+                                   affine=wb.affine.data_ptr() if wb.affine is not None else None, cond_mask=None)
+            return wb.buffer, view, int(wb.base.shape[0]), wb
+        if data.dim() != 4 or tuple(data.shape[1:]) != (self.num_coords, self.seg_len, self.n_joints):
+            raise ValueError(f"data must have shape (B, {self.num_coords}, {self.seg_len}, {self.n_joints}), got {tuple(data.shape)}")
+        data = _f32c(data, self.device)
+        return data, None, int(data.shape[0]), None
+
+    def encode(self, data, *, noise_steps: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+        """windows -> (cond_emb (B,16), z0 (B,D)): condition encoder + down path at t = -1 + to_time_dim (mcd_latent_encode)."""
+        data, view, B, keep = self._windows(data)
+        cond = torch.empty(B, self.emb_dim, device=self.device, dtype=torch.float32)
+        z0 = torch.empty(B, self.latent_dim, device=self.device, dtype=torch.float32)
+        cfg = self._cfg(B, 1, int(noise_steps))
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_latent_encode(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
+                                                _ptr(self.table(int(noise_steps))), _ptr(cond), _ptr(z0), _stream()))
+        del keep
+        return cond, z0
+
+    def denoise(self, x: torch.Tensor, t: int, cond: torch.Tensor, noise_steps: Optional[int] = None) -> torch.Tensor:
+        """TEST ENTRY: Denoiser.forward for rows x (N,D), cond (N,16) at step t -> (N,D)."""
+        if x.dim() != 2 or x.shape[1] != self.latent_dim:
+            raise ValueError(f"x must have shape (N, {self.latent_dim}), got {tuple(x.shape)}")
+        if cond.dim() != 2 or tuple(cond.shape) != (x.shape[0], self.emb_dim):
+            raise ValueError(f"cond must have shape ({x.shape[0]}, {self.emb_dim}), got {tuple(cond.shape)}")
+        if int(t) < 0:
+            raise ValueError("t must be >= 0")
+        x, cond = _f32c(x, self.device), _f32c(cond, self.device)
+        out = torch.empty_like(x)
+        tab = self.table(noise_steps if noise_steps is not None else max(int(t) + 1, 2))
+        if int(t) >= tab.shape[0] - 1:
+            raise ValueError(f"t = {t} is outside the {tab.shape[0] - 1} steps of the table")
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_latent_denoise(self._h, _ptr(x), _ptr(cond), _ptr(tab), int(t), x.shape[0], _ptr(out), _stream()))
+        return out
+
+    def score(self, data, *, n_samples: int, noise_steps: int, aggregation: str = "all", noise: Optional[torch.Tensor] = None,
+              seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_all: bool = False, want_latents: bool = False,
+              want_code: bool = False):
+        """One MoCoDADlatent.forward (mcd_latent_score) -> (loss_agg (B,) | None, loss_all (B,S) | None, latent_all (B,S,D) | None,
+        latent_code (B,D) | None).  aggregation: 'all' (per-sample losses only) or best | worst | mean | median | quantile:q.
+        noise: (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream.  Asynchronous on the current stream."""
+        data, view, B, keep = self._windows(data)
+        S, ns, D = int(n_samples), int(noise_steps), self.latent_dim
+        if S < 1 or ns < 2:
+            raise ValueError("need n_samples >= 1 and noise_steps >= 2")
+        q, name = 0.0, aggregation
+        if "quantile" in aggregation:
+            q, name = _quantile_of(aggregation), "quantile"
+        if name not in ("all", "best", "worst", "mean", "median", "quantile"):
+            raise ValueError(f"the latent scoring call aggregates losses (all, best, worst, mean, median, quantile:q), not {aggregation!r}")
+        if noise is not None:
+            noise = _f32c(noise, self.device)
+            exp = (S, max(ns - 1, 1), B, D)
+            if tuple(noise.shape) != exp:
+                raise ValueError(f"noise must have shape {exp}, got {tuple(noise.shape)}")
+        dev = self.device
+        agg = torch.empty(B, device=dev, dtype=torch.float32) if name != "all" else None
+        loss = torch.empty(B, S, device=dev, dtype=torch.float32) if (want_all or name == "all") else None
+        lat = torch.empty(B, S, D, device=dev, dtype=torch.float32) if want_latents else None
+        code = torch.empty(B, D, device=dev, dtype=torch.float32) if want_code else None
+        cfg = self._cfg(B, S, ns, loss_fn)
+        with torch.cuda.device(dev):
+            need = int(self.L.mcd_latent_workspace_bytes(self._h, B))
+            sid = torch.cuda.current_stream().cuda_stream
+            ws = self._ws.get(sid)
+            if ws is None or ws.numel() < need:
+                ws = self._ws[sid] = torch.empty(max(need, 256), device=dev, dtype=torch.uint8)
+            if B:
+                _lib.check(self.L.mcd_latent_score(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
+                                                   _ptr(noise), C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id),
+                                                   _ptr(self.table(ns)), _ptr(ws), _lib.AGGR[name], C.c_float(q), _ptr(agg), _ptr(loss),
+                                                   _ptr(lat), _ptr(code), _stream()))
+        del keep
+        return agg, loss, lat, code
+
+    def philox_noise(self, n_windows: int, *, n_samples: int, noise_steps: int, seed: int = 0, first_window_id: int = 0) -> torch.Tensor:
+        """The draws (S, max(ns-1,1), B, D) the perf mode of `score` makes in-kernel for these keys."""
+        S, K = int(n_samples), max(int(noise_steps) - 1, 1)
+        out = torch.empty(S, K, int(n_windows), self.latent_dim, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_latent_philox_noise(C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), int(n_windows), S,
+                                                      int(noise_steps), self.latent_dim, _ptr(out), _stream()))
         return out
 
 

@@ -1,0 +1,158 @@
+"""Drop-in for the reference's models/mocodad_latent.py::MoCoDADlatent (stage 'diffusion') on MI355X.
+
+Same constructor keys (`stage`, `latent_embedding_dim`, `hidden_sizes`, `pretrained_model_ckpt_path` on top of MoCoDAD's), the
+same state_dict key layout (a diffusion-stage Lightning checkpoint holds every entry, so `pretrained_model_ckpt_path` is not read
+at evaluation) and the same `forward` lists -- but the encoder (condition encoder + the U-Net's down path + to_time_dim) and the
+reverse-diffusion chain over the latent (the conditioned MLP denoiser, the DDPM updates, the loss, the loss-based aggregation)
+run in the two HIP launches behind mcd_latent_score (mocodad_amd.engine.LatentScorer).
+
+Reference: models/mocodad_latent.py (forward :69-132), models/common/components.py:203-291 (Denoiser),
+models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` and training are outside the accelerated path.
+"""
+import argparse
+from typing import List, Optional
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .mocodad import CondUNetParams, JointResampleParams, MoCoDAD, _stack
+
+
+class LatentUNetParams(nn.Module):
+    """Parameter tree of STSE_Unet as MoCoDADlatent builds it (mocodad_latent.py:51-55): the U-Net's down path WITH the layers'
+    embedding Linears, ending in 64 channels, + to_time_dim onto the latent."""
+    down_channels = [16, 32, 32, 64, 64, 128, 64]
+
+    def __init__(self, c_in: int, embedding_dim: int, latent_dim: int, n_frames: int, dropout: float):
+        super().__init__()
+        d, T, e = self.down_channels, n_frames, embedding_dim
+        self.st_gcnnsp1a = _stack([(c_in, d[0])], T, 17, dropout, e)
+        self.st_gcnnsd1 = _stack([(d[0], d[1]), (d[1], d[2])], T, 17, dropout, e)
+        self.st_gcnnsd2 = _stack([(d[2], d[3]), (d[3], d[4])], T, 12, dropout, e)
+        self.st_gcnnsd3 = _stack([(d[4], d[5]), (d[5], d[6])], T, 10, dropout, e)
+        self.down1 = JointResampleParams(17, 12, dropout)
+        self.down2 = JointResampleParams(12, 10, dropout)
+        self.to_time_dim = nn.Linear(d[6] * T * 10, latent_dim)
+
+
+class DenoiserParams(nn.Module):
+    """Parameter tree of Denoiser (components.py:228-241): Linear -> BatchNorm1d -> ReLU per hidden size, the last a plain Linear
+    whose input is the previous hidden size; one cond_layers Linear per layer."""
+
+    def __init__(self, input_size: int, hidden_sizes: List[int], cond_size: int):
+        super().__init__()
+        self.net = nn.ModuleList()
+        self.cond_layers = nn.ModuleList()
+        n = len(hidden_sizes)
+        for idx, nxt in enumerate(hidden_sizes):
+            self.cond_layers.append(nn.Linear(cond_size, nxt))
+            if idx == n - 1:
+                self.net.append(nn.Linear(input_size, nxt))
+            else:
+                self.net.append(nn.Sequential(nn.Linear(input_size, nxt), nn.BatchNorm1d(nxt), nn.ReLU(inplace=True)))
+                input_size = nxt
+
+
+class MoCoDADlatent(MoCoDAD):
+    is_latent = True
+
+    def __init__(self, args: argparse.Namespace) -> None:
+        self.stage = args.stage
+        self.latent_embedding_dim = args.latent_embedding_dim
+        self.hidden_sizes = list(args.hidden_sizes)
+        self.pretrained_model_ckpt_path = getattr(args, "pretrained_model_ckpt_path", None)
+        if self.stage == "pretrain":
+            raise NotImplementedError("mocodad_amd scores the 'diffusion' stage of MoCoDADlatent; pretrain with the reference implementation")
+        if self.stage != "diffusion":
+            raise ValueError(f"Unknown stage {self.stage}")
+        super().__init__(args)
+        assert self.conditioning_strategy == 'inject', 'Conditioning strategy must be inject. Other strategies are not supported for the latent space'
+
+    def build_model(self) -> None:
+        super().build_model()
+        self.model = LatentUNetParams(self.num_coords, self.embedding_dim, self.latent_embedding_dim, self.n_frames_corrupt, self.dropout)
+        self.denoiser = DenoiserParams(self.latent_embedding_dim, self.hidden_sizes, self.embedding_dim)
+        self.eval()
+
+    def scorer(self):
+        """Packed-weights handle (engine.LatentScorer) on the module's current device, rebuilt after load_state_dict."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("MoCoDADlatent (mocodad_amd) scores on an MI355X only: move the module to a cuda device "
+                               "(there is no CPU fallback)")
+        key = str(dev)
+        if self._scorer is None or self._scorer_key != key:
+            self._scorer = self.build_scorer(dev)
+            self._scorer_key = key
+        return self._scorer
+
+    def build_scorer(self, device):
+        from ..engine import LatentScorer
+        if self.conditioning_strategy != "inject":
+            raise NotImplementedError("the latent model conditions by 'inject' only")
+        if isinstance(self.condition_encoder, CondUNetParams):
+            raise NotImplementedError("the latent encode launch runs the 'AE' / 'E' condition encoders, not 'E_unet'")
+        ci, xi = self._frame_split()
+        return LatentScorer(self.state_dict(), seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi,
+                            cond_channels=list(self.condition_encoder.channels), latent_dim=self.latent_embedding_dim,
+                            hidden_sizes=self.hidden_sizes, num_coords=self.num_coords, n_joints=self.n_joints,
+                            emb_dim=self.embedding_dim, device=device)
+
+    # -------------------------------------------------------------- forward
+    def _loss(self, x: torch.Tensor, z0: torch.Tensor) -> torch.Tensor:
+        fn = {"smooth_l1": F.smooth_l1_loss, "l1": F.l1_loss, "mse": F.mse_loss}[self.loss_name]
+        return fn(x, z0.expand_as(x), reduction="none").mean(dim=-1)
+
+    def forward(self, input_data: List[torch.Tensor], condition_data: torch.Tensor = None, aggr_strategy: str = 'best', *,
+                return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None) -> List[torch.Tensor]:
+        """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or selected latent] + the inputs, as
+        mocodad_latent.py:69-129 (`condition_data` is unused there too; `aggr_strategy` defaults to 'best', None = the module's).
+
+        noise (extension, keyword only): (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream -- slot 0 = the x_T of
+        torch.randn (:109), slot k = the randn_like of step ns-k (:121), in call order.  window_offset keys the Philox stream."""
+        tensor_data, meta_out = self._unpack_data(input_data)
+        aggr = self.aggregation_strategy if aggr_strategy is None else aggr_strategy
+        ret = return_ if return_ is not None else self.model_return_value
+        if ret is None:
+            raise ValueError("Either return_ or self.model_return_value must be set")
+        S, ns = self.n_generated_samples, self.noise_steps
+        sc = self.scorer()
+        if window_offset is None:
+            window_offset = self._calls
+        self._calls += tensor_data.shape[0]
+        kw = dict(n_samples=S, noise_steps=ns, noise=noise, seed=self.seed, first_window_id=window_offset, loss_fn=self.loss_name)
+        loss_based = aggr in ("mean", "median") or "quantile" in aggr
+        if (loss_based or aggr in ("best", "worst")) and (ret == "loss" or loss_based):
+            loss, _, _, _ = sc.score(tensor_data, aggregation=aggr, **kw)         # both launches; one loss per window comes back
+            selected = None
+        else:
+            _, loss_all, lat, z0 = sc.score(tensor_data, aggregation="all", want_latents=True, want_code=True, **kw)
+            selected, loss = self._aggregate_latents(lat, loss_all, z0, aggr)
+        return self._pack_out_data(selected, loss, [tensor_data] + meta_out, return_=ret)
+
+    def _aggregate_latents(self, lat: torch.Tensor, loss_all: torch.Tensor, z0: torch.Tensor, aggr: str):
+        """_aggregation_strategy (mocodad.py:454-520) on the (B,S,D) latents and (B,S) losses the chain launch wrote: device
+        tensor ops, not the hot path."""
+        if aggr == "all":
+            return lat, loss_all
+        if aggr == "random":      # (the reference returns a bare tensor here, mocodad.py:480-481; like the parent: the sample and its loss)
+            s = int(np.random.randint(loss_all.shape[1]))
+            return lat[:, s], loss_all[:, s]
+        if aggr == "mean_pose":
+            sel = lat.mean(dim=1)
+            return sel, self._loss(sel, z0)
+        if aggr == "median_pose":
+            sel = torch.median(lat, dim=1).values
+            return sel, self._loss(sel, z0)
+        if aggr in ("best", "worst"):
+            best = aggr == "best"
+            loss = torch.full((lat.shape[0],), 1e10 if best else -1.0, device=lat.device)
+            sel = torch.zeros_like(z0)
+            for s in range(lat.shape[1]):
+                m = loss_all[:, s] < loss if best else loss_all[:, s] > loss
+                loss = torch.where(m, loss_all[:, s], loss)
+                sel = torch.where(m[:, None], lat[:, s], sel)
+            return sel, loss
+        raise ValueError(f"Unknown aggregation strategy {aggr}")

@@ -224,6 +224,9 @@ class PoseStream:
         import torch
         from .engine import StreamRings
         from .utils.transforms import affine_table
+        if getattr(model, "is_latent", False):
+            raise ValueError("PoseStream does not support the latent model (MoCoDADlatent): live streams score the pose-space "
+                             "model only; evaluate a latent checkpoint with eval_MoCoDAD.py")
         if model.conditioning_strategy == "random_imp":
             raise ValueError("PoseStream does not support the 'random_imp' strategy (its per-window condition-frame sets are drawn "
                              "on the host per batch); use a model with fixed conditioning indices")

@@ -78,3 +78,13 @@ def step_table(noise_steps: int, emb_dim: int = 16) -> torch.Tensor:
     tab[:, 2] = torch.sqrt(beta)
     tab[:, 4:] = pos_encoding(torch.arange(noise_steps, dtype=torch.float32)[:, None], emb_dim)
     return tab
+
+
+def latent_step_table(noise_steps: int, emb_dim: int = 16) -> torch.Tensor:
+    """(ns + 1, 4+emb_dim) fp32 CPU table of the latent path (mcd_latent_score): rows 0 .. ns-1 = `step_table`, row ns =
+    [0, 0, 0, 0, pos_encoding(-1)] — the constant time step MoCoDADlatent hands its encoder (models/mocodad_latent.py:95),
+    computed with the same fp32 torch ops."""
+    tab = torch.zeros(noise_steps + 1, 4 + emb_dim, dtype=torch.float32)
+    tab[:noise_steps] = step_table(noise_steps, emb_dim)
+    tab[noise_steps, 4:] = pos_encoding(torch.full((1, 1), -1.0), emb_dim)[0]
+    return tab

@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Times the latent model's two launches (mcd_latent_encode, the chain launch of mcd_latent_score) on one GPU.
+
+    python tools/latent_bench.py [--out profiles/latent_bench.json] [--reps 30] [--fill-batch 12288]
+
+Shipped configuration (configs/ubnormal_latent_test.yaml: D 64, hidden [64,128,128,64], noise_steps 10, 10 samples), seeded
+random-init weights, perf mode (in-kernel Philox), batch 1024 and a batch that fills the device.  Per batch, three legs alternate
+inside one timed loop, each bracketed by device events:
+  encode        mcd_latent_encode
+  score         mcd_latent_score (encode + chain; the chain launch's time is score - encode: the two run back to back on one stream)
+  pose_onepass  the yardstick of the encode launch: the pose model's one-pass scoring call (score_fused, noise_steps 2, 1 sample,
+                same windows) -- the condition encoder and all 11 U-Net layers, against 7 here
+FLOPs are counted from the shapes (functions below), never copied.  Yardsticks of the chain launch: the MFMAs it issues at 32 cycles
+per SIMD each (v_mfma_f32_16x16x4_f32) on 256 CUs x 4 SIMDs at --clock-ghz, and the CPU restatement tests/latent_ref.py on 16 threads.
+No GPU: fails (a CPU run says nothing about these times)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
+from mocodad_amd.models.mocodad_latent import MoCoDADlatent  # noqa: E402
+from mocodad_amd.utils.argparser import load_config  # noqa: E402
+
+DOWN = [(2, 16, 17), (16, 32, 17), (32, 32, 17), (32, 64, 12), (64, 64, 12), (64, 128, 10), (128, 64, 10)]      # (cin, cout, V)
+UP = [(64, 64, 12), (64, 32, 12), (32, 32, 17), (32, 2, 17)]
+
+
+def stgcn_flops(cin, cout, V, T, emb=True):
+    """one ST_GCNN_layer (stsgcn.py:94-116): time mix, joint mix, 1x1 conv, residual conv when cin != cout, embedding Linear"""
+    f = 2 * cin * V * T * T + 2 * cin * T * V * V + 2 * cin * cout * T * V
+    if cin != cout:
+        f += 2 * cin * cout * T * V
+    return f + (2 * 16 * cout if emb else 0)
+
+
+def encoder_flops(T, D):
+    down = sum(stgcn_flops(a, b, v, T) for a, b, v in DOWN) + 2 * 32 * T * 17 * 12 + 2 * 64 * T * 12 * 10
+    return down, 2 * 64 * T * 10 * D
+
+
+def cond_flops(T, channels=(32, 16, 32, 32)):
+    f, cin = 0, 2
+    for c in channels:
+        f += stgcn_flops(cin, c, 17, T, emb=False)
+        cin = c
+    return f + 2 * cin * T * 17 * 16
+
+
+def pose_pass_flops(T):
+    layers = sum(stgcn_flops(a, b, v, T) for a, b, v in DOWN + UP)
+    return layers + 2 * T * (32 * 17 * 12 + 64 * 12 * 10 + 64 * 10 * 12 + 32 * 12 * 17)
+
+
+def denoiser_flops(D, hidden):
+    ins = [D] + list(hidden[:-1])
+    return 2 * sum((i + 16) * o for i, o in zip(ins, hidden))
+
+
+def chain_mfmas_per_wg_step(D, hidden, n_tiles=2):
+    """v_mfma_f32_16x16x4_f32 issued by one workgroup in one denoiser pass: per m-tile and n-tile, in/4 + 4 (the conditioning product)"""
+    ins = [D] + list(hidden[:-1])
+    return sum((o // 16) * n_tiles * (i // 4 + 4) for i, o in zip(ins, hidden))
+
+
+def timed(legs, reps, warmup):
+    """legs: {name: callable}; alternates them `reps` times -> {name: [ms, ...]}"""
+    for _ in range(warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for k in legs}
+    for r in range(reps):
+        for k, fn in legs.items():
+            ev[k][r][0].record()
+            fn()
+            ev[k][r][1].record()
+    torch.cuda.synchronize()
+    return {k: sorted(a.elapsed_time(b) for a, b in v) for k, v in ev.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "latent_bench.json"))
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--fill-batch", type=int, default=12288)
+    ap.add_argument("--clock-ghz", type=float, default=2.4)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("latent_bench.py needs an MI355X: nothing about these launches can be timed on a CPU")
+    import latent_ref as R
+    dev = torch.device("cuda:0")
+    cfg = load_config(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml"))
+    torch.manual_seed(0)
+    lat = MoCoDADlatent(cfg).to(dev)
+    pose = MoCoDAD(load_config(os.path.join(ROOT, "configs", "hr_avenue_test.yaml"))).to(dev)
+    sl, sp = lat.scorer(), pose.scorer()
+    D, hidden, ns, S, T = lat.latent_embedding_dim, lat.hidden_sizes, lat.noise_steps, lat.n_generated_samples, lat.n_frames_corrupt
+    down_f, ttd_f = encoder_flops(T, D)
+    enc_f = down_f + ttd_f + cond_flops(T)
+    step_f = denoiser_flops(D, hidden)
+    chain_f = step_f * S * (ns - 1)
+    res = {"config": {"latent_dim": D, "hidden_sizes": hidden, "noise_steps": ns, "n_samples": S, "frames": [T, T]},
+           "flops_per_window": {"down_path": down_f, "to_time_dim": ttd_f, "condition_encoder": cond_flops(T), "denoiser_per_chain_step": step_f,
+                                "chain": chain_f, "total": enc_f + chain_f, "pose_one_pass_call": pose_pass_flops(T) + cond_flops(T)},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "clock_ghz_assumed": a.clock_ghz, "batches": {}}
+    gen = torch.Generator().manual_seed(1)
+    for B in (1024, a.fill_batch):
+        data = torch.randn(B, 2, 6, 17, generator=gen).clamp_(-3, 3).to(dev)
+        legs = {"encode": lambda: sl.encode(data, noise_steps=ns),
+                "score": lambda: sl.score(data, n_samples=S, noise_steps=ns, aggregation="best", seed=1),
+                "pose_onepass": lambda: sp.score_fused(data, n_samples=1, noise_steps=2, aggregation="best", seed=1)}
+        t = timed(legs, a.reps, a.warmup)
+        med = {k: v[len(v) // 2] for k, v in t.items()}
+        chain_ms = med["score"] - med["encode"]
+        wpg = 1 if S >= 32 else 32 // S
+        wgs = (B + wpg - 1) // wpg
+        mfma_ms = wgs * (ns - 1) * chain_mfmas_per_wg_step(D, hidden) * 32 / (256 * 4) / (a.clock_ghz * 1e6)
+        res["batches"][str(B)] = {
+            "ms_median": med, "ms_min": {k: v[0] for k, v in t.items()}, "ms_max": {k: v[-1] for k, v in t.items()},
+            "chain_ms_derived": chain_ms, "clips_per_s": B / (med["score"] * 1e-3),
+            "encode_gflops": B * enc_f / (med["encode"] * 1e-3) / 1e9, "chain_gflops": B * chain_f / (chain_ms * 1e-3) / 1e9,
+            "encode_over_pose_onepass": med["encode"] / med["pose_onepass"],
+            "chain_workgroups": wgs, "chain_mfma_issue_bound_ms": mfma_ms, "chain_over_mfma_issue_bound": chain_ms / mfma_ms}
+    # the CPU restatement of the chain on 16 threads, batch 1024 (fp32 torch ops: 4 GEMMs + BN + ReLU per step, as the reference runs it)
+    torch.set_num_threads(16)
+    sd = {k: v.detach().cpu() for k, v in lat.state_dict().items()}
+    B = 1024
+    cond, z0 = torch.randn(B, 16), torch.randn(B, D)
+    noise = torch.randn(S, ns - 1, B, D)
+    with torch.no_grad():
+        R.chain(sd, cond, z0, noise, ns)
+        t0 = time.perf_counter()
+        for _ in range(3):
+            R.chain(sd, cond, z0, noise, ns)
+        cpu_ms = (time.perf_counter() - t0) / 3 * 1e3
+    res["cpu_chain_ms_1024_16_threads"] = cpu_ms
+    res["cpu_over_gpu_chain_1024"] = cpu_ms / res["batches"]["1024"]["chain_ms_derived"]
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
