@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 7
+#define MCD_ABI_VERSION 8
 
 enum {
     MCD_OK = 0,
@@ -328,8 +328,10 @@ int mcd_frame_scores(const mcd_frame_cfg_t* cfg, const float* scores, const int6
 /* ---------------------------------------------------------------------------------------------------------------------------
  * MoCoDADlatent (models/mocodad_latent.py, stage 'diffusion'): the reverse diffusion runs on a D-dimensional latent code of the
  * corrupt frames, through a small conditioned MLP.  A latent model has its own handle type: none of the entry points above
- * takes it.  Two launches per scoring call: encode (condition encoder + the U-Net's down path + to_time_dim) and chain (every
- * denoiser pass, the DDPM updates, the loss and the aggregation). */
+ * takes it.  Two launches per scoring call for the shipped configuration: encode (condition encoder + the U-Net's down path +
+ * to_time_dim) and chain (every denoiser pass, the DDPM updates, the loss and the aggregation).  Any other condition encoder
+ * runs as a launch of its own in front of the encode launch: three launches, or four for a runtime channel list, whose kernel
+ * reads gathered condition frames (gather, cond_encode_kernel, encode, chain); see mcd_pack_latent_weights. */
 
 #define MCD_LATENT_MAX_LAYERS 8
 /* Denoiser of models/common/components.py:203-241 as MoCoDADlatent.build_model constructs it (mocodad_latent.py:51-57):
@@ -348,15 +350,32 @@ typedef struct mcd_latent_weights mcd_latent_weights_t;
  * up path), condition_encoder.* (encoder and bottleneck; the AE decoder is dead work at evaluation) and
  * denoiser.{net,cond_layers}.*.  BatchNorm2d / BatchNorm1d are folded into the preceding conv / Linear in double, the matrices
  * repacked into MFMA fragment order.  cfg: strategy MCD_STRATEGY_INJECT (mocodad_latent.py:32), t_unet = corrupt frames,
- * t_cond = condition frames, the shipped condition encoder (cond_layers 4, channels 32,16,32,32).  The encode launch is
- * instantiated for t_unet = t_cond = 3 (every shipped configuration); another count is MCD_EUNSUPPORTED, naming it.  A missing
- * tensor is MCD_EMISSING with its name -- reported before the device is touched. */
+ * t_cond = condition frames.  Supported:
+ *   t_unet       3 (the down path's LDS plan and to_time_dim are instantiated for it; another count is MCD_EUNSUPPORTED, naming
+ *                "<t_unet> corrupt + <t_cond> condition frames")
+ *   t_cond       1 .. 12
+ *   cond_layers  a channel list of 1 .. MCD_MAX_COND_LAYERS entries (channels + [h_dim], 'AE' / 'E'), or MCD_COND_UNET ('E_unet')
+ * The shipped configuration (cond_layers 4, channels 32,16,32,32, t_cond = t_unet = 3) runs its condition encoder inside the
+ * encode launch.  Every other one is packed as mcd_pack_weights packs it and runs as the pose model's kernel, in a launch of
+ * its own that writes cond_emb (B,16) into the workspace: cond_fast_kernel (the shipped channel list at another t_cond),
+ * cond_unet_kernel ('E_unet'), or cond_encode_kernel behind a gather of the condition frames (any other channel list); the
+ * encode launch then reads cond_emb instead of computing it.  A missing tensor is MCD_EMISSING with its name -- reported, like
+ * the refusals above, before the device is touched. */
 int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg,
                             const mcd_latent_cfg_t* latent_cfg, int32_t device, mcd_latent_weights_t** out);
 void mcd_free_latent_weights(mcd_latent_weights_t* w);
 
-/* Bytes of device scratch mcd_latent_score needs for n_windows windows: cond_emb (B,16) and z0 (B,D) between its two launches. */
+/* Bytes of device scratch mcd_latent_score needs for n_windows windows: cond_emb (B,16) and z0 (B,D) between its launches, plus
+ * what the handle's condition-encoder kernel needs: nothing for the fused form, cond_fast_kernel and cond_unet_kernel; the
+ * gathered condition frames (B,2,t_cond,17) for cond_encode_kernel, and its third activation buffer when three do not fit the
+ * LDS.  A pure function of the handle and n_windows (MCD_LATENT_OPT_SPLIT_ENCODE does not change it). */
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows);
+
+/* Test and diagnostic aid in the style of mcd_set_option.
+ *   MCD_LATENT_OPT_SPLIT_ENCODE  1: the shipped configuration takes the three-launch form too (cond_fast_kernel, then the encode
+ *                                launch reading cond_emb), so the two forms can be compared on the same weights.  0: default. */
+enum { MCD_LATENT_OPT_SPLIT_ENCODE = 0, MCD_LATENT_OPT_COUNT = 1 };
+int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value);
 
 /* The latent step table: (noise_steps + 1, 4 + emb_dim) -- rows 0 .. ns-1 as for mcd_score (update coefficients of
  * mocodad_latent.py:117-123 and pos_encoding(i), components.py:244-262), row ns = [0, 0, 0, 0, pos_encoding(-1)]: the constant
@@ -364,7 +383,9 @@ int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_wind
 
 /* Replaces: _encode_condition + _unet_forward(corrupt_data, t = -1, condition_embedding) (mocodad_latent.py:98-104 ->
  * STSE_Unet.forward, stsae_unet.py:222-249).  cfg: n_windows, seg_len, noise_steps (locates the table's last row) and the frame
- * index lists; data / view as for mcd_score_view -> cond_emb_out (B,16), z0_out (B,D). */
+ * index lists; data / view as for mcd_score_view -> cond_emb_out (B,16), z0_out (B,D).  One launch for the shipped
+ * configuration, two otherwise (three with the gather of a runtime channel list); such an encoder takes its gather buffer from the stream-ordered allocator
+ * (hipMallocAsync / hipFreeAsync on `stream`) because this entry has no workspace argument. */
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                       const float* step_table, float* cond_emb_out, float* z0_out, void* stream);
 

@@ -14,7 +14,8 @@ LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
 COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
-ABI_VERSION = 7
+LATENT_OPT = {"split_encode": 0}     # MCD_LATENT_OPT_*
+ABI_VERSION = 8
 
 
 class Tensor(C.Structure):
@@ -90,6 +91,7 @@ _SIGS = {
                                           C.POINTER(C.c_void_p)]),
     "mcd_free_latent_weights": (None, [C.c_void_p]),
     "mcd_latent_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32]),
+    "mcd_latent_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "mcd_latent_encode": (C.c_int, [C.c_void_p, C.POINTER(ScoreCfg), C.c_void_p, C.POINTER(WindowView), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "mcd_latent_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -1118,183 +1118,33 @@ int launch_cond_view(const mcd_weights* w, CondRoute r, const DataView& data, co
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
-}  // namespace
-
-static unsigned long long* g_prof = nullptr;  // MCD_PROFILE builds: device buffer of 32 accumulators
-
-// test aid (mcd_debug_poison_lds): every CU's LDS filled with signalling garbage (NaN bit patterns), so that a kernel reading
-// shared memory it never wrote produces NaNs instead of depending on what the previous kernel happened to leave there
-__global__ __launch_bounds__(API_THREADS) void poison_lds_kernel(unsigned* sink, int words) {
-    extern __shared__ unsigned psm[];
-    for (int u = threadIdx.x; u < words; u += API_THREADS) psm[u] = 0x7fc00000u | (unsigned)u;
-    __syncthreads();
-    if (threadIdx.x == 0 && sink) atomicOr(sink, psm[(blockIdx.x * 7919) % words] & 1u);      // (keeps the stores alive)
-    __builtin_amdgcn_s_sleep(64);
-}
-
-// the library is built with -fvisibility=hidden: only the C ABI of include/mocodad_hip.h is exported
-#pragma GCC visibility push(default)
-extern "C" {
-
-void mcd_debug_set_prof(void* p) { g_prof = reinterpret_cast<unsigned long long*>(p); }
-
-int mcd_debug_poison_lds(void* stream) {
-    constexpr size_t lds = 160 * 1024;
-    LDS_LIMIT(poison_lds_kernel, lds);
-    // one 160 KB workgroup per CU at a time; several waves of them so that every CU of every XCD takes at least one
-    hipLaunchKernelGGL(poison_lds_kernel, dim3(4096), dim3(API_THREADS), lds, static_cast<hipStream_t>(stream), (unsigned*)nullptr, (int)(lds / 4));
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
-
-const char* mcd_last_error(void) { return g_err.c_str(); }
-int32_t mcd_abi_version(void) { return MCD_ABI_VERSION; }
-
-int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t device,
-                     mcd_weights_t** out) {
-    if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
-    if (cfg->num_coords != C0) return fail(MCD_EUNSUPPORTED, "num_coords must be 2");
-    if (cfg->n_joints != 17) return fail(MCD_EUNSUPPORTED, "n_joints must be 17 (the reference U-Net hard-wires 17/12/10 joints)");
-    if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
-    const int T = cfg->t_unet;
-    if (T < 1 || T > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "U-Net frame count must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    const bool fast_unet = score_has_kernel(T);     // the instantiated score_kernel<T,...>
-    GenNet G;
-    memset(&G, 0, sizeof(G));
-    GenCond GC;
-    memset(&GC, 0, sizeof(GC));
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
-
-    Builder B;
-    struct HostLayer { int tq, am, wp, bias; float slope; };
-    struct { HostLayer L[NLAYERS]; int we, be, rs_w[4], rs_b[4]; } U;
-    memset(&U, 0, sizeof(U));
-    B.alloc(TAB_FLOATS);  // offset table lives at the start of the buffer
-    static const char* names[NLAYERS] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1",
-                                         "st_gcnnsd3.0", "st_gcnnsd3.1", "st_gcnnsu4.0", "st_gcnnsu4.1", "st_gcnnsu3.0",
-                                         "st_gcnnsu3.1"};
-    U.we = B.alloc((size_t)EMB_TOTAL * EDIM);
-    U.be = B.alloc(EMB_TOTAL + 28);
-    for (int l = 0; l < NLAYERS; ++l) {
-        const LDesc D = layer_desc(l);
-        const std::string p = std::string("model.") + names[l];
-        if (!pack_mix_mfma(tm, p, T, D.V, B, U.L[l].tq, U.L[l].am)) return fail(MCD_EMISSING, tm.missing);
-        const int cin = l == 0 ? C0 : D.cin;   // real input channels (layer 0 is zero-padded to one 16-channel block)
-        Folded ft, fr;
-        if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", D.cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
-        if (D.res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", D.cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
-        const float* sl = tm.get(p + ".prelu.weight", 1);
-        const float* we = tm.get(p + ".emb_layer.1.weight", (int64_t)D.cout * EDIM);
-        const float* be = tm.get(p + ".emb_layer.1.bias", D.cout);
-        if (!sl || !we || !be) return fail(MCD_EMISSING, tm.missing);
-        U.L[l].slope = sl[0];
-        memcpy(&B.buf[U.we + (size_t)emb_off(l) * EDIM], we, sizeof(float) * D.cout * EDIM);
-        memcpy(&B.buf[U.be + emb_off(l)], be, sizeof(float) * D.cout);
-        {   // plain layout for the runtime-shape kernel
-            GLayer& g = G.L[l];
-            g.cin = cin; g.cout = D.cout; g.V = D.V; g.slope = sl[0]; g.embo = emb_off(l);
-            if (!pack_mix(tm, p, T, D.V, B, g.tq, g.am)) return fail(MCD_EMISSING, tm.missing);
-            g.wt = B.alloc(ft.w.size());
-            for (size_t i = 0; i < ft.w.size(); ++i) B.buf[g.wt + i] = (float)ft.w[i];
-            g.wr = -1;
-            if (D.res) { g.wr = B.alloc(fr.w.size()); for (size_t i = 0; i < fr.w.size(); ++i) B.buf[g.wr + i] = (float)fr.w[i]; }
-            g.bias = B.alloc(D.cout);
-            for (int o = 0; o < D.cout; ++o) B.buf[g.bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
-        }
-        const int mpad = ceil16(D.cout);
-        U.L[l].bias = B.alloc(mpad);
-        for (int o = 0; o < D.cout; ++o) B.buf[U.L[l].bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
-        // MFMA fragment order.  Logical matrix Wcat[M][K] (cinp = input channels padded to 16):
-        //   mix-first layers: M = cout, K = cinp (W_t') + cinp (W_r', when the layer has a residual conv)
-        //   W-first layers 6, 8 and 10: M = [W_t' ; W_r'] stacked (layer 10: rows 0,1 / 2,3 of one 16-row tile), K = cinp
-        const bool wfirst = (l == 6 || l == 10 || l == 8);
-        const int cinp = D.cin;
-        const int M = (l == 6 || l == 8) ? 2 * D.cout : mpad;
-        const int Kc = wfirst ? cinp : cinp * (D.res ? 2 : 1);
-        auto wt = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? ft.w[(size_t)r * cin + k] : 0.0; };
-        auto wr = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? fr.w[(size_t)r * cin + k] : 0.0; };
-        auto wcat = [&](int r, int k) -> double {
-            if (wfirst) return r < D.cout ? wt(r, k) : (r < 2 * D.cout ? wr(r - D.cout, k) : 0.0);
-            return k < cinp ? wt(r, k) : wr(r, k - cinp);
-        };
-        if (l == 10) {
-            // layer 10's W-first product has 4 useful rows ([W_t' ; W_r'], 2 + 2): kept as plain rows for the FMA path
-            U.L[l].wp = B.alloc(4 * 32);
-            for (int r = 0; r < 4; ++r) for (int k = 0; k < 32; ++k) B.buf[U.L[l].wp + r * 32 + k] = (float)wcat(r, k);
-        } else {
-            U.L[l].wp = pack_gemm_frags(B, M, Kc, wcat);
-        }
-    }
-    static const char* rs_names[4] = {"down1", "down2", "up3", "up2"};
-    static const int rs_in[4] = {17, 12, 10, 12}, rs_out[4] = {12, 10, 12, 17};
-    for (int r = 0; r < 4; ++r) {
-        Folded f;
-        const std::string p = std::string("model.") + rs_names[r];
-        if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", rs_out[r], rs_in[r], f)) return fail(MCD_EMISSING, tm.missing);
-        const int vin = rs_in[r], vout = rs_out[r];
-        const bool capture = r < 2;   // the down-samplers capture the skip tensors (see resample_stage)
-        const int KS = capture ? (vin > 16 ? 5 : 4) : (vin + 3) / 4, MTr = (vout + 15) / 16;
-        U.rs_w[r] = B.alloc((size_t)MTr * KS * 64);
-        U.rs_b[r] = B.alloc(32);
-        for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-            // vout = 17: the second fragment holds joint 16's weights replicated over each lane group (VALU path)
-            const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(capture, vin, ks, lane >> 4);
-            B.buf[U.rs_w[r] + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-        }
-        for (int vo = 0; vo < vout; ++vo) B.buf[U.rs_b[r] + vo] = (float)f.b[vo];
-        G.rs_w[r] = B.alloc((size_t)vout * vin);
-        for (size_t i = 0; i < f.w.size(); ++i) B.buf[G.rs_w[r] + i] = (float)f.w[i];
-        G.rs_b[r] = B.alloc(vout);
-        for (int vo = 0; vo < vout; ++vo) B.buf[G.rs_b[r] + vo] = (float)f.b[vo];
-    }
-    G.we = U.we; G.be = U.be;
-    // tables of score_tiled_kernel (frame counts without a score_kernel, up to its largest padded one): mix coefficients for the padded frame count, non-capture resampler packs;
-    // GEMM fragments, biases, slopes and the embedding Linear are the specialised kernels' own
-    TiledNet TN;
-    memset(&TN, 0, sizeof(TN));
-    const int tiled_tp = fast_unet ? 0 : tiled_tp_for(T);
-    if (tiled_tp) {
-        for (int l = 0; l < NLAYERS; ++l) {
-            const LDesc D = layer_desc(l);
-            if (!pack_mix_mfma(tm, std::string("model.") + names[l], T, D.V, B, TN.tq[l], TN.am[l], tiled_tp)) return fail(MCD_EMISSING, tm.missing);
-            TN.tqm[l] = pack_time_mfma(tm.get(std::string("model.") + names[l] + ".gcn.T", (int64_t)D.V * T * T), T, D.V, tiled_tp, tl_nb(tiled_tp), B);
-            TN.wp[l] = U.L[l].wp; TN.bias[l] = U.L[l].bias; TN.slope[l] = U.L[l].slope;
-            if (l == 6 || l == 8) {    // this kernel runs layers 6 and 8 mix-first like the others: [W_t' | W_r'] fragments (the specialised kernels' are W-first)
-                Folded ft, fr;
-                const std::string p6 = std::string("model.") + names[l];
-                if (!fold_conv_bn(tm, p6 + ".tcn.0", p6 + ".tcn.1", D.cout, D.cin, ft) || !fold_conv_bn(tm, p6 + ".residual.0", p6 + ".residual.1", D.cout, D.cin, fr))
-                    return fail(MCD_EMISSING, tm.missing);
-                TN.wp[l] = pack_gemm_frags(B, D.cout, 2 * D.cin, [&](int r, int k) -> double {
-                    return k < D.cin ? ft.w[(size_t)r * D.cin + k] : fr.w[(size_t)r * D.cin + k - D.cin]; });
-            }
-        }
-        for (int r = 0; r < 4; ++r) {
-            Folded f;
-            if (!fold_conv_bn(tm, std::string("model.") + rs_names[r] + ".block.0", std::string("model.") + rs_names[r] + ".block.1", rs_out[r], rs_in[r], f))
-                return fail(MCD_EMISSING, tm.missing);
-            const int vin = rs_in[r], vout = rs_out[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
-            const int wf = B.alloc((size_t)MTr * KS * 64 + 32);
-            for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-                const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
-                B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-            }
-            for (int vo = 0; vo < vout; ++vo) B.buf[wf + MTr * KS * 64 + vo] = (float)f.b[vo];
-            TN.rsw[r] = wf;
-        }
-        TN.we = U.we; TN.be = U.be;
-    }
-    // condition encoder
+// The condition encoder of a handle (pose model and latent model alike): folded weights, mix tables and GEMM fragments appended to
+// the builder, and where they went.  has: strategy inject; unet: the 'E_unet' architecture; fast: the shipped channel list at a
+// frame count cond_fast_kernel is instantiated for.  The table words are written by write_cond_table once the buffer is complete.
+struct CondPack {
     CondW Cw;
-    memset(&Cw, 0, sizeof(Cw));
-    bool cond_fast = false;
-    int ctab[4][F_STRIDE] = {{0}};
+    bool has, unet, fast;
+    bool fast_table;                // cond_fast_body's table is packed: fast, or asked for by the caller that runs the body itself
+    int ctab[4][F_STRIDE];          // cond_fast_body's table
+    int utab[TABC_ULB + 1];         // cond table of the 'E_unet' encoder: 7 layers, 2 resamplers, Linear
+    TiledNet TNc;                   // ... and its tables for score_tiled_kernel<.., COND> (13 .. 32 condition frames)
+    int tiled_cond_tp;
+    GenCond GC;                     // plain layout for cond_unet_generic_kernel
+};
+// want_fast_table: pack cond_fast_body's table for the shipped channel list even where this library holds no cond_fast_kernel for
+// the frame count (the latent encode launch runs the body itself)
+int pack_cond_encoder(TensorMap& tm, const mcd_model_cfg_t* cfg, Builder& B, CondPack& cp, bool want_fast_table = false) {
+    memset(&cp, 0, sizeof(cp));
+    CondW& Cw = cp.Cw;
+    bool& cond_fast = cp.fast;
+    auto& ctab = cp.ctab;
+    auto& utab = cp.utab;
+    TiledNet& TNc = cp.TNc;
+    int& tiled_cond_tp = cp.tiled_cond_tp;
+    GenCond& GC = cp.GC;
     const bool has_cond = cfg->strategy == MCD_STRATEGY_INJECT;
     const bool cond_unet = has_cond && cfg->cond_layers == MCD_COND_UNET;
-    int utab[TABC_ULB + 1] = {0};   // cond table of the 'E_unet' encoder: 7 layers, 2 resamplers, Linear
-    TiledNet TNc;                   // ... and its tables for score_tiled_kernel<.., COND> (13 .. 32 condition frames)
-    memset(&TNc, 0, sizeof(TNc));
-    int tiled_cond_tp = 0;
+    cp.has = has_cond; cp.unet = cond_unet;
     if (cond_unet) {
         const int Tc = cfg->t_cond;
         if (Tc < 1 || Tc > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "condition frames must be in 1.." + std::to_string(MCD_MAX_FRAMES));
@@ -1419,9 +1269,10 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
         Cw.lw = B.alloc(F * EDIM); memcpy(&B.buf[Cw.lw], lw, sizeof(float) * F * EDIM);
         Cw.lb = B.alloc(EDIM); memcpy(&B.buf[Cw.lb], lb, sizeof(float) * EDIM);
         // fast path (cond_fast_kernel): the shipped architecture at a frame count the MFMA stages are instantiated for
-        cond_fast = Cw.n_layers == 4 && Cw.cout[0] == 32 && Cw.cout[1] == 16 && Cw.cout[2] == 32 && Cw.cout[3] == 32 &&
-                    cond_fast_has_kernel(Cw.Tc);
-        if (cond_fast) {
+        const bool shipped_list = Cw.n_layers == 4 && Cw.cout[0] == 32 && Cw.cout[1] == 16 && Cw.cout[2] == 32 && Cw.cout[3] == 32;
+        cond_fast = shipped_list && cond_fast_has_kernel(Cw.Tc);
+        cp.fast_table = cond_fast || (shipped_list && want_fast_table);
+        if (cp.fast_table) {
             int cinr = C0;
             for (int l = 0; l < 4; ++l) {
                 const int cout = Cw.cout[l], cinp = l == 0 ? 16 : cinr;
@@ -1449,6 +1300,190 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
         Cw.gmode = lds > 160 * 1024;
         if (((size_t)2 * Cw.cmax * Cw.Tc * 17 + CE_THREADS) * 4 > 160 * 1024) return fail(MCD_EUNSUPPORTED, "condition encoder activations exceed LDS");
     }
+    return MCD_OK;
+}
+void write_cond_table(int* tab, const CondPack& cp) {
+    if (cp.unet) for (int i = 0; i <= TABC_ULB; ++i) tab[TABC + i] = cp.utab[i];
+    if (cp.fast_table) {
+        for (int l = 0; l < 4; ++l) for (int f = 0; f < F_STRIDE; ++f) tab[TABC + l * F_STRIDE + f] = cp.ctab[l][f];
+        tab[TABC + TABC_LW] = cp.Cw.lw; tab[TABC + TABC_LB] = cp.Cw.lb;
+    }
+}
+}  // namespace
+
+static unsigned long long* g_prof = nullptr;  // MCD_PROFILE builds: device buffer of 32 accumulators
+
+// test aid (mcd_debug_poison_lds): every CU's LDS filled with signalling garbage (NaN bit patterns), so that a kernel reading
+// shared memory it never wrote produces NaNs instead of depending on what the previous kernel happened to leave there
+__global__ __launch_bounds__(API_THREADS) void poison_lds_kernel(unsigned* sink, int words) {
+    extern __shared__ unsigned psm[];
+    for (int u = threadIdx.x; u < words; u += API_THREADS) psm[u] = 0x7fc00000u | (unsigned)u;
+    __syncthreads();
+    if (threadIdx.x == 0 && sink) atomicOr(sink, psm[(blockIdx.x * 7919) % words] & 1u);      // (keeps the stores alive)
+    __builtin_amdgcn_s_sleep(64);
+}
+
+// the library is built with -fvisibility=hidden: only the C ABI of include/mocodad_hip.h is exported
+#pragma GCC visibility push(default)
+extern "C" {
+
+void mcd_debug_set_prof(void* p) { g_prof = reinterpret_cast<unsigned long long*>(p); }
+
+int mcd_debug_poison_lds(void* stream) {
+    constexpr size_t lds = 160 * 1024;
+    LDS_LIMIT(poison_lds_kernel, lds);
+    // one 160 KB workgroup per CU at a time; several waves of them so that every CU of every XCD takes at least one
+    hipLaunchKernelGGL(poison_lds_kernel, dim3(4096), dim3(API_THREADS), lds, static_cast<hipStream_t>(stream), (unsigned*)nullptr, (int)(lds / 4));
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+const char* mcd_last_error(void) { return g_err.c_str(); }
+int32_t mcd_abi_version(void) { return MCD_ABI_VERSION; }
+
+int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t device,
+                     mcd_weights_t** out) {
+    if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
+    if (cfg->num_coords != C0) return fail(MCD_EUNSUPPORTED, "num_coords must be 2");
+    if (cfg->n_joints != 17) return fail(MCD_EUNSUPPORTED, "n_joints must be 17 (the reference U-Net hard-wires 17/12/10 joints)");
+    if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
+    const int T = cfg->t_unet;
+    if (T < 1 || T > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "U-Net frame count must be in 1.." + std::to_string(MCD_MAX_FRAMES));
+    const bool fast_unet = score_has_kernel(T);     // the instantiated score_kernel<T,...>
+    GenNet G;
+    memset(&G, 0, sizeof(G));
+    TensorMap tm;
+    for (int i = 0; i < n_tensors; ++i) tm.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
+
+    Builder B;
+    struct HostLayer { int tq, am, wp, bias; float slope; };
+    struct { HostLayer L[NLAYERS]; int we, be, rs_w[4], rs_b[4]; } U;
+    memset(&U, 0, sizeof(U));
+    B.alloc(TAB_FLOATS);  // offset table lives at the start of the buffer
+    static const char* names[NLAYERS] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1",
+                                         "st_gcnnsd3.0", "st_gcnnsd3.1", "st_gcnnsu4.0", "st_gcnnsu4.1", "st_gcnnsu3.0",
+                                         "st_gcnnsu3.1"};
+    U.we = B.alloc((size_t)EMB_TOTAL * EDIM);
+    U.be = B.alloc(EMB_TOTAL + 28);
+    for (int l = 0; l < NLAYERS; ++l) {
+        const LDesc D = layer_desc(l);
+        const std::string p = std::string("model.") + names[l];
+        if (!pack_mix_mfma(tm, p, T, D.V, B, U.L[l].tq, U.L[l].am)) return fail(MCD_EMISSING, tm.missing);
+        const int cin = l == 0 ? C0 : D.cin;   // real input channels (layer 0 is zero-padded to one 16-channel block)
+        Folded ft, fr;
+        if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", D.cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
+        if (D.res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", D.cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
+        const float* sl = tm.get(p + ".prelu.weight", 1);
+        const float* we = tm.get(p + ".emb_layer.1.weight", (int64_t)D.cout * EDIM);
+        const float* be = tm.get(p + ".emb_layer.1.bias", D.cout);
+        if (!sl || !we || !be) return fail(MCD_EMISSING, tm.missing);
+        U.L[l].slope = sl[0];
+        memcpy(&B.buf[U.we + (size_t)emb_off(l) * EDIM], we, sizeof(float) * D.cout * EDIM);
+        memcpy(&B.buf[U.be + emb_off(l)], be, sizeof(float) * D.cout);
+        {   // plain layout for the runtime-shape kernel
+            GLayer& g = G.L[l];
+            g.cin = cin; g.cout = D.cout; g.V = D.V; g.slope = sl[0]; g.embo = emb_off(l);
+            if (!pack_mix(tm, p, T, D.V, B, g.tq, g.am)) return fail(MCD_EMISSING, tm.missing);
+            g.wt = B.alloc(ft.w.size());
+            for (size_t i = 0; i < ft.w.size(); ++i) B.buf[g.wt + i] = (float)ft.w[i];
+            g.wr = -1;
+            if (D.res) { g.wr = B.alloc(fr.w.size()); for (size_t i = 0; i < fr.w.size(); ++i) B.buf[g.wr + i] = (float)fr.w[i]; }
+            g.bias = B.alloc(D.cout);
+            for (int o = 0; o < D.cout; ++o) B.buf[g.bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
+        }
+        const int mpad = ceil16(D.cout);
+        U.L[l].bias = B.alloc(mpad);
+        for (int o = 0; o < D.cout; ++o) B.buf[U.L[l].bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
+        // MFMA fragment order.  Logical matrix Wcat[M][K] (cinp = input channels padded to 16):
+        //   mix-first layers: M = cout, K = cinp (W_t') + cinp (W_r', when the layer has a residual conv)
+        //   W-first layers 6, 8 and 10: M = [W_t' ; W_r'] stacked (layer 10: rows 0,1 / 2,3 of one 16-row tile), K = cinp
+        const bool wfirst = (l == 6 || l == 10 || l == 8);
+        const int cinp = D.cin;
+        const int M = (l == 6 || l == 8) ? 2 * D.cout : mpad;
+        const int Kc = wfirst ? cinp : cinp * (D.res ? 2 : 1);
+        auto wt = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? ft.w[(size_t)r * cin + k] : 0.0; };
+        auto wr = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? fr.w[(size_t)r * cin + k] : 0.0; };
+        auto wcat = [&](int r, int k) -> double {
+            if (wfirst) return r < D.cout ? wt(r, k) : (r < 2 * D.cout ? wr(r - D.cout, k) : 0.0);
+            return k < cinp ? wt(r, k) : wr(r, k - cinp);
+        };
+        if (l == 10) {
+            // layer 10's W-first product has 4 useful rows ([W_t' ; W_r'], 2 + 2): kept as plain rows for the FMA path
+            U.L[l].wp = B.alloc(4 * 32);
+            for (int r = 0; r < 4; ++r) for (int k = 0; k < 32; ++k) B.buf[U.L[l].wp + r * 32 + k] = (float)wcat(r, k);
+        } else {
+            U.L[l].wp = pack_gemm_frags(B, M, Kc, wcat);
+        }
+    }
+    static const char* rs_names[4] = {"down1", "down2", "up3", "up2"};
+    static const int rs_in[4] = {17, 12, 10, 12}, rs_out[4] = {12, 10, 12, 17};
+    for (int r = 0; r < 4; ++r) {
+        Folded f;
+        const std::string p = std::string("model.") + rs_names[r];
+        if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", rs_out[r], rs_in[r], f)) return fail(MCD_EMISSING, tm.missing);
+        const int vin = rs_in[r], vout = rs_out[r];
+        const bool capture = r < 2;   // the down-samplers capture the skip tensors (see resample_stage)
+        const int KS = capture ? (vin > 16 ? 5 : 4) : (vin + 3) / 4, MTr = (vout + 15) / 16;
+        U.rs_w[r] = B.alloc((size_t)MTr * KS * 64);
+        U.rs_b[r] = B.alloc(32);
+        for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
+            // vout = 17: the second fragment holds joint 16's weights replicated over each lane group (VALU path)
+            const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(capture, vin, ks, lane >> 4);
+            B.buf[U.rs_w[r] + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
+        }
+        for (int vo = 0; vo < vout; ++vo) B.buf[U.rs_b[r] + vo] = (float)f.b[vo];
+        G.rs_w[r] = B.alloc((size_t)vout * vin);
+        for (size_t i = 0; i < f.w.size(); ++i) B.buf[G.rs_w[r] + i] = (float)f.w[i];
+        G.rs_b[r] = B.alloc(vout);
+        for (int vo = 0; vo < vout; ++vo) B.buf[G.rs_b[r] + vo] = (float)f.b[vo];
+    }
+    G.we = U.we; G.be = U.be;
+    // tables of score_tiled_kernel (frame counts without a score_kernel, up to its largest padded one): mix coefficients for the padded frame count, non-capture resampler packs;
+    // GEMM fragments, biases, slopes and the embedding Linear are the specialised kernels' own
+    TiledNet TN;
+    memset(&TN, 0, sizeof(TN));
+    const int tiled_tp = fast_unet ? 0 : tiled_tp_for(T);
+    if (tiled_tp) {
+        for (int l = 0; l < NLAYERS; ++l) {
+            const LDesc D = layer_desc(l);
+            if (!pack_mix_mfma(tm, std::string("model.") + names[l], T, D.V, B, TN.tq[l], TN.am[l], tiled_tp)) return fail(MCD_EMISSING, tm.missing);
+            TN.tqm[l] = pack_time_mfma(tm.get(std::string("model.") + names[l] + ".gcn.T", (int64_t)D.V * T * T), T, D.V, tiled_tp, tl_nb(tiled_tp), B);
+            TN.wp[l] = U.L[l].wp; TN.bias[l] = U.L[l].bias; TN.slope[l] = U.L[l].slope;
+            if (l == 6 || l == 8) {    // this kernel runs layers 6 and 8 mix-first like the others: [W_t' | W_r'] fragments (the specialised kernels' are W-first)
+                Folded ft, fr;
+                const std::string p6 = std::string("model.") + names[l];
+                if (!fold_conv_bn(tm, p6 + ".tcn.0", p6 + ".tcn.1", D.cout, D.cin, ft) || !fold_conv_bn(tm, p6 + ".residual.0", p6 + ".residual.1", D.cout, D.cin, fr))
+                    return fail(MCD_EMISSING, tm.missing);
+                TN.wp[l] = pack_gemm_frags(B, D.cout, 2 * D.cin, [&](int r, int k) -> double {
+                    return k < D.cin ? ft.w[(size_t)r * D.cin + k] : fr.w[(size_t)r * D.cin + k - D.cin]; });
+            }
+        }
+        for (int r = 0; r < 4; ++r) {
+            Folded f;
+            if (!fold_conv_bn(tm, std::string("model.") + rs_names[r] + ".block.0", std::string("model.") + rs_names[r] + ".block.1", rs_out[r], rs_in[r], f))
+                return fail(MCD_EMISSING, tm.missing);
+            const int vin = rs_in[r], vout = rs_out[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
+            const int wf = B.alloc((size_t)MTr * KS * 64 + 32);
+            for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
+                const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
+                B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
+            }
+            for (int vo = 0; vo < vout; ++vo) B.buf[wf + MTr * KS * 64 + vo] = (float)f.b[vo];
+            TN.rsw[r] = wf;
+        }
+        TN.we = U.we; TN.be = U.be;
+    }
+    // condition encoder
+    CondPack cp;
+    {
+        const int rc = pack_cond_encoder(tm, cfg, B, cp);
+        if (rc != MCD_OK) return rc;
+    }
+    CondW& Cw = cp.Cw;
+    const bool has_cond = cp.has, cond_unet = cp.unet, cond_fast = cp.fast;
+    const int tiled_cond_tp = cp.tiled_cond_tp;
+    const TiledNet& TNc = cp.TNc;
+    const GenCond& GC = cp.GC;
     {
         int* tab = reinterpret_cast<int*>(B.buf.data());
         for (int l = 0; l < NLAYERS; ++l) {
@@ -1457,11 +1492,7 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
             memcpy(&tab[l * F_STRIDE + F_SLOPE], &U.L[l].slope, sizeof(float));
         }
         tab[TAB_WE] = U.we; tab[TAB_BE] = U.be;
-        if (cond_unet) for (int i = 0; i <= TABC_ULB; ++i) tab[TABC + i] = utab[i];
-        if (cond_fast) {
-            for (int l = 0; l < 4; ++l) for (int f = 0; f < F_STRIDE; ++f) tab[TABC + l * F_STRIDE + f] = ctab[l][f];
-            tab[TABC + TABC_LW] = Cw.lw; tab[TABC + TABC_LB] = Cw.lb;
-        }
+        write_cond_table(tab, cp);
         for (int r = 0; r < 4; ++r) { tab[TAB_RSW + r] = U.rs_w[r]; tab[TAB_RSB + r] = U.rs_b[r]; }
     }
     const int zero_row = B.alloc(32);

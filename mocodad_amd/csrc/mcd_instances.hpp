@@ -12,6 +12,7 @@
 //   X(unit, T_c, NB)             cond_fast_kernel / cond_unet_kernel<T_c, NB>
 //   X(unit, TP, NB, LT)          score_tiled_kernel<TP, NB, LT>
 //   X(unit, TP, NB)              score_tiled_kernel<TP, NB, false, true>: the 'E_unet' condition encoder at 13 .. 32 condition frames
+//   X(T, NB, COND_IN_KERNEL)     latent_encode_kernel (at the end of this file; its translation unit is mcd_latent.hip)
 #pragma once
 
 #ifndef MCD_FAST_T      // the shipped library
@@ -96,6 +97,11 @@
 #define MCD_TILED_COND_INSTANCES(X)
 #endif
 #endif  // MCD_FAST_T
+
+// The encode launch of the latent model (mcd_latent.hip, built in shipped and developer libraries alike):
+//   X(T, NB, COND_IN_KERNEL)     latent_encode_kernel<T, NB, COND_IN_KERNEL>: T corrupt frames; true = the shipped condition encoder at
+//                                T condition frames inside the launch, false = cond_emb from a condition-encoder launch of the rows above
+#define MCD_LATENT_ENCODE_INSTANCES(X) X(3, 2, true) X(3, 2, false)
 
 // What the tables hold, for the packer and the dispatch of mcd_api.hip (a frame count outside them takes the next more general
 // kernel: slab-tiled, then runtime-shape).

@@ -6,35 +6,34 @@
 
 namespace mcd {
 
-// Frame splits the encode launch is instantiated for: T_x = T_c = T (every shipped configuration: 3 + 3 of seg_len 6)
-#define MCD_LATENT_ENCODE_INSTANCES(X) X(3, 2)
-
-bool latent_encode_has_kernel(int t) {
-#define MCD_ROW(T, NB) if (t == (T)) return true;
+// MCD_LATENT_ENCODE_INSTANCES (mcd_instances.hpp): X(T, NB, COND_IN_KERNEL) -- T corrupt frames; the fused form also T condition frames
+bool latent_encode_has_kernel(int t, bool cond_in_kernel) {
+#define MCD_ROW(T, NB, CI) if (t == (T) && cond_in_kernel == (CI)) return true;
     MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
 #undef MCD_ROW
     return false;
 }
 
-template <int T, int NB>
+template <int T, int NB, bool CI>
 static int launch_latent_encode_t(const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi, int seg_len,
                                   const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st) {
     static_assert(NWAVES == 8, "the latent encode launch ships with eight waves per workgroup");
     constexpr size_t lds = (size_t)LatentEncLds<T, NB>::FLOATS * 4;
     static_assert(lds <= 160 * 1024, "latent encode: more than 160 KB of LDS");
-    LDS_LIMIT((&latent_encode_kernel<T, NB>), lds);
-    hipLaunchKernelGGL((latent_encode_kernel<T, NB>), dim3((B + NB - 1) / NB), dim3(NTHREADS), lds, st, wbuf, dv, cond_fi, fi, seg_len,
+    LDS_LIMIT((&latent_encode_kernel<T, NB, CI>), lds);
+    hipLaunchKernelGGL((latent_encode_kernel<T, NB, CI>), dim3((B + NB - 1) / NB), dim3(NTHREADS), lds, st, wbuf, dv, cond_fi, fi, seg_len,
                        pe_row, cond_out, z0_out, D, B);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
 
-int launch_latent_encode(int t, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi, int seg_len,
-                         const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st) {
-#define MCD_ROW(T, NB) if (t == (T)) return launch_latent_encode_t<T, NB>(wbuf, dv, cond_fi, fi, seg_len, pe_row, cond_out, z0_out, D, B, st);
+int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
+                         int seg_len, const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st) {
+#define MCD_ROW(T, NB, CI) \
+    if (t == (T) && cond_in_kernel == (CI)) return launch_latent_encode_t<T, NB, CI>(wbuf, dv, cond_fi, fi, seg_len, pe_row, cond_out, z0_out, D, B, st);
     MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
 #undef MCD_ROW
-    return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(t) + " frames (instantiated: 3 corrupt + 3 condition frames)");
+    return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(t) + " frames (instantiated: 3 corrupt frames)");
 }
 
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st) {

@@ -55,9 +55,10 @@ __host__ __device__ inline int latent_chain_lds_floats(int D, int chains_per_wg)
 constexpr int TAB_LAT_LW = 100, TAB_LAT_LB = 101;
 
 // launchers (mcd_latent.hip holds the kernels; mcd_api.hip only calls these)
-bool latent_encode_has_kernel(int t);
-int launch_latent_encode(int t, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi, int seg_len,
-                         const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st);
+// cond_in_kernel: the fused form (shipped condition encoder inside the launch); false: cond_out already holds cond_emb (B,16)
+bool latent_encode_has_kernel(int t, bool cond_in_kernel);
+int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
+                         int seg_len, const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st);
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
 int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
 

@@ -10,6 +10,9 @@ struct mcd_latent_weights {
     float* dbuf;
     size_t n_floats;
     mcd::LatentNet net;
+    bool fused_ok;        // cond_fast_body's table is packed and t_cond = t_unet: the encode launch can run the condition encoder itself
+    mcd_weights cw;       // the condition encoder as the pose model's launchers take it: dbuf, cond and the cond_* flags; nothing else is set
+    int opt[MCD_LATENT_OPT_COUNT];
 };
 
 namespace {
@@ -69,8 +72,31 @@ int latent_frames(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, Frame
     return MCD_OK;
 }
 
+// Which condition-encoder kernel serves a latent handle (decided here and nowhere else)
+enum LatentCondRoute {
+    LAT_COND_FUSED,       // shipped encoder at t_cond = t_unet: inside the encode launch
+    LAT_COND_FAST,        // shipped channel list, another t_cond (or MCD_LATENT_OPT_SPLIT_ENCODE): cond_fast_kernel
+    LAT_COND_UNET,        // 'E_unet': cond_unet_kernel
+    LAT_COND_PLAIN        // any other channel list: gather_frames_kernel + cond_encode_kernel
+};
+LatentCondRoute latent_cond_route(const mcd_latent_weights* w) {
+    if (w->cw.cond_unet) return LAT_COND_UNET;
+    if (w->fused_ok && !w->opt[MCD_LATENT_OPT_SPLIT_ENCODE]) return LAT_COND_FUSED;
+    return w->cw.cond_fast ? LAT_COND_FAST : LAT_COND_PLAIN;      // (no cond_fast_kernel for t_cond: a developer build)
+}
+// scratch of the plain encoder (independent of the options): the gathered condition frames, and its third buffer under gmode
+int64_t lat_ws_gather_bytes(const mcd_latent_weights* w, int64_t B) {
+    if (w->cw.cond_unet || w->cw.cond_fast) return 0;
+    return (B * C0 * w->cfg.t_cond * 17 * 4 + 255) / 256 * 256;
+}
+int64_t lat_ws_plain_bytes(const mcd_latent_weights* w, int64_t B) {
+    if (w->cw.cond_unet || w->cw.cond_fast) return 0;
+    return (cond_scratch_bytes(&w->cw, COND_PLAIN_SCRATCH, B) + 255) / 256 * 256;
+}
+
+// scratch: lat_ws_gather_bytes + lat_ws_plain_bytes of device memory (null when both are 0)
 int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
-                       const float* step_table, float* cond_out, float* z0_out, hipStream_t st) {
+                       const float* step_table, float* cond_out, float* z0_out, char* scratch, hipStream_t st) {
     DataView dv;
     int rc = latent_view(cfg, data, view, dv);
     if (rc != MCD_OK) return rc;
@@ -79,7 +105,25 @@ int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, 
     if (rc != MCD_OK) return rc;
     // row ns of the table: the constant time step -1 the encoder is given (mocodad_latent.py:95)
     const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
-    return launch_latent_encode(w->cfg.t_unet, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D, cfg->n_windows, st);
+    const int B = cfg->n_windows;
+    const LatentCondRoute route = latent_cond_route(w);
+    if (route == LAT_COND_FAST) {
+        rc = launch_cond_fast(&w->cw, dv, cond_fi, cfg->seg_len, cond_out, B, st);
+    } else if (route == LAT_COND_UNET) {
+        rc = launch_cond_unet(&w->cw, dv, cond_fi, cfg->seg_len, cond_out, B, st);
+    } else if (route == LAT_COND_PLAIN) {
+        if (!scratch) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
+        float* cbuf = reinterpret_cast<float*>(scratch);
+        const int Tc = cfg->n_cond;
+        const long long total = (long long)B * C0 * Tc * 17;
+        if (total > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x condition frames exceeds 2^31 - 1 elements: score in smaller batches");
+        hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dv, cbuf, B, C0, cfg->seg_len, 17, Tc, cond_fi);
+        HIP_TRY(hipGetLastError());
+        rc = launch_cond_plain(&w->cw, cbuf, B, cond_out, reinterpret_cast<float*>(scratch + lat_ws_gather_bytes(w, B)), st);
+    }
+    if (rc != MCD_OK) return rc;
+    return launch_latent_encode(w->cfg.t_unet, route == LAT_COND_FUSED, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
+                                B, st);
 }
 
 }  // namespace
@@ -96,11 +140,13 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
     const int T = cfg->t_unet;
     if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
         return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    if (!latent_encode_has_kernel(T) || cfg->t_cond != T)
+    if (!latent_encode_has_kernel(T, false) || cfg->t_cond > 12)
         return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
-                                      " condition frames (instantiated: 3 + 3)");
-    if (cfg->cond_layers != 4 || cfg->cond_channels[0] != 32 || cfg->cond_channels[1] != 16 || cfg->cond_channels[2] != 32 || cfg->cond_channels[3] != 32)
-        return fail(MCD_EUNSUPPORTED, "the latent encode launch runs the shipped condition encoder only (channels [32,16,32], h_dim 32)");
+                                      " condition frames (instantiated: 3 corrupt frames with 1 .. 12 condition frames)");
+    if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
+        return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
+    if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
+        return fail(MCD_EUNSUPPORTED, "this library holds no cond_unet_kernel for " + std::to_string(cfg->t_cond) + " condition frames (MCD_COND_UNET_INSTANCES)");
     const int D = lcfg->latent_dim, NL = lcfg->n_layers;
     if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
     if (NL < 1 || NL > LAT_MAX_LAYERS) return fail(MCD_EUNSUPPORTED, "the denoiser has " + std::to_string(NL) + " layers: 1.." + std::to_string(LAT_MAX_LAYERS) + " are supported");
@@ -169,40 +215,13 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
         tab[TAB_LAT_LW] = B.alloc(F * D); memcpy(&B.buf[tab[TAB_LAT_LW]], lw, sizeof(float) * F * D);
         tab[TAB_LAT_LB] = B.alloc(D); memcpy(&B.buf[tab[TAB_LAT_LB]], lb, sizeof(float) * D);
     }
-    // ---- the condition encoder in cond_fast_body's table (the AE decoder is dead work at evaluation and is not read)
+    // ---- the condition encoder, packed as the pose model's (the AE decoder is dead work at evaluation and is not read)
+    CondPack cp;
     {
-        const int Tc = cfg->t_cond;
-        int cinr = C0;
-        for (int l = 0; l < 4; ++l) {
-            const int cout = cfg->cond_channels[l], cinp = l == 0 ? 16 : cinr;
-            const std::string p = "condition_encoder.encoder.model_layers." + std::to_string(l);
-            Folded ft, fr;
-            const bool res = cinr != cout;
-            if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", cout, cinr, ft)) return fail(MCD_EMISSING, tm.missing);
-            if (res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", cout, cinr, fr)) return fail(MCD_EMISSING, tm.missing);
-            const float* sl = tm.get(p + ".prelu.weight", 1);
-            if (!sl) return fail(MCD_EMISSING, tm.missing);
-            int tq = 0, am = 0;
-            if (!pack_mix_mfma(tm, p, Tc, 17, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-            const int wp = pack_gemm_frags(B, ceil16(cout), cinp * (res ? 2 : 1), [&](int r, int k) -> double {
-                const bool second = k >= cinp;
-                const int kk = second ? k - cinp : k;
-                if (r >= cout || kk >= cinr) return 0.0;
-                return second ? fr.w[(size_t)r * cinr + kk] : ft.w[(size_t)r * cinr + kk];
-            });
-            const int bias = B.alloc(ceil16(cout));
-            for (int o = 0; o < cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
-            const int t0 = TABC + l * F_STRIDE;
-            tab[t0 + F_TQ] = tq; tab[t0 + F_AM] = am; tab[t0 + F_WP] = wp; tab[t0 + F_BIAS] = bias;
-            set_f(t0 + F_SLOPE, sl[0]);
-            cinr = cout;
-        }
-        const int64_t F = (int64_t)cinr * Tc * 17;
-        const float* lw = tm.get("condition_encoder.btlnk.weight", F * EDIM);
-        const float* lb = tm.get("condition_encoder.btlnk.bias", EDIM);
-        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        tab[TABC + TABC_LW] = B.alloc(F * EDIM); memcpy(&B.buf[tab[TABC + TABC_LW]], lw, sizeof(float) * F * EDIM);
-        tab[TABC + TABC_LB] = B.alloc(EDIM); memcpy(&B.buf[tab[TABC + TABC_LB]], lb, sizeof(float) * EDIM);
+        // the fused form runs cond_fast_body itself: its table is packed in every build, whatever cond_fast_kernel rows the library holds
+        const int rc = pack_cond_encoder(tm, cfg, B, cp, cfg->t_cond == T && latent_encode_has_kernel(T, true));
+        if (rc != MCD_OK) return rc;
+        write_cond_table(tab.data(), cp);
     }
     // ---- the denoiser (components.py:228-241): Linear -> BatchNorm1d -> ReLU, the last layer a plain Linear; cond_layers apart
     LatentNet N;
@@ -231,11 +250,24 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_dev};
     mcd_latent_weights* w = new mcd_latent_weights();
     w->cfg = *cfg; w->device = device; w->n_floats = B.buf.size(); w->net = N; w->dbuf = nullptr;
+    memset(w->opt, 0, sizeof(w->opt));
+    w->fused_ok = cp.fast_table && cfg->t_cond == T && latent_encode_has_kernel(T, true);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->dbuf), B.buf.size() * sizeof(float));
     if (e != hipSuccess) { delete w; return fail(MCD_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     e = hipMemcpy(w->dbuf, B.buf.data(), B.buf.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(w->dbuf); delete w; return fail(MCD_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+    w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
+    w->cw.has_cond = true; w->cw.cond_fast = cp.fast; w->cw.cond_unet = cp.unet;
+    w->cw.cond = cp.Cw;
+    w->cw.cond.base = w->dbuf;
     *out = w;
+    return MCD_OK;
+}
+
+int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value) {
+    if (!w) return fail(MCD_EINVAL, "null argument");
+    if (option < 0 || option >= MCD_LATENT_OPT_COUNT) return fail(MCD_EINVAL, "unknown latent option " + std::to_string(option));
+    w->opt[option] = value;
     return MCD_OK;
 }
 
@@ -247,7 +279,7 @@ void mcd_free_latent_weights(mcd_latent_weights_t* w) {
 
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows) {
     if (!w || n_windows <= 0) return 0;
-    return lat_ws_cond_bytes(n_windows) + lat_ws_z0_bytes(n_windows, w->net.D);
+    return lat_ws_cond_bytes(n_windows) + lat_ws_z0_bytes(n_windows, w->net.D) + lat_ws_gather_bytes(w, n_windows) + lat_ws_plain_bytes(w, n_windows);
 }
 
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
@@ -256,7 +288,17 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     if (cfg->n_windows <= 0) return MCD_OK;
     if (!data || !step_table || !cond_emb_out || !z0_out) return fail(MCD_EINVAL, "null argument");
     if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
-    return latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    // no workspace argument here: the plain encoder's scratch comes from the stream-ordered allocator
+    const int64_t need = lat_ws_gather_bytes(w, cfg->n_windows) + lat_ws_plain_bytes(w, cfg->n_windows);
+    char* scratch = nullptr;
+    if (need > 0) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)need, st));
+    const int rc = latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, scratch, st);
+    if (scratch) {
+        const hipError_t e = hipFreeAsync(scratch, st);
+        if (rc == MCD_OK && e != hipSuccess) return fail(MCD_EDEVICE, std::string("hipFreeAsync: ") + hipGetErrorString(e));
+    }
+    return rc;
 }
 
 int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
@@ -299,7 +341,8 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
     hipStream_t st = (hipStream_t)stream;
     float* cond = reinterpret_cast<float*>(workspace);
     float* z0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + lat_ws_cond_bytes(B));
-    int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, st);
+    char* scratch = reinterpret_cast<char*>(workspace) + lat_ws_cond_bytes(B) + lat_ws_z0_bytes(B, D);
+    int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, scratch, st);
     if (rc != MCD_OK) return rc;
     LatentChainParams P;
     memset(&P, 0, sizeof(P));

@@ -226,7 +226,10 @@ struct LatentEncLds {
     static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
 };
 
-template <int T, int NB>
+// COND_IN_KERNEL = false (the three-launch form: any other condition encoder, 1 .. 12 condition frames): a condition-encoder
+// kernel of the pose model (cond_fast_kernel / cond_unet_kernel / cond_encode_kernel) has written cond_emb (B,16) to cond_out in a
+// launch of its own; the prologue is skipped, CE is read from there and the remainder is the same code.
+template <int T, int NB, bool COND_IN_KERNEL = true>
 __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
                                                                     const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
                                                                     float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
@@ -243,10 +246,18 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float*
     const int b0 = blockIdx.x * NB;
     Prof prof;
     prof.off();
-    for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
-    __syncthreads();
-    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
-    __syncthreads();
+    if constexpr (COND_IN_KERNEL) {
+        for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+        __syncthreads();
+        cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
+        __syncthreads();
+    } else {
+        if (tid < NB * EDIM) {
+            const int n = tid / EDIM, b = b0 + n < B ? b0 + n : B - 1;      // (a window past the end repeats the last one, as load_coord below)
+            CE[tid] = cond_out[(size_t)b * EDIM + tid % EDIM];
+        }
+        __syncthreads();
+    }
     const float* wb = wbuf;
     if (tid < NB * EDIM) {
         const float e = pe_row[tid % EDIM] + CE[tid];

@@ -368,11 +368,13 @@ class LatentScorer:
     """One packed MoCoDADlatent model (stage 'diffusion') on one GPU: the mcd_latent_* entry points.
 
     state_dict: the reference's keys ('model.*' without an up path, 'condition_encoder.*', 'denoiser.*').
-    latent_dim / hidden_sizes: latent_embedding_dim and the denoiser's layer widths (the last equals latent_dim)."""
+    cond_channels: output channels of the 'AE' / 'E' condition encoder's layers; cond_unet: the 'E_unet' encoder instead.
+    latent_dim / hidden_sizes: latent_embedding_dim and the denoiser's layer widths (the last equals latent_dim).
+    3 corrupt frames, 1 .. 12 condition frames (mcd_pack_latent_weights)."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
-                 cond_channels: Sequence[int], latent_dim: int, hidden_sizes: Sequence[int], num_coords: int = 2, n_joints: int = 17,
-                 emb_dim: int = 16, device=None):
+                 cond_channels: Sequence[int] = (), latent_dim: int, hidden_sizes: Sequence[int], cond_unet: bool = False,
+                 num_coords: int = 2, n_joints: int = 17, emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
         self.L = _lib.lib()
         self.seg_len = int(seg_len)
         self.cond_idx = [int(i) for i in cond_idx]
@@ -388,9 +390,12 @@ class LatentScorer:
         cfg.emb_dim, cfg.strategy = emb_dim, _lib.STRATEGY["inject"]
         if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
             raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
-        cfg.cond_layers = len(cond_channels)
-        for i, c in enumerate(cond_channels):
-            cfg.cond_channels[i] = int(c)
+        if cond_unet:      # 'E_unet' condition encoder (the U-Net's down path), as HipScorer passes it
+            cfg.cond_layers = _lib.COND_UNET
+        else:
+            cfg.cond_layers = len(cond_channels)
+            for i, c in enumerate(cond_channels):
+                cfg.cond_channels[i] = int(c)
         lcfg = _lib.LatentCfg()
         lcfg.latent_dim, lcfg.n_layers = self.latent_dim, len(self.hidden_sizes)
         for i, h in enumerate(self.hidden_sizes[:8]):       # (more than 8 layers: the library refuses n_layers)
@@ -404,6 +409,15 @@ class LatentScorer:
         _lib.check(self.L.mcd_pack_latent_weights(arr, n, C.byref(cfg), C.byref(lcfg), idx, C.byref(handle)))
         del keep
         self._h = handle
+        for name, value in (options or {}).items():
+            self.set_option(name, value)
+
+    def set_option(self, name: str, value: int) -> None:
+        """Per-handle switch of the library (include/mocodad_hip.h MCD_LATENT_OPT_*): 'split_encode' = 1 makes the shipped
+        configuration take the three-launch form (condition encoder as its own launch) as well."""
+        if name not in _lib.LATENT_OPT:
+            raise ValueError(f"unknown option {name!r} (known: {sorted(_lib.LATENT_OPT)})")
+        _lib.check(self.L.mcd_latent_set_option(self._h, _lib.LATENT_OPT[name], int(value)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -478,10 +492,11 @@ class LatentScorer:
 
     def score(self, data, *, n_samples: int, noise_steps: int, aggregation: str = "all", noise: Optional[torch.Tensor] = None,
               seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_all: bool = False, want_latents: bool = False,
-              want_code: bool = False):
+              want_code: bool = False, out: Optional[torch.Tensor] = None):
         """One MoCoDADlatent.forward (mcd_latent_score) -> (loss_agg (B,) | None, loss_all (B,S) | None, latent_all (B,S,D) | None,
         latent_code (B,D) | None).  aggregation: 'all' (per-sample losses only) or best | worst | mean | median | quantile:q.
-        noise: (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream.  Asynchronous on the current stream."""
+        noise: (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream.  out: optional preallocated (B,) tensor the
+        aggregated losses are written into (it is then the first result).  Asynchronous on the current stream."""
         data, view, B, keep = self._windows(data)
         S, ns, D = int(n_samples), int(noise_steps), self.latent_dim
         if S < 1 or ns < 2:
@@ -497,7 +512,15 @@ class LatentScorer:
             if tuple(noise.shape) != exp:
                 raise ValueError(f"noise must have shape {exp}, got {tuple(noise.shape)}")
         dev = self.device
-        agg = torch.empty(B, device=dev, dtype=torch.float32) if name != "all" else None
+        agg = None
+        if out is not None:
+            if name == "all":
+                raise ValueError("out takes the aggregated losses: not valid with aggregation 'all'")
+            if out.shape != (B,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+                raise ValueError("out must be a contiguous float32 (B,) tensor on the scorer's device")
+            agg = out
+        elif name != "all":
+            agg = torch.empty(B, device=dev, dtype=torch.float32)
         loss = torch.empty(B, S, device=dev, dtype=torch.float32) if (want_all or name == "all") else None
         lat = torch.empty(B, S, D, device=dev, dtype=torch.float32) if want_latents else None
         code = torch.empty(B, D, device=dev, dtype=torch.float32) if want_code else None

@@ -4,7 +4,9 @@ Same constructor keys (`stage`, `latent_embedding_dim`, `hidden_sizes`, `pretrai
 same state_dict key layout (a diffusion-stage Lightning checkpoint holds every entry, so `pretrained_model_ckpt_path` is not read
 at evaluation) and the same `forward` lists -- but the encoder (condition encoder + the U-Net's down path + to_time_dim) and the
 reverse-diffusion chain over the latent (the conditioned MLP denoiser, the DDPM updates, the loss, the loss-based aggregation)
-run in the two HIP launches behind mcd_latent_score (mocodad_amd.engine.LatentScorer).
+run in the HIP launches behind mcd_latent_score (mocodad_amd.engine.LatentScorer): two for the shipped configuration, three
+(the condition encoder as its own launch) for `E_unet` or another number of condition frames, four (a gather of the condition
+frames in front) for another channel list / h_dim.
 
 Reference: models/mocodad_latent.py (forward :69-132), models/common/components.py:203-291 (Denoiser),
 models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` and training are outside the accelerated path.
@@ -92,11 +94,10 @@ class MoCoDADlatent(MoCoDAD):
         from ..engine import LatentScorer
         if self.conditioning_strategy != "inject":
             raise NotImplementedError("the latent model conditions by 'inject' only")
-        if isinstance(self.condition_encoder, CondUNetParams):
-            raise NotImplementedError("the latent encode launch runs the 'AE' / 'E' condition encoders, not 'E_unet'")
         ci, xi = self._frame_split()
-        return LatentScorer(self.state_dict(), seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi,
-                            cond_channels=list(self.condition_encoder.channels), latent_dim=self.latent_embedding_dim,
+        unet = isinstance(self.condition_encoder, CondUNetParams)
+        return LatentScorer(self.state_dict(), seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi, cond_unet=unet,
+                            cond_channels=[] if unet else list(self.condition_encoder.channels), latent_dim=self.latent_embedding_dim,
                             hidden_sizes=self.hidden_sizes, num_coords=self.num_coords, n_joints=self.n_joints,
                             emb_dim=self.embedding_dim, device=device)
 

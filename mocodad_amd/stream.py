@@ -210,7 +210,7 @@ class Tick:
 
 
 class PoseStream:
-    """Online scoring of live pose tracks with `model` (a MoCoDAD module on a cuda device).
+    """Online scoring of live pose tracks with `model` (a MoCoDAD or MoCoDADlatent module on a cuda device).
 
     vid_res, center, scale: as for engine.normalize_poses (center / scale (34,) = the fitted RobustScaler, or both None).
     max_tracks: slots of the device rings; ring_len: rows kept per track (>= seg_len, default seg_len);
@@ -224,9 +224,10 @@ class PoseStream:
         import torch
         from .engine import StreamRings
         from .utils.transforms import affine_table
-        if getattr(model, "is_latent", False):
-            raise ValueError("PoseStream does not support the latent model (MoCoDADlatent): live streams score the pose-space "
-                             "model only; evaluate a latent checkpoint with eval_MoCoDAD.py")
+        self.latent = bool(getattr(model, "is_latent", False))
+        if self.latent and model.device.type != "cuda":
+            raise ValueError("PoseStream scores the latent model (MoCoDADlatent) on a cuda device only: move the module to one "
+                             "first (there is no CPU fallback)")
         if model.conditioning_strategy == "random_imp":
             raise ValueError("PoseStream does not support the 'random_imp' strategy (its per-window condition-frame sets are drawn "
                              "on the host per batch); use a model with fixed conditioning indices")
@@ -282,8 +283,9 @@ class PoseStream:
     def push(self, keys, frame_ids, poses, *, noise=None) -> Tick:
         """One tick = one video frame: poses (n, 34) raw rows x1,y1,...,x17,y17 (as in the trajectory CSVs) of the tracks
         keys[i] = (scene, clip, person) at frame number frame_ids[i].  Asynchronous on the current stream.
-        noise: (S, max(ns-1,1), num_transform * n_emit, C, Tx, V) replacing the in-kernel Philox draws for the tick's windows
-        (parity tests); by default the draws are keyed by (model.seed, Tick.first_window_id + position in the tick)."""
+        noise: (S, max(ns-1,1), num_transform * n_emit, C, Tx, V) -- for a latent model (S, max(ns-1,1), num_transform * n_emit, D)
+        -- replacing the in-kernel Philox draws for the tick's windows (parity tests); by default the draws are keyed by
+        (model.seed, Tick.first_window_id + position in the tick)."""
         import torch
         from .data.windows import WindowBatch
         raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
@@ -304,9 +306,10 @@ class PoseStream:
             if ne:
                 m = self.model
                 wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
-                self.scorer.score_fused(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps,
-                                        aggregation=m.aggregation_strategy, noise=noise, seed=m.seed, first_window_id=first,
-                                        loss_fn=m.loss_name, out=scores)
+                # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches; else HipScorer.score_fused)
+                score = self.scorer.score if self.latent else self.scorer.score_fused
+                score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
+                      noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores)
                 final = self.rings.frame_scores(scores, win_d, ne)
             else:
                 final = torch.empty(0, nt, device=dev, dtype=torch.float32)

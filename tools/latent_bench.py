@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Times the latent model's two launches (mcd_latent_encode, the chain launch of mcd_latent_score) on one GPU.
+"""Times the latent model's launches (mcd_latent_encode, the chain launch of mcd_latent_score) on one GPU.
 
     python tools/latent_bench.py [--out profiles/latent_bench.json] [--reps 30] [--fill-batch 12288]
+    python tools/latent_bench.py --cond-arch E_unet            # the three-launch form: cond_unet_kernel + encode + chain
+    python tools/latent_bench.py --cond-frames 12              # ... cond_fast_kernel<12,1> + encode + chain (seg_len 15)
+    python tools/latent_bench.py --split-encode                # the shipped configuration through the three-launch form
 
 Shipped configuration (configs/ubnormal_latent_test.yaml: D 64, hidden [64,128,128,64], noise_steps 10, 10 samples), seeded
 random-init weights, perf mode (in-kernel Philox), batch 1024 and a batch that fills the device.  Per batch, three legs alternate
@@ -46,7 +49,11 @@ def encoder_flops(T, D):
     return down, 2 * 64 * T * 10 * D
 
 
-def cond_flops(T, channels=(32, 16, 32, 32)):
+def cond_flops(T, channels=(32, 16, 32, 32), unet=False):
+    if unet:      # 'E_unet': the down path without embeddings, ending in 6 channels, + to_time_dim onto 16
+        down = DOWN[:-1] + [(128, 6, 10)]
+        return (sum(stgcn_flops(a, b, v, T, emb=False) for a, b, v in down) + 2 * 32 * T * 17 * 12 + 2 * 64 * T * 12 * 10
+                + 2 * 6 * T * 10 * 16)
     f, cin = 0, 2
     for c in channels:
         f += stgcn_flops(cin, c, 17, T, emb=False)
@@ -93,31 +100,47 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--fill-batch", type=int, default=12288)
     ap.add_argument("--clock-ghz", type=float, default=2.4)
+    ap.add_argument("--cond-arch", choices=["AE", "E", "E_unet"], default=None, help="conditioning_architecture (default: the YAML's 'AE')")
+    ap.add_argument("--cond-frames", type=int, default=3, help="condition frames, 1 .. 12 (seg_len = this + 3 corrupt frames)")
+    ap.add_argument("--split-encode", action="store_true", help="MCD_LATENT_OPT_SPLIT_ENCODE: the shipped configuration in three launches")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU restatement of the chain")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("latent_bench.py needs an MI355X: nothing about these launches can be timed on a CPU")
     import latent_ref as R
     dev = torch.device("cuda:0")
     cfg = load_config(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml"))
+    Tc = int(a.cond_frames)
+    if a.cond_arch:
+        cfg.conditioning_architecture = a.cond_arch
+    if Tc != 3:
+        cfg.seg_len, cfg.conditioning_indices = Tc + 3, list(range(Tc))
+    unet = cfg.conditioning_architecture == "E_unet"
     torch.manual_seed(0)
     lat = MoCoDADlatent(cfg).to(dev)
+    if a.split_encode:
+        lat.scorer().set_option("split_encode", 1)
+    launches = 2 if (not unet and Tc == 3 and not a.split_encode) else 3
     pose = MoCoDAD(load_config(os.path.join(ROOT, "configs", "hr_avenue_test.yaml"))).to(dev)
     sl, sp = lat.scorer(), pose.scorer()
     D, hidden, ns, S, T = lat.latent_embedding_dim, lat.hidden_sizes, lat.noise_steps, lat.n_generated_samples, lat.n_frames_corrupt
     down_f, ttd_f = encoder_flops(T, D)
-    enc_f = down_f + ttd_f + cond_flops(T)
+    cond_f = cond_flops(Tc, unet=unet)
+    enc_f = down_f + ttd_f + cond_f
     step_f = denoiser_flops(D, hidden)
     chain_f = step_f * S * (ns - 1)
-    res = {"config": {"latent_dim": D, "hidden_sizes": hidden, "noise_steps": ns, "n_samples": S, "frames": [T, T]},
-           "flops_per_window": {"down_path": down_f, "to_time_dim": ttd_f, "condition_encoder": cond_flops(T), "denoiser_per_chain_step": step_f,
+    res = {"config": {"latent_dim": D, "hidden_sizes": hidden, "noise_steps": ns, "n_samples": S, "frames": [T, Tc],
+                      "cond_arch": cfg.conditioning_architecture, "launches_per_score": launches},
+           "flops_per_window": {"down_path": down_f, "to_time_dim": ttd_f, "condition_encoder": cond_f, "denoiser_per_chain_step": step_f,
                                 "chain": chain_f, "total": enc_f + chain_f, "pose_one_pass_call": pose_pass_flops(T) + cond_flops(T)},
            "device": torch.cuda.get_device_name(0), "reps": a.reps, "clock_ghz_assumed": a.clock_ghz, "batches": {}}
     gen = torch.Generator().manual_seed(1)
     for B in (1024, a.fill_batch):
-        data = torch.randn(B, 2, 6, 17, generator=gen).clamp_(-3, 3).to(dev)
+        data = torch.randn(B, 2, Tc + 3, 17, generator=gen).clamp_(-3, 3).to(dev)
+        data6 = data if Tc == 3 else torch.randn(B, 2, 6, 17, generator=gen).clamp_(-3, 3).to(dev)      # (the pose yardstick stays 3 + 3)
         legs = {"encode": lambda: sl.encode(data, noise_steps=ns),
                 "score": lambda: sl.score(data, n_samples=S, noise_steps=ns, aggregation="best", seed=1),
-                "pose_onepass": lambda: sp.score_fused(data, n_samples=1, noise_steps=2, aggregation="best", seed=1)}
+                "pose_onepass": lambda: sp.score_fused(data6, n_samples=1, noise_steps=2, aggregation="best", seed=1)}
         t = timed(legs, a.reps, a.warmup)
         med = {k: v[len(v) // 2] for k, v in t.items()}
         chain_ms = med["score"] - med["encode"]
@@ -130,6 +153,12 @@ def main():
             "encode_gflops": B * enc_f / (med["encode"] * 1e-3) / 1e9, "chain_gflops": B * chain_f / (chain_ms * 1e-3) / 1e9,
             "encode_over_pose_onepass": med["encode"] / med["pose_onepass"],
             "chain_workgroups": wgs, "chain_mfma_issue_bound_ms": mfma_ms, "chain_over_mfma_issue_bound": chain_ms / mfma_ms}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.no_cpu:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     # the CPU restatement of the chain on 16 threads, batch 1024 (fp32 torch ops: 4 GEMMs + BN + ReLU per step, as the reference runs it)
     torch.set_num_threads(16)
     sd = {k: v.detach().cpu() for k, v in lat.state_dict().items()}

@@ -5,6 +5,7 @@
     python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --data-dir tests/golden/dataset \\
            --dataset-choice HR-STC --no-scaler                                                # the test fixture
     python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 256 --rows 120
+    python tools/stream_replay.py -c configs/ubnormal_latent_test.yaml --random-init --synthetic-tracks 64    # the latent model
 
 On-disk split: the trajectory CSVs are replayed in frame order, one tick = one frame id across all clips; a track is closed
 after its last row.  The window scores, put back into dataset order, go through the model's own post_processing: the AUC is
@@ -12,7 +13,7 @@ printed.  --synthetic-tracks N: N tracks that all receive a row on every tick (n
 
 Timing (host clock around work that ends in a device synchronise, one warm-up replay, then --reps replays):
   tick      PoseStream.push of one tick: host table + one H2D copy + mcd_stream_push + the scoring call + mcd_stream_frame_scores
-  baseline  ONE score_fused call on a pre-built WindowBatch of the tick's window count over a trajectory buffer already on the
+  baseline  ONE score_fused call (a YAML with diffusion_on_latent: true: ONE LatentScorer.score call) on a pre-built WindowBatch of the tick's window count over a trajectory buffer already on the
             device (what a caller of the dataset path would pay for the same windows if the buffer and the window list cost
             nothing), timed the same way in the same process, alternating with the stream replay.
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
@@ -33,6 +34,7 @@ from mocodad_amd.data import trajectories as T  # noqa: E402
 from mocodad_amd.data.windows import TrajectoryWindows, WindowBatch  # noqa: E402
 from mocodad_amd.engine import normalize_poses  # noqa: E402
 from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
+from mocodad_amd.models.mocodad_latent import MoCoDADlatent  # noqa: E402
 from mocodad_amd.stream import PoseStream, ticks_by_frame  # noqa: E402
 from mocodad_amd.utils.argparser import load_config  # noqa: E402
 
@@ -83,7 +85,8 @@ def main():
     seg_len, nt, vid_res = int(args.seg_len), int(args.num_transform), tuple(args.vid_res)
 
     torch.manual_seed(int(getattr(args, "seed", 0)))
-    model = MoCoDAD(args).to(dev)
+    latent = bool(getattr(args, "diffusion_on_latent", False))      # (the class choice of eval_MoCoDAD.py)
+    model = (MoCoDADlatent if latent else MoCoDAD)(args).to(dev)
     model.save_tensors = False
     ckpt = os.path.join(args.ckpt_dir, args.load_ckpt)
     if os.path.exists(ckpt):
@@ -155,7 +158,7 @@ def main():
                 raise SystemExit("baseline: the tick holds more windows than the dataset path built")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            sc.score_fused(wb, first_window_id=lo, out=out[:c], **kw)
+            (sc.score if latent else sc.score_fused)(wb, first_window_id=lo, out=out[:c], **kw)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         return np.asarray(times)
@@ -175,6 +178,7 @@ def main():
            "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": cli.ring_len or seg_len, "reps": cli.reps, "auc": auc,
+           "model": "MoCoDADlatent" if latent else "MoCoDAD",
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
