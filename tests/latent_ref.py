@@ -5,10 +5,15 @@ stage 'diffusion' (reference models/mocodad_latent.py:93-127), from a state_dict
   denoise(sd, x, t, cond)            -> eps (N,D)                       Denoiser.forward (components.py:265-291)
   chain(sd, cond, z0, noise, ns)     -> latent_all (B,S,D)              the reverse diffusion with the caller's draws
   aggregate(latent_all, z0, aggr)    -> (selected | None, loss)         _aggregation_strategy (mocodad.py:454-520)
+
+Every function runs in the dtype of its inputs: given to_f64(sd) and double inputs it is the float64 reference the GPU tests of
+tests/test_latent_shapes_gpu.py measure against, given the fp32 state_dict it is the yardstick of that measurement.
+random_latent_model builds the random-init models of those tests.
 """
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
 from oracle import mocodad_oracle as O
@@ -43,31 +48,44 @@ def encode(sd: Dict[str, torch.Tensor], data: torch.Tensor, cond_idx: Sequence[i
     return cond, z0
 
 
-def denoise(sd, x: torch.Tensor, t: int, cond: torch.Tensor, emb_dim: int = 16) -> torch.Tensor:
+def to_f64(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Every floating tensor of a state_dict as double (the others, e.g. num_batches_tracked, as they are)."""
+    return {k: v.double() if v.is_floating_point() else v for k, v in sd.items()}
+
+
+def linear_k_chain(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """F.linear in a second summation order: from the bias, one product after the other over k -- the order of an MFMA k-chain."""
+    acc = b.expand(x.shape[0], -1).clone()
+    for k in range(w.shape[1]):
+        acc = acc + x[:, k:k + 1] * w[:, k]
+    return acc
+
+
+def denoise(sd, x: torch.Tensor, t: int, cond: torch.Tensor, emb_dim: int = 16, linear=F.linear) -> torch.Tensor:
     L = n_denoiser_layers(sd)
     e = O.pos_encoding(torch.full((x.shape[0], 1), float(t)), emb_dim).to(x.dtype) + cond
     h = x
     for l in range(L):
         p = f"denoiser.net.{l}"
         if l == L - 1:
-            h = F.linear(h, O._t(sd, p + ".weight"), O._t(sd, p + ".bias"))
+            h = linear(h, O._t(sd, p + ".weight"), O._t(sd, p + ".bias"))
         else:
-            h = F.linear(h, O._t(sd, p + ".0.weight"), O._t(sd, p + ".0.bias"))
+            h = linear(h, O._t(sd, p + ".0.weight"), O._t(sd, p + ".0.bias"))
             h = F.batch_norm(h, O._t(sd, p + ".1.running_mean"), O._t(sd, p + ".1.running_var"), O._t(sd, p + ".1.weight"),
                              O._t(sd, p + ".1.bias"), training=False, eps=BN_EPS)
             h = F.relu(h)
-        h = h + F.linear(e, O._t(sd, f"denoiser.cond_layers.{l}.weight"), O._t(sd, f"denoiser.cond_layers.{l}.bias"))
+        h = h + linear(e, O._t(sd, f"denoiser.cond_layers.{l}.weight"), O._t(sd, f"denoiser.cond_layers.{l}.bias"))
     return h
 
 
-def chain(sd, cond: torch.Tensor, z0: torch.Tensor, noise: torch.Tensor, noise_steps: int) -> torch.Tensor:
+def chain(sd, cond: torch.Tensor, z0: torch.Tensor, noise: torch.Tensor, noise_steps: int, linear=F.linear) -> torch.Tensor:
     """noise (S, max(ns-1,1), B, D): slot 0 = x_T, slot k = z of step ns-k.  -> (B,S,D)"""
     beta, alpha, ah = (v.to(z0.dtype) for v in O.schedule(noise_steps))
     out = []
     for s in range(noise.shape[0]):
         x = noise[s, 0]
         for i in reversed(range(1, noise_steps)):
-            eps = denoise(sd, x, i, cond)
+            eps = denoise(sd, x, i, cond, linear=linear)
             z = noise[s, noise_steps - i] if i > 1 else torch.zeros_like(x)
             x = (1 / torch.sqrt(alpha[i])) * (x - ((1 - alpha[i]) / torch.sqrt(1 - ah[i])) * eps) + torch.sqrt(beta[i]) * z
         out.append(x)
@@ -113,6 +131,71 @@ def score(sd, data, noise, *, noise_steps: int, cond_idx=(0, 1, 2), corrupt_idx=
     cond, z0 = encode(sd, data, cond_idx, corrupt_idx)
     lat = chain(sd, cond, z0, noise, noise_steps)
     return cond, z0, lat, losses(lat, z0, loss_fn)
+
+
+# ---- random-init models (tests/test_latentx_gpu.py, tests/test_latent_shapes_*.py)
+def _perturb(m, gen):
+    """Seeded eval-mode statistics away from the initial (0, 1, 1, 0): a folded BatchNorm that is wrong must show."""
+    for mod in m.modules():
+        if isinstance(mod, (nn.BatchNorm1d, nn.BatchNorm2d)):
+            mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=gen) * 0.1)
+            mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=gen) + 0.5)
+            mod.weight.data.copy_(torch.rand(mod.weight.shape, generator=gen) + 0.5)
+            mod.bias.data.copy_(torch.randn(mod.bias.shape, generator=gen) * 0.1)
+        if isinstance(mod, nn.PReLU):
+            mod.weight.data.copy_(torch.rand(mod.weight.shape, generator=gen) * 0.3 + 0.1)
+
+
+# (D, hidden) of tests/test_latent_shapes_*.py, each named for the branch of latent_chain_kernel it reaches: MT = out / 16 m-tiles
+# over four waves, KQ = in / 16 + 1 k-blocks, activations alternating between two buffers by layer parity
+LATENT_SHAPES = [
+    (16, [16]),                                 # L = 1 (the layer reads a copy of x), MT 1, KQ 2, D / 4 = 4 element groups
+    (128, [128]),                               # L = 1 at full width, MT 8, KQ 9
+    (16, [16, 16]),                             # the smallest two-layer model
+    (96, [96, 96]),                             # even L, MT 6, KQ 7
+    (48, [16, 112, 48]),                        # odd L, MT 1 / 7 / 3, KQ 4 / 2 / 8
+    (112, [64, 80, 112]),                       # state stride 116, MT 4 / 5 / 7, KQ 8 / 5 / 6
+    (80, [96, 32, 128, 16, 80]),                # L 5, a 16-wide layer between wide ones
+    (32, [128, 16, 48, 96, 64, 112, 32]),       # L 7
+    (128, [128] * 8),                           # every limit at once
+]
+SHAPE_IDS = ["-".join(str(h) for h in hidden) if len(hidden) < 8 else "128x8" for _, hidden in LATENT_SHAPES]
+_models = {}
+
+
+def pass_inputs(i: int, n: int = 70):
+    """Rows of one denoiser pass on shape i: x ~ N(0,1) (n,D), cond ~ 0.5 N(0,1) (n,16)."""
+    g = torch.Generator().manual_seed(1000 + i)
+    return torch.randn(n, LATENT_SHAPES[i][0], generator=g), 0.5 * torch.randn(n, 16, generator=g)
+
+
+def chain_inputs(i: int, ns: int, S: int, B: int):
+    """Windows (B,2,6,17) and the parity-mode draws (S, max(ns-1,1), B, D) of a scoring call on shape i."""
+    g = torch.Generator().manual_seed(2000 + i)
+    return torch.randn(B, 2, 6, 17, generator=g), torch.randn(S, max(ns - 1, 1), B, LATENT_SHAPES[i][0], generator=g)
+
+
+def random_latent_model(D: int, hidden: Sequence[int], *, seed: int, ns: int, S: int, tame: bool):
+    """-> (MoCoDADlatent on the CPU, cloned fp32 state_dict): fixture B's settings with latent_embedding_dim D and the denoiser
+    widths `hidden`, seeded random-init weights, perturbed BatchNorm statistics and PReLU slopes.  tame: the last denoiser layer
+    and its cond_layers entry scaled by 0.1, so that eps stays O(0.1) and a chain's size comes from the schedule alone.
+    Built once per argument set and session and shared: treat the state_dict as read-only."""
+    from helpers import make_args
+    from mocodad_amd.models.mocodad_latent import MoCoDADlatent
+    key = (D, tuple(hidden), seed, ns, S, tame)
+    if key not in _models:
+        cfg = load_fixture("B")[2]
+        with torch.random.fork_rng(), torch.no_grad():
+            torch.manual_seed(seed)
+            m = MoCoDADlatent(make_args(cfg, latent_embedding_dim=D, hidden_sizes=list(hidden), noise_steps=ns, n_generated_samples=S))
+            _perturb(m, torch.Generator().manual_seed(seed + 1))
+            if tame:
+                last = len(hidden) - 1
+                for lin in (m.denoiser.net[last], m.denoiser.cond_layers[last]):
+                    lin.weight.mul_(0.1)
+                    lin.bias.mul_(0.1)
+        _models[key] = (m, {k: v.detach().clone() for k, v in m.state_dict().items()})
+    return _models[key]
 
 
 # ---- fixtures of tests/golden/gen_latent_golden.py

@@ -12,12 +12,12 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 import latent_ref as R
 import latentx_fixtures as X
 from conftest import ROOT
 from helpers import make_args
+from latent_ref import _perturb
 
 pytestmark = pytest.mark.gpu
 
@@ -68,18 +68,6 @@ def test_encode_and_score_vs_reference(name, nb):
         if sel is not None:
             close(sel, io[f"sel_{tag}"][:nb], f"forward {a}: selected latent")
         close(m.forward(batch, aggr_strategy=a, return_="loss", noise=noise)[0], io[f"loss_{tag}"][:nb], f"forward {a}: loss only")
-
-
-def _perturb(m, gen):
-    """Seeded eval-mode statistics away from the initial (0, 1, 1, 0): a folded BatchNorm that is wrong must show."""
-    for mod in m.modules():
-        if isinstance(mod, (nn.BatchNorm1d, nn.BatchNorm2d)):
-            mod.running_mean.copy_(torch.randn(mod.running_mean.shape, generator=gen) * 0.1)
-            mod.running_var.copy_(torch.rand(mod.running_var.shape, generator=gen) + 0.5)
-            mod.weight.data.copy_(torch.rand(mod.weight.shape, generator=gen) + 0.5)
-            mod.bias.data.copy_(torch.randn(mod.bias.shape, generator=gen) * 0.1)
-        if isinstance(mod, nn.PReLU):
-            mod.weight.data.copy_(torch.rand(mod.weight.shape, generator=gen) * 0.3 + 0.1)
 
 
 @pytest.mark.parametrize("arch,tc", [("AE", 1), ("AE", 2), ("AE", 7), ("AE", 12), ("E_unet", 1), ("E_unet", 12), ("E96", 12)])
