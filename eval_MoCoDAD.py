@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--device-windows", action="store_true",
                     help="upload per-person trajectories once and let the kernels window + transform them on load "
                          "(instead of materialising seg_len x num_transform copies on the host)")
+    ap.add_argument("--device-masks", action="store_true",
+                    help="'random_imp' only: draw the per-window condition-frame sets on the device from (seed, window id) "
+                         "(random_imp_draw: device) instead of one torch.randperm per window on the host")
     ap.add_argument("--random-init", action="store_true", help="score with seeded random-init weights when the checkpoint "
                     "is missing (otherwise a missing checkpoint is an error)")
     ap.add_argument("--dist-backend", default="nccl", help="'nccl' (= RCCL over xGMI) or 'gloo' (tests with several ranks on one GPU)")
@@ -51,6 +54,8 @@ def main():
     cli = ap.parse_args()
     args = load_config(cli.config)
     model_cls = model_class(args)
+    if cli.device_masks:
+        args.random_imp_draw = "device"
     if not cli.synthetic:
         try:
             check_supported(args)        # (before any GPU call)

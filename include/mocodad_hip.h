@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 8
+#define MCD_ABI_VERSION 9
 
 enum {
     MCD_OK = 0,
@@ -143,6 +143,24 @@ int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, con
 int mcd_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
                      int32_t n_corrupt, float* noise_out, void* stream);
 
+/* Per-window condition-frame sets of MCD_STRATEGY_RANDOM_IMP drawn on the device: mask_out (n_windows,) int32 in the layout
+ * mcd_window_view_t.cond_mask takes -- bit t set = frame t of the window conditions, exactly n_cond of the bits 0 .. seg_len-1
+ * (bit 31 is the int32 sign bit and is legal).  Replaces nothing in the reference (which draws one torch.randperm per window on
+ * the host and takes perm[t] < n_cond, mocodad.py:719-724,535): it is the same distribution, a uniform n_cond-subset, on a
+ * different stream -- exactly as with the noise -- and exists so that the device draw can be exported, tested and replayed by an
+ * oracle (mcd_score_view(cond_mask = these masks)), with no host work per batch.
+ * The draw, fixed here so that it can be restated elsewhere bit for bit (tests/rndimp_ref.py): one thread per window b; random
+ * words from Philox4x32-10 with the round function, multipliers and key schedule of the noise generator, key = (low, high) 32
+ * bits of `seed`; call q = 0, 1, ... has the counter (c0, c1, c2, c3) = (q, 0xFFFFFFFF, 0xFFFFFFFF, (uint32)(first_window_id + b))
+ * -- the noise streams use c1 = slot < noise_steps and c2 = sample < n_samples, so no call coincides with theirs; the window id
+ * wraps at 32 bits like the noise key does -- and yields four words in output order.  Step i = 0 .. n_cond-1 takes word i % 4 of
+ * call i / 4, r = ((uint64)word * (seg_len - i)) >> 32, and sets the bit of the r-th (0-based, ascending) frame not chosen yet.
+ * Each step picks uniformly among the frames left; the multiply-high's bias is below seg_len / 2^32 per step.
+ * 1 <= n_cond < seg_len <= 32 and n_windows >= 0, else MCD_EINVAL -- checked before any device call; n_windows == 0 is MCD_OK and
+ * launches nothing. */
+int mcd_random_imp_masks(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t seg_len, int32_t n_cond,
+                         int32_t* mask_out, void* stream);
+
 /* Bytes of caller-provided device scratch a scoring call may need: condition embeddings when the condition encoder runs
  * as its own launch, (B,S) losses when an aggregation cannot be fused, scratch slabs of the runtime-shape kernels.
  * ALWAYS allocate it: workspace == NULL is accepted only by calls that end up as ONE launch (mcd_plan_split() == 1 with the
@@ -235,6 +253,15 @@ int mcd_score_fused(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const fl
 int mcd_aggregate(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
                   const float* loss_all, const float* pose_all, const float* data, float* loss_agg,
                   float* pose_agg, void* stream);
+
+/* mcd_aggregate with a window view, for the *_pose strategies under MCD_STRATEGY_RANDOM_IMP (the reference computes them for
+ * every conditioning strategy, mocodad.py:494-503).  With view->cond_mask given, the ground-truth corrupt frames of window b are
+ * the frames whose bit is clear, in ascending order -- cfg->n_corrupt of them (exactly seg_len - n_corrupt bits of 0 .. seg_len-1
+ * must be set, seg_len <= 32) -- and cfg->corrupt_idx is ignored.  `data` is the dense (B,C,T,V) tensor: a view with base != NULL
+ * is MCD_EINVAL (materialise it first).  view == NULL, or a view without a mask, is exactly mcd_aggregate. */
+int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
+                       const float* loss_all, const float* pose_all, const float* data, const mcd_window_view_t* view,
+                       float* loss_agg, float* pose_agg, void* stream);
 
 /* Frame-score assembly that follows the path (mocodad.py:386-401 + eval_utils.py:27-34): scatter-max of
  * window scores to their frames.  scores (N,), frames (N,seg_len) 1-based int32, row (N,) int32 = output

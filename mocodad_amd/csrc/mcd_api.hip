@@ -170,6 +170,8 @@ struct AggrParams {
     int B, S, C, Tx, V, seg_len, strategy, loss_fn, in_lds;
     float q;
     int corrupt_idx[MCD_MAX_FRAMES];
+    const int* win_mask;      // random_imp (mcd_aggregate_view): (B,) condition-frame bitmasks; the window's corrupt frames are its
+                              // clear bits in ascending order and corrupt_idx is not read.  null = corrupt_idx
 };
 constexpr int AGG_LDS_MAX = 8192;       // sample values staged in LDS (32 KB); a longer sample axis is read in place
 
@@ -270,7 +272,9 @@ __global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams P) {
                 }
                 if (P.pose_agg && lane == 0) P.pose_agg[(size_t)b * per + e] = val;
                 const int c = e / (P.Tx * P.V), tx = (e / P.V) % P.Tx, v = e % P.V;
-                const float gt = P.data[(((size_t)b * P.C + c) * P.seg_len + P.corrupt_idx[tx]) * P.V + v];
+                // (max: a mask with more than seg_len - Tx bits set, which the caller must not pass, still reads inside the window)
+                const int frame = P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
+                const float gt = P.data[(((size_t)b * P.C + c) * P.seg_len + frame) * P.V + v];
                 acc += loss_elem(val, gt, P.loss_fn);
             }
             if (lane == 0) P.loss_agg[b] = acc / (float)per;
@@ -1643,6 +1647,38 @@ int mcd_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, 
     return MCD_OK;
 }
 
+// One thread per window: n_cond steps, each picking uniformly among the frames not chosen yet (word i % 4 of Philox call i / 4,
+// multiply-high onto 0 .. seg_len-i-1, then the r-th clear bit), so the set is a uniform n_cond-subset of the seg_len frames.
+// Counter (call, ~0, ~0, window id): the noise streams use c1 = slot < ns and c2 = sample < S, so no call coincides with theirs.
+__global__ __launch_bounds__(256) void random_imp_masks_kernel(unsigned long long seed, long long first_window, int B, int T, int n_cond,
+                                                               int* __restrict__ mask_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const unsigned all = low_bits(T), win = (unsigned)(first_window + b);
+    unsigned chosen = 0u, w[4];
+    for (int i = 0; i < n_cond; ++i) {
+        if ((i & 3) == 0) philox_words4(seed, (unsigned)(i >> 2), 0xFFFFFFFFu, 0xFFFFFFFFu, win, w);
+        const unsigned word = (i & 3) == 0 ? w[0] : (i & 3) == 1 ? w[1] : (i & 3) == 2 ? w[2] : w[3];      // (selects: w stays in registers)
+        const int r = (int)(((unsigned long long)word * (unsigned)(T - i)) >> 32);
+        chosen |= 1u << nth_set_bit(~chosen & all, r);
+    }
+    mask_out[b] = (int)chosen;
+}
+
+int mcd_random_imp_masks(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t seg_len, int32_t n_cond,
+                         int32_t* mask_out, void* stream) {
+    // every argument check comes before the first device call
+    if (seg_len < 2 || seg_len > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "seg_len must be in 2 .. 32 (one mask bit per frame)");
+    if (n_cond < 1 || n_cond >= seg_len) return fail(MCD_EINVAL, "n_cond must be in 1 .. seg_len - 1");
+    if (n_windows < 0) return fail(MCD_EINVAL, "n_windows must be >= 0");
+    if (n_windows == 0) return MCD_OK;
+    if (!mask_out) return fail(MCD_EINVAL, "mask_out is null");
+    hipLaunchKernelGGL(random_imp_masks_kernel, dim3((unsigned)((n_windows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, (long long)first_window_id, n_windows, seg_len, n_cond, mask_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 static int64_t ws_loss_bytes(int64_t B, int64_t S) { return (B * S * 4 + 255) / 256 * 256; }
 static int64_t ws_cond_bytes(const mcd_weights* w, int64_t B) {
     const int64_t raw = B * (EDIM + C0 * (w->cfg.t_cond > 0 ? w->cfg.t_cond : 0) * 17) * 4 + 256;
@@ -1837,6 +1873,12 @@ int mcd_score_fused(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const fl
 int mcd_aggregate(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
                   const float* loss_all, const float* pose_all, const float* data, float* loss_agg, float* pose_agg,
                   void* stream) {
+    return mcd_aggregate_view(cfg, num_coords, n_joints, strategy, quantile, loss_all, pose_all, data, nullptr, loss_agg, pose_agg, stream);
+}
+
+int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
+                       const float* loss_all, const float* pose_all, const float* data, const mcd_window_view_t* view,
+                       float* loss_agg, float* pose_agg, void* stream) {
     if (!cfg) return fail(MCD_EINVAL, "null argument");
     if (cfg->n_windows <= 0) return MCD_OK;
     if (!loss_all || !loss_agg) return fail(MCD_EINVAL, "null argument");
@@ -1847,12 +1889,17 @@ int mcd_aggregate(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_join
     if (need_pose && (!pose_all || !data)) return fail(MCD_EINVAL, "pose strategies need pose_all and data");
     if (pose_agg && !pose_all) return fail(MCD_EINVAL, "pose_agg requested without pose_all");
     if (cfg->n_windows <= 0) return MCD_OK;
+    if (view && view->base) return fail(MCD_EINVAL, "mcd_aggregate_view reads dense (B,C,T,V) windows: materialise the view (base must be NULL)");
+    const int32_t* win_mask = view ? view->cond_mask : nullptr;
+    if (win_mask && (cfg->seg_len < 1 || cfg->seg_len > MCD_MAX_FRAMES || cfg->n_corrupt < 1 || cfg->n_corrupt > cfg->seg_len))
+        return fail(MCD_EINVAL, "cond_mask: need 1 <= n_corrupt <= seg_len <= 32");
     AggrParams P;
     memset(&P, 0, sizeof(P));
     P.loss_all = loss_all; P.pose_all = pose_all; P.data = data; P.loss_agg = loss_agg; P.pose_agg = pose_agg;
     P.B = cfg->n_windows; P.S = cfg->n_samples; P.C = num_coords; P.Tx = cfg->n_corrupt; P.V = n_joints;
     P.seg_len = cfg->seg_len; P.strategy = strategy; P.loss_fn = cfg->loss_fn; P.q = quantile;
     for (int t = 0; t < cfg->n_corrupt && t < MCD_MAX_FRAMES; ++t) P.corrupt_idx[t] = cfg->corrupt_idx[t];
+    P.win_mask = win_mask;
     return launch_aggregate(P, (hipStream_t)stream);
 }
 

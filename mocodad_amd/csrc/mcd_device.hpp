@@ -303,6 +303,31 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
     // ~1e-6 relative accuracy is irrelevant to its distribution
     return __fsqrt_rn(-1.38629436111989f * __log2f(u1)) * __cosf(6.28318530717958647692f * u2);
 }
+// the four raw output words of one call, in output order (same rounds, multipliers and key schedule as the two above, which
+// stay as they are: the trajectory kernels' code must not move).  For integer draws: random_imp_masks_kernel.
+__device__ __forceinline__ void philox_words4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                              unsigned (&w)[4]) {
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
+        const unsigned n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        const unsigned n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// position of the r-th (0-based, ascending) set bit of m; PRECONDITION: r < popcount(m).  Clears the r lowest set bits: no
+// per-thread array, nothing for scratch memory.
+__device__ __forceinline__ int nth_set_bit(unsigned m, int r) {
+    for (int i = 0; i < r; ++i) m &= m - 1u;
+    return __ffs(m) - 1;
+}
+__device__ __forceinline__ unsigned low_bits(int n) { return n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; }
 
 // PReLU(x) = x >= 0 ? x : a x  ==  max(x, a x) for a <= 1, min(x, a x) for a > 1: one multiply and one v_med3_f32 against
 // +-inf picked by the (wave-uniform) slope -- the compare + select form costs a third VALU instruction per element, and

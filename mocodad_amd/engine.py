@@ -298,11 +298,27 @@ class HipScorer:
                                                int(noise_steps), Tx, _ptr(out), _stream()))
         return out
 
+    def random_imp_masks(self, n_windows: int, seed: int = 0, first_window_id: int = 0) -> torch.Tensor:
+        """'random_imp' condition-frame sets drawn on the device (mcd_random_imp_masks) -> (n_windows,) int32 bitmasks, keyed by
+        (seed, global window id) like the perf-mode noise: no host work per batch.  Asynchronous on the current stream."""
+        if self.strategy != "random_imp":
+            raise ValueError("random_imp_masks: only the random_imp strategy draws per-window frame sets")
+        n = int(n_windows)
+        if n < 0:
+            raise ValueError("n_windows must be >= 0")
+        out = torch.empty(n, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_random_imp_masks(C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), n, self.seg_len,
+                                                   len(self.cond_idx), _ptr(out), _stream()))
+        return out
+
     def aggregate(self, data: torch.Tensor, loss_all: torch.Tensor, poses_all: Optional[torch.Tensor], strategy: str,
                   *, noise_steps: int, loss_fn: str = "smooth_l1", want_pose: bool = True,
-                  out: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+                  out: Optional[torch.Tensor] = None, cond_mask: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """_aggregation_strategy of the reference on device -> (selected pose | None, loss (B,)).
-        out: optional preallocated contiguous fp32 (B,) device tensor receiving the loss."""
+        out: optional preallocated contiguous fp32 (B,) device tensor receiving the loss.
+        cond_mask (random_imp): the batch's (B,) condition-frame bitmasks -- the *_pose strategies take each window's
+        ground-truth corrupt frames from it (mcd_aggregate_view)."""
         B, S = loss_all.shape
         # the C ABI takes dense (B,S) / (B,S,C,Tx,V) tensors: views with other strides (e.g. a transposed (S,B) stack) are copied
         loss_all = _f32c(loss_all, self.device)
@@ -331,9 +347,19 @@ class HipScorer:
         pose = None
         if gives_pose and want_pose and poses_all is not None:
             pose = torch.empty(poses_all.shape[0], *poses_all.shape[2:], device=self.device, dtype=torch.float32)
+        if cond_mask is not None:
+            cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
+            if cond_mask.numel() != B:
+                raise ValueError(f"cond_mask must have {B} entries")
         with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_aggregate(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
-                                            _ptr(loss_all), _ptr(poses_all), _ptr(data), _ptr(out), _ptr(pose), _stream()))
+            if cond_mask is None:
+                _lib.check(self.L.mcd_aggregate(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
+                                                _ptr(loss_all), _ptr(poses_all), _ptr(data), _ptr(out), _ptr(pose), _stream()))
+            else:
+                view = _lib.WindowView(base=None, stride_c=0, stride_t=0, trans=None, affine=None, cond_mask=cond_mask.data_ptr())
+                _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
+                                                     _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view), _ptr(out), _ptr(pose),
+                                                     _stream()))
         return pose, out
 
     def scatter_max(self, scores: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:

@@ -188,6 +188,11 @@ class MoCoDAD(_Base):
         self.anomaly_score_frames_shift = g("frames_shift", 0)
         self.dataset_name = g("dataset_choice")
         self.seed = int(g("seed", 0) or 0)
+        # 'random_imp' frame sets: 'host' = one torch.randperm per window like the reference (the default), 'device' = drawn by
+        # mcd_random_imp_masks from (seed, global window id): no host work per batch
+        self.random_imp_draw = g("random_imp_draw", "host") or "host"
+        if self.random_imp_draw not in ("host", "device"):
+            raise ValueError(f"random_imp_draw must be 'host' or 'device', got {self.random_imp_draw!r}")
         self._set_diffusion_variables()
         self.build_model()
         self._scorer = None
@@ -303,7 +308,8 @@ class MoCoDAD(_Base):
         stream, slot 0 = x_T, slot k = z of step ns-k — what torch.randn_like returns in the reference in call
         order; used for parity tests.  window_offset: global index of the first window (keys the noise stream).
         cond_mask ('random_imp' only): (B,) bitmasks of the condition frames; default = drawn like the reference does
-        (one torch.randperm per window on the default CPU generator, mocodad.py:719-724)."""
+        (one torch.randperm per window on the default CPU generator, mocodad.py:719-724), or, with random_imp_draw='device',
+        on the device from (seed, window_offset + b) -- the same sets however the windows are cut into batches or shards."""
         tensor_data, meta_out = self._unpack_data(input_data)
         aggr = self.aggregation_strategy if aggr_strategy is None else aggr_strategy
         ret = return_ if return_ is not None else self.model_return_value
@@ -318,10 +324,10 @@ class MoCoDAD(_Base):
         self._calls += tensor_data.shape[0]
         if hasattr(tensor_data, "as_view") and pose_aggr and aggr in ("mean_pose", "median_pose"):
             tensor_data = tensor_data.materialize()      # the *_pose strategies compare against the windows themselves
-        if self.conditioning_strategy == "random_imp":
-            if aggr in ("mean_pose", "median_pose"):
-                raise NotImplementedError("the *_pose aggregations are not available with 'random_imp'")
-            if cond_mask is None:
+        if self.conditioning_strategy == "random_imp" and cond_mask is None:
+            if self.random_imp_draw == "device":
+                cond_mask = sc.random_imp_masks(tensor_data.shape[0], self.seed, window_offset)
+            else:
                 cond_mask = self.draw_random_imp_mask(tensor_data.shape[0])
         kw = dict(n_samples=S, noise_steps=ns, noise=noise, seed=self.seed, first_window_id=window_offset, loss_fn=self.loss_name,
                   cond_mask=cond_mask)
@@ -332,7 +338,7 @@ class MoCoDAD(_Base):
             selected_x = None
         else:
             loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose, **kw)
-            selected_x, loss = self._aggregate(sc, tensor_data, loss_all, poses_all, aggr, want_pose)
+            selected_x, loss = self._aggregate(sc, tensor_data, loss_all, poses_all, aggr, want_pose, cond_mask)
         return self._pack_out_data(selected_x, loss, [tensor_data] + meta_out, return_=ret)
 
     def draw_random_imp_mask(self, n_windows: int) -> torch.Tensor:
@@ -342,7 +348,14 @@ class MoCoDAD(_Base):
         idx = torch.tensor([torch.randperm(T).tolist() for _ in range(n_windows)])
         return ((idx < k).int() << torch.arange(T, dtype=torch.int32)).sum(1).to(torch.int32)
 
-    def _aggregate(self, sc, data, loss_all, poses_all, aggr: str, want_pose: bool):
+    def random_imp_masks(self, n_windows: int, window_offset: int = 0) -> torch.Tensor:
+        """The frame sets random_imp_draw='device' gives the windows window_offset .. window_offset + n_windows - 1 under the
+        module's seed -> (n_windows,) int32 device tensor; forward(cond_mask=these) replays such a call (e.g. against an oracle)."""
+        if self.conditioning_strategy != "random_imp":
+            raise ValueError("random_imp_masks: the conditioning strategy is not 'random_imp'")
+        return self.scorer().random_imp_masks(n_windows, self.seed, window_offset)
+
+    def _aggregate(self, sc, data, loss_all, poses_all, aggr: str, want_pose: bool, cond_mask=None):
         if aggr == "all":
             return poses_all, loss_all
         if aggr == "random":  # the reference returns a bare tensor here (mocodad.py:480-481); return (pose, its loss)
@@ -352,7 +365,7 @@ class MoCoDAD(_Base):
         if aggr not in known and "quantile" not in aggr:
             raise ValueError(f"Unknown aggregation strategy {aggr}")
         return sc.aggregate(data, loss_all, poses_all, aggr, noise_steps=self.noise_steps, loss_fn=self.loss_name,
-                            want_pose=want_pose)
+                            want_pose=want_pose, cond_mask=cond_mask)
 
     def _pack_out_data(self, selected_x, loss_of_selected_x, additional_out, return_: str):
         if return_ is None:
