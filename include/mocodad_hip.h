@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 9
+#define MCD_ABI_VERSION 10
 
 enum {
     MCD_OK = 0,
@@ -451,6 +451,13 @@ void mcd_debug_set_prof(void* device_buffer);
  * that reads shared memory it never wrote yields NaNs instead of whatever the previous kernel left behind
  * (tests/test_hip_parity.py::test_no_uninitialised_reads). */
 int mcd_debug_poison_lds(void* stream);
+
+/* Test aid, host only (no device call, no GPU needed): runs the packer of mcd_pack_weights -- or, with latent_cfg != NULL, of
+ * mcd_pack_latent_weights -- and returns the packed buffer's float count and a 64-bit FNV-1a digest over the buffer's bytes
+ * followed by the tables the handle would keep.  The packers' argument and tensor errors come back as theirs do.
+ * tests/test_pack_layout_host.py pins the layout with it. */
+int mcd_debug_pack_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* latent_cfg,
+                          int64_t* n_floats_out, uint64_t* digest_out);
 
 const char* mcd_last_error(void);
 int32_t mcd_abi_version(void);

@@ -15,7 +15,7 @@ COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
 LATENT_OPT = {"split_encode": 0}     # MCD_LATENT_OPT_*
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class Tensor(C.Structure):
@@ -64,6 +64,8 @@ _SIGS = {
     "mcd_philox_noise": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_debug_set_prof": (None, [C.c_void_p]),
     "mcd_debug_poison_lds": (C.c_int, [C.c_void_p]),
+    "mcd_debug_pack_digest": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.POINTER(LatentCfg), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_uint64)]),
     "mcd_cond_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_score_workspace_bytes": (C.c_int64, [C.c_void_p, C.POINTER(ScoreCfg)]),

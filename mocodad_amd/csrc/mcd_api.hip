@@ -1,20 +1,22 @@
-// mcd_api.hip — host side of libmocodad_hip.so: the C ABI of include/mocodad_hip.h, the weight packer (BatchNorm folding, MFMA
-// fragment order), dispatch to the kernel instantiations of mcd_inst.hip (declared `extern template` in mcd_launch.hpp; every
-// switch over frame counts is an expansion of the tables of mcd_instances.hpp, and which kernel family serves a handle is decided
-// by unet_route() / cond_route() alone: entry points, launches and workspace sizing ask them), and the kernels that are not templates:
-//   cond_encode_kernel          STSE.encode for any channel list / 21 .. 31 condition frames   models/stsae/stsae.py:59-92
-//   cond_unet_generic_kernel    'E_unet' condition encoder at any frame count (cross-check)    models/stsae/stsae_unet.py:62-146
-//   score_generic_kernel        plain-FMA runtime-shape trajectory kernel: the CROSS-CHECK of the MFMA kernels (MCD_OPT_GENERIC_UNET)
+// mcd_api.hip — host side of libmocodad_hip.so: the C ABI of include/mocodad_hip.h, the upload of a packed model, and dispatch to
+// the kernel instantiations of mcd_inst.hip (declared `extern template` in mcd_launch.hpp; every switch over frame counts is an
+// expansion of the tables of mcd_instances.hpp, and which kernel family serves a handle is decided by unet_route() / cond_route()
+// alone: entry points, launches and workspace sizing ask them).  The weight packer (BatchNorm folding, MFMA fragment order) is
+// mcd_pack.hpp; the runtime-shape kernels (cond_encode_kernel, score_generic_kernel, cond_unet_generic_kernel) are
+// mcd_generic_kernel.hpp.  The kernels of this file:
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
 //   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
 //   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
 //                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
+//   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 // The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
 #include <algorithm>
 #include "mcd_launch.hpp"
+#include "mcd_generic_kernel.hpp"
+#include "mcd_pack.hpp"
 
 #if MCD_NWAVES != 8 && !defined(MCD_FAST_T)      // (developer builds pass one flag set to every file)
 #error "mcd_api.hip is built with the default wave count: per-unit wave counts belong to mcd_inst.hip (MCD_UNIT_FLAGS_<n>)"
@@ -25,141 +27,6 @@ namespace { constexpr int API_THREADS = 512; }      // block size of this file's
 using namespace mcd;
 
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// condition encoder (runtime channel list; 0.3 % of the work): one workgroup per window, VALU only.
-// ------------------------------------------------------------------------------------------------
-
-// Stages of a layer as wave tasks of (8 channels, 64 columns): the time mix (Y = X . Tq per joint, into the layer's output
-// buffer as scratch), the joint mix (Z = Y . A), the channel GEMM with 8 accumulators per thread whose weights are wave-uniform
-// scalar loads.  (The first version ran the two mixes as one 17 x (T + 1) loop per output element: 8x the multiplies, 0.45
-// TFLOP/s; at 16 condition frames it was a quarter of the whole scoring step.)
-constexpr int CE_THREADS = 512;
-// gbuf (W.gmode): one buffer of cmax x Tc x 17 floats per workgroup in global scratch -- the buffers rotate, so a different one of
-// the three is the global one in every layer.
-__global__ __launch_bounds__(CE_THREADS) void cond_encode_kernel(const CondW W, const float* __restrict__ cond,
-                                                                 float* __restrict__ emb_out, int B, float* __restrict__ gbuf) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Tc = W.Tc, TV = Tc * 17, nblk = (TV + 63) / 64;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int NW = CE_THREADS / 64;
-    float* RED = smem + (gbuf ? 2 : 3) * W.cmax * TV;  // CE_THREADS partial sums
-    for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    float* X = smem;
-    float* Z = X + W.cmax * TV;
-    float* O = gbuf ? gbuf + (size_t)blockIdx.x * W.cmax * TV : Z + W.cmax * TV;
-    __syncthreads();
-    for (int u = tid; u < C0 * TV; u += CE_THREADS) X[u] = cond[(size_t)b * C0 * TV + u];  // (c, t, v) row-major
-    __syncthreads();
-    for (int l = 0; l < W.n_layers; ++l) {
-        const int cin = W.cin[l], cout = W.cout[l];
-        const float* Tq = W.base + W.tq[l];
-        const float* Am = W.base + W.am[l];
-        const int ngi = (cin + 7) / 8, ngo = (cout + 7) / 8;
-        // time mix: Y[c][q, v] = sum_t X[c][t, v] Tq[q, v][t]   (Y in the output buffer)
-        for (int task = wave; task < ngi * nblk; task += NW) {
-            const int c0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-            if (p < TV) {
-                const float* tq = Tq + (size_t)p * Tc;
-                const float* xb = X + p % 17;
-                int co[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) co[i] = (c0 + i < cin ? c0 + i : cin - 1) * TV;
-                float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                for (int t = 0; t < Tc; ++t) {
-                    const float tv = tq[t];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[i] = fmaf(xb[co[i] + t * 17], tv, acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (c0 + i < cin) O[(c0 + i) * TV + p] = acc[i];
-            }
-        }
-        __syncthreads();
-        // joint mix: Z[c][q, w] = sum_v Y[c][q, v] A[q, v][w]
-        for (int task = wave; task < ngi * nblk; task += NW) {
-            const int c0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-            if (p < TV) {
-                const int q = p / 17, w = p % 17;
-                const float* am = Am + (size_t)q * 289 + w;
-                const float* yb = O + q * 17;
-                int co[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) co[i] = (c0 + i < cin ? c0 + i : cin - 1) * TV;
-                float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int v = 0; v < 17; ++v) {
-                    const float a = am[v * 17];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[i] = fmaf(yb[co[i] + v], a, acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (c0 + i < cin) Z[(c0 + i) * TV + p] = acc[i];
-            }
-        }
-        __syncthreads();
-        // channel GEMM + residual + PReLU: 8 output channels per thread, their weight rows wave-uniform
-        const float* wt = W.base + W.wt[l];
-        const float* wr = W.wr[l] >= 0 ? W.base + W.wr[l] : nullptr;
-        const float* bias = W.base + W.bias[l];
-        const float slope = W.slope[l];
-        for (int task = wave; task < ngo * nblk; task += NW) {
-            const int o0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-            int row[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) row[i] = o0 + i < cout ? o0 + i : cout - 1;
-            if (p < TV) {
-                float acc[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = bias[row[i]];
-                for (int c = 0; c < cin; ++c) {
-                    const float z = Z[c * TV + p];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[i] = fmaf(wt[row[i] * cin + c], z, acc[i]);
-                }
-                if (wr) {
-                    for (int c = 0; c < cin; ++c) {
-                        const float x = X[c * TV + p];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) acc[i] = fmaf(wr[row[i] * cin + c], x, acc[i]);
-                    }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[i] += X[row[i] * TV + p];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (o0 + i < cout) O[(o0 + i) * TV + p] = prelu(acc[i], slope);
-            }
-        }
-        __syncthreads();
-        float* tmp = X; X = O; O = tmp;
-    }
-    // bottleneck Linear over the (c,t,v) flattening (stsae.py:73-89)
-    const int hd = W.cout[W.n_layers - 1];
-    const int F = hd * TV;
-    const int jj = tid / 16, part = tid % 16;  // 16 partial sums per output
-    for (int j0 = 0; j0 < W.latent; j0 += CE_THREADS / 16) {
-        const int jo = j0 + jj;
-        float a = 0.f;
-        if (jo < W.latent) {
-            const float* wrow = W.base + W.lw + (size_t)jo * F;
-            for (int k = part; k < F; k += 16) a = fmaf(wrow[k], X[k], a);
-        }
-        RED[tid] = a;
-        __syncthreads();
-        if (part == 0 && jo < W.latent) {
-            float s = W.base[W.lb + jo];
-            for (int k = 0; k < 16; ++k) s += RED[jj * 16 + k];
-            emb_out[(size_t)b * W.latent + jo] = s;
-        }
-        __syncthreads();
-    }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // aggregation over the S samples (mocodad.py:454-520); one 64-lane wave per window, ANY S (the reference's shipped
@@ -282,300 +149,6 @@ __global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams P) {
     }
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// Runtime-shape form of the trajectory kernel: ANY U-Net frame count 1..MCD_MAX_FRAMES (the reference is generic in
-// n_frames, mocodad.py:780-796, stsgcn.py:134-141), every strategy.  Plain fp32 FMAs, one 256-thread workgroup per chain
-// at a time (persistent grid), activations [channel][frame][joint] in a per-workgroup global scratch slab.  Correct, not fast,
-// and since round 3 off every default path (score_kernel<T,...> covers 1 .. 12 frames, score_tiled_kernel 13 .. 32): it is the
-// independent implementation MCD_OPT_GENERIC_UNET switches to, which the tests compare the MFMA kernels with.
-// Same noise keys, same update, same loss as score_kernel.
-// ------------------------------------------------------------------------------------------------
-constexpr int GEN_THREADS = 256;
-constexpr int GEN_BUF = 1280;        // floats per frame of the three rotating buffers: 128 ch x 10 joints (>= 32 x 17, 64 x 12)
-constexpr int GEN_D1 = 32 * 17, GEN_D2 = 64 * 12;
-constexpr int GEN_SLAB = 3 * GEN_BUF + GEN_D1 + GEN_D2;      // per frame and workgroup
-
-// one ST-GCN layer (stsgcn.py:94-116, BatchNorm folded): X [cin][T][V] -> O [cout][T][V]; Y (>= cin T V floats, may be O) and
-// Z are scratch.  emb: the pass's embedding outputs (LDS) or null.
-// Each stage as wave tasks of (8 channels, 64 columns) with 8 accumulators per thread: a column's activation (or coefficient)
-// is loaded once for 8 multiply-adds, and the GEMM's weight rows are wave-uniform scalar loads (see cond_encode_kernel).
-__device__ void g_layer(const float* wb, const GLayer& L, int T, const float* X, float* Y, float* Z, float* O, const float* emb) {
-    const int V = L.V, TV = T * V, cin = L.cin, cout = L.cout, nblk = (TV + 63) / 64;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    constexpr int NW = GEN_THREADS / 64;
-    const float* Tq = wb + L.tq;      // [q][v][t]
-    const float* Am = wb + L.am;      // [q][v][w]
-    const int ngi = (cin + 7) / 8, ngo = (cout + 7) / 8;
-    for (int task = wave; task < ngi * nblk; task += NW) {          // time mix: Y[c][q, v] = sum_t X[c][t, v] Tq[q, v][t]
-        const int c0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-        if (p < TV) {
-            const float* tq = Tq + (size_t)p * T;
-            const float* xb = X + p % V;
-            int co[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) co[i] = (c0 + i < cin ? c0 + i : cin - 1) * TV;
-            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            for (int t = 0; t < T; ++t) {
-                const float tv = tq[t];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = fmaf(xb[co[i] + t * V], tv, acc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (c0 + i < cin) Y[(c0 + i) * TV + p] = acc[i];
-        }
-    }
-    __syncthreads();
-    for (int task = wave; task < ngi * nblk; task += NW) {          // joint mix: Z[c][q, w] = sum_v Y[c][q, v] A[q, v][w]
-        const int c0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-        if (p < TV) {
-            const int q = p / V, w = p % V;
-            const float* am = Am + (size_t)q * V * V + w;
-            const float* yb = Y + q * V;
-            int co[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) co[i] = (c0 + i < cin ? c0 + i : cin - 1) * TV;
-            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            for (int v = 0; v < V; ++v) {
-                const float a = am[v * V];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = fmaf(yb[co[i] + v], a, acc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (c0 + i < cin) Z[(c0 + i) * TV + p] = acc[i];
-        }
-    }
-    __syncthreads();
-    const float* wt = wb + L.wt;
-    const float* wr = L.wr >= 0 ? wb + L.wr : nullptr;
-    const float* bias = wb + L.bias;
-    const float slope = L.slope;
-    const bool has_emb = emb && L.embo >= 0;
-    for (int task = wave; task < ngo * nblk; task += NW) {          // channel GEMM + residual + PReLU (+ embedding)
-        const int o0 = (task / nblk) * 8, p = (task % nblk) * 64 + lane;
-        int row[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) row[i] = o0 + i < cout ? o0 + i : cout - 1;
-        if (p < TV) {
-            float acc[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] = bias[row[i]];
-            for (int c = 0; c < cin; ++c) {
-                const float z = Z[c * TV + p];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] = fmaf(wt[row[i] * cin + c], z, acc[i]);
-            }
-            if (wr) {
-                for (int c = 0; c < cin; ++c) {
-                    const float x = X[c * TV + p];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc[i] = fmaf(wr[row[i] * cin + c], x, acc[i]);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc[i] += X[row[i] * TV + p];
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (o0 + i < cout) O[(o0 + i) * TV + p] = prelu(acc[i], slope) + (has_emb ? emb[L.embo + row[i]] : 0.f);
-        }
-    }
-    __syncthreads();
-}
-// joint resampler (stsgcn.py:187-199 over the joint axis): X [C][T][vin] -> O [C][T][vout] (+ skip)
-__device__ void g_resample(const float* wb, int wo, int bo, int C, int T, int vin, int vout, const float* X, float* O, const float* skip) {
-    const float* W = wb + wo;
-    const float* bb = wb + bo;
-    for (int u = threadIdx.x; u < C * T * vout; u += GEN_THREADS) {
-        const int vo = u % vout, ct = u / vout;
-        float a = bb[vo];
-        for (int v = 0; v < vin; ++v) a = fmaf(W[vo * vin + v], X[ct * vin + v], a);
-        if (skip) a += skip[u];
-        O[u] = a;
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreParams P, const FrameMaps M, const GenNet N, int T,
-                                                                    float* __restrict__ scratch) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];
-    const int TV = T * 17, CTV = C0 * TV, tid = threadIdx.x;
-    float* XT = gsm;                  // chain state [c][t][v] over the U-Net frames
-    float* EPS = XT + CTV;            // layer 10's output (+ x)
-    float* ZN = EPS + CTV;            // this step's noise at the U-Net frames
-    float* EMB = ZN + CTV;            // [EMB_TOTAL + 4]
-    float* SE = EMB + EMB_TOTAL + 4;  // [16]
-    float* RED = SE + EDIM;           // [GEN_THREADS]
-    float* slab = scratch + (size_t)blockIdx.x * GEN_SLAB * T;
-    float* A = slab;
-    float* Bb = A + GEN_BUF * T;
-    float* Zb = Bb + GEN_BUF * T;
-    float* D1 = Zb + GEN_BUF * T;
-    float* D2 = D1 + GEN_D1 * T;
-    const float* wb = P.wbuf;
-    const int Tx = P.n_corrupt;
-    const int K = P.ns > 2 ? P.ns - 1 : 1;
-    const int per = C0 * Tx * 17;
-    for (long long chain = blockIdx.x; chain < P.n_chains; chain += gridDim.x) {
-        const int b = (int)(chain / P.S), s = (int)(chain % P.S);
-        const unsigned fixed = (unsigned)(P.win_mask ? P.win_mask[b] : P.fixed_mask);
-        auto tx_of = [&](int t) { return P.win_mask ? __popc(~fixed & ((1u << t) - 1u)) : M.tx_of[t]; };
-        auto src_of = [&](int t) { return P.win_mask ? t : M.src_frame[t]; };
-        __syncthreads();
-        for (int u = tid; u < CTV; u += GEN_THREADS) {
-            const int c = u / TV, t = (u % TV) / 17, v = u % 17;
-            float x;
-            if (P.mode == 1) x = P.x_in[((size_t)b * C0 + c) * TV + t * 17 + v];
-            else if ((fixed >> t) & 1u) x = load_coord(P.dv, b, c, src_of(t), v, P.seg_len);
-            else {
-                const int e = (c * Tx + tx_of(t)) * 17 + v;
-                x = P.noise ? P.noise[((size_t)(s * K + 0) * P.B + b) * per + e]
-                            : philox_normal(P.seed, (unsigned)e, 0u, (unsigned)s, (unsigned)(P.first_window + b));
-            }
-            XT[u] = x;
-        }
-        const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
-        const int i_last = P.mode == 1 ? P.step_single : 1;
-        for (int sidx = i_first; sidx >= i_last; --sidx) {
-            const float* srow = P.step_table + sidx * (4 + EDIM);
-            __syncthreads();
-            if (tid < EDIM) {
-                float e = srow[4 + tid];
-                if (P.cond_emb) e += P.cond_emb[(size_t)b * EDIM + tid];
-                SE[tid] = e / (1.f + expf(-e));
-            }
-            // this step's noise, one thread per (frame, joint pair) like score_kernel (same Philox keys)
-            if (P.mode == 0 && sidx > 1) {
-                const int k = P.ns - sidx;
-                for (int gi = tid; gi < T * 9; gi += GEN_THREADS) {
-                    const int t = gi / 9, v0 = (gi % 9) * 2;
-                    float z[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (!((fixed >> t) & 1u)) {
-                        const int tx = tx_of(t);
-                        if (P.noise) {
-                            const float* zp = P.noise + ((size_t)(s * K + k) * P.B + b) * per + tx * 17 + v0;
-                            z[0] = zp[0]; z[1] = zp[Tx * 17];
-                            if (v0 + 1 < 17) { z[2] = zp[1]; z[3] = zp[Tx * 17 + 1]; }
-                        } else {
-                            philox_normal4(P.seed, (unsigned)(tx * 9 + (v0 >> 1)), (unsigned)k, (unsigned)s, (unsigned)(P.first_window + b), z);
-                        }
-                    }
-                    ZN[t * 17 + v0] = z[0]; ZN[TV + t * 17 + v0] = z[1];
-                    if (v0 + 1 < 17) { ZN[t * 17 + v0 + 1] = z[2]; ZN[TV + t * 17 + v0 + 1] = z[3]; }
-                }
-            }
-            __syncthreads();
-            for (int o = tid; o < EMB_TOTAL; o += GEN_THREADS) {
-                const float* we = wb + N.we + o * EDIM;
-                float a = wb[N.be + o];
-                for (int k = 0; k < EDIM; ++k) a = fmaf(we[k], SE[k], a);
-                EMB[o] = a;
-            }
-            __syncthreads();
-            // ---- the U-Net (stsae_unet.py:406-438)
-            g_layer(wb, N.L[0], T, XT, A, Zb, A, EMB);
-            g_layer(wb, N.L[1], T, A, Bb, Zb, Bb, EMB);
-            g_layer(wb, N.L[2], T, Bb, D1, Zb, D1, EMB);                                         // d1
-            g_resample(wb, N.rs_w[0], N.rs_b[0], 32, T, 17, 12, D1, A, nullptr);                  // down1
-            g_layer(wb, N.L[3], T, A, Bb, Zb, Bb, EMB);
-            g_layer(wb, N.L[4], T, Bb, D2, Zb, D2, EMB);                                         // d2
-            g_resample(wb, N.rs_w[1], N.rs_b[1], 64, T, 12, 10, D2, A, nullptr);                  // down2
-            g_layer(wb, N.L[5], T, A, Bb, Zb, Bb, EMB);
-            g_layer(wb, N.L[6], T, Bb, A, Zb, A, EMB);
-            g_resample(wb, N.rs_w[2], N.rs_b[2], 64, T, 10, 12, A, Bb, D2);                       // up3 + d2
-            g_layer(wb, N.L[7], T, Bb, A, Zb, A, EMB);
-            g_layer(wb, N.L[8], T, A, Bb, Zb, Bb, EMB);
-            g_resample(wb, N.rs_w[3], N.rs_b[3], 32, T, 12, 17, Bb, A, D1);                       // up2 + d1
-            g_layer(wb, N.L[9], T, A, Bb, Zb, Bb, EMB);
-            g_layer(wb, N.L[10], T, Bb, A, Zb, EPS, EMB);
-            // ---- eps = U-Net output + its input; DDPM update of the frame each prediction drives (mocodad.py:172-178,829-838)
-            const float ca = srow[0], cb = srow[1], csg = srow[2];
-            const bool zadd = sidx > 1;
-            float xn[(C0 * MCD_MAX_FRAMES * 17 + GEN_THREADS - 1) / GEN_THREADS];
-            int dst[(C0 * MCD_MAX_FRAMES * 17 + GEN_THREADS - 1) / GEN_THREADS];
-            int it = 0;
-            for (int u = tid; u < CTV; u += GEN_THREADS, ++it) {
-                const int c = u / TV, t = (u % TV) / 17, v = u % 17;
-                const float eps = EPS[u] + XT[u];
-                dst[it] = -1; xn[it] = 0.f;
-                if (P.mode == 1) {
-                    P.eps_out[((size_t)b * C0 + c) * TV + t * 17 + v] = eps;
-                } else {
-                    const int k = P.win_mask ? (((fixed >> t) & 1u) ? -1 : 0) : M.upd_of[t];
-                    if (k >= 0) {
-                        const int tp = P.win_mask ? t : M.pos_of[k];
-                        const int up = c * TV + tp * 17 + v;
-                        xn[it] = ca * (XT[up] - cb * eps) + csg * (zadd ? ZN[up] : 0.f);
-                        dst[it] = up;
-                    }
-                }
-            }
-            __syncthreads();
-            it = 0;
-            for (int u = tid; u < CTV; u += GEN_THREADS, ++it)
-                if (dst[it] >= 0) XT[dst[it]] = xn[it];
-        }
-        if (P.mode == 1) continue;
-        __syncthreads();
-        // ---- loss over the corrupt frames (mocodad.py:484)
-        float part = 0.f;
-        for (int e = tid; e < per; e += GEN_THREADS) {
-            const int c = e / (Tx * 17), tx = (e / 17) % Tx, v = e % 17;
-            int tu = M.pos_of[tx];
-            if (P.win_mask) { int cnt = 0; for (int t = 0; t < T; ++t) if (!((fixed >> t) & 1u)) { if (cnt == tx) tu = t; ++cnt; } }
-            const float x0 = XT[c * TV + tu * 17 + v];
-            const float gt = load_coord(P.dv, b, c, src_of(tu), v, P.seg_len);
-            part += loss_elem(x0, gt, P.loss_fn);
-            if (P.pose_out) P.pose_out[(size_t)(b * P.S + s) * per + e] = x0;
-        }
-        RED[tid] = part;
-        __syncthreads();
-        for (int o = GEN_THREADS / 2; o > 0; o >>= 1) { if (tid < o) RED[tid] += RED[tid + o]; __syncthreads(); }
-        if (tid == 0) P.loss_out[chain] = RED[0] / (float)per;
-    }
-}
-
-// 'E_unet' condition encoder at any frame count (the U-Net's down path without embeddings + to_time_dim), same scratch scheme
-__global__ __launch_bounds__(GEN_THREADS) void cond_unet_generic_kernel(const float* wb, const GenCond N, const DataView dv, const FrameIdx fi,
-                                                                        int seg_len, int T, int B, float* __restrict__ emb_out,
-                                                                        float* __restrict__ scratch) {
-    __shared__ float RED[GEN_THREADS];
-    const int TV = T * 17, tid = threadIdx.x;
-    float* slab = scratch + (size_t)blockIdx.x * GEN_SLAB * T;
-    float* A = slab;
-    float* Bb = A + GEN_BUF * T;
-    float* Zb = Bb + GEN_BUF * T;
-    float* D1 = Zb + GEN_BUF * T;
-    for (int b = blockIdx.x; b < B; b += gridDim.x) {
-        __syncthreads();
-        for (int u = tid; u < C0 * TV; u += GEN_THREADS) {
-            const int c = u / TV, t = (u % TV) / 17, v = u % 17;
-            D1[u] = load_coord(dv, b, c, fi.idx[t], v, seg_len);
-        }
-        __syncthreads();
-        g_layer(wb, N.L[0], T, D1, A, Zb, A, nullptr);
-        g_layer(wb, N.L[1], T, A, Bb, Zb, Bb, nullptr);
-        g_layer(wb, N.L[2], T, Bb, A, Zb, A, nullptr);
-        g_resample(wb, N.rs_w[0], N.rs_b[0], 32, T, 17, 12, A, Bb, nullptr);
-        g_layer(wb, N.L[3], T, Bb, A, Zb, A, nullptr);
-        g_layer(wb, N.L[4], T, A, Bb, Zb, Bb, nullptr);
-        g_resample(wb, N.rs_w[1], N.rs_b[1], 64, T, 12, 10, Bb, A, nullptr);
-        g_layer(wb, N.L[5], T, A, Bb, Zb, Bb, nullptr);
-        g_layer(wb, N.L[6], T, Bb, A, Zb, A, nullptr);            // -> A [6][T][10]
-        const int F = CU_OUT * T * 10;
-        for (int jo = 0; jo < EDIM; ++jo) {
-            float a = 0.f;
-            for (int k = tid; k < F; k += GEN_THREADS) a = fmaf(wb[N.lw + (size_t)jo * F + k], A[k], a);
-            RED[tid] = a;
-            __syncthreads();
-            for (int o = GEN_THREADS / 2; o > 0; o >>= 1) { if (tid < o) RED[tid] += RED[tid + o]; __syncthreads(); }
-            if (tid == 0) emb_out[(size_t)b * EDIM + jo] = RED[0] + wb[N.lb + jo];
-            __syncthreads();
-        }
-    }
-}
 
 // scatter-max of window scores to frames (mocodad.py:392-393 + eval_utils.py:27-34); scores >= 0
 __global__ void scatter_max_kernel(const float* __restrict__ scores, const int* __restrict__ frames,
@@ -826,118 +399,6 @@ __global__ __launch_bounds__(256) void frame_scores_kernel(const FrameParams Q) 
 // ================================================================================================
 // host side
 // ================================================================================================
-struct TensorMap {
-    std::unordered_map<std::string, std::pair<const float*, int64_t>> m;
-    std::string missing;
-    const float* get(const std::string& name, int64_t numel) {
-        auto it = m.find(name);
-        if (it == m.end()) { if (missing.empty()) missing = "missing tensor " + name; return nullptr; }
-        if (it->second.second != numel) {
-            if (missing.empty()) missing = "tensor " + name + " has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel);
-            return nullptr;
-        }
-        return it->second.first;
-    }
-    bool has(const std::string& name) const { return m.count(name) != 0; }
-};
-
-struct Folded { std::vector<double> w, b; };  // BN-folded 1x1 conv: w[cout][cin], b[cout]
-
-// conv (cout,cin,1,1)+bias followed by eval BatchNorm2d (eps 1e-5): W' = s W, b' = s (b - mu) + beta
-bool fold_conv_bn(TensorMap& tm, const std::string& conv, const std::string& bn, int cout, int cin, Folded& f) {
-    const float* w = tm.get(conv + ".weight", (int64_t)cout * cin);
-    const float* b = tm.get(conv + ".bias", cout);
-    const float* g = tm.get(bn + ".weight", cout);
-    const float* be = tm.get(bn + ".bias", cout);
-    const float* mu = tm.get(bn + ".running_mean", cout);
-    const float* var = tm.get(bn + ".running_var", cout);
-    if (!w || !b || !g || !be || !mu || !var) return false;
-    f.w.resize((size_t)cout * cin); f.b.resize(cout);
-    for (int o = 0; o < cout; ++o) {
-        const double s = (double)g[o] / sqrt((double)var[o] + 1e-5);
-        for (int i = 0; i < cin; ++i) f.w[(size_t)o * cin + i] = s * (double)w[(size_t)o * cin + i];
-        f.b[o] = s * ((double)b[o] - (double)mu[o]) + (double)be[o];
-    }
-    return true;
-}
-
-struct Builder {
-    std::vector<float> buf;
-    int alloc(size_t n) { size_t o = (buf.size() + 3) & ~size_t(3); buf.resize(o + n, 0.f); return (int)o; }
-};
-
-// Tq[q][v][t] = T[v][t][q]; A copied
-bool pack_mix(TensorMap& tm, const std::string& p, int T, int V, Builder& B, int& tq, int& am) {
-    const float* Tm = tm.get(p + ".gcn.T", (int64_t)V * T * T);
-    const float* A = tm.get(p + ".gcn.A", (int64_t)T * V * V);
-    if (!Tm || !A) return false;
-    tq = B.alloc((size_t)T * V * T);
-    for (int q = 0; q < T; ++q) for (int v = 0; v < V; ++v) for (int t = 0; t < T; ++t)
-        B.buf[tq + (q * V + v) * T + t] = Tm[(v * T + t) * T + q];
-    am = B.alloc((size_t)T * V * V);
-    memcpy(&B.buf[am], A, sizeof(float) * T * V * V);
-    return true;
-}
-
-// fragment-order coefficients for the MFMA mix (see mix_stage)
-// (TP > T: the tables of a frame count padded to TP -- score_tiled_kernel -- with zero coefficients for the pad frames)
-bool pack_mix_mfma(TensorMap& tm, const std::string& p, int T, int V, Builder& B, int& tqf, int& af, int TP = 0) {
-    const float* Tm = tm.get(p + ".gcn.T", (int64_t)V * T * T);
-    const float* A = tm.get(p + ".gcn.A", (int64_t)T * V * V);
-    if (!Tm || !A) return false;
-    if (TP < T) TP = T;
-    const int KS = (V + 3) / 4, MT = (V + 15) / 16;
-    const int NR = (KS * TP + 15) / 16;
-    // (+ MIX_QPAD zero rows: the ragged frame groups of 5 / 7 / 11 frames compute up to one output frame beyond the last)
-    tqf = B.alloc((size_t)(TP + MIX_QPAD) * NR * 64);
-    af = B.alloc((size_t)(TP + MIX_QPAD) * MT * KS * 64);
-    for (int q = 0; q < T; ++q) for (int r = 0; r < NR; ++r) for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 15, g = lane >> 4, idx = r * 16 + i, s = idx / TP, t = idx % TP, v = mix_vmap(V, s, g);
-        B.buf[tqf + (q * NR + r) * 64 + lane] = (idx < KS * TP && v < V && t < T) ? Tm[(v * T + t) * T + q] : 0.f;
-    }
-    for (int q = 0; q < T; ++q) for (int s = 0; s < KS; ++s) for (int lane = 0; lane < 64; ++lane) {
-        const int j = lane & 15, g = lane >> 4, v = mix_vmap(V, s, g);
-        for (int mt = 0; mt < MT; ++mt) {
-            // m-tile 0: MFMA A fragment (output joint 16mt + j).  V = 17: the one joint beyond it is mixed on the VALU
-            // (mix_stage), its coefficient A_q[v][16] replicated over the 16 lanes of the group
-            const int w = (V == 17 && mt == 1) ? 16 : mt * 16 + j;
-            B.buf[af + ((q * MT + mt) * KS + s) * 64 + lane] = (v < V && w < V) ? A[(q * V + v) * V + w] : 0.f;
-        }
-    }
-    return true;
-}
-
-// time-mix coefficients of one layer as the A fragments of tl_time_mix: [joint v][frame tile of a chain][k-step][lane], lane
-// (i, g) = gcn.T[v][t = 4 ks + g][q], q = row i of the tile (tiles follow the layer's frame groups, TlGroups)
-int pack_time_mfma(const float* Tm, int T, int V, int TP, int NB, Builder& B) {
-    const int ngrp = tl_ngrp(V), nch = NB >= ngrp ? NB / ngrp : 1, fgc = NB * TP / ngrp / nch;
-    const int mtg = (fgc + 15) / 16, ntc = mtg * (TP / fgc), kt = TP / 4;
-    const int off = B.alloc((size_t)V * ntc * kt * 64);
-    for (int v = 0; v < V; ++v) for (int tile = 0; tile < ntc; ++tile) for (int ks = 0; ks < kt; ++ks) for (int lane = 0; lane < 64; ++lane) {
-        const int i = lane & 15, g = lane >> 4, t = 4 * ks + g, r = (tile % mtg) * 16 + i, q = (tile / mtg) * fgc + r;
-        B.buf[off + ((size_t)(v * ntc + tile) * kt + ks) * 64 + lane] = (r < fgc && q < T && t < T) ? Tm[((size_t)v * T + t) * T + q] : 0.f;
-    }
-    return off;
-}
-
-// MFMA A-operand fragment order of a logical [M][K] matrix (M, K multiples of 16) with the K permutation that lets
-// one ds_read_b128 of the B operand feed four k-steps (see gemm_tiles): element e of lane (i, g) in group kq is
-// W[16 mt + i][16 kq + 4 g + e]  (k-step e of the group covers channels {16 kq + 4 g + e : g = 0..3}).
-template <class F>
-int pack_gemm_frags(Builder& B, int M, int K, F&& w) {
-    const int MTn = M / 16, KQ = K / 16;
-    const int off = B.alloc((size_t)MTn * KQ * 64 * 4);
-    for (int mt = 0; mt < MTn; ++mt) for (int kq = 0; kq < KQ; ++kq) for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 4; ++e) {
-            const int row = mt * 16 + (lane & 15), g = lane >> 4;
-            B.buf[off + ((size_t)(mt * KQ + kq) * 64 + lane) * 4 + e] = (float)w(row, kq * 16 + 4 * g + e);
-        }
-    return off;
-}
-
-}  // namespace
-
-namespace {
 
 // Dispatch to the launchers of mcd_inst.hip is generated from the tables of mcd_instances.hpp (this file only CALLS launchers).
 // score_kernel<T, ...>: the production form (or, in a build that holds tuning variants, the workgroup shape MCD_OPT_VARIANT
@@ -1122,196 +583,27 @@ int launch_cond_view(const mcd_weights* w, CondRoute r, const DataView& data, co
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
-// The condition encoder of a handle (pose model and latent model alike): folded weights, mix tables and GEMM fragments appended to
-// the builder, and where they went.  has: strategy inject; unet: the 'E_unet' architecture; fast: the shipped channel list at a
-// frame count cond_fast_kernel is instantiated for.  The table words are written by write_cond_table once the buffer is complete.
-struct CondPack {
-    CondW Cw;
-    bool has, unet, fast;
-    bool fast_table;                // cond_fast_body's table is packed: fast, or asked for by the caller that runs the body itself
-    int ctab[4][F_STRIDE];          // cond_fast_body's table
-    int utab[TABC_ULB + 1];         // cond table of the 'E_unet' encoder: 7 layers, 2 resamplers, Linear
-    TiledNet TNc;                   // ... and its tables for score_tiled_kernel<.., COND> (13 .. 32 condition frames)
-    int tiled_cond_tp;
-    GenCond GC;                     // plain layout for cond_unet_generic_kernel
-};
-// want_fast_table: pack cond_fast_body's table for the shipped channel list even where this library holds no cond_fast_kernel for
-// the frame count (the latent encode launch runs the body itself)
-int pack_cond_encoder(TensorMap& tm, const mcd_model_cfg_t* cfg, Builder& B, CondPack& cp, bool want_fast_table = false) {
-    memset(&cp, 0, sizeof(cp));
-    CondW& Cw = cp.Cw;
-    bool& cond_fast = cp.fast;
-    auto& ctab = cp.ctab;
-    auto& utab = cp.utab;
-    TiledNet& TNc = cp.TNc;
-    int& tiled_cond_tp = cp.tiled_cond_tp;
-    GenCond& GC = cp.GC;
-    const bool has_cond = cfg->strategy == MCD_STRATEGY_INJECT;
-    const bool cond_unet = has_cond && cfg->cond_layers == MCD_COND_UNET;
-    cp.has = has_cond; cp.unet = cond_unet;
-    if (cond_unet) {
-        const int Tc = cfg->t_cond;
-        if (Tc < 1 || Tc > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "condition frames must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-        Cw.Tc = Tc; Cw.latent = EDIM;
-        static const char* unames[7] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1", "st_gcnnsd3.0", "st_gcnnsd3.1"};
-        static const int ucin[7] = {C0, 16, 32, 32, 64, 64, 128}, ucout[7] = {16, 32, 32, 64, 64, 128, CU_OUT}, uv[7] = {17, 17, 17, 12, 12, 10, 10};
-        for (int l = 0; l < 7; ++l) {
-            const int cinr = ucin[l], cout = ucout[l], cinp = cinr < 16 ? 16 : cinr;
-            const std::string p = std::string("condition_encoder.") + unames[l];
-            Folded ft, fr;
-            const bool res = cinr != cout;
-            if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", cout, cinr, ft)) return fail(MCD_EMISSING, tm.missing);
-            if (res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", cout, cinr, fr)) return fail(MCD_EMISSING, tm.missing);
-            const float* sl = tm.get(p + ".prelu.weight", 1);
-            if (!sl) return fail(MCD_EMISSING, tm.missing);
-            int tq = 0, am = 0;
-            if (!pack_mix_mfma(tm, p, Tc, uv[l], B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-            const int wp = pack_gemm_frags(B, ceil16(cout), cinp * (res ? 2 : 1), [&](int r, int k) -> double {
-                const bool second = k >= cinp;
-                const int kk = second ? k - cinp : k;
-                if (r >= cout || kk >= cinr) return 0.0;
-                return second ? fr.w[(size_t)r * cinr + kk] : ft.w[(size_t)r * cinr + kk];
-            });
-            const int bias = B.alloc(ceil16(cout));
-            for (int o = 0; o < cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
-            utab[l * F_STRIDE + F_TQ] = tq; utab[l * F_STRIDE + F_AM] = am; utab[l * F_STRIDE + F_WP] = wp; utab[l * F_STRIDE + F_BIAS] = bias;
-            memcpy(&utab[l * F_STRIDE + F_SLOPE], &sl[0], sizeof(float));
-            {   // plain layout for cond_unet_generic_kernel
-                GLayer& g = GC.L[l];
-                g.cin = cinr; g.cout = cout; g.V = uv[l]; g.slope = sl[0]; g.embo = -1;
-                if (!pack_mix(tm, p, Tc, uv[l], B, g.tq, g.am)) return fail(MCD_EMISSING, tm.missing);
-                g.wt = B.alloc(ft.w.size());
-                for (size_t i = 0; i < ft.w.size(); ++i) B.buf[g.wt + i] = (float)ft.w[i];
-                g.wr = -1;
-                if (res) { g.wr = B.alloc(fr.w.size()); for (size_t i = 0; i < fr.w.size(); ++i) B.buf[g.wr + i] = (float)fr.w[i]; }
-                g.bias = B.alloc(cout);
-                for (int o = 0; o < cout; ++o) B.buf[g.bias + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
-            }
+// The device copy of a packed buffer (and, with `tune`, the trajectory kernel's 4 tuning words, zeroed) on `device`, leaving the
+// calling thread's current device as it was.  On an error nothing stays allocated.
+int upload_packed(const std::vector<float>& buf, int device, float** dbuf, int** tune = nullptr) {
+    int prev_dev = 0;
+    HIP_TRY(hipGetDevice(&prev_dev));
+    HIP_TRY(hipSetDevice(device));
+    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_dev};
+    *dbuf = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(dbuf), buf.size() * sizeof(float));
+    if (e != hipSuccess) return fail(MCD_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+    e = hipMemcpy(*dbuf, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(*dbuf); return fail(MCD_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+    if (tune) {
+        *tune = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(tune), 4 * sizeof(int)) != hipSuccess || hipMemset(*tune, 0, 4 * sizeof(int)) != hipSuccess) {
+            if (*tune) (void)hipFree(*tune);
+            (void)hipFree(*dbuf);
+            return fail(MCD_EDEVICE, "hipMalloc (tuning words)");
         }
-        static const char* urs[2] = {"down1", "down2"};
-        static const int urin[2] = {17, 12}, urout[2] = {12, 10};
-        for (int r = 0; r < 2; ++r) {
-            Folded f;
-            const std::string p = std::string("condition_encoder.") + urs[r];
-            if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", urout[r], urin[r], f)) return fail(MCD_EMISSING, tm.missing);
-            const int vin = urin[r], vout = urout[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
-            const int wf = B.alloc((size_t)MTr * KS * 64), bo = B.alloc(32);
-            for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-                const int vo = mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
-                B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-            }
-            for (int vo = 0; vo < vout; ++vo) B.buf[bo + vo] = (float)f.b[vo];
-            utab[TABC_URS + 2 * r] = wf; utab[TABC_URS + 2 * r + 1] = bo;
-            GC.rs_w[r] = B.alloc((size_t)vout * vin);
-            for (size_t i = 0; i < f.w.size(); ++i) B.buf[GC.rs_w[r] + i] = (float)f.w[i];
-            GC.rs_b[r] = B.alloc(vout);
-            for (int vo = 0; vo < vout; ++vo) B.buf[GC.rs_b[r] + vo] = (float)f.b[vo];
-        }
-        const int64_t F = (int64_t)CU_OUT * Tc * 10;
-        const float* lw = tm.get("condition_encoder.to_time_dim.weight", F * EDIM);
-        const float* lb = tm.get("condition_encoder.to_time_dim.bias", EDIM);
-        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        utab[TABC_ULW] = B.alloc(F * EDIM); memcpy(&B.buf[utab[TABC_ULW]], lw, sizeof(float) * F * EDIM);
-        utab[TABC_ULB] = B.alloc(EDIM); memcpy(&B.buf[utab[TABC_ULB]], lb, sizeof(float) * EDIM);
-        GC.lw = utab[TABC_ULW]; GC.lb = utab[TABC_ULB];
-        tiled_cond_tp = cond_unet_has_kernel(Tc) ? 0 : tiled_cond_tp_for(Tc);
-        if (tiled_cond_tp) {      // the slab-tiled MFMA stages: mix tables for the padded frame count; GEMM fragments, biases, slopes as above
-            for (int l = 0; l < 7; ++l) {
-                const std::string p = std::string("condition_encoder.") + unames[l];
-                if (!pack_mix_mfma(tm, p, Tc, uv[l], B, TNc.tq[l], TNc.am[l], tiled_cond_tp)) return fail(MCD_EMISSING, tm.missing);
-                const float* Tm = tm.get(p + ".gcn.T", (int64_t)uv[l] * Tc * Tc);
-                if (!Tm) return fail(MCD_EMISSING, tm.missing);
-                TNc.tqm[l] = pack_time_mfma(Tm, Tc, uv[l], tiled_cond_tp, tl_nb(tiled_cond_tp), B);
-                TNc.wp[l] = utab[l * F_STRIDE + F_WP]; TNc.bias[l] = utab[l * F_STRIDE + F_BIAS];
-                memcpy(&TNc.slope[l], &utab[l * F_STRIDE + F_SLOPE], sizeof(float));
-            }
-            for (int r = 0; r < 2; ++r) {
-                Folded f;
-                const std::string p = std::string("condition_encoder.") + urs[r];
-                if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", urout[r], urin[r], f)) return fail(MCD_EMISSING, tm.missing);
-                const int vin = urin[r], vout = urout[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
-                const int wf = B.alloc((size_t)MTr * KS * 64 + 32);
-                for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-                    const int vo = mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
-                    B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-                }
-                for (int vo = 0; vo < vout; ++vo) B.buf[wf + MTr * KS * 64 + vo] = (float)f.b[vo];
-                TNc.rsw[r] = wf;
-            }
-            TNc.we = utab[TABC_ULW]; TNc.be = utab[TABC_ULB];
-        }
-    } else if (has_cond) {
-        if (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS) return fail(MCD_EINVAL, "bad cond_layers");
-        if (cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "condition frames must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-        Cw.n_layers = cfg->cond_layers; Cw.Tc = cfg->t_cond; Cw.latent = EDIM; Cw.cmax = C0;
-        int cin = C0;
-        for (int l = 0; l < Cw.n_layers; ++l) {
-            const int cout = cfg->cond_channels[l];
-            if (cout < 1 || cout > 128) return fail(MCD_EUNSUPPORTED, "condition-encoder channels must be in 1..128");
-            const std::string p = "condition_encoder.encoder.model_layers." + std::to_string(l);
-            Cw.cin[l] = cin; Cw.cout[l] = cout; if (cout > Cw.cmax) Cw.cmax = cout;
-            if (!pack_mix(tm, p, Cw.Tc, 17, B, Cw.tq[l], Cw.am[l])) return fail(MCD_EMISSING, tm.missing);
-            Folded ft, fr;
-            if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
-            const bool res = cin != cout;
-            if (res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
-            const float* sl = tm.get(p + ".prelu.weight", 1);
-            if (!sl) return fail(MCD_EMISSING, tm.missing);
-            Cw.slope[l] = sl[0];
-            Cw.wt[l] = B.alloc(ft.w.size());
-            for (size_t i = 0; i < ft.w.size(); ++i) B.buf[Cw.wt[l] + i] = (float)ft.w[i];
-            Cw.wr[l] = -1;
-            if (res) { Cw.wr[l] = B.alloc(fr.w.size()); for (size_t i = 0; i < fr.w.size(); ++i) B.buf[Cw.wr[l] + i] = (float)fr.w[i]; }
-            Cw.bias[l] = B.alloc(cout);
-            for (int o = 0; o < cout; ++o) B.buf[Cw.bias[l] + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
-            cin = cout;
-        }
-        const int64_t F = (int64_t)cin * Cw.Tc * 17;
-        const float* lw = tm.get("condition_encoder.btlnk.weight", F * EDIM);
-        const float* lb = tm.get("condition_encoder.btlnk.bias", EDIM);
-        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        Cw.lw = B.alloc(F * EDIM); memcpy(&B.buf[Cw.lw], lw, sizeof(float) * F * EDIM);
-        Cw.lb = B.alloc(EDIM); memcpy(&B.buf[Cw.lb], lb, sizeof(float) * EDIM);
-        // fast path (cond_fast_kernel): the shipped architecture at a frame count the MFMA stages are instantiated for
-        const bool shipped_list = Cw.n_layers == 4 && Cw.cout[0] == 32 && Cw.cout[1] == 16 && Cw.cout[2] == 32 && Cw.cout[3] == 32;
-        cond_fast = shipped_list && cond_fast_has_kernel(Cw.Tc);
-        cp.fast_table = cond_fast || (shipped_list && want_fast_table);
-        if (cp.fast_table) {
-            int cinr = C0;
-            for (int l = 0; l < 4; ++l) {
-                const int cout = Cw.cout[l], cinp = l == 0 ? 16 : cinr;
-                const std::string p = "condition_encoder.encoder.model_layers." + std::to_string(l);
-                Folded ft, fr;
-                const bool res = cinr != cout;
-                fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", cout, cinr, ft);
-                if (res) fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", cout, cinr, fr);
-                int tq = 0, am = 0;
-                pack_mix_mfma(tm, p, Cw.Tc, 17, B, tq, am);
-                const int wp = pack_gemm_frags(B, ceil16(cout), cinp * (res ? 2 : 1), [&](int r, int k) -> double {
-                    const bool second = k >= cinp;
-                    const int kk = second ? k - cinp : k;
-                    if (r >= cout || kk >= cinr) return 0.0;
-                    return second ? fr.w[(size_t)r * cinr + kk] : ft.w[(size_t)r * cinr + kk];
-                });
-                const int bias = B.alloc(ceil16(cout));
-                for (int o = 0; o < cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (res ? fr.b[o] : 0.0));
-                ctab[l][F_TQ] = tq; ctab[l][F_AM] = am; ctab[l][F_WP] = wp; ctab[l][F_BIAS] = bias;
-                memcpy(&ctab[l][F_SLOPE], &Cw.slope[l], sizeof(float));
-                cinr = cout;
-            }
-        }
-        const size_t lds = ((size_t)3 * Cw.cmax * Cw.Tc * 17 + CE_THREADS) * 4;
-        Cw.gmode = lds > 160 * 1024;
-        if (((size_t)2 * Cw.cmax * Cw.Tc * 17 + CE_THREADS) * 4 > 160 * 1024) return fail(MCD_EUNSUPPORTED, "condition encoder activations exceed LDS");
     }
     return MCD_OK;
-}
-void write_cond_table(int* tab, const CondPack& cp) {
-    if (cp.unet) for (int i = 0; i <= TABC_ULB; ++i) tab[TABC + i] = cp.utab[i];
-    if (cp.fast_table) {
-        for (int l = 0; l < 4; ++l) for (int f = 0; f < F_STRIDE; ++f) tab[TABC + l * F_STRIDE + f] = cp.ctab[l][f];
-        tab[TABC + TABC_LW] = cp.Cw.lw; tab[TABC + TABC_LB] = cp.Cw.lb;
-    }
 }
 }  // namespace
 
@@ -1348,180 +640,33 @@ int32_t mcd_abi_version(void) { return MCD_ABI_VERSION; }
 int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t device,
                      mcd_weights_t** out) {
     if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
-    if (cfg->num_coords != C0) return fail(MCD_EUNSUPPORTED, "num_coords must be 2");
-    if (cfg->n_joints != 17) return fail(MCD_EUNSUPPORTED, "n_joints must be 17 (the reference U-Net hard-wires 17/12/10 joints)");
-    if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
-    const int T = cfg->t_unet;
-    if (T < 1 || T > MCD_MAX_FRAMES) return fail(MCD_EUNSUPPORTED, "U-Net frame count must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    const bool fast_unet = score_has_kernel(T);     // the instantiated score_kernel<T,...>
-    GenNet G;
-    memset(&G, 0, sizeof(G));
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
-
-    Builder B;
-    struct HostLayer { int tq, am, wp, bias; float slope; };
-    struct { HostLayer L[NLAYERS]; int we, be, rs_w[4], rs_b[4]; } U;
-    memset(&U, 0, sizeof(U));
-    B.alloc(TAB_FLOATS);  // offset table lives at the start of the buffer
-    static const char* names[NLAYERS] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1",
-                                         "st_gcnnsd3.0", "st_gcnnsd3.1", "st_gcnnsu4.0", "st_gcnnsu4.1", "st_gcnnsu3.0",
-                                         "st_gcnnsu3.1"};
-    U.we = B.alloc((size_t)EMB_TOTAL * EDIM);
-    U.be = B.alloc(EMB_TOTAL + 28);
-    for (int l = 0; l < NLAYERS; ++l) {
-        const LDesc D = layer_desc(l);
-        const std::string p = std::string("model.") + names[l];
-        if (!pack_mix_mfma(tm, p, T, D.V, B, U.L[l].tq, U.L[l].am)) return fail(MCD_EMISSING, tm.missing);
-        const int cin = l == 0 ? C0 : D.cin;   // real input channels (layer 0 is zero-padded to one 16-channel block)
-        Folded ft, fr;
-        if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", D.cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
-        if (D.res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", D.cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
-        const float* sl = tm.get(p + ".prelu.weight", 1);
-        const float* we = tm.get(p + ".emb_layer.1.weight", (int64_t)D.cout * EDIM);
-        const float* be = tm.get(p + ".emb_layer.1.bias", D.cout);
-        if (!sl || !we || !be) return fail(MCD_EMISSING, tm.missing);
-        U.L[l].slope = sl[0];
-        memcpy(&B.buf[U.we + (size_t)emb_off(l) * EDIM], we, sizeof(float) * D.cout * EDIM);
-        memcpy(&B.buf[U.be + emb_off(l)], be, sizeof(float) * D.cout);
-        {   // plain layout for the runtime-shape kernel
-            GLayer& g = G.L[l];
-            g.cin = cin; g.cout = D.cout; g.V = D.V; g.slope = sl[0]; g.embo = emb_off(l);
-            if (!pack_mix(tm, p, T, D.V, B, g.tq, g.am)) return fail(MCD_EMISSING, tm.missing);
-            g.wt = B.alloc(ft.w.size());
-            for (size_t i = 0; i < ft.w.size(); ++i) B.buf[g.wt + i] = (float)ft.w[i];
-            g.wr = -1;
-            if (D.res) { g.wr = B.alloc(fr.w.size()); for (size_t i = 0; i < fr.w.size(); ++i) B.buf[g.wr + i] = (float)fr.w[i]; }
-            g.bias = B.alloc(D.cout);
-            for (int o = 0; o < D.cout; ++o) B.buf[g.bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
-        }
-        const int mpad = ceil16(D.cout);
-        U.L[l].bias = B.alloc(mpad);
-        for (int o = 0; o < D.cout; ++o) B.buf[U.L[l].bias + o] = (float)(ft.b[o] + (D.res ? fr.b[o] : 0.0));
-        // MFMA fragment order.  Logical matrix Wcat[M][K] (cinp = input channels padded to 16):
-        //   mix-first layers: M = cout, K = cinp (W_t') + cinp (W_r', when the layer has a residual conv)
-        //   W-first layers 6, 8 and 10: M = [W_t' ; W_r'] stacked (layer 10: rows 0,1 / 2,3 of one 16-row tile), K = cinp
-        const bool wfirst = (l == 6 || l == 10 || l == 8);
-        const int cinp = D.cin;
-        const int M = (l == 6 || l == 8) ? 2 * D.cout : mpad;
-        const int Kc = wfirst ? cinp : cinp * (D.res ? 2 : 1);
-        auto wt = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? ft.w[(size_t)r * cin + k] : 0.0; };
-        auto wr = [&](int r, int k) -> double { return (r < D.cout && k < cin) ? fr.w[(size_t)r * cin + k] : 0.0; };
-        auto wcat = [&](int r, int k) -> double {
-            if (wfirst) return r < D.cout ? wt(r, k) : (r < 2 * D.cout ? wr(r - D.cout, k) : 0.0);
-            return k < cinp ? wt(r, k) : wr(r, k - cinp);
-        };
-        if (l == 10) {
-            // layer 10's W-first product has 4 useful rows ([W_t' ; W_r'], 2 + 2): kept as plain rows for the FMA path
-            U.L[l].wp = B.alloc(4 * 32);
-            for (int r = 0; r < 4; ++r) for (int k = 0; k < 32; ++k) B.buf[U.L[l].wp + r * 32 + k] = (float)wcat(r, k);
-        } else {
-            U.L[l].wp = pack_gemm_frags(B, M, Kc, wcat);
-        }
-    }
-    static const char* rs_names[4] = {"down1", "down2", "up3", "up2"};
-    static const int rs_in[4] = {17, 12, 10, 12}, rs_out[4] = {12, 10, 12, 17};
-    for (int r = 0; r < 4; ++r) {
-        Folded f;
-        const std::string p = std::string("model.") + rs_names[r];
-        if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", rs_out[r], rs_in[r], f)) return fail(MCD_EMISSING, tm.missing);
-        const int vin = rs_in[r], vout = rs_out[r];
-        const bool capture = r < 2;   // the down-samplers capture the skip tensors (see resample_stage)
-        const int KS = capture ? (vin > 16 ? 5 : 4) : (vin + 3) / 4, MTr = (vout + 15) / 16;
-        U.rs_w[r] = B.alloc((size_t)MTr * KS * 64);
-        U.rs_b[r] = B.alloc(32);
-        for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-            // vout = 17: the second fragment holds joint 16's weights replicated over each lane group (VALU path)
-            const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(capture, vin, ks, lane >> 4);
-            B.buf[U.rs_w[r] + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-        }
-        for (int vo = 0; vo < vout; ++vo) B.buf[U.rs_b[r] + vo] = (float)f.b[vo];
-        G.rs_w[r] = B.alloc((size_t)vout * vin);
-        for (size_t i = 0; i < f.w.size(); ++i) B.buf[G.rs_w[r] + i] = (float)f.w[i];
-        G.rs_b[r] = B.alloc(vout);
-        for (int vo = 0; vo < vout; ++vo) B.buf[G.rs_b[r] + vo] = (float)f.b[vo];
-    }
-    G.we = U.we; G.be = U.be;
-    // tables of score_tiled_kernel (frame counts without a score_kernel, up to its largest padded one): mix coefficients for the padded frame count, non-capture resampler packs;
-    // GEMM fragments, biases, slopes and the embedding Linear are the specialised kernels' own
-    TiledNet TN;
-    memset(&TN, 0, sizeof(TN));
-    const int tiled_tp = fast_unet ? 0 : tiled_tp_for(T);
-    if (tiled_tp) {
-        for (int l = 0; l < NLAYERS; ++l) {
-            const LDesc D = layer_desc(l);
-            if (!pack_mix_mfma(tm, std::string("model.") + names[l], T, D.V, B, TN.tq[l], TN.am[l], tiled_tp)) return fail(MCD_EMISSING, tm.missing);
-            TN.tqm[l] = pack_time_mfma(tm.get(std::string("model.") + names[l] + ".gcn.T", (int64_t)D.V * T * T), T, D.V, tiled_tp, tl_nb(tiled_tp), B);
-            TN.wp[l] = U.L[l].wp; TN.bias[l] = U.L[l].bias; TN.slope[l] = U.L[l].slope;
-            if (l == 6 || l == 8) {    // this kernel runs layers 6 and 8 mix-first like the others: [W_t' | W_r'] fragments (the specialised kernels' are W-first)
-                Folded ft, fr;
-                const std::string p6 = std::string("model.") + names[l];
-                if (!fold_conv_bn(tm, p6 + ".tcn.0", p6 + ".tcn.1", D.cout, D.cin, ft) || !fold_conv_bn(tm, p6 + ".residual.0", p6 + ".residual.1", D.cout, D.cin, fr))
-                    return fail(MCD_EMISSING, tm.missing);
-                TN.wp[l] = pack_gemm_frags(B, D.cout, 2 * D.cin, [&](int r, int k) -> double {
-                    return k < D.cin ? ft.w[(size_t)r * D.cin + k] : fr.w[(size_t)r * D.cin + k - D.cin]; });
-            }
-        }
-        for (int r = 0; r < 4; ++r) {
-            Folded f;
-            if (!fold_conv_bn(tm, std::string("model.") + rs_names[r] + ".block.0", std::string("model.") + rs_names[r] + ".block.1", rs_out[r], rs_in[r], f))
-                return fail(MCD_EMISSING, tm.missing);
-            const int vin = rs_in[r], vout = rs_out[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
-            const int wf = B.alloc((size_t)MTr * KS * 64 + 32);
-            for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-                const int vo = (vout == 17 && mt == 1) ? 16 : mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
-                B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-            }
-            for (int vo = 0; vo < vout; ++vo) B.buf[wf + MTr * KS * 64 + vo] = (float)f.b[vo];
-            TN.rsw[r] = wf;
-        }
-        TN.we = U.we; TN.be = U.be;
-    }
-    // condition encoder
-    CondPack cp;
-    {
-        const int rc = pack_cond_encoder(tm, cfg, B, cp);
-        if (rc != MCD_OK) return rc;
-    }
-    CondW& Cw = cp.Cw;
-    const bool has_cond = cp.has, cond_unet = cp.unet, cond_fast = cp.fast;
-    const int tiled_cond_tp = cp.tiled_cond_tp;
-    const TiledNet& TNc = cp.TNc;
-    const GenCond& GC = cp.GC;
-    {
-        int* tab = reinterpret_cast<int*>(B.buf.data());
-        for (int l = 0; l < NLAYERS; ++l) {
-            tab[l * F_STRIDE + F_TQ] = U.L[l].tq; tab[l * F_STRIDE + F_AM] = U.L[l].am;
-            tab[l * F_STRIDE + F_WP] = U.L[l].wp; tab[l * F_STRIDE + F_BIAS] = U.L[l].bias;
-            memcpy(&tab[l * F_STRIDE + F_SLOPE], &U.L[l].slope, sizeof(float));
-        }
-        tab[TAB_WE] = U.we; tab[TAB_BE] = U.be;
-        write_cond_table(tab, cp);
-        for (int r = 0; r < 4; ++r) { tab[TAB_RSW + r] = U.rs_w[r]; tab[TAB_RSB + r] = U.rs_b[r]; }
-    }
-    const int zero_row = B.alloc(32);
-    // upload on `device`, leaving the calling thread's current device as it was
-    int prev_dev = 0;
-    HIP_TRY(hipGetDevice(&prev_dev));
-    HIP_TRY(hipSetDevice(device));
-    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_dev};
+    PackedModel m;
+    int rc = pack_pose_model(tensors, n_tensors, cfg, m);
+    if (rc != MCD_OK) return rc;
+    float* dbuf = nullptr;
+    int* tune = nullptr;
+    rc = upload_packed(m.buf, device, &dbuf, &tune);
+    if (rc != MCD_OK) return rc;
     mcd_weights* w = new mcd_weights();
     memset(w->opt, 0, sizeof(w->opt));
-    w->zero_row = zero_row; w->fast_unet = fast_unet; w->gen = G; w->gcond = GC; w->tiled = TN; w->tiled_tp = tiled_tp; w->tiled_cond = TNc; w->tiled_cond_tp = tiled_cond_tp;
-    w->cfg = *cfg; w->device = device; w->n_floats = B.buf.size(); w->has_cond = has_cond; w->cond_fast = cond_fast; w->cond_unet = cond_unet;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->dbuf), B.buf.size() * sizeof(float));
-    if (e != hipSuccess) { delete w; return fail(MCD_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipMemcpy(w->dbuf, B.buf.data(), B.buf.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(w->dbuf); delete w; return fail(MCD_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
-    w->tune = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&w->tune), 4 * sizeof(int)) != hipSuccess || hipMemset(w->tune, 0, 4 * sizeof(int)) != hipSuccess) {
-        if (w->tune) (void)hipFree(w->tune);
-        (void)hipFree(w->dbuf); delete w;
-        return fail(MCD_EDEVICE, "hipMalloc (tuning words)");
-    }
-    Cw.base = w->dbuf;
-    w->cond = Cw;
+    w->cfg = *cfg; w->device = device; w->dbuf = dbuf; w->tune = tune; w->n_floats = m.buf.size();
+    w->zero_row = m.zero_row; w->fast_unet = m.fast_unet != 0; w->gen = m.gen; w->tiled = m.tiled; w->tiled_tp = m.tiled_tp;
+    w->gcond = m.cond.GC; w->tiled_cond = m.cond.TNc; w->tiled_cond_tp = m.cond.tiled_cond_tp;
+    w->has_cond = m.cond.has; w->cond_fast = m.cond.fast; w->cond_unet = m.cond.unet;
+    w->cond = m.cond.Cw;
+    w->cond.base = dbuf;
     *out = w;
+    return MCD_OK;
+}
+
+int mcd_debug_pack_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* latent_cfg,
+                          int64_t* n_floats_out, uint64_t* digest_out) {
+    if (!tensors || !cfg || !n_floats_out || !digest_out) return fail(MCD_EINVAL, "null argument");
+    PackedModel m;
+    const int rc = latent_cfg ? pack_latent_model(tensors, n_tensors, cfg, latent_cfg, m) : pack_pose_model(tensors, n_tensors, cfg, m);
+    if (rc != MCD_OK) return rc;
+    *n_floats_out = (int64_t)m.buf.size();
+    *digest_out = pack_digest(m);
     return MCD_OK;
 }
 

@@ -1,6 +1,6 @@
-// mcd_latent_api.hpp — host side of the MoCoDADlatent entry points (include/mocodad_hip.h): the packer and the calls around the
-// launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose packing helpers (TensorMap, fold_conv_bn, pack_mix_mfma,
-// pack_gemm_frags, Builder) it shares; it holds no device code.
+// mcd_latent_api.hpp — host side of the MoCoDADlatent entry points (include/mocodad_hip.h): the handle and the calls around the
+// launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose upload helper and condition-encoder launches it shares; the
+// packer is pack_latent_model of mcd_pack.hpp.  It holds no device code.
 #pragma once
 #include "mcd_latent.hpp"
 
@@ -19,27 +19,6 @@ namespace {
 
 using namespace mcd;
 
-// Linear (out,in) + bias, optionally followed by an eval-mode BatchNorm1d (eps 1e-5): W' = s W, b' = s (b - mu) + beta, in double
-bool fold_linear_bn(TensorMap& tm, const std::string& lin, const std::string& bn, int out, int in, Folded& f) {
-    const float* w = tm.get(lin + ".weight", (int64_t)out * in);
-    const float* b = tm.get(lin + ".bias", out);
-    if (!w || !b) return false;
-    f.w.resize((size_t)out * in); f.b.resize(out);
-    const float *g = nullptr, *be = nullptr, *mu = nullptr, *var = nullptr;
-    if (!bn.empty()) {
-        g = tm.get(bn + ".weight", out); be = tm.get(bn + ".bias", out);
-        mu = tm.get(bn + ".running_mean", out); var = tm.get(bn + ".running_var", out);
-        if (!g || !be || !mu || !var) return false;
-    }
-    for (int o = 0; o < out; ++o) {
-        const double s = g ? (double)g[o] / sqrt((double)var[o] + 1e-5) : 1.0;
-        for (int i = 0; i < in; ++i) f.w[(size_t)o * in + i] = s * (double)w[(size_t)o * in + i];
-        f.b[o] = g ? s * ((double)b[o] - (double)mu[o]) + (double)be[o] : (double)b[o];
-    }
-    return true;
-}
-
-bool latent_dim_ok(int d) { return d >= 16 && d <= LAT_MAX_DIM && d % 16 == 0; }
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int64_t lat_ws_cond_bytes(int64_t B) { return (B * EDIM * 4 + 255) / 256 * 256; }
 int64_t lat_ws_z0_bytes(int64_t B, int D) { return (B * D * 4 + 255) / 256 * 256; }
@@ -133,132 +112,19 @@ extern "C" {
 int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* lcfg,
                             int32_t device, mcd_latent_weights_t** out) {
     if (!tensors || !cfg || !lcfg || !out) return fail(MCD_EINVAL, "null argument");
-    if (cfg->num_coords != C0) return fail(MCD_EUNSUPPORTED, "num_coords must be 2");
-    if (cfg->n_joints != 17) return fail(MCD_EUNSUPPORTED, "n_joints must be 17 (the reference U-Net hard-wires 17/12/10 joints)");
-    if (cfg->emb_dim != EDIM) return fail(MCD_EUNSUPPORTED, "embedding_dim must be 16");
-    if (cfg->strategy != MCD_STRATEGY_INJECT) return fail(MCD_EINVAL, "the latent model conditions by 'inject' only (mocodad_latent.py:32)");
-    const int T = cfg->t_unet;
-    if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
-        return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    if (!latent_encode_has_kernel(T, false) || cfg->t_cond > 12)
-        return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
-                                      " condition frames (instantiated: 3 corrupt frames with 1 .. 12 condition frames)");
-    if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
-        return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
-    if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
-        return fail(MCD_EUNSUPPORTED, "this library holds no cond_unet_kernel for " + std::to_string(cfg->t_cond) + " condition frames (MCD_COND_UNET_INSTANCES)");
-    const int D = lcfg->latent_dim, NL = lcfg->n_layers;
-    if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
-    if (NL < 1 || NL > LAT_MAX_LAYERS) return fail(MCD_EUNSUPPORTED, "the denoiser has " + std::to_string(NL) + " layers: 1.." + std::to_string(LAT_MAX_LAYERS) + " are supported");
-    for (int l = 0; l < NL; ++l)
-        if (!latent_dim_ok(lcfg->hidden[l])) return fail(MCD_EUNSUPPORTED, "denoiser hidden size " + std::to_string(lcfg->hidden[l]) + ": must be a multiple of 16 in 16..128");
-    if (lcfg->hidden[NL - 1] != D) return fail(MCD_EINVAL, "the last denoiser hidden size must equal latent_embedding_dim (it predicts the latent's noise)");
-
-    TensorMap tm;
-    for (int i = 0; i < n_tensors; ++i) tm.m[tensors[i].name] = {tensors[i].data, tensors[i].numel};
-    Builder B;
-    B.alloc(TAB_FLOATS);
-    std::vector<int> tab(TAB_FLOATS, 0);
-    auto set_f = [&](int idx, float v) { memcpy(&tab[idx], &v, sizeof(float)); };
-
-    // ---- the U-Net's down path (stsae_unet.py:182-219) with its embedding Linears
-    static const char* names[LAT_DOWN_LAYERS] = {"st_gcnnsp1a.0", "st_gcnnsd1.0", "st_gcnnsd1.1", "st_gcnnsd2.0", "st_gcnnsd2.1", "st_gcnnsd3.0", "st_gcnnsd3.1"};
-    const int we_off = B.alloc((size_t)LAT_EMB * EDIM), be_off = B.alloc(LAT_EMB);
-    for (int l = 0; l < LAT_DOWN_LAYERS; ++l) {
-        const LDesc Dl = layer_desc(l);
-        const std::string p = std::string("model.") + names[l];
-        int tq = 0, am = 0;
-        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-        const int cin = l == 0 ? C0 : Dl.cin, cinp = Dl.cin;
-        Folded ft, fr;
-        if (!fold_conv_bn(tm, p + ".tcn.0", p + ".tcn.1", Dl.cout, cin, ft)) return fail(MCD_EMISSING, tm.missing);
-        if (Dl.res && !fold_conv_bn(tm, p + ".residual.0", p + ".residual.1", Dl.cout, cin, fr)) return fail(MCD_EMISSING, tm.missing);
-        const float* sl = tm.get(p + ".prelu.weight", 1);
-        const float* we = tm.get(p + ".emb_layer.1.weight", (int64_t)Dl.cout * EDIM);
-        const float* be = tm.get(p + ".emb_layer.1.bias", Dl.cout);
-        if (!sl || !we || !be) return fail(MCD_EMISSING, tm.missing);
-        memcpy(&B.buf[we_off + (size_t)emb_off(l) * EDIM], we, sizeof(float) * Dl.cout * EDIM);
-        memcpy(&B.buf[be_off + emb_off(l)], be, sizeof(float) * Dl.cout);
-        const int bias = B.alloc(ceil16(Dl.cout));
-        for (int o = 0; o < Dl.cout; ++o) B.buf[bias + o] = (float)(ft.b[o] + (Dl.res ? fr.b[o] : 0.0));
-        // every layer mix-first here: [W_t' | W_r'] (layer 6 too, as in cond_unet_kernel)
-        const int wp = pack_gemm_frags(B, ceil16(Dl.cout), cinp * (Dl.res ? 2 : 1), [&](int r, int k) -> double {
-            const bool second = k >= cinp;
-            const int kk = second ? k - cinp : k;
-            if (r >= Dl.cout || kk >= cin) return 0.0;
-            return second ? fr.w[(size_t)r * cin + kk] : ft.w[(size_t)r * cin + kk];
-        });
-        tab[l * F_STRIDE + F_TQ] = tq; tab[l * F_STRIDE + F_AM] = am; tab[l * F_STRIDE + F_WP] = wp; tab[l * F_STRIDE + F_BIAS] = bias;
-        set_f(l * F_STRIDE + F_SLOPE, sl[0]);
-    }
-    tab[TAB_WE] = we_off; tab[TAB_BE] = be_off;
-    static const char* rs_names[2] = {"down1", "down2"};
-    static const int rs_in[2] = {17, 12}, rs_out[2] = {12, 10};
-    for (int r = 0; r < 2; ++r) {
-        Folded f;
-        const std::string p = std::string("model.") + rs_names[r];
-        if (!fold_conv_bn(tm, p + ".block.0", p + ".block.1", rs_out[r], rs_in[r], f)) return fail(MCD_EMISSING, tm.missing);
-        const int vin = rs_in[r], vout = rs_out[r], KS = (vin + 3) / 4, MTr = (vout + 15) / 16;
-        const int wf = B.alloc((size_t)MTr * KS * 64), bo = B.alloc(32);
-        for (int mt = 0; mt < MTr; ++mt) for (int ks = 0; ks < KS; ++ks) for (int lane = 0; lane < 64; ++lane) {
-            const int vo = mt * 16 + (lane & 15), v = rs_vmap(false, vin, ks, lane >> 4);
-            B.buf[wf + (mt * KS + ks) * 64 + lane] = (vo < vout && v < vin) ? (float)f.w[(size_t)vo * vin + v] : 0.f;
-        }
-        for (int vo = 0; vo < vout; ++vo) B.buf[bo + vo] = (float)f.b[vo];
-        tab[TAB_RSW + r] = wf; tab[TAB_RSB + r] = bo;
-    }
-    {
-        const int64_t F = (int64_t)LAT_ENC_C * T * 10;
-        const float* lw = tm.get("model.to_time_dim.weight", F * D);
-        const float* lb = tm.get("model.to_time_dim.bias", D);
-        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        tab[TAB_LAT_LW] = B.alloc(F * D); memcpy(&B.buf[tab[TAB_LAT_LW]], lw, sizeof(float) * F * D);
-        tab[TAB_LAT_LB] = B.alloc(D); memcpy(&B.buf[tab[TAB_LAT_LB]], lb, sizeof(float) * D);
-    }
-    // ---- the condition encoder, packed as the pose model's (the AE decoder is dead work at evaluation and is not read)
-    CondPack cp;
-    {
-        // the fused form runs cond_fast_body itself: its table is packed in every build, whatever cond_fast_kernel rows the library holds
-        const int rc = pack_cond_encoder(tm, cfg, B, cp, cfg->t_cond == T && latent_encode_has_kernel(T, true));
-        if (rc != MCD_OK) return rc;
-        write_cond_table(tab.data(), cp);
-    }
-    // ---- the denoiser (components.py:228-241): Linear -> BatchNorm1d -> ReLU, the last layer a plain Linear; cond_layers apart
-    LatentNet N;
-    memset(&N, 0, sizeof(N));
-    N.D = D; N.n_layers = NL;
-    for (int l = 0; l < NL; ++l) {
-        const int in = l == 0 ? D : lcfg->hidden[l - 1], outc = lcfg->hidden[l];
-        const bool last = l == NL - 1;
-        const std::string p = "denoiser.net." + std::to_string(l), pc = "denoiser.cond_layers." + std::to_string(l);
-        Folded f, fc;
-        if (!fold_linear_bn(tm, last ? p : p + ".0", last ? "" : p + ".1", outc, in, f)) return fail(MCD_EMISSING, tm.missing);
-        if (!fold_linear_bn(tm, pc, "", outc, EDIM, fc)) return fail(MCD_EMISSING, tm.missing);
-        N.in[l] = in; N.out[l] = outc;
-        N.wp[l] = pack_gemm_frags(B, outc, EDIM + in, [&](int r, int k) -> double {
-            return k < EDIM ? fc.w[(size_t)r * EDIM + k] : f.w[(size_t)r * in + (k - EDIM)];
-        });
-        N.bias[l] = B.alloc(outc);
-        N.cbias[l] = B.alloc(outc);
-        for (int o = 0; o < outc; ++o) { B.buf[N.bias[l] + o] = (float)f.b[o]; B.buf[N.cbias[l] + o] = (float)fc.b[o]; }
-    }
-    memcpy(B.buf.data(), tab.data(), sizeof(int) * TAB_FLOATS);
-
-    int prev_dev = 0;
-    HIP_TRY(hipGetDevice(&prev_dev));
-    HIP_TRY(hipSetDevice(device));
-    struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{prev_dev};
+    PackedModel m;
+    int rc = pack_latent_model(tensors, n_tensors, cfg, lcfg, m);
+    if (rc != MCD_OK) return rc;
+    float* dbuf = nullptr;
+    rc = upload_packed(m.buf, device, &dbuf);
+    if (rc != MCD_OK) return rc;
     mcd_latent_weights* w = new mcd_latent_weights();
-    w->cfg = *cfg; w->device = device; w->n_floats = B.buf.size(); w->net = N; w->dbuf = nullptr;
+    w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
     memset(w->opt, 0, sizeof(w->opt));
-    w->fused_ok = cp.fast_table && cfg->t_cond == T && latent_encode_has_kernel(T, true);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->dbuf), B.buf.size() * sizeof(float));
-    if (e != hipSuccess) { delete w; return fail(MCD_EDEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipMemcpy(w->dbuf, B.buf.data(), B.buf.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(w->dbuf); delete w; return fail(MCD_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+    w->fused_ok = m.fused_ok != 0;
     w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
-    w->cw.has_cond = true; w->cw.cond_fast = cp.fast; w->cw.cond_unet = cp.unet;
-    w->cw.cond = cp.Cw;
+    w->cw.has_cond = true; w->cw.cond_fast = m.cond.fast; w->cw.cond_unet = m.cond.unet;
+    w->cw.cond = m.cond.Cw;
     w->cw.cond.base = w->dbuf;
     *out = w;
     return MCD_OK;

@@ -8,18 +8,16 @@
 
 namespace mcd {
 
+struct GLayer { int cin, cout, V, tq, am, wt, wr, bias, embo; float slope; };    // wr < 0: identity residual; embo < 0: no embedding
+constexpr int CE_THREADS = 512;      // block size of cond_encode_kernel (the packer sizes its LDS by it: CondW::gmode)
 struct CondW {
     const float* base;
     int n_layers, Tc, latent, cmax;
     int gmode;       // 1: three LDS buffers of cmax x Tc x 17 do not fit (25 .. 31 condition frames of the shipped encoder): the third one lives in global scratch
-    int cin[MCD_MAX_COND_LAYERS], cout[MCD_MAX_COND_LAYERS];
-    int tq[MCD_MAX_COND_LAYERS], am[MCD_MAX_COND_LAYERS], wt[MCD_MAX_COND_LAYERS], wr[MCD_MAX_COND_LAYERS];
-    int bias[MCD_MAX_COND_LAYERS];
-    float slope[MCD_MAX_COND_LAYERS];
+    GLayer L[MCD_MAX_COND_LAYERS];
     int lw, lb;
 };
 
-struct GLayer { int cin, cout, V, tq, am, wt, wr, bias, embo; float slope; };    // wr < 0: identity residual; embo < 0: no embedding
 struct GenNet { GLayer L[NLAYERS]; int rs_w[4], rs_b[4], we, be; };
 struct GenCond { GLayer L[7]; int rs_w[2], rs_b[2], lw, lb; };
 
