@@ -1,5 +1,6 @@
 """Builds libmocodad_hip.so for gfx950 from mocodad_amd/csrc: mcd_api.hip (C ABI, routes, launches; with its headers mcd_pack.hpp, the
-weight packer, and mcd_generic_kernel.hpp, the runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels), compiled in parallel and linked with hipcc.
+weight packer, mcd_call.hpp, the front end of a scoring call, mcd_post_kernel.hpp, its own kernels, and mcd_generic_kernel.hpp, the
+runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels), compiled in parallel and linked with hipcc.
 
     python -m mocodad_amd.build                       # the shipped library (mocodad_amd/libmocodad_hip.so)
     python -m mocodad_amd.build --profile             # + -DMCD_PROFILE -> libmocodad_hip_prof.so (tools/stage_profile.py)

@@ -1,15 +1,13 @@
 // mcd_api.hip — host side of libmocodad_hip.so: the C ABI of include/mocodad_hip.h, the upload of a packed model, and dispatch to
 // the kernel instantiations of mcd_inst.hip (declared `extern template` in mcd_launch.hpp; every switch over frame counts is an
 // expansion of the tables of mcd_instances.hpp, and which kernel family serves a handle is decided by unet_route() / cond_route()
-// alone: entry points, launches and workspace sizing ask them).  The weight packer (BatchNorm folding, MFMA fragment order) is
-// mcd_pack.hpp; the runtime-shape kernels (cond_encode_kernel, score_generic_kernel, cond_unet_generic_kernel) are
-// mcd_generic_kernel.hpp.  The kernels of this file:
-//   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
-//   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
-//   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
-//   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
-//                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
-//   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
+// alone: entry points, launches and workspace sizing ask them).  Host code only -- routes, launches, ABI -- around four headers:
+//   mcd_post_kernel.hpp      this file's own kernels (aggregation, frame scores, pose normalisation, stream rings, the exported
+//                            Philox draws, gather, LDS poison) and their parameter blocks
+//   mcd_generic_kernel.hpp   the runtime-shape kernels (cond_encode_kernel, score_generic_kernel, cond_unet_generic_kernel)
+//   mcd_pack.hpp             the weight packer (BatchNorm folding, MFMA fragment order)
+//   mcd_call.hpp             the front end of a scoring call, shared with the latent entry points (mcd_latent_api.hpp, included
+//                            at the end): window view, frame-list and aggregation checks, workspace layouts, launch_cond
 // The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
@@ -26,379 +24,9 @@ namespace { constexpr int API_THREADS = 512; }      // block size of this file's
 
 using namespace mcd;
 
+#include "mcd_post_kernel.hpp"      // this file's own kernels; everything below is host code
+
 namespace {
-
-// ------------------------------------------------------------------------------------------------
-// aggregation over the S samples (mocodad.py:454-520); one 64-lane wave per window, ANY S (the reference's shipped
-// n_generated_samples is 50, config/*/mocodad_test.yaml; its _aggregation_strategy has no cap)
-// ------------------------------------------------------------------------------------------------
-struct AggrParams {
-    const float* loss_all; const float* pose_all; const float* data; float* loss_agg; float* pose_agg;
-    int B, S, C, Tx, V, seg_len, strategy, loss_fn, in_lds;
-    float q;
-    int corrupt_idx[MCD_MAX_FRAMES];
-    const int* win_mask;      // random_imp (mcd_aggregate_view): (B,) condition-frame bitmasks; the window's corrupt frames are its
-                              // clear bits in ascending order and corrupt_idx is not read.  null = corrupt_idx
-};
-constexpr int AGG_LDS_MAX = 8192;       // sample values staged in LDS (32 KB); a longer sample axis is read in place
-
-// The S values of one window (its per-sample losses, or one pose element across the samples): staged in LDS, or -- beyond
-// AGG_LDS_MAX samples -- read where they lie (stride = floats between consecutive samples).
-struct SampleVals {
-    const float* p; long long stride;
-    __device__ __forceinline__ float operator()(int k) const { return p[(long long)k * stride]; }
-};
-__device__ __forceinline__ SampleVals stage_samples(const float* src, long long stride, int S, float* lds, bool in_lds, int lane) {
-    if (!in_lds) return SampleVals{src, stride};
-    __syncthreads();                                     // the previous round's readers are done with `lds`
-    for (int k = lane; k < S; k += 64) lds[k] = src[(long long)k * stride];
-    __syncthreads();
-    return SampleVals{lds, 1};
-}
-// Order statistics by rank counting: sample i's rank = #{k : x_k < x_i or (x_k == x_i and k < i)} is a permutation of
-// 0 .. S-1 whatever the ties; lane l ranks the samples l, l + 64, ...; the samples of rank r0 / r1 land in slot[0] / slot[1].
-// (No sort, no per-thread array: O(S^2 / 64) broadcast reads per lane.)  All lanes return the same pair.
-// A NaN among the samples (a diverged chain) breaks the permutation -- every NaN ranks 0 and the rank asked for may have no
-// writer -- and torch.median / torch.quantile return NaN then (mocodad.py:489-492,513-516): so does this, for both values.
-__device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int lane, int r0, int r1, float* slot, float& v0, float& v1) {
-    bool nan = false;
-    for (int i = lane; i < S; i += 64) {
-        const float x = X(i);
-        nan |= x != x;
-        int r = 0;
-        for (int k = 0; k < S; ++k) {
-            const float y = X(k);
-            r += (y < x || (y == x && k < i)) ? 1 : 0;
-        }
-        if (r == r0) slot[0] = x;
-        if (r == r1) slot[1] = x;
-    }
-    __syncthreads();
-    const bool any_nan = __ballot(nan) != 0ull;        // (one 64-lane wave per workgroup: aggregate_kernel's launch bound)
-    v0 = any_nan ? __builtin_nanf("") : slot[0];
-    v1 = any_nan ? __builtin_nanf("") : slot[1];
-    __syncthreads();
-}
-// torch.median: the lower middle value; torch.quantile: linear interpolation, torch.lerp's two-sided form
-__device__ __forceinline__ float wave_order_stat(const SampleVals& X, int S, int lane, int strategy, float q, float* slot) {
-    float a, c;
-    if (strategy == MCD_AGGR_MEDIAN) {
-        wave_rank_select(X, S, lane, (S - 1) / 2, (S - 1) / 2, slot, a, c);
-        return a;
-    }
-    const float pos = fminf(fmaxf(q, 0.f), 1.f) * (float)(S - 1);      // (q is validated on the host; the clamp is a backstop)
-    const int lo = (int)floorf(pos);
-    const int hi = lo + 1 < S ? lo + 1 : S - 1;
-    const float wgt = pos - (float)lo;
-    wave_rank_select(X, S, lane, lo, hi, slot, a, c);
-    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
-}
-
-// Sums and best / worst run in sample order on wave-uniform values: bit-identical to the sequential loops of
-// aggregate_losses in the fused kernel.
-__global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams P) {
-    extern __shared__ float agg_lds[];
-    float* slot = agg_lds;               // [2] selected order statistics
-    float* vals = agg_lds + 2;           // [S] staged sample values (in_lds)
-    const int lane = threadIdx.x, S = P.S, per = P.C * P.Tx * P.V;
-    const bool in_lds = P.in_lds != 0;
-    for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-        if (P.strategy <= MCD_AGGR_QUANTILE && P.strategy != MCD_AGGR_MEAN_POSE && P.strategy != MCD_AGGR_MEDIAN_POSE) {
-            const SampleVals X = stage_samples(P.loss_all + (size_t)b * S, 1, S, vals, in_lds, lane);
-            if (P.strategy == MCD_AGGR_BEST || P.strategy == MCD_AGGR_WORST) {
-                const bool best = P.strategy == MCD_AGGR_BEST;
-                float cur = best ? 1e10f : -1.f;       // mocodad.py:504-512: strict comparisons from 1e10 / -1 (the FIRST of equal samples stays)
-                int sel = -1;
-                for (int k = 0; k < S; ++k) {
-                    const float y = X(k);
-                    if (best ? (y < cur) : (y > cur)) { cur = y; sel = k; }
-                }
-                if (lane == 0) P.loss_agg[b] = cur;
-                if (P.pose_agg)
-                    for (int e = lane; e < per; e += 64)
-                        P.pose_agg[(size_t)b * per + e] = sel >= 0 ? P.pose_all[((size_t)b * S + sel) * per + e] : 0.f;
-            } else if (P.strategy == MCD_AGGR_MEAN) {
-                float sum = 0.f;
-                for (int k = 0; k < S; ++k) sum += X(k);
-                if (lane == 0) P.loss_agg[b] = sum / (float)S;
-            } else {
-                const float r = wave_order_stat(X, S, lane, P.strategy, P.q, slot);
-                if (lane == 0) P.loss_agg[b] = r;
-            }
-        } else {  // mean_pose / median_pose: per element over the S generated poses, then the loss of that pose (mocodad.py:493-503)
-            float acc = 0.f;      // (every lane carries the same running sum: the per-element values are wave-uniform)
-            for (int e = 0; e < per; ++e) {
-                const SampleVals X = stage_samples(P.pose_all + (size_t)b * S * per + e, per, S, vals, in_lds, lane);
-                float val;
-                if (P.strategy == MCD_AGGR_MEAN_POSE) {
-                    float sum = 0.f;
-                    for (int k = 0; k < S; ++k) sum += X(k);
-                    val = sum / (float)S;
-                } else {
-                    val = wave_order_stat(X, S, lane, MCD_AGGR_MEDIAN, 0.f, slot);
-                }
-                if (P.pose_agg && lane == 0) P.pose_agg[(size_t)b * per + e] = val;
-                const int c = e / (P.Tx * P.V), tx = (e / P.V) % P.Tx, v = e % P.V;
-                // (max: a mask with more than seg_len - Tx bits set, which the caller must not pass, still reads inside the window)
-                const int frame = P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
-                const float gt = P.data[(((size_t)b * P.C + c) * P.seg_len + frame) * P.V + v];
-                acc += loss_elem(val, gt, P.loss_fn);
-            }
-            if (lane == 0) P.loss_agg[b] = acc / (float)per;
-        }
-    }
-}
-
-
-// scatter-max of window scores to frames (mocodad.py:392-393 + eval_utils.py:27-34); scores >= 0
-__global__ void scatter_max_kernel(const float* __restrict__ scores, const int* __restrict__ frames,
-                                   const int* __restrict__ row, long long n, int seg_len, int n_frames,
-                                   float* __restrict__ out) {
-    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * seg_len) return;
-    const long long i = u / seg_len;
-    const int f = frames[u] - 1;
-    if (f < 0 || f >= n_frames) return;
-    // non-negative floats order like their bit patterns
-    atomicMax(reinterpret_cast<int*>(out + (size_t)row[i] * n_frames + f), __float_as_int(fmaxf(scores[i], 0.f)));
-}
-
-// Per-frame pose normalisation of the dataset loader (utils/data.py:11-43,165-186 + 350-359), one thread per frame, in the
-// reference's own precision (NumPy >= 2 scalar rules, DESIGN.md "Dataset loading"): the box, its margin and the clip in fp32,
-// round-half-even to int, (x - centre) / size correctly rounded in fp32 (computed in double and rounded once: exact, 53 >= 2*24+2),
-// then sklearn's RobustScaler.transform, which runs x - center_ and / scale_ in float64 and rounds to fp32 after each.
-// raw (n, 34) = x1,y1,...,x17,y17; out (n, 2, 17).
-// normalize_pose_row: one row, written to `o` and, when o2 != nullptr, to `o2` as well (the mirrored copy of a track ring).
-__device__ __forceinline__ void normalize_pose_row(const float* __restrict__ r, float vid_w, float vid_h,
-                                                   const double* __restrict__ center, const double* __restrict__ scale,
-                                                   float* __restrict__ o, float* __restrict__ o2) {
-#pragma clang fp contract(off)      // the margin is 0.1 * (r - l + 1), then l - margin: two roundings, never an FMA
-    float v[34];
-    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
-    for (int k = 0; k < 34; k += 2) {
-        v[k] = r[k]; v[k + 1] = r[k + 1];
-        if (v[k] != 0.f) { xmin = fminf(xmin, v[k]); xmax = fmaxf(xmax, v[k]); }
-        if (v[k + 1] != 0.f) { ymin = fminf(ymin, v[k + 1]); ymax = fmaxf(ymax, v[k + 1]); }
-    }
-    if (xmin > xmax || ymin > ymax) {
-        // all joints missing, or no non-zero x (y): box (0, 0, 0, 0), zero width and height -> the frame is all zeros
-        for (int k = 0; k < 34; ++k) v[k] = 0.f;
-    } else {
-        const float ew = 0.1f * ((xmax - xmin) + 1.f), eh = 0.1f * ((ymax - ymin) + 1.f);
-        const float wm1 = vid_w - 1.f, hm1 = vid_h - 1.f;
-        const int L = (int)rintf(fminf(fmaxf(xmin - ew, 0.f), wm1)), R = (int)rintf(fminf(fmaxf(xmax + ew, 0.f), wm1));
-        const int T = (int)rintf(fminf(fmaxf(ymin - eh, 0.f), hm1)), B = (int)rintf(fminf(fmaxf(ymax + eh, 0.f), hm1));
-        const double cx = 0.5 * (double)(L + R), cy = 0.5 * (double)(T + B);
-        const double w = (double)(R - L), h = (double)(B - T);
-        for (int k = 0; k < 34; k += 2) {
-            // missing joints (0) take the centre, which the subtraction then removes
-            const float dx = (float)((double)(v[k] == 0.f ? (float)cx : v[k]) - cx);
-            const float dy = (float)((double)(v[k + 1] == 0.f ? (float)cy : v[k + 1]) - cy);
-            v[k] = w != 0.0 ? (float)((double)dx / w) : 0.f;
-            v[k + 1] = h != 0.0 ? (float)((double)dy / h) : 0.f;
-        }
-    }
-    for (int k = 0; k < 34; ++k) {
-        float t = v[k];
-        if (center) {
-            // exact zeros are NaN (missing) for the scaler and come back as 0, as does any other NaN of the transform
-            if (t == 0.f) t = 0.f;
-            else {
-                t = (float)((double)t - center[k]);
-                t = (float)((double)t / scale[k]);
-                if (t != t) t = 0.f;
-            }
-        }
-        o[(k & 1) * 17 + (k >> 1)] = t;
-        if (o2) o2[(k & 1) * 17 + (k >> 1)] = t;
-    }
-}
-
-__global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __restrict__ raw, long long n, float vid_w, float vid_h,
-                                                              const double* __restrict__ center, const double* __restrict__ scale,
-                                                              float* __restrict__ out) {
-    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n) return;
-    normalize_pose_row(raw + f * 34, vid_w, vid_h, center, scale, out + f * 34, nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Live pose streams (mcd_stream_state_t): the state between two ticks lives in two caller-owned rings.
-//   pose ring  (n_slots, 2 L, 2, 17): row r of a track sits at positions r % L and r % L + L, so the seg_len rows from row s on
-//              are contiguous from position s % L and a window stays ONE base offset of mcd_window_view_t.
-//   score ring (n_slots, num_transform, L): running max, per row and transform, over the windows covering the row.
-// A tick holds at most one row per track, so no two threads of a launch touch the same cell: plain loads and stores.
-// ------------------------------------------------------------------------------------------------
-struct StreamParams {
-    float* ring; float* fs;
-    int n_slots, L, seg_len, nt;
-};
-
-// one thread per pushed row: desc (n, 3) = [slot, row index r, emit index j | -1]
-__global__ __launch_bounds__(256) void stream_push_kernel(StreamParams S, const float* __restrict__ raw, const int* __restrict__ desc,
-                                                          int n, int n_emit, float vid_w, float vid_h,
-                                                          const double* __restrict__ center, const double* __restrict__ scale,
-                                                          long long* __restrict__ base_out, int* __restrict__ trans_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = desc[3 * i], r = desc[3 * i + 1], j = desc[3 * i + 2];
-    if (slot < 0 || slot >= S.n_slots || r < 0) return;        // (a descriptor the host table cannot produce: touch nothing)
-    const int p = r % S.L;
-    float* o = S.ring + ((size_t)slot * 2 * S.L + p) * 34;
-    normalize_pose_row(raw + (size_t)i * 34, vid_w, vid_h, center, scale, o, o + (size_t)S.L * 34);
-    for (int t = 0; t < S.nt; ++t) S.fs[((size_t)slot * S.nt + t) * S.L + p] = 0.f;
-    if (j < 0 || j >= n_emit || r < S.seg_len - 1) return;
-    const long long base = ((long long)slot * 2 * S.L + (r - S.seg_len + 1) % S.L) * 34;
-    for (int t = 0; t < S.nt; ++t) {
-        base_out[(size_t)t * n_emit + j] = base;
-        trans_out[(size_t)t * n_emit + j] = t;
-    }
-}
-
-// one thread per (emitted window j, transform t): win (n_emit, 2) = [slot, r_last]; scores (num_transform * n_emit,) transform-major.
-// The same clamp and zero start as scatter_max_kernel; final_out (n_emit, num_transform) = the cell of row r_last - seg_len + 1,
-// which no later window covers.
-__global__ __launch_bounds__(256) void stream_frame_scores_kernel(StreamParams S, const float* __restrict__ scores,
-                                                                  const int* __restrict__ win, int n_emit,
-                                                                  float* __restrict__ final_out) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_emit * S.nt) return;
-    const int j = u / S.nt, t = u - j * S.nt;
-    const int slot = win[2 * j], r_last = win[2 * j + 1];
-    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
-    const float sc = fmaxf(scores[(size_t)t * n_emit + j], 0.f);
-    float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
-    const int first = r_last - S.seg_len + 1;
-    for (int k = S.seg_len - 1; k >= 0; --k) {
-        float* c = row + (first + k) % S.L;
-        const float m = fmaxf(*c, sc);
-        *c = m;
-        if (k == 0) final_out[u] = m;
-    }
-}
-
-// one thread per (closed track i, pending row k, transform t): the seg_len - 1 cells of rows r_last - seg_len + 2 .. r_last
-__global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const int* __restrict__ win, int n,
-                                                           float* __restrict__ out) {
-    const int pend = S.seg_len - 1;
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * pend * S.nt) return;
-    const int t = u % S.nt, k = (u / S.nt) % pend, i = u / (S.nt * pend);
-    const int slot = win[2 * i], r_last = win[2 * i + 1];
-    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
-    out[u] = S.fs[((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L];
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// Frame-score assembly after the path (mocodad.py:362-425; eval_utils.py:27-34,100-106,133-149), on device, in float64
-// like the reference's NumPy code.
-//   frame_scatter_kernel: window score -> max over the windows covering each frame of its (transform, clip, person) row.
-//   frame_scores_kernel : one workgroup per clip; for every transform: per person pad_scores, then
-//                         mean_p + (max_p - min_p) of log1p over the persons present, HR-mask compaction, shift,
-//                         gaussian_filter1d (scipy defaults: truncate 4 sigma, 'reflect'), accumulated over the transforms
-//                         and divided by their number.
-// Rows are dense: row = (transform * n_clips + clip) * P + person id; `used[row]` marks persons that have windows.
-// ------------------------------------------------------------------------------------------------
-struct FrameParams {
-    const float* scores; const long long* trans; const long long* meta; const int* frames;
-    const long long* clip_keys;     // (n_clips,) sorted (scene << 32 | clip)
-    const int* clip_n;              // (n_clips,) frames of the clip = len(gt)
-    const int* dst;                 // per clip F entries: position of the frame after the HR masks, -1 = dropped
-    const int* out_len;             // (n_clips,) frames kept
-    const long long* out_off;       // (n_clips,) offset of the clip in the concatenated output
-    const double* gauss;            // (2 radius + 1,) normalised weights
-    float* mat; int* used; double* out;
-    long long n;
-    int seg_len, n_clips, num_transform, P, F, pad, shift, radius;
-};
-
-__global__ void frame_scatter_kernel(const FrameParams Q) {
-    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= Q.n * Q.seg_len) return;
-    const long long i = u / Q.seg_len;
-    const long long tr = Q.trans[i];
-    if (tr < 0 || tr >= Q.num_transform) return;
-    const long long key = (Q.meta[i * 4 + 0] << 32) | (Q.meta[i * 4 + 1] & 0xffffffffll);
-    int lo = 0, hi = Q.n_clips;                     // lower bound in the sorted clip keys
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (Q.clip_keys[mid] < key) lo = mid + 1; else hi = mid; }
-    if (lo >= Q.n_clips || Q.clip_keys[lo] != key) return;        // a clip without a ground-truth file is not evaluated
-    const long long person = Q.meta[i * 4 + 2];
-    if (person < 0 || person >= Q.P) return;
-    const int f = Q.frames[u] - 1;
-    if (f < 0 || f >= Q.clip_n[lo]) return;
-    const long long row = ((long long)tr * Q.n_clips + lo) * Q.P + person;
-    Q.used[row] = 1;
-    // non-negative floats order like their bit patterns (np.nanmax over the windows covering the frame; 0 = absent)
-    atomicMax(reinterpret_cast<int*>(Q.mat + row * Q.F + f), __float_as_int(fmaxf(Q.scores[i], 0.f)));
-}
-
-__global__ __launch_bounds__(256) void frame_scores_kernel(const FrameParams Q) {
-    extern __shared__ __attribute__((aligned(16))) double fsm[];
-    const int ci = blockIdx.x, n = Q.clip_n[ci], m = Q.out_len[ci];
-    double* cs = fsm;                 // [m] compacted clip score of the current transform
-    double* acc = fsm + Q.F;          // [m] sum over the transforms
-    const int* dst = Q.dst + (size_t)ci * Q.F;
-    for (int j = threadIdx.x; j < m; j += blockDim.x) acc[j] = 0.0;
-    for (int tr = 0; tr < Q.num_transform; ++tr) {
-        const size_t row0 = ((size_t)tr * Q.n_clips + ci) * Q.P;
-        __syncthreads();
-        for (int f = threadIdx.x; f < n; f += blockDim.x) {
-            double sum = 0.0, lmax = 0.0, lmin = 0.0;
-            int cnt = 0;
-            for (int p = 0; p < Q.P; ++p) {
-                if (!Q.used[row0 + p]) continue;
-                const float* r = Q.mat + (row0 + p) * Q.F;
-                float v = r[f];
-                if (Q.pad >= 0 && v != 0.f) {
-                    // pad_scores (eval_utils.py:133-149): zero `pad` frames before and pad-1 frames after every interval of
-                    // absence inside frames [0, n-2]; an interval touching frame 0 / frame n-2 is not extended on that side
-                    bool z = false;
-                    for (int d = 1; d <= Q.pad && !z; ++d) z = (f + d <= n - 2) && r[f + d] == 0.f;
-                    if (!z) {
-                        // backwards: for the last frame, the run of absence that ends at frame n-2 does not count
-                        bool in_tail = (f == n - 1);
-                        for (int d = 1; d <= Q.pad - 1 && f - d >= 0 && !z; ++d) {
-                            const bool zero = r[f - d] == 0.f;
-                            if (in_tail) { if (!zero) in_tail = false; }
-                            else z = zero;
-                        }
-                    }
-                    if (z) v = 0.f;
-                }
-                const double dv = (double)v, lg = log1p(dv);
-                sum += dv;
-                if (cnt == 0) { lmax = lg; lmin = lg; } else { lmax = fmax(lmax, lg); lmin = fmin(lmin, lg); }
-                ++cnt;
-            }
-            const int j = dst[f];
-            // a (transform, clip) block without any person: NaN (the reference fails on np.stack of an empty list; the host
-            // wrapper turns the NaN into that error)
-            if (j >= 0) cs[j] = cnt > 0 ? sum / (double)cnt + (lmax - lmin) : (double)NAN;
-        }
-        __syncthreads();
-        // score_process (eval_utils.py:100-106): shift by `shift` frames (zeros enter), then correlate with the Gaussian
-        // in scipy's symmetric form: in[c] w[c] + sum_{i=1..radius} (in[c-i] + in[c+i]) w[c-i], outermost pair first
-        for (int j = threadIdx.x; j < m; j += blockDim.x) {
-            auto at = [&](int k) -> double {          // shifted, 'reflect'-extended (d c b a | a b c d | d c b a)
-                const int per = 2 * m;
-                k %= per; if (k < 0) k += per;
-                if (k >= m) k = per - 1 - k;
-                return k >= Q.shift ? cs[k - Q.shift] : 0.0;
-            };
-            double t = at(j) * Q.gauss[Q.radius];
-            for (int i = Q.radius; i >= 1; --i) t += (at(j - i) + at(j + i)) * Q.gauss[Q.radius - i];
-            acc[j] += t;
-        }
-    }
-    __syncthreads();
-    double* o = Q.out + Q.out_off[ci];
-    for (int j = threadIdx.x; j < m; j += blockDim.x) o[j] = acc[j] / (double)Q.num_transform;
-}
-
-// ================================================================================================
-// host side
-// ================================================================================================
 
 // Dispatch to the launchers of mcd_inst.hip is generated from the tables of mcd_instances.hpp (this file only CALLS launchers).
 // score_kernel<T, ...>: the production form (or, in a build that holds tuning variants, the workgroup shape MCD_OPT_VARIANT
@@ -607,17 +235,9 @@ int upload_packed(const std::vector<float>& buf, int device, float** dbuf, int**
 }
 }  // namespace
 
-static unsigned long long* g_prof = nullptr;  // MCD_PROFILE builds: device buffer of 32 accumulators
+#include "mcd_call.hpp"      // the front end of a call: view, checks, workspace layouts, launch_cond
 
-// test aid (mcd_debug_poison_lds): every CU's LDS filled with signalling garbage (NaN bit patterns), so that a kernel reading
-// shared memory it never wrote produces NaNs instead of depending on what the previous kernel happened to leave there
-__global__ __launch_bounds__(API_THREADS) void poison_lds_kernel(unsigned* sink, int words) {
-    extern __shared__ unsigned psm[];
-    for (int u = threadIdx.x; u < words; u += API_THREADS) psm[u] = 0x7fc00000u | (unsigned)u;
-    __syncthreads();
-    if (threadIdx.x == 0 && sink) atomicOr(sink, psm[(blockIdx.x * 7919) % words] & 1u);      // (keeps the stores alive)
-    __builtin_amdgcn_s_sleep(64);
-}
+static unsigned long long* g_prof = nullptr;  // MCD_PROFILE builds: device buffer of 32 accumulators
 
 // the library is built with -fvisibility=hidden: only the C ABI of include/mocodad_hip.h is exported
 #pragma GCC visibility push(default)
@@ -652,9 +272,7 @@ int mcd_pack_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_m
     w->cfg = *cfg; w->device = device; w->dbuf = dbuf; w->tune = tune; w->n_floats = m.buf.size();
     w->zero_row = m.zero_row; w->fast_unet = m.fast_unet != 0; w->gen = m.gen; w->tiled = m.tiled; w->tiled_tp = m.tiled_tp;
     w->gcond = m.cond.GC; w->tiled_cond = m.cond.TNc; w->tiled_cond_tp = m.cond.tiled_cond_tp;
-    w->has_cond = m.cond.has; w->cond_fast = m.cond.fast; w->cond_unet = m.cond.unet;
-    w->cond = m.cond.Cw;
-    w->cond.base = dbuf;
+    set_cond_weights(w, m, dbuf);
     *out = w;
     return MCD_OK;
 }
@@ -693,13 +311,11 @@ int mcd_cond_encode(const mcd_weights_t* w, const float* cond_data, int32_t n_wi
     if (w->cond_unet && !cond_unet_has_kernel(w->cond.Tc))
         return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: the 'E_unet' encoder at this frame count needs scratch memory; use mcd_score");
     if (route == COND_PLAIN_SCRATCH) return fail(MCD_EUNSUPPORTED, "mcd_cond_encode: this many condition frames need scratch memory; use mcd_score");
-    if (route == COND_PLAIN) return launch_cond_plain(w, cond_data, n_windows, emb_out, nullptr, (hipStream_t)stream);
     FrameIdx fi;
     for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = k;
     DataView dv;
-    memset(&dv, 0, sizeof(dv));
-    dv.data = cond_data;
-    return launch_cond_view(w, route, dv, fi, w->cond.Tc, emb_out, n_windows, nullptr, (hipStream_t)stream);
+    window_view(cond_data, nullptr, w->cond.Tc, dv);      // cond_data holds the condition frames alone: nothing to gather
+    return launch_cond(w, route, dv, fi, w->cond.Tc, emb_out, n_windows, nullptr, nullptr, (hipStream_t)stream);
 }
 
 // scratch of the single-pass entries: the slabs of the slab-tiled kernel (13 .. 32 U-Net frames) or of the runtime-shape kernel
@@ -754,31 +370,6 @@ int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, con
     return launch_score(w, w->cfg.t_unet, P, st, nullptr, true);      // (the layer-test forms: the template arguments and unit flags of the production kernels)
 }
 
-__global__ void philox_noise_kernel(unsigned long long seed, long long first_window, int B, int S, int K, int Tx, float* __restrict__ out) {
-    // one thread per (s, k, b, tx, joint pair): exactly the draws of score_kernel (x_T: one call per element keyed
-    // (element, 0, s, window); step k >= 1: one call per joint pair keyed (tx * 9 + pair, k, s, window))
-    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)S * K * B * Tx * 9;
-    if (u >= total) return;
-    const int jp = (int)(u % 9), tx = (int)((u / 9) % Tx);
-    const int b = (int)((u / (9 * Tx)) % B), k = (int)((u / ((long long)9 * Tx * B)) % K), s = (int)(u / ((long long)9 * Tx * B * K));
-    const int v0 = 2 * jp, CTV = C0 * Tx * 17;
-    float* o = out + ((size_t)(s * K + k) * B + b) * CTV;
-    float z[4];
-    if (k == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int c = i & 1, v = v0 + (i >> 1);
-            z[i] = v < 17 ? philox_normal(seed, (unsigned)((c * Tx + tx) * 17 + v), 0u, (unsigned)s, (unsigned)(first_window + b)) : 0.f;
-        }
-    } else {
-        philox_normal4(seed, (unsigned)(tx * 9 + jp), (unsigned)k, (unsigned)s, (unsigned)(first_window + b), z);
-    }
-    o[tx * 17 + v0] = z[0];
-    o[Tx * 17 + tx * 17 + v0] = z[1];
-    if (v0 + 1 < 17) { o[tx * 17 + v0 + 1] = z[2]; o[Tx * 17 + tx * 17 + v0 + 1] = z[3]; }
-}
-
 int mcd_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
                      int32_t n_corrupt, float* noise_out, void* stream) {
     if (n_windows <= 0) return MCD_OK;
@@ -790,24 +381,6 @@ int mcd_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, 
                        (unsigned long long)seed, (long long)first_window_id, n_windows, n_samples, K, n_corrupt, noise_out);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
-}
-
-// One thread per window: n_cond steps, each picking uniformly among the frames not chosen yet (word i % 4 of Philox call i / 4,
-// multiply-high onto 0 .. seg_len-i-1, then the r-th clear bit), so the set is a uniform n_cond-subset of the seg_len frames.
-// Counter (call, ~0, ~0, window id): the noise streams use c1 = slot < ns and c2 = sample < S, so no call coincides with theirs.
-__global__ __launch_bounds__(256) void random_imp_masks_kernel(unsigned long long seed, long long first_window, int B, int T, int n_cond,
-                                                               int* __restrict__ mask_out) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const unsigned all = low_bits(T), win = (unsigned)(first_window + b);
-    unsigned chosen = 0u, w[4];
-    for (int i = 0; i < n_cond; ++i) {
-        if ((i & 3) == 0) philox_words4(seed, (unsigned)(i >> 2), 0xFFFFFFFFu, 0xFFFFFFFFu, win, w);
-        const unsigned word = (i & 3) == 0 ? w[0] : (i & 3) == 1 ? w[1] : (i & 3) == 2 ? w[2] : w[3];      // (selects: w stays in registers)
-        const int r = (int)(((unsigned long long)word * (unsigned)(T - i)) >> 32);
-        chosen |= 1u << nth_set_bit(~chosen & all, r);
-    }
-    mask_out[b] = (int)chosen;
 }
 
 int mcd_random_imp_masks(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t seg_len, int32_t n_cond,
@@ -824,11 +397,6 @@ int mcd_random_imp_masks(uint64_t seed, int64_t first_window_id, int32_t n_windo
     return MCD_OK;
 }
 
-static int64_t ws_loss_bytes(int64_t B, int64_t S) { return (B * S * 4 + 255) / 256 * 256; }
-static int64_t ws_cond_bytes(const mcd_weights* w, int64_t B) {
-    const int64_t raw = B * (EDIM + C0 * (w->cfg.t_cond > 0 ? w->cfg.t_cond : 0) * 17) * 4 + 256;
-    return (raw + 255) / 256 * 256;
-}
 int32_t mcd_plan_split(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
     if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
     if (cfg->n_windows <= 0) return 1;
@@ -842,18 +410,7 @@ int32_t mcd_plan_split(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
 
 int64_t mcd_score_workspace_bytes(const mcd_weights_t* w, const mcd_score_cfg_t* cfg) {
     if (!w || !cfg) return 0;
-    // condition embeddings (B,16) + gathered condition frames (B,C,Tc,V); then the scratch slabs of the slab-tiled and the
-    // runtime-shape kernels (one region: the condition encoder has finished with it when the trajectories start)
-    const int64_t gen = std::max(unet_ws_bytes(w, (int64_t)cfg->n_windows * cfg->n_samples), cond_ws_bytes(w, cfg->n_windows));
-    return ws_cond_bytes(w, cfg->n_windows) + ws_loss_bytes(cfg->n_windows, cfg->n_samples) + gen;
-}
-
-__global__ void gather_frames_kernel(const DataView dv, float* __restrict__ out, int B, int C, int T, int V, int n,
-                                     const FrameIdx fi) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= B * C * n * V) return;
-    const int v = u % V, k = (u / V) % n, c = (u / (V * n)) % C, b = u / (V * n * C);
-    out[u] = load_coord(dv, b, c, fi.idx[k], v, T);
+    return pose_workspace(w, cfg->n_windows, cfg->n_samples).bytes;
 }
 
 static int launch_aggregate(AggrParams& A, hipStream_t st) {
@@ -877,15 +434,12 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     if (aggr == 0 && !loss_all) return fail(MCD_EINVAL, "null argument");
     if (aggr != 0) {
         if (!loss_agg) return fail(MCD_EINVAL, "null argument");
-        if (aggr != MCD_AGGR_BEST && aggr != MCD_AGGR_WORST && aggr != MCD_AGGR_MEAN && aggr != MCD_AGGR_MEDIAN && aggr != MCD_AGGR_QUANTILE)
-            return fail(MCD_EINVAL, "mcd_score_fused aggregates losses (best, worst, mean, median, quantile); the *_pose strategies go through mcd_score + mcd_aggregate");
-        if (aggr == MCD_AGGR_QUANTILE && !(quantile >= 0.f && quantile <= 1.f))       // (also rejects NaN; torch.quantile raises)
-            return fail(MCD_EINVAL, "quantile must be in [0, 1]");
+        if (int rc = check_aggregation(aggr, quantile, AGGR_LOSSES, "mcd_score_fused aggregates losses (best, worst, mean, median, quantile); "
+                                                                    "the *_pose strategies go through mcd_score + mcd_aggregate")) return rc;
     }
     if (S < 1 || cfg->noise_steps < 2) return fail(MCD_EINVAL, "need n_samples >= 1 and noise_steps >= 2");
     if ((long long)B * S > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x n_samples exceeds 2^31 - 1: score in smaller batches");
-    if (cfg->n_corrupt < 1 || cfg->n_cond + cfg->n_corrupt != cfg->seg_len || cfg->seg_len > MCD_MAX_FRAMES)
-        return fail(MCD_EINVAL, "cond/corrupt index lists do not partition seg_len");
+    if (int rc = check_frame_partition(cfg)) return rc;
     const int strat = w->cfg.strategy;
     const int Tu = w->cfg.t_unet;
     const bool rnd = strat == MCD_STRATEGY_RANDOM_IMP;
@@ -898,15 +452,10 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     hipStream_t st = (hipStream_t)stream;
     ScoreParams P;
     memset(&P, 0, sizeof(P));
-    P.wbuf = w->dbuf; P.prof = g_prof; P.dv.data = data;
+    P.wbuf = w->dbuf; P.prof = g_prof;
     P.tune = w->opt[MCD_OPT_PHASE] == -2 ? nullptr : w->tune;      // (phase -2: the host's estimate only -- A/B of the self-calibration)
-    if (view) {
-        if (view->trans && !view->affine) return fail(MCD_EINVAL, "window view: trans given without an affine table");
-        P.dv.base = reinterpret_cast<const long long*>(view->base); P.dv.sc = view->stride_c; P.dv.st = view->stride_t;
-        P.dv.trans = view->trans; P.dv.aff = view->affine;
-        if (rnd) P.win_mask = view->cond_mask;
-        if (!view->base) { P.dv.sc = (long long)cfg->seg_len * 17; P.dv.st = 17; }
-    }
+    if (int rc = window_view(data, view, cfg->seg_len, P.dv)) return rc;
+    if (rnd) P.win_mask = view->cond_mask;
     P.noise = noise; P.step_table = step_table; P.pose_out = pose_out;
     P.seed = seed; P.first_window = first_window_id;
     P.B = B; P.S = S; P.ns = cfg->noise_steps; P.seg_len = cfg->seg_len; P.n_corrupt = cfg->n_corrupt;
@@ -916,11 +465,7 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     // (mocodad.py:672-683), inject / no_condition = the corrupt frames only
     FrameMaps M;
     memset(&M, 0, sizeof(M));
-    // data frames the kernels read (load_coord) must lie inside the window
-    for (int k = 0; k < cfg->n_cond; ++k)
-        if (cfg->cond_idx[k] < 0 || cfg->cond_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "cond_idx outside [0, seg_len)");
-    for (int k = 0; k < cfg->n_corrupt; ++k)
-        if (cfg->corrupt_idx[k] < 0 || cfg->corrupt_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "corrupt_idx outside [0, seg_len)");
+    if (int rc = check_frame_lists(cfg)) return rc;
     for (int k = 0; k < tf && !rnd; ++k) {
         const int t = strat == MCD_STRATEGY_INBETWEEN_IMP ? cfg->cond_idx[k] : k;
         if (t < 0 || t >= Tu || ((P.fixed_mask >> t) & 1)) return fail(MCD_EINVAL, "bad cond_idx");
@@ -944,10 +489,10 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     for (int t = 0; t < 12; ++t) {      // the specialised kernels (<= 12 frames) carry the maps in their parameter block
         P.src_frame[t] = M.src_frame[t]; P.tx_of[t] = M.tx_of[t]; P.pos_of[t] = M.pos_of[t]; P.upd_of[t] = M.upd_of[t];
     }
-    // workspace: [condition embeddings | gathered condition frames][per-sample losses (B,S)][scratch slabs of the runtime-shape kernels]
+    const PoseWorkspace lay = pose_workspace(w, B, S);
     char* wsb = reinterpret_cast<char*>(workspace);
-    float* ws_loss = wsb ? reinterpret_cast<float*>(wsb + ws_cond_bytes(w, B)) : nullptr;
-    float* gen_scratch = wsb ? reinterpret_cast<float*>(wsb + ws_cond_bytes(w, B) + ws_loss_bytes(B, S)) : nullptr;
+    float* ws_loss = wsb ? reinterpret_cast<float*>(wsb + lay.loss) : nullptr;
+    float* gen_scratch = wsb ? reinterpret_cast<float*>(wsb + lay.scratch) : nullptr;
     P.loss_out = loss_all ? loss_all : ws_loss;       // (skipped by a fused launch when the caller did not ask for it)
     if (route == UNET_KERNEL) {           // how the call is cut into workgroups (decides where the condition encoder runs)
         P.plan_only = 1;
@@ -978,18 +523,7 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
         float* emb = reinterpret_cast<float*>(workspace);
         FrameIdx fi;
         for (int k = 0; k < MCD_MAX_FRAMES; ++k) fi.idx[k] = cfg->cond_idx[k];
-        int rc;
-        if (croute == COND_PLAIN || croute == COND_PLAIN_SCRATCH) {      // this encoder reads gathered frames
-            float* cbuf = emb + (size_t)B * EDIM + 16;
-            const int Tc = cfg->n_cond, total = B * C0 * Tc * 17;
-            hipLaunchKernelGGL(gather_frames_kernel, dim3((total + 255) / 256), dim3(256), 0, st, P.dv, cbuf, B, C0, cfg->seg_len,
-                               17, Tc, fi);
-            HIP_TRY(hipGetLastError());
-            rc = launch_cond_plain(w, cbuf, B, emb, gen_scratch, st);
-        } else {
-            rc = launch_cond_view(w, croute, P.dv, fi, cfg->seg_len, emb, B, gen_scratch, st);
-        }
-        if (rc != MCD_OK) return rc;
+        if (int rc = launch_cond(w, croute, P.dv, fi, cfg->seg_len, emb, B, reinterpret_cast<float*>(wsb + lay.gather), gen_scratch, st)) return rc;
         P.cond_emb = emb;
     }
     return score();
@@ -1028,8 +562,7 @@ int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n
     if (cfg->n_windows <= 0) return MCD_OK;
     if (!loss_all || !loss_agg) return fail(MCD_EINVAL, "null argument");
     if (cfg->n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
-    if (strategy < MCD_AGGR_BEST || strategy > MCD_AGGR_QUANTILE) return fail(MCD_EINVAL, "unknown aggregation strategy");
-    if (strategy == MCD_AGGR_QUANTILE && !(quantile >= 0.f && quantile <= 1.f)) return fail(MCD_EINVAL, "quantile must be in [0, 1]");
+    if (int rc = check_aggregation(strategy, quantile, AGGR_ANY, "unknown aggregation strategy")) return rc;
     const bool need_pose = strategy == MCD_AGGR_MEAN_POSE || strategy == MCD_AGGR_MEDIAN_POSE;
     if (need_pose && (!pose_all || !data)) return fail(MCD_EINVAL, "pose strategies need pose_all and data");
     if (pose_agg && !pose_all) return fail(MCD_EINVAL, "pose_agg requested without pose_all");
@@ -1136,7 +669,7 @@ int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n,
 int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* c) {
     if (!c || c->n_clips <= 0 || c->num_transform <= 0 || c->n_persons <= 0 || c->max_frames <= 0) return 0;
     const int64_t rows = (int64_t)c->num_transform * c->n_clips * c->n_persons;
-    return rows * c->max_frames * 4 + (rows * 4 + 255) / 256 * 256;
+    return rows * c->max_frames * 4 + round256(rows * 4);
 }
 
 int mcd_frame_scores(const mcd_frame_cfg_t* c, const float* scores, const int64_t* trans, const int64_t* meta,

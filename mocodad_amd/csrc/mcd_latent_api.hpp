@@ -1,6 +1,7 @@
 // mcd_latent_api.hpp — host side of the MoCoDADlatent entry points (include/mocodad_hip.h): the handle and the calls around the
-// launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose upload helper and condition-encoder launches it shares; the
-// packer is pack_latent_model of mcd_pack.hpp.  It holds no device code.
+// launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose upload helper and condition-encoder routes it shares; the
+// front end of a call (view, checks, workspace layout, launch_cond) is mcd_call.hpp, the packer pack_latent_model of mcd_pack.hpp.
+// It holds no device code.
 #pragma once
 #include "mcd_latent.hpp"
 
@@ -20,88 +21,32 @@ namespace {
 using namespace mcd;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-int64_t lat_ws_cond_bytes(int64_t B) { return (B * EDIM * 4 + 255) / 256 * 256; }
-int64_t lat_ws_z0_bytes(int64_t B, int D) { return (B * D * 4 + 255) / 256 * 256; }
 
-int latent_view(const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view, DataView& dv) {
-    memset(&dv, 0, sizeof(dv));
-    dv.data = data;
-    if (view) {
-        if (view->trans && !view->affine) return fail(MCD_EINVAL, "window view: trans given without an affine table");
-        dv.base = reinterpret_cast<const long long*>(view->base); dv.sc = view->stride_c; dv.st = view->stride_t;
-        dv.trans = view->trans; dv.aff = view->affine;
-        if (!view->base) { dv.sc = (long long)cfg->seg_len * 17; dv.st = 17; }
-    }
-    return MCD_OK;
-}
-
-int latent_frames(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, FrameIdx& cond_fi, FrameIdx& fi) {
+// gather / plain: the two scratch regions of latent_workspace() (null where the handle's route has none)
+int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                       const float* step_table, float* cond_out, float* z0_out, float* gather, float* plain, hipStream_t st) {
+    DataView dv;
+    if (int rc = window_view(data, view, cfg->seg_len, dv)) return rc;
     if (cfg->n_corrupt != w->cfg.t_unet || cfg->n_cond != w->cfg.t_cond) return fail(MCD_EINVAL, "frame split does not match the packed model (t_unet / t_cond)");
-    if (cfg->n_cond + cfg->n_corrupt != cfg->seg_len || cfg->seg_len > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "cond/corrupt index lists do not partition seg_len");
+    if (int rc = check_frame_partition(cfg)) return rc;
+    if (int rc = check_frame_lists(cfg)) return rc;
+    FrameIdx cond_fi, fi;
     memset(&cond_fi, 0, sizeof(cond_fi));
     memset(&fi, 0, sizeof(fi));
-    for (int k = 0; k < cfg->n_cond; ++k) {
-        if (cfg->cond_idx[k] < 0 || cfg->cond_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "cond_idx outside [0, seg_len)");
-        cond_fi.idx[k] = cfg->cond_idx[k];
-    }
-    for (int k = 0; k < cfg->n_corrupt; ++k) {
-        if (cfg->corrupt_idx[k] < 0 || cfg->corrupt_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "corrupt_idx outside [0, seg_len)");
-        fi.idx[k] = cfg->corrupt_idx[k];
-    }
-    return MCD_OK;
-}
-
-// Which condition-encoder kernel serves a latent handle (decided here and nowhere else)
-enum LatentCondRoute {
-    LAT_COND_FUSED,       // shipped encoder at t_cond = t_unet: inside the encode launch
-    LAT_COND_FAST,        // shipped channel list, another t_cond (or MCD_LATENT_OPT_SPLIT_ENCODE): cond_fast_kernel
-    LAT_COND_UNET,        // 'E_unet': cond_unet_kernel
-    LAT_COND_PLAIN        // any other channel list: gather_frames_kernel + cond_encode_kernel
-};
-LatentCondRoute latent_cond_route(const mcd_latent_weights* w) {
-    if (w->cw.cond_unet) return LAT_COND_UNET;
-    if (w->fused_ok && !w->opt[MCD_LATENT_OPT_SPLIT_ENCODE]) return LAT_COND_FUSED;
-    return w->cw.cond_fast ? LAT_COND_FAST : LAT_COND_PLAIN;      // (no cond_fast_kernel for t_cond: a developer build)
-}
-// scratch of the plain encoder (independent of the options): the gathered condition frames, and its third buffer under gmode
-int64_t lat_ws_gather_bytes(const mcd_latent_weights* w, int64_t B) {
-    if (w->cw.cond_unet || w->cw.cond_fast) return 0;
-    return (B * C0 * w->cfg.t_cond * 17 * 4 + 255) / 256 * 256;
-}
-int64_t lat_ws_plain_bytes(const mcd_latent_weights* w, int64_t B) {
-    if (w->cw.cond_unet || w->cw.cond_fast) return 0;
-    return (cond_scratch_bytes(&w->cw, COND_PLAIN_SCRATCH, B) + 255) / 256 * 256;
-}
-
-// scratch: lat_ws_gather_bytes + lat_ws_plain_bytes of device memory (null when both are 0)
-int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
-                       const float* step_table, float* cond_out, float* z0_out, char* scratch, hipStream_t st) {
-    DataView dv;
-    int rc = latent_view(cfg, data, view, dv);
-    if (rc != MCD_OK) return rc;
-    FrameIdx cond_fi, fi;
-    rc = latent_frames(w, cfg, cond_fi, fi);
-    if (rc != MCD_OK) return rc;
+    for (int k = 0; k < cfg->n_cond; ++k) cond_fi.idx[k] = cfg->cond_idx[k];
+    for (int k = 0; k < cfg->n_corrupt; ++k) fi.idx[k] = cfg->corrupt_idx[k];
     // row ns of the table: the constant time step -1 the encoder is given (mocodad_latent.py:95)
     const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
     const int B = cfg->n_windows;
-    const LatentCondRoute route = latent_cond_route(w);
-    if (route == LAT_COND_FAST) {
-        rc = launch_cond_fast(&w->cw, dv, cond_fi, cfg->seg_len, cond_out, B, st);
-    } else if (route == LAT_COND_UNET) {
-        rc = launch_cond_unet(&w->cw, dv, cond_fi, cfg->seg_len, cond_out, B, st);
-    } else if (route == LAT_COND_PLAIN) {
-        if (!scratch) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
-        float* cbuf = reinterpret_cast<float*>(scratch);
-        const int Tc = cfg->n_cond;
-        const long long total = (long long)B * C0 * Tc * 17;
-        if (total > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x condition frames exceeds 2^31 - 1 elements: score in smaller batches");
-        hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, dv, cbuf, B, C0, cfg->seg_len, 17, Tc, cond_fi);
-        HIP_TRY(hipGetLastError());
-        rc = launch_cond_plain(&w->cw, cbuf, B, cond_out, reinterpret_cast<float*>(scratch + lat_ws_gather_bytes(w, B)), st);
-    }
-    if (rc != MCD_OK) return rc;
-    return launch_latent_encode(w->cfg.t_unet, route == LAT_COND_FUSED, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
+    // the pose model's routes: in the encode launch (shipped encoder at t_cond = t_unet), or a launch of its own in front of it
+    const CondRoute route = cond_route(&w->cw, w->fused_ok && !w->opt[MCD_LATENT_OPT_SPLIT_ENCODE]);
+    const bool plain_route = route == COND_PLAIN || route == COND_PLAIN_SCRATCH;
+    if (route != COND_INKERNEL && route != COND_FAST && route != COND_UNET && !plain_route)      // (a developer build without the frame count)
+        return fail(MCD_EUNSUPPORTED, "E_unet condition encoder: frame count not instantiated");
+    if (plain_route && !gather) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
+    if (route != COND_INKERNEL)
+        if (int rc = launch_cond(&w->cw, route, dv, cond_fi, cfg->seg_len, cond_out, B, gather, plain, st)) return rc;
+    return launch_latent_encode(w->cfg.t_unet, route == COND_INKERNEL, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
                                 B, st);
 }
 
@@ -123,9 +68,8 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
     memset(w->opt, 0, sizeof(w->opt));
     w->fused_ok = m.fused_ok != 0;
     w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
-    w->cw.has_cond = true; w->cw.cond_fast = m.cond.fast; w->cw.cond_unet = m.cond.unet;
-    w->cw.cond = m.cond.Cw;
-    w->cw.cond.base = w->dbuf;
+    memset(w->cw.opt, 0, sizeof(w->cw.opt));
+    set_cond_weights(&w->cw, m, dbuf);
     *out = w;
     return MCD_OK;
 }
@@ -145,7 +89,7 @@ void mcd_free_latent_weights(mcd_latent_weights_t* w) {
 
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows) {
     if (!w || n_windows <= 0) return 0;
-    return lat_ws_cond_bytes(n_windows) + lat_ws_z0_bytes(n_windows, w->net.D) + lat_ws_gather_bytes(w, n_windows) + lat_ws_plain_bytes(w, n_windows);
+    return latent_workspace(&w->cw, n_windows, w->net.D).bytes;
 }
 
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
@@ -156,10 +100,12 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
     hipStream_t st = (hipStream_t)stream;
     // no workspace argument here: the plain encoder's scratch comes from the stream-ordered allocator
-    const int64_t need = lat_ws_gather_bytes(w, cfg->n_windows) + lat_ws_plain_bytes(w, cfg->n_windows);
+    const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D);
+    const int64_t need = lay.bytes - lay.gather;
     char* scratch = nullptr;
     if (need > 0) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)need, st));
-    const int rc = latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, scratch, st);
+    const int rc = latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, reinterpret_cast<float*>(scratch),
+                                      scratch ? reinterpret_cast<float*>(scratch + (lay.plain - lay.gather)) : nullptr, st);
     if (scratch) {
         const hipError_t e = hipFreeAsync(scratch, st);
         if (rc == MCD_OK && e != hipSuccess) return fail(MCD_EDEVICE, std::string("hipFreeAsync: ") + hipGetErrorString(e));
@@ -193,10 +139,7 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
         if (!loss_all) return fail(MCD_EINVAL, "null argument");
     } else {
         if (!loss_agg) return fail(MCD_EINVAL, "null argument");
-        if (aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST && aggregation != MCD_AGGR_MEAN && aggregation != MCD_AGGR_MEDIAN &&
-            aggregation != MCD_AGGR_QUANTILE)
-            return fail(MCD_EINVAL, "mcd_latent_score aggregates losses (best, worst, mean, median, quantile)");
-        if (aggregation == MCD_AGGR_QUANTILE && !(quantile >= 0.f && quantile <= 1.f)) return fail(MCD_EINVAL, "quantile must be in [0, 1]");
+        if (int rc = check_aggregation(aggregation, quantile, AGGR_LOSSES, "mcd_latent_score aggregates losses (best, worst, mean, median, quantile)")) return rc;
     }
     if (S < 1 || cfg->noise_steps < 2) return fail(MCD_EINVAL, "need n_samples >= 1 and noise_steps >= 2");
     if (S > LAT_MAX_S) return fail(MCD_EUNSUPPORTED, "n_samples " + std::to_string(S) + ": at most " + std::to_string(LAT_MAX_S) + " per call");
@@ -205,11 +148,12 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
     if (noise && !aligned16(noise)) return fail(MCD_EINVAL, "noise must be 16-byte aligned");
     if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    float* cond = reinterpret_cast<float*>(workspace);
-    float* z0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + lat_ws_cond_bytes(B));
-    char* scratch = reinterpret_cast<char*>(workspace) + lat_ws_cond_bytes(B) + lat_ws_z0_bytes(B, D);
-    int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, scratch, st);
-    if (rc != MCD_OK) return rc;
+    const LatentWorkspace lay = latent_workspace(&w->cw, B, D);
+    char* wsb = reinterpret_cast<char*>(workspace);
+    float* cond = reinterpret_cast<float*>(wsb);
+    float* z0 = reinterpret_cast<float*>(wsb + lay.z0);
+    if (int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, reinterpret_cast<float*>(wsb + lay.gather),
+                                    reinterpret_cast<float*>(wsb + lay.plain), st)) return rc;
     LatentChainParams P;
     memset(&P, 0, sizeof(P));
     P.wbuf = w->dbuf; P.net = w->net; P.cond = cond; P.z0 = z0; P.noise = noise; P.step_table = step_table;

@@ -34,87 +34,124 @@ def _quantile_of(strategy: str) -> float:
     return q
 
 
-class HipScorer:
-    """One packed model on one GPU.
+LOSS_AGGREGATIONS = ("best", "worst", "mean", "median", "quantile")
 
-    state_dict: the reference's Lightning-checkpoint keys ('model.*', 'condition_encoder.*') -> tensors.
-    strategy: canonical conditioning strategy ('inject' | 'concat' | 'no_condition' | 'inbetween_imp').
-    cond_channels: output channels of the 'AE' / 'E' condition encoder's layers; cond_unet: 'E_unet' encoder instead.
-    """
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], *, strategy: str, seg_len: int, cond_idx: Sequence[int],
-                 corrupt_idx: Sequence[int], cond_channels: Sequence[int] = (), cond_unet: bool = False,
-                 num_coords: int = 2, n_joints: int = 17, emb_dim: int = 16, device=None,
-                 options: Optional[Dict[str, int]] = None):
+def _aggregation_of(strategy: str, allowed, error: str) -> Tuple[str, float]:
+    """'best' | ... | 'quantile:q' -> (name in _lib.AGGR, q); ValueError(error) for a name outside `allowed`."""
+    name, q = strategy, 0.0
+    if "quantile" in strategy:
+        q, name = _quantile_of(strategy), "quantile"
+    if name not in allowed:
+        raise ValueError(error)
+    return name, q
+
+
+def _seed64(seed: int):
+    return C.c_uint64(seed & (2**64 - 1))
+
+
+def _need_gpu() -> None:
+    if not torch.cuda.is_available():
+        raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
+
+
+def _out_vector(out: Optional[torch.Tensor], B: int, device) -> torch.Tensor:
+    """The (B,) fp32 result vector of a call: the caller's preallocated `out`, checked, or a new one."""
+    if out is None:
+        return torch.empty(B, device=device, dtype=torch.float32)
+    if out.shape != (B,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError("out must be a contiguous float32 (B,) tensor on the scorer's device")
+    return out
+
+
+def _window_view(wb=None, cond_mask: Optional[torch.Tensor] = None) -> "_lib.WindowView":
+    """mcd_window_view_t of a WindowBatch (None: dense windows) and / or per-window condition-frame bitmasks."""
+    mask = cond_mask.data_ptr() if cond_mask is not None else None
+    if wb is None:
+        return _lib.WindowView(base=None, stride_c=0, stride_t=0, trans=None, affine=None, cond_mask=mask)
+    return _lib.WindowView(base=wb.base.data_ptr(), stride_c=wb.stride_c, stride_t=wb.stride_t,
+                           trans=wb.trans.data_ptr() if wb.trans is not None else None,
+                           affine=wb.affine.data_ptr() if wb.affine is not None else None, cond_mask=mask)
+
+
+def _pack_tensors(state_dict):
+    """state_dict -> (ctypes array of mcd_tensor_t, count, host copies to keep alive during the call)."""
+    keep = []
+    arr = (_lib.Tensor * len(state_dict))()
+    n = 0
+    for k, v in state_dict.items():
+        if not torch.is_tensor(v) or not v.dtype.is_floating_point:
+            continue
+        h = v.detach().to("cpu", torch.float32).contiguous()
+        keep.append(h)
+        arr[n].name = k.encode()
+        arr[n].data = h.data_ptr()
+        arr[n].numel = h.numel()
+        n += 1
+    return arr, n, keep
+
+
+class _Scorer:
+    """What HipScorer and LatentScorer share: the model's frame lists and sizes, the per-call config, the step-table cache, one
+    workspace per stream, the handle's options and its release.  A subclass names its library entries and its step table."""
+
+    _OPTIONS: Dict[str, int] = {}       # option name -> id, and the entries that set one / free the handle
+    _SET_OPTION = _FREE = ""
+    _step_table = None
+
+    def _init_model(self, seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim) -> None:
         self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-        self.strategy = strategy
+        self._h = None
         self.seg_len = int(seg_len)
         self.cond_idx = [int(i) for i in cond_idx]
         self.corrupt_idx = [int(i) for i in corrupt_idx]
         self.num_coords, self.n_joints, self.emb_dim = num_coords, n_joints, emb_dim
-        self.t_cond = len(self.cond_idx) if strategy == "inject" else 0
-        self.t_unet = len(self.corrupt_idx) + (len(self.cond_idx) if strategy in ("concat", "inbetween_imp", "random_imp") else 0)
         self._tables: Dict[int, torch.Tensor] = {}
-        self._ws: Dict[int, torch.Tensor] = {}   # condition-embedding workspace, one per stream (launches on different
-        #                                          streams may overlap, each needs its own)
+        self._ws: Dict[int, torch.Tensor] = {}   # workspace, one per stream (launches on different streams may overlap, each
+        #                                          needs its own)
 
+    def _model_cfg(self, strategy: str, t_unet: int, t_cond: int, cond_channels, cond_unet: bool) -> "_lib.ModelCfg":
         cfg = _lib.ModelCfg()
-        cfg.num_coords, cfg.n_joints, cfg.t_unet, cfg.t_cond = num_coords, n_joints, self.t_unet, self.t_cond
-        cfg.emb_dim, cfg.strategy = emb_dim, _lib.STRATEGY[strategy]
+        cfg.num_coords, cfg.n_joints, cfg.t_unet, cfg.t_cond = self.num_coords, self.n_joints, t_unet, t_cond
+        cfg.emb_dim, cfg.strategy = self.emb_dim, _lib.STRATEGY[strategy]
         if strategy == "inject" and cond_unet:      # 'E_unet' condition encoder (the U-Net's down path)
             cfg.cond_layers = _lib.COND_UNET
         else:
             cfg.cond_layers = len(cond_channels) if strategy == "inject" else 0
             for i, c in enumerate(cond_channels):
                 cfg.cond_channels[i] = int(c)
-        keep = []  # keep host copies alive during the call
-        arr = (_lib.Tensor * len(state_dict))()
-        n = 0
-        for k, v in state_dict.items():
-            if not torch.is_tensor(v) or not v.dtype.is_floating_point:
-                continue
-            h = v.detach().to("cpu", torch.float32).contiguous()
-            keep.append(h)
-            arr[n].name = k.encode()
-            arr[n].data = h.data_ptr()
-            arr[n].numel = h.numel()
-            n += 1
-        handle = C.c_void_p()
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_pack_weights(arr, n, C.byref(cfg), idx, C.byref(handle)))
-        self._h = handle
+        return cfg
+
+    def _set_options(self, options: Optional[Dict[str, int]]) -> None:
         for name, value in (options or {}).items():
             self.set_option(name, value)
 
     def set_option(self, name: str, value: int) -> None:
-        """Per-handle switch of the library (include/mocodad_hip.h MCD_OPT_*): 'variant', 'cond_generic',
-        'generic_unet', 'split', 'phase'."""
-        if name not in _lib.OPT:
-            raise ValueError(f"unknown option {name!r} (known: {sorted(_lib.OPT)})")
-        _lib.check(self.L.mcd_set_option(self._h, _lib.OPT[name], int(value)))
+        """Per-handle switch of the library (include/mocodad_hip.h): MCD_OPT_* 'variant', 'cond_generic', 'generic_unet', 'split',
+        'phase' on a HipScorer; MCD_LATENT_OPT_* 'split_encode' on a LatentScorer (1 makes the shipped configuration take the
+        three-launch form, condition encoder as its own launch, as well)."""
+        if name not in self._OPTIONS:
+            raise ValueError(f"unknown option {name!r} (known: {sorted(self._OPTIONS)})")
+        _lib.check(getattr(self.L, self._SET_OPTION)(self._h, self._OPTIONS[name], int(value)))
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
             try:
-                self.L.mcd_free_weights(h)
+                getattr(self.L, self._FREE)(h)
             except Exception:
                 pass
             self._h = None
 
-    # ------------------------------------------------------------------ helpers
     def table(self, noise_steps: int) -> torch.Tensor:
         t = self._tables.get(noise_steps)
         if t is None:
-            t = step_table(noise_steps, self.emb_dim).to(self.device)
+            t = self._step_table(noise_steps, self.emb_dim).to(self.device)
             self._tables[noise_steps] = t
         return t
 
-    def _score_cfg(self, B: int, S: int, ns: int, loss_fn: str) -> "_lib.ScoreCfg":
+    def _score_cfg(self, B: int, S: int, ns: int, loss_fn: str = "smooth_l1") -> "_lib.ScoreCfg":
         c = _lib.ScoreCfg()
         c.n_windows, c.n_samples, c.noise_steps, c.seg_len = B, S, ns, self.seg_len
         c.n_cond, c.n_corrupt = len(self.cond_idx), len(self.corrupt_idx)
@@ -124,6 +161,66 @@ class HipScorer:
             c.corrupt_idx[i] = v
         c.loss_fn = _lib.LOSS[loss_fn]
         return c
+
+    def _workspace(self, need: int) -> torch.Tensor:
+        """The current stream's workspace, at least `need` bytes.  Call inside `torch.cuda.device(self.device)`."""
+        sid = torch.cuda.current_stream().cuda_stream
+        ws = self._ws.get(sid)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[sid] = torch.empty(max(need, 256), device=self.device, dtype=torch.uint8)
+        return ws
+
+    def _check_shape(self, what: str, t: torch.Tensor, tail: Tuple[int, ...]) -> None:
+        if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tuple(tail):
+            raise ValueError(f"{what} must have shape (B, {', '.join(map(str, tail))}), got {tuple(t.shape)}")
+
+    def _windows(self, data, cond_mask: Optional[torch.Tensor] = None):
+        """(B,C,T,V) tensor or WindowBatch, (B,) int32 device bitmasks | None -> (data tensor, WindowView | None, B, keep-alive)"""
+        if hasattr(data, "as_view"):
+            wb = data.to(self.device)
+            if wb.seg_len != self.seg_len:
+                raise ValueError(f"window view has seg_len {wb.seg_len}, model expects {self.seg_len}")
+            out = wb.buffer, _window_view(wb, cond_mask), int(wb.base.shape[0]), wb
+        else:
+            self._check_shape("data", data, (self.num_coords, self.seg_len, self.n_joints))
+            data = _f32c(data, self.device)
+            # (dense windows need a view only for their per-window condition sets)
+            out = data, _window_view(None, cond_mask) if cond_mask is not None else None, int(data.shape[0]), None
+        if cond_mask is not None and cond_mask.numel() != out[2]:
+            raise ValueError(f"cond_mask must have {out[2]} entries")
+        return out
+
+
+class HipScorer(_Scorer):
+    """One packed model on one GPU.
+
+    state_dict: the reference's Lightning-checkpoint keys ('model.*', 'condition_encoder.*') -> tensors.
+    strategy: canonical conditioning strategy ('inject' | 'concat' | 'no_condition' | 'inbetween_imp').
+    cond_channels: output channels of the 'AE' / 'E' condition encoder's layers; cond_unet: 'E_unet' encoder instead.
+    """
+
+    _OPTIONS, _SET_OPTION, _FREE = _lib.OPT, "mcd_set_option", "mcd_free_weights"
+    _step_table = staticmethod(step_table)
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, strategy: str, seg_len: int, cond_idx: Sequence[int],
+                 corrupt_idx: Sequence[int], cond_channels: Sequence[int] = (), cond_unet: bool = False,
+                 num_coords: int = 2, n_joints: int = 17, emb_dim: int = 16, device=None,
+                 options: Optional[Dict[str, int]] = None):
+        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
+        _need_gpu()
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.strategy = strategy
+        self.t_cond = len(self.cond_idx) if strategy == "inject" else 0
+        self.t_unet = len(self.corrupt_idx) + (len(self.cond_idx) if strategy in ("concat", "inbetween_imp", "random_imp") else 0)
+        cfg = self._model_cfg(strategy, self.t_unet, self.t_cond, cond_channels, cond_unet)
+        arr, n, keep = _pack_tensors(state_dict)
+        handle = C.c_void_p()
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_pack_weights(arr, n, C.byref(cfg), idx, C.byref(handle)))
+        del keep
+        self._h = handle
+        self._set_options(options)
 
     def plan_split(self, n_windows: int, n_samples: int, noise_steps: int) -> int:
         """How a scoring call of this size is cut into workgroups (mcd_plan_split): 1 = ONE launch (a workgroup runs all samples
@@ -137,10 +234,6 @@ class HipScorer:
         return r
 
     # ------------------------------------------------------------------ entry points
-    def _check_shape(self, what: str, t: torch.Tensor, tail: Tuple[int, ...]) -> None:
-        if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tuple(tail):
-            raise ValueError(f"{what} must have shape (B, {', '.join(map(str, tail))}), got {tuple(t.shape)}")
-
     def cond_encode(self, cond_data: torch.Tensor) -> torch.Tensor:
         if self.strategy != "inject":
             raise ValueError("this model has no condition encoder")
@@ -194,31 +287,11 @@ class HipScorer:
 
     def _score(self, data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask, *, aggregation,
                want_all, out):
-        view = None
-        keep = None
         if (cond_mask is not None) != (self.strategy == "random_imp"):
             raise ValueError("cond_mask is required by, and only valid for, the random_imp strategy")
         if cond_mask is not None:
             cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
-        if hasattr(data, "as_view"):
-            wb = data.to(self.device)
-            keep = wb
-            view = _lib.WindowView(base=wb.base.data_ptr(), stride_c=wb.stride_c, stride_t=wb.stride_t,
-                                   trans=wb.trans.data_ptr() if wb.trans is not None else None,
-                                   affine=wb.affine.data_ptr() if wb.affine is not None else None,
-                                   cond_mask=cond_mask.data_ptr() if cond_mask is not None else None)
-            B = int(wb.base.shape[0])
-            data = wb.buffer
-            if wb.seg_len != self.seg_len:
-                raise ValueError(f"window view has seg_len {wb.seg_len}, model expects {self.seg_len}")
-        else:
-            self._check_shape("data", data, (self.num_coords, self.seg_len, self.n_joints))
-            data = _f32c(data, self.device)
-            B = data.shape[0]
-            if cond_mask is not None:     # dense windows + per-window condition sets
-                view = _lib.WindowView(base=None, stride_c=0, stride_t=0, trans=None, affine=None, cond_mask=cond_mask.data_ptr())
-        if cond_mask is not None and cond_mask.numel() != B:
-            raise ValueError(f"cond_mask must have {B} entries")
+        data, view, B, keep = self._windows(data, cond_mask)
         S = int(n_samples)
         Tx = len(self.corrupt_idx)
         cfg = self._score_cfg(B, S, int(noise_steps), loss_fn)
@@ -229,27 +302,15 @@ class HipScorer:
             exp = (S, max(noise_steps - 1, 1), B, self.num_coords, Tx, self.n_joints)
             if tuple(noise.shape) != exp:
                 raise ValueError(f"noise must have shape {exp}, got {tuple(noise.shape)}")
-        agg, q, name = None, 0.0, None
+        agg = None
         if aggregation is not None:
-            name = aggregation
-            if "quantile" in aggregation:
-                q, name = _quantile_of(aggregation), "quantile"
-            if name not in ("best", "worst", "mean", "median", "quantile"):
-                raise ValueError(f"score_fused aggregates losses (best, worst, mean, median, quantile:q), not {aggregation!r}")
-            if out is None:
-                agg = torch.empty(B, device=self.device, dtype=torch.float32)
-            elif out.shape != (B,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-                raise ValueError("out must be a contiguous float32 (B,) tensor on the scorer's device")
-            else:
-                agg = out
+            name, q = _aggregation_of(aggregation, LOSS_AGGREGATIONS,
+                                      f"score_fused aggregates losses (best, worst, mean, median, quantile:q), not {aggregation!r}")
+            agg = _out_vector(out, B, self.device)
         need = int(self.L.mcd_score_workspace_bytes(self._h, C.byref(cfg)))
         with torch.cuda.device(self.device):
-            sid = torch.cuda.current_stream().cuda_stream
-            ws = self._ws.get(sid)
-            if ws is None or ws.numel() < need:
-                ws = self._ws[sid] = torch.empty(max(need, 256), device=self.device, dtype=torch.uint8)
             common = (self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None, _ptr(noise),
-                      C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), _ptr(self.table(noise_steps)), _ptr(ws))
+                      _seed64(seed), C.c_int64(first_window_id), _ptr(self.table(noise_steps)), _ptr(self._workspace(need)))
             if aggregation is None:
                 _lib.check(self.L.mcd_score_view(*common, _ptr(loss), _ptr(poses), _stream()))
             else:
@@ -294,7 +355,7 @@ class HipScorer:
         S, K, Tx = int(n_samples), max(int(noise_steps) - 1, 1), len(self.corrupt_idx)
         out = torch.empty(S, K, int(n_windows), self.num_coords, Tx, self.n_joints, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_philox_noise(C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), int(n_windows), S,
+            _lib.check(self.L.mcd_philox_noise(_seed64(seed), C.c_int64(first_window_id), int(n_windows), S,
                                                int(noise_steps), Tx, _ptr(out), _stream()))
         return out
 
@@ -308,7 +369,7 @@ class HipScorer:
             raise ValueError("n_windows must be >= 0")
         out = torch.empty(n, device=self.device, dtype=torch.int32)
         with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_random_imp_masks(C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), n, self.seg_len,
+            _lib.check(self.L.mcd_random_imp_masks(_seed64(seed), C.c_int64(first_window_id), n, self.seg_len,
                                                    len(self.cond_idx), _ptr(out), _stream()))
         return out
 
@@ -324,13 +385,7 @@ class HipScorer:
         loss_all = _f32c(loss_all, self.device)
         if poses_all is not None:
             poses_all = _f32c(poses_all, self.device)
-        q = 0.0
-        name = strategy
-        if "quantile" in strategy:
-            q = _quantile_of(strategy)
-            name = "quantile"
-        if name not in _lib.AGGR or name == "all":
-            raise ValueError(f"Unknown aggregation strategy {strategy}")
+        name, q = _aggregation_of(strategy, [a for a in _lib.AGGR if a != "all"], f"Unknown aggregation strategy {strategy}")
         cfg = self._score_cfg(B, S, int(noise_steps), loss_fn)
         needs_data = name in ("mean_pose", "median_pose")
         if torch.is_tensor(data):
@@ -339,10 +394,7 @@ class HipScorer:
             raise ValueError("the *_pose aggregation strategies need the materialised (B,C,T,V) windows")
         else:
             data = None
-        if out is None:
-            out = torch.empty(B, device=self.device, dtype=torch.float32)
-        elif out.shape != (B,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous float32 (B,) tensor on the scorer's device")
+        out = _out_vector(out, B, self.device)
         gives_pose = name in ("best", "worst", "mean_pose", "median_pose")
         pose = None
         if gives_pose and want_pose and poses_all is not None:
@@ -356,7 +408,7 @@ class HipScorer:
                 _lib.check(self.L.mcd_aggregate(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
                                                 _ptr(loss_all), _ptr(poses_all), _ptr(data), _ptr(out), _ptr(pose), _stream()))
             else:
-                view = _lib.WindowView(base=None, stride_c=0, stride_t=0, trans=None, affine=None, cond_mask=cond_mask.data_ptr())
+                view = _window_view(None, cond_mask)
                 _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
                                                      _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view), _ptr(out), _ptr(pose),
                                                      _stream()))
@@ -373,24 +425,7 @@ class HipScorer:
         return out
 
 
-def _pack_tensors(state_dict):
-    """state_dict -> (ctypes array of mcd_tensor_t, count, host copies to keep alive during the call)."""
-    keep = []
-    arr = (_lib.Tensor * len(state_dict))()
-    n = 0
-    for k, v in state_dict.items():
-        if not torch.is_tensor(v) or not v.dtype.is_floating_point:
-            continue
-        h = v.detach().to("cpu", torch.float32).contiguous()
-        keep.append(h)
-        arr[n].name = k.encode()
-        arr[n].data = h.data_ptr()
-        arr[n].numel = h.numel()
-        n += 1
-    return arr, n, keep
-
-
-class LatentScorer:
+class LatentScorer(_Scorer):
     """One packed MoCoDADlatent model (stage 'diffusion') on one GPU: the mcd_latent_* entry points.
 
     state_dict: the reference's keys ('model.*' without an up path, 'condition_encoder.*', 'denoiser.*').
@@ -398,30 +433,18 @@ class LatentScorer:
     latent_dim / hidden_sizes: latent_embedding_dim and the denoiser's layer widths (the last equals latent_dim).
     3 corrupt frames, 1 .. 12 condition frames (mcd_pack_latent_weights)."""
 
+    _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
+    _step_table = staticmethod(latent_step_table)
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
                  cond_channels: Sequence[int] = (), latent_dim: int, hidden_sizes: Sequence[int], cond_unet: bool = False,
                  num_coords: int = 2, n_joints: int = 17, emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
-        self.L = _lib.lib()
-        self.seg_len = int(seg_len)
-        self.cond_idx = [int(i) for i in cond_idx]
-        self.corrupt_idx = [int(i) for i in corrupt_idx]
-        self.num_coords, self.n_joints, self.emb_dim = num_coords, n_joints, emb_dim
+        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
         self.latent_dim = int(latent_dim)
         self.hidden_sizes = [int(h) for h in hidden_sizes]
-        self._tables: Dict[int, torch.Tensor] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
-        self._h = None
-        cfg = _lib.ModelCfg()
-        cfg.num_coords, cfg.n_joints, cfg.t_unet, cfg.t_cond = num_coords, n_joints, len(self.corrupt_idx), len(self.cond_idx)
-        cfg.emb_dim, cfg.strategy = emb_dim, _lib.STRATEGY["inject"]
         if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
             raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
-        if cond_unet:      # 'E_unet' condition encoder (the U-Net's down path), as HipScorer passes it
-            cfg.cond_layers = _lib.COND_UNET
-        else:
-            cfg.cond_layers = len(cond_channels)
-            for i, c in enumerate(cond_channels):
-                cfg.cond_channels[i] = int(c)
+        cfg = self._model_cfg("inject", len(self.corrupt_idx), len(self.cond_idx), cond_channels, cond_unet)
         lcfg = _lib.LatentCfg()
         lcfg.latent_dim, lcfg.n_layers = self.latent_dim, len(self.hidden_sizes)
         for i, h in enumerate(self.hidden_sizes[:8]):       # (more than 8 layers: the library refuses n_layers)
@@ -435,64 +458,14 @@ class LatentScorer:
         _lib.check(self.L.mcd_pack_latent_weights(arr, n, C.byref(cfg), C.byref(lcfg), idx, C.byref(handle)))
         del keep
         self._h = handle
-        for name, value in (options or {}).items():
-            self.set_option(name, value)
-
-    def set_option(self, name: str, value: int) -> None:
-        """Per-handle switch of the library (include/mocodad_hip.h MCD_LATENT_OPT_*): 'split_encode' = 1 makes the shipped
-        configuration take the three-launch form (condition encoder as its own launch) as well."""
-        if name not in _lib.LATENT_OPT:
-            raise ValueError(f"unknown option {name!r} (known: {sorted(_lib.LATENT_OPT)})")
-        _lib.check(self.L.mcd_latent_set_option(self._h, _lib.LATENT_OPT[name], int(value)))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                self.L.mcd_free_latent_weights(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def table(self, noise_steps: int) -> torch.Tensor:
-        t = self._tables.get(noise_steps)
-        if t is None:
-            t = latent_step_table(noise_steps, self.emb_dim).to(self.device)
-            self._tables[noise_steps] = t
-        return t
-
-    def _cfg(self, B: int, S: int, ns: int, loss_fn: str = "smooth_l1") -> "_lib.ScoreCfg":
-        c = _lib.ScoreCfg()
-        c.n_windows, c.n_samples, c.noise_steps, c.seg_len = B, S, ns, self.seg_len
-        c.n_cond, c.n_corrupt = len(self.cond_idx), len(self.corrupt_idx)
-        for i, v in enumerate(self.cond_idx):
-            c.cond_idx[i] = v
-        for i, v in enumerate(self.corrupt_idx):
-            c.corrupt_idx[i] = v
-        c.loss_fn = _lib.LOSS[loss_fn]
-        return c
-
-    def _windows(self, data):
-        """-> (data tensor, WindowView | None, B, keep-alive)"""
-        if hasattr(data, "as_view"):
-            wb = data.to(self.device)
-            if wb.seg_len != self.seg_len:
-                raise ValueError(f"window view has seg_len {wb.seg_len}, model expects {self.seg_len}")
-            view = _lib.WindowView(base=wb.base.data_ptr(), stride_c=wb.stride_c, stride_t=wb.stride_t,
-                                   trans=wb.trans.data_ptr() if wb.trans is not None else None,
-                                   affine=wb.affine.data_ptr() if wb.affine is not None else None, cond_mask=None)
-            return wb.buffer, view, int(wb.base.shape[0]), wb
-        if data.dim() != 4 or tuple(data.shape[1:]) != (self.num_coords, self.seg_len, self.n_joints):
-            raise ValueError(f"data must have shape (B, {self.num_coords}, {self.seg_len}, {self.n_joints}), got {tuple(data.shape)}")
-        data = _f32c(data, self.device)
-        return data, None, int(data.shape[0]), None
+        self._set_options(options)
 
     def encode(self, data, *, noise_steps: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
         """windows -> (cond_emb (B,16), z0 (B,D)): condition encoder + down path at t = -1 + to_time_dim (mcd_latent_encode)."""
         data, view, B, keep = self._windows(data)
         cond = torch.empty(B, self.emb_dim, device=self.device, dtype=torch.float32)
         z0 = torch.empty(B, self.latent_dim, device=self.device, dtype=torch.float32)
-        cfg = self._cfg(B, 1, int(noise_steps))
+        cfg = self._score_cfg(B, 1, int(noise_steps))
         with torch.cuda.device(self.device):
             _lib.check(self.L.mcd_latent_encode(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
                                                 _ptr(self.table(int(noise_steps))), _ptr(cond), _ptr(z0), _stream()))
@@ -527,39 +500,26 @@ class LatentScorer:
         S, ns, D = int(n_samples), int(noise_steps), self.latent_dim
         if S < 1 or ns < 2:
             raise ValueError("need n_samples >= 1 and noise_steps >= 2")
-        q, name = 0.0, aggregation
-        if "quantile" in aggregation:
-            q, name = _quantile_of(aggregation), "quantile"
-        if name not in ("all", "best", "worst", "mean", "median", "quantile"):
-            raise ValueError(f"the latent scoring call aggregates losses (all, best, worst, mean, median, quantile:q), not {aggregation!r}")
+        name, q = _aggregation_of(aggregation, ("all",) + LOSS_AGGREGATIONS,
+                                  f"the latent scoring call aggregates losses (all, best, worst, mean, median, quantile:q), not {aggregation!r}")
         if noise is not None:
             noise = _f32c(noise, self.device)
             exp = (S, max(ns - 1, 1), B, D)
             if tuple(noise.shape) != exp:
                 raise ValueError(f"noise must have shape {exp}, got {tuple(noise.shape)}")
         dev = self.device
-        agg = None
-        if out is not None:
-            if name == "all":
-                raise ValueError("out takes the aggregated losses: not valid with aggregation 'all'")
-            if out.shape != (B,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-                raise ValueError("out must be a contiguous float32 (B,) tensor on the scorer's device")
-            agg = out
-        elif name != "all":
-            agg = torch.empty(B, device=dev, dtype=torch.float32)
+        if out is not None and name == "all":
+            raise ValueError("out takes the aggregated losses: not valid with aggregation 'all'")
+        agg = None if name == "all" else _out_vector(out, B, dev)
         loss = torch.empty(B, S, device=dev, dtype=torch.float32) if (want_all or name == "all") else None
         lat = torch.empty(B, S, D, device=dev, dtype=torch.float32) if want_latents else None
         code = torch.empty(B, D, device=dev, dtype=torch.float32) if want_code else None
-        cfg = self._cfg(B, S, ns, loss_fn)
+        cfg = self._score_cfg(B, S, ns, loss_fn)
         with torch.cuda.device(dev):
-            need = int(self.L.mcd_latent_workspace_bytes(self._h, B))
-            sid = torch.cuda.current_stream().cuda_stream
-            ws = self._ws.get(sid)
-            if ws is None or ws.numel() < need:
-                ws = self._ws[sid] = torch.empty(max(need, 256), device=dev, dtype=torch.uint8)
+            ws = self._workspace(int(self.L.mcd_latent_workspace_bytes(self._h, B)))
             if B:
                 _lib.check(self.L.mcd_latent_score(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
-                                                   _ptr(noise), C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id),
+                                                   _ptr(noise), _seed64(seed), C.c_int64(first_window_id),
                                                    _ptr(self.table(ns)), _ptr(ws), _lib.AGGR[name], C.c_float(q), _ptr(agg), _ptr(loss),
                                                    _ptr(lat), _ptr(code), _stream()))
         del keep
@@ -570,7 +530,7 @@ class LatentScorer:
         S, K = int(n_samples), max(int(noise_steps) - 1, 1)
         out = torch.empty(S, K, int(n_windows), self.latent_dim, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_latent_philox_noise(C.c_uint64(seed & (2**64 - 1)), C.c_int64(first_window_id), int(n_windows), S,
+            _lib.check(self.L.mcd_latent_philox_noise(_seed64(seed), C.c_int64(first_window_id), int(n_windows), S,
                                                       int(noise_steps), self.latent_dim, _ptr(out), _stream()))
         return out
 
@@ -598,8 +558,7 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
     with the fitted statistics in the CSV's interleaved feature order.  `out`: an (n_frames, 2, 17) fp32 device view to write
     into instead (e.g. a slice of a larger trajectory buffer)."""
     L = _lib.lib()
-    if not torch.cuda.is_available():
-        raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
+    _need_gpu()
     if (center is None) != (scale is None):
         raise ValueError("center and scale go together (both None = no robust scaling)")
     dev = torch.device(device if device is not None else (out.device if out is not None else f"cuda:{torch.cuda.current_device()}"))
@@ -643,8 +602,7 @@ class StreamRings:
     def __init__(self, n_slots: int, seg_len: int, ring_len: int, num_transform: int, vid_res: Sequence[float], center=None,
                  scale=None, *, device=None):
         self.L = _lib.lib()
-        if not torch.cuda.is_available():
-            raise RuntimeError("mocodad_amd needs an MI355X (gfx950) GPU: the scoring path has no CPU fallback")
+        _need_gpu()
         self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.n_slots, self.seg_len, self.ring_len, self.num_transform = int(n_slots), int(seg_len), int(ring_len), int(num_transform)
         self.vid_res = tuple(float(np.float32(v)) for v in vid_res)

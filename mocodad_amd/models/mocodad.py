@@ -14,6 +14,8 @@ Scope: inference scoring with the 'inject', 'concat', 'no_condit
 """
 import argparse
 import os
+import sys
+import time
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -58,6 +60,21 @@ except Exception:  # pragma: no cover - exercised in this image
 
         def on_validation_epoch_start(self):
             pass
+
+
+class _Laps:
+    """Diagnostic: where an epoch end's time goes.  Each call ends a lap; report() prints `fmt` % the laps in milliseconds to
+    stderr when MCD_EPOCH_TIMING is set."""
+
+    def __init__(self):
+        self.t = [time.perf_counter()]
+
+    def __call__(self) -> None:
+        self.t.append(time.perf_counter())
+
+    def report(self, fmt: str) -> None:
+        if os.environ.get("MCD_EPOCH_TIMING"):
+            print(fmt % tuple(1e3 * (b - a) for a, b in zip(self.t[:-1], self.t[1:])), file=sys.stderr)
 
 
 # ------------------------------------------------------------------ parameter containers
@@ -280,23 +297,27 @@ class MoCoDAD(_Base):
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def scorer(self):
-        """Packed-weights handle on the module's current device (built lazily, rebuilt after load_state_dict)."""
+        """Packed-weights handle on the module's current device (built lazily by build_scorer, rebuilt after load_state_dict)."""
         dev = self.device
         if dev.type != "cuda":
-            raise RuntimeError("MoCoDAD (mocodad_amd) scores on an MI355X only: move the module to a cuda device "
+            raise RuntimeError(f"{type(self).__name__} (mocodad_amd) scores on an MI355X only: move the module to a cuda device "
                                "(there is no CPU fallback)")
         key = str(dev)
         if self._scorer is None or self._scorer_key != key:
-            from ..engine import HipScorer
-            ci, xi = self._frame_split()
-            unet_enc = isinstance(self.condition_encoder, CondUNetParams)
-            chans = list(self.condition_encoder.channels) if self.condition_encoder is not None and not unet_enc else []
-            self._scorer = HipScorer(self.state_dict(), strategy=self.conditioning_strategy, seg_len=self.n_frames,
-                                     cond_idx=ci, corrupt_idx=xi, cond_channels=chans, cond_unet=unet_enc,
-                                     num_coords=self.num_coords, n_joints=self.n_joints, emb_dim=self.embedding_dim, device=dev,
-                                     options=self.hip_options)
+            self._scorer = self.build_scorer(dev)
             self._scorer_key = key
         return self._scorer
+
+    def build_scorer(self, device):
+        """The engine object that packs this module's weights (a subclass with another model overrides this alone)."""
+        from ..engine import HipScorer
+        ci, xi = self._frame_split()
+        unet_enc = isinstance(self.condition_encoder, CondUNetParams)
+        chans = list(self.condition_encoder.channels) if self.condition_encoder is not None and not unet_enc else []
+        return HipScorer(self.state_dict(), strategy=self.conditioning_strategy, seg_len=self.n_frames,
+                         cond_idx=ci, corrupt_idx=xi, cond_channels=chans, cond_unet=unet_enc,
+                         num_coords=self.num_coords, n_joints=self.n_joints, emb_dim=self.embedding_dim, device=device,
+                         options=self.hip_options)
 
     # -------------------------------------------------------------- forward
     def forward(self, input_data: List[torch.Tensor], aggr_strategy: str = None, return_: str = None, *,
@@ -310,18 +331,9 @@ class MoCoDAD(_Base):
         cond_mask ('random_imp' only): (B,) bitmasks of the condition frames; default = drawn like the reference does
         (one torch.randperm per window on the default CPU generator, mocodad.py:719-724), or, with random_imp_draw='device',
         on the device from (seed, window_offset + b) -- the same sets however the windows are cut into batches or shards."""
-        tensor_data, meta_out = self._unpack_data(input_data)
-        aggr = self.aggregation_strategy if aggr_strategy is None else aggr_strategy
-        ret = return_ if return_ is not None else self.model_return_value
-        if ret is None:
-            raise ValueError("Either return_ or self.model_return_value must be set")
-        S, ns = self.n_generated_samples, self.noise_steps
-        sc = self.scorer()
+        tensor_data, meta_out, aggr, ret, sc, window_offset, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         pose_aggr = aggr in ("all", "random", "mean_pose", "median_pose")
         want_pose = ret in ("pose", "all") or pose_aggr
-        if window_offset is None:
-            window_offset = self._calls
-        self._calls += tensor_data.shape[0]
         if hasattr(tensor_data, "as_view") and pose_aggr and aggr in ("mean_pose", "median_pose"):
             tensor_data = tensor_data.materialize()      # the *_pose strategies compare against the windows themselves
         if self.conditioning_strategy == "random_imp" and cond_mask is None:
@@ -329,8 +341,7 @@ class MoCoDAD(_Base):
                 cond_mask = sc.random_imp_masks(tensor_data.shape[0], self.seed, window_offset)
             else:
                 cond_mask = self.draw_random_imp_mask(tensor_data.shape[0])
-        kw = dict(n_samples=S, noise_steps=ns, noise=noise, seed=self.seed, first_window_id=window_offset, loss_fn=self.loss_name,
-                  cond_mask=cond_mask)
+        kw["cond_mask"] = cond_mask
         fusable = aggr in ("best", "worst", "mean", "median") or "quantile" in aggr
         if fusable and not want_pose:
             # loss-only output: trajectories, condition encoder and the aggregation over the samples in ONE launch
@@ -340,6 +351,22 @@ class MoCoDAD(_Base):
             loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose, **kw)
             selected_x, loss = self._aggregate(sc, tensor_data, loss_all, poses_all, aggr, want_pose, cond_mask)
         return self._pack_out_data(selected_x, loss, [tensor_data] + meta_out, return_=ret)
+
+    def _begin_forward(self, input_data, aggr_strategy, return_, noise, window_offset):
+        """What every forward starts with -> (windows, [transformation_idx, metadata, actual_frames], aggregation, return mode,
+        scorer, global index of the first window, the scoring call's common keywords); counts the windows."""
+        tensor_data, meta_out = self._unpack_data(input_data)
+        aggr = self.aggregation_strategy if aggr_strategy is None else aggr_strategy
+        ret = return_ if return_ is not None else self.model_return_value
+        if ret is None:
+            raise ValueError("Either return_ or self.model_return_value must be set")
+        sc = self.scorer()
+        if window_offset is None:
+            window_offset = self._calls
+        self._calls += tensor_data.shape[0]
+        kw = dict(n_samples=self.n_generated_samples, noise_steps=self.noise_steps, noise=noise, seed=self.seed,
+                  first_window_id=window_offset, loss_fn=self.loss_name)
+        return tensor_data, meta_out, aggr, ret, sc, window_offset, kw
 
     def draw_random_imp_mask(self, n_windows: int) -> torch.Tensor:
         """'random_imp' frame sets exactly as _select_frames draws them (mocodad.py:719-724, 535): one randperm per
@@ -415,15 +442,13 @@ class MoCoDAD(_Base):
         # The test_step loop only ENQUEUES device work: when it returns the GPU still has most of the epoch's batches in front of
         # it.  The host-side first-use work of the post-processing -- reading the ground-truth masks, building the frame tables --
         # is done NOW, under that queue, before anything below waits for the scores (it used to be a constant ~0.1 s behind them).
-        import time as _time
-        _t = [_time.perf_counter()]
-        _tick = lambda: _t.append(_time.perf_counter())
+        lap = _Laps()
         if self.device.type == "cuda" and self.anomaly_score_frames_shift >= 1 and (self.shard is None or self.shard.rank == 0):
             try:
                 self._frame_assembler()
             except (OSError, ValueError, KeyError):
                 pass        # (no / unreadable ground truth: post_processing below reports it where it always did)
-        _tick()
+        lap()
         if self.shard is not None:
             # multi-GPU: every rank scored its contiguous window shard (possibly an empty one); ONE all-gather reassembles
             # the per-window scores, then rank 0 alone runs the post-processing and the AUC (the other ranks return nan)
@@ -439,17 +464,14 @@ class MoCoDAD(_Base):
             if not outs:
                 raise ValueError("no batches were scored")
             out, gt_data, trans, meta, frames = processing_data(outs)
-        _tick()
+        lap()
         self.last_scores = np.asarray(out)     # the (gathered) per-window scores of this epoch, in dataset order
         if self.save_tensors:
             self._save_tensors({"prediction": out, "gt_data": gt_data, "trans": trans, "metadata": meta, "frames": frames},
                                split_name=self.split, aggr_strategy=self.aggregation_strategy, n_gen=self.n_generated_samples)
         auc = self.post_processing(out, gt_data, trans, meta, frames)
-        _tick()
-        if os.environ.get("MCD_EPOCH_TIMING"):      # (diagnostic: where an epoch end's time goes)
-            import sys
-            print("epoch end: frame tables %.1f ms | collate / gather %.1f ms | post-processing + AUC %.1f ms" % tuple(
-                1e3 * (b - a) for a, b in zip(_t[:-1], _t[1:])), file=sys.stderr)
+        lap()
+        lap.report("epoch end: frame tables %.1f ms | collate / gather %.1f ms | post-processing + AUC %.1f ms")
         self.log("AUC", auc)
         return auc
 
@@ -484,16 +506,14 @@ class MoCoDAD(_Base):
         out / trans / meta / frames: NumPy arrays (the reference's signature) or tensors; gt_data is unused, as in the reference."""
         from sklearn.metrics import roc_auc_score
         if self.device.type == "cuda" and self.anomaly_score_frames_shift >= 1:
-            import time as _time
-            _a = _time.perf_counter()
+            lap = _Laps()
             asm = self._frame_assembler()
             pds = asm(out, trans, meta, frames)
-            _b = _time.perf_counter()
+            lap()
             if pds is not None:
                 auc = float(roc_auc_score(asm.gt, pds))
-                if os.environ.get("MCD_EPOCH_TIMING"):
-                    import sys
-                    print("post-processing: frame scores %.1f ms | roc_auc_score over %d frames %.1f ms" % (1e3 * (_b - _a), len(pds), 1e3 * (_time.perf_counter() - _b)), file=sys.stderr)
+                lap()
+                lap.report(f"post-processing: frame scores %.1f ms | roc_auc_score over {len(pds)} frames %.1f ms")
                 return auc
         gts, masks = self._gt_and_masks()
         _np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)

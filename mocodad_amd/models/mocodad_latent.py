@@ -78,19 +78,8 @@ class MoCoDADlatent(MoCoDAD):
         self.denoiser = DenoiserParams(self.latent_embedding_dim, self.hidden_sizes, self.embedding_dim)
         self.eval()
 
-    def scorer(self):
-        """Packed-weights handle (engine.LatentScorer) on the module's current device, rebuilt after load_state_dict."""
-        dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("MoCoDADlatent (mocodad_amd) scores on an MI355X only: move the module to a cuda device "
-                               "(there is no CPU fallback)")
-        key = str(dev)
-        if self._scorer is None or self._scorer_key != key:
-            self._scorer = self.build_scorer(dev)
-            self._scorer_key = key
-        return self._scorer
-
     def build_scorer(self, device):
+        """engine.LatentScorer with this module's weights (MoCoDAD.scorer() caches it per device)."""
         from ..engine import LatentScorer
         if self.conditioning_strategy != "inject":
             raise NotImplementedError("the latent model conditions by 'inject' only")
@@ -113,17 +102,7 @@ class MoCoDADlatent(MoCoDAD):
 
         noise (extension, keyword only): (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream -- slot 0 = the x_T of
         torch.randn (:109), slot k = the randn_like of step ns-k (:121), in call order.  window_offset keys the Philox stream."""
-        tensor_data, meta_out = self._unpack_data(input_data)
-        aggr = self.aggregation_strategy if aggr_strategy is None else aggr_strategy
-        ret = return_ if return_ is not None else self.model_return_value
-        if ret is None:
-            raise ValueError("Either return_ or self.model_return_value must be set")
-        S, ns = self.n_generated_samples, self.noise_steps
-        sc = self.scorer()
-        if window_offset is None:
-            window_offset = self._calls
-        self._calls += tensor_data.shape[0]
-        kw = dict(n_samples=S, noise_steps=ns, noise=noise, seed=self.seed, first_window_id=window_offset, loss_fn=self.loss_name)
+        tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         loss_based = aggr in ("mean", "median") or "quantile" in aggr
         if (loss_based or aggr in ("best", "worst")) and (ret == "loss" or loss_based):
             loss, _, _, _ = sc.score(tensor_data, aggregation=aggr, **kw)         # both launches; one loss per window comes back
