@@ -358,7 +358,10 @@ int mcd_frame_scores(const mcd_frame_cfg_t* cfg, const float* scores, const int6
  * takes it.  Two launches per scoring call for the shipped configuration: encode (condition encoder + the U-Net's down path +
  * to_time_dim) and chain (every denoiser pass, the DDPM updates, the loss and the aggregation).  Any other condition encoder
  * runs as a launch of its own in front of the encode launch: three launches, or four for a runtime channel list, whose kernel
- * reads gathered condition frames (gather, cond_encode_kernel, encode, chain); see mcd_pack_latent_weights. */
+ * reads gathered condition frames (gather, cond_encode_kernel, encode, chain); see mcd_pack_latent_weights.  At 5 .. 12 corrupt
+ * frames to_time_dim is a launch of its own between encode and chain (latent_project_kernel: one MFMA product over all windows
+ * instead of a pass over the matrix per workgroup): condition encoder, encode, project, chain -- four launches, five for a runtime
+ * channel list. */
 
 #define MCD_LATENT_MAX_LAYERS 8
 /* Denoiser of models/common/components.py:203-241 as MoCoDADlatent.build_model constructs it (mocodad_latent.py:51-57):
@@ -378,15 +381,18 @@ typedef struct mcd_latent_weights mcd_latent_weights_t;
  * denoiser.{net,cond_layers}.*.  BatchNorm2d / BatchNorm1d are folded into the preceding conv / Linear in double, the matrices
  * repacked into MFMA fragment order.  cfg: strategy MCD_STRATEGY_INJECT (mocodad_latent.py:32), t_unet = corrupt frames,
  * t_cond = condition frames.  Supported:
- *   t_unet       3 (the down path's LDS plan and to_time_dim are instantiated for it; another count is MCD_EUNSUPPORTED, naming
- *                "<t_unet> corrupt + <t_cond> condition frames")
+ *   t_unet       3 or 5 .. 12 (the rows of MCD_LATENT_ENCODE_INSTANCES: the down path's LDS plan is instantiated per count; another
+ *                count is MCD_EUNSUPPORTED, naming "<t_unet> corrupt + <t_cond> condition frames" and the counts the library holds)
  *   t_cond       1 .. 12
  *   cond_layers  a channel list of 1 .. MCD_MAX_COND_LAYERS entries (channels + [h_dim], 'AE' / 'E'), or MCD_COND_UNET ('E_unet')
  * The shipped configuration (cond_layers 4, channels 32,16,32,32, t_cond = t_unet = 3) runs its condition encoder inside the
  * encode launch.  Every other one is packed as mcd_pack_weights packs it and runs as the pose model's kernel, in a launch of
  * its own that writes cond_emb (B,16) into the workspace: cond_fast_kernel (the shipped channel list at another t_cond),
  * cond_unet_kernel ('E_unet'), or cond_encode_kernel behind a gather of the condition frames (any other channel list); the
- * encode launch then reads cond_emb instead of computing it.  A missing tensor is MCD_EMISSING with its name -- reported, like
+ * encode launch then reads cond_emb instead of computing it.  At t_unet 5 .. 12 the condition encoder is always a launch of
+ * its own (there is no fused form and MCD_LATENT_OPT_SPLIT_ENCODE changes nothing), the encode launch writes the last layer's
+ * output H (B, 640 t_unet) into the workspace, and to_time_dim.weight is packed with its columns in H's order as the MFMA
+ * fragments of the projection launch.  A missing tensor is MCD_EMISSING with its name -- reported, like
  * the refusals above, before the device is touched. */
 int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg,
                             const mcd_latent_cfg_t* latent_cfg, int32_t device, mcd_latent_weights_t** out);
@@ -395,7 +401,8 @@ void mcd_free_latent_weights(mcd_latent_weights_t* w);
 /* Bytes of device scratch mcd_latent_score needs for n_windows windows: cond_emb (B,16) and z0 (B,D) between its launches, plus
  * what the handle's condition-encoder kernel needs: nothing for the fused form, cond_fast_kernel and cond_unet_kernel; the
  * gathered condition frames (B,2,t_cond,17) for cond_encode_kernel, and its third activation buffer when three do not fit the
- * LDS.  A pure function of the handle and n_windows (MCD_LATENT_OPT_SPLIT_ENCODE does not change it). */
+ * LDS; at t_unet 5 .. 12 also H (B, 640 t_unet) between the encode and the projection launch (nothing at t_unet 3: the size of
+ * such a handle's workspace is what it was).  A pure function of the handle and n_windows (MCD_LATENT_OPT_SPLIT_ENCODE does not change it). */
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows);
 
 /* Test and diagnostic aid in the style of mcd_set_option.
@@ -411,8 +418,9 @@ int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value
 /* Replaces: _encode_condition + _unet_forward(corrupt_data, t = -1, condition_embedding) (mocodad_latent.py:98-104 ->
  * STSE_Unet.forward, stsae_unet.py:222-249).  cfg: n_windows, seg_len, noise_steps (locates the table's last row) and the frame
  * index lists; data / view as for mcd_score_view -> cond_emb_out (B,16), z0_out (B,D).  One launch for the shipped
- * configuration, two otherwise (three with the gather of a runtime channel list); such an encoder takes its gather buffer from the stream-ordered allocator
- * (hipMallocAsync / hipFreeAsync on `stream`) because this entry has no workspace argument. */
+ * configuration, two otherwise (three with the gather of a runtime channel list), one more at t_unet 5 .. 12 (the projection); the
+ * gather buffer of such an encoder and H of such a frame count come from the stream-ordered allocator (hipMallocAsync /
+ * hipFreeAsync on `stream`) because this entry has no workspace argument. */
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                       const float* step_table, float* cond_emb_out, float* z0_out, void* stream);
 

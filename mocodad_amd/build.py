@@ -1,6 +1,7 @@
 """Builds libmocodad_hip.so for gfx950 from mocodad_amd/csrc: mcd_api.hip (C ABI, routes, launches; with its headers mcd_pack.hpp, the
 weight packer, mcd_call.hpp, the front end of a scoring call, mcd_post_kernel.hpp, its own kernels, and mcd_generic_kernel.hpp, the
-runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels), compiled in parallel and linked with hipcc.
+runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels; once
+more per unit of its encode kernels), compiled in parallel and linked with hipcc.
 
     python -m mocodad_amd.build                       # the shipped library (mocodad_amd/libmocodad_hip.so)
     python -m mocodad_amd.build --profile             # + -DMCD_PROFILE -> libmocodad_hip_prof.so (tools/stage_profile.py)
@@ -34,6 +35,12 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibili
 def n_units() -> int:
     txt = open(os.path.join(CSRC, "mcd_instances.hpp")).read()
     return int(re.search(r"#define\s+MCD_INST_UNITS\s+(\d+)", txt).group(1))
+
+
+def n_latent_units() -> int:
+    """Units 1 .. n of mcd_latent.hip (encode kernels only; unit 0 is the file compiled as it is): the shipped value of MCD_LATENT_UNITS."""
+    txt = open(os.path.join(CSRC, "mcd_instances.hpp")).read()
+    return max(int(v) for v in re.findall(r"#define\s+MCD_LATENT_UNITS\s+(\d+)", txt))
 
 
 def unit_flags() -> dict:
@@ -131,6 +138,8 @@ def build_library(out: str = DEFAULT_OUT, defines: Iterable[str] = (), extra_fla
     uf = {} if fast else {u: usable_flags(f) for u, f in unit_flags().items()}      # (developer builds: command line / main())
     jobs_l += [(f"mcd_inst_{u}.o", os.path.join(CSRC, "mcd_inst.hip"), [f"-DMCD_INST_UNIT_{u}"] + uf.get(u, [])) for u in units]
     jobs_l += [("mcd_latent.o", os.path.join(CSRC, "mcd_latent.hip"), [])]      # the MoCoDADlatent kernels (developer builds too)
+    # ... and the encode kernels of MCD_LATENT_ENCODE_INSTANCES' units 1 .. n (a developer build holds its rows in unit 0)
+    jobs_l += [(f"mcd_latent_{u}.o", os.path.join(CSRC, "mcd_latent.hip"), [f"-DMCD_LATENT_UNIT={u}"]) for u in ([] if fast else range(1, n_latent_units() + 1))]
     todo = [(o, s, f) for o, s, f in jobs_l
             if force or not os.path.exists(os.path.join(obj_dir, o)) or os.path.getmtime(os.path.join(obj_dir, o)) < newest(s)]
     t0 = time.perf_counter()

@@ -64,17 +64,20 @@ PoseWorkspace pose_workspace(const mcd_weights* w, int64_t B, int64_t S) {
     L.bytes = L.scratch + std::max(unet_ws_bytes(w, B * S), cond_ws_bytes(w, B));
     return L;
 }
-// latent: [condition embeddings (B,16)][z0 (B,D)][gathered condition frames][third buffer of the plain encoder under gmode]; the
-// last two only where the plain encoder serves the handle.  cw: the handle's condition encoder (mcd_latent_weights::cw)
-struct LatentWorkspace { int64_t z0, gather, plain, bytes; };
-LatentWorkspace latent_workspace(const mcd_weights* cw, int64_t B, int D) {
+// latent: [condition embeddings (B,16)][z0 (B,D)][gathered condition frames][third buffer of the plain encoder under gmode][H]; the
+// gather and the third buffer only where the plain encoder serves the handle, H (B, h_floats: the last encoder layer's output,
+// 640 floats per corrupt frame) only where to_time_dim is a launch of its own (h_floats = 0 otherwise).  cw: the handle's condition
+// encoder (mcd_latent_weights::cw)
+struct LatentWorkspace { int64_t z0, gather, plain, h, bytes; };
+LatentWorkspace latent_workspace(const mcd_weights* cw, int64_t B, int D, int64_t h_floats) {
     const CondRoute r = cond_route(cw);
     const bool plain = r == COND_PLAIN || r == COND_PLAIN_SCRATCH;
     LatentWorkspace L;
     L.z0 = round256(B * EDIM * 4);
     L.gather = L.z0 + round256(B * D * 4);
     L.plain = L.gather + (plain ? round256(B * C0 * cw->cfg.t_cond * 17 * 4) : 0);
-    L.bytes = L.plain + (plain ? round256(cond_scratch_bytes(cw, COND_PLAIN_SCRATCH, B)) : 0);
+    L.h = L.plain + (plain ? round256(cond_scratch_bytes(cw, COND_PLAIN_SCRATCH, B)) : 0);
+    L.bytes = L.h + (h_floats ? round256(B * h_floats * 4) : 0);
     return L;
 }
 

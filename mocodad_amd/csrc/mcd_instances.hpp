@@ -99,9 +99,24 @@
 #endif  // MCD_FAST_T
 
 // The encode launch of the latent model (mcd_latent.hip, built in shipped and developer libraries alike):
-//   X(T, NB, COND_IN_KERNEL)     latent_encode_kernel<T, NB, COND_IN_KERNEL>: T corrupt frames; true = the shipped condition encoder at
-//                                T condition frames inside the launch, false = cond_emb from a condition-encoder launch of the rows above
-#define MCD_LATENT_ENCODE_INSTANCES(X) X(3, 2, true) X(3, 2, false)
+//   X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL)   latent_encode_kernel<T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL>: T corrupt frames
+//       COND_IN_KERNEL     true = the shipped condition encoder at T condition frames inside the launch, false = cond_emb from a
+//                          condition-encoder launch of the rows above
+//       PROJECT_IN_KERNEL  true = to_time_dim as the kernel's tail; false = the kernel writes the last layer's output H (B, 640 T)
+//                          and latent_project_kernel (one MFMA launch for all windows) computes z0 from it
+//       unit               0 = mcd_latent.hip as it is compiled for the chain, projection and Philox kernels; n = 1 .. MCD_LATENT_UNITS:
+//                          the same file compiled once more with -DMCD_LATENT_UNIT=n (mocodad_amd/build.py does), holding only the
+//                          encode kernels of its rows.  The assignment only balances compile times.
+// A developer build (MCD_FAST_T) keeps the 3-frame rows and the row of MCD_FAST_T if there is one, all in unit 0.
+#define MCD_LATENT_ENCODE_INSTANCES(X) \
+    X(0, 3, 2, true, true) X(0, 3, 2, false, true) \
+    X(1, 5, 1, false, false) X(1, 12, 1, false, false) X(2, 6, 1, false, false) X(2, 11, 1, false, false) \
+    X(3, 7, 1, false, false) X(3, 10, 1, false, false) X(4, 8, 1, false, false) X(4, 9, 1, false, false)
+#ifndef MCD_FAST_T
+#define MCD_LATENT_UNITS 4
+#else
+#define MCD_LATENT_UNITS 0
+#endif
 
 // What the tables hold, for the packer and the dispatch of mcd_api.hip (a frame count outside them takes the next more general
 // kernel: slab-tiled, then runtime-shape).

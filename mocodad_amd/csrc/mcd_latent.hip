@@ -1,39 +1,113 @@
 // mcd_latent.hip — the translation unit of the MoCoDADlatent kernels (mcd_latent_kernel.hpp) and their launchers; built with
-// the default eight waves per workgroup (the chain kernel has its own four).
+// the default eight waves per workgroup (the chain kernel has its own four).  Compiled once as it is (unit 0: the dispatch, the
+// chain, projection and Philox kernels, the encode kernels of the rows of unit 0) and once per unit n = 1 .. MCD_LATENT_UNITS
+// with -DMCD_LATENT_UNIT=n (the encode kernels of that unit's rows only); see MCD_LATENT_ENCODE_INSTANCES in mcd_instances.hpp.
 #undef MCD_NWAVES      // (a developer build may name another wave count for its trajectory kernel)
+#ifndef MCD_LATENT_UNIT
+#define MCD_LATENT_UNIT 0
+#endif
+#if MCD_LATENT_UNIT != 0
+#define MCD_LATENT_ENCODE_ONLY
+#endif
 #include "mcd_launch.hpp"
 #include "mcd_latent_kernel.hpp"
 
 namespace mcd {
 
-// MCD_LATENT_ENCODE_INSTANCES (mcd_instances.hpp): X(T, NB, COND_IN_KERNEL) -- T corrupt frames; the fused form also T condition frames
+static_assert(MCD_LATENT_UNIT >= 0 && MCD_LATENT_UNIT <= MCD_LATENT_UNITS, "compile with -DMCD_LATENT_UNIT=<n>, n = 1 .. MCD_LATENT_UNITS, or without");
+
+// MCD_LATENT_ENCODE_INSTANCES (mcd_instances.hpp): X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL).  A developer build holds the
+// 3-frame rows and the row of its frame count, in unit 0.
+#ifdef MCD_FAST_T
+constexpr bool latent_row_held(int t) { return t == 3 || t == MCD_FAST_T; }
+constexpr int latent_row_unit(int) { return 0; }
+#else
+constexpr bool latent_row_held(int) { return true; }
+constexpr int latent_row_unit(int unit) { return unit; }
+#endif
+
+struct LatentEncodeArgs {
+    const float* wbuf; const DataView& dv; const FrameIdx& cond_fi; const FrameIdx& fi; int seg_len; const float* pe_row;
+    float* cond_out; float* out; int D, B; hipStream_t st;
+};
+
+template <int T, int NB, bool CI, bool PIK>
+static int launch_latent_encode_t(const LatentEncodeArgs& a) {
+    static_assert(NWAVES == 8, "the latent encode launch ships with eight waves per workgroup");
+    static_assert(PIK || !CI, "the rows that project in a launch of their own take cond_emb from a launch of its own as well");
+    constexpr size_t lds = (size_t)LatentEncLds<T, NB, PIK>::FLOATS * 4;
+    static_assert(lds <= 160 * 1024, "latent encode: more than 160 KB of LDS");
+    LDS_LIMIT((&latent_encode_kernel<T, NB, CI, PIK>), lds);
+    hipLaunchKernelGGL((latent_encode_kernel<T, NB, CI, PIK>), dim3((a.B + NB - 1) / NB), dim3(NTHREADS), lds, a.st, a.wbuf, a.dv, a.cond_fi, a.fi,
+                       a.seg_len, a.pe_row, a.cond_out, a.out, a.D, a.B);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+// a row's launcher in the unit that holds the row; elsewhere nothing of it is instantiated
+template <bool HERE, int T, int NB, bool CI, bool PIK>
+struct LatentRow {
+    static int go(const LatentEncodeArgs& a) { return launch_latent_encode_t<T, NB, CI, PIK>(a); }
+};
+template <int T, int NB, bool CI, bool PIK>
+struct LatentRow<false, T, NB, CI, PIK> {
+    static int go(const LatentEncodeArgs&) { return fail(MCD_EUNSUPPORTED, "latent encode: the row is not part of this unit"); }
+};
+
+// the dispatch over the rows of unit U: defined by the translation unit compiled as that unit
+template <int U>
+int launch_latent_encode_unit(int t, bool cond_in_kernel, const LatentEncodeArgs& a);
+#define MCD_ROW(unit, T, NB, CI, PIK) template <> int launch_latent_encode_unit<latent_row_unit(unit)>(int, bool, const LatentEncodeArgs&);
+MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+
+template <>
+int launch_latent_encode_unit<MCD_LATENT_UNIT>(int t, bool cond_in_kernel, const LatentEncodeArgs& a) {
+#define MCD_ROW(unit, T, NB, CI, PIK) \
+    if (t == (T) && cond_in_kernel == (CI)) return LatentRow<latent_row_held(T) && latent_row_unit(unit) == MCD_LATENT_UNIT, T, NB, CI, PIK>::go(a);
+    MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+    return fail(MCD_EUNSUPPORTED, "latent encode: no such row");
+}
+
+#if MCD_LATENT_UNIT == 0
+
 bool latent_encode_has_kernel(int t, bool cond_in_kernel) {
-#define MCD_ROW(T, NB, CI) if (t == (T) && cond_in_kernel == (CI)) return true;
+#define MCD_ROW(unit, T, NB, CI, PIK) if (latent_row_held(T) && t == (T) && cond_in_kernel == (CI)) return true;
     MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
 #undef MCD_ROW
     return false;
 }
 
-template <int T, int NB, bool CI>
-static int launch_latent_encode_t(const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi, int seg_len,
-                                  const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st) {
-    static_assert(NWAVES == 8, "the latent encode launch ships with eight waves per workgroup");
-    constexpr size_t lds = (size_t)LatentEncLds<T, NB>::FLOATS * 4;
-    static_assert(lds <= 160 * 1024, "latent encode: more than 160 KB of LDS");
-    LDS_LIMIT((&latent_encode_kernel<T, NB, CI>), lds);
-    hipLaunchKernelGGL((latent_encode_kernel<T, NB, CI>), dim3((B + NB - 1) / NB), dim3(NTHREADS), lds, st, wbuf, dv, cond_fi, fi, seg_len,
-                       pe_row, cond_out, z0_out, D, B);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+bool latent_project_in_kernel(int t) {
+#define MCD_ROW(unit, T, NB, CI, PIK) if (latent_row_held(T) && t == (T) && !(CI)) return PIK;
+    MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+    return true;
+}
+
+std::string latent_encode_counts() {
+    std::string s;
+    for (int t = 1; t <= MCD_MAX_FRAMES; ++t)
+        if (latent_encode_has_kernel(t, false)) s += (s.empty() ? "" : ", ") + std::to_string(t);
+    return s;
 }
 
 int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
-                         int seg_len, const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st) {
-#define MCD_ROW(T, NB, CI) \
-    if (t == (T) && cond_in_kernel == (CI)) return launch_latent_encode_t<T, NB, CI>(wbuf, dv, cond_fi, fi, seg_len, pe_row, cond_out, z0_out, D, B, st);
+                         int seg_len, const float* pe_row, float* cond_out, float* out, int D, int B, hipStream_t st) {
+    const LatentEncodeArgs a{wbuf, dv, cond_fi, fi, seg_len, pe_row, cond_out, out, D, B, st};
+#define MCD_ROW(unit, T, NB, CI, PIK) \
+    if (latent_row_held(T) && t == (T) && cond_in_kernel == (CI)) return launch_latent_encode_unit<latent_row_unit(unit)>(t, cond_in_kernel, a);
     MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
 #undef MCD_ROW
-    return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(t) + " frames (instantiated: 3 corrupt frames)");
+    return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(t) + " frames (instantiated: " + latent_encode_counts() + " corrupt frames)");
+}
+
+int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_out, int D, int B, hipStream_t st) {
+    hipLaunchKernelGGL(latent_project_kernel, dim3((B + PROJ_NC - 1) / PROJ_NC, D / 16), dim3(PROJ_THREADS), 0, st, wbuf, H, z0_out,
+                       LAT_ENC_C * t * 10 / 16, D, B);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
 }
 
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st) {
@@ -52,5 +126,7 @@ int launch_latent_philox(unsigned long long seed, long long first_window, int B,
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
+
+#endif  // MCD_LATENT_UNIT == 0
 
 }  // namespace mcd

@@ -55,10 +55,17 @@ __host__ __device__ inline int latent_chain_lds_floats(int D, int chains_per_wg)
 constexpr int TAB_LAT_LW = 100, TAB_LAT_LB = 101;
 
 // launchers (mcd_latent.hip holds the kernels; mcd_api.hip only calls these)
-// cond_in_kernel: the fused form (shipped condition encoder inside the launch); false: cond_out already holds cond_emb (B,16)
+// The rows of MCD_LATENT_ENCODE_INSTANCES this library holds: is there an encode kernel for t corrupt frames (cond_in_kernel: the
+// fused form, the shipped condition encoder inside the launch); does its row compute z0 itself (false: it writes H and
+// latent_project_kernel follows); the corrupt-frame counts of the rows, for messages ("3, 5, 6")
 bool latent_encode_has_kernel(int t, bool cond_in_kernel);
+bool latent_project_in_kernel(int t);
+std::string latent_encode_counts();
+// cond_in_kernel = false: cond_out already holds cond_emb (B,16).  out: z0 (B,D), or H (B, 640 t) for a row that does not project
 int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
-                         int seg_len, const float* pe_row, float* cond_out, float* z0_out, int D, int B, hipStream_t st);
+                         int seg_len, const float* pe_row, float* cond_out, float* out, int D, int B, hipStream_t st);
+// H (B, 640 t) -> z0 (B,D): to_time_dim of the rows with PROJECT_IN_KERNEL = false
+int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_out, int D, int B, hipStream_t st);
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
 int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
 

@@ -12,6 +12,8 @@ struct mcd_latent_weights {
     size_t n_floats;
     mcd::LatentNet net;
     bool fused_ok;        // cond_fast_body's table is packed and t_cond = t_unet: the encode launch can run the condition encoder itself
+    int h_floats;         // per window: the last encoder layer's output H that the encode launch leaves for latent_project_kernel; 0 = the
+                          // encode launch computes z0 itself (3 corrupt frames)
     mcd_weights cw;       // the condition encoder as the pose model's launchers take it: dbuf, cond and the cond_* flags; nothing else is set
     int opt[MCD_LATENT_OPT_COUNT];
 };
@@ -22,9 +24,9 @@ using namespace mcd;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// gather / plain: the two scratch regions of latent_workspace() (null where the handle's route has none)
+// gather / plain / hbuf: the scratch regions of latent_workspace() (null where the handle's route has none)
 int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
-                       const float* step_table, float* cond_out, float* z0_out, float* gather, float* plain, hipStream_t st) {
+                       const float* step_table, float* cond_out, float* z0_out, float* gather, float* plain, float* hbuf, hipStream_t st) {
     DataView dv;
     if (int rc = window_view(data, view, cfg->seg_len, dv)) return rc;
     if (cfg->n_corrupt != w->cfg.t_unet || cfg->n_cond != w->cfg.t_cond) return fail(MCD_EINVAL, "frame split does not match the packed model (t_unet / t_cond)");
@@ -46,8 +48,13 @@ int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, 
     if (plain_route && !gather) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
     if (route != COND_INKERNEL)
         if (int rc = launch_cond(&w->cw, route, dv, cond_fi, cfg->seg_len, cond_out, B, gather, plain, st)) return rc;
-    return launch_latent_encode(w->cfg.t_unet, route == COND_INKERNEL, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
-                                B, st);
+    if (!w->h_floats)
+        return launch_latent_encode(w->cfg.t_unet, route == COND_INKERNEL, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
+                                    B, st);
+    // 5 .. 12 corrupt frames: the encode launch leaves H, one projection launch computes every window's z0
+    if (!hbuf) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this frame count");
+    if (int rc = launch_latent_encode(w->cfg.t_unet, false, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, hbuf, w->net.D, B, st)) return rc;
+    return launch_latent_project(w->cfg.t_unet, w->dbuf, hbuf, z0_out, w->net.D, B, st);
 }
 
 }  // namespace
@@ -67,6 +74,7 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
     w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
     memset(w->opt, 0, sizeof(w->opt));
     w->fused_ok = m.fused_ok != 0;
+    w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
     w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
     memset(w->cw.opt, 0, sizeof(w->cw.opt));
     set_cond_weights(&w->cw, m, dbuf);
@@ -89,7 +97,7 @@ void mcd_free_latent_weights(mcd_latent_weights_t* w) {
 
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows) {
     if (!w || n_windows <= 0) return 0;
-    return latent_workspace(&w->cw, n_windows, w->net.D).bytes;
+    return latent_workspace(&w->cw, n_windows, w->net.D, w->h_floats).bytes;
 }
 
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
@@ -99,13 +107,14 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     if (!data || !step_table || !cond_emb_out || !z0_out) return fail(MCD_EINVAL, "null argument");
     if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
     hipStream_t st = (hipStream_t)stream;
-    // no workspace argument here: the plain encoder's scratch comes from the stream-ordered allocator
-    const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D);
+    // no workspace argument here: the plain encoder's scratch and H come from the stream-ordered allocator
+    const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D, w->h_floats);
     const int64_t need = lay.bytes - lay.gather;
     char* scratch = nullptr;
     if (need > 0) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)need, st));
     const int rc = latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, reinterpret_cast<float*>(scratch),
-                                      scratch ? reinterpret_cast<float*>(scratch + (lay.plain - lay.gather)) : nullptr, st);
+                                      scratch ? reinterpret_cast<float*>(scratch + (lay.plain - lay.gather)) : nullptr,
+                                      scratch ? reinterpret_cast<float*>(scratch + (lay.h - lay.gather)) : nullptr, st);
     if (scratch) {
         const hipError_t e = hipFreeAsync(scratch, st);
         if (rc == MCD_OK && e != hipSuccess) return fail(MCD_EDEVICE, std::string("hipFreeAsync: ") + hipGetErrorString(e));
@@ -148,12 +157,12 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
     if (noise && !aligned16(noise)) return fail(MCD_EINVAL, "noise must be 16-byte aligned");
     if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const LatentWorkspace lay = latent_workspace(&w->cw, B, D);
+    const LatentWorkspace lay = latent_workspace(&w->cw, B, D, w->h_floats);
     char* wsb = reinterpret_cast<char*>(workspace);
     float* cond = reinterpret_cast<float*>(wsb);
     float* z0 = reinterpret_cast<float*>(wsb + lay.z0);
     if (int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, reinterpret_cast<float*>(wsb + lay.gather),
-                                    reinterpret_cast<float*>(wsb + lay.plain), st)) return rc;
+                                    reinterpret_cast<float*>(wsb + lay.plain), reinterpret_cast<float*>(wsb + lay.h), st)) return rc;
     LatentChainParams P;
     memset(&P, 0, sizeof(P));
     P.wbuf = w->dbuf; P.net = w->net; P.cond = cond; P.z0 = z0; P.noise = noise; P.step_table = step_table;

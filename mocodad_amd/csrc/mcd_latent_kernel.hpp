@@ -5,6 +5,8 @@
 //                                 v_mfma_f32_16x16x4_f32 products with the chains as the N dimension, the DDPM updates, the loss
 //                                 against z0 and the loss-based aggregation over the samples
 //   latent_philox_kernel          the perf mode's draws in the parity layout
+//   latent_project_kernel         to_time_dim for all windows of a call as MFMA products (5 .. 12 corrupt frames, whose encode launch
+//                                 stops at the last layer's output)
 // The stage functions, the LDS plan and the fragment orders are those of mcd_device.hpp / mcd_score_kernel.hpp, included unchanged.
 #pragma once
 #include "mcd_device.hpp"
@@ -13,6 +15,7 @@
 
 namespace mcd {
 
+#ifndef MCD_LATENT_ENCODE_ONLY      // (a unit that holds encode kernels only: see MCD_LATENT_ENCODE_INSTANCES)
 __device__ __forceinline__ f32x4 lat_mfma4(const float4 a, const float4 b, f32x4 acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
@@ -207,6 +210,53 @@ __global__ __launch_bounds__(256) void latent_philox_kernel(unsigned long long s
     store_global4(out + (((size_t)(s * K + k) * B + b) * D + grp * 4), make_float4(z[0], z[1], z[2], z[3]));
 }
 
+// to_time_dim of the rows that project in a launch of their own: z0[b][j] = bias[j] + sum_k W'[j][k] H[b][k] with H (B, K = 640 T)
+// as the encode launch left it (k = (t 10 + v) 64 + c) and W' = to_time_dim.weight with its columns in that order, in
+// pack_gemm_frags order (M = D, K).  Workgroup (x, y): windows 32 x .. 32 x + 31 as two n-tiles, m-tile y of the D / 16.  Wave w
+// accumulates the 16-wide k-groups w, w + 8, ...; the eight partial tiles are summed through LDS in wave order, so a window's z0
+// is one fixed sequence of operations on its own column: columns of an MFMA never mix, and the columns past the batch hold zeros.
+// Every workgroup streams W' once per 32 windows (the in-kernel tail of the 3-frame rows: once per workgroup of NB windows).
+constexpr int PROJ_WAVES = 8, PROJ_THREADS = PROJ_WAVES * 64, PROJ_NC = 32;
+__global__ __launch_bounds__(PROJ_THREADS) void latent_project_kernel(const float* __restrict__ wbuf, const float* __restrict__ H,
+                                                                      float* __restrict__ z0_out, int KQ, int D, int B) {
+    __shared__ __attribute__((aligned(16))) float RED[PROJ_WAVES * 2 * 64 * 4];
+    const int tid = threadIdx.x, lane = tid & 63, n16 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mt = blockIdx.y, b_first = blockIdx.x * PROJ_NC;
+    const size_t K = (size_t)KQ * 16;
+    const int bA = b_first + n16, bB = bA + 16;
+    // (a column past the batch reads the last window's row, inside H, and is replaced by zeros)
+    const float* hA = H + (size_t)(bA < B ? bA : B - 1) * K + 4 * g;
+    const float* hB = H + (size_t)(bB < B ? bB : B - 1) * K + 4 * g;
+    const float* wp = wbuf + tab_i(wbuf, TAB_LAT_LW) + ((size_t)mt * KQ * 64 + lane) * 4;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int kq = wave; kq < KQ; kq += PROJ_WAVES) {
+        const float4 a = load_global4(wp + (size_t)kq * 256);
+        float4 xA = load_global4(hA + kq * 16), xB = load_global4(hB + kq * 16);
+        if (bA >= B) xA = zero;
+        if (bB >= B) xB = zero;
+        accA = lat_mfma4(a, xA, accA);
+        accB = lat_mfma4(a, xB, accB);
+    }
+    lds_store4(lds_addr(RED + ((wave * 2 + 0) * 64 + lane) * 4), accA[0], accA[1], accA[2], accA[3]);
+    lds_store4(lds_addr(RED + ((wave * 2 + 1) * 64 + lane) * 4), accB[0], accB[1], accB[2], accB[3]);
+    __syncthreads();
+    if (tid < 2 * 64) {      // thread = (n-tile, lane): the lane's four output rows of one window
+        const int nt = tid >> 6, c0 = mt * 16 + 4 * g, b = b_first + nt * 16 + n16;
+        float4 s = lds_load4(lds_addr(RED + (nt * 64 + lane) * 4));
+#pragma unroll
+        for (int w = 1; w < PROJ_WAVES; ++w) {
+            const float4 v = lds_load4(lds_addr(RED + ((w * 2 + nt) * 64 + lane) * 4));
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        const float4 bb = load_global4(wbuf + tab_i(wbuf, TAB_LAT_LB) + c0);
+        if (b < B) store_global4(z0_out + (size_t)b * D + c0, make_float4(s.x + bb.x, s.y + bb.y, s.z + bb.z, s.w + bb.w));
+    }
+}
+#endif  // MCD_LATENT_ENCODE_ONLY
+
 // ------------------------------------------------------------------------------------------------
 // Encode launch: windows b0 .. b0 + NB - 1 of a workgroup.  cond_fast_body (the shipped condition encoder) -> cond_emb; the
 // embeddings Linear(SiLU(pos_encoding(-1) + cond_emb)) of the seven down-path layers; the layers on Plan<T, NB> as in
@@ -216,12 +266,14 @@ __global__ __launch_bounds__(256) void latent_philox_kernel(unsigned long long s
 // encoder's table at TABC as cond_fast_body expects it.
 // ------------------------------------------------------------------------------------------------
 
-template <int T, int NB>
+// PROJECT_IN_KERNEL = false: the last layer runs as two halves of 32 output channels, each [P10][36] at H_OFF and copied to global
+// memory before the next (12 frames: 332 P10 floats for the whole output would be 168 KB)
+template <int T, int NB, bool PROJECT_IN_KERNEL = true>
 struct LatentEncLds {
     using PL = Plan<T, NB>;
     static constexpr int P17 = ceil16(NB * T * 17);
     static constexpr int H_OFF = 2 * PL::s128;                   // [P10][68] output of the last layer behind its (in, z)
-    static constexpr int WORK = cmax(cmax(PL::R, H_OFF + PL::P10 * 68), P17 * (2 * 20 + 2 * 36));
+    static constexpr int WORK = cmax(cmax(PL::R, H_OFF + PL::P10 * (PROJECT_IN_KERNEL ? 68 : 36)), P17 * (2 * 20 + 2 * 36));
     static constexpr int EMB = NB * EMB_STRIDE;
     static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
 };
@@ -229,12 +281,14 @@ struct LatentEncLds {
 // COND_IN_KERNEL = false (the three-launch form: any other condition encoder, 1 .. 12 condition frames): a condition-encoder
 // kernel of the pose model (cond_fast_kernel / cond_unet_kernel / cond_encode_kernel) has written cond_emb (B,16) to cond_out in a
 // launch of its own; the prologue is skipped, CE is read from there and the remainder is the same code.
-template <int T, int NB, bool COND_IN_KERNEL = true>
+// PROJECT_IN_KERNEL = false (5 .. 12 corrupt frames): no to_time_dim tail; z0_out is H (B, 640 T), the last layer's output of window b
+// at H[b][(t 10 + v) 64 + c] -- the order the LDS holds, so the copy is 16-byte stores -- for latent_project_kernel.
+template <int T, int NB, bool COND_IN_KERNEL = true, bool PROJECT_IN_KERNEL = true>
 __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
                                                                     const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
                                                                     float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
     using PL = Plan<T, NB>;
-    using LD = LatentEncLds<T, NB>;
+    using LD = LatentEncLds<T, NB, PROJECT_IN_KERNEL>;
     constexpr int TV17 = T * 17, COLS17 = NB * TV17, TV10 = T * 10;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const RG = smem;
@@ -308,9 +362,29 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float*
         __syncthreads();
     }
     layer_generic<64, 128, 10, true, true, T, NB>(wb, layer_w(wb, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, EMB + emb_off(5), wave, lane, prof, 0);
+    constexpr int F = LAT_ENC_C * TV10;
+    if constexpr (!PROJECT_IN_KERNEL) {
+        // the last layer as two halves of 32 output channels: m-tiles 2 h, 2 h + 1 of its fragments are one contiguous block, so a
+        // half is the same layer with its weight, bias and embedding pointers moved on.  (The mix runs again for the second half;
+        // the copy of a half has finished in every thread before the next half's GEMM writes: the mix's barrier lies between.)
+        const LayerW l6 = layer_w(wb, 6);
+        const float* HL = RG + LD::H_OFF;
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            LayerW lh = l6;
+            lh.wp += h * 2 * (2 * 128 / 16) * 256;
+            lh.bias += h * 32;
+            layer_generic<128, 32, 10, true, true, T, NB>(wb, lh, RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6) + h * 32, wave, lane, prof, 0);
+            for (int u = tid; u < NB * TV10 * 8; u += NTHREADS) {
+                const int col = u >> 3, q = u & 7, n = col / TV10;
+                if (b0 + n < B)
+                    store_global4(z0_out + (size_t)(b0 + n) * F + (col - n * TV10) * LAT_ENC_C + h * 32 + 4 * q, lds_load4(lds_addr(HL + col * 36 + 4 * q)));
+            }
+        }
+        return;
+    }
     layer_generic<128, 64, 10, true, true, T, NB>(wb, layer_w(wb, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6), wave, lane, prof, 0);
     // to_time_dim: z0[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v.  thread = (j, part of 16), every window of the workgroup
-    constexpr int F = LAT_ENC_C * TV10;
     const float* H = RG + LD::H_OFF;
     gfloat* W = as_global(wb + tab_i(wb, TAB_LAT_LW));
     gfloat* bb = as_global(wb + tab_i(wb, TAB_LAT_LB));

@@ -472,7 +472,7 @@ int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_
         return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
     if (!latent_encode_has_kernel(T, false) || cfg->t_cond > 12)
         return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
-                                      " condition frames (instantiated: 3 corrupt frames with 1 .. 12 condition frames)");
+                                      " condition frames (instantiated: " + latent_encode_counts() + " corrupt frames with 1 .. 12 condition frames)");
     if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
         return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
     if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
@@ -512,7 +512,14 @@ int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_
         const float* lw = tm.get("model.to_time_dim.weight", F * D);
         const float* lb = tm.get("model.to_time_dim.bias", D);
         if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        tab[TAB_LAT_LW] = emit_copy(B, lw, F * D);
+        if (latent_project_in_kernel(T)) {
+            tab[TAB_LAT_LW] = emit_copy(B, lw, F * D);
+        } else {
+            // latent_project_kernel: A fragments of W' [D][K], column k' = (t 10 + v) 64 + c of W' = column c T 10 + (t 10 + v) of the
+            // weight -- the order in which the encode launch leaves H
+            const int TV = T * 10;
+            tab[TAB_LAT_LW] = pack_gemm_frags(B, D, (int)F, [&](int r, int k) -> double { return lw[(size_t)r * F + (size_t)(k % LAT_ENC_C) * TV + k / LAT_ENC_C]; });
+        }
         tab[TAB_LAT_LB] = emit_copy(B, lb, D);
     }
     // ---- the condition encoder, packed as the pose model's (the AE decoder is dead work at evaluation and is not read).  The fused

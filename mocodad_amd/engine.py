@@ -431,7 +431,10 @@ class LatentScorer(_Scorer):
     state_dict: the reference's keys ('model.*' without an up path, 'condition_encoder.*', 'denoiser.*').
     cond_channels: output channels of the 'AE' / 'E' condition encoder's layers; cond_unet: the 'E_unet' encoder instead.
     latent_dim / hidden_sizes: latent_embedding_dim and the denoiser's layer widths (the last equals latent_dim).
-    3 corrupt frames, 1 .. 12 condition frames (mcd_pack_latent_weights)."""
+    3 or 5 .. 12 corrupt frames, 1 .. 12 condition frames (mcd_pack_latent_weights).  At 5 .. 12 corrupt frames a scoring call is
+    four launches -- condition encoder, encode, the projection onto the latent (to_time_dim over all windows), chain -- and the
+    workspace also holds the encoder's last activation (n_windows x 640 x corrupt frames floats); `encode`, `score` and the
+    workspace size are used the same way."""
 
     _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
     _step_table = staticmethod(latent_step_table)

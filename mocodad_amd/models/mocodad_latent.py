@@ -7,6 +7,8 @@ reverse-diffusion chain over the latent (the conditioned MLP denoiser, the DDPM 
 run in the HIP launches behind mcd_latent_score (mocodad_amd.engine.LatentScorer): two for the shipped configuration, three
 (the condition encoder as its own launch) for `E_unet` or another number of condition frames, four (a gather of the condition
 frames in front) for another channel list / h_dim.
+3 or 5 .. 12 corrupt frames (e.g. seg_len 12 or 24 split in halves); at 5 .. 12 the condition encoder is always its own launch and
+to_time_dim is one more launch between the encoder and the chain.
 
 Reference: models/mocodad_latent.py (forward :69-132), models/common/components.py:203-291 (Denoiser),
 models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` and training are outside the accelerated path.

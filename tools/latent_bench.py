@@ -5,11 +5,13 @@
     python tools/latent_bench.py --cond-arch E_unet            # the three-launch form: cond_unet_kernel + encode + chain
     python tools/latent_bench.py --cond-frames 12              # ... cond_fast_kernel<12,1> + encode + chain (seg_len 15)
     python tools/latent_bench.py --split-encode                # the shipped configuration through the three-launch form
+    python tools/latent_bench.py --corrupt-frames 12 --cond-frames 12     # seg_len 24: cond_fast_kernel + encode + projection + chain
+                                                               # (default output: profiles/latent_bench_tx12.json)
 
 Shipped configuration (configs/ubnormal_latent_test.yaml: D 64, hidden [64,128,128,64], noise_steps 10, 10 samples), seeded
 random-init weights, perf mode (in-kernel Philox), batch 1024 and a batch that fills the device.  Per batch, three legs alternate
 inside one timed loop, each bracketed by device events:
-  encode        mcd_latent_encode
+  encode        mcd_latent_encode (5 .. 12 corrupt frames: condition encoder + encode + projection launches)
   score         mcd_latent_score (encode + chain; the chain launch's time is score - encode: the two run back to back on one stream)
   pose_onepass  the yardstick of the encode launch: the pose model's one-pass scoring call (score_fused, noise_steps 2, 1 sample,
                 same windows) -- the condition encoder and all 11 U-Net layers, against 7 here
@@ -95,13 +97,15 @@ def timed(legs, reps, warmup):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "latent_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/latent_bench.json, profiles/latent_bench_tx<N>.json with --corrupt-frames N")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--fill-batch", type=int, default=12288)
     ap.add_argument("--clock-ghz", type=float, default=2.4)
     ap.add_argument("--cond-arch", choices=["AE", "E", "E_unet"], default=None, help="conditioning_architecture (default: the YAML's 'AE')")
-    ap.add_argument("--cond-frames", type=int, default=3, help="condition frames, 1 .. 12 (seg_len = this + 3 corrupt frames)")
+    ap.add_argument("--cond-frames", type=int, default=3, help="condition frames, 1 .. 12 (seg_len = this + the corrupt frames)")
+    ap.add_argument("--corrupt-frames", type=int, default=3, help="corrupt frames: 3 or 5 .. 12")
+    ap.add_argument("--batches", type=int, nargs="+", default=None, help="window counts to time (default: 1024 and --fill-batch)")
     ap.add_argument("--split-encode", action="store_true", help="MCD_LATENT_OPT_SPLIT_ENCODE: the shipped configuration in three launches")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU restatement of the chain")
     a = ap.parse_args()
@@ -110,17 +114,20 @@ def main():
     import latent_ref as R
     dev = torch.device("cuda:0")
     cfg = load_config(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml"))
-    Tc = int(a.cond_frames)
+    Tc, Tx = int(a.cond_frames), int(a.corrupt_frames)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "latent_bench.json" if Tx == 3 else f"latent_bench_tx{Tx}.json")
     if a.cond_arch:
         cfg.conditioning_architecture = a.cond_arch
-    if Tc != 3:
-        cfg.seg_len, cfg.conditioning_indices = Tc + 3, list(range(Tc))
+    if Tc != 3 or Tx != 3:
+        cfg.seg_len, cfg.conditioning_indices = Tc + Tx, list(range(Tc))
     unet = cfg.conditioning_architecture == "E_unet"
     torch.manual_seed(0)
     lat = MoCoDADlatent(cfg).to(dev)
     if a.split_encode:
         lat.scorer().set_option("split_encode", 1)
-    launches = 2 if (not unet and Tc == 3 and not a.split_encode) else 3
+    # 3 corrupt frames: the fused form, or the condition encoder in front; 5 .. 12: condition encoder, encode, projection, chain
+    launches = 4 if Tx != 3 else 2 if (not unet and Tc == 3 and not a.split_encode) else 3
     pose = MoCoDAD(load_config(os.path.join(ROOT, "configs", "hr_avenue_test.yaml"))).to(dev)
     sl, sp = lat.scorer(), pose.scorer()
     D, hidden, ns, S, T = lat.latent_embedding_dim, lat.hidden_sizes, lat.noise_steps, lat.n_generated_samples, lat.n_frames_corrupt
@@ -132,12 +139,12 @@ def main():
     res = {"config": {"latent_dim": D, "hidden_sizes": hidden, "noise_steps": ns, "n_samples": S, "frames": [T, Tc],
                       "cond_arch": cfg.conditioning_architecture, "launches_per_score": launches},
            "flops_per_window": {"down_path": down_f, "to_time_dim": ttd_f, "condition_encoder": cond_f, "denoiser_per_chain_step": step_f,
-                                "chain": chain_f, "total": enc_f + chain_f, "pose_one_pass_call": pose_pass_flops(T) + cond_flops(T)},
+                                "chain": chain_f, "total": enc_f + chain_f, "pose_one_pass_call": pose_pass_flops(3) + cond_flops(3)},      # (the yardstick stays 3 + 3 frames)
            "device": torch.cuda.get_device_name(0), "reps": a.reps, "clock_ghz_assumed": a.clock_ghz, "batches": {}}
     gen = torch.Generator().manual_seed(1)
-    for B in (1024, a.fill_batch):
-        data = torch.randn(B, 2, Tc + 3, 17, generator=gen).clamp_(-3, 3).to(dev)
-        data6 = data if Tc == 3 else torch.randn(B, 2, 6, 17, generator=gen).clamp_(-3, 3).to(dev)      # (the pose yardstick stays 3 + 3)
+    for B in (a.batches or (1024, a.fill_batch)):
+        data = torch.randn(B, 2, Tc + Tx, 17, generator=gen).clamp_(-3, 3).to(dev)
+        data6 = data if Tc + Tx == 6 else torch.randn(B, 2, 6, 17, generator=gen).clamp_(-3, 3).to(dev)      # (the pose yardstick stays 3 + 3)
         legs = {"encode": lambda: sl.encode(data, noise_steps=ns),
                 "score": lambda: sl.score(data, n_samples=S, noise_steps=ns, aggregation="best", seed=1),
                 "pose_onepass": lambda: sp.score_fused(data6, n_samples=1, noise_steps=2, aggregation="best", seed=1)}
@@ -163,6 +170,8 @@ def main():
     torch.set_num_threads(16)
     sd = {k: v.detach().cpu() for k, v in lat.state_dict().items()}
     B = 1024
+    if "1024" not in res["batches"]:
+        raise SystemExit("the CPU comparison is made at batch 1024: add it to --batches or pass --no-cpu")
     cond, z0 = torch.randn(B, 16), torch.randn(B, D)
     noise = torch.randn(S, ns - 1, B, D)
     with torch.no_grad():
