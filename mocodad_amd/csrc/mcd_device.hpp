@@ -7,7 +7,7 @@
 //                                                                       score_generic_kernel (plain FMAs, any count) cross-checks both
 //   ST_GCNN_layer / ConvTemporalGraphical / CNN_layer  models/gcae/stsgcn.py:94-199
 //   DDPM ancestral update + SmoothL1    models/mocodad.py:172-178,484
-//   STSE.encode (condition encoder)     models/stsae/stsae.py:59-92    -> cond_fast_kernel (1 .. 12 frames) / cond_encode_kernel;
+//   STSE.encode (condition encoder)     models/stsae/stsae.py:59-92    -> cond_fast_kernel (1 .. 20 frames) / cond_encode_kernel;
 //   STSE_Unet ('E_unet' encoder)        models/stsae/stsae_unet.py:62-146     cond_unet_kernel (1 .. 12) / cond_unet_generic_kernel
 //   _aggregation_strategy               models/mocodad.py:454-520      -> aggregate_kernel
 //

@@ -1,0 +1,329 @@
+// mcd_encode_kernel.hpp — the encoder family: the MFMA condition encoders of the pose model, cond_fast_kernel<T, NB> (shipped
+// channel list) and cond_unet_kernel<T, NB> ('E_unet'), and the latent model's encode launch latent_encode_kernel<T, NB,
+// COND_IN_KERNEL, PROJECT_IN_KERNEL>.  All three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear
+// over the (c,t,v) flattening; the shared pieces -- load_window_frames, unet_down_path, flatten_linear -- are stated here once
+// (DESIGN.md 2.1-2.2, 2.6).  cond_fast_body is also the trajectory kernel's prologue (score_kernel, P.cond_inkernel).
+#pragma once
+#include "mcd_device.hpp"
+#include "mcd_latent.hpp"
+
+namespace mcd {
+
+constexpr int TABC = 128;                  // cond table: second 128 words of the weight buffer
+constexpr int TABC_LW = 40, TABC_LB = 41;  // bottleneck Linear weight [16][32*T*17] / bias
+constexpr int TABC_URS = 56;               // down1 / down2 fragments + bias: 4 words
+constexpr int TABC_ULW = 60, TABC_ULB = 61;  // to_time_dim weight [16][6*T*10] / bias
+constexpr int CU_OUT = 6;                  // unet_down_channels[6] of STSE_Unet
+
+// condition / corrupt frames of windows b0 .. b0 + NB - 1 -> dst[col = (n,t,v)][20], channels 0, 1; frame_of(t) = data frame of
+// frame t.  A window past the end repeats the last one.
+template <int T, int NB, class FrameOf>
+__device__ __forceinline__ void load_window_frames(float* dst, const DataView& dv, FrameOf&& frame_of, int seg_len, int b0, int B) {
+    constexpr int TV = T * 17, COLS = NB * TV;
+    for (int u = threadIdx.x; u < COLS * C0; u += NTHREADS) {
+        const int c = u % C0, col = u / C0;
+        const int n = col / TV, t = (col / 17) % T, v = col % 17;
+        const int b = b0 + n < B ? b0 + n : B - 1;
+        dst[col * 20 + c] = load_coord(dv, b, c, frame_of(t), v, seg_len);
+    }
+}
+
+// The U-Net's down path 2->16->32->32 | 17->12 | 32->64->64 | 12->10 | 64->128 on Plan<T, NB> (layers 0 .. 5 and the two
+// non-capturing down-samplers, each with its barrier), input at RG + L0_in, output at RG + L5_out.  tab: the layer table (layer l
+// at l * F_STRIDE); rs: the table words, relative to wb, of down1 / down2's fragments and biases.  HASEMB: the embedding
+// EMB + emb_off(l) is added in each layer's GEMM epilogue as in score_kernel.  The last layer differs per kernel: the caller's.
+struct RsWords { int w1, b1, w2, b2; };
+template <int T, int NB, bool HASEMB>
+__device__ __forceinline__ void unet_down_path(const float* wb, const float* tab, const RsWords rs, float* RG, const float* EMB,
+                                               int wave, int lane, Prof& prof) {
+    using PL = Plan<T, NB>;
+    auto emb = [&](int l) { return HASEMB ? EMB + emb_off(l) : nullptr; };
+    float nosk[1] = {0.f};
+    layer_generic<16, 16, 17, true, HASEMB, T, NB>(wb, layer_w(tab, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, emb(0), wave, lane, prof, 0);
+    layer_generic<16, 32, 17, true, HASEMB, T, NB>(wb, layer_w(tab, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, emb(1), wave, lane, prof, 0);
+    layer_generic<32, 32, 17, false, HASEMB, T, NB>(wb, layer_w(tab, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, emb(2), wave, lane, prof, 0);
+    {
+        RsCoef<32, 17, 12, T, NB, false> rc;
+        rc.load(wb + tab_i(wb, rs.w1), wb + tab_i(wb, rs.b1), lane);
+        resample_stage<32, 17, 12, T, NB, false, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, nosk, wave, lane);
+        __syncthreads();
+    }
+    layer_generic<32, 64, 12, true, HASEMB, T, NB>(wb, layer_w(tab, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, emb(3), wave, lane, prof, 0);
+    layer_generic<64, 64, 12, false, HASEMB, T, NB>(wb, layer_w(tab, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, emb(4), wave, lane, prof, 0);
+    {
+        RsCoef<64, 12, 10, T, NB, false> rc;
+        rc.load(wb + tab_i(wb, rs.w2), wb + tab_i(wb, rs.b2), lane);
+        resample_stage<64, 12, 10, T, NB, false, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, nosk, wave, lane);
+        __syncthreads();
+    }
+    layer_generic<64, 128, 10, true, HASEMB, T, NB>(wb, layer_w(tab, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, emb(5), wave, lane, prof, 0);
+}
+
+// Linear over the (c, tv) flattening of H[(n TV + tv) CS + c]: out[n][j] = bias[j] + sum_k W[j][k] H[n][k], k = c TV + tv, for the
+// NB windows of the workgroup and n_out outputs; store(n, j, value) takes the result.  A thread owns one (output, part of 16) --
+// the 16 parts of an output are the 16 lanes of a DPP row -- of one window, or with SHARE_W of all NB windows, which then share
+// every weight load.  (c, tv) loops instead of k % TV, k / TV per element, with compile-time trip counts (the ragged last
+// 16-block is predicated): the loops unroll (UNROLL channels at a time) and the weight loads of several channels are in flight
+// together -- with the data-dependent bound `tv + part < TV` every load waited for the FMA before it (one L2 round trip per
+// element: 100 .. 400 of them per thread, the whole encoder's time).  An output is one fmaf chain in c-then-i order per part, the
+// 16-lane sum, then the bias.
+template <int C, int CS, int TV, int NB, bool SHARE_W, int UNROLL, class Store>
+__device__ __forceinline__ void flatten_linear(const float* H, gfloat* W, gfloat* bias, int n_out, Store&& store) {
+    constexpr int F = C * TV, NT16 = (TV + 15) / 16, NW = SHARE_W ? NB : 1;
+    for (int u = threadIdx.x; u < (NB / NW) * n_out * 16; u += NTHREADS) {
+        const int part = u & 15, jo = SHARE_W ? u >> 4 : (u >> 4) % n_out, n0 = SHARE_W ? 0 : u / (16 * n_out);
+        float a[NW];
+#pragma unroll
+        for (int n = 0; n < NW; ++n) a[n] = 0.f;
+        gfloat* wr = W + (size_t)jo * F + part;
+        const float* hr = H + (n0 * TV + part) * CS;
+#pragma unroll UNROLL
+        for (int c = 0; c < C; ++c) {
+            float wv[NT16];
+#pragma unroll
+            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV) ? wr[c * TV + i * 16] : 0.f;
+#pragma unroll
+            for (int n = 0; n < NW; ++n)
+#pragma unroll
+                for (int i = 0; i < NT16; ++i) a[n] = fmaf(wv[i], (i * 16 + part < TV) ? hr[(n * TV + i * 16) * CS + c] : 0.f, a[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < NW; ++n) {
+            const float r = row16_sum(a[n]);
+            if (part == 0) store(n0 + n, jo, r + bias[jo]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// condition encoder, fast path for the shipped architecture (channels [32,16,32] + h_dim 32, latent 16):
+// the same MFMA mix / GEMM stages as the U-Net, NB windows per 512-thread workgroup, followed by the
+// bottleneck Linear over the (c,t,v) flattening (stsae.py:73-89).  Reads the condition frames straight from the
+// window tensor (no gather pass).  Other channel lists use cond_encode_kernel (mcd_generic_kernel.hpp).
+// ------------------------------------------------------------------------------------------------
+template <int T, int NB>
+struct CondFastLds {     // cond_fast_body's region: X0, Z0 [P17][20] | Y0, Z1 [P17][36]
+    static constexpr int P17 = ceil16(NB * T * 17);
+    static constexpr int FLOATS = P17 * (2 * 20 + 2 * 36);
+};
+
+// body shared by cond_fast_kernel, the trajectory kernel's prologue (P.cond_inkernel) and the latent encode launch: windows
+// b0 .. b0 + NB - 1, frame_of(t) = data frame of condition frame t; the embeddings go to emb_lds[n][16] (LDS) and / or emb_out (B,16).
+// smem: CondFastLds<T, NB>::FLOATS floats, zeroed by the caller.
+// Its loader and tail are its own copies of load_window_frames / flatten_linear<32, 36, T * 17, NB, false, 4>: the body is inlined
+// into every score_kernel row, and the trajectory kernels' text does not move for a refactor.
+template <int T, int NB, class FrameOf>
+__device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView& dv, FrameOf&& frame_of, int seg_len, float* smem,
+                                               int b0, int B, float* emb_lds, float* __restrict__ emb_out) {
+    constexpr int P17 = ceil16(NB * T * 17);
+    constexpr int s16 = P17 * 20, s32 = P17 * 36;
+    constexpr int TV = T * 17, COLS = NB * TV;
+    float* const X0 = smem;                   // [P17][20]  in of layers 0, 2 ; out of layer 1
+    float* const Z0 = smem + s16;             // [P17][20]
+    float* const Y0 = smem + 2 * s16;         // [P17][36]  out of layers 0, 2 ; in of layers 1, 3
+    float* const Z1 = smem + 2 * s16 + s32;   // [P17][36]
+    float* const H = smem;                    // [P17][36]  out of layer 3 (over X0/Z0: 36 <= 40)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    Prof prof;
+    prof.off();
+    for (int u = tid; u < COLS * C0; u += NTHREADS) {
+        const int c = u % C0, col = u / C0;
+        const int n = col / TV, t = (col / 17) % T, v = col % 17;
+        const int b = b0 + n < B ? b0 + n : B - 1;
+        X0[col * 20 + c] = load_coord(dv, b, c, frame_of(t), v, seg_len);
+    }
+    bsync();
+    const float* wb = wbuf;
+    layer_generic<16, 32, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 0), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 2(16) -> 32
+    layer_generic<32, 16, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 1), Y0, Z1, X0, nullptr, wave, lane, prof, 0);   // 32 -> 16
+    layer_generic<16, 32, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 2), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 16 -> 32
+    layer_generic<32, 32, 17, false, false, T, NB>(wb, layer_w(wb + TABC, 3), Y0, Z1, H, nullptr, wave, lane, prof, 0);   // 32 -> 32
+    // bottleneck Linear: emb[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*TV + tv.  thread = (n, j, part of 16)
+    constexpr int F = 32 * TV;
+    gfloat* W = as_global(wb + tab_i(wb, TABC + TABC_LW));
+    gfloat* bb = as_global(wb + tab_i(wb, TABC + TABC_LB));
+    for (int u = tid; u < NB * EDIM * 16; u += NTHREADS) {
+        const int part = u & 15, jo = (u >> 4) % EDIM, n = u / (16 * EDIM);
+        constexpr int NT16 = (TV + 15) / 16;      // (compile-time trip counts: see flatten_linear)
+        float a = 0.f;
+        gfloat* wr = W + jo * F + part;
+        const float* hr = H + (n * TV + part) * 36;
+#pragma unroll 4
+        for (int c = 0; c < 32; ++c) {
+            float wv[NT16];
+#pragma unroll
+            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV) ? wr[c * TV + i * 16] : 0.f;
+#pragma unroll
+            for (int i = 0; i < NT16; ++i) a = fmaf(wv[i], (i * 16 + part < TV) ? hr[i * 16 * 36 + c] : 0.f, a);
+        }
+        a = row16_sum(a);
+        if (part == 0) {
+            const float e = a + bb[jo];
+            if (emb_lds) emb_lds[n * EDIM + jo] = e;
+            if (emb_out && b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + jo] = e;
+        }
+    }
+}
+
+template <int T, int NB>
+__global__ __launch_bounds__(NTHREADS, 2) void cond_fast_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
+                                                                int seg_len, float* __restrict__ emb_out, int B) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    for (int u = threadIdx.x; u < CondFastLds<T, NB>::FLOATS; u += NTHREADS) smem[u] = 0.f;
+    __syncthreads();
+    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return fi.idx[t]; }, seg_len, smem, blockIdx.x * NB, B, nullptr, emb_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// condition encoder 'E_unet' (STSE_Unet with set_out_layer, stsae_unet.py:62-146,182-251): the U-Net's down path
+// 2->16->32->32 | 17->12 | 32->64->64 | 12->10 | 64->128->6 without embeddings (t = None), then
+// Linear(6*T*10 -> latent) over the (c,t,v) flattening.  Same MFMA stages and LDS plan as the scoring kernel.
+// ------------------------------------------------------------------------------------------------
+template <int T, int NB>
+struct DownPathLds {     // the scoring kernel's work region, with the [P10][cs] output of the last layer behind its (in, z) = 2 x s128
+    using PL = Plan<T, NB>;
+    static constexpr int H_OFF = 2 * PL::s128;
+    static constexpr int work(int cs) { return cmax(PL::R, H_OFF + PL::P10 * cs); }
+};
+template <int T, int NB>
+struct CondUnetLds : DownPathLds<T, NB> {
+    static constexpr int FLOATS = DownPathLds<T, NB>::work(20);
+};
+
+template <int T, int NB>
+__global__ __launch_bounds__(NTHREADS, 2) void cond_unet_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
+                                                                int seg_len, float* __restrict__ emb_out, int B) {
+    using PL = Plan<T, NB>;
+    using LD = CondUnetLds<T, NB>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const RG = smem;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b0 = blockIdx.x * NB;
+    Prof prof;
+    prof.off();
+    for (int u = tid; u < LD::FLOATS; u += NTHREADS) smem[u] = 0.f;
+    __syncthreads();
+    load_window_frames<T, NB>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B);
+    __syncthreads();
+    const float* wb = wbuf;
+    unet_down_path<T, NB, false>(wb, wb + TABC, RsWords{TABC + TABC_URS + 0, TABC + TABC_URS + 1, TABC + TABC_URS + 2, TABC + TABC_URS + 3},
+                                 RG, nullptr, wave, lane, prof);
+    layer_generic<128, 16, 10, true, false, T, NB>(wb, layer_w(wb + TABC, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, nullptr, wave, lane, prof, 0);
+    // to_time_dim: emb[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v
+    flatten_linear<CU_OUT, 20, T * 10, NB, false, CU_OUT>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TABC + TABC_ULW)),
+                                                          as_global(wb + tab_i(wb, TABC + TABC_ULB)), EDIM, [&](int n, int j, float e) {
+        if (b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + j] = e;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Encode launch of the latent model: windows b0 .. b0 + NB - 1 of a workgroup.  cond_fast_body (the shipped condition encoder) ->
+// cond_emb; the embeddings Linear(SiLU(pos_encoding(-1) + cond_emb)) of the seven down-path layers; the down path as in
+// cond_unet_kernel, with the embedding added in the GEMM epilogue as in score_kernel; to_time_dim over the (c,t,v) flattening.
+// Table of the packed buffer: layers 0 .. 6 at l * F_STRIDE (all mix-first [W_t' | W_r']), TAB_WE / TAB_BE = W_e [400][16] / b_e,
+// TAB_RSW / TAB_RSB + 0, 1 = down1 / down2 (non-capturing fragments), TAB_LAT_LW / TAB_LAT_LB = to_time_dim; the condition
+// encoder's table at TABC as cond_fast_body expects it.
+// ------------------------------------------------------------------------------------------------
+
+// PROJECT_IN_KERNEL = false: the last layer runs as two halves of 32 output channels, each [P10][36] at H_OFF and copied to global
+// memory before the next (12 frames: 332 P10 floats for the whole output would be 168 KB)
+template <int T, int NB, bool PROJECT_IN_KERNEL = true>
+struct LatentEncLds : DownPathLds<T, NB> {
+    static constexpr int WORK = cmax(DownPathLds<T, NB>::work(PROJECT_IN_KERNEL ? 68 : 36), CondFastLds<T, NB>::FLOATS);
+    static constexpr int EMB = NB * EMB_STRIDE;
+    static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
+};
+
+// COND_IN_KERNEL = false (the three-launch form: any other condition encoder, 1 .. 12 condition frames): a condition-encoder
+// kernel of the pose model (cond_fast_kernel / cond_unet_kernel / cond_encode_kernel) has written cond_emb (B,16) to cond_out in a
+// launch of its own; the prologue is skipped, CE is read from there and the remainder is the same code.
+// PROJECT_IN_KERNEL = false (5 .. 12 corrupt frames): no to_time_dim tail; z0_out is H (B, 640 T), the last layer's output of window b
+// at H[b][(t 10 + v) 64 + c] -- the order the LDS holds, so the copy is 16-byte stores -- for latent_project_kernel.
+template <int T, int NB, bool COND_IN_KERNEL = true, bool PROJECT_IN_KERNEL = true>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
+                                                                    const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
+                                                                    float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
+    using PL = Plan<T, NB>;
+    using LD = LatentEncLds<T, NB, PROJECT_IN_KERNEL>;
+    constexpr int TV10 = T * 10;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const RG = smem;
+    float* const EMB = smem + LD::WORK;
+    float* const CE = EMB + LD::EMB;
+    float* const SEN = CE + NB * EDIM;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b0 = blockIdx.x * NB;
+    Prof prof;
+    prof.off();
+    if constexpr (COND_IN_KERNEL) {
+        for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+        __syncthreads();
+        cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
+        __syncthreads();
+    } else {
+        if (tid < NB * EDIM) {
+            const int n = tid / EDIM, b = b0 + n < B ? b0 + n : B - 1;      // (a window past the end repeats the last one, as load_window_frames)
+            CE[tid] = cond_out[(size_t)b * EDIM + tid % EDIM];
+        }
+        __syncthreads();
+    }
+    const float* wb = wbuf;
+    if (tid < NB * EDIM) {
+        const float e = pe_row[tid % EDIM] + CE[tid];
+        SEN[tid] = e / (1.f + expf(-e));
+    }
+    for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
+    __syncthreads();
+    load_window_frames<T, NB>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B);
+    {
+        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
+        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
+        for (int o = tid; o < LAT_EMB; o += NTHREADS) {
+            float w[EDIM];
+#pragma unroll
+            for (int k = 0; k < EDIM; ++k) w[k] = we[o * EDIM + k];
+            const float bo = be[o];
+#pragma unroll
+            for (int n = 0; n < NB; ++n) {
+                float a = bo;
+#pragma unroll
+                for (int k = 0; k < EDIM; ++k) a = fmaf(w[k], SEN[n * EDIM + k], a);
+                EMB[n * EMB_STRIDE + o] = a;
+            }
+        }
+    }
+    __syncthreads();
+    unet_down_path<T, NB, true>(wb, wb, RsWords{TAB_RSW + 0, TAB_RSB + 0, TAB_RSW + 1, TAB_RSB + 1}, RG, EMB, wave, lane, prof);
+    constexpr int F = LAT_ENC_C * TV10;
+    if constexpr (!PROJECT_IN_KERNEL) {
+        // the last layer as two halves of 32 output channels: m-tiles 2 h, 2 h + 1 of its fragments are one contiguous block, so a
+        // half is the same layer with its weight, bias and embedding pointers moved on.  (The mix runs again for the second half;
+        // the copy of a half has finished in every thread before the next half's GEMM writes: the mix's barrier lies between.)
+        const LayerW l6 = layer_w(wb, 6);
+        const float* HL = RG + LD::H_OFF;
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            LayerW lh = l6;
+            lh.wp += h * 2 * (2 * 128 / 16) * 256;
+            lh.bias += h * 32;
+            layer_generic<128, 32, 10, true, true, T, NB>(wb, lh, RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6) + h * 32, wave, lane, prof, 0);
+            for (int u = tid; u < NB * TV10 * 8; u += NTHREADS) {
+                const int col = u >> 3, q = u & 7, n = col / TV10;
+                if (b0 + n < B)
+                    store_global4(z0_out + (size_t)(b0 + n) * F + (col - n * TV10) * LAT_ENC_C + h * 32 + 4 * q, lds_load4(lds_addr(HL + col * 36 + 4 * q)));
+            }
+        }
+        return;
+    }
+    layer_generic<128, 64, 10, true, true, T, NB>(wb, layer_w(wb, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6), wave, lane, prof, 0);
+    // to_time_dim: z0[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v; a thread serves every window of the workgroup
+    flatten_linear<LAT_ENC_C, 68, TV10, NB, true, 4>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TAB_LAT_LW)), as_global(wb + tab_i(wb, TAB_LAT_LB)),
+                                                     D, [&](int n, int j, float z) {
+        if (b0 + n < B) z0_out[(size_t)(b0 + n) * D + j] = z;
+    });
+}
+
+}  // namespace mcd

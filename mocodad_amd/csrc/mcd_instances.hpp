@@ -1,6 +1,7 @@
 // mcd_instances.hpp — every kernel instantiation of libmocodad_hip.so and the translation unit that holds it.
 //
-// The library is built from mcd_api.hip (C ABI, packers, dispatch, the runtime-shape kernels) plus mcd_inst.hip compiled once
+// The library is built from mcd_api.hip (C ABI, dispatch; it includes the packer, mcd_pack.hpp, and the runtime-shape kernels,
+// mcd_generic_kernel.hpp) plus mcd_inst.hip compiled once
 // per unit with -DMCD_INST_UNIT_<n>: a unit explicitly instantiates the launcher templates of its rows (and with them the
 // kernels); every other translation unit sees them as `extern template` and compiles none of that device code.  The units
 // build in parallel (mocodad_amd/build.py); their number and the assignment below only balance compile times.
@@ -12,7 +13,7 @@
 //   X(unit, T_c, NB)             cond_fast_kernel / cond_unet_kernel<T_c, NB>
 //   X(unit, TP, NB, LT)          score_tiled_kernel<TP, NB, LT>
 //   X(unit, TP, NB)              score_tiled_kernel<TP, NB, false, true>: the 'E_unet' condition encoder at 13 .. 32 condition frames
-//   X(T, NB, COND_IN_KERNEL)     latent_encode_kernel (at the end of this file; its translation unit is mcd_latent.hip)
+//   X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL)   latent_encode_kernel (at the end of this file; its translation unit is mcd_latent.hip)
 #pragma once
 
 #ifndef MCD_FAST_T      // the shipped library

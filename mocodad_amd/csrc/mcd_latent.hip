@@ -1,4 +1,5 @@
-// mcd_latent.hip — the translation unit of the MoCoDADlatent kernels (mcd_latent_kernel.hpp) and their launchers; built with
+// mcd_latent.hip — the translation unit of the MoCoDADlatent kernels (mcd_latent_kernel.hpp, and latent_encode_kernel of
+// mcd_encode_kernel.hpp, which mcd_launch.hpp brings) and their launchers; built with
 // the default eight waves per workgroup (the chain kernel has its own four).  Compiled once as it is (unit 0: the dispatch, the
 // chain, projection and Philox kernels, the encode kernels of the rows of unit 0) and once per unit n = 1 .. MCD_LATENT_UNITS
 // with -DMCD_LATENT_UNIT=n (the encode kernels of that unit's rows only); see MCD_LATENT_ENCODE_INSTANCES in mcd_instances.hpp.
@@ -6,11 +7,10 @@
 #ifndef MCD_LATENT_UNIT
 #define MCD_LATENT_UNIT 0
 #endif
-#if MCD_LATENT_UNIT != 0
-#define MCD_LATENT_ENCODE_ONLY
-#endif
 #include "mcd_launch.hpp"
+#if MCD_LATENT_UNIT == 0
 #include "mcd_latent_kernel.hpp"
+#endif
 
 namespace mcd {
 

@@ -1,21 +1,17 @@
-// mcd_latent_kernel.hpp — MoCoDADlatent (models/mocodad_latent.py:69-132, stage 'diffusion'): the two launches of a latent
-// scoring call and their test / replay companions.
-//   latent_encode_kernel<T, NB>   condition encoder + the U-Net's down path with embeddings + to_time_dim -> cond_emb (B,16), z0 (B,D)
+// mcd_latent_kernel.hpp — MoCoDADlatent (models/mocodad_latent.py:69-132, stage 'diffusion'): the launches of a latent scoring
+// call behind its encode launch (latent_encode_kernel, mcd_encode_kernel.hpp) and their test / replay companions.
 //   latent_chain_kernel           every reverse-diffusion chain of the call: S (ns-1) denoiser passes (components.py:203-291) as
 //                                 v_mfma_f32_16x16x4_f32 products with the chains as the N dimension, the DDPM updates, the loss
 //                                 against z0 and the loss-based aggregation over the samples
 //   latent_philox_kernel          the perf mode's draws in the parity layout
 //   latent_project_kernel         to_time_dim for all windows of a call as MFMA products (5 .. 12 corrupt frames, whose encode launch
 //                                 stops at the last layer's output)
-// The stage functions, the LDS plan and the fragment orders are those of mcd_device.hpp / mcd_score_kernel.hpp, included unchanged.
 #pragma once
 #include "mcd_device.hpp"
-#include "mcd_score_kernel.hpp"
 #include "mcd_latent.hpp"
 
 namespace mcd {
 
-#ifndef MCD_LATENT_ENCODE_ONLY      // (a unit that holds encode kernels only: see MCD_LATENT_ENCODE_INSTANCES)
 __device__ __forceinline__ f32x4 lat_mfma4(const float4 a, const float4 b, f32x4 acc) {
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
@@ -253,162 +249,6 @@ __global__ __launch_bounds__(PROJ_THREADS) void latent_project_kernel(const floa
         }
         const float4 bb = load_global4(wbuf + tab_i(wbuf, TAB_LAT_LB) + c0);
         if (b < B) store_global4(z0_out + (size_t)b * D + c0, make_float4(s.x + bb.x, s.y + bb.y, s.z + bb.z, s.w + bb.w));
-    }
-}
-#endif  // MCD_LATENT_ENCODE_ONLY
-
-// ------------------------------------------------------------------------------------------------
-// Encode launch: windows b0 .. b0 + NB - 1 of a workgroup.  cond_fast_body (the shipped condition encoder) -> cond_emb; the
-// embeddings Linear(SiLU(pos_encoding(-1) + cond_emb)) of the seven down-path layers; the layers on Plan<T, NB> as in
-// cond_unet_kernel, with the embedding added in the GEMM epilogue as in score_kernel; to_time_dim over the (c,t,v) flattening.
-// Table of the packed buffer: layers 0 .. 6 at l * F_STRIDE (all mix-first [W_t' | W_r']), TAB_WE / TAB_BE = W_e [400][16] / b_e,
-// TAB_RSW / TAB_RSB + 0, 1 = down1 / down2 (non-capturing fragments), TAB_LAT_LW / TAB_LAT_LB = to_time_dim; the condition
-// encoder's table at TABC as cond_fast_body expects it.
-// ------------------------------------------------------------------------------------------------
-
-// PROJECT_IN_KERNEL = false: the last layer runs as two halves of 32 output channels, each [P10][36] at H_OFF and copied to global
-// memory before the next (12 frames: 332 P10 floats for the whole output would be 168 KB)
-template <int T, int NB, bool PROJECT_IN_KERNEL = true>
-struct LatentEncLds {
-    using PL = Plan<T, NB>;
-    static constexpr int P17 = ceil16(NB * T * 17);
-    static constexpr int H_OFF = 2 * PL::s128;                   // [P10][68] output of the last layer behind its (in, z)
-    static constexpr int WORK = cmax(cmax(PL::R, H_OFF + PL::P10 * (PROJECT_IN_KERNEL ? 68 : 36)), P17 * (2 * 20 + 2 * 36));
-    static constexpr int EMB = NB * EMB_STRIDE;
-    static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
-};
-
-// COND_IN_KERNEL = false (the three-launch form: any other condition encoder, 1 .. 12 condition frames): a condition-encoder
-// kernel of the pose model (cond_fast_kernel / cond_unet_kernel / cond_encode_kernel) has written cond_emb (B,16) to cond_out in a
-// launch of its own; the prologue is skipped, CE is read from there and the remainder is the same code.
-// PROJECT_IN_KERNEL = false (5 .. 12 corrupt frames): no to_time_dim tail; z0_out is H (B, 640 T), the last layer's output of window b
-// at H[b][(t 10 + v) 64 + c] -- the order the LDS holds, so the copy is 16-byte stores -- for latent_project_kernel.
-template <int T, int NB, bool COND_IN_KERNEL = true, bool PROJECT_IN_KERNEL = true>
-__global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
-                                                                    const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
-                                                                    float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
-    using PL = Plan<T, NB>;
-    using LD = LatentEncLds<T, NB, PROJECT_IN_KERNEL>;
-    constexpr int TV17 = T * 17, COLS17 = NB * TV17, TV10 = T * 10;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const RG = smem;
-    float* const EMB = smem + LD::WORK;
-    float* const CE = EMB + LD::EMB;
-    float* const SEN = CE + NB * EDIM;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = blockIdx.x * NB;
-    Prof prof;
-    prof.off();
-    if constexpr (COND_IN_KERNEL) {
-        for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
-        __syncthreads();
-        cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
-        __syncthreads();
-    } else {
-        if (tid < NB * EDIM) {
-            const int n = tid / EDIM, b = b0 + n < B ? b0 + n : B - 1;      // (a window past the end repeats the last one, as load_coord below)
-            CE[tid] = cond_out[(size_t)b * EDIM + tid % EDIM];
-        }
-        __syncthreads();
-    }
-    const float* wb = wbuf;
-    if (tid < NB * EDIM) {
-        const float e = pe_row[tid % EDIM] + CE[tid];
-        SEN[tid] = e / (1.f + expf(-e));
-    }
-    for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
-    __syncthreads();
-    for (int u = tid; u < COLS17 * C0; u += NTHREADS) {
-        const int c = u % C0, col = u / C0;
-        const int n = col / TV17, t = (col / 17) % T, v = col % 17;
-        const int b = b0 + n < B ? b0 + n : B - 1;
-        RG[PL::L0_in + col * 20 + c] = load_coord(dv, b, c, fi.idx[t], v, seg_len);
-    }
-    {
-        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
-        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
-        for (int o = tid; o < LAT_EMB; o += NTHREADS) {
-            float w[EDIM];
-#pragma unroll
-            for (int k = 0; k < EDIM; ++k) w[k] = we[o * EDIM + k];
-            const float bo = be[o];
-#pragma unroll
-            for (int n = 0; n < NB; ++n) {
-                float a = bo;
-#pragma unroll
-                for (int k = 0; k < EDIM; ++k) a = fmaf(w[k], SEN[n * EDIM + k], a);
-                EMB[n * EMB_STRIDE + o] = a;
-            }
-        }
-    }
-    __syncthreads();
-    float nosk[1] = {0.f};
-    layer_generic<16, 16, 17, true, true, T, NB>(wb, layer_w(wb, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, EMB + emb_off(0), wave, lane, prof, 0);
-    layer_generic<16, 32, 17, true, true, T, NB>(wb, layer_w(wb, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, EMB + emb_off(1), wave, lane, prof, 0);
-    layer_generic<32, 32, 17, false, true, T, NB>(wb, layer_w(wb, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, EMB + emb_off(2), wave, lane, prof, 0);
-    {
-        RsCoef<32, 17, 12, T, NB, false> rc;
-        rc.load(wb + tab_i(wb, TAB_RSW + 0), wb + tab_i(wb, TAB_RSB + 0), lane);
-        resample_stage<32, 17, 12, T, NB, false, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, nosk, wave, lane);
-        __syncthreads();
-    }
-    layer_generic<32, 64, 12, true, true, T, NB>(wb, layer_w(wb, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, EMB + emb_off(3), wave, lane, prof, 0);
-    layer_generic<64, 64, 12, false, true, T, NB>(wb, layer_w(wb, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, EMB + emb_off(4), wave, lane, prof, 0);
-    {
-        RsCoef<64, 12, 10, T, NB, false> rc;
-        rc.load(wb + tab_i(wb, TAB_RSW + 1), wb + tab_i(wb, TAB_RSB + 1), lane);
-        resample_stage<64, 12, 10, T, NB, false, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, nosk, wave, lane);
-        __syncthreads();
-    }
-    layer_generic<64, 128, 10, true, true, T, NB>(wb, layer_w(wb, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, EMB + emb_off(5), wave, lane, prof, 0);
-    constexpr int F = LAT_ENC_C * TV10;
-    if constexpr (!PROJECT_IN_KERNEL) {
-        // the last layer as two halves of 32 output channels: m-tiles 2 h, 2 h + 1 of its fragments are one contiguous block, so a
-        // half is the same layer with its weight, bias and embedding pointers moved on.  (The mix runs again for the second half;
-        // the copy of a half has finished in every thread before the next half's GEMM writes: the mix's barrier lies between.)
-        const LayerW l6 = layer_w(wb, 6);
-        const float* HL = RG + LD::H_OFF;
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-            LayerW lh = l6;
-            lh.wp += h * 2 * (2 * 128 / 16) * 256;
-            lh.bias += h * 32;
-            layer_generic<128, 32, 10, true, true, T, NB>(wb, lh, RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6) + h * 32, wave, lane, prof, 0);
-            for (int u = tid; u < NB * TV10 * 8; u += NTHREADS) {
-                const int col = u >> 3, q = u & 7, n = col / TV10;
-                if (b0 + n < B)
-                    store_global4(z0_out + (size_t)(b0 + n) * F + (col - n * TV10) * LAT_ENC_C + h * 32 + 4 * q, lds_load4(lds_addr(HL + col * 36 + 4 * q)));
-            }
-        }
-        return;
-    }
-    layer_generic<128, 64, 10, true, true, T, NB>(wb, layer_w(wb, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6), wave, lane, prof, 0);
-    // to_time_dim: z0[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v.  thread = (j, part of 16), every window of the workgroup
-    const float* H = RG + LD::H_OFF;
-    gfloat* W = as_global(wb + tab_i(wb, TAB_LAT_LW));
-    gfloat* bb = as_global(wb + tab_i(wb, TAB_LAT_LB));
-    for (int u = tid; u < D * 16; u += NTHREADS) {
-        const int part = u & 15, jo = u >> 4;
-        float a[NB];
-#pragma unroll
-        for (int n = 0; n < NB; ++n) a[n] = 0.f;
-        constexpr int NT16 = (TV10 + 15) / 16;
-#pragma unroll 4
-        for (int c = 0; c < LAT_ENC_C; ++c) {
-            float wv[NT16];
-#pragma unroll
-            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV10) ? W[(size_t)jo * F + c * TV10 + i * 16 + part] : 0.f;
-#pragma unroll
-            for (int n = 0; n < NB; ++n)
-#pragma unroll
-                for (int i = 0; i < NT16; ++i) a[n] = fmaf(wv[i], (i * 16 + part < TV10) ? H[(n * TV10 + i * 16 + part) * 68 + c] : 0.f, a[n]);
-        }
-#pragma unroll
-        for (int n = 0; n < NB; ++n) {
-            const float r = row16_sum(a[n]);
-            if (part == 0 && b0 + n < B) z0_out[(size_t)(b0 + n) * D + jo] = r + bb[jo];
-        }
     }
 }
 

@@ -145,8 +145,7 @@ int launch_score_t(ScoreParams& P, hipStream_t st, bool* fused) {
 // MFMA encoder of the shipped architecture: its four 17-joint layers need 112 floats of LDS per column (20 frames: 158 KB)
 template <int T, int NB>
 int launch_cond_fast_t(const mcd_weights* w, const DataView& data, const FrameIdx& fi, int seg_len, float* emb, int B, hipStream_t st) {
-    constexpr int P17 = ceil16(NB * T * 17);
-    constexpr size_t bytes = (size_t)P17 * (2 * 20 + 2 * 36) * 4;
+    constexpr size_t bytes = (size_t)CondFastLds<T, NB>::FLOATS * 4;
     LDS_LIMIT((&cond_fast_kernel<T, NB>), bytes);
     hipLaunchKernelGGL((cond_fast_kernel<T, NB>), dim3((B + NB - 1) / NB), dim3(NTHREADS), bytes, st, w->dbuf, data, fi, seg_len, emb, B);
     HIP_TRY(hipGetLastError());

@@ -1,96 +1,10 @@
-// mcd_score_kernel.hpp — the persistent trajectory kernel score_kernel<T_u, NB, MINW> (1 .. 12 U-Net frames) and the MFMA
-// condition encoders cond_fast_kernel / cond_unet_kernel built from the same stage functions (see mcd_device.hpp).
+// mcd_score_kernel.hpp — the persistent trajectory kernel score_kernel<T_u, NB, MINW> (1 .. 12 U-Net frames), built from the stage
+// functions of mcd_device.hpp; its prologue runs the shipped condition encoder (cond_fast_body, mcd_encode_kernel.hpp).
 #pragma once
 #include "mcd_device.hpp"
+#include "mcd_encode_kernel.hpp"
 
 namespace mcd {
-
-// ------------------------------------------------------------------------------------------------
-// condition encoder, fast path for the shipped architecture (channels [32,16,32] + h_dim 32, latent 16):
-// the same MFMA mix / GEMM stages as the U-Net, NB windows per 512-thread workgroup, followed by the
-// bottleneck Linear over the (c,t,v) flattening (stsae.py:73-89).  Reads the condition frames straight from the
-// window tensor (no gather pass).  Other channel lists use cond_encode_kernel below.
-// ------------------------------------------------------------------------------------------------
-constexpr int TABC = 128;                  // cond table: second 128 words of the weight buffer
-constexpr int TABC_LW = 40, TABC_LB = 41;  // bottleneck Linear weight [16][32*T*17] / bias
-
-// body shared by cond_fast_kernel and by the trajectory kernel's prologue (P.cond_inkernel): windows b0 .. b0 + NB - 1,
-// frame_of(t) = data frame of condition frame t; the embeddings go to emb_lds[n][16] (LDS) and / or emb_out (B,16).
-// smem: P17 * (2 * 20 + 2 * 36) floats, zeroed by the caller.
-template <int T, int NB, class FrameOf>
-__device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView& dv, FrameOf&& frame_of, int seg_len, float* smem,
-                                               int b0, int B, float* emb_lds, float* __restrict__ emb_out) {
-    constexpr int P17 = ceil16(NB * T * 17);
-    constexpr int s16 = P17 * 20, s32 = P17 * 36;
-    constexpr int TV = T * 17, COLS = NB * TV;
-    float* const X0 = smem;                   // [P17][20]  in of layers 0, 2 ; out of layer 1
-    float* const Z0 = smem + s16;             // [P17][20]
-    float* const Y0 = smem + 2 * s16;         // [P17][36]  out of layers 0, 2 ; in of layers 1, 3
-    float* const Z1 = smem + 2 * s16 + s32;   // [P17][36]
-    float* const H = smem;                    // [P17][36]  out of layer 3 (over X0/Z0: 36 <= 40)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    Prof prof;
-    prof.off();
-    for (int u = tid; u < COLS * C0; u += NTHREADS) {
-        const int c = u % C0, col = u / C0;
-        const int n = col / TV, t = (col / 17) % T, v = col % 17;
-        const int b = b0 + n < B ? b0 + n : B - 1;
-        X0[col * 20 + c] = load_coord(dv, b, c, frame_of(t), v, seg_len);
-    }
-    bsync();
-    const float* wb = wbuf;
-    auto lw = [&](int l) {
-        LayerW w;
-        w.tq = tab_i(wb, TABC + l * F_STRIDE + F_TQ); w.am = tab_i(wb, TABC + l * F_STRIDE + F_AM);
-        w.wp = tab_i(wb, TABC + l * F_STRIDE + F_WP); w.bias = tab_i(wb, TABC + l * F_STRIDE + F_BIAS);
-        w.slope = tab_f(wb, TABC + l * F_STRIDE + F_SLOPE);
-        return w;
-    };
-    layer_generic<16, 32, 17, true, false, T, NB>(wb, lw(0), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 2(16) -> 32
-    layer_generic<32, 16, 17, true, false, T, NB>(wb, lw(1), Y0, Z1, X0, nullptr, wave, lane, prof, 0);   // 32 -> 16
-    layer_generic<16, 32, 17, true, false, T, NB>(wb, lw(2), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 16 -> 32
-    layer_generic<32, 32, 17, false, false, T, NB>(wb, lw(3), Y0, Z1, H, nullptr, wave, lane, prof, 0);   // 32 -> 32
-    // bottleneck Linear: emb[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*TV + tv.  thread = (n, j, part of 16)
-    constexpr int F = 32 * TV;
-    gfloat* W = as_global(wb + tab_i(wb, TABC + TABC_LW));
-    gfloat* bb = as_global(wb + tab_i(wb, TABC + TABC_LB));
-    for (int u = tid; u < NB * EDIM * 16; u += NTHREADS) {
-        const int part = u & 15, jo = (u >> 4) % EDIM, n = u / (16 * EDIM);
-        // (c, tv) loops instead of k % TV, k / TV per element; the 16 parts of an output are the 16 lanes of a DPP row.
-        // Compile-time trip counts (the ragged last 16-block is predicated): the loops unroll and the weight loads of several
-        // channels are in flight together -- with the data-dependent bound `tv + part < TV` every load waited for the FMA
-        // before it (one L2 round trip per element: 100 .. 400 of them per thread, the whole encoder's time)
-        constexpr int NT16 = (TV + 15) / 16;
-        float a = 0.f;
-        gfloat* wr = W + jo * F + part;
-        const float* hr = H + (n * TV + part) * 36;
-#pragma unroll 4
-        for (int c = 0; c < 32; ++c) {
-            float wv[NT16];
-#pragma unroll
-            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV) ? wr[c * TV + i * 16] : 0.f;
-#pragma unroll
-            for (int i = 0; i < NT16; ++i) a = fmaf(wv[i], (i * 16 + part < TV) ? hr[i * 16 * 36 + c] : 0.f, a);
-        }
-        a = row16_sum(a);
-        if (part == 0) {
-            const float e = a + bb[jo];
-            if (emb_lds) emb_lds[n * EDIM + jo] = e;
-            if (emb_out && b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + jo] = e;
-        }
-    }
-}
-
-template <int T, int NB>
-__global__ __launch_bounds__(NTHREADS, 2) void cond_fast_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
-                                                                int seg_len, float* __restrict__ emb_out, int B) {
-    constexpr int P17 = ceil16(NB * T * 17);
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    for (int u = threadIdx.x; u < P17 * (2 * 20 + 2 * 36); u += NTHREADS) smem[u] = 0.f;
-    __syncthreads();
-    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return fi.idx[t]; }, seg_len, smem, blockIdx.x * NB, B, nullptr, emb_out);
-}
 
 // ------------------------------------------------------------------------------------------------
 // The persistent scoring kernel.  mode 0: full reverse-diffusion trajectories + loss (mcd_score);
@@ -201,6 +115,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     // ---- condition embeddings of the workgroup's windows -> CE[n][16]: computed right here with the condition encoder's
     //      MFMA stages (the shipped architecture at T condition frames), or read from the caller's (B,16) tensor
     if (P.cond_inkernel) {
+        static_assert(CondFastLds<T, NB>::FLOATS <= PL::R, "cond_fast_body's region does not fit the work region zeroed for it");
         for (int u = tid; u < PL::R; u += NTHREADS) smem[u] = 0.f;
         bsync();
         cond_fast_body<T, NB>(P.wbuf, P.dv, [&](int t) { return P.cond_idx[t]; }, P.seg_len, smem, win0, P.B, CE, nullptr);
@@ -866,94 +781,5 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     if (P.mode == 0 && P.loss_agg && te < NB && win0 + te < P.B)
         P.loss_agg[win0 + te] = aggregate_losses(LOSSB + te * 64, P.S, P.aggr, P.aggr_q);
 }
-
-// ------------------------------------------------------------------------------------------------
-// condition encoder 'E_unet' (STSE_Unet with set_out_layer, stsae_unet.py:62-146,182-251): the U-Net's down path
-// 2->16->32->32 | 17->12 | 32->64->64 | 12->10 | 64->128->6 without embeddings (t = None), then
-// Linear(6*T*10 -> latent) over the (c,t,v) flattening.  Same MFMA stages and LDS plan as the scoring kernel.
-// ------------------------------------------------------------------------------------------------
-constexpr int TABC_URS = 56;               // down1 / down2 fragments + bias: 4 words
-constexpr int TABC_ULW = 60, TABC_ULB = 61;  // to_time_dim weight [16][6*T*10] / bias
-constexpr int CU_OUT = 6;                  // unet_down_channels[6] of STSE_Unet
-
-template <int T, int NB>
-struct CondUnetLds {     // the scoring kernel's work region, with the [P10][20] output of the last layer behind 2 x s128
-    using PL = Plan<T, NB>;
-    static constexpr int H_OFF = 2 * PL::s128;
-    static constexpr int FLOATS = cmax(PL::R, H_OFF + PL::P10 * 20);
-};
-
-template <int T, int NB>
-__global__ __launch_bounds__(NTHREADS, 2) void cond_unet_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
-                                                                int seg_len, float* __restrict__ emb_out, int B) {
-    using PL = Plan<T, NB>;
-    constexpr int TV17 = T * 17, COLS17 = NB * TV17, TV10 = T * 10;
-    constexpr int H_OFF = CondUnetLds<T, NB>::H_OFF;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const RG = smem;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = blockIdx.x * NB;
-    Prof prof;
-    prof.off();
-    for (int u = tid; u < CondUnetLds<T, NB>::FLOATS; u += NTHREADS) smem[u] = 0.f;
-    __syncthreads();
-    for (int u = tid; u < COLS17 * C0; u += NTHREADS) {
-        const int c = u % C0, col = u / C0;
-        const int n = col / TV17, t = (col / 17) % T, v = col % 17;
-        const int b = b0 + n < B ? b0 + n : B - 1;
-        RG[PL::L0_in + col * 20 + c] = load_coord(dv, b, c, fi.idx[t], v, seg_len);
-    }
-    __syncthreads();
-    const float* wb = wbuf;
-    auto lw = [&](int l) {
-        LayerW w;
-        w.tq = tab_i(wb, TABC + l * F_STRIDE + F_TQ); w.am = tab_i(wb, TABC + l * F_STRIDE + F_AM);
-        w.wp = tab_i(wb, TABC + l * F_STRIDE + F_WP); w.bias = tab_i(wb, TABC + l * F_STRIDE + F_BIAS);
-        w.slope = tab_f(wb, TABC + l * F_STRIDE + F_SLOPE);
-        return w;
-    };
-    float nosk[1] = {0.f};
-    layer_generic<16, 16, 17, true, false, T, NB>(wb, lw(0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, nullptr, wave, lane, prof, 0);
-    layer_generic<16, 32, 17, true, false, T, NB>(wb, lw(1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, nullptr, wave, lane, prof, 0);
-    layer_generic<32, 32, 17, false, false, T, NB>(wb, lw(2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, nullptr, wave, lane, prof, 0);
-    {
-        RsCoef<32, 17, 12, T, NB, false> rc;
-        rc.load(wb + tab_i(wb, TABC + TABC_URS + 0), wb + tab_i(wb, TABC + TABC_URS + 1), lane);
-        resample_stage<32, 17, 12, T, NB, false, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, nosk, wave, lane);
-        __syncthreads();
-    }
-    layer_generic<32, 64, 12, true, false, T, NB>(wb, lw(3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, nullptr, wave, lane, prof, 0);
-    layer_generic<64, 64, 12, false, false, T, NB>(wb, lw(4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, nullptr, wave, lane, prof, 0);
-    {
-        RsCoef<64, 12, 10, T, NB, false> rc;
-        rc.load(wb + tab_i(wb, TABC + TABC_URS + 2), wb + tab_i(wb, TABC + TABC_URS + 3), lane);
-        resample_stage<64, 12, 10, T, NB, false, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, nosk, wave, lane);
-        __syncthreads();
-    }
-    layer_generic<64, 128, 10, true, false, T, NB>(wb, lw(5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, nullptr, wave, lane, prof, 0);
-    layer_generic<128, 16, 10, true, false, T, NB>(wb, lw(6), RG + PL::L6_in, RG + PL::L6_p, RG + H_OFF, nullptr, wave, lane, prof, 0);
-    // to_time_dim: emb[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v.  thread = (n, j, part of 16)
-    constexpr int F = CU_OUT * TV10;
-    const float* H = RG + H_OFF;
-    gfloat* W = as_global(wb + tab_i(wb, TABC + TABC_ULW));
-    gfloat* bb = as_global(wb + tab_i(wb, TABC + TABC_ULB));
-    for (int u = tid; u < NB * EDIM * 16; u += NTHREADS) {
-        const int part = u & 15, jo = (u >> 4) % EDIM, n = u / (16 * EDIM);
-        float a = 0.f;
-        constexpr int NT16 = (TV10 + 15) / 16;      // compile-time trip counts: the weight loads are issued together (see cond_fast_body)
-#pragma unroll
-        for (int c = 0; c < CU_OUT; ++c) {
-            float wv[NT16];
-#pragma unroll
-            for (int i = 0; i < NT16; ++i) wv[i] = (i * 16 + part < TV10) ? W[jo * F + c * TV10 + i * 16 + part] : 0.f;
-#pragma unroll
-            for (int i = 0; i < NT16; ++i) a = fmaf(wv[i], (i * 16 + part < TV10) ? H[(n * TV10 + i * 16 + part) * 20 + c] : 0.f, a);
-        }
-        a = row16_sum(a);
-        if (part == 0 && b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + jo] = a + bb[jo];
-    }
-}
-
 
 }  // namespace mcd

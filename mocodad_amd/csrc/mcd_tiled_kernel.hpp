@@ -1,6 +1,7 @@
 // mcd_tiled_kernel.hpp — score_tiled_kernel<TP, NB>: the MFMA trajectory kernel of 13 .. 32 U-Net frames.
 #pragma once
 #include "mcd_device.hpp"
+#include "mcd_encode_kernel.hpp"      // CU_OUT
 
 namespace mcd {
 
@@ -495,7 +496,6 @@ __device__ __forceinline__ void gemm_part(const float4 (&a)[NA], const float* __
 // layout): the per-layer table offsets of TiledNet are read through a pointer into the segment that is made opaque per step and
 // per layer -- read as plain kernel arguments they are loop-invariant, the compiler hoists all ~80 of them above the step loop,
 // and they came back as 441 v_writelane + 985 v_readlane of SGPR spills (round 3: 427 spilled SGPRs at 32 frames)
-constexpr int CU_OUT_TL = 6;               // unet_down_channels[6] of STSE_Unet (CU_OUT of cond_unet_kernel)
 struct TiledKernArgs { ScoreParams P; FrameMaps M; TiledNet N; int T; float* slabs; };
 typedef const TiledNet __attribute__((address_space(4))) KTiledNet;
 
@@ -1095,7 +1095,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                 __syncthreads();
                 int tid = tid0;
                 asm volatile("" : "+v"(tid));
-                const int F = CU_OUT_TL * T * 10;
+                const int F = CU_OUT * T * 10;
                 const float* Wl = wb + Ns->we;
                 for (int u = tid >> 5; u < NB * EDIM; u += NTHREADS / 32) {        // 32 lanes per (chain, output)
                     const int i = u / EDIM, jo = u % EDIM, part = tid & 31;
