@@ -122,6 +122,15 @@ constexpr int TAB_RSW = 90, TAB_RSB = 94; // down1, down2, up3, up2: MFMA A frag
 typedef const int __attribute__((address_space(4))) cint;
 __device__ __forceinline__ int tab_i(const float* base, int idx) { return ((cint*)base)[idx]; }
 __device__ __forceinline__ float tab_f(const float* base, int idx) { return ((cfloat*)base)[idx]; }
+// wb + off for a table offset (floats from the buffer's start).  U32: the byte offset is formed in 32 bits and zero-extended --
+// s_lshl_b32, s_add_u32, s_addc_u32 -- where the plain pointer sum sign-extends the int and shifts in 64 bits (5 scalar instructions,
+// and the 3-frame step loop forms ~60 such pointers per pass).  The packed buffer of the fixed architecture is a few hundred KB: every
+// offset is non-negative and 4 * off is far from 2^32.
+template <bool U32>
+__device__ __forceinline__ const float* wptr(const float* wb, int off) {
+    if constexpr (U32) return reinterpret_cast<const float*>(reinterpret_cast<const char*>(wb) + 4u * (unsigned)off);
+    else return wb + off;
+}
 struct LayerW { int tq, am, wp, bias; float slope; };
 __device__ __forceinline__ LayerW layer_w(const float* base, int l) {
     LayerW w;
@@ -949,7 +958,9 @@ __device__ __forceinline__ void load_afrags(const float4* __restrict__ wp, int w
 // FRONT of the tile's MFMA chain and handed to epi as a 7th argument -- read inside the epilogue they put an LDS round trip
 // between the tile's last MFMA and its store
 struct NoPre { static constexpr bool none = true; };
-template <int MT, int NT, int KQ1, int KQ2, bool IDRES, bool FORCE = false, bool DUAL = FORCE, class Epi, class Pre = NoPre>
+// SLOTK: a tile slot that every n-group of the m-tile fills ((i + 1) NG <= NT; ng < NG by construction) runs without the
+// run-time "does this wave have a tile here" compare and branch -- only the last, partly filled slot keeps them
+template <int MT, int NT, int KQ1, int KQ2, bool IDRES, bool FORCE = false, bool DUAL = FORCE, bool SLOTK = false, class Epi, class Pre = NoPre>
 __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const float* __restrict__ b1, int cs1,
                                            const float* __restrict__ b2, int cs2, int wave, int lane, Epi&& epi, int mi = 0,
                                            const float4 cinit = make_float4(0.f, 0.f, 0.f, 0.f), Pre&& pre = Pre{}) {
@@ -1151,7 +1162,8 @@ __device__ __forceinline__ void gemm_tiles(const float4 (&a)[KQ1 + KQ2], const f
         });
     } else {
         static_for<MAXN>([&](auto ii) {
-            if (ng + decltype(ii)::value * NG < NT) one_tile(ii);
+            if constexpr (SLOTK && (decltype(ii)::value + 1) * NG <= NT) one_tile(ii);
+            else if (ng + decltype(ii)::value * NG < NT) one_tile(ii);
         });
     }
 }
@@ -1168,17 +1180,18 @@ template <int KQ>
 struct LayerAfr {
     float4 a[KQ];
     float4 bcur;
-    template <int MT>
+    template <int MT, bool U32 = false>
     __device__ __forceinline__ void load(const float* wb, const LayerW& lw, int wave, int lane) {
-        load_afrags<MT, KQ>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, a);
-        bcur = load_global4(wb + lw.bias + (wave % MT) * 16 + 4 * (lane >> 4));
+        load_afrags<MT, KQ>(reinterpret_cast<const float4*>(wptr<U32>(wb, lw.wp)), wave, lane, a);
+        bcur = load_global4(wptr<U32>(wb, lw.bias) + (wave % MT) * 16 + 4 * (lane >> 4));
     }
 };
 
 // `mc`: this layer's mix coefficients (already loaded); `pre_gemm` runs between the mix barrier and the GEMM, `pre_barrier`
 // between the GEMM and the closing barrier -- the callers use them to issue the NEXT stage's coefficient loads.
 // `pre_afr`: the layer's weight fragments when the caller fetched them ahead (null: fetched here).
-template <int CIN, int COUT, int V, bool RES, bool HASEMB, int T, int NB, bool FORCE = false, int CSX = cs_of(CIN), class H1, class H2>
+// `SLOTSEL`: the caller asks for the compile-time per-slot forms (TSEL below); only the trajectory kernel's U-Net layers do (layer_std)
+template <int CIN, int COUT, int V, bool RES, bool HASEMB, int T, int NB, bool FORCE = false, int CSX = cs_of(CIN), bool SLOTSEL = false, class H1, class H2>
 __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, const MixCoef<CIN, V, T, NB>& mc,
                                               const float* __restrict__ in, float* __restrict__ z, float* __restrict__ out,
                                               const float* __restrict__ embl, int wave, int lane, Prof& prof, int prof_id,
@@ -1193,19 +1206,24 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
     float4 afr[KQ1 + KQ2];
     const int trs = 8 + 8 * ((prof_id - 32) / 3);      // trace slots of this layer (profile builds)
     prof.trace(trs + 0);
-    const float* bias = wb + lw.bias;
+    // TSEL (the trajectory kernel's U-Net layers at 3 frames x 2 chains, the shape it was measured at): what is fixed per tile SLOT is said at compile
+    // time -- the chain side of a tile (emb_of) and whether every wave has a tile in the slot (gemm_tiles' SLOTK); the run-time form
+    // costs every tile a scalar compare / select / branch set and two VALU instructions (a move of the selected offset and an
+    // add) -- and the weight pointers are formed from 32-bit byte offsets (wptr)
+    constexpr bool TSEL = SLOTSEL && HASEMB && NB == 2 && T == 3;
+    const float* bias = wptr<TSEL>(wb, lw.bias);
     float4 bcur;
     if (pre_afr != nullptr) {
 #pragma unroll
         for (int k = 0; k < KQ1 + KQ2; ++k) afr[k] = pre_afr->a[k];
         bcur = pre_afr->bcur;
     } else {
-        load_afrags<MT, KQ1 + KQ2>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr);
+        load_afrags<MT, KQ1 + KQ2>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr);
         // (the folded bias starts the first tile's accumulators: fetched here, with the weight fragments, so that its L2
         // latency hides behind the mix as well)
         bcur = load_global4(bias + (wave % MT) * 16 + 4 * (lane >> 4));
     }
-    mix_stage<CIN, V, T, NB, FORCE, HASEMB>(in, CSX, mc, wb + lw.tq, wb + lw.am, wave, lane,
+    mix_stage<CIN, V, T, NB, FORCE, HASEMB>(in, CSX, mc, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                              ZeroInit{},
                              [&](int n, int q, int w, ChIdx c, auto v) {
                                  // joint w's row, the lane's channels: the unit's part of the address on the scalar unit, the lane's
@@ -1253,7 +1271,30 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
     auto emb_of = [&](auto ti, int col, int ng) -> float4 {
         // Two chains: a tile lies on one side of the chain boundary (wave-uniform: picked on the scalar unit) except the one
         // tile that straddles it
-        if constexpr (NB == 2) {
+        if constexpr (TSEL) {
+            // The tiles of slot I are t_lo .. t_hi over the waves' n-groups; tile t_st holds columns of both chains.  A slot whose
+            // tiles all lie on one side reads its embedding row at a compile-time offset from eaddr (no instruction besides the
+            // read); in a slot that holds t_st, the one n-group that owns it picks the row per lane, the others take the side the
+            // slot leaves them (compile time where there is only one, else one scalar select and one add)
+            constexpr int I = decltype(ti)::value, NG = Tiling<MT, NT>::NG;
+            constexpr int t_lo = I * NG, t_hi = t_lo + NG - 1 < NT - 1 ? t_lo + NG - 1 : NT - 1;
+            constexpr int t_st = TV % 16 != 0 ? TV / 16 : -1;
+            constexpr unsigned HI = 4u * EMB_STRIDE;
+            if constexpr ((t_hi + 1) * 16 <= TV) {
+                return lds_load4(eaddr);
+            } else if constexpr (t_lo * 16 >= TV) {
+                return lds_load4(eaddr + HI);
+            } else if constexpr (t_st < t_lo || t_st > t_hi) {      // chain boundary on a tile boundary inside the slot
+                return lds_load4(eaddr + ((ng + t_lo) * 16 >= TV ? HI : 0u));
+            } else {
+                unsigned a = eaddr + (t_st == t_hi ? 0u : t_st == t_lo ? HI : ng > t_st - t_lo ? HI : 0u);
+                if (ng == t_st - t_lo) {
+                    a = eaddr + (col >= TV ? HI : 0u);
+                    asm volatile("" : "+v"(a));        // (keeps this a scalar branch, as below)
+                }
+                return lds_load4(a);
+            }
+        } else if constexpr (NB == 2) {
             const int tile_lo = (ng + decltype(ti)::value * Tiling<MT, NT>::NG) * 16;
             unsigned eo = tile_lo >= TV ? 4u * EMB_STRIDE : 0u;                          // scalar unit
             if (tile_lo < TV && tile_lo + 16 > TV) {                                      // the straddling tile: per lane
@@ -1289,16 +1330,16 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
         }
     };
     prof.trace(trs + 3);
-    if constexpr (EPRE) gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE>(afr, z, CSI, in, CSX, wave, lane, epi, 0, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f), emb_of);
-    else gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE>(afr, z, CSI, in, CSX, wave, lane, epi, 0, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f));
+    if constexpr (EPRE) gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE, FORCE, TSEL>(afr, z, CSI, in, CSX, wave, lane, epi, 0, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f), emb_of);
+    else gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE, FORCE, TSEL>(afr, z, CSI, in, CSX, wave, lane, epi, 0, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f));
 #pragma unroll
     for (int mi = 1; mi < Tiling<MT, NT>::MW; ++mi) {     // workgroups with fewer waves than m-tiles: next m-tile(s)
-        load_afrags<MT, KQ1 + KQ2>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr, mi);
+        load_afrags<MT, KQ1 + KQ2>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr, mi);
         bcur = load_global4(bias + ((wave + mi * NWAVES) % MT) * 16 + 4 * (lane >> 4));
         set_bases(mi);
         if constexpr (EHOIST) e_pre = lds_load4(eaddr);
-        if constexpr (EPRE) gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE>(afr, z, CSI, in, CSX, wave, lane, epi, mi, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f), emb_of);
-        else gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE>(afr, z, CSI, in, CSX, wave, lane, epi, mi, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f));
+        if constexpr (EPRE) gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE, FORCE, TSEL>(afr, z, CSI, in, CSX, wave, lane, epi, mi, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f), emb_of);
+        else gemm_tiles<MT, NT, KQ1, KQ2, !RES, FORCE, FORCE, TSEL>(afr, z, CSI, in, CSX, wave, lane, epi, mi, FOLD ? bcur : make_float4(0.f, 0.f, 0.f, 0.f));
     }
     prof.trace(trs + 4);
     pre_barrier();
@@ -1325,16 +1366,16 @@ template <int L, int T, int NB>
 using LMix = MixCoef<layer_desc(L).cin, layer_desc(L).V, T, NB>;
 template <int L>
 using LAfr = LayerAfr<(layer_desc(L).cin / 16) * (layer_desc(L).res ? 2 : 1)>;
-template <int L>
+template <int L, bool U32 = false>
 __device__ __forceinline__ void load_lafr(LAfr<L>& A, const float* wb, int wave, int lane) {
-    A.template load<ceil16(layer_desc(L).cout) / 16>(wb, layer_w(wb, L), wave, lane);
+    A.template load<ceil16(layer_desc(L).cout) / 16, U32>(wb, layer_w(wb, L), wave, lane);
 }
 template <int L, int T, int NB, bool FORCE = false, int CSX = cs_of(layer_desc(L).cin), class H1, class H2>
 __device__ __forceinline__ void layer_std(const float* wb, const LMix<L, T, NB>& mc, const float* in, float* z, float* out,
                                           const float* emb, int wave, int lane, Prof& prof, H1&& pre_gemm, H2&& pre_barrier,
                                           const LAfr<L>* pre_afr = nullptr) {
     constexpr LDesc D = layer_desc(L);
-    layer_generic<D.cin, D.cout, D.V, D.res != 0, true, T, NB, FORCE, CSX>(wb, layer_w(wb, L), mc, in, z, out, emb + emb_off(L), wave, lane,
+    layer_generic<D.cin, D.cout, D.V, D.res != 0, true, T, NB, FORCE, CSX, true>(wb, layer_w(wb, L), mc, in, z, out, emb + emb_off(L), wave, lane,
                                                                prof, 32 + 3 * L, pre_gemm, pre_barrier, pre_afr);
 }
 
@@ -1349,11 +1390,12 @@ __device__ __forceinline__ void layer_std(const float* wb, const LMix<L, T, NB>&
 struct EmbRow {              // W_e row + bias of one output channel
     float4 w[4];
     float b;
+    template <bool U32 = false>
     __device__ __forceinline__ void load(const float* wb, int o) {
-        const float* we = wb + tab_i(wb, TAB_WE);
+        const float* we = wptr<U32>(wb, tab_i(wb, TAB_WE));
 #pragma unroll
         for (int q = 0; q < 4; ++q) w[q] = load_global4(we + o * EDIM + 4 * q);
-        b = as_global(wb + tab_i(wb, TAB_BE))[o];
+        b = as_global(wptr<U32>(wb, tab_i(wb, TAB_BE)))[o];
     }
 };
 // se: SiLU(pe + cond) [NB][16] in LDS; emb: EMB[n][536] (layers 0..9); e10: layer 10's outputs [n][4]

@@ -175,6 +175,10 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     // loop): +1.1 %; 3 frames -5 %, 5 frames +0.3 % (profiles/r05u_lowocc4_ab.txt).  Round 6 took it out again: with layer 8 W-first,
     // the single-read mixes and the swapped-operand fragments in, the plain forms are +1.2 .. 1.4 % there (profiles/r06j_switch_sweep_ab.txt)
     constexpr bool LOWO = MINW <= (NWAVES == 12 ? 3 : 2);
+    // TSEL (3 frames x 2 chains, as in layer_generic): per-tile tests that depend on the tile SLOT alone are made at compile time --
+    // a W-first GEMM's pad-column test (only the slot that holds the last real column keeps it) and gemm_tiles' SLOTK -- and the
+    // step loop forms its weight pointers from 32-bit byte offsets (wptr)
+    constexpr bool TSEL = T == 3 && NB == 2;
 
     const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
     const int i_last = P.mode == 1 ? P.step_single : 1;
@@ -319,8 +323,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
 #endif
         // Every stage issues the coefficient loads of the stage after it (mcN = mix rows / fragments of layer N,
         // rcX = resampler fragments) before its own closing barrier, so no stage starts with an L2 round trip.
-        auto mixload = [&](auto& mc, int l) { mc.load(wb + tab_i(wb, l * F_STRIDE + F_TQ), wb + tab_i(wb, l * F_STRIDE + F_AM), wave, lane); };
-        auto rsload = [&](auto& rc, int r) { rc.load(wb + tab_i(wb, TAB_RSW + r), wb + tab_i(wb, TAB_RSB + r), lane); };
+        auto mixload = [&](auto& mc, int l) { mc.load(wptr<TSEL>(wb, tab_i(wb, l * F_STRIDE + F_TQ)), wptr<TSEL>(wb, tab_i(wb, l * F_STRIDE + F_AM)), wave, lane); };
+        auto rsload = [&](auto& rc, int r) { rc.load(wptr<TSEL>(wb, tab_i(wb, TAB_RSW + r)), wptr<TSEL>(wb, tab_i(wb, TAB_RSB + r)), lane); };
         auto mix_early = mixload;
         auto rs_early = rsload;
         NoHook nohook;
@@ -335,7 +339,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         // columns' coordinates -- finite, and multiplied by the zero-padded K rows of the layer's weights -- so no 16-channel
         // copy of x has to be zeroed and rewritten every pass
         LAfr<1> A1; LAfr<2> A2; LAfr<3> A3; LAfr<4> A4; LAfr<5> A5; LAfr<7> A7; LAfr<9> A9;
-        auto wearly = [&](auto& A, auto lc) { if constexpr (WEARLY) load_lafr<decltype(lc)::value>(A, wb, wave, lane); };
+        auto wearly = [&](auto& A, auto lc) { if constexpr (WEARLY) load_lafr<decltype(lc)::value, TSEL>(A, wb, wave, lane); };
 #define MCD_LC(l) std::integral_constant<int, l>{}
         layer_std<0, T, NB, LOWO, 4>(wb, mc0, XT, RG + PL::L0_z, RG + PL::L0_out, EMB, wave, lane, prof,
                             [&] { mix_early(mc1, 1); }, [&] { wearly(A1, MCD_LC(1)); }, WEARLY ? &A0 : nullptr);     // sp1a (2 -> 16)
@@ -401,30 +405,31 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             MixCoef<64, 10, T, NB> mc6;
             layer_std<5, T, NB, LOWO>(wb, mc5, RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, EMB, wave, lane, prof, nohook,
                                 [&] {
-                                    load_afrags<8, 8>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr, 0);
-                                    if constexpr (EARLY2) mc6.load(wb + lw.tq, wb + lw.am, wave, lane);
+                                    load_afrags<8, 8>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr, 0);
+                                    if constexpr (EARLY2) mc6.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
                                 }, WEARLY ? &A5 : nullptr);  // sd3.0
             STAGE(9);
             lt_dump(5, RG + PL::L5_out, 132, 128, 10);
             lt_inject(6, RG + PL::L6_in, 132, 128, 10);
             float* Pb = RG + PL::L6_p;
-            if constexpr (!EARLY2) mc6.load(wb + lw.tq, wb + lw.am, wave, lane);
+            if constexpr (!EARLY2) mc6.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
             auto epi6 = [&](auto ti, int col, int c0, f32x4 acc, int col0, int) {
                 constexpr int STEP = Tiling<8, NT>::NG * 16 * 132;
-                if (col < COLS) *reinterpret_cast<float4*>(Pb + __mul24(col0, 132) + c0 + decltype(ti)::value * STEP) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                constexpr bool FULL = TSEL && (decltype(ti)::value + 1) * Tiling<8, NT>::NG * 16 <= COLS;      // no pad column in any n-group's tile of this slot
+                if (FULL || col < COLS) *reinterpret_cast<float4*>(Pb + __mul24(col0, 132) + c0 + decltype(ti)::value * STEP) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             };
-            gemm_tiles<8, NT, 8, 0, false, LOWO>(afr, RG + PL::L6_in, 132, RG + PL::L6_in, 132, wave, lane, epi6, 0);
+            gemm_tiles<8, NT, 8, 0, false, LOWO, LOWO, TSEL>(afr, RG + PL::L6_in, 132, RG + PL::L6_in, 132, wave, lane, epi6, 0);
 #pragma unroll
             for (int mi = 1; mi < Tiling<8, NT>::MW; ++mi) {
-                load_afrags<8, 8>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr, mi);
-                gemm_tiles<8, NT, 8, 0, false, LOWO>(afr, RG + PL::L6_in, 132, RG + PL::L6_in, 132, wave, lane, epi6, mi);
+                load_afrags<8, 8>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr, mi);
+                gemm_tiles<8, NT, 8, 0, false, LOWO, LOWO, TSEL>(afr, RG + PL::L6_in, 132, RG + PL::L6_in, 132, wave, lane, epi6, mi);
             }
             if constexpr (EARLY2) { rs_early(rc3, 2); mix_early(mc7, 7); }      // up3's fragments, layer 7's mix coefficients
             bsync();
             STAGE(10);
             const float slope6 = lw.slope;
             const float pinf6 = prelu_bound(slope6);
-            mix_stage<64, 10, T, NB, LOWO, true>(Pb, 132, mc6, wb + lw.tq, wb + lw.am, wave, lane,
+            mix_stage<64, 10, T, NB, LOWO, true>(Pb, 132, mc6, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                                      [&](int n, int q, int w, ChIdx c) {   // P_r of joint w, the lane's 4 channels: one ds_read_b128
                                          // (address: the unit's part on the scalar unit + one v_mad for the lane's, see mix_stage;
                                          // joints >= 10 read the next frame's rows -- inside the 64-column region -- and are never stored)
@@ -493,30 +498,31 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             MixCoef<32, 12, T, NB> mc8w;
             layer_std<7, T, NB, LOWO>(wb, mc7, RG + PL::L7_in, RG + PL::L7_z, RG + PL::L7_out, EMB, wave, lane, prof, nohook,
                                 [&] {
-                                    load_afrags<4, 4>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr8, 0);
-                                    if constexpr (EARLY2) mc8w.load(wb + lw.tq, wb + lw.am, wave, lane);
+                                    load_afrags<4, 4>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr8, 0);
+                                    if constexpr (EARLY2) mc8w.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
                                 }, WEARLY ? &A7 : nullptr);     // su4.0
             STAGE(13);
             lt_dump(7, RG + PL::L7_out, 68, 64, 12);
             lt_inject(8, RG + PL::L8_in, 68, 64, 12);
             float* Pb = RG + PL::L8_p;
-            if constexpr (!EARLY2) mc8w.load(wb + lw.tq, wb + lw.am, wave, lane);
+            if constexpr (!EARLY2) mc8w.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
             auto epi8 = [&](auto ti, int col, int c0, f32x4 acc, int col0, int) {
                 constexpr int STEP = Tiling<4, NT>::NG * 16 * 68;
-                if (col < COLS) *reinterpret_cast<float4*>(Pb + __mul24(col0, 68) + c0 + decltype(ti)::value * STEP) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+                constexpr bool FULL = TSEL && (decltype(ti)::value + 1) * Tiling<4, NT>::NG * 16 <= COLS;
+                if (FULL || col < COLS) *reinterpret_cast<float4*>(Pb + __mul24(col0, 68) + c0 + decltype(ti)::value * STEP) = make_float4(acc[0], acc[1], acc[2], acc[3]);
             };
-            gemm_tiles<4, NT, 4, 0, false, LOWO>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, 0);
+            gemm_tiles<4, NT, 4, 0, false, LOWO, LOWO, TSEL>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, 0);
 #pragma unroll
             for (int mi = 1; mi < Tiling<4, NT>::MW; ++mi) {
-                load_afrags<4, 4>(reinterpret_cast<const float4*>(wb + lw.wp), wave, lane, afr8, mi);
-                gemm_tiles<4, NT, 4, 0, false, LOWO>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, mi);
+                load_afrags<4, 4>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr8, mi);
+                gemm_tiles<4, NT, 4, 0, false, LOWO, LOWO, TSEL>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, mi);
             }
             if constexpr (EARLY2) { rs_early(rc4, 3); mix_early(mc9, 9); }      // up2's fragments, layer 9's mix coefficients
             bsync();
             prof.mark(32 + 3 * 8 + 1);                                          // (the tool's "gemm" column of layer 8)
             const float slope8 = lw.slope;
             const float pinf8 = prelu_bound(slope8);
-            mix_stage<32, 12, T, NB, LOWO, true>(Pb, 68, mc8w, wb + lw.tq, wb + lw.am, wave, lane,
+            mix_stage<32, 12, T, NB, LOWO, true>(Pb, 68, mc8w, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                                      [&](int n, int q, int w, ChIdx c) {   // P_r of joint w, the lane's 4 channels (w >= 12: the next frame's rows, inside the region, never stored)
                                          const float* pp = (Pb + (n * (T * 12) * 68 + q * (12 * 68) + 32 + c.cb16)) + (__mul24(w, 68) + c.j);
                                          const float4 r = lds_load4(lds_addr(pp));
@@ -554,10 +560,10 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             // next pass's embedding rows.  Unconditional (after the last pass the result is simply unused): a
             // conditionally loaded register struct costs ~35 VGPRs of phi copies here.
             EmbRow ef;
-            auto ef_load = [&] { ef.load(wb, tid); };
+            auto ef_load = [&] { ef.template load<TSEL>(wb, tid); };
             layer_std<9, T, NB, LOWO>(wb, mc9, RG + PL::L9_in, RG + PL::L9_z, RG + PL::L9_out, EMB, wave, lane, prof,
                                 [&] {
-                                    mc10.load(wb + lw.tq, wb + lw.am, wave, lane);
+                                    mc10.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
                                     ef_load();
                                 }, nohook, WEARLY ? &A9 : nullptr);                                      // su3.0
             STAGE(16);
@@ -570,7 +576,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             // of 64 columns), weights as scalar operands.
             {
                 const int r = wave & 3;
-                const cfloat* w4 = (const cfloat*)(wb + lw.wp + r * 32);
+                const cfloat* w4 = (const cfloat*)(wptr<TSEL>(wb, lw.wp) + r * 32);
                 for (int cblk = wave >> 2; cblk * 64 < COLS17; cblk += NWAVES / 4) {
                     const int col = cblk * 64 + lane;
                     if (col < COLS17) {
@@ -597,7 +603,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             const float slope10 = lw.slope;
             const bool single = P.mode == 1, zadd = sidx > 1;
             const int e10_off = (sidx & 1) * 16;
-            mix_stage<16, 17, T, NB, LOWO, true>(Pb, 20, mc10, wb + lw.tq, wb + lw.am, wave, lane,
+            mix_stage<16, 17, T, NB, LOWO, true>(Pb, 20, mc10, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                                      ZeroInit{},
                                      [&](int n, int t, int w, ChIdx c, auto val) {
                                          if constexpr (std::is_same_v<decltype(val), f32x4>) {     // joint w, channels c.j .. c.j + 3: the two coordinates are lane group 0's
@@ -650,7 +656,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
 #pragma unroll
             for (int it = 0; it < TAIL_IT; ++it)
                 if (dst_t[it] >= 0) XT[dst_t[it]] = xn_t[it];
-            mc0.load(wb + tab_i(wb, F_TQ), wb + tab_i(wb, F_AM), wave, lane);      // for the next pass
+            mc0.load(wptr<TSEL>(wb, tab_i(wb, F_TQ)), wptr<TSEL>(wb, tab_i(wb, F_AM)), wave, lane);      // for the next pass
             wearly(A0, MCD_LC(0));
             STAGE(21);
             bsync();
