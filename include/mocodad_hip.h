@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 10
+#define MCD_ABI_VERSION 11
 
 enum {
     MCD_OK = 0,
@@ -103,6 +103,8 @@ void mcd_free_weights(mcd_weights_t* w);
 
 /* Replaces: MoCoDAD._encode_condition -> STSAE/STSE.encode (mocodad.py:546-560, stsae.py:59-92).
  * cond_data (B,C,t_cond,V) -> emb_out (B,emb_dim).  The AE decoder (dead work at eval) is not run.
+ * Windows are independent (ABI version 11, see mcd_score): a window with non-finite poses, or whose encoding overflows, gets
+ * the non-finite embedding it gets as the only window of a call and changes no bit of any other window's.
  * (A test / diagnostic entry without a workspace argument: encoders that need scratch memory -- 'E_unet' above 12 condition
  * frames, the shipped encoder at 25 .. 31 (three 32-channel activation buffers no longer fit LDS) -- return MCD_EUNSUPPORTED here and run inside mcd_score / mcd_score_fused.) */
 int mcd_cond_encode(const mcd_weights_t* w, const float* cond_data, int32_t n_windows, float* emb_out,
@@ -205,8 +207,11 @@ int mcd_set_option(mcd_weights_t* w, int32_t option, int32_t value);
  *   pose_out    NULL or (B,S,C,Tx,V) generated x_0
  * Chains are independent, as in the reference: a chain that diverges (NaN / Inf activations; a NaN in `noise`) returns a
  * non-finite loss and changes no other chain's result -- the persistent kernels clear their state behind it and re-run the
- * chains that shared its passes on their own.  PRECONDITION: `data` is finite.  (A window with non-finite poses scores NaN, as
- * in the reference, but can take the other windows of its workgroup -- up to 4 neighbours in the batch -- with it.) */
+ * chains that shared its passes on their own.  Windows are independent as well (ABI version 11): a window with a NaN / Inf
+ * pose, or whose condition encoding overflows, yields what it yields as the only window of a call -- non-finite per-sample
+ * losses, as in the reference; under `inject` a NaN in a corrupt frame alone leaves pose_out finite -- and every other window's
+ * losses, aggregated loss and poses are bit-identical to the same call without it, however the batch is cut into workgroups
+ * (mcd_score_view and mcd_score_fused alike).  The call after such a call starts clean. */
 int mcd_score(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const float* noise,
               uint64_t seed, int64_t first_window_id, const float* step_table, void* workspace,
               float* loss_out, float* pose_out, void* stream);
@@ -420,7 +425,9 @@ int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value
  * index lists; data / view as for mcd_score_view -> cond_emb_out (B,16), z0_out (B,D).  One launch for the shipped
  * configuration, two otherwise (three with the gather of a runtime channel list), one more at t_unet 5 .. 12 (the projection); the
  * gather buffer of such an encoder and H of such a frame count come from the stream-ordered allocator (hipMallocAsync /
- * hipFreeAsync on `stream`) because this entry has no workspace argument. */
+ * hipFreeAsync on `stream`) because this entry has no workspace argument.
+ * Windows are independent (ABI version 11, see mcd_score): a non-finite pose in a condition frame (cond_emb and z0) or in a
+ * corrupt frame (z0 alone) stays with its window; every other window's cond_emb and z0 are bit-identical to the call without it. */
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                       const float* step_table, float* cond_emb_out, float* z0_out, void* stream);
 
@@ -440,7 +447,9 @@ int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const floa
  *   loss_all (B,S), latent_all (B,S,D) generated latents, latent_code (B,D) = z0: optional outputs (NULL = not wanted)
  * cfg->loss_fn is applied to (generated latent, z0) and averaged over D.  1 .. 1024 samples per call.  Chains are independent:
  * one whose state becomes non-finite returns a non-finite loss and changes no other chain's result; `best` / `worst` skip it
- * like the reference's strict comparisons do. */
+ * like the reference's strict comparisons do.  Windows are independent too (ABI version 11, see mcd_score and
+ * mcd_latent_encode): a window with non-finite poses has non-finite losses, and no other window's losses, latents or code
+ * change by a bit. */
 int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                      const float* noise, uint64_t seed, int64_t first_window_id, const float* step_table, void* workspace,
                      int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,

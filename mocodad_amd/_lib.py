@@ -15,7 +15,7 @@ COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
 LATENT_OPT = {"split_encode": 0}     # MCD_LATENT_OPT_*
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class Tensor(C.Structure):

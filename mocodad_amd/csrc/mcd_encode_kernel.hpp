@@ -15,16 +15,65 @@ constexpr int TABC_URS = 56;               // down1 / down2 fragments + bias: 4 
 constexpr int TABC_ULW = 60, TABC_ULB = 61;  // to_time_dim weight [16][6*T*10] / bias
 constexpr int CU_OUT = 6;                  // unet_down_channels[6] of STSE_Unet
 
+// ------------------------------------------------------------------------------------------------
+// Window isolation: the NB windows of a workgroup are columns of the same MFMA tiles, and the padded k-steps of the
+// mixes and resamplers read the NEXT window's rows against zero coefficients -- NaN x 0 = NaN, so a window with a non-finite pose
+// (or whose encoding overflows) reaches its neighbours' results, where the reference's windows are independent
+// (mocodad.py:155-180).  A window's columns never see a neighbour's FINITE values, so: every encoder below runs its windows
+// jointly, tests the joint RESULT once (the NB x 16 embeddings, a flag per window set by the threads that store z0), and behind a
+// result that is not finite runs again once per such window ALONE (`solo`: the other slots load zeros and store nothing) on a
+// region cleared again.  A finite window gets the bits of the joint run back; a non-finite one what it yields as the only window
+// of a call.  Slots past the end of the batch repeat the last window, are never tested and never run alone.
+// The solo runs are a second, cold instance of the same functions (OPAQUE = true: thread id and weight pointer are made opaque
+// per run, or every per-lane address of the pass is hoisted in front of the loop and kept live -- as in score_kernel's step
+// loop); the joint run keeps the straight-line text it had, plus the test.  score_kernel's prologue, where a second instance of
+// cond_fast_body would double the trajectory kernels' encoder text, loops over the opaque one instead.
+// (Which stages do it: the 12- / 10-joint mixes and the resamplers of the down path -- cond_unet_kernel, latent_encode_kernel.  A
+// 17-joint mix does not: its trailing k-step holds joint 16 alone and every lane group reads that joint again, mix_stage's load_x --
+// so cond_fast_body's four 17-joint layers cannot leak as they stand; its result is tested all the same, so that the guarantee
+// does not rest on that detail of the mix.)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.0e38f); }
+// the barrier between the joint run's last stores and the test: behind the workgroup's LDS traffic (the flags) alone -- nothing
+// here needs the results just stored to global memory to have arrived, which __syncthreads(), a release fence as well, waits for
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// the first slot behind `solo` of the workgroup's windows b0 .. whose 16 embeddings ce[n][16] (LDS) are not all finite; -1: none.
+// Every thread reads the same words: the answer is uniform.
+template <int NB>
+__device__ __forceinline__ int next_nonfinite_slot(const float* ce, int solo, int b0, int B) {
+    int nxt = -1;
+#pragma unroll
+    for (int n = NB - 1; n >= 0; --n) {
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < EDIM; ++k) bad |= not_finite(ce[n * EDIM + k]);
+        if (bad && n > solo && b0 + n < B) nxt = n;
+    }
+    return __builtin_amdgcn_readfirstlane(nxt);
+}
+// ... the same from one flag per slot (set while the joint run stored its results)
+template <int NB>
+__device__ __forceinline__ int next_flagged_slot(const int* bad, int solo) {
+    int nxt = -1;
+#pragma unroll
+    for (int n = NB - 1; n >= 0; --n)
+        if (bad[n] && n > solo) nxt = n;
+    return __builtin_amdgcn_readfirstlane(nxt);
+}
+
 // condition / corrupt frames of windows b0 .. b0 + NB - 1 -> dst[col = (n,t,v)][20], channels 0, 1; frame_of(t) = data frame of
-// frame t.  A window past the end repeats the last one.
-template <int T, int NB, class FrameOf>
-__device__ __forceinline__ void load_window_frames(float* dst, const DataView& dv, FrameOf&& frame_of, int seg_len, int b0, int B) {
+// frame t.  A window past the end repeats the last one.  solo >= 0: that slot alone, the others hold zeros.
+template <int T, int NB, bool OPAQUE = false, class FrameOf>
+__device__ __forceinline__ void load_window_frames(float* dst, const DataView& dv, FrameOf&& frame_of, int seg_len, int b0, int B, int solo = -1) {
     constexpr int TV = T * 17, COLS = NB * TV;
-    for (int u = threadIdx.x; u < COLS * C0; u += NTHREADS) {
+    int tid = threadIdx.x;
+    if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+    for (int u = tid; u < COLS * C0; u += NTHREADS) {
         const int c = u % C0, col = u / C0;
         const int n = col / TV, t = (col / 17) % T, v = col % 17;
         const int b = b0 + n < B ? b0 + n : B - 1;
-        dst[col * 20 + c] = load_coord(dv, b, c, frame_of(t), v, seg_len);
+        dst[col * 20 + c] = (NB == 1 || solo < 0 || n == solo) ? load_coord(dv, b, c, frame_of(t), v, seg_len) : 0.f;
     }
 }
 
@@ -67,10 +116,12 @@ __device__ __forceinline__ void unet_down_path(const float* wb, const float* tab
 // together -- with the data-dependent bound `tv + part < TV` every load waited for the FMA before it (one L2 round trip per
 // element: 100 .. 400 of them per thread, the whole encoder's time).  An output is one fmaf chain in c-then-i order per part, the
 // 16-lane sum, then the bias.
-template <int C, int CS, int TV, int NB, bool SHARE_W, int UNROLL, class Store>
+template <int C, int CS, int TV, int NB, bool SHARE_W, int UNROLL, bool OPAQUE = false, class Store>
 __device__ __forceinline__ void flatten_linear(const float* H, gfloat* W, gfloat* bias, int n_out, Store&& store) {
     constexpr int F = C * TV, NT16 = (TV + 15) / 16, NW = SHARE_W ? NB : 1;
-    for (int u = threadIdx.x; u < (NB / NW) * n_out * 16; u += NTHREADS) {
+    int tid = threadIdx.x;
+    if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+    for (int u = tid; u < (NB / NW) * n_out * 16; u += NTHREADS) {
         const int part = u & 15, jo = SHARE_W ? u >> 4 : (u >> 4) % n_out, n0 = SHARE_W ? 0 : u / (16 * n_out);
         float a[NW];
 #pragma unroll
@@ -109,12 +160,13 @@ struct CondFastLds {     // cond_fast_body's region: X0, Z0 [P17][20] | Y0, Z1 [
 
 // body shared by cond_fast_kernel, the trajectory kernel's prologue (P.cond_inkernel) and the latent encode launch: windows
 // b0 .. b0 + NB - 1, frame_of(t) = data frame of condition frame t; the embeddings go to emb_lds[n][16] (LDS) and / or emb_out (B,16).
-// smem: CondFastLds<T, NB>::FLOATS floats, zeroed by the caller.
+// smem: CondFastLds<T, NB>::FLOATS floats, zeroed by the caller.  solo >= 0: that slot alone (window isolation, above) -- the other
+// slots load zeros and store nothing; OPAQUE: the instance a caller runs in a loop.
 // Its loader and tail are its own copies of load_window_frames / flatten_linear<32, 36, T * 17, NB, false, 4>: the body is inlined
 // into every score_kernel row, and the trajectory kernels' text does not move for a refactor.
-template <int T, int NB, class FrameOf>
+template <int T, int NB, bool OPAQUE = false, class FrameOf>
 __device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView& dv, FrameOf&& frame_of, int seg_len, float* smem,
-                                               int b0, int B, float* emb_lds, float* __restrict__ emb_out) {
+                                               int b0, int B, float* emb_lds, float* __restrict__ emb_out, int solo = -1) {
     constexpr int P17 = ceil16(NB * T * 17);
     constexpr int s16 = P17 * 20, s32 = P17 * 36;
     constexpr int TV = T * 17, COLS = NB * TV;
@@ -123,7 +175,9 @@ __device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView
     float* const Y0 = smem + 2 * s16;         // [P17][36]  out of layers 0, 2 ; in of layers 1, 3
     float* const Z1 = smem + 2 * s16 + s32;   // [P17][36]
     float* const H = smem;                    // [P17][36]  out of layer 3 (over X0/Z0: 36 <= 40)
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     Prof prof;
     prof.off();
@@ -131,10 +185,11 @@ __device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView
         const int c = u % C0, col = u / C0;
         const int n = col / TV, t = (col / 17) % T, v = col % 17;
         const int b = b0 + n < B ? b0 + n : B - 1;
-        X0[col * 20 + c] = load_coord(dv, b, c, frame_of(t), v, seg_len);
+        X0[col * 20 + c] = (NB == 1 || solo < 0 || n == solo) ? load_coord(dv, b, c, frame_of(t), v, seg_len) : 0.f;
     }
     bsync();
     const float* wb = wbuf;
+    if constexpr (OPAQUE) asm volatile("" : "+s"(wb));
     layer_generic<16, 32, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 0), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 2(16) -> 32
     layer_generic<32, 16, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 1), Y0, Z1, X0, nullptr, wave, lane, prof, 0);   // 32 -> 16
     layer_generic<16, 32, 17, true, false, T, NB>(wb, layer_w(wb + TABC, 2), X0, Z0, Y0, nullptr, wave, lane, prof, 0);   // 16 -> 32
@@ -158,7 +213,7 @@ __device__ __forceinline__ void cond_fast_body(const float* wbuf, const DataView
             for (int i = 0; i < NT16; ++i) a = fmaf(wv[i], (i * 16 + part < TV) ? hr[i * 16 * 36 + c] : 0.f, a);
         }
         a = row16_sum(a);
-        if (part == 0) {
+        if (part == 0 && (NB == 1 || solo < 0 || n == solo)) {
             const float e = a + bb[jo];
             if (emb_lds) emb_lds[n * EDIM + jo] = e;
             if (emb_out && b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + jo] = e;
@@ -170,9 +225,20 @@ template <int T, int NB>
 __global__ __launch_bounds__(NTHREADS, 2) void cond_fast_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
                                                                 int seg_len, float* __restrict__ emb_out, int B) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int b0 = blockIdx.x * NB;
+    __shared__ float CE[NB > 1 ? NB * EDIM : 1];      // the embeddings once more in LDS, for the isolation test (unused with one window)
     for (int u = threadIdx.x; u < CondFastLds<T, NB>::FLOATS; u += NTHREADS) smem[u] = 0.f;
     __syncthreads();
-    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return fi.idx[t]; }, seg_len, smem, blockIdx.x * NB, B, nullptr, emb_out);
+    cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return fi.idx[t]; }, seg_len, smem, b0, B, NB > 1 ? CE : nullptr, emb_out);
+    if constexpr (NB > 1) {      // window isolation (top of this file): every window whose embedding is not finite, alone
+        lds_barrier();
+        for (int solo = next_nonfinite_slot<NB>(CE, -1, b0, B); solo >= 0; solo = next_nonfinite_slot<NB>(CE, solo, b0, B)) {
+            for (int u = threadIdx.x; u < CondFastLds<T, NB>::FLOATS; u += NTHREADS) smem[u] = 0.f;
+            __syncthreads();
+            cond_fast_body<T, NB, true>(wbuf, dv, [&](int t) { return fi.idx[t]; }, seg_len, smem, b0, B, CE, emb_out, solo);
+            __syncthreads();
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -191,31 +257,54 @@ struct CondUnetLds : DownPathLds<T, NB> {
     static constexpr int FLOATS = DownPathLds<T, NB>::work(20);
 };
 
-template <int T, int NB>
-__global__ __launch_bounds__(NTHREADS, 2) void cond_unet_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
-                                                                int seg_len, float* __restrict__ emb_out, int B) {
+// one run of the encoder over the workgroup's region: all windows (solo < 0; the joint run raises bad[n] for a window whose result
+// is not finite) or window `solo` alone
+template <int T, int NB, bool OPAQUE>
+__device__ __forceinline__ void cond_unet_pass(const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len,
+                                               float* __restrict__ emb_out, int b0, int B, float* smem, int* bad, int solo) {
     using PL = Plan<T, NB>;
     using LD = CondUnetLds<T, NB>;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const RG = smem;
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = blockIdx.x * NB;
     Prof prof;
     prof.off();
     for (int u = tid; u < LD::FLOATS; u += NTHREADS) smem[u] = 0.f;
     __syncthreads();
-    load_window_frames<T, NB>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B);
+    load_window_frames<T, NB, OPAQUE>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B, solo);
     __syncthreads();
     const float* wb = wbuf;
+    if constexpr (OPAQUE) asm volatile("" : "+s"(wb));
     unet_down_path<T, NB, false>(wb, wb + TABC, RsWords{TABC + TABC_URS + 0, TABC + TABC_URS + 1, TABC + TABC_URS + 2, TABC + TABC_URS + 3},
                                  RG, nullptr, wave, lane, prof);
     layer_generic<128, 16, 10, true, false, T, NB>(wb, layer_w(wb + TABC, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, nullptr, wave, lane, prof, 0);
     // to_time_dim: emb[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v
-    flatten_linear<CU_OUT, 20, T * 10, NB, false, CU_OUT>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TABC + TABC_ULW)),
-                                                          as_global(wb + tab_i(wb, TABC + TABC_ULB)), EDIM, [&](int n, int j, float e) {
-        if (b0 + n < B) emb_out[(size_t)(b0 + n) * EDIM + j] = e;
+    flatten_linear<CU_OUT, 20, T * 10, NB, false, CU_OUT, OPAQUE>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TABC + TABC_ULW)),
+                                                                  as_global(wb + tab_i(wb, TABC + TABC_ULB)), EDIM, [&](int n, int j, float e) {
+        if (b0 + n < B && (solo < 0 || n == solo)) {
+            emb_out[(size_t)(b0 + n) * EDIM + j] = e;
+            if (NB > 1 && solo < 0 && not_finite(e)) bad[n] = 1;
+        }
     });
+}
+
+template <int T, int NB>
+__global__ __launch_bounds__(NTHREADS, 2) void cond_unet_kernel(const float* wbuf, const DataView dv, const FrameIdx fi,
+                                                                int seg_len, float* __restrict__ emb_out, int B) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int b0 = blockIdx.x * NB;
+    __shared__ int BAD[NB];      // window isolation (top of this file): slot n's joint result is not finite
+    if (NB > 1 && threadIdx.x < NB) BAD[threadIdx.x] = 0;      // (the pass's barriers lie before the first store)
+    cond_unet_pass<T, NB, false>(wbuf, dv, fi, seg_len, emb_out, b0, B, smem, BAD, -1);
+    if constexpr (NB > 1) {
+        lds_barrier();
+        for (int solo = next_flagged_slot<NB>(BAD, -1); solo >= 0; solo = next_flagged_slot<NB>(BAD, solo)) {
+            cond_unet_pass<T, NB, true>(wbuf, dv, fi, seg_len, emb_out, b0, B, smem, BAD, solo);
+            __syncthreads();
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -233,7 +322,8 @@ template <int T, int NB, bool PROJECT_IN_KERNEL = true>
 struct LatentEncLds : DownPathLds<T, NB> {
     static constexpr int WORK = cmax(DownPathLds<T, NB>::work(PROJECT_IN_KERNEL ? 68 : 36), CondFastLds<T, NB>::FLOATS);
     static constexpr int EMB = NB * EMB_STRIDE;
-    static constexpr int FLOATS = WORK + EMB + 2 * NB * EDIM;    // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
+    static constexpr int FLAGS = WORK + EMB + 2 * NB * EDIM;     // + cond_emb [NB][16] + SiLU(pe + cond_emb) [NB][16]
+    static constexpr int FLOATS = FLAGS + 4;                     // + one word per window: its joint z0 is not finite (window isolation)
 };
 
 // COND_IN_KERNEL = false (the three-launch form: any other condition encoder, 1 .. 12 condition frames): a condition-encoder
@@ -241,43 +331,35 @@ struct LatentEncLds : DownPathLds<T, NB> {
 // launch of its own; the prologue is skipped, CE is read from there and the remainder is the same code.
 // PROJECT_IN_KERNEL = false (5 .. 12 corrupt frames): no to_time_dim tail; z0_out is H (B, 640 T), the last layer's output of window b
 // at H[b][(t 10 + v) 64 + c] -- the order the LDS holds, so the copy is 16-byte stores -- for latent_project_kernel.
-template <int T, int NB, bool COND_IN_KERNEL = true, bool PROJECT_IN_KERNEL = true>
-__global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
-                                                                    const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
-                                                                    float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
+// one run of everything behind cond_emb -- embedding rows, down path, last layer, to_time_dim (or the copy of H) -- over the
+// workgroup's region: all windows (solo < 0; the joint run raises bad[n] for a window whose z0 is not finite) or window `solo`
+// alone, the other slots on zero poses and bias-only embedding rows
+template <int T, int NB, bool PROJECT_IN_KERNEL, bool OPAQUE>
+__device__ __forceinline__ void latent_down_pass(const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len,
+                                                 const float* __restrict__ pe_row, float* __restrict__ z0_out, int D, int b0, int B,
+                                                 float* smem, int* bad, int solo) {
     using PL = Plan<T, NB>;
     using LD = LatentEncLds<T, NB, PROJECT_IN_KERNEL>;
     constexpr int TV10 = T * 10;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const RG = smem;
     float* const EMB = smem + LD::WORK;
     float* const CE = EMB + LD::EMB;
     float* const SEN = CE + NB * EDIM;
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    if constexpr (OPAQUE) asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b0 = blockIdx.x * NB;
     Prof prof;
     prof.off();
-    if constexpr (COND_IN_KERNEL) {
-        for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
-        __syncthreads();
-        cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
-        __syncthreads();
-    } else {
-        if (tid < NB * EDIM) {
-            const int n = tid / EDIM, b = b0 + n < B ? b0 + n : B - 1;      // (a window past the end repeats the last one, as load_window_frames)
-            CE[tid] = cond_out[(size_t)b * EDIM + tid % EDIM];
-        }
-        __syncthreads();
-    }
     const float* wb = wbuf;
+    if constexpr (OPAQUE) asm volatile("" : "+s"(wb));
     if (tid < NB * EDIM) {
         const float e = pe_row[tid % EDIM] + CE[tid];
-        SEN[tid] = e / (1.f + expf(-e));
+        SEN[tid] = (solo >= 0 && tid / EDIM != solo) ? 0.f : e / (1.f + expf(-e));
     }
     for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
     __syncthreads();
-    load_window_frames<T, NB>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B);
+    load_window_frames<T, NB, OPAQUE>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B, solo);
     {
         gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
         gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
@@ -320,10 +402,58 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float*
     }
     layer_generic<128, 64, 10, true, true, T, NB>(wb, layer_w(wb, 6), RG + PL::L6_in, RG + PL::L6_p, RG + LD::H_OFF, EMB + emb_off(6), wave, lane, prof, 0);
     // to_time_dim: z0[n][j] = b[j] + sum_k W[j][k] H[n][k], k = c*T*10 + t*10 + v; a thread serves every window of the workgroup
-    flatten_linear<LAT_ENC_C, 68, TV10, NB, true, 4>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TAB_LAT_LW)), as_global(wb + tab_i(wb, TAB_LAT_LB)),
-                                                     D, [&](int n, int j, float z) {
-        if (b0 + n < B) z0_out[(size_t)(b0 + n) * D + j] = z;
+    flatten_linear<LAT_ENC_C, 68, TV10, NB, true, 4, OPAQUE>(RG + LD::H_OFF, as_global(wb + tab_i(wb, TAB_LAT_LW)), as_global(wb + tab_i(wb, TAB_LAT_LB)),
+                                                             D, [&](int n, int j, float z) {
+        if (b0 + n < B && (solo < 0 || n == solo)) {
+            z0_out[(size_t)(b0 + n) * D + j] = z;
+            if (NB > 1 && solo < 0 && not_finite(z)) bad[n] = 1;
+        }
     });
+}
+
+template <int T, int NB, bool COND_IN_KERNEL = true, bool PROJECT_IN_KERNEL = true>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float* wbuf, const DataView dv, const FrameIdx cond_fi,
+                                                                    const FrameIdx fi, int seg_len, const float* __restrict__ pe_row,
+                                                                    float* __restrict__ cond_out, float* __restrict__ z0_out, int D, int B) {
+    using LD = LatentEncLds<T, NB, PROJECT_IN_KERNEL>;
+    static_assert(NB == 1 || PROJECT_IN_KERNEL, "the rows without the to_time_dim tail hold one window per workgroup: nothing tests their result");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const CE = smem + LD::WORK + LD::EMB;
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * NB;
+    if constexpr (COND_IN_KERNEL) {
+        for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+        __syncthreads();
+        cond_fast_body<T, NB>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out);
+        __syncthreads();
+    } else {
+        if (tid < NB * EDIM) {
+            const int n = tid / EDIM, b = b0 + n < B ? b0 + n : B - 1;      // (a window past the end repeats the last one, as load_window_frames)
+            CE[tid] = cond_out[(size_t)b * EDIM + tid % EDIM];
+        }
+        __syncthreads();
+    }
+    // Window isolation (top of this file), tested ONCE, on z0: a non-finite corrupt frame leaves cond_emb finite and reaches the
+    // neighbour's z0 through the shared down path; a cond_emb that is not finite -- its window's own, or (were a condition-encoder
+    // stage to hand it on) a neighbour's -- makes that window's embedding rows and with them its z0 non-finite as well.  So no
+    // second test sits between the two phases, where it cost the launch 1.1 % (profiles/nonfinite_windows.txt); a flagged window
+    // runs BOTH again alone, the condition encoder first.
+    int* const BAD = reinterpret_cast<int*>(smem + LD::FLAGS);
+    if (NB > 1 && tid < NB) BAD[tid] = 0;      // (the pass's barriers lie before the first store)
+    latent_down_pass<T, NB, PROJECT_IN_KERNEL, false>(wbuf, dv, fi, seg_len, pe_row, z0_out, D, b0, B, smem, BAD, -1);
+    if constexpr (NB > 1) {
+        lds_barrier();
+        for (int solo = next_flagged_slot<NB>(BAD, -1); solo >= 0; solo = next_flagged_slot<NB>(BAD, solo)) {
+            if constexpr (COND_IN_KERNEL) {
+                for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+                __syncthreads();
+                cond_fast_body<T, NB, true>(wbuf, dv, [&](int t) { return cond_fi.idx[t]; }, seg_len, smem, b0, B, CE, cond_out, solo);
+                __syncthreads();
+            }
+            latent_down_pass<T, NB, PROJECT_IN_KERNEL, true>(wbuf, dv, fi, seg_len, pe_row, z0_out, D, b0, B, smem, BAD, solo);
+            __syncthreads();
+        }
+    }
 }
 
 }  // namespace mcd

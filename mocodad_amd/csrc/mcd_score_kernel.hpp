@@ -116,10 +116,21 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     //      MFMA stages (the shipped architecture at T condition frames), or read from the caller's (B,16) tensor
     if (P.cond_inkernel) {
         static_assert(CondFastLds<T, NB>::FLOATS <= PL::R, "cond_fast_body's region does not fit the work region zeroed for it");
-        for (int u = tid; u < PL::R; u += NTHREADS) smem[u] = 0.f;
-        bsync();
-        cond_fast_body<T, NB>(P.wbuf, P.dv, [&](int t) { return P.cond_idx[t]; }, P.seg_len, smem, win0, P.B, CE, nullptr);
-        bsync();
+        // all windows jointly, then -- window isolation, mcd_encode_kernel.hpp -- every window whose embedding is not finite ALONE on
+        // a region cleared again: a window with a non-finite condition frame, and whichever neighbour it reached through a pad row.
+        // With NB > 1 the joint run is the OPAQUE instance of cond_fast_body too -- ONE copy of the encoder's text, in a loop -- so
+        // the prologue of these rows is not the parent's text on the common path either (the encoder kernels keep theirs and
+        // hold the solo runs as a second instance); resources and the bench line of the rows did not move for it
+        // (profiles/nonfinite_windows.txt).
+        int enc_solo = -1;
+        do {
+            for (int u = tid; u < PL::R; u += NTHREADS) smem[u] = 0.f;
+            bsync();
+            cond_fast_body<T, NB, (NB > 1)>(P.wbuf, P.dv, [&](int t) { return P.cond_idx[t]; }, P.seg_len, smem, win0, P.B, CE, nullptr, enc_solo);
+            bsync();
+            if constexpr (NB == 1) break;
+            enc_solo = next_nonfinite_slot<NB>(CE, enc_solo, win0, P.B);
+        } while (enc_solo >= 0);
     } else if (threadIdx.x < NB * EDIM) {
         CE[threadIdx.x] = P.cond_emb ? P.cond_emb[(size_t)window_of(threadIdx.x / EDIM) * EDIM + threadIdx.x % EDIM] : 0.f;
     }
@@ -723,7 +734,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             if (solo < 0 || n == solo) {
                 if (win0 + n < Bq && loss_out) loss_out[(size_t)(win0 + n) * Sq + s] = l;
                 if (s < 64) LOSSB[n * 64 + s] = l;
-                if (!(fabsf(l) <= 3.0e38f)) WM[8] = 1;       // NaN / Inf: this chain diverged
+                if (win0 + n < Bq && !(fabsf(l) <= 3.0e38f)) WM[8] = 1;       // NaN / Inf: this chain diverged (a slot past the end of the batch repeats the last window: it starts no recovery)
             }
         }
     }
@@ -736,9 +747,10 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     // not finite: (ii) the region is cleared again, and (i) with several chains per workgroup the sample is run again once per
     // chain slot, ALONE -- the other slots sit out as benign chains (x = 0, no noise, no condition) and write nothing -- so that a
     // chain that is finite on its own gets its own loss back (bit-identical: a chain's arithmetic never depends on its
-    // neighbours' finite values).  The common path pays two LDS reads per sample.  Not covered: non-finite INPUT poses, whose
-    // window takes its workgroup partners along through the in-kernel condition encoder (include/mocodad_hip.h: inputs are finite).
-    // (Found by tests/test_samples50_gpu.py::test_a_diverged_chain_stays_alone.)
+    // neighbours' finite values).  The common path pays two LDS reads per sample.  A window with non-finite INPUT poses is such a
+    // chain in every sample; the embeddings CE its partners run on are kept clear of it by the prologue above (and by the encoder
+    // kernels' own isolation when they ran as a launch), so the partners' solo runs return their own losses.
+    // (tests/test_samples50_gpu.py::test_a_diverged_chain_stays_alone, tests/test_nonfinite_windows_gpu.py.)
     {
         const int div = WM[8], solo = NB > 1 ? WM[9] : -1;
         if (div) {
@@ -747,7 +759,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         }
         if (NB > 1 && (div || solo >= 0)) {
             // the joint run diverged: slot 0 alone next; a solo run: the next slot, or on to the next sample
-            const int nxt = solo < 0 ? 0 : (solo + 1 < NB ? solo + 1 : -1);
+            // (slots past the end of the batch never run alone)
+            const int nxt = solo < 0 ? 0 : (solo + 1 < NB && win0 + solo + 1 < P.B ? solo + 1 : -1);
             if (nxt >= 0) s -= P.split;                  // (the same sample again)
             bsync();                                     // every thread has read WM[8] / WM[9]
             if (tid_s == 0) { WM[8] = 0; WM[9] = nxt; }
