@@ -8,7 +8,7 @@
 //   mcd_pack.hpp             the weight packer (BatchNorm folding, MFMA fragment order)
 //   mcd_call.hpp             the front end of a scoring call, shared with the latent entry points (mcd_latent_api.hpp, included
 //                            at the end): window view, frame-list and aggregation checks, workspace layouts, launch_cond
-// The device code shared by the trajectory kernels (stage functions, LDS plan) is mcd_device.hpp; the kernels themselves are
+// The device code shared by the trajectory kernels is mcd_chain.hpp (what a chain is) and mcd_device.hpp (stage functions, LDS plan); the kernels themselves are
 // mcd_score_kernel.hpp (1 .. 12 U-Net frames) and mcd_tiled_kernel.hpp (13 .. 32).  See DESIGN.md section 2.
 
 #include <algorithm>

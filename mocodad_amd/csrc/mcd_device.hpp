@@ -1,4 +1,5 @@
 // mcd_device.hpp — shared device code of libmocodad_hip.so: MI355X (gfx950 / CDNA4) kernels + C ABI for the MoCoDAD anomaly-scoring path.
+// Stage functions (mix, GEMM, resampler) and the LDS plan; what a chain is (parameters, frame maps, draws, loss): mcd_chain.hpp.
 //
 // What runs here (reference: /root/reference, Python/PyTorch):
 //   MoCoDAD.forward hot loop            models/mocodad.py:155-180      -> score_kernel<T_u, ...> for 1 .. 12 U-Net frames (persistent,
@@ -41,6 +42,7 @@
 #include <atomic>
 
 #include "../../include/mocodad_hip.h"
+#include "mcd_chain.hpp"      // what a chain is: parameters, frame maps, draws, loss
 
 namespace mcd {
 
@@ -83,7 +85,6 @@ __device__ __forceinline__ float4 load_global4(const float* p) {       // 16-byt
 #endif
 constexpr int NWAVES = MCD_NWAVES;          // waves per workgroup (8; 16 is a tuning experiment)
 constexpr int NTHREADS = NWAVES * 64;
-constexpr int C0 = 2;        // num_coords
 constexpr int EDIM = 16;     // embedding_dim
 constexpr int NLAYERS = 11;  // ST-GCN layers of the U-Net
 constexpr int EMB_TOTAL = 532;  // sum of C_out over the 11 layers, last padded to 4
@@ -193,151 +194,6 @@ struct Prof {
 #define bsync() prof.sync()
 #define STAGE(id) prof.mark(id)
 
-// where the windows live: a dense (B,C,T,V) tensor, or a view into trajectory buffers with an optional affine
-// test-time transform applied on load (mcd_window_view_t)
-struct DataView {
-    const float* data;
-    const long long* base;
-    long long sc, st;
-    const int* trans;
-    const float* aff;
-};
-__device__ __forceinline__ float load_coord(const DataView& dv, int b, int c, int t, int v, int seg_len) {
-    const long long sc = dv.base ? dv.sc : (long long)seg_len * 17;
-    const long long st = dv.base ? dv.st : 17;
-    const float* p = dv.data + (dv.base ? dv.base[b] : (long long)b * C0 * seg_len * 17) + t * st + v;
-    if (!dv.trans) return p[c * sc];
-    const float x = p[0], y = p[sc];
-    const float* a = dv.aff + dv.trans[b] * 6 + c * 3;
-    return (a[0] * x + a[1] * y) + a[2];
-}
-
-struct ScoreParams {
-    unsigned long long* prof; // stage timing accumulators (MCD_PROFILE builds) or null
-    const float* wbuf;        // packed weights; first TAB_FLOATS words = offset table
-    DataView dv;              // windows: (B,C,T,V) tensor or a trajectory view
-    const float* noise;       // (S,K,B,C,Tx,V) or null
-    const float* cond_emb;    // (B,16) or null
-    const float* step_table;  // (ns, 4+16)
-    const float* x_in;        // single-pass mode: (B,C,Tu,V)
-    float* loss_out;          // (B,S)
-    float* pose_out;          // (B,S,C,Tx,V) or null
-    float* eps_out;           // single-pass mode
-    unsigned long long seed;
-    long long first_window;
-    int B, S, ns, seg_len, n_corrupt, loss_fn, mode, step_single, n_chains;
-    // A workgroup owns NB WINDOWS (group g = blockIdx / split) and runs the samples s = part, part + split, ... of both
-    // (part = blockIdx % split) one trajectory after the other.  split = 1: it sees every sample of its windows, so the
-    // condition encoder runs once per workgroup in its own LDS (cond_inkernel) and the aggregation over the samples
-    // (loss_agg, aggr, aggr_q) happens here too: ONE launch per scoring call.
-    int split, aggr, cond_inkernel;
-    int force_split;          // host only (MCD_OPT_SPLIT): 0 = choose
-    int loss_out_optional;    // host only: loss_out is the library's own scratch, not wanted when the aggregation is fused
-    int plan_only;            // host only: choose `split`, do not launch
-    int phase;                // tuning experiment (MCD_OPT_PHASE): the second half of the grid starts `phase` x 1024 cycles late
-    int prio_shift;           // host: log2 of the priority time slice in 100 MHz ticks (see the top of the step loop); 0 = off
-                              // (an ESTIMATE from the shapes; the kernel replaces it by a sixth of the measured duration of the
-                              // previous launch of the same grid when `tune` holds one)
-    int prio_rounds;          // host: rounds of workgroups of this launch (grid / resident slots, rounded up)
-    int* tune;                // per-handle device words: [0] signature (grid, S, ns) of the launch that wrote [1] = lifetime of its
-                              // workgroup 0 in 100 MHz ticks; or null
-    float aggr_q;
-    float* loss_agg;          // (B,) aggregated loss, or null
-    int cond_idx[12];         // cond_inkernel: data frames the condition encoder reads
-    int upd_shift;            // some prediction updates a frame other than the one it is read at (element-wise tail: barrier between reads and writes)
-    unsigned fixed_mask;      // bit t: U-Net frame t is a condition frame copied from the window (concat / imputation)
-    int src_frame[12];        // data frame feeding U-Net frame t (condition frame, or ground truth of a denoised one)
-    int tx_of[12];            // denoised U-Net frame t -> its index among the corrupt frames
-    int pos_of[12];           // corrupt frame k -> its U-Net frame
-    int upd_of[12];           // U-Net frame t -> corrupt frame whose eps-prediction is read at t (-1: none)
-    const int* win_mask;      // random_imp: (B,) per-window bitmask of the condition frames (frames in natural order;
-                              // replaces fixed_mask and the four maps above, which are then derived from the mask)
-    // layer-test instantiation only (mcd_layer_forward): stage id (0..10 ST-GCN layer, 11 down1, 12 down2, 13 up3, 14 up2),
-    // its input (B,Cin,T,Vin) and output (B,Cout,T,Vout)
-    int lt_stage;
-    const float* lt_in;
-    float* lt_out;
-    const float* lt_skip;     // slab-tiled kernel, stages 7 / 9: the U-Net skip tensor added behind the fused resampler (or null)
-};
-// frame layout of one window: `fixed` = its condition-frame bitmask (P.fixed_mask, or the window's own for random_imp)
-__device__ __forceinline__ int fm_tx(const ScoreParams& P, int fixed, int t) {
-    return P.win_mask ? __popc(~fixed & ((1 << t) - 1)) : P.tx_of[t];
-}
-__device__ __forceinline__ int fm_src(const ScoreParams& P, int t) { return P.win_mask ? t : P.src_frame[t]; }
-
-// ------------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller (perf mode noise; parity mode reads the caller's noise tensor)
-// ------------------------------------------------------------------------------------------------
-// all four output words: two Box-Muller pairs = four normals per call
-__device__ __forceinline__ void philox_normal4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                               float (&z)[4]) {
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const unsigned w[4] = {c0, c1, c2, c3};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = ((float)(w[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float u2 = ((float)(w[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-        const float r = __fsqrt_rn(-1.38629436111989f * __log2f(u1));       // hardware log2 / sqrt / sin / cos, as below
-        z[2 * h] = r * __cosf(6.28318530717958647692f * u2);
-        z[2 * h + 1] = r * __sinf(6.28318530717958647692f * u2);
-    }
-}
-__device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3) {
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const float u1 = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c1 >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    // Box-Muller on the hardware transcendental units (v_log_f32, v_cos_f32, v_sqrt_f32): this is a noise source,
-    // ~1e-6 relative accuracy is irrelevant to its distribution
-    return __fsqrt_rn(-1.38629436111989f * __log2f(u1)) * __cosf(6.28318530717958647692f * u2);
-}
-// the four raw output words of one call, in output order (same rounds, multipliers and key schedule as the two above, which
-// stay as they are: the trajectory kernels' code must not move).  For integer draws: random_imp_masks_kernel.
-__device__ __forceinline__ void philox_words4(unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                              unsigned (&w)[4]) {
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-// position of the r-th (0-based, ascending) set bit of m; PRECONDITION: r < popcount(m).  Clears the r lowest set bits: no
-// per-thread array, nothing for scratch memory.
-__device__ __forceinline__ int nth_set_bit(unsigned m, int r) {
-    for (int i = 0; i < r; ++i) m &= m - 1u;
-    return __ffs(m) - 1;
-}
-__device__ __forceinline__ unsigned low_bits(int n) { return n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; }
-
 // PReLU(x) = x >= 0 ? x : a x  ==  max(x, a x) for a <= 1, min(x, a x) for a > 1: one multiply and one v_med3_f32 against
 // +-inf picked by the (wave-uniform) slope -- the compare + select form costs a third VALU instruction per element, and
 // the fp32 MFMAs share the SIMD's issue time with the VALU (tools/ubench/coissue.hip)
@@ -359,38 +215,6 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += dpp_f<0x141>(v);     // row_half_mirror
     v += dpp_f<0x140>(v);     // row_mirror
     return v;
-}
-
-// aggregation of one window's S per-sample losses (mocodad.py:504-512 best / worst with strict comparisons from 1e10 / -1,
-// :489-492 mean / median, :513-516 quantile): torch's conventions -- median = lower middle, quantile = linear interpolation
-// (torch.lerp).  Sorts L in place for the order statistics.
-__device__ __forceinline__ float aggregate_losses(float* L, int S, int strategy, float q) {
-    if (strategy == MCD_AGGR_BEST || strategy == MCD_AGGR_WORST) {
-        const bool best = strategy == MCD_AGGR_BEST;
-        float cur = best ? 1e10f : -1.f;
-        for (int s = 0; s < S; ++s) if (best ? (L[s] < cur) : (L[s] > cur)) cur = L[s];
-        return cur;
-    }
-    if (strategy == MCD_AGGR_MEAN) {
-        float sum = 0.f;
-        for (int s = 0; s < S; ++s) sum += L[s];
-        return sum / (float)S;
-    }
-    for (int s = 0; s < S; ++s)            // torch.median / torch.quantile return NaN when a sample is NaN (a diverged chain);
-        if (L[s] != L[s]) return L[s];     // a comparison sort would leave an arbitrary finite value at the rank instead
-    for (int i = 1; i < S; ++i) {          // insertion sort (S <= 64)
-        const float x = L[i];
-        int k = i - 1;
-        while (k >= 0 && L[k] > x) { L[k + 1] = L[k]; --k; }
-        L[k + 1] = x;
-    }
-    if (strategy == MCD_AGGR_MEDIAN) return L[(S - 1) / 2];
-    const float pos = fminf(fmaxf(q, 0.f), 1.f) * (float)(S - 1);      // (q is validated on the host; the clamp is a backstop)
-    const int lo = (int)floorf(pos);
-    const int hi = lo + 1 < S ? lo + 1 : S - 1;
-    const float wgt = pos - (float)lo;
-    const float a = L[lo], c = L[hi];
-    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1487,16 +1311,5 @@ struct Plan {
     static_assert((size_t)TOTAL * 4 <= 160 * 1024, "LDS plan: more than 160 KB");
     static constexpr size_t BYTES = (size_t)TOTAL * 4;
 };
-
-// data frames a condition encoder reads, in order
-struct FrameIdx { int idx[MCD_MAX_FRAMES]; };
-// U-Net frame layout of a scoring call for the kernels that take it at run time (more than 12 frames)
-struct FrameMaps { int src_frame[MCD_MAX_FRAMES], tx_of[MCD_MAX_FRAMES], pos_of[MCD_MAX_FRAMES], upd_of[MCD_MAX_FRAMES]; };
-__device__ __forceinline__ float loss_elem(float a, float b, int fn) {
-    const float d = fabsf(a - b);
-    if (fn == MCD_LOSS_SMOOTH_L1) return d < 1.f ? 0.5f * d * d : d - 0.5f;
-    if (fn == MCD_LOSS_L1) return d;
-    return d * d;
-}
 
 }  // namespace mcd

@@ -33,7 +33,6 @@ constexpr int CU_OUT = 6;                  // unet_down_channels[6] of STSE_Unet
 // so cond_fast_body's four 17-joint layers cannot leak as they stand; its result is tested all the same, so that the guarantee
 // does not rest on that detail of the mix.)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.0e38f); }
 // the barrier between the joint run's last stores and the test: behind the workgroup's LDS traffic (the flags) alone -- nothing
 // here needs the results just stored to global memory to have arrived, which __syncthreads(), a release fence as well, waits for
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

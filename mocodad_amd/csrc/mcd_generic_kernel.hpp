@@ -137,7 +137,7 @@ __device__ void g_resample(const float* wb, int wo, int bo, int C, int T, int vi
 // at a time (persistent grid), activations [channel][frame][joint] in a per-workgroup global scratch slab.  Correct, not fast,
 // and since round 3 off every default path (score_kernel<T,...> covers 1 .. 12 frames, score_tiled_kernel 13 .. 32): it is the
 // independent implementation MCD_OPT_GENERIC_UNET switches to, which the tests compare the MFMA kernels with.
-// Same noise keys, same update, same loss as score_kernel.
+// The chain -- draws, frame maps, update, loss -- is mcd_chain.hpp's.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreParams P, const FrameMaps M, const GenNet N, int T,
                                                                     float* __restrict__ scratch) {
@@ -156,25 +156,17 @@ __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreP
     float* D1 = Zb + GEN_BUF * T;
     float* D2 = D1 + GEN_D1 * T;
     const float* wb = P.wbuf;
-    const int Tx = P.n_corrupt;
-    const int K = P.ns > 2 ? P.ns - 1 : 1;
-    const int per = C0 * Tx * 17;
+    const int Tx = P.n_corrupt, K = P.ns > 2 ? P.ns - 1 : 1, per = C0 * Tx * 17;
     for (long long chain = blockIdx.x; chain < P.n_chains; chain += gridDim.x) {
         const int b = (int)(chain / P.S), s = (int)(chain % P.S);
         const unsigned fixed = (unsigned)(P.win_mask ? P.win_mask[b] : P.fixed_mask);
-        auto tx_of = [&](int t) { return P.win_mask ? __popc(~fixed & ((1u << t) - 1u)) : M.tx_of[t]; };
-        auto src_of = [&](int t) { return P.win_mask ? t : M.src_frame[t]; };
         __syncthreads();
         for (int u = tid; u < CTV; u += GEN_THREADS) {
             const int c = u / TV, t = (u % TV) / 17, v = u % 17;
             float x;
             if (P.mode == 1) x = P.x_in[((size_t)b * C0 + c) * TV + t * 17 + v];
-            else if ((fixed >> t) & 1u) x = load_coord(P.dv, b, c, src_of(t), v, P.seg_len);
-            else {
-                const int e = (c * Tx + tx_of(t)) * 17 + v;
-                x = P.noise ? P.noise[((size_t)(s * K + 0) * P.B + b) * per + e]
-                            : philox_normal(P.seed, (unsigned)e, 0u, (unsigned)s, (unsigned)(P.first_window + b));
-            }
+            else if ((fixed >> t) & 1u) x = load_coord(P.dv, b, c, fm_src(P, M, t), v, P.seg_len);
+            else x = chain_xT(P, b, s, K, per, c, fm_tx(P, M, fixed, t), v);
             XT[u] = x;
         }
         const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
@@ -187,22 +179,13 @@ __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreP
                 if (P.cond_emb) e += P.cond_emb[(size_t)b * EDIM + tid];
                 SE[tid] = e / (1.f + expf(-e));
             }
-            // this step's noise, one thread per (frame, joint pair) like score_kernel (same Philox keys)
+            // this step's noise, one thread per (frame, joint pair)
             if (P.mode == 0 && sidx > 1) {
                 const int k = P.ns - sidx;
                 for (int gi = tid; gi < T * 9; gi += GEN_THREADS) {
                     const int t = gi / 9, v0 = (gi % 9) * 2;
                     float z[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (!((fixed >> t) & 1u)) {
-                        const int tx = tx_of(t);
-                        if (P.noise) {
-                            const float* zp = P.noise + ((size_t)(s * K + k) * P.B + b) * per + tx * 17 + v0;
-                            z[0] = zp[0]; z[1] = zp[Tx * 17];
-                            if (v0 + 1 < 17) { z[2] = zp[1]; z[3] = zp[Tx * 17 + 1]; }
-                        } else {
-                            philox_normal4(P.seed, (unsigned)(tx * 9 + (v0 >> 1)), (unsigned)k, (unsigned)s, (unsigned)(P.first_window + b), z);
-                        }
-                    }
+                    if (!((fixed >> t) & 1u)) chain_step_noise4(P, b, s, k, K, per, Tx, fm_tx(P, M, fixed, t), v0, z);
                     ZN[t * 17 + v0] = z[0]; ZN[TV + t * 17 + v0] = z[1];
                     if (v0 + 1 < 17) { ZN[t * 17 + v0 + 1] = z[2]; ZN[TV + t * 17 + v0 + 1] = z[3]; }
                 }
@@ -244,9 +227,8 @@ __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreP
                 if (P.mode == 1) {
                     P.eps_out[((size_t)b * C0 + c) * TV + t * 17 + v] = eps;
                 } else {
-                    const int k = P.win_mask ? (((fixed >> t) & 1u) ? -1 : 0) : M.upd_of[t];
-                    if (k >= 0) {
-                        const int tp = P.win_mask ? t : M.pos_of[k];
+                    const int tp = fm_upd(P, M, fixed, t);
+                    if (tp >= 0) {
                         const int up = c * TV + tp * 17 + v;
                         xn[it] = ca * (XT[up] - cb * eps) + csg * (zadd ? ZN[up] : 0.f);
                         dst[it] = up;
@@ -264,10 +246,9 @@ __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreP
         float part = 0.f;
         for (int e = tid; e < per; e += GEN_THREADS) {
             const int c = e / (Tx * 17), tx = (e / 17) % Tx, v = e % 17;
-            int tu = M.pos_of[tx];
-            if (P.win_mask) { int cnt = 0; for (int t = 0; t < T; ++t) if (!((fixed >> t) & 1u)) { if (cnt == tx) tu = t; ++cnt; } }
+            const int tu = fm_corrupt_frame(P, M, fixed, tx, T);
             const float x0 = XT[c * TV + tu * 17 + v];
-            const float gt = load_coord(P.dv, b, c, src_of(tu), v, P.seg_len);
+            const float gt = load_coord(P.dv, b, c, fm_src(P, M, tu), v, P.seg_len);
             part += loss_elem(x0, gt, P.loss_fn);
             if (P.pose_out) P.pose_out[(size_t)(b * P.S + s) * per + e] = x0;
         }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_chain_kernel(const LatentC
                         const float4 v = load_global4(P.noise + ((size_t)(s * K) * P.B + b) * D + d0);
                         z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
                     } else {
-                        philox_normal4(P.seed, (unsigned)(d0 >> 2), 0u, (unsigned)s, (unsigned)(P.first_window + b), z);
+                        latent_philox4(P.seed, P.first_window, b, s, 0, d0, z);
                     }
                     zc = load_global4(P.z0 + (size_t)b * D + d0);
                 }
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(LAT_THREADS) void latent_chain_kernel(const LatentC
                                     const float4 zv = load_global4(P.noise + ((size_t)(s * K + k) * P.B + b) * D + c0);
                                     z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
                                 } else {
-                                    philox_normal4(P.seed, (unsigned)(c0 >> 2), (unsigned)k, (unsigned)s, (unsigned)(P.first_window + b), z);
+                                    latent_philox4(P.seed, P.first_window, b, s, k, c0, z);
                                 }
                             }
                             const unsigned xa = lds_addr(X + col * XS + c0);
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void latent_philox_kernel(unsigned long long s
     const int k = (int)((u / ((long long)(D >> 2) * B)) % K);
     const int s = (int)(u / ((long long)(D >> 2) * B * K));
     float z[4];
-    philox_normal4(seed, (unsigned)grp, (unsigned)k, (unsigned)s, (unsigned)(first_window + b), z);
+    latent_philox4(seed, first_window, b, s, k, grp * 4, z);
     store_global4(out + (((size_t)(s * K + k) * B + b) * D + grp * 4), make_float4(z[0], z[1], z[2], z[3]));
 }
 

@@ -399,8 +399,8 @@ __global__ __launch_bounds__(API_THREADS) void poison_lds_kernel(unsigned* sink,
 extern "C" {
 
 __global__ void philox_noise_kernel(unsigned long long seed, long long first_window, int B, int S, int K, int Tx, float* __restrict__ out) {
-    // one thread per (s, k, b, tx, joint pair): exactly the draws of score_kernel (x_T: one call per element keyed
-    // (element, 0, s, window); step k >= 1: one call per joint pair keyed (tx * 9 + pair, k, s, window))
+    // one thread per (s, k, b, tx, joint pair): the Philox half of chain_xT / chain_step_noise4 (mcd_chain.hpp), so the export
+    // is the kernels' draw by construction
     const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = (long long)S * K * B * Tx * 9;
     if (u >= total) return;
@@ -413,10 +413,10 @@ __global__ void philox_noise_kernel(unsigned long long seed, long long first_win
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = i & 1, v = v0 + (i >> 1);
-            z[i] = v < 17 ? philox_normal(seed, (unsigned)((c * Tx + tx) * 17 + v), 0u, (unsigned)s, (unsigned)(first_window + b)) : 0.f;
+            z[i] = v < 17 ? chain_xT_philox(seed, first_window, b, s, Tx, c, tx, v) : 0.f;
         }
     } else {
-        philox_normal4(seed, (unsigned)(tx * 9 + jp), (unsigned)k, (unsigned)s, (unsigned)(first_window + b), z);
+        chain_step_philox4(seed, first_window, b, s, k, tx, v0, z);
     }
     o[tx * 17 + v0] = z[0];
     o[Tx * 17 + tx * 17 + v0] = z[1];

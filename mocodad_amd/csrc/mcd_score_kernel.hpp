@@ -235,7 +235,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                 } else if ((fixed >> t) & 1) {
                     xv[c] = load_coord(dv, b, c, fm_src(P, t), v, seg_len);
                 } else {
-                    const int e = (c * Tx + fm_tx(P, fixed, t)) * 17 + v;
+                    const int e = (c * Tx + fm_tx(P, fixed, t)) * 17 + v;        // (chain_xT, mcd_chain.hpp, on this kernel's hoisted arguments)
                     if (noise) xv[c] = noise[((size_t)(s * K + 0) * Bq + b) * CTV + e];
                     else xv[c] = philox_normal(seed, (unsigned)e, 0u, (unsigned)s, (unsigned)(first_window + b));
                 }
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                     const int b = WM[4 + n];
                     const int tx = fm_tx(P, fixed, t);
                     const int k = P.ns - sidx;
-                    if (P.noise) {
+                    if (P.noise) {          // (chain_step_noise4, mcd_chain.hpp: kept in place, this kernel's code does not move)
                         const float* zp = P.noise + ((size_t)(s * K + k) * P.B + b) * CTV + tx * 17 + v0;
                         z[0] = zp[0]; z[1] = zp[Tx * 17];                                   // (c = 0, v0), (c = 1, v0)
                         if (v0 + 1 < 17) { z[2] = zp[1]; z[3] = zp[Tx * 17 + 1]; }         // (c = 0, v0+1), (c = 1, v0+1)
@@ -696,7 +696,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             const bool valid = win0 + n < Bq && (solo < 0 || n == solo);
             const int b = WM[4 + n];
             int tu = P.pos_of[tx];
-            if (wmask) {                       // frame of the tx-th corrupt frame = tx-th clear bit of the window's mask
+            if (wmask) {                       // frame of the tx-th corrupt frame = tx-th clear bit of the window's mask (fm_corrupt_frame, mcd_chain.hpp)
                 const int fixed = WM[n];
                 int cnt = 0;
                 for (int t = 0; t < T; ++t)
@@ -734,7 +734,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             if (solo < 0 || n == solo) {
                 if (win0 + n < Bq && loss_out) loss_out[(size_t)(win0 + n) * Sq + s] = l;
                 if (s < 64) LOSSB[n * 64 + s] = l;
-                if (win0 + n < Bq && !(fabsf(l) <= 3.0e38f)) WM[8] = 1;       // NaN / Inf: this chain diverged (a slot past the end of the batch repeats the last window: it starts no recovery)
+                if (win0 + n < Bq && not_finite(l)) WM[8] = 1;       // NaN / Inf: this chain diverged (a slot past the end of the batch repeats the last window: it starts no recovery)
             }
         }
     }

@@ -26,7 +26,7 @@ namespace mcd {
 // The frame count is padded to TP = 16, 24 or 32 with zero mixing coefficients (a padded frame's activations are finite
 // garbage that no real frame ever reads).  13 .. 16 frames run as <16, 1>: one chain per workgroup, 79 KB of LDS, TWO workgroups
 // per CU under the 128-register cap (+10.6 % over two chains in one workgroup, profiles/r04v_tl16_nb1_ab.txt).
-// Same noise keys, update, loss and strategies as score_kernel.  Slab traffic: 9 k floats per frame and pass (the first
+// Same noise keys, update, loss and strategies as score_kernel: mcd_chain.hpp states them (KEY LAYOUT, fm_*); this kernel keeps its own text of the draws, like score_kernel.  Slab traffic: 9 k floats per frame and pass (the first
 // version, every stage through the slab: 37 k -- it ran at the HBM / fabric roofline, 4.6 TB/s, profiles/README.md).
 // ------------------------------------------------------------------------------------------------
 struct TiledNet {
@@ -576,8 +576,6 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
         auto b_of = [&](int i) { return NB == 1 ? bq[0] : bq[i]; };
         auto s_of = [&](int i) { return NB == 1 ? sq[0] : sq[i]; };
         auto fixed_of = [&](int i) { return NB == 1 ? fq[0] : fq[i]; };
-        auto tx_of = [&](unsigned fixed, int t) { return P.win_mask ? __popc(~fixed & ((1u << t) - 1u)) : M.tx_of[t]; };
-        auto src_of = [&](int t) { return P.win_mask ? t : M.src_frame[t]; };
         __syncthreads();
         for (int u = tid; u < NB * T * 17; u += NTHREADS) {
             const int i = u / (T * 17), t = (u / 17) % T, v = u % 17;
@@ -588,9 +586,9 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                 float x;
                 if constexpr (COND) x = load_coord(P.dv, b, c, M.src_frame[t], v, P.seg_len);
                 else if (P.mode == 1) x = P.x_in ? P.x_in[((size_t)(b * C0 + c) * T + t) * 17 + v] : 0.f;
-                else if ((fixed >> t) & 1u) x = load_coord(P.dv, b, c, src_of(t), v, P.seg_len);
-                else {
-                    const int e = (c * Tx + tx_of(fixed, t)) * 17 + v;
+                else if ((fixed >> t) & 1u) x = load_coord(P.dv, b, c, fm_src(P, M, t), v, P.seg_len);
+                else {      // chain_xT's statement (mcd_chain.hpp), kept in place like the step noise and the corrupt-frame loop below: a call moves this kernel's objects
+                    const int e = (c * Tx + fm_tx(P, M, fixed, t)) * 17 + v;
                     x = P.noise ? P.noise[((size_t)(s * K + 0) * P.B + b) * per + e]
                                 : philox_normal(P.seed, (unsigned)e, 0u, (unsigned)s, (unsigned)(P.first_window + b));
                 }
@@ -647,7 +645,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                     const unsigned fixed = fixed_of(i);
                     float z[4] = {0.f, 0.f, 0.f, 0.f};
                     if (!((fixed >> t) & 1u)) {
-                        const int tx = tx_of(fixed, t);
+                        const int tx = fm_tx(P, M, fixed, t);      // (chain_step_noise4's statement)
                         if (P.noise) {
                             const float* zp = P.noise + ((size_t)(s * K + k) * P.B + b) * per + tx * 17 + v0;
                             z[0] = zp[0]; z[1] = zp[Tx * 17];
@@ -1196,7 +1194,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
                             if (t < T && P.eps_out && grp * NB + i < P.n_chains) P.eps_out[(((size_t)b_of(i) * C0 + c) * T + t) * 17 + v] = eps;
                             continue;
                         }
-                        const int tpm = UPDT[t];                             // (LDS: M.upd_of[t] -> M.pos_of[k] were two dependent global loads per element)
+                        const int tpm = UPDT[t];                             // (LDS: M.upd_of[t] -> M.pos_of[k] were two dependent global loads per element); k, tp: must agree with fm_upd (mcd_chain.hpp)
                         const int k = t >= T ? -1 : P.win_mask ? (((fixed_of(i) >> t) & 1u) ? -1 : 0) : tpm;
                         if (k >= 0) {
                             const int tp = P.win_mask ? t : tpm;
@@ -1225,10 +1223,10 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
             float part = 0.f;
             for (int e = tid; e < per; e += NTHREADS) {
                 const int c = e / (Tx * 17), tx = (e / 17) % Tx, v = e % 17;
-                int tu = M.pos_of[tx];
+                int tu = M.pos_of[tx];      // (fm_corrupt_frame's statement)
                 if (P.win_mask) { int cnt = 0; for (int t = 0; t < T; ++t) if (!((fixed >> t) & 1u)) { if (cnt == tx) tu = t; ++cnt; } }
                 const float x0 = XT[((i * TP + tu) * 17 + v) * 4 + c];
-                const float gt = load_coord(P.dv, b, c, src_of(tu), v, P.seg_len);
+                const float gt = load_coord(P.dv, b, c, fm_src(P, M, tu), v, P.seg_len);
                 part += loss_elem(x0, gt, P.loss_fn);
                 if (P.pose_out) P.pose_out[(size_t)(b * P.S + s) * per + e] = x0;
             }
@@ -1239,7 +1237,7 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
             for (int o = RP2 / 2; o > 0; o >>= 1) { if (tid < o && tid + o < NTHREADS) RED[tid] += RED[tid + o]; __syncthreads(); }
             const float lsum = RED[0];                 // (every thread: the same LDS word)
             if (tid == 0) P.loss_out[chain] = lsum / (float)per;
-            diverged |= !(fabsf(lsum) <= 3.0e38f);      // NaN / Inf
+            diverged |= not_finite(lsum);
             __syncthreads();
         }
         // A diverged chain (NaN / Inf activations) leaves non-finite values in the slab and the LDS regions; the NEXT chain of this
