@@ -61,6 +61,7 @@ __device__ __forceinline__ gfloat* as_global(const float* p) { return (gfloat*)p
 // rather re-derive it per use), constant byte offsets folded into the instruction's offset field
 typedef float __attribute__((address_space(3))) lds_float;
 typedef f32x4 __attribute__((address_space(3))) lds_f32x4;
+typedef f32x2 __attribute__((address_space(3))) lds_f32x2;
 // (the low half of a generic pointer into LDS IS its LDS address; an addrspacecast would add a null check per use -- and with
 // -amdgpu-sched-strategy=iterative-minreg one of those trips "Illegal instruction detected: V_CMP_NE_U32_e32 0, $src_shared_base")
 __device__ __forceinline__ unsigned lds_addr(const float* p) { return (unsigned)(uintptr_t)p; }
@@ -376,7 +377,7 @@ struct MixCfg {
     // instantiated shape is either one round, full rounds, or the SAMEQ pair map -- a new shape that is not has to pick its QC here
     static_assert(T > 12 || PER == 1 || UNITS % NWAVES == 0 || SAMEQ, "mix units: a partial round of units (see MixCfg::QX)");     // (T > 12: the condition encoders of 13 .. 20 frames, < 1 % of a step)
     // unit (frame chunk index, group = chain * CB + channel block) of (wave, round); u < 0: none
-    __device__ static __forceinline__ int unit_of(int wave, int round) {
+    __host__ __device__ static constexpr int unit_of(int wave, int round) {
         if constexpr (SAMEQ) {
             if (wave < 4) return (wave >> 1) + NQ * ((wave & 1) * 2 + round);
             return round == 0 ? 2 + NQ * (wave - 4) : -1;
@@ -395,6 +396,20 @@ struct MixCoef {
     // the coefficients of the wave's first unit
     __device__ __forceinline__ void load(const float* tqd, const float* af, int wave, int lane) {
         load_unit(tqd, af, M::unit_of(wave, 0), lane);
+    }
+    // the coefficients of a one-frame unit whose frame is given as byte offsets into the two tables (a stage-table row's tq_o / af_o,
+    // added to the table pointers on the scalar unit: every load is then table + constant + 4 lane, the SGPR-base form of
+    // global_load, where the unit index in the per-lane part costs a 64-bit VALU add and a VGPR pair per table)
+    __device__ __forceinline__ void load_at(const float* tqd, const float* af, int lane) {
+        static_assert(M::QC == 1, "one output frame per unit");
+        gfloat* tqd_g = as_global(tqd);
+        gfloat* af_g = as_global(af);
+#pragma unroll
+        for (int r = 0; r < M::NR; ++r) tq[0][r] = tqd_g[r * 64 + lane];
+#pragma unroll
+        for (int mt = 0; mt < M::MT; ++mt)
+#pragma unroll
+            for (int ks = 0; ks < M::KS; ++ks) aop[0][mt][ks] = af_g[(mt * M::KS + ks) * 64 + lane];
     }
     __device__ __forceinline__ void load_unit(const float* tqd, const float* af, int u, int lane) {
         gfloat* tqd_g = as_global(tqd);
@@ -418,14 +433,48 @@ struct ChIdx {
     int cb16, j;
     __device__ __forceinline__ operator int() const { return cb16 + j; }
 };
+// One row of the per-wave stage table (mcd_stage_table.hpp): the LDS byte addresses of ONE unit of a stage -- what the stage
+// otherwise derives from the wave index on the scalar unit (wave -> unit -> chain, channel block, frame -> byte offset, ~15 scalar
+// instructions per unit and use) -- and the unit's frame in the coefficient tables, read with scalar loads a stage ahead.
+//   in_b    the unit's first input row: region + chain (or frame) rows + 16-channel block
+//   out_b   the unit's first output row (mixes: + output frame)
+//   aux_b   W-first layers: the unit's embedding row EMB[chain][layer offset + block]
+//   aux2_b  W-first layers: the block's folded bias BIA[...]
+//   tq_o, af_o  mixes: byte offsets of the unit's output frame in the layer's time-mix rows / joint-mix fragments (MixCoef::load_at)
+struct StageRow { unsigned in_b, out_b, aux_b, aux2_b, tq_o, af_o, pad0, pad1; };      // (32 bytes: an s_load_dwordx4 and an s_load_dwordx2)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef const u32x4 __attribute__((address_space(4))) cu32x4;
+typedef const u32x2 __attribute__((address_space(4))) cu32x2;
+// row `id` of this wave's rows (`tbw`: the table's base + wave x rows, opaque per pass); lds0: the LDS address of the kernel's dynamic LDS
+__device__ __forceinline__ StageRow stage_row(const StageRow* tbw, int id, unsigned lds0) {
+    const u32x4 v = ((cu32x4*)tbw)[2 * id];
+    const u32x2 c = ((cu32x2*)tbw)[4 * id + 2];
+    return StageRow{v[0] + lds0, v[1] + lds0, v[2] + lds0, v[3] + lds0, c[0], c[1], 0u, 0u};
+}
+// ... with the unit's out / aux / aux2 LDS byte addresses of its stage-table row (the functors of a ROWS mix take this one)
+struct ChIdxRow {
+    int cb16, j;
+    unsigned ob, ab, ab2;
+    __device__ __forceinline__ operator int() const { return cb16 + j; }
+};
+template <bool ROWS>
+struct ChIdxOf {
+    __device__ static __forceinline__ auto make(int cb16, int jj, const StageRow* rows, int rnd) {
+        if constexpr (ROWS) return ChIdxRow{cb16, jj, rows[rnd].out_b, rows[rnd].aux_b, rows[rnd].aux2_b};
+        else return ChIdx{cb16, jj};
+    }
+};
 // init functor of a mix whose accumulators start at zero (x + 0.f is not folded away: -0.0)
 struct ZeroInit { __device__ __forceinline__ float operator()(int, int, int, int) const { return 0.f; } };
 // FORCE (kernels without a register cap): the unit's X reads are pinned in front of its arithmetic (the scheduler otherwise
 // sinks each k-step's reads to their first use and the wave pays an LDS round trip per k-step)
-template <int CIN, int V, int T, int NB, bool FORCE = false, bool SCORE = false, class Init, class Store>
+// ROWS: the units' LDS addresses come from stage-table rows (`rows[round]`, see StageRow): load_x starts from in_b, and the
+// functors get out_b / aux_b / aux2_b in their ChIdx instead of deriving them from (n, q, cb16)
+template <int CIN, int V, int T, int NB, bool FORCE = false, bool SCORE = false, bool ROWS = false, class Init, class Store>
 __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_in, const MixCoef<CIN, V, T, NB>& pre,
                                           const float* __restrict__ tqd, const float* __restrict__ af, int wave, int lane,
-                                          Init&& init, Store&& store) {
+                                          Init&& init, Store&& store, const StageRow* rows = nullptr) {
     using M = MixCfg<CIN, V, T, NB>;
     constexpr int KS = M::KS, KP = M::KP, MT = M::MT, CB = M::CB, QC = M::QC, NQ = M::NQ, PER = M::PER;
     // (XB32 in the register-capped trajectory kernels too: +0.7 % at 3 frames, profiles/r06g_t3_variants_ab.txt)
@@ -437,10 +486,12 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
     // v_mad_u32_u24 (lane group x row stride + channel), the reads sit at instruction offsets from their sum.  Written as one
     // product (n T V + voff) x stride the compiler multiplied per unit and rebuilt the sum on the VALU: 6 instructions per unit
     // against 3 -- and integer VALU instructions cost the matrix pipe as much as floating-point ones (tools/ubench/mix_ceiling.hip)
-    auto load_x = [&](int u, float (&x)[KS][T]) {
+    auto load_x = [&](int u, float (&x)[KS][T], int rnd) {
         const int rest = u / NQ;
         const int cb = rest % CB, n = rest / CB;
-        unsigned ua = lds_addr(in) + 4u * (unsigned)(n * (T * V) * cs_in + cb * 16);          // scalar unit
+        unsigned ua;
+        if constexpr (ROWS) ua = rows[rnd].in_b;
+        else ua = lds_addr(in) + 4u * (unsigned)(n * (T * V) * cs_in + cb * 16);          // scalar unit
         asm volatile("" : "+s"(ua));      // (opaque: the region's offset stays in this sum -- split off into the reads' offset fields it costs the first pair a re-basing add too)
         const lds_float* ub = (const lds_float*)(uintptr_t)ua;
         const lds_float* a_p = ub + (__mul24(voff_pair, cs_in) + j);
@@ -461,9 +512,12 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
             }
         });
     };
-    auto unit = [&](const MixCoef<CIN, V, T, NB>& cur, int u, const float (&xs)[KS][T]) {
+    auto unit = [&](const MixCoef<CIN, V, T, NB>& cur, int u, const float (&xs)[KS][T], int rnd) {
         const int q0 = (u % NQ) * QC, rest = u / NQ;
         const int cb = rest % CB, n = rest / CB;
+        static_assert(!ROWS || (QC == 1 && !M::RAGGED), "stage-table rows: one output frame per unit");
+        // the functors' channel index of lane part jj (ROWS: + the unit's row addresses)
+        auto chidx = [&](int jj) { return ChIdxOf<ROWS>::make(cb * 16, jj, rows, rnd); };
         // V = 17: output joint 16 would cost a whole second m-tile (15/16 wasted, and the kernel is bound by matrix-pipe
         // time); it is accumulated with plain FMAs instead -- 5 per frame, partial sums over this lane group's joints
         constexpr bool J16 = V == 17;
@@ -489,7 +543,7 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
                 if ((M::RAGGED && q0 + qi >= T) || ZINIT) {
                     acc[qi][mt] = f32x4{0.f, 0.f, 0.f, 0.f};      // (the frame behind a ragged chain's last: computed on zero coefficients, never stored)
                 } else {
-                    acc[qi][mt] = init(n, q0 + qi, mt * 16 + j, ChIdx{cb * 16, 4 * g});
+                    acc[qi][mt] = init(n, q0 + qi, mt * 16 + j, chidx(4 * g));
                 }
         }
         static_for<KS>([&](auto si) {
@@ -518,7 +572,7 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
             if (M::RAGGED && q0 + qi >= T) continue;
 #pragma unroll
             for (int mt = 0; mt < MTM; ++mt) {
-                if ((mt + 1) * 16 <= V || mt * 16 + j < V) store(n, q0 + qi, mt * 16 + j, ChIdx{cb * 16, 4 * g}, acc[qi][mt]);
+                if ((mt + 1) * 16 <= V || mt * 16 + j < V) store(n, q0 + qi, mt * 16 + j, chidx(4 * g), acc[qi][mt]);
             }
             if constexpr (J16) {
                 // sum the four lane groups' partials (lanes j, j+16, j+32, j+48): two register-swap steps
@@ -527,7 +581,7 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
                 const unsigned v2 = __float_as_uint(__uint_as_float(h[0]) + __uint_as_float(h[1]));
                 const auto f = __builtin_amdgcn_permlane16_swap(v2, v2, false, false);
                 const float z16 = __uint_as_float(f[0]) + __uint_as_float(f[1]);
-                if (g == 0) store(n, q0 + qi, 16, ChIdx{cb * 16, j}, z16);
+                if (g == 0) store(n, q0 + qi, 16, chidx(j), z16);
             }
         }
     };
@@ -543,11 +597,11 @@ __device__ __forceinline__ void mix_stage(const float* __restrict__ in, int cs_i
             const int u = ALLW ? wave + rnd * NWAVES : M::unit_of(wave, rnd);
             constexpr bool SURE = ALLW;       // (the SAMEQ map's first round gives every wave a unit as well: said too, -0.3 %, profiles/r05n_sameq_ab.txt)
             float xs[KS][T];
-            load_x(SURE ? u : (u < 0 ? 0 : u), xs);
+            load_x(SURE ? u : (u < 0 ? 0 : u), xs, rnd);
             if constexpr (FORCE) __builtin_amdgcn_sched_barrier(0);
             MixCoef<CIN, V, T, NB> nxt;
             if constexpr (rnd + 1 < PER && !M::SAMEQ && NQ > 1) nxt.load_unit(tqd, af, M::unit_of(wave, rnd + 1), lane);
-            if (SURE || u >= 0) unit(cur, u, xs);       // (full rounds: every wave has a unit, said at compile time)
+            if (SURE || u >= 0) unit(cur, u, xs, rnd);       // (full rounds: every wave has a unit, said at compile time)
             if constexpr (rnd + 1 < PER && !M::SAMEQ && NQ > 1) cur = nxt;       // (one frame group: every unit has the same coefficients)
         });
     }
@@ -616,10 +670,12 @@ struct RsCoef {
 // waves) instead of wave + i NWAVES -- the wave that mixes frame q of (chain, block) in a W-first layer's mix then resamples
 // exactly that frame, so no barrier separates the two stages; the matching down-sampler uses the same map so that the skip
 // registers it captures meet the up-sampler's units.
-template <int C, int VIN, int VOUT, int T, int NB, bool CAPTURE, bool ADD, bool ILP = false, bool SQMAP = false, int NSK>
+// ROWS: unit slot i reads from rows[i].in_b and stores to rows[i].out_b (stage-table rows, see StageRow) instead of deriving
+// (frame, channel block) -> byte offset from the wave index, once for the reads and once for the stores
+template <int C, int VIN, int VOUT, int T, int NB, bool CAPTURE, bool ADD, bool ILP = false, bool SQMAP = false, bool ROWS = false, int NSK>
 __device__ __forceinline__ void resample_stage(const float* __restrict__ in, int cs_in, float* __restrict__ out, int cs_out,
                                                const RsCoef<C, VIN, VOUT, T, NB, CAPTURE>& rc,
-                                               float (&skip)[NSK], int wave, int lane) {
+                                               float (&skip)[NSK], int wave, int lane, const StageRow* rows = nullptr) {
     using RC = RsCfg<C, VIN, VOUT, T, NB, CAPTURE>;
     constexpr int KS = RC::KS, MT = RC::MT, CB = RC::CB, UNITS = RC::UNITS, PER = RC::PER, SK = RC::SK;
     static_assert(!(CAPTURE || ADD) || NSK == PER * SK, "skip register count");
@@ -654,19 +710,22 @@ __device__ __forceinline__ void resample_stage(const float* __restrict__ in, int
         if (unit_at(i, cb, nt)) {
             // addresses: the unit's part on the scalar unit, the lane's part one v_mad, the k-steps at instruction offsets
             // (see mix_stage's load_x)
-            const float* ub = in + (nt * VIN * cs_in + cb * 16);
-            const float* a_main = ub + (__mul24(CAPTURE ? 4 * g : 4 * (g & 1) + (g >> 1), cs_in) + j);
             // the k-step behind the main ones: joints 16 + g (capture; only joint 16 exists: every lane group reads it, the
             // others' weights are zero and their captured value is never used) or 4 KP + g
-            const float* a_tail = CAPTURE ? ub + j : ub + (__mul24(g, cs_in) + j);
-            static_for<KS>([&](auto si) {
-                constexpr int ks = decltype(si)::value;
-                constexpr bool MAIN = CAPTURE ? ks < 4 : ks < KP;
-                constexpr int row0 = CAPTURE ? (ks < 4 ? ks : 16) : (ks < KP ? 8 * (ks >> 1) + 2 * (ks & 1) : 4 * KP);
-                const float xv = (MAIN ? a_main : a_tail)[row0 * cs_in];
-                if constexpr (CAPTURE) skip[i * SK + ks] = xv;
-                else xr[i][ks] = xv;
-            });
+            auto reads = [&](auto ub) {     // ub: the unit's first row (a generic pointer, or an LDS pointer from the stage table)
+                const auto a_main = ub + (__mul24(CAPTURE ? 4 * g : 4 * (g & 1) + (g >> 1), cs_in) + j);
+                const auto a_tail = CAPTURE ? ub + j : ub + (__mul24(g, cs_in) + j);
+                static_for<KS>([&](auto si) {
+                    constexpr int ks = decltype(si)::value;
+                    constexpr bool MAIN = CAPTURE ? ks < 4 : ks < KP;
+                    constexpr int row0 = CAPTURE ? (ks < 4 ? ks : 16) : (ks < KP ? 8 * (ks >> 1) + 2 * (ks & 1) : 4 * KP);
+                    const float xv = (MAIN ? a_main : a_tail)[row0 * cs_in];
+                    if constexpr (CAPTURE) skip[i * SK + ks] = xv;
+                    else xr[i][ks] = xv;
+                });
+            };
+            if constexpr (ROWS) reads((const lds_float*)(uintptr_t)rows[i].in_b);
+            else reads(in + (nt * VIN * cs_in + cb * 16));
         }
     });
     constexpr bool J16 = VOUT == 17;     // output joint 16 on the VALU (partial sums per lane group, permlane-swap reduction)
@@ -681,22 +740,25 @@ __device__ __forceinline__ void resample_stage(const float* __restrict__ in, int
             for (int r = 0; r < 4; ++r) acc[0][r] += skip[i * SK + r];
             if constexpr (SK == 5 && !J16) acc[MT - 1][0] += skip[i * SK + 4];   // joint 16: lane group g = 0, row 0 of m-tile 1
         }
-        float* uo = out + (nt * VOUT * cs_out + cb * 16);
-        float* zo = uo + (__mul24(4 * g, cs_out) + j);
+        auto stores = [&](auto uo) {        // uo: the unit's first output row (generic, or an LDS pointer from the stage table)
+            const auto zo = uo + (__mul24(4 * g, cs_out) + j);
 #pragma unroll
-        for (int mt = 0; mt < MTM; ++mt)
+            for (int mt = 0; mt < MTM; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (mt * 16 + 4 * g + r < VOUT) zo[(mt * 16 + r) * cs_out] = acc[mt][r];
-        if constexpr (J16) {
-            const unsigned pu = __float_as_uint(part);
-            const auto h = __builtin_amdgcn_permlane32_swap(pu, pu, false, false);
-            const unsigned v2 = __float_as_uint(__uint_as_float(h[0]) + __uint_as_float(h[1]));
-            const auto f = __builtin_amdgcn_permlane16_swap(v2, v2, false, false);
-            float z16 = __uint_as_float(f[0]) + __uint_as_float(f[1]) + bias[1][0];
-            if constexpr (ADD && SK == 5) z16 += skip[i * SK + 4];          // captured by lane group g = 0 (k-step 4: joint 16 + g)
-            if (g == 0) uo[16 * cs_out + j] = z16;
-        }
+                for (int r = 0; r < 4; ++r)
+                    if (mt * 16 + 4 * g + r < VOUT) zo[(mt * 16 + r) * cs_out] = acc[mt][r];
+            if constexpr (J16) {
+                const unsigned pu = __float_as_uint(part);
+                const auto h = __builtin_amdgcn_permlane32_swap(pu, pu, false, false);
+                const unsigned v2 = __float_as_uint(__uint_as_float(h[0]) + __uint_as_float(h[1]));
+                const auto f = __builtin_amdgcn_permlane16_swap(v2, v2, false, false);
+                float z16 = __uint_as_float(f[0]) + __uint_as_float(f[1]) + bias[1][0];
+                if constexpr (ADD && SK == 5) z16 += skip[i * SK + 4];          // captured by lane group g = 0 (k-step 4: joint 16 + g)
+                if (g == 0) uo[16 * cs_out + j] = z16;
+            }
+        };
+        if constexpr (ROWS) stores((lds_float*)(uintptr_t)rows[i].out_b);
+        else stores(out + (nt * VOUT * cs_out + cb * 16));
     };
     if constexpr (ILP) {
         f32x4 acc[PER][MTM];
@@ -1020,7 +1082,7 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
                                               const float* __restrict__ in, float* __restrict__ z, float* __restrict__ out,
                                               const float* __restrict__ embl, int wave, int lane, Prof& prof, int prof_id,
                                               H1&& pre_gemm, H2&& pre_barrier,
-                                              const LayerAfr<(CIN / 16) * (RES ? 2 : 1)>* pre_afr = nullptr) {
+                                              const LayerAfr<(CIN / 16) * (RES ? 2 : 1)>* pre_afr = nullptr, const StageRow* rows = nullptr) {
     constexpr int MT = ceil16(COUT) / 16;
     constexpr int COLS = NB * T * V;
     constexpr int NT = ceil16(COLS) / 16;
@@ -1035,6 +1097,9 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
     // costs every tile a scalar compare / select / branch set and two VALU instructions (a move of the selected offset and an
     // add) -- and the weight pointers are formed from 32-bit byte offsets (wptr)
     constexpr bool TSEL = SLOTSEL && HASEMB && NB == 2 && T == 3;
+    // ... and the mixes of one output frame per unit (6 or 12 units on 8 waves: the unit maps that cost a division by 3 per use)
+    // take their units' LDS addresses from the caller's stage-table rows (StageRow; one row per round)
+    constexpr bool ROWS = TSEL && MixCfg<CIN, V, T, NB>::QC == 1;
     const float* bias = wptr<TSEL>(wb, lw.bias);
     float4 bcur;
     if (pre_afr != nullptr) {
@@ -1047,15 +1112,21 @@ __device__ __forceinline__ void layer_generic(const float* wb, const LayerW lw, 
         // latency hides behind the mix as well)
         bcur = load_global4(bias + (wave % MT) * 16 + 4 * (lane >> 4));
     }
-    mix_stage<CIN, V, T, NB, FORCE, HASEMB>(in, CSX, mc, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
+    mix_stage<CIN, V, T, NB, FORCE, HASEMB, ROWS>(in, CSX, mc, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                              ZeroInit{},
-                             [&](int n, int q, int w, ChIdx c, auto v) {
+                             [&](int n, int q, int w, auto c, auto v) {
                                  // joint w's row, the lane's channels: the unit's part of the address on the scalar unit, the lane's
                                  // part (w CSI + channel offset) one v_mad (see load_x)
+                                 if constexpr (ROWS) {      // the unit's part: out_b of its table row
+                                     const unsigned za = c.ob + 4u * (unsigned)(__mul24(w, CSI) + c.j);
+                                     if constexpr (std::is_same_v<decltype(v), f32x4>) lds_store4(za, v[0], v[1], v[2], v[3]);
+                                     else *(lds_float*)(uintptr_t)za = v;
+                                 } else {
                                  float* zp = (z + (n * (T * V) * CSI + q * (V * CSI) + c.cb16)) + (__mul24(w, CSI) + c.j);
                                  if constexpr (std::is_same_v<decltype(v), f32x4>) lds_store4(lds_addr(zp), v[0], v[1], v[2], v[3]);   // 4 channels: one ds_write_b128
                                  else *zp = v;                                                                                       // joint 16, one channel
-                             });
+                                 }
+                             }, rows);
     prof.trace(trs + 1);
     // The NEXT stage's coefficient loads.  The vector-memory path accepts ~1 wave-wide load per 10 cycles and all eight waves
     // issue 10 .. 40 of them at the same point of the stage: in front of the GEMM tiles (where they used to be) the last
@@ -1197,10 +1268,10 @@ __device__ __forceinline__ void load_lafr(LAfr<L>& A, const float* wb, int wave,
 template <int L, int T, int NB, bool FORCE = false, int CSX = cs_of(layer_desc(L).cin), class H1, class H2>
 __device__ __forceinline__ void layer_std(const float* wb, const LMix<L, T, NB>& mc, const float* in, float* z, float* out,
                                           const float* emb, int wave, int lane, Prof& prof, H1&& pre_gemm, H2&& pre_barrier,
-                                          const LAfr<L>* pre_afr = nullptr) {
+                                          const LAfr<L>* pre_afr = nullptr, const StageRow* rows = nullptr) {
     constexpr LDesc D = layer_desc(L);
     layer_generic<D.cin, D.cout, D.V, D.res != 0, true, T, NB, FORCE, CSX, true>(wb, layer_w(wb, L), mc, in, z, out, emb + emb_off(L), wave, lane,
-                                                               prof, 32 + 3 * L, pre_gemm, pre_barrier, pre_afr);
+                                                               prof, 32 + 3 * L, pre_gemm, pre_barrier, pre_afr, rows);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1310,6 +1381,9 @@ struct Plan {
     static constexpr int TOTAL = R + XT + EMB + EAUX + ZN + WM + BIA + UPD + ZO + TT + CE + LOSS + EXW + PROF;
     static_assert((size_t)TOTAL * 4 <= 160 * 1024, "LDS plan: more than 160 KB");
     static constexpr size_t BYTES = (size_t)TOTAL * 4;
+    // where score_kernel's carve-up puts the regions a stage-table row points into (floats from the start of the dynamic LDS)
+    static constexpr int O_XT = R, O_EMB = O_XT + XT, O_E10 = O_EMB + EMB, O_ZN = O_E10 + EAUX, O_WM = O_ZN + ZN, O_BIA = O_WM + WM,
+                         O_UPD = O_BIA + BIA, O_ZO = O_UPD + UPD;
 };
 
 }  // namespace mcd

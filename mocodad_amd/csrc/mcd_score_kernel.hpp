@@ -3,6 +3,7 @@
 #pragma once
 #include "mcd_device.hpp"
 #include "mcd_encode_kernel.hpp"
+#include "mcd_stage_table.hpp"
 
 namespace mcd {
 
@@ -20,15 +21,15 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     constexpr int COLS17 = NB * TV17;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const RG = smem;                 // work region (see Plan)
-    float* const XT = RG + PL::R;
-    float* const EMB = XT + PL::XT;
-    float* const E10 = EMB + PL::EMB;
+    float* const XT = smem + PL::O_XT;      // (Plan::O_*: the offsets the stage table's rows are generated from)
+    float* const EMB = smem + PL::O_EMB;
+    float* const E10 = smem + PL::O_E10;
     float* const SEN = E10 + 32;
-    float* const ZN = E10 + PL::EAUX;
-    int* const WM = reinterpret_cast<int*>(ZN + PL::ZN);
-    float* const BIA = reinterpret_cast<float*>(WM + PL::WM);
-    int* const UPD = reinterpret_cast<int*>(BIA + PL::BIA);
-    float* const ZO = reinterpret_cast<float*>(UPD + PL::UPD);
+    float* const ZN = smem + PL::O_ZN;
+    int* const WM = reinterpret_cast<int*>(smem + PL::O_WM);
+    float* const BIA = smem + PL::O_BIA;
+    int* const UPD = reinterpret_cast<int*>(smem + PL::O_UPD);
+    float* const ZO = smem + PL::O_ZO;
 
     const int tid0 = threadIdx.x;
     int tid = tid0;
@@ -190,6 +191,26 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     // a W-first GEMM's pad-column test (only the slot that holds the last real column keeps it) and gemm_tiles' SLOTK -- and the
     // step loop forms its weight pointers from 32-bit byte offsets (wptr)
     constexpr bool TSEL = T == 3 && NB == 2;
+    // ... and the stages whose unit map is not a shift of the wave index take their units' LDS addresses from the per-wave stage
+    // table (mcd_stage_table.hpp): one row load per unit, issued with the stage's coefficient prefetch, instead of ~15 scalar
+    // instructions per unit and use.  srows(r, id): rows id .. of this wave through `tbw` (table + wave x rows, opaque per pass like wb)
+    const unsigned lds0 = (unsigned)(uintptr_t)(lds_float*)smem;
+    const StageRow* tbw = nullptr;
+    auto stage_rows_of = [&](int wv) {
+        if constexpr (TSEL) {
+            static_assert(stage_tab_checked<T, NB>());
+            const StageRow* tb = &StageTab<T, NB>::tab.r[0][0];
+            asm volatile("" : "+s"(tb));
+            tbw = tb + wv * srow::NROWS;
+        }
+    };
+    auto srows = [&](auto& r, int id) {
+        if constexpr (TSEL) {
+#pragma unroll
+            for (int k = 0; k < (int)std::extent_v<std::remove_reference_t<decltype(r)>>; ++k) r[k] = stage_row(tbw, id + k, lds0);
+        }
+    };
+    StageRow r0[1], r1[1], r2[2], rdn1[2], r3[2], r8[2], rup2[2], r9[2], r10[1];
 
     const int i_first = P.mode == 1 ? P.step_single : P.ns - 1;
     const int i_last = P.mode == 1 ? P.step_single : 1;
@@ -261,6 +282,8 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
     constexpr bool WEARLY = T <= 4;
     LAfr<0> A0;
     if constexpr (WEARLY) load_lafr<0>(A0, P.wbuf, wave, lane);
+    stage_rows_of(wave);
+    srows(r0, srow::L0);
     for (int sidx = i_first; sidx >= i_last; --sidx) {
         const float* srow = P.step_table + sidx * (4 + EDIM);
         const float* wb = P.wbuf;
@@ -271,6 +294,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         asm volatile("" : "+v"(tid));
         lane = tid & 63;
         wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        stage_rows_of(wave);
         if constexpr (MINW >= 4) {
             // Two workgroups share a CU, and the issue arbiter serves the OLDER one first on every SIMD: over a launch in which
             // each runs several trajectories the older one finished 18 % earlier and the younger one ran its last 400 us alone, at
@@ -336,6 +360,13 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         // rcX = resampler fragments) before its own closing barrier, so no stage starts with an L2 round trip.
         auto mixload = [&](auto& mc, int l) { mc.load(wptr<TSEL>(wb, tab_i(wb, l * F_STRIDE + F_TQ)), wptr<TSEL>(wb, tab_i(wb, l * F_STRIDE + F_AM)), wave, lane); };
         auto rsload = [&](auto& rc, int r) { rc.load(wptr<TSEL>(wb, tab_i(wb, TAB_RSW + r)), wptr<TSEL>(wb, tab_i(wb, TAB_RSB + r)), lane); };
+        // ... of a stage-table stage (TSEL): its rows first, then the coefficients of the unit's frame at the row's byte offsets
+        auto wptrb = [&](unsigned bytes) { return reinterpret_cast<const float*>(reinterpret_cast<const char*>(wb) + bytes); };
+        auto mixrow_at = [&](auto& mc, int tq, int am, const StageRow& r) { mc.load_at(wptrb(4u * (unsigned)tq + r.tq_o), wptrb(4u * (unsigned)am + r.af_o), lane); };
+        auto mixrows = [&](auto& mc, int l, auto& r, int id) {
+            if constexpr (TSEL) { srows(r, id); mixrow_at(mc, tab_i(wb, l * F_STRIDE + F_TQ), tab_i(wb, l * F_STRIDE + F_AM), r[0]); }
+            else mixload(mc, l);
+        };
         auto mix_early = mixload;
         auto rs_early = rsload;
         NoHook nohook;
@@ -353,7 +384,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         auto wearly = [&](auto& A, auto lc) { if constexpr (WEARLY) load_lafr<decltype(lc)::value, TSEL>(A, wb, wave, lane); };
 #define MCD_LC(l) std::integral_constant<int, l>{}
         layer_std<0, T, NB, LOWO, 4>(wb, mc0, XT, RG + PL::L0_z, RG + PL::L0_out, EMB, wave, lane, prof,
-                            [&] { mix_early(mc1, 1); }, [&] { wearly(A1, MCD_LC(1)); }, WEARLY ? &A0 : nullptr);     // sp1a (2 -> 16)
+                            [&] { mixrows(mc1, 1, r1, srow::L1); }, [&] { wearly(A1, MCD_LC(1)); }, WEARLY ? &A0 : nullptr, r0);     // sp1a (2 -> 16)
         STAGE(2);
         lt_dump(0, RG + PL::L0_out, 20, 16, 17);
         lt_inject(1, RG + PL::L1_in, 20, 16, 17);
@@ -363,21 +394,21 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         // exp -- by the idle waves too, not on wave 0's path at the top of the pass
         silu_row(sidx > 0 ? sidx - 1 : 0, tid - NZ_T0);
         layer_std<1, T, NB, LOWO>(wb, mc1, RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, EMB, wave, lane, prof,
-                            [&] { mix_early(mc2, 2); }, [&] { wearly(A2, MCD_LC(2)); }, WEARLY ? &A1 : nullptr);     // sd1.0
+                            [&] { mixrows(mc2, 2, r2, srow::L2); }, [&] { wearly(A2, MCD_LC(2)); }, WEARLY ? &A1 : nullptr, r1);     // sd1.0
         STAGE(3);
         lt_dump(1, RG + PL::L1_out, 36, 32, 17);
         lt_inject(2, RG + PL::L2_in, 36, 32, 17);
         RsCoef<32, 17, 12, T, NB, true> rc1;
         LMix<3, T, NB> mc3;
+        // (SQ12: down1 / up2 take their units in the order of layer 8's W-first mix, so that up2 follows that mix without a barrier)
+        constexpr bool SQ12 = !LT && MixCfg<32, 12, T, NB>::SAMEQ;
         layer_std<2, T, NB, LOWO>(wb, mc2, RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, EMB, wave, lane, prof,
-                            [&] { rs_early(rc1, 0); }, [&] { if constexpr (EARLY2) mix_early(mc3, 3); }, WEARLY ? &A2 : nullptr);      // sd1.1 -> d1
+                            [&] { rs_early(rc1, 0); if constexpr (SQ12) srows(rdn1, srow::DN1); }, [&] { if constexpr (EARLY2) mixrows(mc3, 3, r3, srow::L3); }, WEARLY ? &A2 : nullptr, r2);      // sd1.1 -> d1
         STAGE(4);
         lt_dump(2, RG + PL::L2_out, 36, 32, 17);
         lt_inject(11, RG + PL::L2_out, 36, 32, 17);
-        if constexpr (!EARLY2) mix_early(mc3, 3);
-        // (SQ12: down1 / up2 take their units in the order of layer 8's W-first mix, so that up2 follows that mix without a barrier)
-        constexpr bool SQ12 = !LT && MixCfg<32, 12, T, NB>::SAMEQ;
-        resample_stage<32, 17, 12, T, NB, true, false, LOWO, SQ12>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc1, skip1, wave, lane);  // down1 (captures d1)
+        if constexpr (!EARLY2) mixrows(mc3, 3, r3, srow::L3);
+        resample_stage<32, 17, 12, T, NB, true, false, LOWO, SQ12, TSEL && SQ12>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc1, skip1, wave, lane, rdn1);  // down1 (captures d1)
         wearly(A3, MCD_LC(3));
         bsync();
         STAGE(5);
@@ -385,7 +416,7 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
         lt_inject(3, RG + PL::L3_in, 36, 32, 12);
         LMix<4, T, NB> mc4;
         layer_std<3, T, NB, LOWO>(wb, mc3, RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, EMB, wave, lane, prof,
-                            [&] { mix_early(mc4, 4); }, [&] { wearly(A4, MCD_LC(4)); }, WEARLY ? &A3 : nullptr);     // sd2.0
+                            [&] { mix_early(mc4, 4); }, [&] { wearly(A4, MCD_LC(4)); }, WEARLY ? &A3 : nullptr, r3);     // sd2.0
         STAGE(6);
         lt_dump(3, RG + PL::L3_out, 68, 64, 12);
         lt_inject(4, RG + PL::L4_in, 68, 64, 12);
@@ -516,7 +547,11 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             lt_dump(7, RG + PL::L7_out, 68, 64, 12);
             lt_inject(8, RG + PL::L8_in, 68, 64, 12);
             float* Pb = RG + PL::L8_p;
-            if constexpr (!EARLY2) mc8w.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
+            srows(r8, srow::L8);
+            if constexpr (!EARLY2) {
+                if constexpr (TSEL) mixrow_at(mc8w, lw.tq, lw.am, r8[0]);
+                else mc8w.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
+            }
             auto epi8 = [&](auto ti, int col, int c0, f32x4 acc, int col0, int) {
                 constexpr int STEP = Tiling<4, NT>::NG * 16 * 68;
                 constexpr bool FULL = TSEL && (decltype(ti)::value + 1) * Tiling<4, NT>::NG * 16 <= COLS;
@@ -528,18 +563,33 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                 load_afrags<4, 4>(reinterpret_cast<const float4*>(wptr<TSEL>(wb, lw.wp)), wave, lane, afr8, mi);
                 gemm_tiles<4, NT, 4, 0, false, LOWO, LOWO, TSEL>(afr8, RG + PL::L8_in, 68, RG + PL::L8_in, 68, wave, lane, epi8, mi);
             }
-            if constexpr (EARLY2) { rs_early(rc4, 3); mix_early(mc9, 9); }      // up2's fragments, layer 9's mix coefficients
+            if constexpr (EARLY2) { rs_early(rc4, 3); if constexpr (SQ12) srows(rup2, srow::UP2); mixrows(mc9, 9, r9, srow::L9); }      // up2's fragments, layer 9's mix coefficients
             bsync();
             prof.mark(32 + 3 * 8 + 1);                                          // (the tool's "gemm" column of layer 8)
             const float slope8 = lw.slope;
             const float pinf8 = prelu_bound(slope8);
-            mix_stage<32, 12, T, NB, LOWO, true>(Pb, 68, mc8w, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
-                                     [&](int n, int q, int w, ChIdx c) {   // P_r of joint w, the lane's 4 channels (w >= 12: the next frame's rows, inside the region, never stored)
+            // (TSEL: the unit's P_r rows, embedding row and bias block are its stage-table row's out_b / aux_b / aux2_b)
+            mix_stage<32, 12, T, NB, LOWO, true, TSEL>(Pb, 68, mc8w, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
+                                     [&](int n, int q, int w, auto c) {   // P_r of joint w, the lane's 4 channels (w >= 12: the next frame's rows, inside the region, never stored)
+                                         if constexpr (TSEL) {
+                                             const float4 r = lds_load4(c.ob + 4u * (unsigned)(__mul24(w, 68) + c.j));
+                                             return f32x4{r.x, r.y, r.z, r.w};
+                                         } else {
                                          const float* pp = (Pb + (n * (T * 12) * 68 + q * (12 * 68) + 32 + c.cb16)) + (__mul24(w, 68) + c.j);
                                          const float4 r = lds_load4(lds_addr(pp));
                                          return f32x4{r.x, r.y, r.z, r.w};
+                                         }
                                      },
-                                     [&](int n, int q, int w, ChIdx c, f32x4 v) {
+                                     [&](int n, int q, int w, auto c, f32x4 v) {
+                                         if constexpr (TSEL) {
+                                             const float4 b4 = lds_load4(c.ab2 + 4u * (unsigned)c.j);
+                                             const float4 e4 = lds_load4(c.ab + 4u * (unsigned)c.j);
+                                             const f32x2 t0 = f32x2{v[0], v[1]} + f32x2{b4.x, b4.y}, t1 = f32x2{v[2], v[3]} + f32x2{b4.z, b4.w};
+                                             const f32x2 m0 = t0 * slope8, m1 = t1 * slope8;
+                                             const f32x2 r0 = f32x2{__builtin_amdgcn_fmed3f(t0[0], m0[0], pinf8), __builtin_amdgcn_fmed3f(t0[1], m0[1], pinf8)} + f32x2{e4.x, e4.y};
+                                             const f32x2 r1 = f32x2{__builtin_amdgcn_fmed3f(t1[0], m1[0], pinf8), __builtin_amdgcn_fmed3f(t1[1], m1[1], pinf8)} + f32x2{e4.z, e4.w};
+                                             lds_store4(c.ob + 4u * (unsigned)(__mul24(w, 68) + c.j), r0[0], r0[1], r1[0], r1[1]);
+                                         } else {
                                          const float4 b4 = lds_load4(lds_addr(BIA + 80 + c.cb16) + 4u * (unsigned)c.j);
                                          const float4 e4 = lds_load4(lds_addr(EMB + n * EMB_STRIDE + emb_off(8) + c.cb16) + 4u * (unsigned)c.j);
                                          float* pp = (Pb + (n * (T * 12) * 68 + q * (12 * 68) + 32 + c.cb16)) + (__mul24(w, 68) + c.j);
@@ -548,15 +598,16 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
                                          const f32x2 r0 = f32x2{__builtin_amdgcn_fmed3f(t0[0], m0[0], pinf8), __builtin_amdgcn_fmed3f(t0[1], m0[1], pinf8)} + f32x2{e4.x, e4.y};
                                          const f32x2 r1 = f32x2{__builtin_amdgcn_fmed3f(t1[0], m1[0], pinf8), __builtin_amdgcn_fmed3f(t1[1], m1[1], pinf8)} + f32x2{e4.z, e4.w};
                                          lds_store4(lds_addr(pp), r0[0], r0[1], r1[0], r1[1]);
-                                     });
-            if constexpr (!EARLY2) rs_early(rc4, 3);
+                                         }
+                                     }, r8);
+            if constexpr (!EARLY2) { rs_early(rc4, 3); if constexpr (SQ12) srows(rup2, srow::UP2); }
             if constexpr (!SQ12) bsync();      // (SQ12: up2's unit (frame, block) is the one this wave's mix unit just wrote)
             prof.mark(32 + 3 * 8);                                              // (the tool's "mix" column: mix + epilogue)
             STAGE(14);
             lt_dump(8, RG + PL::L8_p + 32, 68, 32, 12);
             lt_inject(14, RG + PL::L8_p + 32, 68, 32, 12);
-            if constexpr (!EARLY2) mix_early(mc9, 9);
-            resample_stage<32, 12, 17, T, NB, false, true, LOWO, SQ12>(RG + PL::L8_p + 32, 68, RG + PL::UP2_out, 36, rc4, skip1, wave, lane);  // up2 (+ d1)
+            if constexpr (!EARLY2) mixrows(mc9, 9, r9, srow::L9);
+            resample_stage<32, 12, 17, T, NB, false, true, LOWO, SQ12, TSEL && SQ12>(RG + PL::L8_p + 32, 68, RG + PL::UP2_out, 36, rc4, skip1, wave, lane, rup2);  // up2 (+ d1)
         }
         wearly(A9, MCD_LC(9));
         bsync();
@@ -574,9 +625,11 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             auto ef_load = [&] { ef.template load<TSEL>(wb, tid); };
             layer_std<9, T, NB, LOWO>(wb, mc9, RG + PL::L9_in, RG + PL::L9_z, RG + PL::L9_out, EMB, wave, lane, prof,
                                 [&] {
-                                    mc10.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
+                                    srows(r10, srow::L10);
+                                    if constexpr (TSEL) mixrow_at(mc10, lw.tq, lw.am, r10[0]);
+                                    else mc10.load(wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane);
                                     ef_load();
-                                }, nohook, WEARLY ? &A9 : nullptr);                                      // su3.0
+                                }, nohook, WEARLY ? &A9 : nullptr, r9);                                      // su3.0
             STAGE(16);
             lt_dump(9, RG + PL::L9_out, 36, 32, 17);
             lt_inject(10, RG + PL::L10_in, 36, 32, 17);
@@ -614,15 +667,23 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
             const float slope10 = lw.slope;
             const bool single = P.mode == 1, zadd = sidx > 1;
             const int e10_off = (sidx & 1) * 16;
-            mix_stage<16, 17, T, NB, LOWO, true>(Pb, 20, mc10, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
+            mix_stage<16, 17, T, NB, LOWO, true, TSEL>(Pb, 20, mc10, wptr<TSEL>(wb, lw.tq), wptr<TSEL>(wb, lw.am), wave, lane,
                                      ZeroInit{},
-                                     [&](int n, int t, int w, ChIdx c, auto val) {
+                                     [&](int n, int t, int w, auto c, auto val) {
+                                         if constexpr (TSEL) {          // (the unit's frame ZO[(n T + t) 17][.]: out_b of its stage-table row)
+                                             lds_float* zo = (lds_float*)(uintptr_t)c.ob;
+                                             if constexpr (std::is_same_v<decltype(val), f32x4>) {
+                                                 if (c.j == 0) *(lds_f32x2*)(zo + w * C0) = f32x2{val[0], val[1]};
+                                             } else {
+                                                 if (c.j < C0) zo[w * C0 + c.j] = val;
+                                             }
+                                         } else
                                          if constexpr (std::is_same_v<decltype(val), f32x4>) {     // joint w, channels c.j .. c.j + 3: the two coordinates are lane group 0's
                                              if (c.j == 0) *reinterpret_cast<float2*>(ZO + ((n * T + t) * 17 + w) * C0) = make_float2(val[0], val[1]);
                                          } else {                                                  // joint 16, channel c.j
                                              if (c.j < C0) ZO[((n * T + t) * 17 + w) * C0 + c.j] = val;
                                          }
-                                     });
+                                     }, r10);
             bsync();
             // element-wise tail of the pass, one (column, coordinate) per thread: eps = PReLU(mix(P_t) + P_r + b) + e + x
             // (layer 10 + the U-Net's residual), then the DDPM update of the frame this prediction drives and the next
@@ -667,7 +728,9 @@ __global__ __launch_bounds__(NTHREADS, MINW) void score_kernel(const ScoreParams
 #pragma unroll
             for (int it = 0; it < TAIL_IT; ++it)
                 if (dst_t[it] >= 0) XT[dst_t[it]] = xn_t[it];
-            mc0.load(wptr<TSEL>(wb, tab_i(wb, F_TQ)), wptr<TSEL>(wb, tab_i(wb, F_AM)), wave, lane);      // for the next pass
+            srows(r0, srow::L0);
+            if constexpr (TSEL) mixrow_at(mc0, tab_i(wb, F_TQ), tab_i(wb, F_AM), r0[0]);      // for the next pass
+            else mc0.load(wptr<TSEL>(wb, tab_i(wb, F_TQ)), wptr<TSEL>(wb, tab_i(wb, F_AM)), wave, lane);
             wearly(A0, MCD_LC(0));
             STAGE(21);
             bsync();
