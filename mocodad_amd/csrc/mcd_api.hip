@@ -665,6 +665,43 @@ int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n,
     return MCD_OK;
 }
 
+// rows (windows) one group may hold: n_slots * (ring_len - seg_len + 1), the per-track bound times the tracks
+static int64_t stream_group_rows(const mcd_stream_state_t* s) { return (int64_t)s->n_slots * (s->ring_len - s->seg_len + 1); }
+
+int mcd_stream_push_group(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_windows,
+                          float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
+                          int32_t* trans_out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_params(s, &P)) return rc;
+    if (n < 0 || n_windows < 0 || n_windows > n) return fail(MCD_EINVAL, "need 0 <= n_windows <= n");
+    if (n > stream_group_rows(s))
+        return fail(MCD_EINVAL, "more rows than n_slots * (ring_len - seg_len + 1): a group holds at most ring_len - seg_len + 1 rows per track");
+    if ((int64_t)n_windows * P.nt > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    if (n == 0) return MCD_OK;
+    if (!raw || !desc || (n_windows > 0 && (!base_out || !trans_out))) return fail(MCD_EINVAL, "null argument");
+    hipLaunchKernelGGL(stream_push_group_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, raw, desc,
+                       n, n_windows * P.nt, vid_w, vid_h, center, scale, reinterpret_cast<long long*>(base_out), trans_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_windows,
+                                  float* final_out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_params(s, &P)) return rc;
+    if (n_windows < 0 || n_windows > stream_group_rows(s)) return fail(MCD_EINVAL, "need 0 <= n_windows <= n_slots * (ring_len - seg_len + 1)");
+    if (n_windows == 0) return MCD_OK;
+    if (!scores || !win || !final_out) return fail(MCD_EINVAL, "null argument");
+    const long long total = (long long)n_windows * P.nt;
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    hipLaunchKernelGGL(stream_frame_scores_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
+                       scores, win, n_windows, (int)total, final_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 
 int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* c) {
     if (!c || c->n_clips <= 0 || c->num_transform <= 0 || c->n_persons <= 0 || c->max_frames <= 0) return 0;

@@ -4,6 +4,7 @@
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
 //   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
 //                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
+//   stream_push_group / stream_frame_scores_group kernels   the same for a group of ticks in one launch each
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
@@ -273,6 +274,62 @@ __global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const
     const int slot = win[2 * i], r_last = win[2 * i + 1];
     if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
     out[u] = S.fs[((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L];
+}
+
+// A GROUP of ticks in one launch (PoseStream.push_many): a track may receive R <= L - seg_len + 1 rows, so the rows
+// r0 - seg_len + 1 .. r0 + R - 1 of a track -- the pending ones and the new ones -- sit at distinct ring positions, and no two
+// rows of the launch share a pose position or a frame-score cell.  The group's windows are tick-major, inside a tick
+// transform-major: the window of transform t of a row is at batch position pos0 + t * ne, with ne = its tick's window count.
+// one thread per pushed row: desc (n, 4) = [slot, row index r, pos0 | -1, ne]; n_win = windows x transforms of the group
+__global__ __launch_bounds__(256) void stream_push_group_kernel(StreamParams S, const float* __restrict__ raw,
+                                                                const int* __restrict__ desc, int n, int n_win, float vid_w,
+                                                                float vid_h, const double* __restrict__ center,
+                                                                const double* __restrict__ scale, long long* __restrict__ base_out,
+                                                                int* __restrict__ trans_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int slot = desc[4 * i], r = desc[4 * i + 1], pos0 = desc[4 * i + 2], ne = desc[4 * i + 3];
+    if (slot < 0 || slot >= S.n_slots || r < 0) return;        // (a descriptor the host table cannot produce: touch nothing)
+    const int p = r % S.L;
+    float* o = S.ring + ((size_t)slot * 2 * S.L + p) * 34;
+    normalize_pose_row(raw + (size_t)i * 34, vid_w, vid_h, center, scale, o, o + (size_t)S.L * 34);
+    for (int t = 0; t < S.nt; ++t) S.fs[((size_t)slot * S.nt + t) * S.L + p] = 0.f;
+    if (pos0 < 0 || ne < 1 || r < S.seg_len - 1 || (long long)pos0 + (long long)(S.nt - 1) * ne >= n_win) return;
+    const long long base = ((long long)slot * 2 * S.L + (r - S.seg_len + 1) % S.L) * 34;
+    for (int t = 0; t < S.nt; ++t) {
+        base_out[(size_t)pos0 + (size_t)t * ne] = base;
+        trans_out[(size_t)pos0 + (size_t)t * ne] = t;
+    }
+}
+
+// win (n, 5) = [slot, r_last, pos0, ne, w] per window, sorted by slot and, within a slot, by row; w = the window's index in
+// (tick, j) order = its row of final_out (n, num_transform).  The windows of one track overlap, so one thread per (track,
+// transform) -- the thread of the track's FIRST window -- applies them in row order with plain loads and stores: the cells end
+// as after tick-by-tick stream_frame_scores_kernel launches, and each window's oldest row is final once that window is in.
+// (An emitting slot holds ONE track within a group: a slot is only handed out again inside a group when its track got no row in it.)
+__global__ __launch_bounds__(256) void stream_frame_scores_group_kernel(StreamParams S, const float* __restrict__ scores,
+                                                                        const int* __restrict__ win, int n, int n_win,
+                                                                        float* __restrict__ final_out) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n * S.nt) return;
+    const int q0 = u / S.nt, t = u - q0 * S.nt;
+    const int slot = win[5 * q0];
+    if (slot < 0 || slot >= S.n_slots) return;
+    if (q0 > 0 && win[5 * (q0 - 1)] == slot) return;           // not the track's first window: the thread of that one walks on
+    float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
+    for (int q = q0; q < n && win[5 * q] == slot; ++q) {
+        const int r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
+        const long long pos = (long long)pos0 + (long long)t * ne;
+        if (r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos >= n_win || w < 0 || w >= n) continue;
+        const float sc = fmaxf(scores[pos], 0.f);
+        const int first = r_last - S.seg_len + 1;
+        for (int k = S.seg_len - 1; k >= 0; --k) {
+            float* c = row + (first + k) % S.L;
+            const float m = fmaxf(*c, sc);
+            *c = m;
+            if (k == 0) final_out[(size_t)w * S.nt + t] = m;
+        }
+    }
 }
 
 

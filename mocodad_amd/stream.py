@@ -17,7 +17,12 @@ oldest row of each window is final and comes back).
 NumPy and imports no GPU module.  Windows follow the reference's rule (utils/preprocessing.py:14-86, the rule
 TrajectoryWindows.from_buffer implements): they run over CONSECUTIVE ROWS of a track, frame-number gaps included, so
 meta = [scene, clip, person, frame id of the window's first row] and frames = the frame ids of its seg_len rows.
-`PoseStream` owns the rings (engine.StreamRings) and the staging buffers and drives the launches of a tick."""
+`PoseStream` owns the rings (engine.StreamRings) and the staging buffers and drives the launches of a tick.
+
+Several ticks at once (a pose estimator that delivers frames in batches, a stream catching up, recorded video on the online path):
+`PoseStream.push_many` returns what the same ticks pushed one by one return, bit for bit, but runs them in launch groups --
+`pack_ticks` cuts the call into groups of consecutive ticks that the rings can hold at once (ring_len - seg_len + 1 rows per
+track), and a group is one copy, mcd_stream_push_group, ONE scoring call on all of its windows, mcd_stream_frame_scores_group."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -40,6 +45,7 @@ class ClosePlan:
     keys: List[Key] = field(default_factory=list)
     win: np.ndarray = None            # (n, 2) int32 [slot, index of the track's last row]
     frames: np.ndarray = None         # (n, seg_len - 1) int32 frame ids of the pending rows
+    slots: List[int] = field(default_factory=list)   # every slot freed, those of shorter tracks (absent above) included
 
     def __len__(self):
         return len(self.keys)
@@ -99,6 +105,26 @@ class TrackTable:
     def free_slots(self) -> int:
         return len(self._free)
 
+    def copy(self) -> "TrackTable":
+        """An independent table in the same state (pack_ticks plans a call on one)."""
+        t = TrackTable.__new__(TrackTable)
+        t.__dict__.update(self.__dict__)
+        t.slot_of, t._free, t._closed = dict(self.slot_of), list(self._free), set(self._closed)
+        t.rows, t._fids, t._last_tick = self.rows.copy(), self._fids.copy(), self._last_tick.copy()
+        return t
+
+    def same_state(self, other: "TrackTable") -> bool:
+        """Every field equal: the next pushes and closes of both tables give the same plans."""
+        return ((self.max_tracks, self.seg_len, self.ring_len, self.max_idle, self.tick) ==
+                (other.max_tracks, other.seg_len, other.ring_len, other.max_idle, other.tick)
+                and list(self.slot_of.items()) == list(other.slot_of.items()) and self._free == other._free
+                and self._closed == other._closed and np.array_equal(self.rows, other.rows)
+                and np.array_equal(self._fids, other._fids) and np.array_equal(self._last_tick, other._last_tick))
+
+    def adopt(self, other: "TrackTable") -> None:
+        """Take over the state of `other` (a planned copy of this table; `other` is not to be used afterwards)."""
+        self.__dict__.update(other.__dict__)
+
     def base_offset(self, slot: int, first_row: int) -> int:
         """Element offset in the pose ring of the seg_len rows of `slot` from row `first_row` on."""
         return (slot * 2 * self.ring_len + first_row % self.ring_len) * ROW
@@ -109,6 +135,7 @@ class TrackTable:
         win, frames = [], []
         for k in keys:
             s = self.slot_of.pop(k)
+            plan.slots.append(int(s))
             if self.rows[s] >= T:          # (shorter tracks have no window and no frame score: offline they are dropped)
                 plan.keys.append(k)
                 win.append((s, self.rows[s] - 1))
@@ -183,6 +210,93 @@ class TrackTable:
 
 
 @dataclass
+class GroupPlan:
+    """Consecutive ticks of one call that share their launches (pack_ticks): one upload, one mcd_stream_push_group, one scoring
+    call, one mcd_stream_frame_scores_group.  The group's windows are tick-major, inside a tick transform-major: the window of
+    the j-th emitting row of tick i under transform t is at batch position offsets[i] * num_transform + t * n_emit_i + j."""
+    first_tick: int                   # index of the group's first tick in the call
+    plans: List[TickPlan]             # the plans of its ticks, exactly those of sequential TrackTable.push calls
+    desc: np.ndarray                  # (n, 4) int32 per pushed row, tick after tick: [slot, row index r, pos0 | -1, n_emit of its tick]
+    win: np.ndarray                   # (n_windows, 5) int32 [slot, r_last, pos0, n_emit of its tick, index in (tick, j) order],
+    #                                   sorted by slot, then row: the windows of a track are adjacent and ascending
+    offsets: np.ndarray               # (len(plans) + 1,) int64 windows (one transform) emitted before each tick of the group
+    closed: ClosePlan                 # the idle closures of all its ticks, tick after tick (none of them got a row in the group)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.desc.shape[0])
+
+    @property
+    def n_windows(self) -> int:
+        return int(self.offsets[-1])
+
+
+def _group(first_tick: int, plans: List[TickPlan], num_transform: int, seg_len: int) -> GroupPlan:
+    ne = np.asarray([p.n_emit for p in plans], np.int64)
+    offsets = np.zeros(len(plans) + 1, np.int64)
+    offsets[1:] = np.cumsum(ne)
+    desc, win = [], []
+    for i, p in enumerate(plans):
+        j = p.desc[:, 2].astype(np.int64)
+        pos0 = np.where(j >= 0, offsets[i] * num_transform + j, -1)
+        desc.append(np.stack([p.desc[:, 0], p.desc[:, 1], pos0, np.full(len(j), ne[i])], axis=1))
+        jj = np.arange(ne[i])
+        win.append(np.stack([p.win[:, 0], p.win[:, 1], offsets[i] * num_transform + jj, np.full(ne[i], ne[i]), offsets[i] + jj],
+                            axis=1))
+    desc = np.concatenate(desc).astype(np.int32).reshape(-1, 4)
+    win = np.concatenate(win).astype(np.int32).reshape(-1, 5)
+    win = win[np.argsort(win[:, 0], kind="stable")]            # (stable: within a slot the ticks, hence the rows, stay ascending)
+    closed = ClosePlan()
+    for p in plans:
+        closed.keys += p.closed.keys
+        closed.slots += p.closed.slots
+    closed.win = np.concatenate([p.closed.win for p in plans]).reshape(-1, 2)
+    closed.frames = np.concatenate([p.closed.frames for p in plans]).reshape(-1, seg_len - 1)
+    return GroupPlan(first_tick, plans, desc, win, offsets, closed)
+
+
+def pack_ticks(table: TrackTable, ticks, num_transform: int = 1, max_rows: Optional[int] = None):
+    """Plan a call of several ticks: ticks = [(keys, frame_ids), ...], each what one TrackTable.push takes.  Pure host logic on a
+    COPY of `table` -> (groups, the copy after the last tick); `table` itself is not changed, so a call that is rejected at tick
+    i (ValueError / RuntimeError of TrackTable.push, with "tick i: " in front) leaves no trace.  The caller adopts the copy.
+
+    Consecutive ticks share a group as long as
+      1. no track receives more than ring_len - seg_len + 1 rows in it (a track that gets R rows needs its rows
+         r0 - seg_len + 1 .. r0 + R - 1 alive at once: ring_len >= seg_len + R - 1; the same bound keeps a frame-score cell that
+         is zeroed from aliasing a pending one),
+      2. no slot that received a row in it is freed inside it (max_idle closes its track, whether or not the slot is handed out
+         again at once) -- idle closures of tracks WITHOUT a row in the group stay inside: their cells are final before the
+         group's first launch,
+      3. its rows number at most `max_rows` (default max_tracks * (ring_len - seg_len + 1), at least max_tracks).
+    With ring_len = seg_len every group is one tick."""
+    work = table.copy()
+    per_track = table.ring_len - table.seg_len + 1
+    cap = table.max_tracks * per_track if max_rows is None else int(max_rows)
+    if cap < table.max_tracks:
+        raise ValueError(f"max_rows = {cap} is less than max_tracks = {table.max_tracks}: one tick would not fit a group")
+    groups: List[GroupPlan] = []
+    first, plans, count, n_rows = 0, [], {}, 0
+    for i, (keys, fids) in enumerate(ticks):
+        try:
+            plan = work.push(keys, fids)
+        except (ValueError, RuntimeError) as e:
+            raise type(e)(f"tick {i}: {e}") from None
+        slots = plan.desc[:, 0].tolist()
+        # (ring_len = seg_len: one tick per group, today's launches, also where two ticks happen to share no track)
+        if plans and (per_track == 1 or n_rows + len(slots) > cap or any(count.get(s, 0) >= per_track for s in slots)
+                      or any(s in count for s in plan.closed.slots)):
+            groups.append(_group(first, plans, num_transform, table.seg_len))
+            first, plans, count, n_rows = i, [], {}, 0
+        plans.append(plan)
+        n_rows += len(slots)
+        for s in slots:
+            count[s] = count.get(s, 0) + 1
+    if plans:
+        groups.append(_group(first, plans, num_transform, table.seg_len))
+    return groups, work
+
+
+@dataclass
 class FrameScores:
     """Final per-row frame scores: row i belongs to track keys[i] at frame id frames[i]; values (n, num_transform) fp32 on the
     device = the maximum over the windows of that track covering the row, per transform."""
@@ -196,7 +310,7 @@ class FrameScores:
 
 @dataclass
 class Tick:
-    """Result of PoseStream.push.  The tick's windows are transform-major like the dataset order: entry t * n_emit + j is the
+    """Result of PoseStream.push (push_many: one per tick).  The tick's windows are transform-major like the dataset order: entry t * n_emit + j is the
     window of the j-th emitting track under transform t."""
     meta: np.ndarray                  # (num_transform * n_emit, 4) int64
     frames: np.ndarray                # (num_transform * n_emit, seg_len) int32
@@ -214,13 +328,14 @@ class PoseStream:
 
     vid_res, center, scale: as for engine.normalize_poses (center / scale (34,) = the fitted RobustScaler, or both None).
     max_tracks: slots of the device rings; ring_len: rows kept per track (>= seg_len, default seg_len);
-    num_transform: default the model's; max_idle: see TrackTable.
+    num_transform: default the model's; max_idle: see TrackTable; max_group_rows: cap on the rows of one launch group of
+    push_many (default and upper limit max_tracks * (ring_len - seg_len + 1), at least max_tracks): it sizes the staging buffers.
 
     One PoseStream is driven from ONE stream (the current stream of the first push): its rings, staging buffers and the track
     table are per-tick state, and the launches of a tick are ordered only by that stream."""
 
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
-                 num_transform: Optional[int] = None, max_idle: Optional[int] = None):
+                 num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None):
         import torch
         from .engine import StreamRings
         from .utils.transforms import affine_table
@@ -246,9 +361,14 @@ class PoseStream:
         self.ring = self.rings.ring
         with torch.cuda.device(dev):
             self.affine = affine_table(nt).to(dev)
-            # one tick's host-to-device traffic: raw rows (n, 34) f32 | descriptors (n, 3) i32 | windows (n, 2) i32, in ONE copy
-            self._pinned = torch.empty(n * (ROW + 3 + 2), dtype=torch.int32).pin_memory()
-            self._staged = torch.empty(n * (ROW + 3 + 2), device=dev, dtype=torch.int32)
+            # one group's host-to-device traffic: raw rows (n, 34) f32 | descriptors (n, 4) i32 | windows (n, 5) i32, in ONE copy
+            # (a tick of push: (n, 3) and (n, 2)); a group of push_many holds at most max_group_rows rows
+            per_track = self.table.ring_len - self.seg_len + 1
+            self.max_group_rows = n * per_track if max_group_rows is None else min(int(max_group_rows), n * per_track)
+            if self.max_group_rows < n:
+                raise ValueError(f"max_group_rows = {max_group_rows} is less than max_tracks = {n}: one tick would not fit a group")
+            self._pinned = torch.empty(self.max_group_rows * (ROW + 4 + 5), dtype=torch.int32).pin_memory()
+            self._staged = torch.empty(self.max_group_rows * (ROW + 4 + 5), device=dev, dtype=torch.int32)
             self._copied = torch.cuda.Event()
         self._host = self._pinned.numpy()
         self.n_emitted = 0          # windows (x transforms) emitted so far = first_window_id of the next tick
@@ -317,6 +437,77 @@ class PoseStream:
         return Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                     trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores, windows=wb,
                     final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final), closed=closed, first_window_id=first)
+
+    def push_many(self, ticks, *, noise=None) -> List[Tick]:
+        """Several ticks in one call: ticks = [(keys, frame_ids, poses), ...], each triple what one `push` takes.  Returns, bit
+        for bit, what [push(*t) for t in ticks] returns on a stream in the same state, and leaves the stream in the same state;
+        the work runs in as few launch groups as the rings allow (pack_ticks: with ring_len = seg_len one group per tick, with
+        ring_len = seg_len + K - 1 up to K ticks per group), each group ONE upload, mcd_stream_push_group, ONE scoring call and
+        mcd_stream_frame_scores_group.  The windows of a group are tick-major, so each keeps the global window id -- hence the
+        Philox draws -- sequential pushes give it, and every Tick holds contiguous views of its group's device tensors.
+        noise: (S, max(ns-1,1), windows of the whole call, ...) in that order: tick after tick, inside a tick as for `push`.
+        A rejected call (a bad shape, a non-finite row, a duplicate or closed key, no free slot: the error names the tick) changes
+        nothing."""
+        import torch
+        ticks = list(ticks)
+        raws = []
+        for i, t in enumerate(ticks):
+            if len(t) != 3:
+                raise ValueError(f"tick {i}: a tick is a (keys, frame_ids, poses) triple")
+            keys, _, poses = t
+            raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
+            if raw.ndim != 2 or raw.shape[1] != ROW or raw.shape[0] != len(keys):
+                raise ValueError(f"tick {i}: poses must be ({len(keys)}, {ROW}) = one row x1,y1,...,x17,y17 per key, got {raw.shape}")
+            if not np.isfinite(raw).all():
+                raise ValueError(f"tick {i}: raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+            raws.append(raw)
+        groups, planned = pack_ticks(self.table, [(t[0], t[1]) for t in ticks], self.num_transform, self.max_group_rows)
+        total = self.num_transform * sum(g.n_windows for g in groups)
+        if noise is not None and (noise.dim() < 3 or noise.shape[2] != total):
+            raise ValueError(f"noise must hold the {total} windows of the call on its third axis, got {tuple(noise.shape)}")
+        self.table.adopt(planned)
+        out, lo = [], 0
+        for g in groups:
+            nw = self.num_transform * g.n_windows
+            part = None if noise is None or not nw else noise if nw == total else noise[:, :, lo:lo + nw].contiguous()
+            out += self._run_group(g, raws[g.first_tick:g.first_tick + len(g.plans)], part)
+            lo += nw
+        return out
+
+    def _run_group(self, g: GroupPlan, raws, noise) -> List[Tick]:
+        import torch
+        from .data.windows import WindowBatch
+        n, nw, nt, dev, pend = g.n_rows, g.n_windows, self.num_transform, self.device, self.seg_len - 1
+        first = self.n_emitted
+        with torch.cuda.device(dev):
+            closed = self._flush(g.closed)            # before the new rows: a freed slot may be handed out again in this group
+            scores = torch.empty(nt * nw, device=dev, dtype=torch.float32)
+            if n:
+                raw_d, desc_d, win_d = self._upload([np.concatenate(raws), g.desc, g.win])
+                base, trans = self.rings.push_group(raw_d, desc_d, n, nw)
+            if nw:
+                m = self.model
+                wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
+                score = self.scorer.score if self.latent else self.scorer.score_fused
+                score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
+                      noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores)
+                final = self.rings.frame_scores_group(scores, win_d, nw)
+            else:
+                final = torch.empty(0, nt, device=dev, dtype=torch.float32)
+        self.n_emitted += nt * nw
+        out, c0 = [], 0
+        for i, plan in enumerate(g.plans):
+            ne, w0, c1 = plan.n_emit, int(g.offsets[i]), c0 + len(plan.closed)
+            a, b = nt * w0, nt * (w0 + ne)
+            wb = WindowBatch(self.ring, base[a:b], trans[a:b], self.affine, self.seg_len) if ne else None
+            tail = FrameScores(closed.keys[c0 * pend:c1 * pend], closed.frames[c0 * pend:c1 * pend].copy(),
+                               closed.values[c0 * pend:c1 * pend])
+            out.append(Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
+                            trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores[a:b], windows=wb,
+                            final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne]), closed=tail,
+                            first_window_id=first + a))
+            c0 = c1
+        return out
 
     def close(self, keys) -> FrameScores:
         """End the tracks `keys` and free their slots -> the frame scores of their last seg_len - 1 rows (tracks that never had

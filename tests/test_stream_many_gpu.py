@@ -1,0 +1,295 @@
+"""PoseStream.push_many on the GPU (mocodad_amd/stream.py over mcd_stream_push_group / mcd_stream_frame_scores_group): several ticks
+per call against a second PoseStream of the same model fed the same ticks one by one through `push`, on the committed dataset
+fixture with the settings of tests/test_stream_gpu.py.  Every comparison is exact (uint32 views): a compared value is a copy, a
+maximum, or the output of a scoring launch whose result does not depend on the batch it ran in, under noise keyed by the global
+window id."""
+import ctypes as C
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from dataset_spec import DATASET, ROOT, load_dataset_golden, stress_rows
+from mocodad_amd.data import trajectories as T
+from mocodad_amd.data.windows import WindowBatch
+from mocodad_amd.stream import PoseStream, ticks_by_frame
+
+pytestmark = pytest.mark.gpu
+SEG_LEN = 6
+VID_RES = (640, 360)
+DEV = "cuda:0"
+NT = 5
+
+
+def _bits(a):
+    if torch.is_tensor(a):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _model(tmp, g, latent=False):
+    """A random-init MoCoDAD (MoCoDADlatent) on the fixture's settings: noise_steps 4, 2 samples, 5 transforms."""
+    from sklearn.preprocessing import RobustScaler
+    from mocodad_amd.models.mocodad import MoCoDAD
+    from mocodad_amd.models.mocodad_latent import MoCoDADlatent
+    from mocodad_amd.utils.argparser import load_config
+    with open(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml" if latent else "hr_avenue_test.yaml")) as f:
+        cfg = yaml.safe_load(f)
+    cfg.update(data_dir=DATASET, test_path=os.path.join(DATASET, "testing", "test_frame_mask"), exp_dir=str(tmp / "exp"),
+               dataset_choice="HR-STC", dir_name="fixture", noise_steps=4, n_generated_samples=2, batch_size=256,
+               seg_len=SEG_LEN, vid_res=list(VID_RES), num_transform=NT, seed=11)
+    p = tmp / "cfg.yaml"
+    p.write_text(yaml.safe_dump(cfg))
+    args = load_config(str(p))
+    sc = RobustScaler(quantile_range=(10.0, 90.0))
+    sc.center_, sc.scale_ = g["train_center"], g["train_scale"]
+    os.makedirs(args.ckpt_dir, exist_ok=True)
+    with open(os.path.join(args.ckpt_dir, "local_robust.pickle"), "wb") as f:
+        pickle.dump(sc, f)
+    torch.manual_seed(123)
+    m = (MoCoDADlatent if latent else MoCoDAD)(args).to(DEV)
+    m.save_tensors = False
+    return m, args
+
+
+@pytest.fixture(scope="module")
+def env(tmp_path_factory):
+    g = load_dataset_golden()
+    m, args = _model(tmp_path_factory.mktemp("stream_many"), g)
+    files = T.list_trajectory_files(T.trajectories_root(DATASET, "test"))
+    tracks = [(key,) + T.read_trajectory_csv(path) for key, path in files]
+    ticks = [(keys, fids, poses) for _, keys, fids, poses in ticks_by_frame(tracks)]
+    assert len(tracks) == 22 and len(ticks) == 45
+    return dict(g=g, model=m, args=args, tracks=tracks, ticks=ticks)
+
+
+def _same_frame_scores(a, b):
+    assert a.keys == b.keys and a.frames.dtype == b.frames.dtype and np.array_equal(a.frames, b.frames)
+    assert a.values.shape == b.values.shape and a.values.dtype == b.values.dtype
+    assert np.array_equal(_bits(a.values), _bits(b.values))
+
+
+def _same_tick(a, b):
+    """Every field of two Ticks."""
+    for name in ("meta", "frames", "trans"):
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), name
+    assert a.scores.shape == b.scores.shape and a.scores.dtype == b.scores.dtype and a.scores.is_contiguous()
+    assert np.array_equal(_bits(a.scores), _bits(b.scores))
+    assert (a.windows is None) == (b.windows is None)
+    if a.windows is not None:
+        assert a.windows.base.dtype == b.windows.base.dtype and torch.equal(a.windows.base.cpu(), b.windows.base.cpu())
+        assert a.windows.trans.dtype == b.windows.trans.dtype and torch.equal(a.windows.trans.cpu(), b.windows.trans.cpu())
+        assert a.windows.seg_len == b.windows.seg_len and torch.equal(a.windows.affine.cpu(), b.windows.affine.cpu())
+    _same_frame_scores(a.final, b.final)
+    _same_frame_scores(a.closed, b.closed)
+    assert a.first_window_id == b.first_window_id
+    return a.scores.numel()
+
+
+def _same_state(a, b):
+    """Rings, table and window count of two streams."""
+    assert a.table.same_state(b.table) and a.n_emitted == b.n_emitted
+    assert np.array_equal(_bits(a.ring), _bits(b.ring))
+    assert np.array_equal(_bits(a.rings.frame_scores_ring), _bits(b.rings.frame_scores_ring))
+
+
+def _count_groups(stream):
+    """Counts the mcd_stream_push_group launches of `stream` (one per group that holds a row)."""
+    calls, inner = [], stream.rings.push_group
+
+    def counted(*a, **kw):
+        calls.append(1)
+        return inner(*a, **kw)
+    stream.rings.push_group = counted
+    return calls
+
+
+def _replay_many(many, single, tracks, ticks, k, noise_of_call=None):
+    """The fixture in frame order, k ticks per call: push_many on `many`, the same ticks one by one through push on `single`;
+    tracks are closed on both right after the call that held their last row.  Compares every Tick, every tail and the state
+    after every call; returns the ticks of `many`, the tails, and the group launches per call."""
+    left = {key: len(f) for key, f, _ in tracks}
+    groups = _count_groups(many)
+    out, tails, per_call, compared = [], [], [], 0
+    for lo in range(0, len(ticks), k):
+        call = ticks[lo:lo + k]
+        before = len(groups)
+        got = many.push_many(call, noise=None if noise_of_call is None else noise_of_call(lo, call))
+        per_call.append(len(groups) - before)
+        want = [single.push(*t) for t in call] if single is not None else got
+        assert len(got) == len(want) == len(call)
+        for a, b in zip(got, want):
+            compared += _same_tick(a, b)
+        done = []
+        for keys, _, _ in call:
+            for key in keys:
+                left[key] -= 1
+                if left[key] == 0:
+                    done.append(key)
+        if done:
+            tails.append((done, many.close(done)))
+            if single is not None:
+                _same_frame_scores(tails[-1][1], single.close(done))
+        if single is not None:
+            _same_state(many, single)
+        out += got
+    assert compared == 283 * NT == many.n_emitted
+    return out, tails, per_call
+
+
+@pytest.mark.parametrize("k", [1, 2, SEG_LEN, SEG_LEN + 1])
+def test_fixture_replay_k_ticks_per_call_equals_sequential_pushes(env, k):
+    """k = 1: the group entries on single ticks; 2: the smallest overlap inside a launch; seg_len: a track's first window made
+    only of rows of this group; seg_len + 1: a row is zeroed and finalised within one group.  Philox mode: the draws are keyed
+    by the global window id, which the tick-major order keeps."""
+    g, m = env["g"], env["model"]
+    kw = dict(vid_res=VID_RES, center=g["train_center"], scale=g["train_scale"], max_tracks=22, ring_len=SEG_LEN + k - 1)
+    many, single = PoseStream(m, **kw), PoseStream(m, **kw)
+    ticks, tails, per_call = _replay_many(many, single, env["tracks"], env["ticks"], k)
+    assert per_call == [1] * len(per_call) and len(per_call) == -(-45 // k)          # ONE group per call
+    assert sum(len(fs) for _, fs in tails) == (SEG_LEN - 1) * 14 and len(many.table) == 0
+    scores = np.concatenate([t.scores.cpu().numpy() for t in ticks])
+    assert np.isfinite(scores).all() and len(np.unique(scores)) > 1000                 # (not a constant: the test can fail)
+
+
+def test_whole_replay_in_one_call_is_cut_where_the_rings_demand(env):
+    g, m = env["g"], env["model"]
+    kw = dict(vid_res=VID_RES, center=g["train_center"], scale=g["train_scale"], max_tracks=22, ring_len=SEG_LEN + 3)
+    many, single = PoseStream(m, **kw), PoseStream(m, **kw)
+    _, tails, per_call = _replay_many(many, single, env["tracks"], env["ticks"], 45)
+    assert len(per_call) == 1 and per_call[0] == 12            # 45 ticks, at most 4 rows per track and group
+    assert len(tails) == 1 and len(tails[0][1]) == (SEG_LEN - 1) * 14
+
+
+def test_given_noise_scores_equal_the_offline_scores_of_the_dataset_path(env):
+    """K = 7 with a noise tensor: every window score equals what ONE score_fused call on the dataset path's windows gives for
+    the same noise -- the feature tied to the dataset path directly, not through `push`."""
+    g, m, args, tracks = env["g"], env["model"], env["args"], env["tracks"]
+    sc = m.scorer()
+    tw, _ = T.load_dataset(args, DEV)
+    n = tw.n_samples
+    assert n == 283
+    S, ns = m.n_generated_samples, m.noise_steps
+    noise = torch.randn(S, ns - 1, NT * n, 2, 3, 17, generator=torch.Generator().manual_seed(7)).to(DEV)
+    wb = WindowBatch(tw.buffer, tw.base.to(DEV), tw.trans.to(DEV), tw.affine, SEG_LEN)
+    offline = sc.score_fused(wb, n_samples=S, noise_steps=ns, aggregation=m.aggregation_strategy, noise=noise,
+                             loss_fn=m.loss_name)[0].cpu().numpy()
+    sample_of = {tuple(int(v) for v in r): i for i, r in enumerate(tw.meta[:n].numpy())}
+    frames_of = {key: f for key, f, _ in tracks}
+    pos = {key: 0 for key in frames_of}
+    idx_of_tick = []
+    for keys, _, _ in env["ticks"]:                 # the dataset index of every window, tick by tick, transform-major
+        metas = [key + (int(frames_of[key][pos[key] - SEG_LEN + 1]),) for key in keys if pos[key] + 1 >= SEG_LEN]
+        idx_of_tick.append(np.asarray([t * n + sample_of[mm] for t in range(NT) for mm in metas], np.int64))
+        for key in keys:
+            pos[key] += 1
+
+    def noise_of_call(lo, call):
+        idx = np.concatenate(idx_of_tick[lo:lo + len(call)])
+        return noise[:, :, torch.from_numpy(idx).to(DEV)] if len(idx) else None
+
+    k = SEG_LEN + 1
+    stream = PoseStream(m, vid_res=VID_RES, center=g["train_center"], scale=g["train_scale"], max_tracks=22,
+                        ring_len=SEG_LEN + k - 1)
+    ticks, _, per_call = _replay_many(stream, None, tracks, env["ticks"], k, noise_of_call)
+    assert per_call == [1] * 7
+    compared = 0
+    for tick, idx in zip(ticks, idx_of_tick):
+        got = tick.scores.cpu().numpy()
+        assert got.shape == idx.shape
+        print(f"tick of {len(idx)} windows: max |push_many - offline| = "
+              f"{float(np.abs(got - offline[idx]).max()) if len(idx) else 0.0:.3e}")
+        assert np.array_equal(_bits(got), _bits(offline[idx]))
+        assert [tuple(int(v) for v in r) for r in tick.meta] == [tuple(int(v) for v in tw.meta[i % n].numpy()) for i in idx]
+        compared += len(idx)
+    assert compared == 283 * NT and np.isfinite(offline).all() and len(np.unique(offline)) > 1000
+    with pytest.raises(ValueError, match="noise must hold the 0 windows of the call"):
+        stream.push_many([([(9, 9, 9)], [1], stress_rows(1, seed=1))], noise=noise[:, :, :5])
+    assert (9, 9, 9) not in stream.table
+
+
+def test_max_idle_closure_of_a_track_with_rows_in_the_group_cuts_the_group(env):
+    """Two slots, max_idle = 1: `a` gets rows in ticks 0-1 of the call, is idle-closed at tick 3, and its slot goes to the new
+    track `c` in that same tick: the group ends before tick 3, whose `closed` tail is a's."""
+    m = env["model"]
+    kw = dict(vid_res=VID_RES, max_tracks=2, max_idle=1, ring_len=SEG_LEN + 3)
+    many, single = PoseStream(m, **kw), PoseStream(m, **kw)
+    raw = stress_rows(64, seed=9)
+    a, b, c, d = (1, 1, 1), (1, 1, 2), (1, 1, 3), (1, 1, 4)
+    for i in range(SEG_LEN):                              # a reaches seg_len rows before the call (on both streams)
+        for st in (many, single):
+            st.push([a], [10 + i], raw[i:i + 1])
+    call = [([a, b], [20, 20], raw[8:10]), ([b, a], [21, 21], raw[10:12]), ([b], [22], raw[12:13]),
+            ([c, b], [23, 23], raw[13:15])] + [([b, c], [24 + i] * 2, raw[16 + 2 * i:18 + 2 * i]) for i in range(7)]
+    # rejected calls first: nothing changes, the tick is named
+    bad = [call[0], ([a, b], [21, 21], np.full((2, 34), np.inf, np.float32))]
+    with pytest.raises(ValueError, match="tick 1: raw pose rows hold NaN / inf"):
+        many.push_many(bad)
+    with pytest.raises(RuntimeError, match=r"tick 2: max_tracks = 2 exhausted.*\(1, 1, 4\)"):
+        many.push_many(call[:2] + [([a, b, d], [22] * 3, raw[:3])])
+    with pytest.raises(ValueError, match=r"tick 1: track \(1, 1, 2\) has two rows in one tick"):
+        many.push_many([call[0], ([b, b], [21, 22], raw[:2])])
+    _same_state(many, single)
+    groups = _count_groups(many)
+    got = many.push_many(call)
+    want = [single.push(*t) for t in call]
+    # ticks 0-2 | ticks 3-6: a closed at tick 3 and its slot reused, then rule 1 (4 rows of b) | ticks 7-10
+    assert len(groups) == 3
+    for x, y in zip(got, want):
+        _same_tick(x, y)
+    assert [len(t.closed) for t in got] == [0, 0, 0, SEG_LEN - 1] + [0] * 7
+    assert got[3].closed.keys == [a] * (SEG_LEN - 1) and got[3].closed.frames.tolist() == [13, 14, 15, 20, 21]
+    assert float(got[3].closed.values.min()) >= 0 and float(got[3].closed.values.max()) > 0
+    assert many.table.slot_of[c] == 0 and len(got[-1].final) == 2          # c emits windows from the reused slot
+    _same_state(many, single)
+    _same_frame_scores(many.close_all(), single.close_all())
+
+
+def test_latent_model_three_ticks_per_call_equals_sequential_pushes(env, tmp_path):
+    g = env["g"]
+    m, _ = _model(tmp_path, g, latent=True)
+    kw = dict(vid_res=VID_RES, center=g["train_center"], scale=g["train_scale"], max_tracks=22, ring_len=SEG_LEN + 2)
+    many, single = PoseStream(m, **kw), PoseStream(m, **kw)
+    ticks, _, per_call = _replay_many(many, single, env["tracks"], env["ticks"], 3)
+    assert per_call == [1] * 15
+    scores = np.concatenate([t.scores.cpu().numpy() for t in ticks])
+    assert np.isfinite(scores).all() and len(np.unique(scores)) > 1000
+
+
+def test_frame_score_group_entry_equals_tick_by_tick_launches():
+    """mcd_stream_frame_scores_group alone on synthetic scores (a NaN, negatives): four overlapping windows on slot 0, two on slot
+    2, one on slot 1, in four ticks -- cells and finals equal sequential mcd_stream_frame_scores launches on a second state."""
+    from mocodad_amd.engine import StreamRings
+    L, nt = SEG_LEN + 3, NT
+    a = StreamRings(3, SEG_LEN, L, nt, VID_RES, device=DEV)
+    b = StreamRings(3, SEG_LEN, L, nt, VID_RES, device=DEV)
+    gen = torch.Generator().manual_seed(5)
+    stale = torch.rand(3, nt, L, generator=gen) * 0.5         # pending maxima of earlier windows, the same in both states
+    a.frame_scores_ring.copy_(stale)
+    b.frame_scores_ring.copy_(stale)
+    ticks = [[(0, 5), (2, 7)], [(0, 6), (1, 5), (2, 8)], [(0, 7)], [(0, 8)]]          # per tick: [slot, r_last] in emit order
+    n = sum(len(t) for t in ticks)
+    scores = torch.randn(nt * n, generator=gen)
+    scores[3], scores[11], scores[17] = float("nan"), -2.0, -0.0
+    assert int((scores < 0).sum()) > 5
+    scores = scores.to(DEV)
+    win5, finals, off = [], [], 0
+    for t in ticks:
+        ne = len(t)
+        finals.append(b.frame_scores(scores[nt * off:nt * (off + ne)], torch.tensor(t, dtype=torch.int32, device=DEV), ne))
+        win5 += [(slot, r, nt * off + j, ne, off + j) for j, (slot, r) in enumerate(t)]
+        off += ne
+    win5.sort(key=lambda w: (w[0], w[1]))
+    got = a.frame_scores_group(scores, torch.tensor(win5, dtype=torch.int32, device=DEV), n)
+    want = torch.cat(finals)
+    assert got.shape == want.shape == (n, nt)
+    assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(_bits(a.frame_scores_ring), _bits(b.frame_scores_ring))
+    assert not torch.isnan(got).any() and not torch.equal(a.frame_scores_ring.cpu(), stale)
+    # the entry refuses more windows than a group can hold
+    rc = a.L.mcd_stream_frame_scores_group(C.byref(a._state), None, None, 3 * (L - SEG_LEN + 1) + 1, None, None)
+    assert rc != 0 and b"n_windows" in a.L.mcd_last_error()

@@ -6,6 +6,7 @@
            --dataset-choice HR-STC --no-scaler                                                # the test fixture
     python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 256 --rows 120
     python tools/stream_replay.py -c configs/ubnormal_latent_test.yaml --random-init --synthetic-tracks 64    # the latent model
+    python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 64 --ticks-per-call 8
 
 On-disk split: the trajectory CSVs are replayed in frame order, one tick = one frame id across all clips; a track is closed
 after its last row.  The window scores, put back into dataset order, go through the model's own post_processing: the AUC is
@@ -16,6 +17,11 @@ Timing (host clock around work that ends in a device synchronise, one warm-up re
   baseline  ONE score_fused call (a YAML with diffusion_on_latent: true: ONE LatentScorer.score call) on a pre-built WindowBatch of the tick's window count over a trajectory buffer already on the
             device (what a caller of the dataset path would pay for the same windows if the buffer and the window list cost
             nothing), timed the same way in the same process, alternating with the stream replay.
+--ticks-per-call K (default 1 = the path above through `push`): K ticks per PoseStream.push_many call, ring_len = seg_len + K - 1
+unless --ring-len says otherwise (then a call may be cut into several launch groups); tracks are closed after the call that held
+their last row.  "tick" is then one CALL (K ticks: one copy, one mcd_stream_push_group, ONE scoring call on the windows of all K
+ticks, one mcd_stream_frame_scores_group per group), the baseline ONE scoring call on a pre-built batch of the call's window count,
+and rows_per_s = pose rows pushed / time in push or push_many over a whole replay (every call, also those without a window).
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
 emitted windows, the range of the per-replay medians (the spread), and the same for the baseline."""
 import argparse
@@ -70,6 +76,7 @@ def main():
     ap.add_argument("--synthetic-tracks", type=int, default=0)
     ap.add_argument("--rows", type=int, default=120, help="rows per synthetic track")
     ap.add_argument("--ring-len", type=int, default=None)
+    ap.add_argument("--ticks-per-call", type=int, default=1, help="K > 1: K ticks per push_many call (1: one push per tick)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
     cli = ap.parse_args()
@@ -103,16 +110,24 @@ def main():
         files = T.list_trajectory_files(T.trajectories_root(args.data_dir, split))
         tracks = [(key,) + T.read_trajectory_csv(path) for key, path in files]
         source = f"{args.data_dir} ({split}): {len(tracks)} track files"
+    K = cli.ticks_per_call
+    if K < 1:
+        raise SystemExit("--ticks-per-call must be at least 1")
+    ring_len = cli.ring_len if cli.ring_len is not None or K == 1 else seg_len + K - 1
     size = {k: len(f) for k, f, _ in tracks}
-    ticks, left, n_open, peak = [], dict(size), 0, 0
-    for _, keys, fids, poses in ticks_by_frame(tracks):
+    calls, left, n_open, peak = [], dict(size), 0, 0
+    for i, (_, keys, fids, poses) in enumerate(ticks_by_frame(tracks)):
+        if i % K == 0:
+            calls.append(([], []))
         n_open += sum(left[k] == size[k] for k in keys)
         peak = max(peak, n_open)
         for k in keys:
             left[k] -= 1
-        done = [k for k in keys if left[k] == 0]        # closed right after their last row
-        n_open -= len(done)
-        ticks.append((keys, fids, poses, done))
+        calls[-1][0].append((keys, fids, poses))
+        calls[-1][1].extend(k for k in keys if left[k] == 0)
+        if i % K == K - 1:                              # closed right after the call that held their last row
+            n_open -= len(calls[-1][1])
+    n_ticks = sum(len(c[0]) for c in calls)
     # the dataset path on the same rows: the trajectory buffer + window list the baseline scores from (and the AUC needs)
     kept = sorted(((k, f, p) for k, f, p in tracks if len(f) >= seg_len), key=lambda t: t[0])
     off = np.zeros(len(kept) + 1, np.int64)
@@ -128,25 +143,29 @@ def main():
               seed=model.seed, loss_fn=model.loss_name)
 
     def replay(collect=None):
-        stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=cli.ring_len,
+        stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=ring_len,
                             num_transform=nt)
-        times, counts = [], []
-        for keys, fids, poses, done in ticks:
+        times, counts, rows, spent = [], [], 0, 0.0
+        for call, done in calls:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            tick = stream.push(keys, fids, poses)
+            out = [stream.push(*call[0])] if K == 1 else stream.push_many(call)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            ne = len(tick.final)
-            if ne:
+            rows += sum(len(keys) for keys, _, _ in call)
+            spent += dt
+            nw = sum(len(tick.final) for tick in out) * nt
+            if nw:
                 times.append(dt)
-                counts.append(ne * nt)
-                if collect is not None:
-                    idx = np.asarray([t * n + sample_of[tuple(int(v) for v in m)] for t in range(nt) for m in tick.meta[:ne]])
-                    collect[idx] = tick.scores.cpu().numpy()
+                counts.append(nw)
+                for tick in out if collect is not None else ():
+                    ne = len(tick.final)
+                    if ne:
+                        idx = np.asarray([t * n + sample_of[tuple(int(v) for v in m)] for t in range(nt) for m in tick.meta[:ne]])
+                        collect[idx] = tick.scores.cpu().numpy()
             if done:
                 stream.close(done)
-        return np.asarray(times), counts
+        return np.asarray(times), counts, rows / spent
 
     def baseline(counts):
         times = []
@@ -164,25 +183,28 @@ def main():
         return np.asarray(times)
 
     scores = np.full(nt * n, np.nan, np.float32)
-    _, counts = replay(scores)                  # warm-up replay (code objects, allocator pools); also the scores for the AUC
+    _, counts, _ = replay(scores)                # warm-up replay (code objects, allocator pools); also the scores for the AUC
     baseline(counts)
     assert not np.isnan(scores).any() and sum(counts) == nt * n, "the replay did not emit every window of the dataset path"
     auc = None
     if not cli.synthetic_tracks:
         auc = float(model.post_processing(scores, None, tw.trans.long().numpy(), tw.meta.numpy(), tw.frames.numpy()))
-    t_stream, t_base = [], []
+    t_stream, t_base, rate = [], [], []
     for _ in range(cli.reps):                   # alternating: both legs see the same machine state
-        t_stream.append(replay()[0])
+        t, _, r = replay()
+        t_stream.append(t)
+        rate.append(r)
         t_base.append(baseline(counts))
-    res = {"source": source, "ticks": len(ticks), "ticks_with_windows": len(counts), "peak_open_tracks": peak,
+    res = {"source": source, "ticks": n_ticks, "ticks_per_call": K, "calls": len(calls), "ticks_with_windows": len(counts),
+           "peak_open_tracks": peak, "rows_per_s": {"median": round(float(np.median(rate))), "min": round(min(rate)), "max": round(max(rate))},
            "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
-           "n_samples": int(model.n_generated_samples), "ring_len": cli.ring_len or seg_len, "reps": cli.reps, "auc": auc,
+           "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
            "model": "MoCoDADlatent" if latent else "MoCoDAD",
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
-    print(f"tick: median {res['tick']['median_us']} us, p99 {res['tick']['p99_us']} us | baseline score_fused alone: median "
+    print(f"{K} tick(s) per call, {res['rows_per_s']['median']} rows/s | tick: median {res['tick']['median_us']} us, p99 {res['tick']['p99_us']} us | baseline score_fused alone: median "
           f"{res['baseline_score_fused']['median_us']} us, p99 {res['baseline_score_fused']['p99_us']} us")
     line = json.dumps(res)
     print(line)
