@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 12
+#define MCD_ABI_VERSION 13
 
 enum {
     MCD_OK = 0,
@@ -360,6 +360,54 @@ int mcd_stream_push_group(const mcd_stream_state_t* s, const float* raw, const i
  * which no later window covers -- what mcd_stream_frame_scores returns for it tick by tick. */
 int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_windows,
                                   float* final_out, void* stream);
+
+/* Online clip scores of a live stream: the last stage of post_processing -- the person aggregation
+ * mean_p s + (max_p log1p s - min_p log1p s) (mocodad.py:399-401), score_process = shift + gaussian_filter1d (eval_utils.py:100-106)
+ * and the mean over the transforms (mocodad.py:424) -- incrementally, one value per video frame of a clip, from the final per-row
+ * frame scores the entries above return (final_out of mcd_stream_frame_scores[_group], out of mcd_stream_flush).
+ * Semantics (mocodad_amd/stream.py: ClipTable holds the host half):
+ *   raw(f, t)   = sum_p s_p / n + (max_p log1p(s_p) - min_p log1p(s_p)) over the n persons that have a final score at frame f,
+ *                 in float64, 0 when n = 0.  (The dataset path counts every person of the WHOLE clip, absent ones as zeros; a live
+ *                 clip has no final roster.  Where every person is present on every frame the two coincide, bit for bit.)
+ *   shifted(k)  = raw(k - shift) for k - origin >= shift, else 0; origin = the first frame id of the clip's current segment.
+ *   out(j, t)   = scipy gaussian_filter1d(shifted, sigma; truncate 4, 'reflect') over the segment origin .. head, summed as
+ *                 mcd_frame_scores sums it: the centre tap, then the pairs from the outermost inwards;
+ *   score(j)    = sum_t out(j, t) / num_transform, transforms added in ascending order.
+ * pad_size and the HR masks of mcd_frame_cfg_t are not applied: they need the clip's final length.
+ * State, CALLER-owned device memory, per (clip slot, transform, ring position) one cell = the aggregate of one frame so far:
+ *   sum, lmax, lmin  (n_clips, num_transform, clip_ring_len) f64
+ *   n                (n_clips, num_transform, clip_ring_len) i32 persons added
+ * Which frame sits at which position, and which cells are open, complete or emitted, is the host's business.  One state is driven
+ * from one stream. */
+typedef struct {
+    double* sum;
+    double* lmax;
+    double* lmin;
+    int32_t* n;
+    int32_t n_clips;
+    int32_t clip_ring_len;
+    int32_t num_transform;
+} mcd_clip_state_t;
+
+/* Final frame scores into their cells.  runs (n_runs, 5) i32 device = [clip slot, ring position, first contribution, count,
+ * zero-first] per cell touched -- a cell is named AT MOST ONCE per call (one thread per (run, transform) owns it: plain loads and
+ * stores); zero-first != 0 opens the cell (aggregate and count start from zero; a newly opened cell without a contribution is a
+ * run with count 0).  contrib (n_contrib, 2) i32 device = [source, row]: source 0 = finals (n_finals, num_transform) f32, source
+ * 1 = tails (n_tails, num_transform) f32 (either may be NULL with a count of 0); the contributions first .. first + count - 1 of a
+ * run are added in list order.  Runs whose slot or position is out of range, runs whose contribution range leaves the list, and
+ * contributions whose source or row is out of range are ignored.  0 <= n_runs <= n_clips * clip_ring_len. */
+int mcd_stream_clip_update(const mcd_clip_state_t* c, const int32_t* runs, int32_t n_runs, const int32_t* contrib,
+                           int32_t n_contrib, const float* finals, int32_t n_finals, const float* tails, int32_t n_tails,
+                           void* stream);
+
+/* Clip scores of the frames that became computable.  outs (n_out, 4) i32 device = [clip slot, frame offset j from the segment's
+ * origin, segment length m (the segment has ended: 'reflect' at both ends) or -1 (open: every tap right of j lies inside the
+ * segment; 'reflect' at the origin only), ring position of the origin]: the cell of offset k is at position (origin position + k)
+ * % clip_ring_len.  gauss (2 * radius + 1,) f64 device = the normalised weights; shift >= 0, radius >= 0.  out (n_out,) f64 device
+ * = score(j) as defined above.  Outputs whose slot, offset (j < 0, j >= m, j >= 2^29) or origin position is out of range come back
+ * as 0.  0 <= n_out <= n_clips * clip_ring_len; num_transform <= 256. */
+int mcd_stream_clip_emit(const mcd_clip_state_t* c, const int32_t* outs, int32_t n_out, const double* gauss, int32_t radius,
+                         int32_t shift, double* out, void* stream);
 
 /* Frame-score assembly after the path, whole: replaces the (transform, clip, person) loops of
  * MoCoDAD.post_processing (mocodad.py:362-425) with compute_var_matrix + np.nanmax (eval_utils.py:27-34, mocodad.py:392-393),

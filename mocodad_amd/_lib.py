@@ -15,7 +15,7 @@ COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
 LATENT_OPT = {"split_encode": 0}     # MCD_LATENT_OPT_*
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class Tensor(C.Structure):
@@ -53,6 +53,11 @@ class LatentCfg(C.Structure):
 class StreamState(C.Structure):
     _fields_ = [("ring", C.c_void_p), ("frame_scores", C.c_void_p), ("n_slots", C.c_int32), ("ring_len", C.c_int32),
                 ("seg_len", C.c_int32), ("num_transform", C.c_int32)]
+
+
+class ClipState(C.Structure):
+    _fields_ = [("sum", C.c_void_p), ("lmax", C.c_void_p), ("lmin", C.c_void_p), ("n", C.c_void_p), ("n_clips", C.c_int32),
+                ("clip_ring_len", C.c_int32), ("num_transform", C.c_int32)]
 
 
 _SIGS = {
@@ -95,6 +100,10 @@ _SIGS = {
     "mcd_stream_push_group": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_stream_frame_scores_group": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcd_stream_clip_update": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_int32, C.c_void_p]),
+    "mcd_stream_clip_emit": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_void_p]),
     "mcd_pack_latent_weights": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.POINTER(LatentCfg), C.c_int32,
                                           C.POINTER(C.c_void_p)]),
     "mcd_free_latent_weights": (None, [C.c_void_p]),

@@ -702,6 +702,59 @@ int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scor
     return MCD_OK;
 }
 
+static int clip_params(const mcd_clip_state_t* c, ClipParams* P) {
+    if (!c || !c->sum || !c->lmax || !c->lmin || !c->n) return fail(MCD_EINVAL, "null clip state");
+    if (c->n_clips <= 0 || c->num_transform <= 0 || c->clip_ring_len <= 0)
+        return fail(MCD_EINVAL, "clip state: need n_clips, num_transform, clip_ring_len >= 1");
+    if (c->num_transform > 256) return fail(MCD_EUNSUPPORTED, "clip state: more than 256 transforms");
+    if ((int64_t)c->n_clips * c->clip_ring_len > 0x7fffffffll / c->num_transform)
+        return fail(MCD_EUNSUPPORTED, "clip rings of more than 2^31 cells");
+    P->sum = c->sum; P->lmax = c->lmax; P->lmin = c->lmin; P->n = c->n;
+    P->n_clips = c->n_clips; P->L = c->clip_ring_len; P->nt = c->num_transform;
+    return MCD_OK;
+}
+
+int mcd_stream_clip_update(const mcd_clip_state_t* c, const int32_t* runs, int32_t n_runs, const int32_t* contrib,
+                           int32_t n_contrib, const float* finals, int32_t n_finals, const float* tails, int32_t n_tails,
+                           void* stream) {
+    ClipParams P;
+    if (int rc = clip_params(c, &P)) return rc;
+    if (n_runs < 0 || n_runs > (int64_t)c->n_clips * c->clip_ring_len)
+        return fail(MCD_EINVAL, "need 0 <= n_runs <= n_clips * clip_ring_len: a call names a cell at most once");
+    if (n_contrib < 0 || n_finals < 0 || n_tails < 0) return fail(MCD_EINVAL, "need n_contrib, n_finals, n_tails >= 0");
+    if (n_runs == 0) return MCD_OK;
+    if (!runs || (n_contrib > 0 && !contrib) || (n_finals > 0 && !finals) || (n_tails > 0 && !tails))
+        return fail(MCD_EINVAL, "null argument");
+    const long long total = (long long)n_runs * P.nt;
+    hipLaunchKernelGGL(stream_clip_update_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, runs,
+                       n_runs, contrib, n_contrib, finals, n_finals, tails, n_tails);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_clip_emit(const mcd_clip_state_t* c, const int32_t* outs, int32_t n_out, const double* gauss, int32_t radius,
+                         int32_t shift, double* out, void* stream) {
+    ClipParams P;
+    if (int rc = clip_params(c, &P)) return rc;
+    if (n_out < 0 || n_out > (int64_t)c->n_clips * c->clip_ring_len) return fail(MCD_EINVAL, "need 0 <= n_out <= n_clips * clip_ring_len");
+    if (radius < 0 || radius > (1 << 24) || shift < 0) return fail(MCD_EINVAL, "need 0 <= radius <= 2^24 and shift >= 0");
+    if (n_out == 0) return MCD_OK;
+    if (!outs || !gauss || !out) return fail(MCD_EINVAL, "null argument");
+    // outputs per workgroup: as many (output, transform) tap threads as a workgroup has, fewer when their staged values
+    // (2 radius + 1 doubles each) would not fit 48 KB of LDS; a kernel wider than that reads its values in place
+    const size_t per_out = (size_t)P.nt * (2 * (size_t)radius + 1) * sizeof(double);
+    ClipEmitParams E;
+    E.outs = outs; E.gauss = gauss; E.out = out; E.n_out = n_out; E.radius = radius; E.shift = shift;
+    E.staged = per_out <= (size_t)48 * 1024 ? 1 : 0;
+    E.opb = 256 / P.nt;
+    if (E.staged) E.opb = std::min<int>(E.opb, (int)((size_t)48 * 1024 / per_out));
+    E.opb = std::max(1, std::min(E.opb, 16));         // (few outputs per tick: more workgroups, shorter staging loops)
+    const size_t lds = ((size_t)E.opb * P.nt + (E.staged ? (size_t)E.opb * P.nt * (2 * (size_t)radius + 1) : 0)) * sizeof(double);
+    hipLaunchKernelGGL(stream_clip_emit_kernel, dim3((unsigned)((n_out + E.opb - 1) / E.opb)), dim3(256), lds, (hipStream_t)stream, P, E);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 
 int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* c) {
     if (!c || c->n_clips <= 0 || c->num_transform <= 0 || c->n_persons <= 0 || c->max_frames <= 0) return 0;

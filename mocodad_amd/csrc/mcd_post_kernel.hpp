@@ -5,10 +5,12 @@
 //   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
 //                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
 //   stream_push_group / stream_frame_scores_group kernels   the same for a group of ticks in one launch each
+//   stream_clip_update / stream_clip_emit kernels   online per-clip frame scores: the person aggregate, shift and Gaussian of
+//                               post_processing, incrementally on a per-clip ring     models/mocodad.py:399-424, utils/eval_utils.py:100-106
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
-// with the parameter blocks the host fills (AggrParams, StreamParams, FrameParams).  Included once, by mcd_api.hip (which defines
+// with the parameter blocks the host fills (AggrParams, StreamParams, FrameParams, ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines
 // API_THREADS and says `using namespace mcd`), in front of its host code; the kernels keep the order, the linkage and the
 // visibility they had inside that file, so its device object does not change.
 #pragma once
@@ -356,6 +358,34 @@ struct FrameParams {
     int seg_len, n_clips, num_transform, P, F, pad, shift, radius;
 };
 
+// The pieces frame_scores_kernel shares with the online clip kernels (stream_clip_update / stream_clip_emit below): one
+// definition each, so the operations, their order and the FMA contraction are the same in both and the online scores of a clip
+// whose persons are all present on every frame carry the bits of the dataset path.
+//   person_aggr_add / person_aggr_value: mean_p s + (max_p log1p s - min_p log1p s) over the persons added (mocodad.py:399-401)
+//   reflect_index: position k of scipy's 'reflect' extension (d c b a | a b c d | d c b a) of a sequence of m entries, any k
+//   gauss_taps: correlation with the symmetric weights g[0 .. 2 radius]: the centre tap, then the pairs from the outermost inwards
+__device__ __forceinline__ void person_aggr_add(double& sum, double& lmax, double& lmin, int& cnt, float v) {
+    const double dv = (double)v, lg = log1p(dv);
+    sum += dv;
+    if (cnt == 0) { lmax = lg; lmin = lg; } else { lmax = fmax(lmax, lg); lmin = fmin(lmin, lg); }
+    ++cnt;
+}
+__device__ __forceinline__ double person_aggr_value(double sum, double lmax, double lmin, int cnt) {
+    return sum / (double)cnt + (lmax - lmin);
+}
+__device__ __forceinline__ int reflect_index(int k, int m) {
+    const int per = 2 * m;
+    k %= per; if (k < 0) k += per;
+    if (k >= m) k = per - 1 - k;
+    return k;
+}
+template <class At>
+__device__ __forceinline__ double gauss_taps(const At& at, int j, const double* __restrict__ g, int radius) {
+    double t = at(j) * g[radius];
+    for (int i = radius; i >= 1; --i) t += (at(j - i) + at(j + i)) * g[radius - i];
+    return t;
+}
+
 __global__ void frame_scatter_kernel(const FrameParams Q) {
     const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= Q.n * Q.seg_len) return;
@@ -409,34 +439,125 @@ __global__ __launch_bounds__(256) void frame_scores_kernel(const FrameParams Q) 
                     }
                     if (z) v = 0.f;
                 }
-                const double dv = (double)v, lg = log1p(dv);
-                sum += dv;
-                if (cnt == 0) { lmax = lg; lmin = lg; } else { lmax = fmax(lmax, lg); lmin = fmin(lmin, lg); }
-                ++cnt;
+                person_aggr_add(sum, lmax, lmin, cnt, v);
             }
             const int j = dst[f];
             // a (transform, clip) block without any person: NaN (the reference fails on np.stack of an empty list; the host
             // wrapper turns the NaN into that error)
-            if (j >= 0) cs[j] = cnt > 0 ? sum / (double)cnt + (lmax - lmin) : (double)NAN;
+            if (j >= 0) cs[j] = cnt > 0 ? person_aggr_value(sum, lmax, lmin, cnt) : (double)NAN;
         }
         __syncthreads();
         // score_process (eval_utils.py:100-106): shift by `shift` frames (zeros enter), then correlate with the Gaussian
         // in scipy's symmetric form: in[c] w[c] + sum_{i=1..radius} (in[c-i] + in[c+i]) w[c-i], outermost pair first
         for (int j = threadIdx.x; j < m; j += blockDim.x) {
-            auto at = [&](int k) -> double {          // shifted, 'reflect'-extended (d c b a | a b c d | d c b a)
-                const int per = 2 * m;
-                k %= per; if (k < 0) k += per;
-                if (k >= m) k = per - 1 - k;
+            auto at = [&](int k) -> double {          // shifted, 'reflect'-extended
+                k = reflect_index(k, m);
                 return k >= Q.shift ? cs[k - Q.shift] : 0.0;
             };
-            double t = at(j) * Q.gauss[Q.radius];
-            for (int i = Q.radius; i >= 1; --i) t += (at(j - i) + at(j + i)) * Q.gauss[Q.radius - i];
-            acc[j] += t;
+            acc[j] += gauss_taps(at, j, Q.gauss, Q.radius);
         }
     }
     __syncthreads();
     double* o = Q.out + Q.out_off[ci];
     for (int j = threadIdx.x; j < m; j += blockDim.x) o[j] = acc[j] / (double)Q.num_transform;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Online clip scores of a live stream (mcd_clip_state_t): per (clip slot, transform, ring position) one CELL = the person
+// aggregate of one video frame so far, sum / lmax / lmin in f64 and the person count n.  The host (mocodad_amd/stream.py:
+// ClipTable) owns the frame axis: which frame sits at which position, which cells are open, complete, emitted.
+//   stream_clip_update_kernel: the final per-row frame scores of a tick (or a group of ticks) into their cells.
+//   stream_clip_emit_kernel  : shift + gaussian_filter1d ('reflect') + mean over the transforms for the frames that became
+//                              computable, with the functions and the summation order of frame_scores_kernel.
+// ------------------------------------------------------------------------------------------------
+struct ClipParams {
+    double* sum; double* lmax; double* lmin; int* n;
+    int n_clips, L, nt;
+};
+
+// One thread per (cell run, transform): runs (n_runs, 5) = [clip slot, ring position, first contribution, count, zero-first];
+// contrib (n_contrib, 2) = [source: 0 = finals, 1 = tails; row of that (rows, num_transform) f32 tensor].  A launch names a cell
+// at most once, so its thread owns it: plain loads and stores, contributions added in list order.
+__global__ __launch_bounds__(256) void stream_clip_update_kernel(ClipParams C, const int* __restrict__ runs, int n_runs,
+                                                                 const int* __restrict__ contrib, int n_contrib,
+                                                                 const float* __restrict__ finals, int n_finals,
+                                                                 const float* __restrict__ tails, int n_tails) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_runs * C.nt) return;
+    const int q = u / C.nt, t = u - q * C.nt;
+    const int slot = runs[5 * q], pos = runs[5 * q + 1], first = runs[5 * q + 2], count = runs[5 * q + 3], zero = runs[5 * q + 4];
+    if (slot < 0 || slot >= C.n_clips || pos < 0 || pos >= C.L) return;      // (a run the host table cannot produce: touch nothing)
+    const size_t c = ((size_t)slot * C.nt + t) * C.L + pos;
+    double sum = 0.0, lmax = 0.0, lmin = 0.0;
+    int cnt = 0;
+    if (!zero) { sum = C.sum[c]; lmax = C.lmax[c]; lmin = C.lmin[c]; cnt = C.n[c]; }
+    if (first >= 0 && count > 0 && (long long)first + count <= n_contrib)
+        for (int i = first; i < first + count; ++i) {
+            const int src = contrib[2 * i], row = contrib[2 * i + 1];
+            const float* p = src == 0 ? finals : src == 1 ? tails : nullptr;
+            if (!p || row < 0 || row >= (src == 0 ? n_finals : n_tails)) continue;
+            person_aggr_add(sum, lmax, lmin, cnt, p[(size_t)row * C.nt + t]);
+        }
+    C.sum[c] = sum; C.lmax[c] = lmax; C.lmin[c] = lmin; C.n[c] = cnt;
+}
+
+struct ClipEmitParams {
+    const int* outs;          // (n_out, 4) = [clip slot, frame offset j from the segment's origin, segment length m | -1 = open, ring position of the origin]
+    const double* gauss;      // (2 radius + 1,)
+    double* out;              // (n_out,)
+    int n_out, radius, shift, opb, staged;
+};
+constexpr int CLIP_OPEN_LEN = 1 << 29;      // "no end yet": offsets stay below it, so 'reflect' only acts at the origin
+
+// shifted(k) of transform t: the raw score of frame offset k - shift (0 before the origin + shift, 0 for a frame nobody contributed to)
+__device__ __forceinline__ double clip_shifted(const ClipParams& C, int slot, int t, int pbase, int k, int m, int shift) {
+    k = reflect_index(k, m);
+    if (k < shift) return 0.0;
+    const size_t c = ((size_t)slot * C.nt + t) * C.L + (size_t)(((long long)pbase + (k - shift)) % C.L);
+    const int cnt = C.n[c];
+    return cnt > 0 ? person_aggr_value(C.sum[c], C.lmax[c], C.lmin[c], cnt) : 0.0;
+}
+
+// One workgroup per `opb` outputs.  Staged mapping: all threads fill the 2 radius + 1 shifted values of every (output, transform)
+// into LDS (the divisions and the cell loads run in parallel), then one thread per (output, transform) runs the tap chain in the
+// stated order, then one thread per output adds the transforms in ascending order.  A kernel too wide for LDS (staged = 0) lets the
+// tap thread compute its values itself.  Outputs with a slot, offset or origin position out of range come back as 0.
+__global__ __launch_bounds__(256) void stream_clip_emit_kernel(ClipParams C, ClipEmitParams E) {
+    extern __shared__ __attribute__((aligned(16))) double csm[];
+    const int W = 2 * E.radius + 1, o0 = blockIdx.x * E.opb, tid = threadIdx.x;
+    double* part = csm;                          // [opb * nt] filtered value per (output, transform)
+    double* sh = csm + E.opb * C.nt;             // staged: [opb * nt][W]
+    auto valid = [&](int o, int& slot, int& j, int& m, int& pbase) -> bool {
+        if (o >= E.n_out) return false;
+        slot = E.outs[4 * o]; j = E.outs[4 * o + 1]; m = E.outs[4 * o + 2]; pbase = E.outs[4 * o + 3];
+        if (m < 0) m = CLIP_OPEN_LEN;
+        return slot >= 0 && slot < C.n_clips && j >= 0 && j < m && m <= CLIP_OPEN_LEN && pbase >= 0 && pbase < C.L;
+    };
+    int slot, j, m, pbase;
+    if (E.staged)
+        for (int e = tid; e < E.opb * C.nt * W; e += blockDim.x) {
+            const int ot = e / W, i = e - ot * W, ol = ot / C.nt, t = ot - ol * C.nt;
+            if (valid(o0 + ol, slot, j, m, pbase)) sh[e] = clip_shifted(C, slot, t, pbase, j - E.radius + i, m, E.shift);
+        }
+    __syncthreads();
+    if (tid < E.opb * C.nt) {
+        const int ol = tid / C.nt, t = tid - ol * C.nt;
+        if (valid(o0 + ol, slot, j, m, pbase)) {
+            if (E.staged) {
+                const double* row = sh + (size_t)tid * W + (E.radius - j);
+                part[tid] = gauss_taps([&](int k) -> double { return row[k]; }, j, E.gauss, E.radius);
+            } else {
+                part[tid] = gauss_taps([&](int k) -> double { return clip_shifted(C, slot, t, pbase, k, m, E.shift); }, j, E.gauss, E.radius);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < E.opb && o0 + tid < E.n_out) {
+        double acc = 0.0;
+        const bool ok = valid(o0 + tid, slot, j, m, pbase);
+        for (int t = 0; ok && t < C.nt; ++t) acc += part[tid * C.nt + t];
+        E.out[o0 + tid] = acc / (double)C.nt;
+    }
 }
 
 }  // namespace

@@ -674,6 +674,53 @@ class StreamRings:
         return out
 
 
+class ClipRings:
+    """Device state of the online clip scores of a live pose stream (mcd_clip_state_t) and the two launches on it; the host half
+    -- which frame of which clip sits in which cell, what is complete, what was emitted -- is mocodad_amd.stream.ClipTable.
+      sum, lmax, lmin  (n_clips, num_transform, clip_ring_len) fp64: the person aggregate of one video frame per cell
+      n                (same) int32: persons added
+      gauss            (2 radius + 1,) fp64: utils/eval_utils.gaussian_kernel1d(sigma)
+    All calls are asynchronous on the current stream; one state is driven from one stream."""
+
+    def __init__(self, n_clips: int, clip_ring_len: int, num_transform: int, sigma: float, shift: int, *, device=None):
+        from .utils.eval_utils import gaussian_kernel1d
+        self.L = _lib.lib()
+        _need_gpu()
+        self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.n_clips, self.clip_ring_len, self.num_transform = int(n_clips), int(clip_ring_len), int(num_transform)
+        w = gaussian_kernel1d(sigma)
+        self.radius, self.shift = (len(w) - 1) // 2, int(shift)
+        shape = (self.n_clips, self.num_transform, self.clip_ring_len)
+        with torch.cuda.device(dev):
+            self.sum, self.lmax, self.lmin = (torch.zeros(shape, device=dev, dtype=torch.float64) for _ in range(3))
+            self.n = torch.zeros(shape, device=dev, dtype=torch.int32)
+            self.gauss = torch.from_numpy(w).to(dev)
+        self._state = _lib.ClipState(sum=self.sum.data_ptr(), lmax=self.lmax.data_ptr(), lmin=self.lmin.data_ptr(),
+                                     n=self.n.data_ptr(), n_clips=self.n_clips, clip_ring_len=self.clip_ring_len,
+                                     num_transform=self.num_transform)
+
+    def update(self, runs: torch.Tensor, n_runs: int, contrib: Optional[torch.Tensor], n_contrib: int,
+               finals: Optional[torch.Tensor], tails: Optional[torch.Tensor]) -> None:
+        """mcd_stream_clip_update: runs (n_runs, 5) int32 [clip slot, ring position, first contribution, count, zero-first],
+        contrib (n_contrib, 2) int32 [0 = finals | 1 = tails, row]; finals / tails (rows, num_transform) fp32 or None."""
+        nf = int(finals.shape[0]) if finals is not None and finals.numel() else 0
+        ntl = int(tails.shape[0]) if tails is not None and tails.numel() else 0
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_stream_clip_update(C.byref(self._state), _ptr(runs), int(n_runs), _ptr(contrib) if n_contrib else None,
+                                                     int(n_contrib), _ptr(finals) if nf else None, nf, _ptr(tails) if ntl else None,
+                                                     ntl, _stream()))
+
+    def emit(self, outs: Optional[torch.Tensor], n_out: int) -> torch.Tensor:
+        """mcd_stream_clip_emit: outs (n_out, 4) int32 [clip slot, frame offset from the origin, segment length | -1, ring position
+        of the origin] -> (n_out,) fp64 clip scores."""
+        with torch.cuda.device(self.device):
+            out = torch.empty(int(n_out), device=self.device, dtype=torch.float64)
+            if n_out:
+                _lib.check(self.L.mcd_stream_clip_emit(C.byref(self._state), _ptr(outs), int(n_out), _ptr(self.gauss), self.radius,
+                                                       self.shift, _ptr(out), _stream()))
+        return out
+
+
 class FrameScoreAssembler:
     """Window scores -> per-frame anomaly scores on the device (mcd_frame_scores): the whole of the reference's
     post_processing loops (mocodad.py:362-425) except roc_auc_score.  Built once per dataset from the ground-truth masks."""

@@ -22,7 +22,14 @@ meta = [scene, clip, person, frame id of the window's first row] and frames = th
 Several ticks at once (a pose estimator that delivers frames in batches, a stream catching up, recorded video on the online path):
 `PoseStream.push_many` returns what the same ticks pushed one by one return, bit for bit, but runs them in launch groups --
 `pack_ticks` cuts the call into groups of consecutive ticks that the rings can hold at once (ring_len - seg_len + 1 rows per
-track), and a group is one copy, mcd_stream_push_group, ONE scoring call on all of its windows, mcd_stream_frame_scores_group."""
+track), and a group is one copy, mcd_stream_push_group, ONE scoring call on all of its windows, mcd_stream_frame_scores_group.
+
+Online clip scores (opt-in, `PoseStream(clip_scores=ClipScoreCfg(...))`): the number the model is evaluated on -- per video frame
+of a clip the person aggregation of the final row scores, shifted, Gaussian-filtered and averaged over the transforms -- leaves
+the device with the tick that makes it computable (`Tick.clip`), and `close_clip` ends a clip with the reflected tail.  `ClipTable`
+is the host half (clip slots, per clip the frame axis, watermark and emit cursor; plain NumPy), engine.ClipRings the device half
+(mcd_clip_state_t); a tick or a group adds one mcd_stream_clip_update and one mcd_stream_clip_emit launch, their descriptors ride
+in the tick's one copy.  The definitions stand above `ClipScoreCfg`."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -221,6 +228,7 @@ class GroupPlan:
     #                                   sorted by slot, then row: the windows of a track are adjacent and ascending
     offsets: np.ndarray               # (len(plans) + 1,) int64 windows (one transform) emitted before each tick of the group
     closed: ClosePlan                 # the idle closures of all its ticks, tick after tick (none of them got a row in the group)
+    clip: Optional[list] = None       # with online clip scores: the ClipTick of each of its ticks (pack_ticks(..., clips=))
 
     @property
     def n_rows(self) -> int:
@@ -255,7 +263,7 @@ def _group(first_tick: int, plans: List[TickPlan], num_transform: int, seg_len: 
     return GroupPlan(first_tick, plans, desc, win, offsets, closed)
 
 
-def pack_ticks(table: TrackTable, ticks, num_transform: int = 1, max_rows: Optional[int] = None):
+def pack_ticks(table: TrackTable, ticks, num_transform: int = 1, max_rows: Optional[int] = None, clips: Optional["ClipTable"] = None):
     """Plan a call of several ticks: ticks = [(keys, frame_ids), ...], each what one TrackTable.push takes.  Pure host logic on a
     COPY of `table` -> (groups, the copy after the last tick); `table` itself is not changed, so a call that is rejected at tick
     i (ValueError / RuntimeError of TrackTable.push, with "tick i: " in front) leaves no trace.  The caller adopts the copy.
@@ -268,16 +276,30 @@ def pack_ticks(table: TrackTable, ticks, num_transform: int = 1, max_rows: Optio
          again at once) -- idle closures of tracks WITHOUT a row in the group stay inside: their cells are final before the
          group's first launch,
       3. its rows number at most `max_rows` (default max_tracks * (ring_len - seg_len + 1), at least max_tracks).
-    With ring_len = seg_len every group is one tick."""
+    With ring_len = seg_len every group is one tick.
+    clips: the stream's ClipTable (online clip scores): every tick is checked and planned on a COPY of it as well, in the order
+    sequential pushes would (ClipTable.check, TrackTable.push, ClipTable.push), each GroupPlan carries the ClipTicks of its ticks
+    (their row numbers count within the group) and the result is (groups, table copy, clip table copy)."""
     work = table.copy()
+    cwork = None if clips is None else clips.copy()
+    pend = table.seg_len - 1
     per_track = table.ring_len - table.seg_len + 1
     cap = table.max_tracks * per_track if max_rows is None else int(max_rows)
     if cap < table.max_tracks:
         raise ValueError(f"max_rows = {cap} is less than max_tracks = {table.max_tracks}: one tick would not fit a group")
     groups: List[GroupPlan] = []
-    first, plans, count, n_rows = 0, [], {}, 0
+    first, plans, count, n_rows, cticks = 0, [], {}, 0, []
+
+    def cut():
+        groups.append(_group(first, plans, num_transform, table.seg_len))
+        if cwork is not None:
+            groups[-1].clip = cticks
+
     for i, (keys, fids) in enumerate(ticks):
         try:
+            if cwork is not None:
+                keys = [_key(k) for k in keys]
+                cwork.check(keys, fids, True)
             plan = work.push(keys, fids)
         except (ValueError, RuntimeError) as e:
             raise type(e)(f"tick {i}: {e}") from None
@@ -285,15 +307,407 @@ def pack_ticks(table: TrackTable, ticks, num_transform: int = 1, max_rows: Optio
         # (ring_len = seg_len: one tick per group, today's launches, also where two ticks happen to share no track)
         if plans and (per_track == 1 or n_rows + len(slots) > cap or any(count.get(s, 0) >= per_track for s in slots)
                       or any(s in count for s in plan.closed.slots)):
-            groups.append(_group(first, plans, num_transform, table.seg_len))
-            first, plans, count, n_rows = i, [], {}, 0
+            cut()
+            first, plans, count, n_rows, cticks = i, [], {}, 0, []
+        if cwork is not None:
+            cticks.append(cwork.push(plan, keys, fids, final0=sum(p.n_emit for p in plans),
+                                     tail0=pend * sum(len(p.closed) for p in plans), normalised=True))
         plans.append(plan)
         n_rows += len(slots)
         for s in slots:
             count[s] = count.get(s, 0) + 1
     if plans:
-        groups.append(_group(first, plans, num_transform, table.seg_len))
-    return groups, work
+        cut()
+    return (groups, work) if clips is None else (groups, work, cwork)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Online clip scores (include/mocodad_hip.h: mcd_clip_state_t): one value per video frame of a clip, the number the
+# model is evaluated on, incrementally.  Definitions (f = frame id, t = transform):
+#   contribution  s_p(f, t) = the FINAL frame score of person p's row at frame f (Tick.final / Tick.closed / close()); rows of
+#                 tracks that end with fewer than seg_len rows have none, as offline.
+#   raw(f, t)     = sum_p s_p / n + (max_p log1p s_p - min_p log1p s_p) over the n contributing persons, float64; 0 for n = 0.
+#                 (The dataset path's dense matrix counts every person of the WHOLE clip, absent ones as zeros, so there a frame's
+#                 value depends on who appears later; a live clip has no final roster.  Where every person contributes to every
+#                 frame the two coincide.)
+#   shifted(k)    = raw(k - shift) for k - origin >= shift, else 0;  out(., t) = scipy gaussian_filter1d(shifted, sigma)
+#                 (truncate 4, 'reflect', radius R = int(4 sigma + 0.5)) over the SEGMENT origin .. head;
+#                 score(j) = sum_t out(j, t) / num_transform.
+#   complete      raw(f) is complete when no open track of the clip has a pending (pushed, not yet final) row at a frame <= f and
+#                 the clip's head (largest pushed frame id) is >= f.  The WATERMARK is the smallest frame that is not complete.
+#   emission      frame j is emitted once every frame <= j + R - shift is complete and the head is >= j + R (every tap right of j
+#                 then lies inside the segment whatever comes later, so the value is the one the filter over the whole segment
+#                 gives); each frame once, ascending.  Ending a segment (close_clip, a frame-id jump) emits the rest, up to the
+#                 head, with the reflection at the end.
+# pad_size and the HR masks of the dataset path are not applied: they need the clip's final length.
+# ----------------------------------------------------------------------------------------------------------------------
+Clip = Tuple[int, int]
+
+
+@dataclass
+class ClipScoreCfg:
+    """PoseStream(clip_scores=ClipScoreCfg(...)).  sigma / shift: None = the model's filter_kernel_size / frames_shift;
+    max_clips: clip slots of the device rings; clip_ring_len: frames a clip's ring holds, default
+    2 R + shift + seg_len + (max_idle or 64) + (ring_len - seg_len + 1) + 1."""
+    sigma: Optional[float] = None
+    shift: Optional[int] = None
+    max_clips: int = 64
+    clip_ring_len: Optional[int] = None
+
+
+@dataclass
+class ClipFrames:
+    """Clip scores emitted by one tick (Tick.clip) or by close_clip: values[i] (fp64, device) is the score of frame frames[i] of
+    clip clips[i] = (scene, clip); per clip the frames ascend, and over a clip's life every frame origin .. head comes once.
+    dropped_rows: final row scores that arrived for frames of an already ended segment (or closed clip) and were not used."""
+    clips: List[Clip]
+    frames: np.ndarray
+    values: "object"
+    dropped_rows: int = 0
+
+    def __len__(self):
+        return len(self.clips)
+
+
+@dataclass
+class ClipTick:
+    """What one tick (ClipTable.push), one close (ClipTable.close) or the end of a clip (ClipTable.end_clip) does to the clip
+    rings.  Cells are numbered per clip slot by a counter that never wraps; the ring position of cell c is c % clip_ring_len."""
+    opened: List[Tuple[int, int]]                 # (clip slot, cell) newly opened: zeroed before anything is added
+    contribs: List[Tuple[int, int, int, int]]     # (clip slot, cell, source: 0 = finals | 1 = tails, row), in order of addition
+    outs: np.ndarray                              # (n_out, 4) int32 [clip slot, frame offset, segment length | -1, ring position of the origin]
+    clips: List[Clip]                             # (n_out) the clip of each output
+    frames: np.ndarray                            # (n_out,) int32 its frame id
+    dropped: int                                  # contributions for frames of ended segments
+    span: Dict[int, Tuple[int, int]]              # clip slot -> (lowest cell alive at the start, highest cell after it)
+    n_pre: int = 0                                # the first n_pre outputs are emitted BEFORE the update (catch-up after a close)
+
+    @property
+    def n_out(self) -> int:
+        return int(self.outs.shape[0])
+
+
+@dataclass
+class ClipLaunch:
+    """One mcd_stream_clip_update + one mcd_stream_clip_emit: the ClipTicks of consecutive ticks merged (merge_clip_ticks)."""
+    runs: np.ndarray                  # (n_runs, 5) int32 [clip slot, ring position, first contribution, count, zero-first]
+    contrib: np.ndarray               # (n_contrib, 2) int32 [source, row]
+    outs: np.ndarray                  # (n_out, 4) int32, tick after tick
+    n_out: List[int]                  # outputs of each tick
+    n_pre: int = 0                    # outputs (the first ones) to emit before the update launch: ClipTick.n_pre of the first tick
+
+
+def merge_clip_ticks(ticks: Sequence[ClipTick], ring_len: int) -> ClipLaunch:
+    """One launch pair for consecutive ticks: one run per cell touched, its contributions tick after tick in their order within
+    the tick.  (batch_clip_ticks says which ticks may share a launch.)"""
+    cells: Dict[Tuple[int, int], list] = {}
+    for t in ticks:
+        for sc in t.opened:
+            cells[sc] = [1, []]
+        for s, c, src, row in t.contribs:
+            cells.setdefault((s, c), [0, []])[1].append((src, row))
+    runs, contrib = [], []
+    for (s, c), (zero, lst) in cells.items():
+        runs.append((s, c % ring_len, len(contrib), len(lst), zero))
+        contrib += lst
+    if len({(r[0], r[1]) for r in runs}) != len(runs):
+        raise AssertionError("two cells of one launch share a ring position")      # (batch_clip_ticks / ClipTable.check prevent it)
+    outs = np.concatenate([t.outs for t in ticks]).reshape(-1, 4) if ticks else np.zeros((0, 4), np.int32)
+    if any(t.n_pre for t in ticks[1:]):
+        raise AssertionError("only the first tick after a close catches up")
+    return ClipLaunch(np.asarray(runs, np.int32).reshape(-1, 5), np.asarray(contrib, np.int32).reshape(-1, 2),
+                      outs.astype(np.int32), [t.n_out for t in ticks], ticks[0].n_pre if ticks else 0)
+
+
+def batch_clip_ticks(ticks: Sequence[ClipTick], ring_len: int) -> List[List[int]]:
+    """Consecutive ticks (indices) that may share one launch pair.  The emit launch of a batch runs after its update launch, so
+    the cells a tick's outputs read must survive the cells later ticks of the batch open: per clip, the lowest cell alive at the
+    batch's first tick and the highest cell after its last lie within one ring.  ClipTable.check guarantees that for every single
+    tick; a group whose clip advances further (frame-id gaps inside a group) is cut into more than one launch pair."""
+    batches, cur, lo = [], [], {}
+    for i, t in enumerate(ticks):
+        if cur and any(hi - lo.get(s, l) + 1 > ring_len for s, (l, hi) in t.span.items()):
+            batches.append(cur)
+            cur, lo = [], {}
+        cur.append(i)
+        for s, (l, _) in t.span.items():
+            lo.setdefault(s, l)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+class ClipTable:
+    """Host half of the online clip scores: (scene, clip) -> slot of the clip rings (free list; opened by the clip's first row,
+    freed by end_clip), per clip the current SEGMENT's origin and head, the completeness watermark and the emit cursor, per
+    open track its pending frame ids; from a TickPlan plus the keys and frame ids pushed it plans the cell runs, the contribution
+    list and the outputs of the two launches.  Plain NumPy, no GPU module (like TrackTable).
+
+    Rules, all decided in `check` before any change (a rejected tick leaves this table as it was):
+      late rows     a row whose frame id is below the clip's watermark is a ValueError; rows from the watermark on are accepted.
+      ring          the cells alive run from frame (next to emit) - R - shift to the head; a push that would overwrite one raises
+                    RuntimeError (a stalled track holds the watermark back).
+      jumps         a head that advances by more than the free part of the ring ends the clip's segment (its tail is emitted
+                    with the reflection at the end, tracks stay open) and starts a new one whose origin is the smallest new frame
+                    id beyond the old head; if even that does not fit beside the live cells: the RuntimeError above.  Finals that
+                    arrive later for frames of an ended segment are dropped and counted.
+      clip slots    no free slot for a new clip: RuntimeError.
+    Contributions to one cell are added tick by tick, within a tick in ascending person id (finals and idle tails alike).
+    Emission is planned by push and end_clip only.  An explicit close moves watermarks but emits nothing; the frames it made
+    computable are the FIRST outputs of the next push (ClipTick.n_pre), emitted before that tick's update launch -- so the cells
+    they read count as free for that tick's rows, and closing a stalled track does unblock a full ring."""
+
+    def __init__(self, max_clips: int, clip_ring_len: int, radius: int, shift: int, seg_len: int):
+        self.max_clips, self.ring_len = int(max_clips), int(clip_ring_len)
+        self.radius, self.shift, self.seg_len = int(radius), int(shift), int(seg_len)
+        if self.max_clips < 1 or self.radius < 0 or self.shift < 0 or self.seg_len < 1:
+            raise ValueError("max_clips and seg_len must be at least 1, the radius and the shift not negative")
+        if self.ring_len < 2 * self.radius + self.shift + 1:
+            raise ValueError(f"clip_ring_len = {self.ring_len} is shorter than 2 R + shift + 1 = {2 * self.radius + self.shift + 1}: "
+                             "the cells one output reads would not fit")
+        self.slot_of: Dict[Clip, int] = {}
+        self._free = list(range(self.max_clips - 1, -1, -1))
+        self._clip_of: List[Optional[Clip]] = [None] * self.max_clips
+        z = lambda: [0] * self.max_clips             # (per clip slot; plain ints: this is per-tick host work)
+        self.origin, self.head, self.cursor, self.cbase, self.wm = z(), z(), z(), z(), z()
+        self._tracks: Dict[int, list] = {}           # track slot -> [key, pending frame ids (oldest first), rows pushed]
+        self._of_clip: Dict[int, List[int]] = {}     # clip slot -> its open track slots
+        self._stale = set()                          # clip slots whose watermark a close moved since their last emission
+        self.tick = 0
+        self.dropped_total = 0
+
+    def __len__(self):
+        return len(self.slot_of)
+
+    def copy(self) -> "ClipTable":
+        t = ClipTable.__new__(ClipTable)
+        t.__dict__.update(self.__dict__)
+        t.slot_of, t._free, t._clip_of = dict(self.slot_of), list(self._free), list(self._clip_of)
+        t.origin, t.head, t.cursor, t.cbase, t.wm = (list(a) for a in (self.origin, self.head, self.cursor, self.cbase, self.wm))
+        t._tracks = {s: [r[0], list(r[1]), r[2]] for s, r in self._tracks.items()}
+        t._of_clip = {s: list(v) for s, v in self._of_clip.items()}
+        t._stale = set(self._stale)
+        return t
+
+    def same_state(self, other: "ClipTable") -> bool:
+        cfg = lambda c: (c.max_clips, c.ring_len, c.radius, c.shift, c.seg_len, c.tick, c.dropped_total)
+        return (cfg(self) == cfg(other) and list(self.slot_of.items()) == list(other.slot_of.items()) and self._free == other._free
+                and self._clip_of == other._clip_of and self._tracks == other._tracks and self._of_clip == other._of_clip
+                and self._stale == other._stale
+                and (self.origin, self.head, self.cursor, self.cbase, self.wm)
+                == (other.origin, other.head, other.cursor, other.cbase, other.wm))
+
+    def adopt(self, other: "ClipTable") -> None:
+        self.__dict__.update(other.__dict__)
+
+    # ---- geometry of a clip slot
+    def _cell(self, cs: int, f: int) -> int:
+        return int(self.cbase[cs] + f - self.origin[cs])
+
+    def _cursor_now(self, cs: int) -> int:
+        """The next frame to emit -- after the catch-up the next push starts with, if a close moved the clip's watermark."""
+        c = int(self.cursor[cs])
+        if cs in self._stale:
+            c = max(c, min(int(self.wm[cs]) - 1 + self.shift, int(self.head[cs])) - self.radius + 1)
+        return c
+
+    def _lo_cell(self, cs: int) -> int:
+        """The lowest cell still alive: an output at the cursor reads down to frame cursor - R - shift."""
+        return self._cell(cs, max(int(self.origin[cs]), self._cursor_now(cs) - self.radius - self.shift))
+
+    def _watermark(self, cs: int) -> int:
+        w, o = int(self.head[cs]) + 1, int(self.origin[cs])
+        for ts in self._of_clip[cs]:
+            for f in self._tracks[ts][1]:
+                if o <= f < w:
+                    w = f
+        return w
+
+    def _decide(self, cs: int, fl: List[int]):
+        """New frame ids of a clip -> None (no advance) | ("advance", head) | ("jump", origin, head); RuntimeError if neither fits."""
+        hmax, head = max(fl), int(self.head[cs])
+        if hmax <= head:
+            return None
+        lo, hc = self._lo_cell(cs), self._cell(cs, head)
+        if hc + (hmax - head) - lo + 1 <= self.ring_len:
+            return ("advance", hmax)
+        o2 = min(f for f in fl if f > head)
+        if hc + 1 + (hmax - o2) - lo + 1 <= self.ring_len:
+            return ("jump", o2, hmax)
+        raise RuntimeError(f"clip {self._clip_of[cs]}: frame {hmax} would overwrite a live cell of the clip ring (clip_ring_len = "
+                           f"{self.ring_len}, frames {int(self.origin[cs]) + lo - int(self.cbase[cs])} .. {head} alive: a track with "
+                           "pending rows holds the watermark back): close idle tracks, set max_idle, or size clip_ring_len")
+
+    @staticmethod
+    def _by_clip(keys, fids) -> Dict[Clip, List[int]]:
+        out: Dict[Clip, List[int]] = {}
+        for k, f in zip(keys, fids):
+            out.setdefault(k[:2], []).append(f)
+        return out
+
+    def check(self, keys, frame_ids, normalised: bool = False) -> None:
+        """The rules above for one tick, on the state BEFORE it; changes nothing.  normalised: keys are tuples of ints already."""
+        if not normalised:
+            keys = [_key(k) for k in keys]
+        fids = np.asarray(frame_ids, dtype=np.int64).reshape(-1).tolist()
+        if len(fids) != len(keys):
+            raise ValueError(f"{len(keys)} keys but {len(fids)} frame ids")
+        new = 0
+        for clip, fl in self._by_clip(keys, fids).items():
+            cs = self.slot_of.get(clip)
+            if cs is None:
+                new += 1
+                if new > len(self._free):
+                    raise RuntimeError(f"max_clips = {self.max_clips} exhausted: no clip slot for clip {clip} (close_clip finished "
+                                       "clips, or size the stream for more clips)")
+                if max(fl) - min(fl) + 1 > self.ring_len:
+                    raise RuntimeError(f"clip {clip}: frames {min(fl)} .. {max(fl)} of one tick exceed clip_ring_len = {self.ring_len}")
+            else:
+                if min(fl) < self.wm[cs]:
+                    raise ValueError(f"late row (tick {self.tick + 1} of the stream): frame {min(fl)} of clip {clip} is below the "
+                                     f"clip's completeness watermark {int(self.wm[cs])}: its score is final")
+                self._decide(cs, fl)
+
+    # ---- planning
+    def _finish(self, touched, ended, raw, opened, span, emit: bool = True, pre=None) -> ClipTick:
+        """Resolve the tick's contributions (ascending person id) to cells, move the watermarks, then (emit) plan the outputs that
+        became computable."""
+        raw.sort(key=lambda c: c[2])                  # (stable: a person's tail rows stay in frame order)
+        contribs, dropped = [], 0
+        for cs, f, _, src, row in raw:
+            e = ended.get(cs)
+            if self.origin[cs] <= f <= self.head[cs]:
+                contribs.append((cs, self._cell(cs, f), src, row))
+            elif e is not None and e[0] <= f <= e[1]:
+                contribs.append((cs, int(e[3] + f - e[0]), src, row))
+            else:
+                dropped += 1
+        self.dropped_total += dropped
+        outs, oc, of = pre if pre is not None else ([], [], [])
+        n_pre = len(outs)
+        L, R, sh = self.ring_len, self.radius, self.shift
+        for cs in sorted(touched):
+            clip = self._clip_of[cs]
+            if cs in ended:
+                o, h, c, b = ended[cs]
+                for j in range(c, h + 1):
+                    outs.append((cs, j - o, h - o + 1, b % L)); oc.append(clip); of.append(j)
+            w = self._watermark(cs)
+            self.wm[cs] = w
+            if not emit:
+                continue
+            o, b = int(self.origin[cs]), int(self.cbase[cs])
+            jmax = min(w - 1 + sh, int(self.head[cs])) - R
+            for j in range(int(self.cursor[cs]), jmax + 1):
+                outs.append((cs, j - o, -1, b % L)); oc.append(clip); of.append(j)
+            self.cursor[cs] = max(int(self.cursor[cs]), jmax + 1)
+        return ClipTick(opened, contribs, np.asarray(outs, np.int32).reshape(-1, 4), oc, np.asarray(of, np.int32), dropped,
+                        {s: (a, b) for s, (a, b) in span.items()}, n_pre)
+
+    def _drop_tracks(self, plan: ClosePlan, tail0: int, raw, touch) -> None:
+        pend, ci = self.seg_len - 1, 0
+        for ts in plan.slots:
+            key, _, rows = self._tracks.pop(int(ts))
+            cs = self.slot_of[key[:2]]
+            self._of_clip[cs].remove(int(ts))
+            touch(cs)
+            if rows >= self.seg_len:
+                if plan.keys[ci] != key:
+                    raise AssertionError(f"close plan names {plan.keys[ci]}, the clip table holds {key}")
+                raw += [(cs, int(plan.frames[ci, k]), key[2], 1, tail0 + ci * pend + k) for k in range(pend)]
+                ci += 1
+
+    def push(self, plan: TickPlan, keys, frame_ids, final0: int = 0, tail0: int = 0, normalised: bool = False) -> ClipTick:
+        """One tick, after `check` passed and TrackTable.push returned `plan` for the same keys and frame ids.  final0 / tail0:
+        rows of the finals / tails tensors at which this tick's finals / idle tails start (a group of ticks shares them)."""
+        if not normalised:
+            keys = [_key(k) for k in keys]
+        fids = np.asarray(frame_ids, dtype=np.int64).reshape(-1).tolist()
+        self.tick += 1
+        opened, raw, span, ended = [], [], {}, {}
+        pre = ([], [], [])
+        for cs in sorted(self._stale):               # catch up on what closes since the last push made computable
+            c, o = self._cursor_now(cs), int(self.origin[cs])
+            for j in range(int(self.cursor[cs]), c):
+                pre[0].append((cs, j - o, -1, int(self.cbase[cs]) % self.ring_len)); pre[1].append(self._clip_of[cs]); pre[2].append(j)
+            self.cursor[cs] = c
+        self._stale.clear()
+
+        def touch(cs):
+            if cs not in span:
+                span[cs] = [self._lo_cell(cs), self._cell(cs, int(self.head[cs]))]
+
+        self._drop_tracks(plan.closed, tail0, raw, touch)
+        for clip, fl in self._by_clip(keys, fids).items():
+            cs = self.slot_of.get(clip)
+            if cs is None:
+                cs = self.slot_of[clip] = self._free.pop()
+                self._clip_of[cs], self._of_clip[cs] = clip, []
+                o, h = min(fl), max(fl)
+                self.origin[cs], self.head[cs], self.cursor[cs], self.cbase[cs], self.wm[cs] = o, h, o, 0, o
+                opened += [(cs, c) for c in range(h - o + 1)]
+                span[cs] = [0, h - o]
+                continue
+            touch(cs)
+            d = self._decide(cs, fl)
+            if d is None:
+                continue
+            hc = self._cell(cs, int(self.head[cs]))
+            if d[0] == "advance":
+                opened += [(cs, c) for c in range(hc + 1, hc + 1 + d[1] - int(self.head[cs]))]
+                self.head[cs] = d[1]
+            else:
+                ended[cs] = (int(self.origin[cs]), int(self.head[cs]), int(self.cursor[cs]), int(self.cbase[cs]))
+                self.origin[cs], self.head[cs], self.cursor[cs], self.cbase[cs] = d[1], d[2], d[1], hc + 1
+                opened += [(cs, c) for c in range(hc + 1, hc + 2 + d[2] - d[1])]
+            span[cs][1] = self._cell(cs, int(self.head[cs]))
+        for (ts, r, j), k, f in zip(plan.desc.tolist(), keys, fids):
+            cs = self.slot_of[k[:2]]
+            if r == 0:
+                self._tracks[ts] = [k, [], 0]
+                self._of_clip[cs].append(ts)
+            rec = self._tracks[ts]
+            rec[1].append(f)
+            rec[2] += 1
+            if j >= 0:
+                raw.append((cs, rec[1].pop(0), k[2], 0, final0 + j))
+        return self._finish(set(span), ended, raw, opened, span, pre=pre)
+
+    def close(self, plan: ClosePlan, tail0: int = 0) -> ClipTick:
+        """Tracks closed by TrackTable.close: their tails are contributions; nothing is emitted (the next push or end_clip does)."""
+        raw, span = [], {}
+
+        def touch(cs):
+            if cs not in span:
+                span[cs] = [self._lo_cell(cs), self._cell(cs, int(self.head[cs]))]
+
+        self._drop_tracks(plan, tail0, raw, touch)
+        self._stale |= set(span)
+        return self._finish(set(span), {}, raw, [], span, emit=False)
+
+    def tracks_of(self, clip) -> List[Key]:
+        """The open tracks of a clip, in the order they were opened."""
+        cs = self.slot_of[(int(clip[0]), int(clip[1]))]
+        return [self._tracks[ts][0] for ts in self._of_clip[cs]]
+
+    def end_clip(self, clip) -> ClipTick:
+        """Free the clip's slot (all of its tracks are closed) -> the outputs of its remaining frames, cursor .. head, with the
+        reflection at the end of the segment."""
+        clip = (int(clip[0]), int(clip[1]))
+        cs = self.slot_of.get(clip)
+        if cs is None:
+            raise KeyError(f"clip {clip} is not open")
+        if self._of_clip[cs]:
+            raise ValueError(f"clip {clip} still has open tracks: {self.tracks_of(clip)}")
+        o, h, c, b = int(self.origin[cs]), int(self.head[cs]), int(self.cursor[cs]), int(self.cbase[cs])
+        fr = np.arange(c, h + 1, dtype=np.int64)
+        outs = np.stack([np.full_like(fr, cs), fr - o, np.full_like(fr, h - o + 1), np.full_like(fr, b % self.ring_len)], axis=1)
+        span = {cs: (self._lo_cell(cs), self._cell(cs, h))}
+        del self.slot_of[clip], self._of_clip[cs]
+        self._stale.discard(cs)
+        self._clip_of[cs] = None
+        self._free.append(cs)
+        return ClipTick([], [], outs.astype(np.int32).reshape(-1, 4), [clip] * len(fr), fr.astype(np.int32), 0, span)
 
 
 @dataclass
@@ -321,6 +735,7 @@ class Tick:
     final: FrameScores                # the row each emitted window finalised
     closed: FrameScores               # tails of the tracks max_idle closed at the start of this tick
     first_window_id: int              # windows this stream had emitted before the tick (keys the in-kernel noise)
+    clip: Optional[ClipFrames] = None  # PoseStream(clip_scores=...): the clip scores that became computable with this tick
 
 
 class PoseStream:
@@ -330,14 +745,19 @@ class PoseStream:
     max_tracks: slots of the device rings; ring_len: rows kept per track (>= seg_len, default seg_len);
     num_transform: default the model's; max_idle: see TrackTable; max_group_rows: cap on the rows of one launch group of
     push_many (default and upper limit max_tracks * (ring_len - seg_len + 1), at least max_tracks): it sizes the staging buffers.
+    clip_scores: None, or a ClipScoreCfg: online per-clip frame scores (the definitions above ClipScoreCfg) -- every Tick then
+    carries `clip`, the ClipFrames that became computable with it, and close_clip ends a clip.  The model's pad_size and the HR
+    masks are NOT applied online (they need the clip's final length: evaluation devices of the dataset path); whatever
+    anomaly_score_pad_size the model has is ignored here.  With clip_scores = None nothing of this runs.
 
     One PoseStream is driven from ONE stream (the current stream of the first push): its rings, staging buffers and the track
     table are per-tick state, and the launches of a tick are ordered only by that stream."""
 
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
-                 num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None):
+                 num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
+                 clip_scores: Optional[ClipScoreCfg] = None):
         import torch
-        from .engine import StreamRings
+        from .engine import ClipRings, StreamRings
         from .utils.transforms import affine_table
         self.latent = bool(getattr(model, "is_latent", False))
         if self.latent and model.device.type != "cuda":
@@ -359,6 +779,22 @@ class PoseStream:
         n = self.table.max_tracks
         self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev)
         self.ring = self.rings.ring
+        self.clips, self.clip_rings, clip_words = None, None, 0
+        if clip_scores is not None:
+            cc = clip_scores
+            sigma = float(model.anomaly_score_filter_kernel_size if cc.sigma is None else cc.sigma)
+            shift = int(model.anomaly_score_frames_shift if cc.shift is None else cc.shift)
+            if not sigma > 0 or shift < 0:
+                raise ValueError(f"clip_scores: need sigma > 0 and shift >= 0, got {sigma}, {shift}")
+            radius = int(4.0 * sigma + 0.5)
+            per_track = self.table.ring_len - self.seg_len + 1
+            clen = (2 * radius + shift + self.seg_len + (self.table.max_idle or 64) + per_track + 1
+                    if cc.clip_ring_len is None else int(cc.clip_ring_len))
+            self.clips = ClipTable(cc.max_clips, clen, radius, shift, self.seg_len)
+            self.clip_rings = ClipRings(self.clips.max_clips, clen, nt, sigma, shift, device=dev)
+            # one launch pair of a group: a run (5) and an output (4) per cell of the clip rings at most, a contribution (2) per
+            # final of the group and per tail row of an idle closure
+            clip_words = self.clips.max_clips * clen * 9 + 2 * n * (self.seg_len - 1)
         with torch.cuda.device(dev):
             self.affine = affine_table(nt).to(dev)
             # one group's host-to-device traffic: raw rows (n, 34) f32 | descriptors (n, 4) i32 | windows (n, 5) i32, in ONE copy
@@ -367,8 +803,9 @@ class PoseStream:
             self.max_group_rows = n * per_track if max_group_rows is None else min(int(max_group_rows), n * per_track)
             if self.max_group_rows < n:
                 raise ValueError(f"max_group_rows = {max_group_rows} is less than max_tracks = {n}: one tick would not fit a group")
-            self._pinned = torch.empty(self.max_group_rows * (ROW + 4 + 5), dtype=torch.int32).pin_memory()
-            self._staged = torch.empty(self.max_group_rows * (ROW + 4 + 5), device=dev, dtype=torch.int32)
+            words = self.max_group_rows * (ROW + 4 + 5 + (2 if self.clips is not None else 0)) + clip_words
+            self._pinned = torch.empty(words, dtype=torch.int32).pin_memory()
+            self._staged = torch.empty(words, device=dev, dtype=torch.int32)
             self._copied = torch.cuda.Event()
         self._host = self._pinned.numpy()
         self.n_emitted = 0          # windows (x transforms) emitted so far = first_window_id of the next tick
@@ -399,6 +836,39 @@ class PoseStream:
             out = self.rings.flush(win, n)
         return FrameScores(keys, plan.frames.reshape(-1).copy(), out)
 
+    def _clip_launches(self, cticks: List[ClipTick], parts: list):
+        """The launch pairs of a tick's / a group's ClipTicks (one, unless batch_clip_ticks has to cut) -> (launches, index in
+        `parts` of the first one's three arrays, appended there so that they ride in the caller's one copy)."""
+        launches = [merge_clip_ticks([cticks[i] for i in b], self.clips.ring_len) for b in batch_clip_ticks(cticks, self.clips.ring_len)]
+        at = len(parts)
+        first = launches[0]
+        if len(first.runs) or len(first.outs):
+            parts += [first.runs, first.contrib, first.outs]
+        return launches, at
+
+    def _clip_run(self, cticks: List[ClipTick], launches, views, finals, tails) -> List[ClipFrames]:
+        """Run the launch pairs -> one ClipFrames per ClipTick.  views: the device views of the first launch's arrays (None if it
+        is empty); a further launch pair of the same group (rare: batch_clip_ticks) takes a copy of its own."""
+        import torch
+        vals = []
+        for k, la in enumerate(launches):
+            n_runs, n_out = len(la.runs), len(la.outs)
+            if k == 0:
+                v = views
+            else:
+                v = self._upload([la.runs, la.contrib, la.outs]) if n_runs or n_out else None
+            pre = self.clip_rings.emit(v[2][:4 * la.n_pre], la.n_pre) if la.n_pre else None      # (before the update: see ClipTable)
+            if n_runs:
+                self.clip_rings.update(v[0], n_runs, v[1], len(la.contrib), finals, tails)
+            out = self.clip_rings.emit(v[2][4 * la.n_pre:] if n_out > la.n_pre else None, n_out - la.n_pre)
+            if pre is not None:
+                out = torch.cat([pre, out])
+            o = 0
+            for c in la.n_out:
+                vals.append(out[o:o + c])
+                o += c
+        return [ClipFrames(list(t.clips), t.frames.copy(), vals[i], t.dropped) for i, t in enumerate(cticks)]
+
     # ------------------------------------------------------------------ the tick
     def push(self, keys, frame_ids, poses, *, noise=None) -> Tick:
         """One tick = one video frame: poses (n, 34) raw rows x1,y1,...,x17,y17 (as in the trajectory CSVs) of the tracks
@@ -413,15 +883,23 @@ class PoseStream:
             raise ValueError(f"poses must be ({len(keys)}, {ROW}) = one row x1,y1,...,x17,y17 per key, got {raw.shape}")
         if not np.isfinite(raw).all():
             raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+        if self.clips is not None:
+            keys = [_key(k) for k in keys]
+            self.clips.check(keys, frame_ids, True)   # (before any change: a tick the clip rules reject leaves both tables alone)
         plan = self.table.push(keys, frame_ids)
         n, ne, nt, dev = len(plan.desc), plan.n_emit, self.num_transform, self.device
         first = self.n_emitted
+        cticks = None if self.clips is None else [self.clips.push(plan, keys, frame_ids, normalised=True)]
         with torch.cuda.device(dev):
             closed = self._flush(plan.closed)         # before the new rows: a freed slot may be handed out again in this tick
             wb = None
             scores = torch.empty(nt * ne, device=dev, dtype=torch.float32)
+            parts = [raw, plan.desc, plan.win] if n else []
+            if cticks is not None:
+                launches, at = self._clip_launches(cticks, parts)
+            views = self._upload(parts) if parts else []
             if n:
-                raw_d, desc_d, win_d = self._upload([raw, plan.desc, plan.win])
+                raw_d, desc_d, win_d = views[:3]
                 base, trans = self.rings.push(raw_d, desc_d, n, ne)
             if ne:
                 m = self.model
@@ -433,10 +911,14 @@ class PoseStream:
                 final = self.rings.frame_scores(scores, win_d, ne)
             else:
                 final = torch.empty(0, nt, device=dev, dtype=torch.float32)
+            clip = None
+            if cticks is not None:
+                clip = self._clip_run(cticks, launches, views[at:at + 3] or None, final, closed.values)[0]
         self.n_emitted += nt * ne
         return Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                     trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores, windows=wb,
-                    final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final), closed=closed, first_window_id=first)
+                    final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final), closed=closed, first_window_id=first,
+                    clip=clip)
 
     def push_many(self, ticks, *, noise=None) -> List[Tick]:
         """Several ticks in one call: ticks = [(keys, frame_ids, poses), ...], each triple what one `push` takes.  Returns, bit
@@ -461,11 +943,14 @@ class PoseStream:
             if not np.isfinite(raw).all():
                 raise ValueError(f"tick {i}: raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
             raws.append(raw)
-        groups, planned = pack_ticks(self.table, [(t[0], t[1]) for t in ticks], self.num_transform, self.max_group_rows)
+        packed = pack_ticks(self.table, [(t[0], t[1]) for t in ticks], self.num_transform, self.max_group_rows, self.clips)
+        groups, planned = packed[0], packed[1]
         total = self.num_transform * sum(g.n_windows for g in groups)
         if noise is not None and (noise.dim() < 3 or noise.shape[2] != total):
             raise ValueError(f"noise must hold the {total} windows of the call on its third axis, got {tuple(noise.shape)}")
         self.table.adopt(planned)
+        if self.clips is not None:
+            self.clips.adopt(packed[2])
         out, lo = [], 0
         for g in groups:
             nw = self.num_transform * g.n_windows
@@ -482,8 +967,12 @@ class PoseStream:
         with torch.cuda.device(dev):
             closed = self._flush(g.closed)            # before the new rows: a freed slot may be handed out again in this group
             scores = torch.empty(nt * nw, device=dev, dtype=torch.float32)
+            parts = [np.concatenate(raws), g.desc, g.win] if n else []
+            if g.clip is not None:
+                launches, at = self._clip_launches(g.clip, parts)
+            views = self._upload(parts) if parts else []
             if n:
-                raw_d, desc_d, win_d = self._upload([np.concatenate(raws), g.desc, g.win])
+                raw_d, desc_d, win_d = views[:3]
                 base, trans = self.rings.push_group(raw_d, desc_d, n, nw)
             if nw:
                 m = self.model
@@ -494,6 +983,9 @@ class PoseStream:
                 final = self.rings.frame_scores_group(scores, win_d, nw)
             else:
                 final = torch.empty(0, nt, device=dev, dtype=torch.float32)
+            clips = [None] * len(g.plans)
+            if g.clip is not None:
+                clips = self._clip_run(g.clip, launches, views[at:at + 3] or None, final, closed.values)
         self.n_emitted += nt * nw
         out, c0 = [], 0
         for i, plan in enumerate(g.plans):
@@ -505,14 +997,46 @@ class PoseStream:
             out.append(Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                             trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores[a:b], windows=wb,
                             final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne]), closed=tail,
-                            first_window_id=first + a))
+                            first_window_id=first + a, clip=clips[i]))
             c0 = c1
         return out
 
     def close(self, keys) -> FrameScores:
         """End the tracks `keys` and free their slots -> the frame scores of their last seg_len - 1 rows (tracks that never had
         seg_len rows return nothing).  Asynchronous on the current stream."""
-        return self._flush(self.table.close(keys))
+        return self._close(keys)[0]
+
+    def _close(self, keys):
+        import torch
+        plan = self.table.close(keys)
+        tails = self._flush(plan)
+        if self.clips is None:
+            return tails, None
+        ct = self.clips.close(plan)          # the tails into their cells at once, in a launch of their own; nothing is emitted
+        if ct.contribs:
+            with torch.cuda.device(self.device):
+                la = merge_clip_ticks([ct], self.clips.ring_len)
+                runs_d, contrib_d = self._upload([la.runs, la.contrib])
+                self.clip_rings.update(runs_d, len(la.runs), contrib_d, len(la.contrib), None, tails.values)
+        return tails, ct
+
+    def close_clip(self, key):
+        """End the clip key = (scene, clip): close its open tracks (their tails come back as `close` returns them), emit the
+        clip's remaining frames up to its head with the reflection at the end of the sequence, and free its slot
+        -> (FrameScores, ClipFrames).  Across the ticks and this tail, the clip's output is the filter over its whole current
+        segment.  A later row for the clip opens a new clip (its tracks need `reopen` first)."""
+        import torch
+        if self.clips is None:
+            raise RuntimeError("close_clip needs PoseStream(clip_scores=ClipScoreCfg(...))")
+        clip = (int(key[0]), int(key[1]))
+        if clip not in self.clips.slot_of:
+            raise KeyError(f"clip {clip} is not open")
+        tails, ct = self._close(self.clips.tracks_of(clip))
+        end = self.clips.end_clip(clip)
+        with torch.cuda.device(self.device):
+            outs = self._upload([end.outs])[0] if end.n_out else None
+            values = self.clip_rings.emit(outs, end.n_out)
+        return tails, ClipFrames(end.clips, end.frames, values, ct.dropped)
 
     def close_all(self) -> FrameScores:
         return self.close(list(self.table.slot_of))

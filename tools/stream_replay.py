@@ -22,6 +22,12 @@ unless --ring-len says otherwise (then a call may be cut into several launch gro
 their last row.  "tick" is then one CALL (K ticks: one copy, one mcd_stream_push_group, ONE scoring call on the windows of all K
 ticks, one mcd_stream_frame_scores_group per group), the baseline ONE scoring call on a pre-built batch of the call's window count,
 and rows_per_s = pose rows pushed / time in push or push_many over a whole replay (every call, also those without a window).
+--clip-scores [--sigma S]: the online per-clip frame scores (PoseStream(clip_scores=...)) ride in every tick, so
+"tick" includes mcd_stream_clip_update + mcd_stream_clip_emit; every clip is ended with close_clip after the last call (not timed).
+On an on-disk split the AUC of the ONLINE scores against the ground-truth masks is printed next to the offline AUC (frames of the
+masks without an emitted score are excluded and counted).  The two differ by definition -- online, a frame's persons are those
+with a score at that frame, not the clip's whole roster, and neither pad_size nor the HR masks are applied -- so neither is
+asserted against the other.
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
 emitted windows, the range of the per-replay medians (the spread), and the same for the baseline."""
 import argparse
@@ -41,7 +47,7 @@ from mocodad_amd.data.windows import TrajectoryWindows, WindowBatch  # noqa: E40
 from mocodad_amd.engine import normalize_poses  # noqa: E402
 from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
 from mocodad_amd.models.mocodad_latent import MoCoDADlatent  # noqa: E402
-from mocodad_amd.stream import PoseStream, ticks_by_frame  # noqa: E402
+from mocodad_amd.stream import ClipScoreCfg, PoseStream, ticks_by_frame  # noqa: E402
 from mocodad_amd.utils.argparser import load_config  # noqa: E402
 
 
@@ -77,6 +83,8 @@ def main():
     ap.add_argument("--rows", type=int, default=120, help="rows per synthetic track")
     ap.add_argument("--ring-len", type=int, default=None)
     ap.add_argument("--ticks-per-call", type=int, default=1, help="K > 1: K ticks per push_many call (1: one push per tick)")
+    ap.add_argument("--clip-scores", action="store_true", help="online per-clip frame scores in every tick (Tick.clip)")
+    ap.add_argument("--sigma", type=float, default=None, help="Gaussian sigma of the clip scores (default: the model's filter_kernel_size)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
     cli = ap.parse_args()
@@ -142,9 +150,12 @@ def main():
     kw = dict(n_samples=model.n_generated_samples, noise_steps=model.noise_steps, aggregation=model.aggregation_strategy,
               seed=model.seed, loss_fn=model.loss_name)
 
-    def replay(collect=None):
+    clip_keys = sorted({k[:2] for k, _, _ in tracks})
+    clip_cfg = ClipScoreCfg(sigma=cli.sigma, max_clips=len(clip_keys)) if cli.clip_scores else None
+
+    def replay(collect=None, online=None):
         stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=ring_len,
-                            num_transform=nt)
+                            num_transform=nt, clip_scores=clip_cfg)
         times, counts, rows, spent = [], [], 0, 0.0
         for call, done in calls:
             torch.cuda.synchronize()
@@ -163,8 +174,15 @@ def main():
                     if ne:
                         idx = np.asarray([t * n + sample_of[tuple(int(v) for v in m)] for t in range(nt) for m in tick.meta[:ne]])
                         collect[idx] = tick.scores.cpu().numpy()
+            if online is not None:
+                online += [tick.clip for tick in out]
             if done:
                 stream.close(done)
+        if clip_cfg is not None:
+            for clip in clip_keys:
+                _, tail = stream.close_clip(clip)
+                if online is not None:
+                    online.append(tail)
         return np.asarray(times), counts, rows / spent
 
     def baseline(counts):
@@ -183,12 +201,34 @@ def main():
         return np.asarray(times)
 
     scores = np.full(nt * n, np.nan, np.float32)
-    _, counts, _ = replay(scores)                # warm-up replay (code objects, allocator pools); also the scores for the AUC
+    online = [] if cli.clip_scores else None
+    _, counts, _ = replay(scores, online)        # warm-up replay (code objects, allocator pools); also the scores for the AUC
     baseline(counts)
     assert not np.isnan(scores).any() and sum(counts) == nt * n, "the replay did not emit every window of the dataset path"
     auc = None
     if not cli.synthetic_tracks:
         auc = float(model.post_processing(scores, None, tw.trans.long().numpy(), tw.meta.numpy(), tw.frames.numpy()))
+    clip_res = None
+    if online is not None:
+        n_scores = sum(len(cf) for cf in online)
+        clip_res = {"sigma": float(model.anomaly_score_filter_kernel_size if cli.sigma is None else cli.sigma),
+                    "shift": int(model.anomaly_score_frames_shift), "frames_scored": n_scores,
+                    "dropped_rows": sum(cf.dropped_rows for cf in online)}
+        if not cli.synthetic_tracks:
+            from sklearn.metrics import roc_auc_score
+            gts, _ = model._gt_and_masks()
+            score_of = {(clip, int(f)): float(v) for cf in online for clip, f, v in zip(cf.clips, cf.frames, cf.values.cpu().numpy())}
+            y, p, missing = [], [], 0
+            for clip, gt in gts.items():
+                for i, label in enumerate(np.asarray(gt).reshape(-1)):
+                    v = score_of.get((tuple(int(c) for c in clip), i + 1))        # frame ids are 1-based
+                    if v is None:
+                        missing += 1
+                    else:
+                        y.append(int(label))
+                        p.append(v)
+            clip_res.update(gt_frames=len(y) + missing, gt_frames_without_score=missing,
+                            auc_online=float(roc_auc_score(y, p)) if len(set(y)) == 2 else None)
     t_stream, t_base, rate = [], [], []
     for _ in range(cli.reps):                   # alternating: both legs see the same machine state
         t, _, r = replay()
@@ -200,10 +240,13 @@ def main():
            "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
-           "model": "MoCoDADlatent" if latent else "MoCoDAD",
+           "model": "MoCoDADlatent" if latent else "MoCoDAD", "clip_scores": clip_res,
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
+    if clip_res is not None and clip_res.get("auc_online") is not None:
+        print(f"AUC of the online clip scores: {clip_res['auc_online']:.6f} ({clip_res['gt_frames_without_score']} of "
+              f"{clip_res['gt_frames']} ground-truth frames without an emitted score excluded; a different definition: not comparable bit for bit)")
     print(f"{K} tick(s) per call, {res['rows_per_s']['median']} rows/s | tick: median {res['tick']['median_us']} us, p99 {res['tick']['p99_us']} us | baseline score_fused alone: median "
           f"{res['baseline_score_fused']['median_us']} us, p99 {res['baseline_score_fused']['p99_us']} us")
     line = json.dumps(res)
