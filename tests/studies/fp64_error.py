@@ -21,8 +21,9 @@ import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from oracle import mocodad_oracle as O  # noqa: E402
+from pose_ref import oracle_dtype, to_f64, trained_scale  # noqa: E402  (the reference's dtype switch and the trained-scale recipe, stated once)
 
 torch.set_grad_enabled(False)
 _orig = O._conv_bn
@@ -56,10 +57,7 @@ def _conv_bn_split(sd, conv, bn, x):
     return y + bf[None, :, None, None]
 
 
-O._conv_bn = _conv_bn_split
-_pe = O.pos_encoding
-DTYPE = torch.float32
-O.pos_encoding = lambda t, ch: _pe(t, ch).to(DTYPE)     # (the fp32 sinusoid table is part of the model: same values in the fp64 run)
+O._conv_bn = _conv_bn_split      # (this script is its own process: nothing else imports the patched oracle)
 
 
 def load(variant):
@@ -69,41 +67,11 @@ def load(variant):
     return {k: torch.from_numpy(v) for k, v in w.items()}, cfg
 
 
-def trained_scale(sd, cfg, seed):
-    """BatchNorm gains x 10^U(-1,1), PReLU slopes alternating 0.01 / 1.5; the last layer rescaled so that the U-Net's
-    eps-prediction stays O(1) (otherwise the 200x..1000x gain of the reverse chain overflows, with any arithmetic)."""
-    g = torch.Generator().manual_seed(seed)
-    out = {k: v.clone() for k, v in sd.items()}
-    i = 0
-    for k in sorted(out):
-        if k.endswith(".tcn.1.weight") or k.endswith(".residual.1.weight") or k.endswith(".block.1.weight"):
-            out[k] = out[k] * 10 ** (torch.rand(out[k].shape, generator=g) * 2 - 1)
-        if k.endswith(".prelu.weight"):
-            out[k] = torch.full_like(out[k], 0.01 if i % 2 == 0 else 1.5)
-            i += 1
-    Tu = cfg["seg_len"] if cfg["conditioning_strategy"] != "inject" else len(O.split_indices(cfg["seg_len"], cfg["conditioning_indices"], "inject")[1])
-    for _ in range(3):
-        x = torch.randn(16, 2, Tu, 17, generator=g)
-        cond = torch.randn(16, 16, generator=g) * 0.5 if cfg["conditioning_strategy"] == "inject" else None
-        eps = O.unet_forward(out, x, torch.full((16,), 5, dtype=torch.long), cond) - x
-        s = float(eps.std())
-        for n in ("tcn.0.weight", "tcn.0.bias", "residual.0.weight", "residual.0.bias", "tcn.1.bias", "residual.1.bias"):
-            k = "model.st_gcnnsu3.1." + n
-            if k.endswith("1.bias"):
-                out[k] = out[k] * (0.5 / s)
-            elif k.endswith("0.weight") or k.endswith("0.bias"):
-                out[k] = out[k] * (0.5 / s)
-        for n in ("tcn.1.running_mean", "residual.1.running_mean"):
-            out["model.st_gcnnsu3.1." + n] = out["model.st_gcnnsu3.1." + n] * (0.5 / s)
-    return out
-
-
 def scores(sd, cfg, data, noise, ns, dtype):
-    global DTYPE
-    DTYPE = dtype
-    sdd = {k: (v.to(dtype) if v.dtype.is_floating_point else v) for k, v in sd.items()}
-    p, corrupt = O.reverse_diffusion(sdd, data.to(dtype), noise.to(dtype), noise_steps=ns, strategy=cfg["conditioning_strategy"],
-                                     conditioning_indices=cfg["conditioning_indices"])
+    sdd = to_f64(sd) if dtype == torch.float64 else sd
+    with oracle_dtype(dtype):      # (the fp32 sinusoid table is part of the model: same values in the fp64 run)
+        p, corrupt = O.reverse_diffusion(sdd, data.to(dtype), noise.to(dtype), noise_steps=ns, strategy=cfg["conditioning_strategy"],
+                                         conditioning_indices=cfg["conditioning_indices"])
     return O.window_losses(p, corrupt).t().double().numpy()
 
 
