@@ -506,12 +506,15 @@ int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value
  * gather buffer of such an encoder and H of such a frame count come from the stream-ordered allocator (hipMallocAsync /
  * hipFreeAsync on `stream`) because this entry has no workspace argument.
  * Windows are independent (ABI version 11, see mcd_score): a non-finite pose in a condition frame (cond_emb and z0) or in a
- * corrupt frame (z0 alone) stays with its window; every other window's cond_emb and z0 are bit-identical to the call without it. */
+ * corrupt frame (z0 alone) stays with its window; every other window's cond_emb and z0 are bit-identical to the call without it.
+ * Alignment: at t_unet 5 .. 12 z0_out must be 16-byte aligned (the projection launch stores four floats at a time), else
+ * MCD_EINVAL before any launch; at t_unet 3 any float alignment is taken. */
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                       const float* step_table, float* cond_emb_out, float* z0_out, void* stream);
 
 /* TEST ENTRY.  Replaces: Denoiser.forward (components.py:265-291) for n_rows arbitrary rows at one time step t >= 0 shared by
- * them: x (N,D), cond (N,16), step_table with at least t + 1 rows -> eps_out (N,D).  Runs the chain kernel's layer code. */
+ * them: x (N,D), cond (N,16), step_table with at least t + 1 rows -> eps_out (N,D).  Runs the chain kernel's layer code.
+ * Alignment: x and eps_out must be 16-byte aligned (rows are read and stored four floats at a time), else MCD_EINVAL. */
 int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
                        int32_t n_rows, float* eps_out, void* stream);
 
@@ -528,14 +531,17 @@ int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const floa
  * one whose state becomes non-finite returns a non-finite loss and changes no other chain's result; `best` / `worst` skip it
  * like the reference's strict comparisons do.  Windows are independent too (ABI version 11, see mcd_score and
  * mcd_latent_encode): a window with non-finite poses has non-finite losses, and no other window's losses, latents or code
- * change by a bit. */
+ * change by a bit.
+ * Alignment: noise (when given) and workspace must be 16-byte aligned, else MCD_EINVAL before any launch; the regions carved
+ * from the workspace (cond_emb, z0, gather, H) then are too.  The outputs take any float alignment. */
 int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                      const float* noise, uint64_t seed, int64_t first_window_id, const float* step_table, void* workspace,
                      int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,
                      void* stream);
 
 /* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
- * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121). */
+ * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121).
+ * Alignment: noise_out must be 16-byte aligned (an element group of four floats is one store), else MCD_EINVAL. */
 int mcd_latent_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
                             int32_t latent_dim, float* noise_out, void* stream);
 

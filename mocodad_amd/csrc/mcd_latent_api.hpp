@@ -106,6 +106,9 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     if (cfg->n_windows <= 0) return MCD_OK;
     if (!data || !step_table || !cond_emb_out || !z0_out) return fail(MCD_EINVAL, "null argument");
     if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
+    // 5 .. 12 corrupt frames: latent_project_kernel writes z0 with 16-byte stores (the 3-frame encode launch stores single floats;
+    // mcd_latent_score's z0 is a region of its 16-byte aligned workspace)
+    if (w->h_floats && !aligned16(z0_out)) return fail(MCD_EINVAL, "z0_out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     // no workspace argument here: the plain encoder's scratch and H come from the stream-ordered allocator
     const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D, w->h_floats);

@@ -14,7 +14,7 @@ descriptors), ONE scoring call on the windows that end at the new rows, mcd_stre
 oldest row of each window is final and comes back).
 
 `TrackTable` is the host half: (scene, clip, person) -> ring slot, row counts, the frame ids of the last seg_len rows.  It is plain
-NumPy and imports no GPU module.  Windows follow the reference's rule (utils/preprocessing.py:14-86, the rule
+NumPy and touches no GPU module.  Windows follow the reference's rule (utils/preprocessing.py:14-86, the rule
 TrajectoryWindows.from_buffer implements): they run over CONSECUTIVE ROWS of a track, frame-number gaps included, so
 meta = [scene, clip, person, frame id of the window's first row] and frames = the frame ids of its seg_len rows.
 `PoseStream` owns the rings (engine.StreamRings) and the staging buffers and drives the launches of a tick.
@@ -34,6 +34,7 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
+import torch      # (module level: the one name every device allocation of this file goes through, tests/guarded.py)
 
 ROW = 34                 # floats of one pose row: (2, 17)
 Key = Tuple[int, int, int]
@@ -756,7 +757,6 @@ class PoseStream:
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
                  num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
                  clip_scores: Optional[ClipScoreCfg] = None):
-        import torch
         from .engine import ClipRings, StreamRings
         from .utils.transforms import affine_table
         self.latent = bool(getattr(model, "is_latent", False))
@@ -828,7 +828,6 @@ class PoseStream:
         return [self._staged[o:o + w] for o, w in views]
 
     def _flush(self, plan: ClosePlan) -> FrameScores:
-        import torch
         n, pend = len(plan), self.seg_len - 1
         keys = [k for k in plan.keys for _ in range(pend)]
         with torch.cuda.device(self.device):
@@ -849,7 +848,6 @@ class PoseStream:
     def _clip_run(self, cticks: List[ClipTick], launches, views, finals, tails) -> List[ClipFrames]:
         """Run the launch pairs -> one ClipFrames per ClipTick.  views: the device views of the first launch's arrays (None if it
         is empty); a further launch pair of the same group (rare: batch_clip_ticks) takes a copy of its own."""
-        import torch
         vals = []
         for k, la in enumerate(launches):
             n_runs, n_out = len(la.runs), len(la.outs)
@@ -876,7 +874,6 @@ class PoseStream:
         noise: (S, max(ns-1,1), num_transform * n_emit, C, Tx, V) -- for a latent model (S, max(ns-1,1), num_transform * n_emit, D)
         -- replacing the in-kernel Philox draws for the tick's windows (parity tests); by default the draws are keyed by
         (model.seed, Tick.first_window_id + position in the tick)."""
-        import torch
         from .data.windows import WindowBatch
         raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
         if raw.ndim != 2 or raw.shape[1] != ROW or raw.shape[0] != len(keys):
@@ -930,7 +927,6 @@ class PoseStream:
         noise: (S, max(ns-1,1), windows of the whole call, ...) in that order: tick after tick, inside a tick as for `push`.
         A rejected call (a bad shape, a non-finite row, a duplicate or closed key, no free slot: the error names the tick) changes
         nothing."""
-        import torch
         ticks = list(ticks)
         raws = []
         for i, t in enumerate(ticks):
@@ -960,7 +956,6 @@ class PoseStream:
         return out
 
     def _run_group(self, g: GroupPlan, raws, noise) -> List[Tick]:
-        import torch
         from .data.windows import WindowBatch
         n, nw, nt, dev, pend = g.n_rows, g.n_windows, self.num_transform, self.device, self.seg_len - 1
         first = self.n_emitted
@@ -1007,7 +1002,6 @@ class PoseStream:
         return self._close(keys)[0]
 
     def _close(self, keys):
-        import torch
         plan = self.table.close(keys)
         tails = self._flush(plan)
         if self.clips is None:
@@ -1025,7 +1019,6 @@ class PoseStream:
         clip's remaining frames up to its head with the reflection at the end of the sequence, and free its slot
         -> (FrameScores, ClipFrames).  Across the ticks and this tail, the clip's output is the filter over its whole current
         segment.  A later row for the clip opens a new clip (its tracks need `reopen` first)."""
-        import torch
         if self.clips is None:
             raise RuntimeError("close_clip needs PoseStream(clip_scores=ClipScoreCfg(...))")
         clip = (int(key[0]), int(key[1]))

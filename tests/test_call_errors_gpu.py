@@ -158,9 +158,10 @@ def pose_cases(p: Pose):
 class Latent:
     def __init__(self, name="A_benign"):
         import latent_ref as R
+        import latentt_fixtures as TT
         from helpers import make_args
         from mocodad_amd.models.mocodad_latent import MoCoDADlatent
-        sd, _, cfg, _ = R.load_fixture(name)
+        sd, _, cfg, _ = TT.load(name) if name in TT.NAMES else R.load_fixture(name)
         m = MoCoDADlatent(make_args(cfg))
         m.load_state_dict(sd, strict=False)
         self.sc = m.to("cuda:0").scorer()
@@ -186,11 +187,11 @@ class Latent:
                                        C.byref(v) if v is not None else None, noise, 1, 0, d(table, _ptr(self.table)), d(ws, _ptr(self.ws)),
                                        aggr, C.c_float(q), d(agg, _ptr(self.agg)), loss, None, None, None)
 
-    def encode(self, cfg="default", data="default", cond="default"):
+    def encode(self, cfg="default", data="default", cond="default", z_off=0):
         d = lambda a, b: b if isinstance(a, str) else a
         cfg = d(cfg, self.cfg())
         return self.L.mcd_latent_encode(self.h, C.byref(cfg), d(data, _ptr(self.data)), None, _ptr(self.table), d(cond, _ptr(self.emb)),
-                                        _ptr(self.z), None)
+                                        _ptr(self.z, z_off), None)
 
     def denoise(self, x="default", t=1, off=0):
         return self.L.mcd_latent_denoise(self.h, _ptr(self.z, off) if isinstance(x, str) else x, _ptr(self.emb), _ptr(self.table), t, B,
@@ -236,13 +237,24 @@ def latent_cases(p: Latent):
     }
 
 
-HANDLES = ["inject", "concat", "rndimp", "latent"]
+def latent_s12_cases(p: Latent):
+    """6 + 6 frames: at 5 .. 12 corrupt frames latent_project_kernel stores z0 four floats at a time (at 3 the encode launch stores
+    single floats and takes any float alignment: nothing to reject there)."""
+    return {
+        "encode: misaligned z0_out": lambda: p.encode(z_off=4),
+    }
+
+
+HANDLES = ["inject", "concat", "rndimp", "latent", "latentS12"]
 
 
 def cases(handle):
     if handle not in _ctx:
-        p = Latent() if handle == "latent" else Pose(handle)
-        _ctx[handle] = latent_cases(p) if handle == "latent" else pose_cases(p)
+        if handle == "latentS12":
+            _ctx[handle] = latent_s12_cases(Latent("S12"))
+        else:
+            p = Latent() if handle == "latent" else Pose(handle)
+            _ctx[handle] = latent_cases(p) if handle == "latent" else pose_cases(p)
     return _ctx[handle]
 
 
