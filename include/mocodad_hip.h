@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 13
+#define MCD_ABI_VERSION 14
 
 enum {
     MCD_OK = 0,
@@ -295,8 +295,8 @@ int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float v
  *                 trajectory buffer.
  *   frame_scores  (n_slots, num_transform, ring_len) f32: cell r % ring_len = running maximum over the windows that cover row r.
  * A slot is one track; which track owns which slot, its row count and its frame ids are the host's business.  A tick holds AT MOST
- * ONE row per slot (the kernels use plain loads and stores); a GROUP of ticks (the two *_group entries below) at most
- * ring_len - seg_len + 1.  One state is driven from one stream. */
+ * ONE row per slot, a GROUP of ticks -- what the entries below take; a tick is a group of one -- at most ring_len - seg_len + 1
+ * (the kernels use plain loads and stores).  One state is driven from one stream. */
 typedef struct {
     float* ring;
     float* frame_scores;
@@ -306,65 +306,52 @@ typedef struct {
     int32_t num_transform;
 } mcd_stream_state_t;
 
-/* One tick's rows into the rings.  raw (n, 34) f32 as for mcd_normalize_poses, same arithmetic bit for bit (center / scale (34,)
- * f64 or both NULL; PRECONDITION: finite); desc (n, 3) i32 device = [slot, row index r, emit index j] per row, j = -1 while the
- * track has fewer than seg_len rows, else its position among the tick's n_emit windows.  Per row: the normalised pose goes to both
- * ring positions, the row's frame-score cell is zeroed for every transform (which also makes a reused slot start clean), and for
- * j >= 0 the window descriptors of the window ENDING at row r are written for all transforms, transform-major like the dataset
- * order (utils/dataset.py:67-71): base_out[t * n_emit + j] (i64 element offsets into `ring`), trans_out[t * n_emit + j] = t --
- * the `base` / `trans` of a mcd_window_view_t over `ring` for mcd_score_view / mcd_score_fused.  Rows whose slot is out of range
- * are ignored. */
-int mcd_stream_push(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_emit,
-                    float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
-                    int32_t* trans_out, void* stream);
+/* A GROUP of consecutive ticks in one launch each: mcd_stream_push_group, ONE scoring call on all of the group's windows,
+ * mcd_stream_frame_scores_group -- with the result of one such triple per tick, bit for bit.  A track may receive up to
+ * ring_len - seg_len + 1 rows in a group (so ring_len > seg_len is what makes a group longer than a tick): then its
+ * rows r0 - seg_len + 1 .. r0 + R - 1, the pending ones and the R new ones, sit at distinct ring positions, and no cell that is
+ * zeroed aliases a pending one.  No track that receives a row in the group may be closed inside it (its slot is not handed out
+ * again within the group); the caller cuts groups accordingly (mocodad_amd/stream.py: pack_ticks).
+ * The group's windows are TICK-major, and inside a tick transform-major like the dataset order (utils/dataset.py:67-71): with
+ * ne_i windows emitted by tick i and off_i = num_transform * (ne_0 + ... + ne_{i-1}), the window of the j-th emitting row of
+ * tick i under transform t is at batch position off_i + t * ne_i + j -- consecutive ticks are consecutive slices, and a caller
+ * that numbers windows globally gives each the id sequential ticks would have given it.
+ * A SINGLE TICK is a group of one: at most one row per slot, pos0 = j (the row's position among the tick's n_emit windows),
+ * ne = n_emit, w = j; n_windows = n_emit.
+ *
+ * mcd_stream_push_group: raw (n, 34) f32 as for mcd_normalize_poses, same arithmetic bit for bit (center / scale (34,) f64 or
+ * both NULL; PRECONDITION: finite); desc (n, 4) i32 device = [slot, row index r, pos0, ne] per row: pos0 = off_i + j, the batch
+ * position of the row's window under transform 0 (-1 while the track has fewer than seg_len rows), ne = ne_i, the stride between
+ * transforms.  Slots may repeat (rows of one track, ascending r).  Per row: the normalised pose goes to both ring positions, the
+ * row's frame-score cell is zeroed for every transform (which also makes a reused slot start clean), and for pos0 >= 0 the
+ * window descriptors of the window ENDING at row r are written for every transform: base_out[pos0 + t * ne] (i64 element offsets
+ * into `ring`), trans_out[pos0 + t * ne] = t -- the `base` / `trans` of a mcd_window_view_t over `ring` for mcd_score_view /
+ * mcd_score_fused; base_out / trans_out hold num_transform * n_windows entries, n_windows = the sum of the ne_i.  Rows whose slot
+ * is out of range are ignored, window positions outside the outputs are not written. */
+int mcd_stream_push_group(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_windows,
+                          float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
+                          int32_t* trans_out, void* stream);
 
-/* The tick's window scores into the frame-score ring (replaces mocodad.py:392-393 + eval_utils.py:27-34 for the rows in flight).
- * scores (num_transform * n_emit,) f32 in the order of base_out; win (n_emit, 2) i32 device = [slot, r_last] (the row the window
- * ends at).  max(score, 0) -- the clamp of mcd_scatter_max -- is taken into the cells of rows r_last - seg_len + 1 .. r_last;
- * final_out (n_emit, num_transform) f32 = the cell of row r_last - seg_len + 1, which no later window covers: that row's final
- * frame score. */
-int mcd_stream_frame_scores(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_emit,
-                            float* final_out, void* stream);
+/* The group's window scores into the frame-score ring (replaces mocodad.py:392-393 + eval_utils.py:27-34 for the rows in
+ * flight).  scores (num_transform * n_windows,) f32 in the order of base_out; win (n_windows, 5) i32 device =
+ * [slot, r_last, pos0, ne, w], SORTED by slot and within a slot by r_last; r_last = the row the window ends at, w = the window's
+ * index in (tick, j) order.  Per window max(score, 0) -- the clamp of mcd_scatter_max; a NaN score adds 0 -- is taken into the
+ * cells of rows r_last - seg_len + 1 .. r_last.  The windows of one track overlap within the launch: one thread per (track,
+ * transform) applies them in row order with plain loads and stores (no atomics, no race).
+ * final_out (n_windows, num_transform) f32 in (tick, j) order: row w = the cell of row r_last - seg_len + 1 once window w is in,
+ * which no later window covers: that row's final frame score. */
+int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_windows,
+                                  float* final_out, void* stream);
 
 /* Tracks being closed: win (n, 2) i32 device = [slot, r_last = index of the track's last row]; out (n, seg_len - 1, num_transform)
  * f32 = the cells of the still-pending rows r_last - seg_len + 2 .. r_last.  (Tracks of fewer than seg_len rows have no window,
  * hence no frame score -- the dataset path drops them, utils/preprocessing.py:4-10 -- and are not passed here.) */
 int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream);
 
-/* A GROUP of consecutive ticks in one launch each: mcd_stream_push_group, ONE scoring call on all of the group's windows,
- * mcd_stream_frame_scores_group -- with the result of the per-tick entries above called tick by tick, bit for bit.  A track may
- * receive up to ring_len - seg_len + 1 rows in a group (so ring_len > seg_len is what makes a group longer than a tick): then its
- * rows r0 - seg_len + 1 .. r0 + R - 1, the pending ones and the R new ones, sit at distinct ring positions, and no cell that is
- * zeroed aliases a pending one.  No track that receives a row in the group may be closed inside it (its slot is not handed out
- * again within the group); the caller cuts groups accordingly (mocodad_amd/stream.py: pack_ticks).
- * The group's windows are TICK-major, and inside a tick transform-major as above: with ne_i windows emitted by tick i and
- * off_i = num_transform * (ne_0 + ... + ne_{i-1}), the window of the j-th emitting row of tick i under transform t is at batch
- * position off_i + t * ne_i + j -- consecutive ticks are consecutive slices, and a caller that numbers windows globally gives
- * each the id sequential ticks would have given it.
- *
- * mcd_stream_push_group: raw (n, 34) f32, desc (n, 4) i32 device = [slot, row index r, pos0, ne] per row: pos0 = off_i + j, the
- * batch position of the row's window under transform 0 (-1 while the track has fewer than seg_len rows), ne = ne_i, the stride
- * between transforms.  Slots may repeat (rows of one track, ascending r).  Per row exactly what mcd_stream_push does: both ring
- * positions, the row's frame-score cells zeroed, and for pos0 >= 0 base_out[pos0 + t * ne], trans_out[pos0 + t * ne] = t for
- * every transform; base_out / trans_out hold num_transform * n_windows entries, n_windows = the sum of the ne_i.  Rows whose slot
- * is out of range are ignored, window positions outside the outputs are not written. */
-int mcd_stream_push_group(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_windows,
-                          float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
-                          int32_t* trans_out, void* stream);
-
-/* The group's window scores into the frame-score ring.  scores (num_transform * n_windows,) f32 in the order of base_out;
- * win (n_windows, 5) i32 device = [slot, r_last, pos0, ne, w], SORTED by slot and within a slot by r_last; w = the window's index
- * in (tick, j) order.  The windows of one track overlap within the launch: one thread per (track, transform) applies them in row
- * order with plain loads and stores (no atomics, no race), max(score, 0) as in mcd_stream_frame_scores (a NaN score adds 0).
- * final_out (n_windows, num_transform) f32 in (tick, j) order: row w = the cell of row r_last - seg_len + 1 once window w is in,
- * which no later window covers -- what mcd_stream_frame_scores returns for it tick by tick. */
-int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_windows,
-                                  float* final_out, void* stream);
-
 /* Online clip scores of a live stream: the last stage of post_processing -- the person aggregation
  * mean_p s + (max_p log1p s - min_p log1p s) (mocodad.py:399-401), score_process = shift + gaussian_filter1d (eval_utils.py:100-106)
  * and the mean over the transforms (mocodad.py:424) -- incrementally, one value per video frame of a clip, from the final per-row
- * frame scores the entries above return (final_out of mcd_stream_frame_scores[_group], out of mcd_stream_flush).
+ * frame scores the entries above return (final_out of mcd_stream_frame_scores_group, out of mcd_stream_flush).
  * Semantics (mocodad_amd/stream.py: ClipTable holds the host half):
  *   raw(f, t)   = sum_p s_p / n + (max_p log1p(s_p) - min_p log1p(s_p)) over the n persons that have a final score at frame f,
  *                 in float64, 0 when n = 0.  (The dataset path counts every person of the WHOLE clip, absent ones as zeros; a live

@@ -620,38 +620,6 @@ static int stream_params(const mcd_stream_state_t* s, StreamParams* P) {
     return MCD_OK;
 }
 
-int mcd_stream_push(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_emit,
-                    float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
-                    int32_t* trans_out, void* stream) {
-    StreamParams P;
-    if (int rc = stream_params(s, &P)) return rc;
-    if (n < 0 || n_emit < 0 || n_emit > n) return fail(MCD_EINVAL, "need 0 <= n_emit <= n");
-    if (n > s->n_slots) return fail(MCD_EINVAL, "more rows than slots: a tick holds at most one row per track");
-    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
-    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
-    if (n == 0) return MCD_OK;
-    if (!raw || !desc || (n_emit > 0 && (!base_out || !trans_out))) return fail(MCD_EINVAL, "null argument");
-    hipLaunchKernelGGL(stream_push_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, raw, desc, n,
-                       n_emit, vid_w, vid_h, center, scale, reinterpret_cast<long long*>(base_out), trans_out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
-
-int mcd_stream_frame_scores(const mcd_stream_state_t* s, const float* scores, const int32_t* win, int32_t n_emit,
-                            float* final_out, void* stream) {
-    StreamParams P;
-    if (int rc = stream_params(s, &P)) return rc;
-    if (n_emit < 0 || n_emit > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n_emit <= n_slots");
-    if (n_emit == 0) return MCD_OK;
-    if (!scores || !win || !final_out) return fail(MCD_EINVAL, "null argument");
-    const long long total = (long long)n_emit * P.nt;
-    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
-    hipLaunchKernelGGL(stream_frame_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
-                       scores, win, n_emit, final_out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
-
 int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream) {
     StreamParams P;
     if (int rc = stream_params(s, &P)) return rc;

@@ -2,9 +2,9 @@
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
 //   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
-//   stream_push / stream_frame_scores / stream_flush kernels   the same loader step + sliding windows + scatter-max, one tick at a
-//                               time on device rings            utils/preprocessing.py:14-86, models/mocodad.py:392-393
-//   stream_push_group / stream_frame_scores_group kernels   the same for a group of ticks in one launch each
+//   stream_push_group / stream_frame_scores_group / stream_flush kernels   the same loader step + sliding windows + scatter-max,
+//                               one group of ticks at a time (a single tick is a group of one) on device rings
+//                                                               utils/preprocessing.py:14-86, models/mocodad.py:392-393
 //   stream_clip_update / stream_clip_emit kernels   online per-clip frame scores: the person aggregate, shift and Gaussian of
 //                               post_processing, incrementally on a per-clip ring     models/mocodad.py:399-424, utils/eval_utils.py:100-106
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
@@ -216,55 +216,13 @@ __global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __res
 //   pose ring  (n_slots, 2 L, 2, 17): row r of a track sits at positions r % L and r % L + L, so the seg_len rows from row s on
 //              are contiguous from position s % L and a window stays ONE base offset of mcd_window_view_t.
 //   score ring (n_slots, num_transform, L): running max, per row and transform, over the windows covering the row.
-// A tick holds at most one row per track, so no two threads of a launch touch the same cell: plain loads and stores.
+// The launches on them take a GROUP of consecutive ticks; a single tick is a group of one.  No two threads of a launch touch the
+// same cell (the bound on a group, below, and one thread per track where windows overlap): plain loads and stores.
 // ------------------------------------------------------------------------------------------------
 struct StreamParams {
     float* ring; float* fs;
     int n_slots, L, seg_len, nt;
 };
-
-// one thread per pushed row: desc (n, 3) = [slot, row index r, emit index j | -1]
-__global__ __launch_bounds__(256) void stream_push_kernel(StreamParams S, const float* __restrict__ raw, const int* __restrict__ desc,
-                                                          int n, int n_emit, float vid_w, float vid_h,
-                                                          const double* __restrict__ center, const double* __restrict__ scale,
-                                                          long long* __restrict__ base_out, int* __restrict__ trans_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int slot = desc[3 * i], r = desc[3 * i + 1], j = desc[3 * i + 2];
-    if (slot < 0 || slot >= S.n_slots || r < 0) return;        // (a descriptor the host table cannot produce: touch nothing)
-    const int p = r % S.L;
-    float* o = S.ring + ((size_t)slot * 2 * S.L + p) * 34;
-    normalize_pose_row(raw + (size_t)i * 34, vid_w, vid_h, center, scale, o, o + (size_t)S.L * 34);
-    for (int t = 0; t < S.nt; ++t) S.fs[((size_t)slot * S.nt + t) * S.L + p] = 0.f;
-    if (j < 0 || j >= n_emit || r < S.seg_len - 1) return;
-    const long long base = ((long long)slot * 2 * S.L + (r - S.seg_len + 1) % S.L) * 34;
-    for (int t = 0; t < S.nt; ++t) {
-        base_out[(size_t)t * n_emit + j] = base;
-        trans_out[(size_t)t * n_emit + j] = t;
-    }
-}
-
-// one thread per (emitted window j, transform t): win (n_emit, 2) = [slot, r_last]; scores (num_transform * n_emit,) transform-major.
-// The same clamp and zero start as scatter_max_kernel; final_out (n_emit, num_transform) = the cell of row r_last - seg_len + 1,
-// which no later window covers.
-__global__ __launch_bounds__(256) void stream_frame_scores_kernel(StreamParams S, const float* __restrict__ scores,
-                                                                  const int* __restrict__ win, int n_emit,
-                                                                  float* __restrict__ final_out) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_emit * S.nt) return;
-    const int j = u / S.nt, t = u - j * S.nt;
-    const int slot = win[2 * j], r_last = win[2 * j + 1];
-    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
-    const float sc = fmaxf(scores[(size_t)t * n_emit + j], 0.f);
-    float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
-    const int first = r_last - S.seg_len + 1;
-    for (int k = S.seg_len - 1; k >= 0; --k) {
-        float* c = row + (first + k) % S.L;
-        const float m = fmaxf(*c, sc);
-        *c = m;
-        if (k == 0) final_out[u] = m;
-    }
-}
 
 // one thread per (closed track i, pending row k, transform t): the seg_len - 1 cells of rows r_last - seg_len + 2 .. r_last
 __global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const int* __restrict__ win, int n,
@@ -278,11 +236,14 @@ __global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const
     out[u] = S.fs[((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L];
 }
 
-// A GROUP of ticks in one launch (PoseStream.push_many): a track may receive R <= L - seg_len + 1 rows, so the rows
+// A GROUP of ticks in one launch (PoseStream.push / push_many): a track may receive R <= L - seg_len + 1 rows, so the rows
 // r0 - seg_len + 1 .. r0 + R - 1 of a track -- the pending ones and the new ones -- sit at distinct ring positions, and no two
 // rows of the launch share a pose position or a frame-score cell.  The group's windows are tick-major, inside a tick
-// transform-major: the window of transform t of a row is at batch position pos0 + t * ne, with ne = its tick's window count.
-// one thread per pushed row: desc (n, 4) = [slot, row index r, pos0 | -1, ne]; n_win = windows x transforms of the group
+// transform-major: the window of transform t of a row is at batch position pos0 + t * ne, with ne = its tick's window count
+// (a single tick with n_emit windows: pos0 = the row's emit index j, ne = n_emit, the dataset's transform-major order).
+// one thread per pushed row: desc (n, 4) = [slot, row index r, pos0 | -1, ne]; n_win = windows x transforms of the group.
+// Per row: the normalised pose to both ring positions, the row's frame-score cell zeroed for every transform, and for pos0 >= 0
+// the descriptors of the window ENDING at row r for every transform.
 __global__ __launch_bounds__(256) void stream_push_group_kernel(StreamParams S, const float* __restrict__ raw,
                                                                 const int* __restrict__ desc, int n, int n_win, float vid_w,
                                                                 float vid_h, const double* __restrict__ center,
@@ -306,8 +267,10 @@ __global__ __launch_bounds__(256) void stream_push_group_kernel(StreamParams S, 
 
 // win (n, 5) = [slot, r_last, pos0, ne, w] per window, sorted by slot and, within a slot, by row; w = the window's index in
 // (tick, j) order = its row of final_out (n, num_transform).  The windows of one track overlap, so one thread per (track,
-// transform) -- the thread of the track's FIRST window -- applies them in row order with plain loads and stores: the cells end
-// as after tick-by-tick stream_frame_scores_kernel launches, and each window's oldest row is final once that window is in.
+// transform) -- the thread of the track's FIRST window -- applies them in row order with plain loads and stores: per window
+// max(score, 0), the clamp and zero start of scatter_max_kernel, goes into the cells of its rows r_last - seg_len + 1 .. r_last,
+// so the cells end as after one launch per tick, and each window's oldest row, which no later window covers, is final once
+// that window is in.
 // (An emitting slot holds ONE track within a group: a slot is only handed out again inside a group when its track got no row in it.)
 __global__ __launch_bounds__(256) void stream_frame_scores_group_kernel(StreamParams S, const float* __restrict__ scores,
                                                                         const int* __restrict__ win, int n, int n_win,

@@ -595,9 +595,9 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
 
 
 class StreamRings:
-    """Device state of a live pose stream (mcd_stream_state_t) and the launches on it (three per tick; push_group /
-    frame_scores_group: the same for a group of ticks, PoseStream.push_many); the host half -- which track owns
-    which slot, row counts, frame ids -- is mocodad_amd.stream.TrackTable, the tick that ties them together PoseStream.push.
+    """Device state of a live pose stream (mcd_stream_state_t) and the launches on it: flush, push_group and frame_scores_group
+    per group of ticks (a single tick is a group of one); the host half -- which track owns which slot, row counts, frame
+    ids -- is mocodad_amd.stream.TrackTable, the call that ties them together PoseStream.push / push_many.
       ring          flat (n_slots * 2 * ring_len * 34,) fp32: row r of slot s at positions r % L and r % L + L of its 2 L rows
       frame_scores  (n_slots, num_transform, ring_len) fp32 running maxima
     vid_res / center / scale: as for normalize_poses.  All calls are asynchronous on the current stream; one state is driven
@@ -620,30 +620,11 @@ class StreamRings:
                                        n_slots=self.n_slots, ring_len=self.ring_len, seg_len=self.seg_len,
                                        num_transform=self.num_transform)
 
-    def push(self, raw: torch.Tensor, desc: torch.Tensor, n: int, n_emit: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """mcd_stream_push: raw (n, 34) fp32 rows, desc (n, 3) int32 [slot, row index, emit index | -1] (device; any dtype of 4
-        bytes: views of one staging buffer) -> (base (num_transform * n_emit,) int64, trans (same,) int32), transform-major."""
-        nw = self.num_transform * int(n_emit)
-        with torch.cuda.device(self.device):
-            base = torch.empty(nw, device=self.device, dtype=torch.int64)
-            trans = torch.empty(nw, device=self.device, dtype=torch.int32)
-            c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
-            _lib.check(self.L.mcd_stream_push(C.byref(self._state), _ptr(raw), _ptr(desc), int(n), int(n_emit), self.vid_res[0],
-                                              self.vid_res[1], _ptr(c), _ptr(s), _ptr(base), _ptr(trans), _stream()))
-        return base, trans
-
-    def frame_scores(self, scores: torch.Tensor, win: torch.Tensor, n_emit: int) -> torch.Tensor:
-        """mcd_stream_frame_scores: scores (num_transform * n_emit,) fp32, win (n_emit, 2) int32 [slot, r_last] ->
-        (n_emit, num_transform) final frame scores of the windows' first rows."""
-        with torch.cuda.device(self.device):
-            final = torch.empty(int(n_emit), self.num_transform, device=self.device, dtype=torch.float32)
-            _lib.check(self.L.mcd_stream_frame_scores(C.byref(self._state), _ptr(scores), _ptr(win), int(n_emit), _ptr(final), _stream()))
-        return final
-
     def push_group(self, raw: torch.Tensor, desc: torch.Tensor, n: int, n_windows: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """mcd_stream_push_group: the rows of a group of ticks, raw (n, 34) fp32, desc (n, 4) int32 [slot, row index, batch
-        position of the row's window under transform 0 | -1, windows of its tick] -> (base (num_transform * n_windows,) int64,
-        trans (same,) int32), tick-major, inside a tick transform-major."""
+        position of the row's window under transform 0 | -1, windows of its tick] (device; any dtype of 4 bytes: views of one
+        staging buffer) -> (base (num_transform * n_windows,) int64, trans (same,) int32), tick-major, inside a tick
+        transform-major."""
         nw = self.num_transform * int(n_windows)
         with torch.cuda.device(self.device):
             base = torch.empty(nw, device=self.device, dtype=torch.int64)

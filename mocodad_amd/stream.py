@@ -9,9 +9,10 @@ between two ticks lives on the device (include/mocodad_hip.h: mcd_stream_state_t
               kernels read the ring exactly as they read a trajectory buffer.
   score ring  (max_tracks, num_transform, L): the running maximum, per row and transform, over the windows covering that row.
 
-and a tick is: one host-to-device copy of the new rows and their descriptors, mcd_stream_push (normalise + store + window
-descriptors), ONE scoring call on the windows that end at the new rows, mcd_stream_frame_scores (max into the score ring; the
-oldest row of each window is final and comes back).
+and a tick is: one host-to-device copy of the new rows and their descriptors, mcd_stream_push_group (normalise + store + window
+descriptors), ONE scoring call on the windows that end at the new rows, mcd_stream_frame_scores_group (max into the score ring;
+the oldest row of each window is final and comes back).  These launches take a GROUP of consecutive ticks; a tick is a group of
+one, and `PoseStream.push` and `push_many` share the one launch sequence (`PoseStream._run_group`).
 
 `TrackTable` is the host half: (scene, clip, person) -> ring slot, row counts, the frame ids of the last seg_len rows.  It is plain
 NumPy and touches no GPU module.  Windows follow the reference's rule (utils/preprocessing.py:14-86, the rule
@@ -41,10 +42,23 @@ Key = Tuple[int, int, int]
 
 
 def _key(k) -> Key:
+    if type(k) is tuple and len(k) == 3 and type(k[0]) is int and type(k[1]) is int and type(k[2]) is int:
+        return k                 # (already normalised: the case of every row of every tick once a feed hands out its own keys)
     k = tuple(int(v) for v in k)
     if len(k) != 3:
         raise ValueError(f"a track key is (scene, clip, person), got {k}")
     return k
+
+
+def _pose_rows(keys, poses) -> np.ndarray:
+    """The raw pose rows of one tick as a contiguous (len(keys), 34) fp32 host array; ValueError for another shape or a row that
+    is not finite."""
+    raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
+    if raw.ndim != 2 or raw.shape[1] != ROW or raw.shape[0] != len(keys):
+        raise ValueError(f"poses must be ({len(keys)}, {ROW}) = one row x1,y1,...,x17,y17 per key, got {raw.shape}")
+    if not np.isfinite(raw).all():
+        raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+    return raw
 
 
 @dataclass
@@ -175,7 +189,7 @@ class TrackTable:
         fids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
         if len(fids) != len(keys):
             raise ValueError(f"{len(keys)} keys but {len(fids)} frame ids")
-        if len(fids) and (fids.min() < np.iinfo(np.int32).min or fids.max() > np.iinfo(np.int32).max):
+        if len(fids) and (fids.min() < -2 ** 31 or fids.max() > 2 ** 31 - 1):
             raise ValueError("frame ids must fit int32")
         # every check before any change: a rejected tick leaves the table as it was
         seen = set()
@@ -210,7 +224,7 @@ class TrackTable:
         emit = r + 1 >= T
         desc = np.stack([slots, r, np.where(emit, np.cumsum(emit) - 1, -1)], axis=1).astype(np.int32)
         win = np.stack([slots[emit], r[emit]], axis=1).astype(np.int32)
-        ekeys = [keys[i] for i in np.flatnonzero(emit)]
+        ekeys = [keys[i] for i in np.flatnonzero(emit).tolist()]
         frames = self._fids[win[:, 0]].copy()
         base = (win[:, 0].astype(np.int64) * 2 * self.ring_len + (win[:, 1].astype(np.int64) - T + 1) % self.ring_len) * ROW
         meta = np.concatenate([np.asarray(ekeys, np.int64).reshape(-1, 3), frames[:, :1].astype(np.int64)], axis=1)
@@ -219,9 +233,10 @@ class TrackTable:
 
 @dataclass
 class GroupPlan:
-    """Consecutive ticks of one call that share their launches (pack_ticks): one upload, one mcd_stream_push_group, one scoring
-    call, one mcd_stream_frame_scores_group.  The group's windows are tick-major, inside a tick transform-major: the window of
-    the j-th emitting row of tick i under transform t is at batch position offsets[i] * num_transform + t * n_emit_i + j."""
+    """Consecutive ticks of one call that share their launches (pack_ticks; PoseStream.push: the one tick of the call): one
+    upload, one mcd_stream_push_group, one scoring call, one mcd_stream_frame_scores_group.  The group's windows are tick-major,
+    inside a tick transform-major: the window of the j-th emitting row of tick i under transform t is at batch position
+    offsets[i] * num_transform + t * n_emit_i + j (a group of one tick: t * n_emit + j, the dataset order)."""
     first_tick: int                   # index of the group's first tick in the call
     plans: List[TickPlan]             # the plans of its ticks, exactly those of sequential TrackTable.push calls
     desc: np.ndarray                  # (n, 4) int32 per pushed row, tick after tick: [slot, row index r, pos0 | -1, n_emit of its tick]
@@ -241,26 +256,36 @@ class GroupPlan:
 
 
 def _group(first_tick: int, plans: List[TickPlan], num_transform: int, seg_len: int) -> GroupPlan:
-    ne = np.asarray([p.n_emit for p in plans], np.int64)
-    offsets = np.zeros(len(plans) + 1, np.int64)
-    offsets[1:] = np.cumsum(ne)
-    desc, win = [], []
-    for i, p in enumerate(plans):
-        j = p.desc[:, 2].astype(np.int64)
-        pos0 = np.where(j >= 0, offsets[i] * num_transform + j, -1)
-        desc.append(np.stack([p.desc[:, 0], p.desc[:, 1], pos0, np.full(len(j), ne[i])], axis=1))
-        jj = np.arange(ne[i])
-        win.append(np.stack([p.win[:, 0], p.win[:, 1], offsets[i] * num_transform + jj, np.full(ne[i], ne[i]), offsets[i] + jj],
-                            axis=1))
-    desc = np.concatenate(desc).astype(np.int32).reshape(-1, 4)
-    win = np.concatenate(win).astype(np.int32).reshape(-1, 5)
-    win = win[np.argsort(win[:, 0], kind="stable")]            # (stable: within a slot the ticks, hence the rows, stay ascending)
-    closed = ClosePlan()
+    # (per-tick host work of PoseStream.push too: the tables are filled in place, a group of one tick takes no concatenation)
+    offs = [0]
     for p in plans:
-        closed.keys += p.closed.keys
-        closed.slots += p.closed.slots
-    closed.win = np.concatenate([p.closed.win for p in plans]).reshape(-1, 2)
-    closed.frames = np.concatenate([p.closed.frames for p in plans]).reshape(-1, seg_len - 1)
+        offs.append(offs[-1] + p.n_emit)
+    desc = np.empty((sum(len(p.desc) for p in plans), 4), np.int32)
+    win = np.empty((offs[-1], 5), np.int32)
+    r0 = 0
+    for i, p in enumerate(plans):
+        w0, ne, r1 = offs[i], offs[i + 1] - offs[i], r0 + len(p.desc)
+        d, w = desc[r0:r1], win[w0:w0 + ne]
+        d[:, :3] = p.desc                                      # [slot, r, j | -1] -> pos0 = off_i + j; -1 stays -1
+        if w0:
+            d[:, 2] += np.where(p.desc[:, 2] >= 0, w0 * num_transform, 0).astype(np.int32)
+        d[:, 3] = ne
+        w[:, :2] = p.win
+        w[:, 2] = np.arange(w0 * num_transform, w0 * num_transform + ne, dtype=np.int32)
+        w[:, 3] = ne
+        w[:, 4] = np.arange(w0, w0 + ne, dtype=np.int32)
+        r0 = r1
+    offsets = np.asarray(offs, np.int64)
+    win = win[np.argsort(win[:, 0], kind="stable")]            # (stable: within a slot the ticks, hence the rows, stay ascending)
+    if len(plans) == 1:
+        closed = plans[0].closed         # (nothing to merge: the ClosePlan of the tick itself)
+    else:
+        closed = ClosePlan()
+        for p in plans:
+            closed.keys += p.closed.keys
+            closed.slots += p.closed.slots
+        closed.win = np.concatenate([p.closed.win for p in plans]).reshape(-1, 2)
+        closed.frames = np.concatenate([p.closed.frames for p in plans]).reshape(-1, seg_len - 1)
     return GroupPlan(first_tick, plans, desc, win, offsets, closed)
 
 
@@ -797,8 +822,8 @@ class PoseStream:
             clip_words = self.clips.max_clips * clen * 9 + 2 * n * (self.seg_len - 1)
         with torch.cuda.device(dev):
             self.affine = affine_table(nt).to(dev)
-            # one group's host-to-device traffic: raw rows (n, 34) f32 | descriptors (n, 4) i32 | windows (n, 5) i32, in ONE copy
-            # (a tick of push: (n, 3) and (n, 2)); a group of push_many holds at most max_group_rows rows
+            # one group's host-to-device traffic: raw rows (n, 34) f32 | descriptors (n, 4) i32 | windows (n, 5) i32, in ONE copy;
+            # a tick of push is a group of one (at most max_tracks rows), a group of push_many holds at most max_group_rows rows
             per_track = self.table.ring_len - self.seg_len + 1
             self.max_group_rows = n * per_track if max_group_rows is None else min(int(max_group_rows), n * per_track)
             if self.max_group_rows < n:
@@ -874,48 +899,15 @@ class PoseStream:
         noise: (S, max(ns-1,1), num_transform * n_emit, C, Tx, V) -- for a latent model (S, max(ns-1,1), num_transform * n_emit, D)
         -- replacing the in-kernel Philox draws for the tick's windows (parity tests); by default the draws are keyed by
         (model.seed, Tick.first_window_id + position in the tick)."""
-        from .data.windows import WindowBatch
-        raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
-        if raw.ndim != 2 or raw.shape[1] != ROW or raw.shape[0] != len(keys):
-            raise ValueError(f"poses must be ({len(keys)}, {ROW}) = one row x1,y1,...,x17,y17 per key, got {raw.shape}")
-        if not np.isfinite(raw).all():
-            raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+        raw = _pose_rows(keys, poses)
         if self.clips is not None:
             keys = [_key(k) for k in keys]
             self.clips.check(keys, frame_ids, True)   # (before any change: a tick the clip rules reject leaves both tables alone)
         plan = self.table.push(keys, frame_ids)
-        n, ne, nt, dev = len(plan.desc), plan.n_emit, self.num_transform, self.device
-        first = self.n_emitted
-        cticks = None if self.clips is None else [self.clips.push(plan, keys, frame_ids, normalised=True)]
-        with torch.cuda.device(dev):
-            closed = self._flush(plan.closed)         # before the new rows: a freed slot may be handed out again in this tick
-            wb = None
-            scores = torch.empty(nt * ne, device=dev, dtype=torch.float32)
-            parts = [raw, plan.desc, plan.win] if n else []
-            if cticks is not None:
-                launches, at = self._clip_launches(cticks, parts)
-            views = self._upload(parts) if parts else []
-            if n:
-                raw_d, desc_d, win_d = views[:3]
-                base, trans = self.rings.push(raw_d, desc_d, n, ne)
-            if ne:
-                m = self.model
-                wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
-                # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches; else HipScorer.score_fused)
-                score = self.scorer.score if self.latent else self.scorer.score_fused
-                score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
-                      noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores)
-                final = self.rings.frame_scores(scores, win_d, ne)
-            else:
-                final = torch.empty(0, nt, device=dev, dtype=torch.float32)
-            clip = None
-            if cticks is not None:
-                clip = self._clip_run(cticks, launches, views[at:at + 3] or None, final, closed.values)[0]
-        self.n_emitted += nt * ne
-        return Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
-                    trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores, windows=wb,
-                    final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final), closed=closed, first_window_id=first,
-                    clip=clip)
+        g = _group(0, [plan], self.num_transform, self.seg_len)
+        if self.clips is not None:
+            g.clip = [self.clips.push(plan, keys, frame_ids, normalised=True)]
+        return self._run_group(g, [raw], noise)[0]
 
     def push_many(self, ticks, *, noise=None) -> List[Tick]:
         """Several ticks in one call: ticks = [(keys, frame_ids, poses), ...], each triple what one `push` takes.  Returns, bit
@@ -932,13 +924,10 @@ class PoseStream:
         for i, t in enumerate(ticks):
             if len(t) != 3:
                 raise ValueError(f"tick {i}: a tick is a (keys, frame_ids, poses) triple")
-            keys, _, poses = t
-            raw = np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)
-            if raw.ndim != 2 or raw.shape[1] != ROW or raw.shape[0] != len(keys):
-                raise ValueError(f"tick {i}: poses must be ({len(keys)}, {ROW}) = one row x1,y1,...,x17,y17 per key, got {raw.shape}")
-            if not np.isfinite(raw).all():
-                raise ValueError(f"tick {i}: raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
-            raws.append(raw)
+            try:
+                raws.append(_pose_rows(t[0], t[2]))
+            except ValueError as e:
+                raise ValueError(f"tick {i}: {e}") from None
         packed = pack_ticks(self.table, [(t[0], t[1]) for t in ticks], self.num_transform, self.max_group_rows, self.clips)
         groups, planned = packed[0], packed[1]
         total = self.num_transform * sum(g.n_windows for g in groups)
@@ -962,7 +951,7 @@ class PoseStream:
         with torch.cuda.device(dev):
             closed = self._flush(g.closed)            # before the new rows: a freed slot may be handed out again in this group
             scores = torch.empty(nt * nw, device=dev, dtype=torch.float32)
-            parts = [np.concatenate(raws), g.desc, g.win] if n else []
+            parts = [raws[0] if len(raws) == 1 else np.concatenate(raws), g.desc, g.win] if n else []
             if g.clip is not None:
                 launches, at = self._clip_launches(g.clip, parts)
             views = self._upload(parts) if parts else []
@@ -972,6 +961,7 @@ class PoseStream:
             if nw:
                 m = self.model
                 wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
+                # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches; else HipScorer.score_fused)
                 score = self.scorer.score if self.latent else self.scorer.score_fused
                 score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
                       noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores)

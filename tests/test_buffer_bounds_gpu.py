@@ -34,10 +34,10 @@ Guarded allocations seen per entry, from the proxy's registry (the last test pri
   mcd_latent_score        the test's out (B,); score: loss (B,2), latents (B,2,D), code (B,D); _workspace 512 B .. 513 536 B
   mcd_normalize_poses     normalize_poses (n,2,17);  mcd_scatter_max: scatter_max (3,7)
   mcd_frame_scores        FrameScoreAssembler.__call__: workspace (384,) uint8, out (15,) float64
-  mcd_stream_push, _frame_scores, _flush, _push_group, _frame_scores_group
+  mcd_stream_push_group, _frame_scores_group, _flush     (through PoseStream.push, a group of one tick, and push_many)
                           StreamRings.__init__: zeros ring (3*2*L*34,), zeros frame_scores (3,5,L); PoseStream.__init__: staging
-                          int32; push / _run_group: scores; StreamRings.push / push_group: base int64, trans int32;
-                          frame_scores[_group]: final (n,5); flush: (n*5,5); the scorer's _workspace
+                          int32; _run_group: scores; StreamRings.push_group: base int64, trans int32;
+                          frame_scores_group: final (n,5); flush: (n*5,5); the scorer's _workspace
   mcd_stream_clip_update, _clip_emit
                           ClipRings.__init__: zeros sum, lmax, lmin (2,5,90|92) float64, n int32; emit: (n_out,) float64
 
@@ -496,7 +496,7 @@ def test_stream_replay(stream_env, extra, how, clip):
     from test_stream_many_gpu import SEG_LEN
     g, model = stream_env
     names = (["clip_sum", "clip_lmax", "clip_lmin", "clip_n"] if clip else []) + ["ring", "frame_scores_ring"]
-    entry = "mcd_stream_push_group + frame_scores_group" if how != "push" else "mcd_stream_push + frame_scores"
+    entry = "mcd_stream_push_group + frame_scores_group" + (" (PoseStream.push: groups of one tick)" if how == "push" else "")
     r = run(entry + " + flush" + (" + clip_update + clip_emit" if clip else ""),
             lambda T: _replay(g, model, SEG_LEN + extra, how, clip), None, [model.scorer()], partial=names)
     ring = r["ring"].view(3, 2, SEG_LEN + extra, 34)
@@ -534,7 +534,7 @@ def test_the_guard_sees_one_row_past_the_end():
 # ------------------------------------------------------------------------------------------------ coverage of the C ABI
 COVERED = ["mcd_cond_encode", "mcd_unet_forward", "mcd_layer_forward", "mcd_philox_noise", "mcd_random_imp_masks", "mcd_score",
            "mcd_score_view", "mcd_score_fused", "mcd_aggregate", "mcd_aggregate_view", "mcd_scatter_max", "mcd_normalize_poses",
-           "mcd_stream_push", "mcd_stream_frame_scores", "mcd_stream_flush", "mcd_stream_push_group", "mcd_stream_frame_scores_group",
+           "mcd_stream_flush", "mcd_stream_push_group", "mcd_stream_frame_scores_group",
            "mcd_stream_clip_update", "mcd_stream_clip_emit", "mcd_frame_scores", "mcd_latent_encode", "mcd_latent_denoise",
            "mcd_latent_score", "mcd_latent_philox_noise"]
 

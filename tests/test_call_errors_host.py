@@ -4,6 +4,9 @@ before the call front end (mcd_call.hpp) existed:
 
     python tests/test_call_errors_host.py --record      # rewrites the "host" key; see the file's "how" entry
 
+(the stream_push_group / stream_frame_scores_group pairs: from the library of the last commit that also had per-tick stream
+entries, whose state and argument rules they took over one to one -- `--record FILE` writes a copy of the JSON elsewhere)
+
 Pointers that a rejected call never reads are the dummy address P."""
 import ctypes as C
 import json
@@ -57,8 +60,8 @@ def _agg_dense(L, cfg, strategy=1, q=0.0, loss_all=P, loss_agg=P):
     return L.mcd_aggregate(C.byref(cfg), 2, 17, strategy, C.c_float(q), loss_all, None, None, loss_agg, None, None)
 
 
-def _push(L, s, raw=P, desc=P, n=2, n_emit=1, w=640.0, h=360.0, center=None, scale=None, base=P, trans=P):
-    return L.mcd_stream_push(C.byref(s) if s is not None else None, raw, desc, n, n_emit, w, h, center, scale, base, trans, None)
+def _push(L, s, raw=P, desc=P, n=2, n_windows=1, w=640.0, h=360.0, center=None, scale=None, base=P, trans=P):
+    return L.mcd_stream_push_group(C.byref(s) if s is not None else None, raw, desc, n, n_windows, w, h, center, scale, base, trans, None)
 
 
 def _frames(L, c, scores=P, trans=P, meta=P, frames=P, n=4, ws=P, out=P):
@@ -117,29 +120,33 @@ CASES = {
     "normalize_poses: null out": lambda L: L.mcd_normalize_poses(P, 4, 640.0, 360.0, None, None, None, None),
     "normalize_poses: 2^40 frames": lambda L: L.mcd_normalize_poses(P, 1 << 40, 640.0, 360.0, None, None, P, None),
     # ---- mcd_stream_*
-    "stream_push: null state": lambda L: _push(L, None),
-    "stream_push: null ring": lambda L: _push(L, state(ring=None)),
-    "stream_push: null frame_scores": lambda L: _push(L, state(fs=None)),
-    "stream_push: n_slots 0": lambda L: _push(L, state(n_slots=0)),
-    "stream_push: num_transform 0": lambda L: _push(L, state(nt=0)),
-    "stream_push: seg_len 33": lambda L: _push(L, state(seg_len=33, ring_len=40)),
-    "stream_push: ring_len < seg_len": lambda L: _push(L, state(ring_len=5)),
-    "stream_push: rings over 2^31": lambda L: _push(L, state(n_slots=1 << 26, ring_len=32)),
-    "stream_push: score ring over 2^31": lambda L: _push(L, state(n_slots=1 << 19, ring_len=32, nt=1 << 8)),
-    "stream_push: n_emit > n": lambda L: _push(L, state(), n=1, n_emit=2),
-    "stream_push: n -1": lambda L: _push(L, state(), n=-1, n_emit=0),
-    "stream_push: n > n_slots": lambda L: _push(L, state(), n=5),
-    "stream_push: vid_w inf": lambda L: _push(L, state(), w=INF),
-    "stream_push: center without scale": lambda L: _push(L, state(), center=P),
-    "stream_push: null raw": lambda L: _push(L, state(), raw=None),
-    "stream_push: null desc": lambda L: _push(L, state(), desc=None),
-    "stream_push: null base_out": lambda L: _push(L, state(), base=None),
-    "stream_frame_scores: null state": lambda L: L.mcd_stream_frame_scores(None, P, P, 1, P, None),
-    "stream_frame_scores: seg_len 0": lambda L: L.mcd_stream_frame_scores(C.byref(state(seg_len=0)), P, P, 1, P, None),
-    "stream_frame_scores: n_emit -1": lambda L: L.mcd_stream_frame_scores(C.byref(state()), P, P, -1, P, None),
-    "stream_frame_scores: n_emit > n_slots": lambda L: L.mcd_stream_frame_scores(C.byref(state()), P, P, 5, P, None),
-    "stream_frame_scores: null scores": lambda L: L.mcd_stream_frame_scores(C.byref(state()), None, P, 1, P, None),
-    "stream_frame_scores: null final_out": lambda L: L.mcd_stream_frame_scores(C.byref(state()), P, P, 1, None, None),
+    "stream_push_group: null state": lambda L: _push(L, None),
+    "stream_push_group: null ring": lambda L: _push(L, state(ring=None)),
+    "stream_push_group: null frame_scores": lambda L: _push(L, state(fs=None)),
+    "stream_push_group: n_slots 0": lambda L: _push(L, state(n_slots=0)),
+    "stream_push_group: num_transform 0": lambda L: _push(L, state(nt=0)),
+    "stream_push_group: seg_len 33": lambda L: _push(L, state(seg_len=33, ring_len=40)),
+    "stream_push_group: ring_len < seg_len": lambda L: _push(L, state(ring_len=5)),
+    "stream_push_group: rings over 2^31": lambda L: _push(L, state(n_slots=1 << 26, ring_len=32)),
+    "stream_push_group: score ring over 2^31": lambda L: _push(L, state(n_slots=1 << 19, ring_len=32, nt=1 << 8)),
+    "stream_push_group: n_windows > n": lambda L: _push(L, state(), n=1, n_windows=2),
+    "stream_push_group: n -1": lambda L: _push(L, state(), n=-1, n_windows=0),
+    "stream_push_group: n = 29": lambda L: _push(L, state(), n=29),       # (state(): 4 * (12 - 6 + 1) = 28 rows per group)
+    # (n_windows <= n <= n_slots * (ring_len - seg_len + 1) <= n_slots * ring_len: the product reaches 2^31 only where the score
+    # ring does, so the state is what the entry refuses -- here the smallest such call, seg_len 1 and a window per cell)
+    "stream_push_group: n_windows * num_transform over 2^31": lambda L: _push(L, state(n_slots=1 << 19, ring_len=16, seg_len=1, nt=1 << 8),
+                                                                              n=1 << 23, n_windows=1 << 23),
+    "stream_push_group: vid_w inf": lambda L: _push(L, state(), w=INF),
+    "stream_push_group: center without scale": lambda L: _push(L, state(), center=P),
+    "stream_push_group: null raw": lambda L: _push(L, state(), raw=None),
+    "stream_push_group: null desc": lambda L: _push(L, state(), desc=None),
+    "stream_push_group: null base_out": lambda L: _push(L, state(), base=None),
+    "stream_frame_scores_group: null state": lambda L: L.mcd_stream_frame_scores_group(None, P, P, 1, P, None),
+    "stream_frame_scores_group: seg_len 0": lambda L: L.mcd_stream_frame_scores_group(C.byref(state(seg_len=0)), P, P, 1, P, None),
+    "stream_frame_scores_group: n_windows -1": lambda L: L.mcd_stream_frame_scores_group(C.byref(state()), P, P, -1, P, None),
+    "stream_frame_scores_group: n_windows = 29": lambda L: L.mcd_stream_frame_scores_group(C.byref(state()), P, P, 29, P, None),
+    "stream_frame_scores_group: null scores": lambda L: L.mcd_stream_frame_scores_group(C.byref(state()), None, P, 1, P, None),
+    "stream_frame_scores_group: null final_out": lambda L: L.mcd_stream_frame_scores_group(C.byref(state()), P, P, 1, None, None),
     "stream_flush: null state": lambda L: L.mcd_stream_flush(None, P, 1, P, None),
     "stream_flush: ring_len < seg_len": lambda L: L.mcd_stream_flush(C.byref(state(ring_len=3)), P, 1, P, None),
     "stream_flush: n > n_slots": lambda L: L.mcd_stream_flush(C.byref(state()), P, 5, P, None),

@@ -1,5 +1,5 @@
-"""Live pose streams on the GPU (mocodad_amd/stream.py: PoseStream over mcd_stream_push / mcd_stream_frame_scores /
-mcd_stream_flush) against the dataset path on the same rows.  Every comparison is exact: a compared value is a copy, a maximum, or
+"""Live pose streams on the GPU (mocodad_amd/stream.py: PoseStream over mcd_stream_push_group / mcd_stream_frame_scores_group /
+mcd_stream_flush, a tick being a group of one) against the dataset path on the same rows.  Every comparison is exact: a compared value is a copy, a maximum, or
 the output of a scoring launch whose result does not depend on the batch it ran in (tests/test_multirank_gpu.py)."""
 import os
 import pickle

@@ -122,7 +122,7 @@ def test_a_reused_slot_starts_at_row_0():
 
 @pytest.mark.parametrize("ring_len", [SEG_LEN, SEG_LEN + 3, 16])
 def test_base_offsets_address_the_right_rows_of_a_mirrored_ring(ring_len):
-    """NumPy model of the pose ring: row r of a track at positions r % L and r % L + L (what mcd_stream_push writes)."""
+    """NumPy model of the pose ring: row r of a track at positions r % L and r % L + L (what mcd_stream_push_group writes)."""
     tracks = _split_tracks("test")
     L, n_slots = ring_len, 18                                 # fewer slots than the 22 tracks: reused through close()
     table = TrackTable(max_tracks=n_slots, seg_len=SEG_LEN, ring_len=L)

@@ -262,13 +262,16 @@ def test_latent_model_three_ticks_per_call_equals_sequential_pushes(env, tmp_pat
 
 def test_frame_score_group_entry_equals_tick_by_tick_launches():
     """mcd_stream_frame_scores_group alone on synthetic scores (a NaN, negatives): four overlapping windows on slot 0, two on slot
-    2, one on slot 1, in four ticks -- cells and finals equal sequential mcd_stream_frame_scores launches on a second state."""
+    2, one on slot 1, in four ticks -- cells and finals equal (1) a NumPy model of one launch per tick, the loop of
+    tests/test_stream_many_host.py::_model_sequential with np.fmax for both maxima (a NaN score adds 0, as fmaxf does), and
+    (2) the entry itself called tick by tick, one one-tick group each (win rows [slot, r_last, j, n_emit, j]), on a second state."""
     from mocodad_amd.engine import StreamRings
     L, nt = SEG_LEN + 3, NT
     a = StreamRings(3, SEG_LEN, L, nt, VID_RES, device=DEV)
     b = StreamRings(3, SEG_LEN, L, nt, VID_RES, device=DEV)
     gen = torch.Generator().manual_seed(5)
     stale = torch.rand(3, nt, L, generator=gen) * 0.5         # pending maxima of earlier windows, the same in both states
+    assert (stale > 0).all()                                  # (no zero whose sign the model would have to get right)
     a.frame_scores_ring.copy_(stale)
     b.frame_scores_ring.copy_(stale)
     ticks = [[(0, 5), (2, 7)], [(0, 6), (1, 5), (2, 8)], [(0, 7)], [(0, 8)]]          # per tick: [slot, r_last] in emit order
@@ -276,17 +279,29 @@ def test_frame_score_group_entry_equals_tick_by_tick_launches():
     scores = torch.randn(nt * n, generator=gen)
     scores[3], scores[11], scores[17] = float("nan"), -2.0, -0.0
     assert int((scores < 0).sum()) > 5
+    scores_h = scores.numpy().copy()
     scores = scores.to(DEV)
-    win5, finals, off = [], [], 0
+    fs = stale.numpy().copy()                                 # the model: window after window in (tick, j) order
+    win5, finals, model, off = [], [], [], 0
     for t in ticks:
         ne = len(t)
-        finals.append(b.frame_scores(scores[nt * off:nt * (off + ne)], torch.tensor(t, dtype=torch.int32, device=DEV), ne))
+        one = [(slot, r, j, ne, j) for j, (slot, r) in enumerate(t)]      # a single tick as a group: sorted by slot within the tick
+        one.sort(key=lambda w: (w[0], w[1]))
+        finals.append(b.frame_scores_group(scores[nt * off:nt * (off + ne)], torch.tensor(one, dtype=torch.int32, device=DEV), ne))
+        for j, (slot, r) in enumerate(t):
+            sc = np.fmax(scores_h[nt * off + np.arange(nt) * ne + j], np.float32(0))
+            for k in range(SEG_LEN):
+                c = (r - SEG_LEN + 1 + k) % L
+                fs[slot, :, c] = np.fmax(fs[slot, :, c], sc)
+            model.append(fs[slot, :, (r - SEG_LEN + 1) % L].copy())
         win5 += [(slot, r, nt * off + j, ne, off + j) for j, (slot, r) in enumerate(t)]
         off += ne
     win5.sort(key=lambda w: (w[0], w[1]))
     got = a.frame_scores_group(scores, torch.tensor(win5, dtype=torch.int32, device=DEV), n)
     want = torch.cat(finals)
     assert got.shape == want.shape == (n, nt)
+    assert np.array_equal(_bits(got), _bits(np.stack(model)))
+    assert np.array_equal(_bits(a.frame_scores_ring), _bits(fs))
     assert np.array_equal(_bits(got), _bits(want))
     assert np.array_equal(_bits(a.frame_scores_ring), _bits(b.frame_scores_ring))
     assert not torch.isnan(got).any() and not torch.equal(a.frame_scores_ring.cpu(), stale)

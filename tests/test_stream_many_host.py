@@ -1,13 +1,14 @@
 """Host half of PoseStream.push_many (mocodad_amd/stream.py: pack_ticks) without a GPU: the groups of a call concatenate to exactly
 the plans of sequential TrackTable.push calls, every group respects the three cutting rules and is as long as they allow, the
 merged descriptors follow the tick-major formula, a NumPy model of the two group launches leaves the frame-score ring and the
-finals that tick-by-tick launches leave, and a rejected call names its tick and changes nothing."""
+finals that tick-by-tick launches leave, a one-plan group (what PoseStream.push builds) is the group pack_ticks returns for
+that tick, and a rejected call names its tick and changes nothing."""
 import numpy as np
 import pytest
 
 from dataset_spec import DATASET
 from mocodad_amd.data import trajectories as T
-from mocodad_amd.stream import TrackTable, pack_ticks, ticks_by_frame
+from mocodad_amd.stream import TrackTable, _group, pack_ticks, ticks_by_frame
 
 SEG_LEN = 6
 NT = 5
@@ -90,7 +91,8 @@ def _check_descriptors(g, nt, seg_len):
 
 
 def _model_sequential(table, plans, scores_of, nt):
-    """NumPy model of mcd_stream_push + mcd_stream_frame_scores, tick by tick, on the frame-score ring."""
+    """NumPy model of one mcd_stream_push_group + mcd_stream_frame_scores_group pair per tick (each tick a group of one), on the
+    frame-score ring."""
     L, T = table.ring_len, table.seg_len
     fs = np.full((table.max_tracks, nt, L), 7.0, np.float32)       # (stale cells: pushes must zero what they use)
     finals = []
@@ -200,6 +202,38 @@ def test_fixture_replay_in_calls_of_k_ticks(k, ring_len, n_groups):
         a, b = table.close(done), seq.close(done)            # closes at the call boundaries
         assert a.keys == b.keys and np.array_equal(a.win, b.win) and table.same_state(seq)
     assert n_win == 283 and len(table) == 0
+
+
+def test_a_one_plan_group_is_the_group_pack_ticks_returns_for_the_tick():
+    """PoseStream.push plans its tick on the table itself and wraps the plan with _group(0, [plan], ...), without pack_ticks' copy
+    of the table: for a tick that emits, one that does not and an empty one, on a table with a history, that is the single group
+    pack_ticks returns -- desc, win, offsets, closed."""
+    table = TrackTable(max_tracks=7, seg_len=SEG_LEN, ring_len=SEG_LEN + 3, max_idle=2)
+    for keys, fids in _interleaving(100)[:9]:
+        table.push(keys, fids)
+    open_keys = list(table.slot_of)
+    emitting = [k for k in open_keys if table.rows[table.slot_of[k]] >= SEG_LEN - 1]
+    assert emitting and len(table) < 7
+    cases = {"emits": (open_keys, [40] * len(open_keys)), "no window": ([(3, 1, 50), (3, 1, 51)], [40, 40]), "empty": ([], [])}
+    n_win = {}
+    for name, (keys, fids) in cases.items():
+        before = table.copy()
+        plan = table.copy().push(keys, fids)
+        g = _group(0, [plan], NT, SEG_LEN)
+        groups, planned = pack_ticks(table, [(keys, fids)], NT)
+        assert table.same_state(before) and len(groups) == 1 and groups[0].first_tick == g.first_tick == 0
+        p = groups[0]
+        _same_plan(p.plans[0], plan)
+        for x, y in ((g.desc, p.desc), (g.win, p.win), (g.offsets, p.offsets), (g.closed.win, p.closed.win), (g.closed.frames, p.closed.frames)):
+            assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), name
+        assert g.closed.keys == p.closed.keys and g.closed.slots == p.closed.slots and g.clip is None and p.clip is None
+        assert g.desc.shape == (len(keys), 4) and g.win.shape == (plan.n_emit, 5) and g.offsets.tolist() == [0, plan.n_emit]
+        _check_descriptors(g, NT, SEG_LEN)
+        # the single tick as the entries see it: pos0 = j, ne = n_emit, w = j
+        assert g.desc[:, 2].tolist() == plan.desc[:, 2].tolist() and (g.desc[:, 3] == plan.n_emit).all()
+        assert sorted(g.win[:, 2].tolist()) == list(range(plan.n_emit)) and np.array_equal(g.win[:, 2], g.win[:, 4])
+        n_win[name] = plan.n_emit
+    assert n_win["emits"] == len(emitting) and n_win["no window"] == 0 and n_win["empty"] == 0
 
 
 def test_a_rejected_call_names_the_tick_and_leaves_the_table_as_it_was():

@@ -13,7 +13,8 @@ after its last row.  The window scores, put back into dataset order, go through 
 printed.  --synthetic-tracks N: N tracks that all receive a row on every tick (no AUC) -- the load of N tracked people.
 
 Timing (host clock around work that ends in a device synchronise, one warm-up replay, then --reps replays):
-  tick      PoseStream.push of one tick: host table + one H2D copy + mcd_stream_push + the scoring call + mcd_stream_frame_scores
+  tick      PoseStream.push of one tick (a launch group of one): host table + one H2D copy + mcd_stream_push_group + the scoring
+            call + mcd_stream_frame_scores_group
   baseline  ONE score_fused call (a YAML with diffusion_on_latent: true: ONE LatentScorer.score call) on a pre-built WindowBatch of the tick's window count over a trajectory buffer already on the
             device (what a caller of the dataset path would pay for the same windows if the buffer and the window list cost
             nothing), timed the same way in the same process, alternating with the stream replay.
