@@ -51,9 +51,21 @@ def main():
                     "is missing (otherwise a missing checkpoint is an error)")
     ap.add_argument("--dist-backend", default="nccl", help="'nccl' (= RCCL over xGMI) or 'gloo' (tests with several ranks on one GPU)")
     ap.add_argument("--dump-scores", type=str, default=None, help="rank 0 writes the gathered window scores + AUC to this .npz")
+    ap.add_argument("--joint-scores", type=str, default=None, metavar="OUT.npz",
+                    help="pose model, one process: also write, per (scene, clip, person) row, the (n_frames, 17) per-joint frame "
+                         "scores -- the scatter-max of the windows' error maps (which joints and forecast frames a score comes "
+                         "from), averaged over the transforms -- with the row table and the joint names")
     cli = ap.parse_args()
     args = load_config(cli.config)
     model_cls = model_class(args)
+    if cli.joint_scores:
+        if model_cls is not MoCoDAD:
+            raise SystemExit("eval_MoCoDAD.py: --joint-scores needs the pose model (a latent has no joints)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("eval_MoCoDAD.py: --joint-scores runs in one process (the maps are not gathered across ranks)")
+        if getattr(args, "aggregation_strategy", "best") in ("all", "random") or "random" in str(args.conditioning_strategy):
+            raise SystemExit("eval_MoCoDAD.py: --joint-scores needs one map per window with the same forecast frames under every "
+                             "transform: not aggregation_strategy all / random, not the random_imp strategy")
     if cli.device_masks:
         args.random_imp_draw = "device"
     if not cli.synthetic:
@@ -132,9 +144,16 @@ def main():
     with torch.no_grad():
         batches = tw.batches(args.batch_size, shard.lo, shard.hi) if tw is not None else \
             synthetic.batches((data, trans, meta, frames), args.batch_size, shard.lo, shard.hi)
+        maps, map_frames = [], []
         for i, batch in enumerate(batches):
             model._calls = shard.lo + i * args.batch_size     # global window id keys the noise stream
-            model.test_step(batch, i)
+            if cli.joint_scores:      # test_step with the error maps of the batch's windows beside its output
+                out = model.forward(batch, return_maps=True)
+                model._test_output_list.append(out[:-2])
+                maps.append(out[-2])
+                map_frames.append(torch.gather(batch[3].to(dev).long(), 1, out[-1]))      # frame ids of the map rows
+            else:
+                model.test_step(batch, i)
     ev1.record()                             # (no synchronisation here: the epoch end's host work runs under the queued batches)
     auc = model.on_test_epoch_end()          # gather of the scores + frame-score assembly (device) + roc_auc_score (host)
     torch.cuda.synchronize()
@@ -147,6 +166,16 @@ def main():
         if cli.dump_scores:
             import numpy as np
             np.savez(cli.dump_scores, scores=model.last_scores, auc=np.float64(auc))
+        if cli.joint_scores:
+            import numpy as np
+            from mocodad_amd._lib import JOINT_NAMES
+            from mocodad_amd.utils.eval_utils import joint_score_rows
+            gts, _ = model._gt_and_masks()
+            js, rows = joint_score_rows(torch.cat(maps), trans.numpy(), meta.numpy(), torch.cat(map_frames).cpu().numpy(), gts,
+                                        args.num_transform, model.scorer().joint_scatter_max)
+            np.savez(cli.joint_scores, joint_scores=js, rows=rows, row_columns=np.asarray(["scene", "clip", "person"]),
+                     joint_names=np.asarray(JOINT_NAMES))
+            print(f"joint scores: {js.shape[0]} (scene, clip, person) rows x {js.shape[1]} frames x {js.shape[2]} joints -> {cli.joint_scores}")
     if use_dist:
         dist.destroy_process_group()
 

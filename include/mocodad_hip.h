@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCD_ABI_VERSION 14
+#define MCD_ABI_VERSION 15
 
 enum {
     MCD_OK = 0,
@@ -268,11 +268,44 @@ int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n
                        const float* loss_all, const float* pose_all, const float* data, const mcd_window_view_t* view,
                        float* loss_agg, float* pose_agg, void* stream);
 
+/* Error maps (ABI version 15): WHERE a window's score comes from -- which joints, which forecast frames.  Replaces what a caller
+ * would otherwise redo in PyTorch from pose_out: the per-element loss of mocodad.py:484 before its mean over C*Tx*V, with the
+ * sample selection, tie rules and NaN behaviour of _aggregation_strategy (mocodad.py:454-520) as mcd_aggregate implements them.
+ * Pose model only (a latent has no joints); num_coords must be 2 and n_joints 17, the layout the window loader reads.
+ *   E[b,s,t,v] = (1/C) sum_c loss_elem(pose_all[b,s,c,t,v], x[b,c,t,v])       mean_{t,v} E[b,s] = loss_all[b,s] up to rounding
+ * x = the ground-truth corrupt frame t of window b, read through `view` with the affine transform applied -- by the device function
+ * the trajectory kernels load it with, so its bits are the ones the loss was computed on.  With view->cond_mask the corrupt frames of
+ * window b are the clear bits of its mask in ascending order (cfg->corrupt_idx is ignored), else cfg->corrupt_idx.
+ * maps_out (B,Tx,V) = M with mean_{t,v} M[b] = loss_agg[b] up to rounding:
+ *   BEST / WORST   M[b] = E[b,s*], s* the sample aggregate_kernel selects (strict comparisons from 1e10 / -1 on the loss_all bits, the
+ *                  first of equal samples stays); no sample selected (all NaN): a NaN map
+ *   MEAN           the sum over s, in sample order, of E[b,s], divided by S
+ *   MEDIAN         E[b,s_(r)], r = (S-1)/2, s_(r) the sample of rank r by (loss, sample index)
+ *   QUANTILE       E_lo + wgt (E_hi - E_lo) in torch.lerp's two-sided form, lo / hi / wgt as for loss_agg
+ *                  (MEDIAN / QUANTILE with a NaN among the window's S losses: a NaN map, as loss_agg is NaN)
+ *   MEAN_POSE / MEDIAN_POSE   (1/C) sum_c loss_elem(p[b,c,t,v], x), p = the pose_agg of mcd_aggregate bit for bit (same device
+ *                  functions, same order); loss_all is not read and may be NULL
+ *   ALL            maps_out (B,S,Tx,V) = E itself; loss_all is not read and may be NULL
+ * Selection is decided on the loss_all bits alone.  Unlike mcd_aggregate_view, a view with base != NULL is accepted: the dataset
+ * and stream paths score through views.  One wave per window, any n_samples >= 1, one launch.  Argument errors are MCD_EINVAL before
+ * any device call (with a mask: n_cond + n_corrupt must be seg_len <= 32, the bit count the mask carries); n_windows == 0 is MCD_OK
+ * and launches nothing. */
+int mcd_error_maps(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
+                   const float* loss_all, const float* pose_all, const float* data, const mcd_window_view_t* view,
+                   float* maps_out, void* stream);
+
 /* Frame-score assembly that follows the path (mocodad.py:386-401 + eval_utils.py:27-34): scatter-max of
  * window scores to their frames.  scores (N,), frames (N,seg_len) 1-based int32, row (N,) int32 = output
  * row (one per (transform, clip, person)), out (n_rows, n_frames) pre-zeroed by the callee. */
 int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* row, int64_t n, int32_t seg_len,
                     int32_t n_rows, int32_t n_frames, float* out, void* stream);
+
+/* The per-joint sibling of mcd_scatter_max (V = 17): maps (N,Tx,V) f32 (mcd_error_maps), frames (N,Tx) 1-based int32 = the frame id of each
+ * map row, row (N,) int32 -> out (n_rows, n_frames, V), pre-zeroed by the callee; out[row, f, v] = the maximum of max(map, 0) (a NaN
+ * adds 0) over the windows that forecast frame f.  Frames outside [1, n_frames] and rows outside [0, n_rows) are ignored; a cell no
+ * window forecasts stays 0 -- the convention of the frame scores (for a tail forecast the first n_cond rows of a track stay 0). */
+int mcd_joint_scatter_max(const float* maps, const int32_t* frames, const int32_t* row, int64_t n, int32_t n_corrupt,
+                          int32_t n_rows, int32_t n_frames, float* out, void* stream);
 
 /* Replaces: Trajectory._from_image_to_centre_bounding_box + compute_bounding_box (utils/data.py:11-43,165-186)
  * and scale_trajectories_robust (utils/data.py:350-359).  raw (n_frames, 34) f32 = the CSV columns 1..34
@@ -347,6 +380,30 @@ int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scor
  * f32 = the cells of the still-pending rows r_last - seg_len + 2 .. r_last.  (Tracks of fewer than seg_len rows have no window,
  * hence no frame score -- the dataset path drops them, utils/preprocessing.py:4-10 -- and are not passed here.) */
 int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream);
+
+/* Per-joint frame scores of a live stream (ABI version 15): a second CALLER-owned ring beside mcd_stream_state_t, which -- like the
+ * three entries above -- stays as it is.
+ *   joint_scores  (n_slots, num_transform, ring_len, 17) f32: cell (r % ring_len, v) = running maximum, over the windows that
+ *                 FORECAST row r, of max(map value, 0) at joint v.
+ * Cell rules (nothing here depends on the push kernel): a cell is initialised by the window that ENDS at its row -- with that window's
+ * map value if it forecasts the row, else 0 -- and the first window of a track (r_last = seg_len - 1) initialises all seg_len cells;
+ * so a reused slot and a wrapped ring start clean.  Every older row a window forecasts takes the maximum.  The cell of the window's
+ * oldest row is then final.  The finals equal mcd_joint_scatter_max over the same track's windows bit for bit. */
+typedef struct {
+    float* joint_scores;
+} mcd_stream_joint_state_t;
+
+/* maps (num_transform * n_windows, n_corrupt, 17) f32 in the order of base_out (mcd_error_maps on the group's windows); win
+ * (n_windows, 5) the SAME sorted table mcd_stream_frame_scores_group takes; cfg gives the forecast rows: seg_len (must equal the
+ * state's), n_corrupt and corrupt_idx (ascending positions inside the window; n_cond + n_corrupt = seg_len).  One thread per (track,
+ * transform, joint) walks the track's windows in row order with plain loads and stores.
+ * final_out (n_windows, num_transform, 17) f32 in (tick, j) order. */
+int mcd_stream_joint_scores_group(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, const float* maps,
+                                  const int32_t* win, int32_t n_windows, const mcd_score_cfg_t* cfg, float* final_out, void* stream);
+
+/* Tracks being closed, as for mcd_stream_flush: win (n, 2) = [slot, r_last] -> out (n, seg_len - 1, num_transform, 17) f32. */
+int mcd_stream_joint_flush(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, const int32_t* win, int32_t n,
+                           float* out, void* stream);
 
 /* Online clip scores of a live stream: the last stage of post_processing -- the person aggregation
  * mean_p s + (max_p log1p s - min_p log1p s) (mocodad.py:399-401), score_process = shift + gaussian_filter1d (eval_utils.py:100-106)

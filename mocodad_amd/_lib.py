@@ -15,7 +15,10 @@ COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
 LATENT_OPT = {"split_encode": 0}     # MCD_LATENT_OPT_*
-ABI_VERSION = 14
+# the 17 joints of a pose row, in the trajectory CSVs' order (COCO keypoints): the joint axis of the error maps
+JOINT_NAMES = ("nose", "left_eye", "right_eye", "left_ear", "right_ear", "left_shoulder", "right_shoulder", "left_elbow", "right_elbow",
+               "left_wrist", "right_wrist", "left_hip", "right_hip", "left_knee", "right_knee", "left_ankle", "right_ankle")
+ABI_VERSION = 15
 
 
 class Tensor(C.Structure):
@@ -55,6 +58,10 @@ class StreamState(C.Structure):
                 ("seg_len", C.c_int32), ("num_transform", C.c_int32)]
 
 
+class StreamJointState(C.Structure):
+    _fields_ = [("joint_scores", C.c_void_p)]
+
+
 class ClipState(C.Structure):
     _fields_ = [("sum", C.c_void_p), ("lmax", C.c_void_p), ("lmin", C.c_void_p), ("n", C.c_void_p), ("n_clips", C.c_int32),
                 ("clip_ring_len", C.c_int32), ("num_transform", C.c_int32)]
@@ -85,6 +92,10 @@ _SIGS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_aggregate_view": (C.c_int, [C.POINTER(ScoreCfg), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(WindowView), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_error_maps": (C.c_int, [C.POINTER(ScoreCfg), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(WindowView), C.c_void_p, C.c_void_p]),
+    "mcd_joint_scatter_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p]),
     "mcd_random_imp_masks": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_scatter_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_void_p]),
@@ -97,6 +108,10 @@ _SIGS = {
     "mcd_stream_push_group": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_stream_frame_scores_group": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mcd_stream_joint_scores_group": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamJointState), C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.POINTER(ScoreCfg), C.c_void_p, C.c_void_p]),
+    "mcd_stream_joint_flush": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamJointState), C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p]),
     "mcd_stream_clip_update": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_int32, C.c_void_p]),
     "mcd_stream_clip_emit": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,

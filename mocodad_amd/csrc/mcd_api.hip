@@ -581,6 +581,61 @@ int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n
     return launch_aggregate(P, (hipStream_t)stream);
 }
 
+int mcd_error_maps(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
+                   const float* loss_all, const float* pose_all, const float* data, const mcd_window_view_t* view,
+                   float* maps_out, void* stream) {
+    // every argument check comes before the first device call
+    if (!cfg) return fail(MCD_EINVAL, "null argument");
+    if (cfg->n_windows < 0) return fail(MCD_EINVAL, "n_windows must be >= 0");
+    if (num_coords != C0 || n_joints != 17) return fail(MCD_EINVAL, "mcd_error_maps: num_coords must be 2 and n_joints 17 (the window layout)");
+    if (cfg->n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
+    if (int rc = check_aggregation(strategy, quantile, AGGR_ANY | 1u << MCD_AGGR_ALL, "unknown aggregation strategy")) return rc;
+    if (cfg->seg_len < 1 || cfg->seg_len > MCD_MAX_FRAMES || cfg->n_corrupt < 1 || cfg->n_corrupt > cfg->seg_len)
+        return fail(MCD_EINVAL, "need 1 <= n_corrupt <= seg_len <= 32");
+    const int32_t* win_mask = view ? view->cond_mask : nullptr;
+    if (win_mask) {
+        if (cfg->n_cond + cfg->n_corrupt != cfg->seg_len)
+            return fail(MCD_EINVAL, "cond_mask: the mask carries n_cond = seg_len - n_corrupt set bits (n_cond + n_corrupt != seg_len)");
+    } else {
+        for (int k = 0; k < cfg->n_corrupt; ++k)
+            if (cfg->corrupt_idx[k] < 0 || cfg->corrupt_idx[k] >= cfg->seg_len) return fail(MCD_EINVAL, "corrupt_idx outside [0, seg_len)");
+    }
+    const bool needs_loss = strategy != MCD_AGGR_ALL && strategy != MCD_AGGR_MEAN_POSE && strategy != MCD_AGGR_MEDIAN_POSE && strategy != MCD_AGGR_MEAN;
+    if (!pose_all || !data || !maps_out || (needs_loss && !loss_all)) return fail(MCD_EINVAL, "null argument");
+    if ((long long)cfg->n_windows * cfg->n_samples > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x n_samples exceeds 2^31 - 1");
+    MapParams P;
+    memset(&P, 0, sizeof(P));
+    if (int rc = window_view(data, view, cfg->seg_len, P.dv)) return rc;
+    if (cfg->n_windows == 0) return MCD_OK;
+    P.loss_all = loss_all; P.pose_all = pose_all; P.maps = maps_out; P.win_mask = win_mask;
+    P.B = cfg->n_windows; P.S = cfg->n_samples; P.Tx = cfg->n_corrupt; P.seg_len = cfg->seg_len;
+    P.strategy = strategy; P.loss_fn = cfg->loss_fn; P.q = quantile;
+    for (int t = 0; t < cfg->n_corrupt; ++t) P.corrupt_idx[t] = cfg->corrupt_idx[t];
+    P.in_lds = P.S <= AGG_LDS_MAX;
+    const size_t lds = (size_t)(4 + (P.in_lds ? P.S : 0)) * sizeof(float);
+    hipLaunchKernelGGL(error_maps_kernel, dim3(P.B < 65536 ? P.B : 65536), dim3(64), lds, (hipStream_t)stream, P);      // one wave per window
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_joint_scatter_max(const float* maps, const int32_t* frames, const int32_t* row, int64_t n, int32_t n_corrupt,
+                          int32_t n_rows, int32_t n_frames, float* out, void* stream) {
+    if (!out) return fail(MCD_EINVAL, "null argument");
+    if (n < 0 || n_corrupt < 1 || n_corrupt > MCD_MAX_FRAMES || n_rows < 0 || n_frames < 0)
+        return fail(MCD_EINVAL, "need n, n_rows, n_frames >= 0 and 1 <= n_corrupt <= 32");
+    if (n > 0 && (!maps || !frames || !row)) return fail(MCD_EINVAL, "null argument");
+    const long long total = (long long)n * n_corrupt * 17;
+    if ((total + 255) / 256 > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    if ((size_t)n_rows * n_frames == 0) return MCD_OK;
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_rows * n_frames * 17 * sizeof(float), st));
+    if (n == 0) return MCD_OK;
+    hipLaunchKernelGGL(joint_scatter_max_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, maps, frames, row,
+                       (long long)n, n_corrupt, n_rows, n_frames, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* row, int64_t n, int32_t seg_len,
                     int32_t n_rows, int32_t n_frames, float* out, void* stream) {
     if (!scores || !frames || !row || !out) return fail(MCD_EINVAL, "null argument");
@@ -666,6 +721,57 @@ int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scor
     if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
     hipLaunchKernelGGL(stream_frame_scores_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
                        scores, win, n_windows, (int)total, final_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+// the joint ring beside a stream state: (n_slots, num_transform, ring_len, 17) floats
+static int stream_joint_params(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, StreamParams* P) {
+    if (int rc = stream_params(s, P)) return rc;
+    if (!js || !js->joint_scores) return fail(MCD_EINVAL, "null stream joint state");
+    if ((int64_t)s->n_slots * s->num_transform * s->ring_len > 0x7fffffffll / 17)
+        return fail(MCD_EUNSUPPORTED, "stream joint ring of more than 2^31 elements");
+    return MCD_OK;
+}
+
+int mcd_stream_joint_scores_group(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, const float* maps,
+                                  const int32_t* win, int32_t n_windows, const mcd_score_cfg_t* cfg, float* final_out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_joint_params(s, js, &P)) return rc;
+    if (!cfg) return fail(MCD_EINVAL, "null argument");
+    if (cfg->seg_len != P.seg_len) return fail(MCD_EINVAL, "cfg->seg_len is not the stream state's seg_len");
+    if (int rc = check_frame_partition(cfg)) return rc;
+    StreamJointParams J;
+    memset(&J, 0, sizeof(J));
+    J.js = js->joint_scores; J.Tx = cfg->n_corrupt;
+    for (int k = 0; k < MCD_MAX_FRAMES; ++k) J.tx_of[k] = -1;
+    for (int k = 0; k < cfg->n_corrupt; ++k) {
+        const int t = cfg->corrupt_idx[k];
+        if (t < 0 || t >= cfg->seg_len || J.tx_of[t] >= 0) return fail(MCD_EINVAL, "bad corrupt_idx");
+        J.tx_of[t] = k;
+    }
+    if (n_windows < 0 || n_windows > stream_group_rows(s)) return fail(MCD_EINVAL, "need 0 <= n_windows <= n_slots * (ring_len - seg_len + 1)");
+    if (n_windows == 0) return MCD_OK;
+    if (!maps || !win || !final_out) return fail(MCD_EINVAL, "null argument");
+    const long long n_win = (long long)n_windows * P.nt, total = n_win * 17;
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    hipLaunchKernelGGL(stream_joint_scores_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, J,
+                       maps, win, n_windows, (int)n_win, final_out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_joint_flush(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, const int32_t* win, int32_t n,
+                           float* out, void* stream) {
+    StreamParams P;
+    if (int rc = stream_joint_params(s, js, &P)) return rc;
+    if (n < 0 || n > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
+    const long long total = (long long)n * (P.seg_len - 1) * P.nt * 17;
+    if (total == 0) return MCD_OK;
+    if (!win || !out) return fail(MCD_EINVAL, "null argument");
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
+    hipLaunchKernelGGL(stream_joint_flush_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
+                       js->joint_scores, win, n, out);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }

@@ -1,16 +1,18 @@
 // mcd_post_kernel.hpp — the device code of mcd_api.hip's own launches, everything around the trajectory kernels:
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
-//   scatter_max / frame_scatter / frame_scores kernels   post_processing                       models/mocodad.py:362-425
+//   error_maps_kernel           the per-element loss of :484 before its mean, under the same sample selection (mcd_error_maps)
+//   scatter_max / joint_scatter_max / frame_scatter / frame_scores kernels   post_processing    models/mocodad.py:362-425
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
 //   stream_push_group / stream_frame_scores_group / stream_flush kernels   the same loader step + sliding windows + scatter-max,
 //                               one group of ticks at a time (a single tick is a group of one) on device rings
 //                                                               utils/preprocessing.py:14-86, models/mocodad.py:392-393
 //   stream_clip_update / stream_clip_emit kernels   online per-clip frame scores: the person aggregate, shift and Gaussian of
 //                               post_processing, incrementally on a per-clip ring     models/mocodad.py:399-424, utils/eval_utils.py:100-106
+//   stream_joint_scores_group / stream_joint_flush kernels   the per-joint sibling of the stream's score ring, fed by the error maps
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
-// with the parameter blocks the host fills (AggrParams, StreamParams, FrameParams, ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines
+// with the parameter blocks the host fills (AggrParams, MapParams, StreamParams, StreamJointParams, FrameParams, ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines
 // API_THREADS and says `using namespace mcd`), in front of its host code; the kernels keep the order, the linkage and the
 // visibility they had inside that file, so its device object does not change.
 #pragma once
@@ -49,7 +51,10 @@ __device__ __forceinline__ SampleVals stage_samples(const float* src, long long 
 // (No sort, no per-thread array: O(S^2 / 64) broadcast reads per lane.)  All lanes return the same pair.
 // A NaN among the samples (a diverged chain) breaks the permutation -- every NaN ranks 0 and the rank asked for may have no
 // writer -- and torch.median / torch.quantile return NaN then (mocodad.py:489-492,513-516): so does this, for both values.
-__device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int lane, int r0, int r1, float* slot, float& v0, float& v1) {
+// sel (error_maps_kernel; null = not wanted, and the code is the one without it): the INDICES of the two samples land in
+// islot[0] / islot[1] beside the values and come back in sel[0] / sel[1], -1 for both under a NaN.
+__device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int lane, int r0, int r1, float* slot, float& v0, float& v1,
+                                                 int* islot = nullptr, int* sel = nullptr) {
     bool nan = false;
     for (int i = lane; i < S; i += 64) {
         const float x = X(i);
@@ -59,28 +64,38 @@ __device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int
             const float y = X(k);
             r += (y < x || (y == x && k < i)) ? 1 : 0;
         }
-        if (r == r0) slot[0] = x;
-        if (r == r1) slot[1] = x;
+        if (r == r0) { slot[0] = x; if (sel) islot[0] = i; }
+        if (r == r1) { slot[1] = x; if (sel) islot[1] = i; }
     }
     __syncthreads();
     const bool any_nan = __ballot(nan) != 0ull;        // (one 64-lane wave per workgroup: aggregate_kernel's launch bound)
     v0 = any_nan ? __builtin_nanf("") : slot[0];
     v1 = any_nan ? __builtin_nanf("") : slot[1];
+    if (sel) { sel[0] = any_nan ? -1 : islot[0]; sel[1] = any_nan ? -1 : islot[1]; }
     __syncthreads();
 }
 // torch.median: the lower middle value; torch.quantile: linear interpolation, torch.lerp's two-sided form
-__device__ __forceinline__ float wave_order_stat(const SampleVals& X, int S, int lane, int strategy, float q, float* slot) {
+// the interpolation of two order statistics a <= c (also applied per map cell by error_maps_kernel, where a, c are any two values)
+__device__ __forceinline__ float lerp_two_sided(float a, float c, float wgt) {
+    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
+}
+// islot / sel / wgt_out (error_maps_kernel; null = not wanted): the two samples' indices as wave_rank_select yields them (the median:
+// the same sample twice, weight 0) and the interpolation weight
+__device__ __forceinline__ float wave_order_stat(const SampleVals& X, int S, int lane, int strategy, float q, float* slot,
+                                                 int* islot = nullptr, int* sel = nullptr, float* wgt_out = nullptr) {
     float a, c;
     if (strategy == MCD_AGGR_MEDIAN) {
-        wave_rank_select(X, S, lane, (S - 1) / 2, (S - 1) / 2, slot, a, c);
+        wave_rank_select(X, S, lane, (S - 1) / 2, (S - 1) / 2, slot, a, c, islot, sel);
+        if (wgt_out) *wgt_out = 0.f;
         return a;
     }
     const float pos = fminf(fmaxf(q, 0.f), 1.f) * (float)(S - 1);      // (q is validated on the host; the clamp is a backstop)
     const int lo = (int)floorf(pos);
     const int hi = lo + 1 < S ? lo + 1 : S - 1;
     const float wgt = pos - (float)lo;
-    wave_rank_select(X, S, lane, lo, hi, slot, a, c);
-    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
+    wave_rank_select(X, S, lane, lo, hi, slot, a, c, islot, sel);
+    if (wgt_out) *wgt_out = wgt;
+    return lerp_two_sided(a, c, wgt);
 }
 
 // Sums and best / worst run in sample order on wave-uniform values: bit-identical to the sequential loops of
@@ -136,6 +151,119 @@ __global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams P) {
             if (lane == 0) P.loss_agg[b] = acc / (float)per;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Error maps (mcd_error_maps): which joints and forecast frames a window's score comes from.  One 64-lane wave per window like
+// aggregate_kernel, whose selection it repeats on the same loss_all bits with the same functions: E[b,s,t,v] = (1/C) sum_c
+// loss_elem(pose, gt), the ground truth loaded by load_coord -- the trajectory kernels' loader, so the bits the loss saw.
+// The window's sample(s) are chosen by the wave, then the lanes take the Tx * V cells.
+// ------------------------------------------------------------------------------------------------
+struct MapParams {
+    const float* loss_all; const float* pose_all; float* maps;
+    DataView dv;
+    const int* win_mask;      // as AggrParams::win_mask
+    int B, S, Tx, seg_len, strategy, loss_fn, in_lds;
+    float q;
+    int corrupt_idx[MCD_MAX_FRAMES];
+};
+// data frame of the window's tx-th corrupt frame (the max: as in aggregate_kernel, a bad mask still reads inside the window)
+__device__ __forceinline__ int map_frame(const MapParams& P, int b, int tx) {
+    return P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
+}
+// E of one cell for the pose at `p` (element (c, cell) at p[c * cells + cell]) against the ground truth (g0, g1)
+__device__ __forceinline__ float map_cell(const float* __restrict__ p, int cells, int cell, float g0, float g1, int loss_fn) {
+    return (loss_elem(p[cell], g0, loss_fn) + loss_elem(p[cells + cell], g1, loss_fn)) / (float)C0;
+}
+
+__global__ __launch_bounds__(64) void error_maps_kernel(const MapParams P) {
+    extern __shared__ float map_lds[];
+    float* slot = map_lds;                                    // [2] selected order statistics
+    int* islot = reinterpret_cast<int*>(map_lds + 2);         // [2] their sample indices
+    float* vals = map_lds + 4;                                // [S] staged sample values (in_lds)
+    const int lane = threadIdx.x, S = P.S, cells = P.Tx * 17, per = C0 * cells;
+    const bool in_lds = P.in_lds != 0;
+    const float nanv = __builtin_nanf("");
+    for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
+        const float* pose_b = P.pose_all + (size_t)b * S * per;
+        if (P.strategy == MCD_AGGR_MEAN_POSE || P.strategy == MCD_AGGR_MEDIAN_POSE) {
+            // per element over the S poses exactly as aggregate_kernel forms pose_agg (wave-uniform values), cell by cell
+            float* out = P.maps + (size_t)b * cells;
+            for (int cell = 0; cell < cells; ++cell) {
+                const int tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
+                float acc = 0.f;
+                for (int c = 0; c < C0; ++c) {
+                    const SampleVals X = stage_samples(pose_b + c * cells + cell, per, S, vals, in_lds, lane);
+                    float val;
+                    if (P.strategy == MCD_AGGR_MEAN_POSE) {
+                        float sum = 0.f;
+                        for (int k = 0; k < S; ++k) sum += X(k);
+                        val = sum / (float)S;
+                    } else {
+                        val = wave_order_stat(X, S, lane, MCD_AGGR_MEDIAN, 0.f, slot);
+                    }
+                    acc += loss_elem(val, load_coord(P.dv, b, c, frame, v, P.seg_len), P.loss_fn);
+                }
+                if (lane == 0) out[cell] = acc / (float)C0;
+            }
+            continue;
+        }
+        if (P.strategy == MCD_AGGR_ALL) {
+            float* out = P.maps + (size_t)b * S * cells;
+            for (int u = lane; u < S * cells; u += 64) {
+                const int s = u / cells, cell = u - s * cells, tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
+                out[u] = map_cell(pose_b + (size_t)s * per, cells, cell, load_coord(P.dv, b, 0, frame, v, P.seg_len),
+                                  load_coord(P.dv, b, 1, frame, v, P.seg_len), P.loss_fn);
+            }
+            continue;
+        }
+        // loss-based strategies: the sample(s), decided on the loss_all bits alone
+        int sel[2] = {-1, -1};
+        float wgt = 0.f;
+        if (P.strategy != MCD_AGGR_MEAN) {
+            const SampleVals X = stage_samples(P.loss_all + (size_t)b * S, 1, S, vals, in_lds, lane);
+            if (P.strategy == MCD_AGGR_BEST || P.strategy == MCD_AGGR_WORST) {
+                const bool best = P.strategy == MCD_AGGR_BEST;
+                float cur = best ? 1e10f : -1.f;       // aggregate_kernel's loop: strict comparisons, the first of equal samples stays
+                for (int k = 0; k < S; ++k) {
+                    const float y = X(k);
+                    if (best ? (y < cur) : (y > cur)) { cur = y; sel[0] = k; }
+                }
+                sel[1] = sel[0];
+            } else {
+                (void)wave_order_stat(X, S, lane, P.strategy, P.q, slot, islot, sel, &wgt);
+            }
+        }
+        float* out = P.maps + (size_t)b * cells;
+        for (int cell = lane; cell < cells; cell += 64) {
+            const int tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
+            const float g0 = load_coord(P.dv, b, 0, frame, v, P.seg_len), g1 = load_coord(P.dv, b, 1, frame, v, P.seg_len);
+            float m;
+            if (P.strategy == MCD_AGGR_MEAN) {
+                float sum = 0.f;
+                for (int k = 0; k < S; ++k) sum += map_cell(pose_b + (size_t)k * per, cells, cell, g0, g1, P.loss_fn);
+                m = sum / (float)S;
+            } else if (sel[0] < 0 || sel[1] < 0) {
+                m = nanv;
+            } else {
+                m = map_cell(pose_b + (size_t)sel[0] * per, cells, cell, g0, g1, P.loss_fn);
+                if (P.strategy == MCD_AGGR_QUANTILE && sel[1] != sel[0])
+                    m = lerp_two_sided(m, map_cell(pose_b + (size_t)sel[1] * per, cells, cell, g0, g1, P.loss_fn), wgt);
+            }
+            out[cell] = m;
+        }
+    }
+}
+
+// per-joint scatter-max (mcd_joint_scatter_max): one thread per (window i, corrupt frame tx, joint v); maps >= 0 after the clamp
+__global__ void joint_scatter_max_kernel(const float* __restrict__ maps, const int* __restrict__ frames, const int* __restrict__ row,
+                                         long long n, int Tx, int n_rows, int n_frames, float* __restrict__ out) {
+    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n * Tx * 17) return;
+    const long long it = u / 17, i = it / Tx;
+    const int v = (int)(u - it * 17), f = frames[it] - 1, r = row[i];
+    if (f < 0 || f >= n_frames || r < 0 || r >= n_rows) return;
+    atomicMax(reinterpret_cast<int*>(out + ((size_t)r * n_frames + f) * 17 + v), __float_as_int(fmaxf(maps[u], 0.f)));
 }
 
 
@@ -295,6 +423,57 @@ __global__ __launch_bounds__(256) void stream_frame_scores_group_kernel(StreamPa
             if (k == 0) final_out[(size_t)w * S.nt + t] = m;
         }
     }
+}
+
+// Per-joint frame scores of a stream (mcd_stream_joint_state_t): ring (n_slots, nt, L, 17).  tx_of[k] = the index among the corrupt
+// frames of window row k, or -1 (a condition frame: the window forecasts nothing there).
+struct StreamJointParams {
+    float* js;
+    int tx_of[MCD_MAX_FRAMES];
+    int Tx;
+};
+// The walk of stream_frame_scores_group_kernel, per joint: one thread per (track's FIRST window, transform, joint).  The window
+// ending at row r_last INITIALISES that row's cell (its value there if it forecasts the row, else 0) -- the track's first window
+// (r_last = seg_len - 1) all seg_len cells, which is what lets a reused slot or a wrapped ring start clean without the push kernel
+// -- and takes the maximum into the older rows it forecasts; its oldest row is then final.  max(value, 0) as joint_scatter_max_kernel.
+__global__ __launch_bounds__(256) void stream_joint_scores_group_kernel(StreamParams S, StreamJointParams J, const float* __restrict__ maps,
+                                                                        const int* __restrict__ win, int n, int n_win,
+                                                                        float* __restrict__ final_out) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n * S.nt * 17) return;
+    const int v = u % 17, qt = u / 17, q0 = qt / S.nt, t = qt - q0 * S.nt;
+    const int slot = win[5 * q0];
+    if (slot < 0 || slot >= S.n_slots) return;
+    if (q0 > 0 && win[5 * (q0 - 1)] == slot) return;           // not the track's first window: the thread of that one walks on
+    float* cells = J.js + ((size_t)slot * S.nt + t) * S.L * 17 + v;
+    for (int q = q0; q < n && win[5 * q] == slot; ++q) {
+        const int r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
+        const long long pos = (long long)pos0 + (long long)t * ne;
+        if (r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos >= n_win || w < 0 || w >= n) continue;
+        const float* m = maps + (size_t)pos * J.Tx * 17 + v;
+        const int first = r_last - S.seg_len + 1;
+        const bool init_all = first == 0;
+        for (int k = S.seg_len - 1; k >= 0; --k) {
+            float* c = cells + (size_t)((first + k) % S.L) * 17;
+            const int tx = J.tx_of[k];
+            const float val = tx >= 0 ? fmaxf(m[tx * 17], 0.f) : 0.f;
+            const float cur = (init_all || k == S.seg_len - 1) ? val : fmaxf(*c, val);
+            *c = cur;
+            if (k == 0) final_out[((size_t)w * S.nt + t) * 17 + v] = cur;
+        }
+    }
+}
+
+// one thread per (closed track i, pending row k, transform t, joint v), as stream_flush_kernel
+__global__ __launch_bounds__(256) void stream_joint_flush_kernel(StreamParams S, const float* __restrict__ js, const int* __restrict__ win,
+                                                                 int n, float* __restrict__ out) {
+    const int pend = S.seg_len - 1;
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n * pend * S.nt * 17) return;
+    const int v = u % 17, t = (u / 17) % S.nt, k = (u / (17 * S.nt)) % pend, i = u / (17 * S.nt * pend);
+    const int slot = win[2 * i], r_last = win[2 * i + 1];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
+    out[u] = js[(((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L) * 17 + v];
 }
 
 

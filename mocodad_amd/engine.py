@@ -110,6 +110,7 @@ class _Scorer:
         self._tables: Dict[int, torch.Tensor] = {}
         self._ws: Dict[int, torch.Tensor] = {}   # workspace, one per stream (launches on different streams may overlap, each
         #                                          needs its own)
+        self._map_bufs: Dict[tuple, torch.Tensor] = {}   # want_maps: poses / per-sample losses nobody asked for, per stream
 
     def _model_cfg(self, strategy: str, t_unet: int, t_cond: int, cond_channels, cond_unet: bool) -> "_lib.ModelCfg":
         cfg = _lib.ModelCfg()
@@ -267,26 +268,93 @@ class HipScorer(_Scorer):
 
     def score(self, data, *, n_samples: int, noise_steps: int, noise: Optional[torch.Tensor] = None,
               seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_poses: bool = False,
-              cond_mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+              cond_mask: Optional[torch.Tensor] = None, want_maps: bool = False):
         """data (B,C,T,V) tensor, or a mocodad_amd.data.windows.WindowBatch (windows read in place from trajectory
         buffers, test-time transform applied on load) -> (loss (B,S), poses (B,S,C,Tx,V) | None).
         cond_mask (random_imp only): (B,) int32, bit t set = frame t of the window conditions.
+        want_maps: a third result, the per-sample error maps E (B,S,Tx,V) (mcd_error_maps, MCD_AGGR_ALL): one more small launch
+        behind the scoring call, on the poses it wrote (into the scorer's own per-stream buffer unless want_poses).
         Asynchronous on the current stream."""
-        _, loss, poses = self._score(data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask,
-                                     aggregation=None, want_all=True, out=None)
-        return loss, poses
+        _, loss, poses, maps = self._score(data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask,
+                                           aggregation=None, want_all=True, out=None, want_maps=want_maps)
+        return (loss, poses, maps) if want_maps else (loss, poses)
 
     def score_fused(self, data, *, n_samples: int, noise_steps: int, aggregation: str = "best", noise: Optional[torch.Tensor] = None,
                     seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_all: bool = False, want_poses: bool = False,
-                    cond_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+                    cond_mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_maps: bool = False):
         """`score` + the loss-based aggregation over the samples ('best' | 'worst' | 'mean' | 'median' | 'quantile:q') in one
         call -- one kernel launch whenever the workgroups own whole windows (mcd_score_fused).
-        -> (aggregated loss (B,), loss (B,S) | None, poses | None).  out: optional preallocated (B,) result."""
-        return self._score(data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask,
-                           aggregation=aggregation, want_all=want_all, out=out)
+        -> (aggregated loss (B,), loss (B,S) | None, poses | None).  out: optional preallocated (B,) result.
+        want_maps: a fourth result, the error maps M (B,Tx,V) under the aggregation (mean_{t,v} M[b] = loss[b] up to rounding;
+        mcd_error_maps): the call then also writes the per-sample losses and the poses (into the scorer's own per-stream buffers
+        unless asked for) and one small launch follows it."""
+        r = self._score(data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask,
+                        aggregation=aggregation, want_all=want_all, out=out, want_maps=want_maps)
+        return r if want_maps else r[:3]
+
+    def _scratch(self, kind: str, numel: int) -> torch.Tensor:
+        """`numel` floats of the current stream's scratch buffer `kind` (the poses / per-sample losses a maps launch reads when the
+        caller did not ask for them): grown on demand, reused by the next call.  Call inside `torch.cuda.device(self.device)`."""
+        key = (kind, torch.cuda.current_stream().cuda_stream)
+        buf = self._map_bufs.get(key)
+        if buf is None or buf.numel() < numel:
+            buf = self._map_bufs[key] = torch.empty(max(numel, 1), device=self.device, dtype=torch.float32)
+        return buf[:numel]
+
+    def error_maps(self, data, loss_all: Optional[torch.Tensor], poses_all: torch.Tensor, strategy: str, *, loss_fn: str = "smooth_l1",
+                   cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcd_error_maps: which joints and forecast frames a window's score comes from.  data: the windows the poses were
+        scored on ((B,C,T,V) tensor or WindowBatch: the ground truth is read through the view, transform applied); loss_all (B,S)
+        (None for 'all', 'mean', 'mean_pose', 'median_pose', which do not read it); poses_all (B,S,C,Tx,V); strategy: 'all' |
+        'best' | 'worst' | 'mean' | 'median' | 'quantile:q' | 'mean_pose' | 'median_pose' -> M (B,Tx,V), for 'all' E (B,S,Tx,V).
+        cond_mask ('random_imp'): the batch's (B,) condition-frame bitmasks.  Asynchronous on the current stream."""
+        name, q = _aggregation_of(strategy, list(_lib.AGGR), f"Unknown aggregation strategy {strategy}")
+        if cond_mask is not None:
+            cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
+        data, view, B, keep = self._windows(data, cond_mask)
+        poses_all = _f32c(poses_all, self.device)
+        Tx = len(self.corrupt_idx)
+        if poses_all.dim() != 5 or poses_all.shape[0] != B or tuple(poses_all.shape[2:]) != (self.num_coords, Tx, self.n_joints):
+            raise ValueError(f"poses_all must have shape ({B}, S, {self.num_coords}, {Tx}, {self.n_joints}), got {tuple(poses_all.shape)}")
+        S = int(poses_all.shape[1])
+        if loss_all is not None:
+            loss_all = _f32c(loss_all, self.device)
+            if tuple(loss_all.shape) != (B, S):
+                raise ValueError(f"loss_all must have shape ({B}, {S}), got {tuple(loss_all.shape)}")
+        elif name not in ("all", "mean", "mean_pose", "median_pose"):
+            raise ValueError(f"the {name!r} maps select samples by their losses: loss_all is required")
+        with torch.cuda.device(self.device):
+            maps = self._maps_launch(data, view, B, S, name, q, loss_all, poses_all, loss_fn)
+        del keep
+        return maps
+
+    def _maps_launch(self, data, view, B, S, name, q, loss_all, poses_all, loss_fn) -> torch.Tensor:
+        Tx = len(self.corrupt_idx)
+        shape = (B, S, Tx, self.n_joints) if name == "all" else (B, Tx, self.n_joints)
+        maps = torch.empty(shape, device=self.device, dtype=torch.float32)
+        cfg = self._score_cfg(B, S, 2, loss_fn)
+        _lib.check(self.L.mcd_error_maps(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q), _ptr(loss_all),
+                                         _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None, _ptr(maps),
+                                         _stream()))
+        return maps
+
+    def joint_scatter_max(self, maps: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
+        """mcd_joint_scatter_max: maps (N,Tx,V), frames (N,Tx) 1-based frame id of each map row, row (N,) output row
+        -> (n_rows, n_frames, V): per joint the maximum over the windows forecasting the frame; 0 where none does."""
+        maps = _f32c(maps, self.device)
+        frames = frames.to(self.device, torch.int32).contiguous()
+        row = row.to(self.device, torch.int32).contiguous()
+        n = int(row.numel())
+        if maps.dim() != 3 or maps.shape[0] != n or maps.shape[2] != 17 or tuple(frames.shape) != (n, maps.shape[1]):
+            raise ValueError(f"need maps (N, Tx, 17), frames (N, Tx) and row (N,), got {tuple(maps.shape)}, {tuple(frames.shape)}, {tuple(row.shape)}")
+        out = torch.empty(int(n_rows), int(n_frames), 17, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_joint_scatter_max(_ptr(maps), _ptr(frames), _ptr(row), n, int(maps.shape[1]), int(n_rows), int(n_frames),
+                                                    _ptr(out), _stream()))
+        return out
 
     def _score(self, data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask, *, aggregation,
-               want_all, out):
+               want_all, out, want_maps=False):
         if (cond_mask is not None) != (self.strategy == "random_imp"):
             raise ValueError("cond_mask is required by, and only valid for, the random_imp strategy")
         if cond_mask is not None:
@@ -308,15 +376,30 @@ class HipScorer(_Scorer):
                                       f"score_fused aggregates losses (best, worst, mean, median, quantile:q), not {aggregation!r}")
             agg = _out_vector(out, B, self.device)
         need = int(self.L.mcd_score_workspace_bytes(self._h, C.byref(cfg)))
+        maps = None
         with torch.cuda.device(self.device):
+            # the maps launch reads the poses and (to select samples) the per-sample losses: the scoring call writes them into the
+            # scorer's own buffers where the caller did not ask for them
+            loss_w, poses_w = loss, poses
+            if want_maps and B:
+                if poses_w is None:
+                    poses_w = self._scratch("poses", B * S * self.num_coords * Tx * self.n_joints).view(B, S, self.num_coords, Tx, self.n_joints)
+                if loss_w is None:
+                    loss_w = self._scratch("loss", B * S).view(B, S)
             common = (self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None, _ptr(noise),
                       _seed64(seed), C.c_int64(first_window_id), _ptr(self.table(noise_steps)), _ptr(self._workspace(need)))
             if aggregation is None:
-                _lib.check(self.L.mcd_score_view(*common, _ptr(loss), _ptr(poses), _stream()))
+                _lib.check(self.L.mcd_score_view(*common, _ptr(loss_w), _ptr(poses_w), _stream()))
             else:
-                _lib.check(self.L.mcd_score_fused(*common, _lib.AGGR[name], C.c_float(q), _ptr(agg), _ptr(loss), _ptr(poses), _stream()))
+                _lib.check(self.L.mcd_score_fused(*common, _lib.AGGR[name], C.c_float(q), _ptr(agg), _ptr(loss_w), _ptr(poses_w), _stream()))
+            if want_maps:
+                mname, mq = ("all", 0.0) if aggregation is None else (name, q)
+                if B:
+                    maps = self._maps_launch(data, view, B, S, mname, mq, loss_w, poses_w, loss_fn)
+                else:
+                    maps = torch.empty((0, S, Tx, self.n_joints) if mname == "all" else (0, Tx, self.n_joints), device=self.device)
         del keep
-        return agg, loss, poses
+        return agg, loss, poses, maps
 
     # stage ids of mcd_layer_forward: (Cin, Vin, Cout, Vout)
     _STAGES = {0: (2, 17, 16, 17), 1: (16, 17, 32, 17), 2: (32, 17, 32, 17), 3: (32, 12, 64, 12), 4: (64, 12, 64, 12),
@@ -604,7 +687,7 @@ class StreamRings:
     from one stream."""
 
     def __init__(self, n_slots: int, seg_len: int, ring_len: int, num_transform: int, vid_res: Sequence[float], center=None,
-                 scale=None, *, device=None):
+                 scale=None, *, device=None, joint_scores: bool = False):
         self.L = _lib.lib()
         _need_gpu()
         self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -619,6 +702,31 @@ class StreamRings:
         self._state = _lib.StreamState(ring=self.ring.data_ptr(), frame_scores=self.frame_scores_ring.data_ptr(),
                                        n_slots=self.n_slots, ring_len=self.ring_len, seg_len=self.seg_len,
                                        num_transform=self.num_transform)
+        # joint_scores: the per-joint ring (mcd_stream_joint_state_t) beside the two above; without it nothing is allocated
+        self.joint_scores_ring, self._jstate = None, None
+        if joint_scores:
+            with torch.cuda.device(dev):
+                self.joint_scores_ring = torch.zeros(self.n_slots, self.num_transform, self.ring_len, 17, device=dev, dtype=torch.float32)
+            self._jstate = _lib.StreamJointState(joint_scores=self.joint_scores_ring.data_ptr())
+
+    def joint_scores_group(self, maps: torch.Tensor, win: torch.Tensor, n_windows: int, cfg: "_lib.ScoreCfg") -> torch.Tensor:
+        """mcd_stream_joint_scores_group: maps (num_transform * n_windows, Tx, 17) error maps of the group's windows in the order
+        of push_group's base, win as for frame_scores_group, cfg: the model's frame lists -> (n_windows, num_transform, 17) final
+        per-joint frame scores in (tick, j) order."""
+        with torch.cuda.device(self.device):
+            final = torch.empty(int(n_windows), self.num_transform, 17, device=self.device, dtype=torch.float32)
+            _lib.check(self.L.mcd_stream_joint_scores_group(C.byref(self._state), C.byref(self._jstate), _ptr(maps), _ptr(win),
+                                                            int(n_windows), C.byref(cfg), _ptr(final), _stream()))
+        return final
+
+    def joint_flush(self, win: Optional[torch.Tensor], n: int) -> torch.Tensor:
+        """mcd_stream_joint_flush: as `flush` -> (n * (seg_len - 1), num_transform, 17)."""
+        with torch.cuda.device(self.device):
+            out = torch.empty(int(n) * (self.seg_len - 1), self.num_transform, 17, device=self.device, dtype=torch.float32)
+            if out.numel():
+                _lib.check(self.L.mcd_stream_joint_flush(C.byref(self._state), C.byref(self._jstate), _ptr(win), int(n), _ptr(out),
+                                                         _stream()))
+        return out
 
     def push_group(self, raw: torch.Tensor, desc: torch.Tensor, n: int, n_windows: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """mcd_stream_push_group: the rows of a group of ticks, raw (n, 34) fp32, desc (n, 4) int32 [slot, row index, batch

@@ -322,7 +322,7 @@ class MoCoDAD(_Base):
     # -------------------------------------------------------------- forward
     def forward(self, input_data: List[torch.Tensor], aggr_strategy: str = None, return_: str = None, *,
                 noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,
-                cond_mask: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+                cond_mask: Optional[torch.Tensor] = None, return_maps: bool = False) -> List[torch.Tensor]:
         """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or pose] + the inputs.
 
         noise (extension, keyword only): (S, max(ns-1,1), B, C, Tx, V) tensor replacing the in-kernel Philox
@@ -330,7 +330,13 @@ class MoCoDAD(_Base):
         order; used for parity tests.  window_offset: global index of the first window (keys the noise stream).
         cond_mask ('random_imp' only): (B,) bitmasks of the condition frames; default = drawn like the reference does
         (one torch.randperm per window on the default CPU generator, mocodad.py:719-724), or, with random_imp_draw='device',
-        on the device from (seed, window_offset + b) -- the same sets however the windows are cut into batches or shards."""
+        on the device from (seed, window_offset + b) -- the same sets however the windows are cut into batches or shards.
+        return_maps (extension, keyword only; off: exactly the list above): two more entries at the END of the list -- maps
+        (B,Tx,V), which joints and forecast frames the window's score comes from (mean_{t,v} maps[b] = loss[b] up to rounding,
+        under the aggregation's own sample selection: mcd_error_maps; 'all': the per-sample maps (B,S,Tx,V)), and map_frames
+        (B,Tx) int64, the 0-based window frame index of each map row."""
+        if return_maps and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
+            raise ValueError("return_maps: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
         tensor_data, meta_out, aggr, ret, sc, window_offset, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         pose_aggr = aggr in ("all", "random", "mean_pose", "median_pose")
         want_pose = ret in ("pose", "all") or pose_aggr
@@ -343,14 +349,29 @@ class MoCoDAD(_Base):
                 cond_mask = self.draw_random_imp_mask(tensor_data.shape[0])
         kw["cond_mask"] = cond_mask
         fusable = aggr in ("best", "worst", "mean", "median") or "quantile" in aggr
+        maps = None
         if fusable and not want_pose:
             # loss-only output: trajectories, condition encoder and the aggregation over the samples in ONE launch
-            loss, _, _ = sc.score_fused(tensor_data, aggregation=aggr, **kw)
+            if return_maps:
+                loss, _, _, maps = sc.score_fused(tensor_data, aggregation=aggr, want_maps=True, **kw)
+            else:
+                loss, _, _ = sc.score_fused(tensor_data, aggregation=aggr, **kw)
             selected_x = None
         else:
-            loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose, **kw)
+            loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose or return_maps, **kw)
             selected_x, loss = self._aggregate(sc, tensor_data, loss_all, poses_all, aggr, want_pose, cond_mask)
-        return self._pack_out_data(selected_x, loss, [tensor_data] + meta_out, return_=ret)
+            if return_maps:
+                maps = sc.error_maps(tensor_data, loss_all, poses_all, aggr, loss_fn=self.loss_name, cond_mask=cond_mask)
+        out = self._pack_out_data(selected_x, loss, [tensor_data] + meta_out, return_=ret)
+        return out + [maps, self.map_frames(cond_mask, maps.shape[0])] if return_maps else out
+
+    def map_frames(self, cond_mask: Optional[torch.Tensor], n_windows: int) -> torch.Tensor:
+        """(B,Tx) int64: the 0-based window frame index of each row of an error map -- the corrupt frames, for 'random_imp' the
+        clear bits of each window's condition mask in ascending order."""
+        if cond_mask is None:
+            return torch.tensor(self._frame_split()[1], dtype=torch.int64, device=self.device).repeat(n_windows, 1)
+        bits = (cond_mask.to(self.device, torch.int64)[:, None] >> torch.arange(self.n_frames, device=self.device)) & 1
+        return (bits == 0).nonzero()[:, 1].reshape(n_windows, self.n_frames_corrupt)
 
     def _begin_forward(self, input_data, aggr_strategy, return_, noise, window_offset):
         """What every forward starts with -> (windows, [transformation_idx, metadata, actual_frames], aggregation, return mode,

@@ -101,12 +101,18 @@ class MoCoDADlatent(MoCoDAD):
         return fn(x, z0.expand_as(x), reduction="none").mean(dim=-1)
 
     def forward(self, input_data: List[torch.Tensor], condition_data: torch.Tensor = None, aggr_strategy: str = 'best', *,
-                return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None) -> List[torch.Tensor]:
+                return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,
+                return_maps: bool = False) -> List[torch.Tensor]:
         """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or selected latent] + the inputs, as
         mocodad_latent.py:69-129 (`condition_data` is unused there too; `aggr_strategy` defaults to 'best', None = the module's).
 
         noise (extension, keyword only): (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream -- slot 0 = the x_T of
-        torch.randn (:109), slot k = the randn_like of step ns-k (:121), in call order.  window_offset keys the Philox stream."""
+        torch.randn (:109), slot k = the randn_like of step ns-k (:121), in call order.  window_offset keys the Philox stream.
+        return_maps: NotImplementedError -- the error maps of MoCoDAD.forward are per joint and forecast frame, and a latent has
+        no joints."""
+        if return_maps:
+            raise NotImplementedError("MoCoDADlatent has no error maps: its loss is taken on a latent code, and a latent has no joints "
+                                      "(return_maps is for the pose model, MoCoDAD)")
         tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         loss_based = aggr in ("mean", "median") or "quantile" in aggr
         if (loss_based or aggr in ("best", "worst")) and (ret == "loss" or loss_based):

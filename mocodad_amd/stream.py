@@ -30,7 +30,12 @@ of a clip the person aggregation of the final row scores, shifted, Gaussian-filt
 the device with the tick that makes it computable (`Tick.clip`), and `close_clip` ends a clip with the reflected tail.  `ClipTable`
 is the host half (clip slots, per clip the frame axis, watermark and emit cursor; plain NumPy), engine.ClipRings the device half
 (mcd_clip_state_t); a tick or a group adds one mcd_stream_clip_update and one mcd_stream_clip_emit launch, their descriptors ride
-in the tick's one copy.  The definitions stand above `ClipScoreCfg`."""
+in the tick's one copy.  The definitions stand above `ClipScoreCfg`.
+
+Per-joint frame scores (opt-in, `PoseStream(joint_scores=True)`): the tick's scoring call also yields the error maps
+of its windows (mcd_error_maps: per forecast frame and joint, the loss behind the window's score), a second ring (max_tracks,
+num_transform, L, 17) takes their per-row maximum with the same window table (mcd_stream_joint_scores_group), and
+`Tick.joint_final` / `FrameScores.joints` carry them row for row with the frame scores."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -743,6 +748,7 @@ class FrameScores:
     keys: List[Key]
     frames: np.ndarray
     values: "object"
+    joints: "object" = None           # PoseStream(joint_scores=True): (n, num_transform, 17) fp32 device, the same rows per joint
 
     def __len__(self):
         return len(self.keys)
@@ -762,6 +768,9 @@ class Tick:
     closed: FrameScores               # tails of the tracks max_idle closed at the start of this tick
     first_window_id: int              # windows this stream had emitted before the tick (keys the in-kernel noise)
     clip: Optional[ClipFrames] = None  # PoseStream(clip_scores=...): the clip scores that became computable with this tick
+    joint_final: "object" = None      # PoseStream(joint_scores=True): (n_emit, num_transform, 17) fp32 device, row for row with
+    #                                   `final` (= final.joints): per joint the maximum over the windows FORECASTING the row; 0 for
+    #                                   a row no window forecasts (the first n_cond rows of a track).  closed.joints: the tails
 
 
 class PoseStream:
@@ -775,16 +784,25 @@ class PoseStream:
     carries `clip`, the ClipFrames that became computable with it, and close_clip ends a clip.  The model's pad_size and the HR
     masks are NOT applied online (they need the clip's final length: evaluation devices of the dataset path); whatever
     anomaly_score_pad_size the model has is ignored here.  With clip_scores = None nothing of this runs.
+    joint_scores: per-joint frame scores beside the frame scores (pose model only): every scoring call also yields the error maps
+    of its windows (mcd_error_maps), a second ring (max_tracks, num_transform, ring_len, 17) takes their per-row, per-joint
+    maximum (mcd_stream_joint_scores_group), and `Tick.joint_final`, `Tick.closed.joints` and the `joints` of what `close`
+    returns carry them row for row with the frame scores -- bit for bit the dataset path's mcd_joint_scatter_max.  Off (the
+    default): no extra launch, no poses requested, nothing allocated.
 
     One PoseStream is driven from ONE stream (the current stream of the first push): its rings, staging buffers and the track
     table are per-tick state, and the launches of a tick are ordered only by that stream."""
 
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
                  num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
-                 clip_scores: Optional[ClipScoreCfg] = None):
+                 clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False):
         from .engine import ClipRings, StreamRings
         from .utils.transforms import affine_table
         self.latent = bool(getattr(model, "is_latent", False))
+        self.joint_scores = bool(joint_scores)
+        if self.joint_scores and self.latent:
+            raise NotImplementedError("PoseStream(joint_scores=True) needs the pose model: MoCoDADlatent takes its loss on a latent "
+                                      "code, and a latent has no joints")
         if self.latent and model.device.type != "cuda":
             raise ValueError("PoseStream scores the latent model (MoCoDADlatent) on a cuda device only: move the module to one "
                              "first (there is no CPU fallback)")
@@ -802,7 +820,8 @@ class PoseStream:
         self.num_transform = nt = max(1, int(model.num_transforms if num_transform is None else num_transform))
         self.table = TrackTable(max_tracks, self.seg_len, ring_len, max_idle)
         n = self.table.max_tracks
-        self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev)
+        self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev,
+                                 **({"joint_scores": True} if self.joint_scores else {}))
         self.ring = self.rings.ring
         self.clips, self.clip_rings, clip_words = None, None, 0
         if clip_scores is not None:
@@ -858,7 +877,8 @@ class PoseStream:
         with torch.cuda.device(self.device):
             win = self._upload([plan.win])[0] if n and pend else None
             out = self.rings.flush(win, n)
-        return FrameScores(keys, plan.frames.reshape(-1).copy(), out)
+            joints = self.rings.joint_flush(win, n) if self.joint_scores else None
+        return FrameScores(keys, plan.frames.reshape(-1).copy(), out, joints)
 
     def _clip_launches(self, cticks: List[ClipTick], parts: list):
         """The launch pairs of a tick's / a group's ClipTicks (one, unless batch_clip_ticks has to cut) -> (launches, index in
@@ -963,11 +983,16 @@ class PoseStream:
                 wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
                 # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches; else HipScorer.score_fused)
                 score = self.scorer.score if self.latent else self.scorer.score_fused
-                score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
-                      noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores)
+                res = score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
+                            noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores,
+                            **({"want_maps": True} if self.joint_scores else {}))
                 final = self.rings.frame_scores_group(scores, win_d, nw)
+                if self.joint_scores:       # the windows' error maps into the joint ring, by the same sorted window table
+                    jfinal = self.rings.joint_scores_group(res[3], win_d, nw, self.scorer._score_cfg(nw, 1, 2))
             else:
                 final = torch.empty(0, nt, device=dev, dtype=torch.float32)
+                if self.joint_scores:
+                    jfinal = torch.empty(0, nt, 17, device=dev, dtype=torch.float32)
             clips = [None] * len(g.plans)
             if g.clip is not None:
                 clips = self._clip_run(g.clip, launches, views[at:at + 3] or None, final, closed.values)
@@ -977,12 +1002,13 @@ class PoseStream:
             ne, w0, c1 = plan.n_emit, int(g.offsets[i]), c0 + len(plan.closed)
             a, b = nt * w0, nt * (w0 + ne)
             wb = WindowBatch(self.ring, base[a:b], trans[a:b], self.affine, self.seg_len) if ne else None
+            jf = jfinal[w0:w0 + ne] if self.joint_scores else None
             tail = FrameScores(closed.keys[c0 * pend:c1 * pend], closed.frames[c0 * pend:c1 * pend].copy(),
-                               closed.values[c0 * pend:c1 * pend])
+                               closed.values[c0 * pend:c1 * pend], closed.joints[c0 * pend:c1 * pend] if self.joint_scores else None)
             out.append(Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                             trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores[a:b], windows=wb,
-                            final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne]), closed=tail,
-                            first_window_id=first + a, clip=clips[i]))
+                            final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne], jf), closed=tail,
+                            first_window_id=first + a, clip=clips[i], joint_final=jf))
             c0 = c1
         return out
 

@@ -94,6 +94,38 @@ def frame_score_rows(out, trans, meta, frames, gts, num_transform, scatter_max: 
     return mat, row_keys
 
 
+def joint_score_rows(maps, trans, meta, frames, gts, num_transform: int, joint_scatter_max: Callable):
+    """Per-joint frame scores of a dataset (eval_MoCoDAD.py --joint-scores): the error maps of every window (N, Tx, V) (device
+    tensor, MoCoDAD.forward(return_maps=True)) with frames (N, Tx) = the 1-based frame id of each map row are averaged over the
+    transforms -- a transform only negates or rotates coordinates, so a joint keeps its index; a torch op on the device, not a hot
+    path -- and scatter-maxed (mcd_joint_scatter_max) onto one row per (scene, clip, person) of the clips in `gts`, in
+    lexicographic order: the rows of frame_score_rows without the transform.  Every window (scene, clip, person, first frame) must
+    be there once under every transform 0 .. num_transform - 1, in any order.
+    -> (scores (n_rows, n_frames_max, V) fp32 NumPy, row_keys (n_rows, 3)); a frame no window forecasts stays 0."""
+    import torch
+    trans, meta, frames = np.asarray(trans), np.asarray(meta), np.asarray(frames)
+    nt = max(1, int(num_transform))
+    N = len(trans)
+    n = N // nt
+    order = np.lexsort((trans, meta[:, 3], meta[:, 2], meta[:, 1], meta[:, 0])) if N else np.zeros(0, np.int64)      # by window, then transform
+    grid = order[:n * nt].reshape(n, nt)
+    if n * nt != N or maps.shape[0] != N or not np.array_equal(trans[grid], np.tile(np.arange(nt), (n, 1))) \
+            or not (meta[grid] == meta[grid[:, :1]]).all() or not (frames[grid] == frames[grid[:, :1]]).all() \
+            or (n > 1 and (meta[grid[1:, 0]] == meta[grid[:-1, 0]]).all(1).any()):
+        raise ValueError("joint scores need every window once under every transform 0 .. num_transform - 1, with the same frames")
+    mean = maps[torch.from_numpy(grid.reshape(-1)).to(maps.device)].reshape(n, nt, *maps.shape[1:]).mean(1)
+    meta, frames = meta[grid[:, 0]], frames[grid[:, 0]]
+    sel = np.zeros(n, dtype=bool)
+    for (sc, cl) in gts:
+        sel |= (meta[:, 0] == sc) & (meta[:, 1] == cl)
+    row_keys, row = np.unique(meta[sel, :3].astype(np.int64), axis=0, return_inverse=True)
+    n_frames = max(len(g) for g in gts.values())
+    idx = torch.from_numpy(np.flatnonzero(sel)).to(mean.device)
+    out = joint_scatter_max(mean[idx], torch.from_numpy(np.ascontiguousarray(frames[sel], dtype=np.int32)),
+                            torch.from_numpy(row.reshape(-1).astype(np.int32)), len(row_keys), n_frames)
+    return out.cpu().numpy(), row_keys
+
+
 def post_process_scores(out, trans, meta, frames, gts: Dict[Tuple[int, int], np.ndarray], *, num_transform: int,
                         pad_size: int, filter_kernel_size: float, frames_shift: int, masks: Optional[Dict] = None,
                         scatter_max: Optional[Callable] = None) -> Tuple[np.ndarray, np.ndarray]:

@@ -29,6 +29,8 @@ On an on-disk split the AUC of the ONLINE scores against the ground-truth masks 
 masks without an emitted score are excluded and counted).  The two differ by definition -- online, a frame's persons are those
 with a score at that frame, not the clip's whole roster, and neither pad_size nor the HR masks are applied -- so neither is
 asserted against the other.
+--joint-scores: per-joint frame scores in every tick (PoseStream(joint_scores=True)): "tick" then includes the error
+maps launch behind the scoring call and mcd_stream_joint_scores_group; pose model only.
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
 emitted windows, the range of the per-replay medians (the spread), and the same for the baseline."""
 import argparse
@@ -86,6 +88,7 @@ def main():
     ap.add_argument("--ticks-per-call", type=int, default=1, help="K > 1: K ticks per push_many call (1: one push per tick)")
     ap.add_argument("--clip-scores", action="store_true", help="online per-clip frame scores in every tick (Tick.clip)")
     ap.add_argument("--sigma", type=float, default=None, help="Gaussian sigma of the clip scores (default: the model's filter_kernel_size)")
+    ap.add_argument("--joint-scores", action="store_true", help="per-joint frame scores in every tick (Tick.joint_final)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
     cli = ap.parse_args()
@@ -156,7 +159,7 @@ def main():
 
     def replay(collect=None, online=None):
         stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=ring_len,
-                            num_transform=nt, clip_scores=clip_cfg)
+                            num_transform=nt, clip_scores=clip_cfg, **({"joint_scores": True} if cli.joint_scores else {}))
         times, counts, rows, spent = [], [], 0, 0.0
         for call, done in calls:
             torch.cuda.synchronize()
@@ -241,7 +244,7 @@ def main():
            "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
-           "model": "MoCoDADlatent" if latent else "MoCoDAD", "clip_scores": clip_res,
+           "model": "MoCoDADlatent" if latent else "MoCoDAD", "clip_scores": clip_res, "joint_scores": bool(cli.joint_scores),
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
