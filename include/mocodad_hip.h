@@ -296,7 +296,10 @@ int mcd_error_maps(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joi
 
 /* Frame-score assembly that follows the path (mocodad.py:386-401 + eval_utils.py:27-34): scatter-max of
  * window scores to their frames.  scores (N,), frames (N,seg_len) 1-based int32, row (N,) int32 = output
- * row (one per (transform, clip, person)), out (n_rows, n_frames) pre-zeroed by the callee. */
+ * row (one per (transform, clip, person)), out (n_rows, n_frames) pre-zeroed by the callee; out[row, f] = the maximum of
+ * max(score, 0) (a NaN adds 0) over the windows covering frame f.  Frames outside [1, n_frames] and rows outside [0, n_rows) are
+ * ignored.  Argument errors (n, n_rows, n_frames < 0, seg_len < 1, a null pointer -- the inputs only when n > 0) are MCD_EINVAL
+ * before any device call; an empty output is MCD_OK and launches nothing. */
 int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* row, int64_t n, int32_t seg_len,
                     int32_t n_rows, int32_t n_frames, float* out, void* stream);
 

@@ -239,6 +239,60 @@ int upload_packed(const std::vector<float>& buf, int device, float** dbuf, int**
 
 static unsigned long long* g_prof = nullptr;  // MCD_PROFILE builds: device buffer of 32 accumulators
 
+// ---- host helpers shared by several entries below (templates: outside the extern "C" block)
+// The sample selection of aggregate_kernel / error_maps_kernel (Params = AggrParams / MapParams, zeroed and with P.s first):
+// the block both read, and their launch -- one 64-lane wave per window
+static void fill_select(SelectParams& s, const mcd_score_cfg_t* cfg, int strategy, float quantile, const float* loss_all,
+                        const float* pose_all, const mcd_window_view_t* view) {
+    s.loss_all = loss_all; s.pose_all = pose_all; s.win_mask = view ? view->cond_mask : nullptr;
+    s.B = cfg->n_windows; s.S = cfg->n_samples; s.Tx = cfg->n_corrupt; s.seg_len = cfg->seg_len;
+    s.strategy = strategy; s.loss_fn = cfg->loss_fn; s.q = quantile;
+    for (int t = 0; t < cfg->n_corrupt && t < MCD_MAX_FRAMES; ++t) s.corrupt_idx[t] = cfg->corrupt_idx[t];
+}
+template <class Params>
+static int launch_select(void (*kernel)(Params), Params& P, hipStream_t st) {
+    P.s.in_lds = P.s.S <= AGG_LDS_MAX;
+    const size_t lds = (size_t)(SEL_LDS_WORDS + (P.s.in_lds ? P.s.S : 0)) * sizeof(float);
+    hipLaunchKernelGGL(kernel, dim3(P.s.B < 65536 ? P.s.B : 65536), dim3(64), lds, st, P);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+// mcd_scatter_max (W = 1, n_slot = seg_len, any) / mcd_joint_scatter_max (W = 17, n_slot = n_corrupt <= 32): vals (n,) / (n, n_slot, 17)
+// -> out (n_rows, n_frames, W), zeroed here; every check before the first device call
+template <int W>
+static int scatter_max(const float* vals, const int32_t* frames, const int32_t* row, int64_t n, int32_t n_slot, int32_t n_rows,
+                       int32_t n_frames, float* out, void* stream) {
+    if (!out) return fail(MCD_EINVAL, "null argument");
+    if (n < 0 || n_slot < 1 || (W > 1 && n_slot > MCD_MAX_FRAMES) || n_rows < 0 || n_frames < 0)
+        return fail(MCD_EINVAL, W > 1 ? "need n, n_rows, n_frames >= 0 and 1 <= n_corrupt <= 32" : "need n, n_rows, n_frames >= 0 and 1 <= seg_len");
+    if (n > 0 && (!vals || !frames || !row)) return fail(MCD_EINVAL, "null argument");
+    if (n > 0x7fffffffffffffffll / ((long long)n_slot * W)) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    const long long total = (long long)n * n_slot * W;
+    if ((total + 255) / 256 > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    if ((size_t)n_rows * n_frames == 0) return MCD_OK;
+    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_rows * n_frames * W * sizeof(float), st));
+    if (n == 0) return MCD_OK;
+    hipLaunchKernelGGL(scatter_max_kernel<W>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, vals, frames, row,
+                       (long long)n, n_slot, n_rows, n_frames, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+// the pending cells of n closed tracks out of a ring (n_slots, nt, L, W): the score ring (W = 1) or the joint ring (W = 17)
+template <int W>
+static int stream_flush(const StreamParams& P, const float* cells, const int32_t* win, int32_t n, float* out, void* stream) {
+    if (n < 0 || n > P.n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
+    const long long total = (long long)n * (P.seg_len - 1) * P.nt * W;
+    if (total == 0) return MCD_OK;
+    if (!win || !out) return fail(MCD_EINVAL, "null argument");
+    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
+    hipLaunchKernelGGL(stream_flush_kernel<W>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, cells, win, n, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 // the library is built with -fvisibility=hidden: only the C ABI of include/mocodad_hip.h is exported
 #pragma GCC visibility push(default)
 extern "C" {
@@ -413,14 +467,6 @@ int64_t mcd_score_workspace_bytes(const mcd_weights_t* w, const mcd_score_cfg_t*
     return pose_workspace(w, cfg->n_windows, cfg->n_samples).bytes;
 }
 
-static int launch_aggregate(AggrParams& A, hipStream_t st) {
-    A.in_lds = A.S <= AGG_LDS_MAX;
-    const size_t lds = (size_t)(2 + (A.in_lds ? A.S : 0)) * sizeof(float);
-    hipLaunchKernelGGL(aggregate_kernel, dim3(A.B < 65536 ? A.B : 65536), dim3(64), lds, st, A);      // one wave per window
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
-
 // One scoring call.  aggr = 0: per-sample losses only (loss_all required).  aggr = a loss-based MCD_AGGR_* strategy: loss_agg
 // (B,) is produced too -- inside the trajectory kernel when its workgroups see all samples of their windows (one launch per
 // call), by aggregate_kernel otherwise.
@@ -509,9 +555,9 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
         if (rc != MCD_OK || aggr == 0 || fused) return rc;
         AggrParams A;        // the workgroups did not see all samples of their windows: aggregate the (B,S) losses afterwards
         memset(&A, 0, sizeof(A));
-        A.loss_all = P.loss_out; A.loss_agg = loss_agg; A.B = B; A.S = S; A.C = C0; A.Tx = cfg->n_corrupt; A.V = 17;
-        A.seg_len = cfg->seg_len; A.strategy = aggr; A.loss_fn = cfg->loss_fn; A.q = quantile;
-        return launch_aggregate(A, st);
+        fill_select(A.s, cfg, aggr, quantile, P.loss_out, nullptr, nullptr);
+        A.loss_agg = loss_agg; A.C = C0; A.V = 17;
+        return launch_select(aggregate_kernel, A, st);
     };
     // (strategy inject <=> the handle has a condition encoder)
     const CondRoute croute = cond_route(w, route == UNET_KERNEL && P.split == 1 && cfg->n_cond == Tu);
@@ -566,19 +612,15 @@ int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n
     const bool need_pose = strategy == MCD_AGGR_MEAN_POSE || strategy == MCD_AGGR_MEDIAN_POSE;
     if (need_pose && (!pose_all || !data)) return fail(MCD_EINVAL, "pose strategies need pose_all and data");
     if (pose_agg && !pose_all) return fail(MCD_EINVAL, "pose_agg requested without pose_all");
-    if (cfg->n_windows <= 0) return MCD_OK;
     if (view && view->base) return fail(MCD_EINVAL, "mcd_aggregate_view reads dense (B,C,T,V) windows: materialise the view (base must be NULL)");
     const int32_t* win_mask = view ? view->cond_mask : nullptr;
     if (win_mask && (cfg->seg_len < 1 || cfg->seg_len > MCD_MAX_FRAMES || cfg->n_corrupt < 1 || cfg->n_corrupt > cfg->seg_len))
         return fail(MCD_EINVAL, "cond_mask: need 1 <= n_corrupt <= seg_len <= 32");
     AggrParams P;
     memset(&P, 0, sizeof(P));
-    P.loss_all = loss_all; P.pose_all = pose_all; P.data = data; P.loss_agg = loss_agg; P.pose_agg = pose_agg;
-    P.B = cfg->n_windows; P.S = cfg->n_samples; P.C = num_coords; P.Tx = cfg->n_corrupt; P.V = n_joints;
-    P.seg_len = cfg->seg_len; P.strategy = strategy; P.loss_fn = cfg->loss_fn; P.q = quantile;
-    for (int t = 0; t < cfg->n_corrupt && t < MCD_MAX_FRAMES; ++t) P.corrupt_idx[t] = cfg->corrupt_idx[t];
-    P.win_mask = win_mask;
-    return launch_aggregate(P, (hipStream_t)stream);
+    fill_select(P.s, cfg, strategy, quantile, loss_all, pose_all, view);
+    P.data = data; P.loss_agg = loss_agg; P.pose_agg = pose_agg; P.C = num_coords; P.V = n_joints;
+    return launch_select(aggregate_kernel, P, (hipStream_t)stream);
 }
 
 int mcd_error_maps(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joints, int32_t strategy, float quantile,
@@ -607,46 +649,19 @@ int mcd_error_maps(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n_joi
     memset(&P, 0, sizeof(P));
     if (int rc = window_view(data, view, cfg->seg_len, P.dv)) return rc;
     if (cfg->n_windows == 0) return MCD_OK;
-    P.loss_all = loss_all; P.pose_all = pose_all; P.maps = maps_out; P.win_mask = win_mask;
-    P.B = cfg->n_windows; P.S = cfg->n_samples; P.Tx = cfg->n_corrupt; P.seg_len = cfg->seg_len;
-    P.strategy = strategy; P.loss_fn = cfg->loss_fn; P.q = quantile;
-    for (int t = 0; t < cfg->n_corrupt; ++t) P.corrupt_idx[t] = cfg->corrupt_idx[t];
-    P.in_lds = P.S <= AGG_LDS_MAX;
-    const size_t lds = (size_t)(4 + (P.in_lds ? P.S : 0)) * sizeof(float);
-    hipLaunchKernelGGL(error_maps_kernel, dim3(P.B < 65536 ? P.B : 65536), dim3(64), lds, (hipStream_t)stream, P);      // one wave per window
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    fill_select(P.s, cfg, strategy, quantile, loss_all, pose_all, view);
+    P.maps = maps_out;
+    return launch_select(error_maps_kernel, P, (hipStream_t)stream);
 }
 
 int mcd_joint_scatter_max(const float* maps, const int32_t* frames, const int32_t* row, int64_t n, int32_t n_corrupt,
                           int32_t n_rows, int32_t n_frames, float* out, void* stream) {
-    if (!out) return fail(MCD_EINVAL, "null argument");
-    if (n < 0 || n_corrupt < 1 || n_corrupt > MCD_MAX_FRAMES || n_rows < 0 || n_frames < 0)
-        return fail(MCD_EINVAL, "need n, n_rows, n_frames >= 0 and 1 <= n_corrupt <= 32");
-    if (n > 0 && (!maps || !frames || !row)) return fail(MCD_EINVAL, "null argument");
-    const long long total = (long long)n * n_corrupt * 17;
-    if ((total + 255) / 256 > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    if ((size_t)n_rows * n_frames == 0) return MCD_OK;
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_rows * n_frames * 17 * sizeof(float), st));
-    if (n == 0) return MCD_OK;
-    hipLaunchKernelGGL(joint_scatter_max_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, maps, frames, row,
-                       (long long)n, n_corrupt, n_rows, n_frames, out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return scatter_max<17>(maps, frames, row, n, n_corrupt, n_rows, n_frames, out, stream);
 }
 
 int mcd_scatter_max(const float* scores, const int32_t* frames, const int32_t* row, int64_t n, int32_t seg_len,
                     int32_t n_rows, int32_t n_frames, float* out, void* stream) {
-    if (!scores || !frames || !row || !out) return fail(MCD_EINVAL, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_rows * n_frames * sizeof(float), st));
-    if (n <= 0) return MCD_OK;
-    const long long total = (long long)n * seg_len;
-    hipLaunchKernelGGL(scatter_max_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, scores, frames, row,
-                       (long long)n, seg_len, n_frames, out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return scatter_max<1>(scores, frames, row, n, seg_len, n_rows, n_frames, out, stream);
 }
 
 int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float vid_h, const double* center,
@@ -678,18 +693,18 @@ static int stream_params(const mcd_stream_state_t* s, StreamParams* P) {
 int mcd_stream_flush(const mcd_stream_state_t* s, const int32_t* win, int32_t n, float* out, void* stream) {
     StreamParams P;
     if (int rc = stream_params(s, &P)) return rc;
-    if (n < 0 || n > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
-    const long long total = (long long)n * (P.seg_len - 1) * P.nt;
-    if (total == 0) return MCD_OK;
-    if (!win || !out) return fail(MCD_EINVAL, "null argument");
-    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
-    hipLaunchKernelGGL(stream_flush_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, win, n, out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return stream_flush<1>(P, P.fs, win, n, out, stream);
 }
 
 // rows (windows) one group may hold: n_slots * (ring_len - seg_len + 1), the per-track bound times the tracks
 static int64_t stream_group_rows(const mcd_stream_state_t* s) { return (int64_t)s->n_slots * (s->ring_len - s->seg_len + 1); }
+// the window count of a group's score launch, one thread per (window, transform, lane of a W-wide cell): *total = the threads
+static int check_group_windows(const mcd_stream_state_t* s, int32_t n_windows, int W, long long* total) {
+    if (n_windows < 0 || n_windows > stream_group_rows(s)) return fail(MCD_EINVAL, "need 0 <= n_windows <= n_slots * (ring_len - seg_len + 1)");
+    *total = (long long)n_windows * s->num_transform * W;
+    if (*total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
+    return MCD_OK;
+}
 
 int mcd_stream_push_group(const mcd_stream_state_t* s, const float* raw, const int32_t* desc, int32_t n, int32_t n_windows,
                           float vid_w, float vid_h, const double* center, const double* scale, int64_t* base_out,
@@ -714,11 +729,10 @@ int mcd_stream_frame_scores_group(const mcd_stream_state_t* s, const float* scor
                                   float* final_out, void* stream) {
     StreamParams P;
     if (int rc = stream_params(s, &P)) return rc;
-    if (n_windows < 0 || n_windows > stream_group_rows(s)) return fail(MCD_EINVAL, "need 0 <= n_windows <= n_slots * (ring_len - seg_len + 1)");
+    long long total;
+    if (int rc = check_group_windows(s, n_windows, 1, &total)) return rc;
     if (n_windows == 0) return MCD_OK;
     if (!scores || !win || !final_out) return fail(MCD_EINVAL, "null argument");
-    const long long total = (long long)n_windows * P.nt;
-    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
     hipLaunchKernelGGL(stream_frame_scores_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
                        scores, win, n_windows, (int)total, final_out);
     HIP_TRY(hipGetLastError());
@@ -750,13 +764,12 @@ int mcd_stream_joint_scores_group(const mcd_stream_state_t* s, const mcd_stream_
         if (t < 0 || t >= cfg->seg_len || J.tx_of[t] >= 0) return fail(MCD_EINVAL, "bad corrupt_idx");
         J.tx_of[t] = k;
     }
-    if (n_windows < 0 || n_windows > stream_group_rows(s)) return fail(MCD_EINVAL, "need 0 <= n_windows <= n_slots * (ring_len - seg_len + 1)");
+    long long total;
+    if (int rc = check_group_windows(s, n_windows, 17, &total)) return rc;
     if (n_windows == 0) return MCD_OK;
     if (!maps || !win || !final_out) return fail(MCD_EINVAL, "null argument");
-    const long long n_win = (long long)n_windows * P.nt, total = n_win * 17;
-    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many windows for one launch");
     hipLaunchKernelGGL(stream_joint_scores_group_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P, J,
-                       maps, win, n_windows, (int)n_win, final_out);
+                       maps, win, n_windows, n_windows * P.nt, final_out);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
 }
@@ -765,15 +778,7 @@ int mcd_stream_joint_flush(const mcd_stream_state_t* s, const mcd_stream_joint_s
                            float* out, void* stream) {
     StreamParams P;
     if (int rc = stream_joint_params(s, js, &P)) return rc;
-    if (n < 0 || n > s->n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
-    const long long total = (long long)n * (P.seg_len - 1) * P.nt * 17;
-    if (total == 0) return MCD_OK;
-    if (!win || !out) return fail(MCD_EINVAL, "null argument");
-    if (total > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
-    hipLaunchKernelGGL(stream_joint_flush_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, P,
-                       js->joint_scores, win, n, out);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return stream_flush<17>(P, js->joint_scores, win, n, out, stream);
 }
 
 static int clip_params(const mcd_clip_state_t* c, ClipParams* P) {

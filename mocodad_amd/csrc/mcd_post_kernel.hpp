@@ -1,37 +1,48 @@
 // mcd_post_kernel.hpp — the device code of mcd_api.hip's own launches, everything around the trajectory kernels:
 //   aggregate_kernel            MoCoDAD._aggregation_strategy                                  models/mocodad.py:454-520
 //   error_maps_kernel           the per-element loss of :484 before its mean, under the same sample selection (mcd_error_maps)
-//   scatter_max / joint_scatter_max / frame_scatter / frame_scores kernels   post_processing    models/mocodad.py:362-425
+//                               -- both on ONE statement of that selection: SelectParams, corrupt_frame, wave_select, wave_pose_stat
+//   scatter_max<W> / frame_scatter / frame_scores kernels   post_processing                    models/mocodad.py:362-425
+//                               (W = 1: window scores, W = 17: per-joint maps; atomic_max_nonneg is the one scatter-max idiom)
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
-//   stream_push_group / stream_frame_scores_group / stream_flush kernels   the same loader step + sliding windows + scatter-max,
+//   stream_push_group / stream_frame_scores_group / stream_flush<W> kernels   the same loader step + sliding windows + scatter-max,
 //                               one group of ticks at a time (a single tick is a group of one) on device rings
 //                                                               utils/preprocessing.py:14-86, models/mocodad.py:392-393
 //   stream_clip_update / stream_clip_emit kernels   online per-clip frame scores: the person aggregate, shift and Gaussian of
 //                               post_processing, incrementally on a per-clip ring     models/mocodad.py:399-424, utils/eval_utils.py:100-106
-//   stream_joint_scores_group / stream_joint_flush kernels   the per-joint sibling of the stream's score ring, fed by the error maps
+//   stream_joint_scores_group kernel   the per-joint sibling of the stream's score ring, fed by the error maps: the same walk over a
+//                               track's windows (walk_track_windows) with its own cell rule; flushed by stream_flush<17>
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
-// with the parameter blocks the host fills (AggrParams, MapParams, StreamParams, StreamJointParams, FrameParams, ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines
-// API_THREADS and says `using namespace mcd`), in front of its host code; the kernels keep the order, the linkage and the
-// visibility they had inside that file, so its device object does not change.
+// with the parameter blocks the host fills (SelectParams inside AggrParams and MapParams, StreamParams, StreamJointParams, FrameParams,
+// ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines API_THREADS and says `using namespace mcd`), in front
+// of its host code.
 #pragma once
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// aggregation over the S samples (mocodad.py:454-520); one 64-lane wave per window, ANY S (the reference's shipped
-// n_generated_samples is 50, config/*/mocodad_test.yaml; its _aggregation_strategy has no cap)
+// Which samples a window's score comes from (mocodad.py:454-520), stated once for aggregate_kernel and error_maps_kernel: one
+// 64-lane wave per window, ANY S (the reference's shipped n_generated_samples is 50, config/*/mocodad_test.yaml; its
+// _aggregation_strategy has no cap)
 // ------------------------------------------------------------------------------------------------
-struct AggrParams {
-    const float* loss_all; const float* pose_all; const float* data; float* loss_agg; float* pose_agg;
-    int B, S, C, Tx, V, seg_len, strategy, loss_fn, in_lds;
+struct SelectParams {         // filled by fill_select, in_lds by launch_select (mcd_api.hip)
+    const float* loss_all; const float* pose_all;
+    const int* win_mask;      // random_imp: (B,) condition-frame bitmasks; the window's corrupt frames are its clear bits in ascending
+                              // order and corrupt_idx is not read.  null = corrupt_idx
+    int B, S, Tx, seg_len, strategy, loss_fn, in_lds;
     float q;
     int corrupt_idx[MCD_MAX_FRAMES];
-    const int* win_mask;      // random_imp (mcd_aggregate_view): (B,) condition-frame bitmasks; the window's corrupt frames are its
-                              // clear bits in ascending order and corrupt_idx is not read.  null = corrupt_idx
 };
 constexpr int AGG_LDS_MAX = 8192;       // sample values staged in LDS (32 KB); a longer sample axis is read in place
+constexpr int SEL_LDS_WORDS = 4;        // in front of them: the two selected order statistics and their sample indices
+
+// data frame of the window's tx-th corrupt frame (max: a mask with more than seg_len - Tx bits set, which the caller must not
+// pass, still reads inside the window)
+__device__ __forceinline__ int corrupt_frame(const SelectParams& P, int b, int tx) {
+    return P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
+}
 
 // The S values of one window (its per-sample losses, or one pose element across the samples): staged in LDS, or -- beyond
 // AGG_LDS_MAX samples -- read where they lie (stride = floats between consecutive samples).
@@ -46,15 +57,50 @@ __device__ __forceinline__ SampleVals stage_samples(const float* src, long long 
     __syncthreads();
     return SampleVals{lds, 1};
 }
-// Order statistics by rank counting: sample i's rank = #{k : x_k < x_i or (x_k == x_i and k < i)} is a permutation of
-// 0 .. S-1 whatever the ties; lane l ranks the samples l, l + 64, ...; the samples of rank r0 / r1 land in slot[0] / slot[1].
-// (No sort, no per-thread array: O(S^2 / 64) broadcast reads per lane.)  All lanes return the same pair.
-// A NaN among the samples (a diverged chain) breaks the permutation -- every NaN ranks 0 and the rank asked for may have no
-// writer -- and torch.median / torch.quantile return NaN then (mocodad.py:489-492,513-516): so does this, for both values.
-// sel (error_maps_kernel; null = not wanted, and the code is the one without it): the INDICES of the two samples land in
-// islot[0] / islot[1] beside the values and come back in sel[0] / sel[1], -1 for both under a NaN.
-__device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int lane, int r0, int r1, float* slot, float& v0, float& v1,
-                                                 int* islot = nullptr, int* sel = nullptr) {
+// Sums and best / worst run in sample order on wave-uniform values: bit-identical to the sequential loops of
+// aggregate_losses in the fused kernel.
+__device__ __forceinline__ float wave_mean(const SampleVals& X, int S) {
+    float sum = 0.f;
+    for (int k = 0; k < S; ++k) sum += X(k);
+    return sum / (float)S;
+}
+// torch.lerp's two-sided form (torch.quantile): the interpolation of two order statistics a <= c (also applied per map cell by
+// error_maps_kernel, where a, c are any two values)
+__device__ __forceinline__ float lerp_two_sided(float a, float c, float wgt) {
+    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
+}
+// The selection of the loss-based strategies best / worst / median / quantile (mean needs none) on the staged losses X of one
+// window: the aggregated loss `value` (aggregate_kernel) and the one or two samples i0, i1 it comes from, with the interpolation
+// weight between them (error_maps_kernel; best / worst / median: the same sample twice, weight 0).  All lanes return the same.
+//   best / worst (mocodad.py:504-512): strict comparisons from 1e10 / -1, so the FIRST of equal samples stays; no sample
+//     passes (all NaN, or none below 1e10) -> i0 = i1 = -1.
+//   median / quantile: order statistics by rank counting: sample i's rank = #{k : x_k < x_i or (x_k == x_i and k < i)} is a
+//     permutation of 0 .. S-1 whatever the ties; lane l ranks the samples l, l + 64, ...; the samples of rank r0 / r1 land in
+//     slot[0] / slot[1], their indices in slot[2] / slot[3].  (No sort, no per-thread array: O(S^2 / 64) broadcast reads per lane.)
+//     torch.median: the lower middle value; torch.quantile: linear interpolation.
+//     A NaN among the samples (a diverged chain) breaks the permutation -- every NaN ranks 0 and the rank asked for may have no
+//     writer -- and torch.median / torch.quantile return NaN then (mocodad.py:489-492,513-516): so does this, with i0 = i1 = -1.
+struct Selection { int i0, i1; float wgt, value; };
+__device__ __forceinline__ Selection wave_select(const SampleVals& X, int S, int lane, int strategy, float q, float* slot) {
+    if (strategy == MCD_AGGR_BEST || strategy == MCD_AGGR_WORST) {
+        const bool best = strategy == MCD_AGGR_BEST;
+        float cur = best ? 1e10f : -1.f;
+        int sel = -1;
+        for (int k = 0; k < S; ++k) {
+            const float y = X(k);
+            if (best ? (y < cur) : (y > cur)) { cur = y; sel = k; }
+        }
+        return Selection{sel, sel, 0.f, cur};
+    }
+    int r0 = (S - 1) / 2, r1 = r0;
+    float wgt = 0.f;
+    if (strategy != MCD_AGGR_MEDIAN) {      // (as aggregate_losses, mcd_chain.hpp: sharing the text moved the trajectory objects)
+        const float pos = fminf(fmaxf(q, 0.f), 1.f) * (float)(S - 1);      // (q is validated on the host; the clamp is a backstop)
+        r0 = (int)floorf(pos);
+        r1 = r0 + 1 < S ? r0 + 1 : S - 1;
+        wgt = pos - (float)r0;
+    }
+    int* islot = reinterpret_cast<int*>(slot + 2);
     bool nan = false;
     for (int i = lane; i < S; i += 64) {
         const float x = X(i);
@@ -64,220 +110,153 @@ __device__ __forceinline__ void wave_rank_select(const SampleVals& X, int S, int
             const float y = X(k);
             r += (y < x || (y == x && k < i)) ? 1 : 0;
         }
-        if (r == r0) { slot[0] = x; if (sel) islot[0] = i; }
-        if (r == r1) { slot[1] = x; if (sel) islot[1] = i; }
+        if (r == r0) { slot[0] = x; islot[0] = i; }
+        if (r == r1) { slot[1] = x; islot[1] = i; }
     }
     __syncthreads();
-    const bool any_nan = __ballot(nan) != 0ull;        // (one 64-lane wave per workgroup: aggregate_kernel's launch bound)
-    v0 = any_nan ? __builtin_nanf("") : slot[0];
-    v1 = any_nan ? __builtin_nanf("") : slot[1];
-    if (sel) { sel[0] = any_nan ? -1 : islot[0]; sel[1] = any_nan ? -1 : islot[1]; }
+    const bool any_nan = __ballot(nan) != 0ull;        // (one 64-lane wave per workgroup: the kernels' launch bound)
+    const float a = any_nan ? __builtin_nanf("") : slot[0], c = any_nan ? __builtin_nanf("") : slot[1];
+    const Selection sel{any_nan ? -1 : islot[0], any_nan ? -1 : islot[1], wgt, strategy == MCD_AGGR_MEDIAN ? a : lerp_two_sided(a, c, wgt)};
     __syncthreads();
+    return sel;
 }
-// torch.median: the lower middle value; torch.quantile: linear interpolation, torch.lerp's two-sided form
-// the interpolation of two order statistics a <= c (also applied per map cell by error_maps_kernel, where a, c are any two values)
-__device__ __forceinline__ float lerp_two_sided(float a, float c, float wgt) {
-    return wgt < 0.5f ? a + wgt * (c - a) : c - (c - a) * (1.f - wgt);
-}
-// islot / sel / wgt_out (error_maps_kernel; null = not wanted): the two samples' indices as wave_rank_select yields them (the median:
-// the same sample twice, weight 0) and the interpolation weight
-__device__ __forceinline__ float wave_order_stat(const SampleVals& X, int S, int lane, int strategy, float q, float* slot,
-                                                 int* islot = nullptr, int* sel = nullptr, float* wgt_out = nullptr) {
-    float a, c;
-    if (strategy == MCD_AGGR_MEDIAN) {
-        wave_rank_select(X, S, lane, (S - 1) / 2, (S - 1) / 2, slot, a, c, islot, sel);
-        if (wgt_out) *wgt_out = 0.f;
-        return a;
-    }
-    const float pos = fminf(fmaxf(q, 0.f), 1.f) * (float)(S - 1);      // (q is validated on the host; the clamp is a backstop)
-    const int lo = (int)floorf(pos);
-    const int hi = lo + 1 < S ? lo + 1 : S - 1;
-    const float wgt = pos - (float)lo;
-    wave_rank_select(X, S, lane, lo, hi, slot, a, c, islot, sel);
-    if (wgt_out) *wgt_out = wgt;
-    return lerp_two_sided(a, c, wgt);
+// mean_pose / median_pose (mocodad.py:493-503): the mean or the lower median of ONE pose element across the S samples, wave-uniform
+__device__ __forceinline__ float wave_pose_stat(const SampleVals& X, int S, int lane, int strategy, float* slot) {
+    return strategy == MCD_AGGR_MEAN_POSE ? wave_mean(X, S) : wave_select(X, S, lane, MCD_AGGR_MEDIAN, 0.f, slot).value;
 }
 
-// Sums and best / worst run in sample order on wave-uniform values: bit-identical to the sequential loops of
-// aggregate_losses in the fused kernel.
-__global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams P) {
+// aggregation over the S samples: loss_agg (B,), and pose_agg under best / worst and the *_pose strategies.  data: dense
+// (B,C,T,V) windows at any C, V (read by the *_pose strategies only)
+struct AggrParams {
+    SelectParams s;
+    const float* data; float* loss_agg; float* pose_agg;
+    int C, V;
+};
+__global__ __launch_bounds__(64) void aggregate_kernel(const AggrParams A) {
     extern __shared__ float agg_lds[];
-    float* slot = agg_lds;               // [2] selected order statistics
-    float* vals = agg_lds + 2;           // [S] staged sample values (in_lds)
-    const int lane = threadIdx.x, S = P.S, per = P.C * P.Tx * P.V;
+    float* slot = agg_lds;                      // [SEL_LDS_WORDS] wave_select's
+    float* vals = agg_lds + SEL_LDS_WORDS;      // [S] staged sample values (in_lds)
+    const SelectParams& P = A.s;
+    const int lane = threadIdx.x, S = P.S, per = A.C * P.Tx * A.V;
     const bool in_lds = P.in_lds != 0;
     for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
-        if (P.strategy <= MCD_AGGR_QUANTILE && P.strategy != MCD_AGGR_MEAN_POSE && P.strategy != MCD_AGGR_MEDIAN_POSE) {
+        if (P.strategy != MCD_AGGR_MEAN_POSE && P.strategy != MCD_AGGR_MEDIAN_POSE) {
             const SampleVals X = stage_samples(P.loss_all + (size_t)b * S, 1, S, vals, in_lds, lane);
-            if (P.strategy == MCD_AGGR_BEST || P.strategy == MCD_AGGR_WORST) {
-                const bool best = P.strategy == MCD_AGGR_BEST;
-                float cur = best ? 1e10f : -1.f;       // mocodad.py:504-512: strict comparisons from 1e10 / -1 (the FIRST of equal samples stays)
-                int sel = -1;
-                for (int k = 0; k < S; ++k) {
-                    const float y = X(k);
-                    if (best ? (y < cur) : (y > cur)) { cur = y; sel = k; }
-                }
-                if (lane == 0) P.loss_agg[b] = cur;
-                if (P.pose_agg)
-                    for (int e = lane; e < per; e += 64)
-                        P.pose_agg[(size_t)b * per + e] = sel >= 0 ? P.pose_all[((size_t)b * S + sel) * per + e] : 0.f;
-            } else if (P.strategy == MCD_AGGR_MEAN) {
-                float sum = 0.f;
-                for (int k = 0; k < S; ++k) sum += X(k);
-                if (lane == 0) P.loss_agg[b] = sum / (float)S;
-            } else {
-                const float r = wave_order_stat(X, S, lane, P.strategy, P.q, slot);
-                if (lane == 0) P.loss_agg[b] = r;
+            if (P.strategy == MCD_AGGR_MEAN) {
+                const float mean = wave_mean(X, S);
+                if (lane == 0) A.loss_agg[b] = mean;
+                continue;
             }
-        } else {  // mean_pose / median_pose: per element over the S generated poses, then the loss of that pose (mocodad.py:493-503)
+            const Selection sel = wave_select(X, S, lane, P.strategy, P.q, slot);
+            if (lane == 0) A.loss_agg[b] = sel.value;
+            if (A.pose_agg && (P.strategy == MCD_AGGR_BEST || P.strategy == MCD_AGGR_WORST))
+                for (int e = lane; e < per; e += 64)
+                    A.pose_agg[(size_t)b * per + e] = sel.i0 >= 0 ? P.pose_all[((size_t)b * S + sel.i0) * per + e] : 0.f;
+        } else {  // per element over the S generated poses, then the loss of that pose
             float acc = 0.f;      // (every lane carries the same running sum: the per-element values are wave-uniform)
             for (int e = 0; e < per; ++e) {
                 const SampleVals X = stage_samples(P.pose_all + (size_t)b * S * per + e, per, S, vals, in_lds, lane);
-                float val;
-                if (P.strategy == MCD_AGGR_MEAN_POSE) {
-                    float sum = 0.f;
-                    for (int k = 0; k < S; ++k) sum += X(k);
-                    val = sum / (float)S;
-                } else {
-                    val = wave_order_stat(X, S, lane, MCD_AGGR_MEDIAN, 0.f, slot);
-                }
-                if (P.pose_agg && lane == 0) P.pose_agg[(size_t)b * per + e] = val;
-                const int c = e / (P.Tx * P.V), tx = (e / P.V) % P.Tx, v = e % P.V;
-                // (max: a mask with more than seg_len - Tx bits set, which the caller must not pass, still reads inside the window)
-                const int frame = P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
-                const float gt = P.data[(((size_t)b * P.C + c) * P.seg_len + frame) * P.V + v];
+                const float val = wave_pose_stat(X, S, lane, P.strategy, slot);
+                if (A.pose_agg && lane == 0) A.pose_agg[(size_t)b * per + e] = val;
+                const int c = e / (P.Tx * A.V), tx = (e / A.V) % P.Tx, v = e % A.V;
+                const float gt = A.data[(((size_t)b * A.C + c) * P.seg_len + corrupt_frame(P, b, tx)) * A.V + v];
                 acc += loss_elem(val, gt, P.loss_fn);
             }
-            if (lane == 0) P.loss_agg[b] = acc / (float)per;
+            if (lane == 0) A.loss_agg[b] = acc / (float)per;
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Error maps (mcd_error_maps): which joints and forecast frames a window's score comes from.  One 64-lane wave per window like
-// aggregate_kernel, whose selection it repeats on the same loss_all bits with the same functions: E[b,s,t,v] = (1/C) sum_c
-// loss_elem(pose, gt), the ground truth loaded by load_coord -- the trajectory kernels' loader, so the bits the loss saw.
-// The window's sample(s) are chosen by the wave, then the lanes take the Tx * V cells.
+// aggregate_kernel, with the same selection on the same loss_all bits -- wave_select, wave_pose_stat, corrupt_frame above:
+// E[b,s,t,v] = (1/C) sum_c loss_elem(pose, gt), the ground truth loaded by load_coord -- the trajectory kernels' loader, so the
+// bits the loss saw.  The window's sample(s) are chosen by the wave, then the lanes take the Tx * V cells.
 // ------------------------------------------------------------------------------------------------
 struct MapParams {
-    const float* loss_all; const float* pose_all; float* maps;
+    SelectParams s;
     DataView dv;
-    const int* win_mask;      // as AggrParams::win_mask
-    int B, S, Tx, seg_len, strategy, loss_fn, in_lds;
-    float q;
-    int corrupt_idx[MCD_MAX_FRAMES];
+    float* maps;
 };
-// data frame of the window's tx-th corrupt frame (the max: as in aggregate_kernel, a bad mask still reads inside the window)
-__device__ __forceinline__ int map_frame(const MapParams& P, int b, int tx) {
-    return P.win_mask ? max(nth_set_bit(~(unsigned)P.win_mask[b] & low_bits(P.seg_len), tx), 0) : P.corrupt_idx[tx];
-}
 // E of one cell for the pose at `p` (element (c, cell) at p[c * cells + cell]) against the ground truth (g0, g1)
 __device__ __forceinline__ float map_cell(const float* __restrict__ p, int cells, int cell, float g0, float g1, int loss_fn) {
     return (loss_elem(p[cell], g0, loss_fn) + loss_elem(p[cells + cell], g1, loss_fn)) / (float)C0;
 }
 
-__global__ __launch_bounds__(64) void error_maps_kernel(const MapParams P) {
+__global__ __launch_bounds__(64) void error_maps_kernel(const MapParams M) {
     extern __shared__ float map_lds[];
-    float* slot = map_lds;                                    // [2] selected order statistics
-    int* islot = reinterpret_cast<int*>(map_lds + 2);         // [2] their sample indices
-    float* vals = map_lds + 4;                                // [S] staged sample values (in_lds)
+    float* slot = map_lds;                      // [SEL_LDS_WORDS] wave_select's
+    float* vals = map_lds + SEL_LDS_WORDS;      // [S] staged sample values (in_lds)
+    const SelectParams& P = M.s;
     const int lane = threadIdx.x, S = P.S, cells = P.Tx * 17, per = C0 * cells;
     const bool in_lds = P.in_lds != 0;
     const float nanv = __builtin_nanf("");
     for (int b = blockIdx.x; b < P.B; b += gridDim.x) {
         const float* pose_b = P.pose_all + (size_t)b * S * per;
         if (P.strategy == MCD_AGGR_MEAN_POSE || P.strategy == MCD_AGGR_MEDIAN_POSE) {
-            // per element over the S poses exactly as aggregate_kernel forms pose_agg (wave-uniform values), cell by cell
-            float* out = P.maps + (size_t)b * cells;
+            // per element over the S poses as aggregate_kernel forms pose_agg (wave-uniform values), cell by cell
+            float* out = M.maps + (size_t)b * cells;
             for (int cell = 0; cell < cells; ++cell) {
-                const int tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
+                const int tx = cell / 17, v = cell - tx * 17, frame = corrupt_frame(P, b, tx);
                 float acc = 0.f;
                 for (int c = 0; c < C0; ++c) {
                     const SampleVals X = stage_samples(pose_b + c * cells + cell, per, S, vals, in_lds, lane);
-                    float val;
-                    if (P.strategy == MCD_AGGR_MEAN_POSE) {
-                        float sum = 0.f;
-                        for (int k = 0; k < S; ++k) sum += X(k);
-                        val = sum / (float)S;
-                    } else {
-                        val = wave_order_stat(X, S, lane, MCD_AGGR_MEDIAN, 0.f, slot);
-                    }
-                    acc += loss_elem(val, load_coord(P.dv, b, c, frame, v, P.seg_len), P.loss_fn);
+                    acc += loss_elem(wave_pose_stat(X, S, lane, P.strategy, slot), load_coord(M.dv, b, c, frame, v, P.seg_len), P.loss_fn);
                 }
                 if (lane == 0) out[cell] = acc / (float)C0;
             }
             continue;
         }
         if (P.strategy == MCD_AGGR_ALL) {
-            float* out = P.maps + (size_t)b * S * cells;
+            float* out = M.maps + (size_t)b * S * cells;
             for (int u = lane; u < S * cells; u += 64) {
-                const int s = u / cells, cell = u - s * cells, tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
-                out[u] = map_cell(pose_b + (size_t)s * per, cells, cell, load_coord(P.dv, b, 0, frame, v, P.seg_len),
-                                  load_coord(P.dv, b, 1, frame, v, P.seg_len), P.loss_fn);
+                const int s = u / cells, cell = u - s * cells, tx = cell / 17, v = cell - tx * 17, frame = corrupt_frame(P, b, tx);
+                out[u] = map_cell(pose_b + (size_t)s * per, cells, cell, load_coord(M.dv, b, 0, frame, v, P.seg_len),
+                                  load_coord(M.dv, b, 1, frame, v, P.seg_len), P.loss_fn);
             }
             continue;
         }
         // loss-based strategies: the sample(s), decided on the loss_all bits alone
-        int sel[2] = {-1, -1};
-        float wgt = 0.f;
-        if (P.strategy != MCD_AGGR_MEAN) {
-            const SampleVals X = stage_samples(P.loss_all + (size_t)b * S, 1, S, vals, in_lds, lane);
-            if (P.strategy == MCD_AGGR_BEST || P.strategy == MCD_AGGR_WORST) {
-                const bool best = P.strategy == MCD_AGGR_BEST;
-                float cur = best ? 1e10f : -1.f;       // aggregate_kernel's loop: strict comparisons, the first of equal samples stays
-                for (int k = 0; k < S; ++k) {
-                    const float y = X(k);
-                    if (best ? (y < cur) : (y > cur)) { cur = y; sel[0] = k; }
-                }
-                sel[1] = sel[0];
-            } else {
-                (void)wave_order_stat(X, S, lane, P.strategy, P.q, slot, islot, sel, &wgt);
-            }
-        }
-        float* out = P.maps + (size_t)b * cells;
+        Selection sel{-1, -1, 0.f, 0.f};
+        if (P.strategy != MCD_AGGR_MEAN) sel = wave_select(stage_samples(P.loss_all + (size_t)b * S, 1, S, vals, in_lds, lane), S, lane, P.strategy, P.q, slot);
+        float* out = M.maps + (size_t)b * cells;
         for (int cell = lane; cell < cells; cell += 64) {
-            const int tx = cell / 17, v = cell - tx * 17, frame = map_frame(P, b, tx);
-            const float g0 = load_coord(P.dv, b, 0, frame, v, P.seg_len), g1 = load_coord(P.dv, b, 1, frame, v, P.seg_len);
+            const int tx = cell / 17, v = cell - tx * 17, frame = corrupt_frame(P, b, tx);
+            const float g0 = load_coord(M.dv, b, 0, frame, v, P.seg_len), g1 = load_coord(M.dv, b, 1, frame, v, P.seg_len);
             float m;
             if (P.strategy == MCD_AGGR_MEAN) {
                 float sum = 0.f;
                 for (int k = 0; k < S; ++k) sum += map_cell(pose_b + (size_t)k * per, cells, cell, g0, g1, P.loss_fn);
                 m = sum / (float)S;
-            } else if (sel[0] < 0 || sel[1] < 0) {
+            } else if (sel.i0 < 0 || sel.i1 < 0) {
                 m = nanv;
             } else {
-                m = map_cell(pose_b + (size_t)sel[0] * per, cells, cell, g0, g1, P.loss_fn);
-                if (P.strategy == MCD_AGGR_QUANTILE && sel[1] != sel[0])
-                    m = lerp_two_sided(m, map_cell(pose_b + (size_t)sel[1] * per, cells, cell, g0, g1, P.loss_fn), wgt);
+                m = map_cell(pose_b + (size_t)sel.i0 * per, cells, cell, g0, g1, P.loss_fn);
+                if (P.strategy == MCD_AGGR_QUANTILE && sel.i1 != sel.i0)
+                    m = lerp_two_sided(m, map_cell(pose_b + (size_t)sel.i1 * per, cells, cell, g0, g1, P.loss_fn), sel.wgt);
             }
             out[cell] = m;
         }
     }
 }
 
-// per-joint scatter-max (mcd_joint_scatter_max): one thread per (window i, corrupt frame tx, joint v); maps >= 0 after the clamp
-__global__ void joint_scatter_max_kernel(const float* __restrict__ maps, const int* __restrict__ frames, const int* __restrict__ row,
-                                         long long n, int Tx, int n_rows, int n_frames, float* __restrict__ out) {
-    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * Tx * 17) return;
-    const long long it = u / 17, i = it / Tx;
-    const int v = (int)(u - it * 17), f = frames[it] - 1, r = row[i];
-    if (f < 0 || f >= n_frames || r < 0 || r >= n_rows) return;
-    atomicMax(reinterpret_cast<int*>(out + ((size_t)r * n_frames + f) * 17 + v), __float_as_int(fmaxf(maps[u], 0.f)));
+// Scatter-max (mocodad.py:392-393 + eval_utils.py:27-34).  Non-negative floats order like their bit patterns, so the maximum of
+// max(v, 0) (a NaN adds 0) over many writers is one atomicMax on the int view of a cell that starts at 0 (= absent).
+__device__ __forceinline__ void atomic_max_nonneg(float* cell, float v) {
+    atomicMax(reinterpret_cast<int*>(cell), __float_as_int(fmaxf(v, 0.f)));
 }
-
-
-// scatter-max of window scores to frames (mocodad.py:392-393 + eval_utils.py:27-34); scores >= 0
-__global__ void scatter_max_kernel(const float* __restrict__ scores, const int* __restrict__ frames,
-                                   const int* __restrict__ row, long long n, int seg_len, int n_frames,
-                                   float* __restrict__ out) {
+// One thread per (window i, frame slot k, lane v of the W-wide row): out (n_rows, n_frames, W).  W = 1 (mcd_scatter_max): the
+// window's score for each of its n_slot = seg_len frames; W = 17 (mcd_joint_scatter_max): vals = maps (n, n_slot = Tx, 17), per
+// joint.  Frames outside [1, n_frames] and rows outside [0, n_rows) are ignored.
+template <int W>
+__global__ void scatter_max_kernel(const float* __restrict__ vals, const int* __restrict__ frames, const int* __restrict__ row,
+                                   long long n, int n_slot, int n_rows, int n_frames, float* __restrict__ out) {
     const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * seg_len) return;
-    const long long i = u / seg_len;
-    const int f = frames[u] - 1;
-    if (f < 0 || f >= n_frames) return;
-    // non-negative floats order like their bit patterns
-    atomicMax(reinterpret_cast<int*>(out + (size_t)row[i] * n_frames + f), __float_as_int(fmaxf(scores[i], 0.f)));
+    if (u >= n * n_slot * W) return;
+    const long long ik = u / W, i = ik / n_slot;
+    const int v = (int)(u - ik * W), f = frames[ik] - 1, r = row[i];
+    if (f < 0 || f >= n_frames || r < 0 || r >= n_rows) return;
+    atomic_max_nonneg(out + ((size_t)r * n_frames + f) * W + v, vals[W == 1 ? i : u]);
 }
 
 // Per-frame pose normalisation of the dataset loader (utils/data.py:11-43,165-186 + 350-359), one thread per frame, in the
@@ -352,16 +331,18 @@ struct StreamParams {
     int n_slots, L, seg_len, nt;
 };
 
-// one thread per (closed track i, pending row k, transform t): the seg_len - 1 cells of rows r_last - seg_len + 2 .. r_last
-__global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const int* __restrict__ win, int n,
-                                                           float* __restrict__ out) {
+// one thread per (closed track i, pending row k, transform t, lane v of the row): the seg_len - 1 cells of rows r_last - seg_len + 2
+// .. r_last of a ring (n_slots, nt, L, W) -- W = 1: the score ring (mcd_stream_flush), W = 17: the joint ring (mcd_stream_joint_flush)
+template <int W>
+__global__ __launch_bounds__(256) void stream_flush_kernel(StreamParams S, const float* __restrict__ cells, const int* __restrict__ win,
+                                                           int n, float* __restrict__ out) {
     const int pend = S.seg_len - 1;
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * pend * S.nt) return;
-    const int t = u % S.nt, k = (u / S.nt) % pend, i = u / (S.nt * pend);
+    if (u >= n * pend * S.nt * W) return;
+    const int v = u % W, t = (u / W) % S.nt, k = (u / (W * S.nt)) % pend, i = u / (W * S.nt * pend);
     const int slot = win[2 * i], r_last = win[2 * i + 1];
     if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
-    out[u] = S.fs[((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L];
+    out[u] = cells[(((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L) * W + v];
 }
 
 // A GROUP of ticks in one launch (PoseStream.push / push_many): a track may receive R <= L - seg_len + 1 rows, so the rows
@@ -400,20 +381,30 @@ __global__ __launch_bounds__(256) void stream_push_group_kernel(StreamParams S, 
 // so the cells end as after one launch per tick, and each window's oldest row, which no later window covers, is final once
 // that window is in.
 // (An emitting slot holds ONE track within a group: a slot is only handed out again inside a group when its track got no row in it.)
+// walk_track_windows: that walk for transform t, begun at window q0 -- nothing unless q0 is its track's first window; then
+// body(slot, r_last, pos, w) for every valid window of the track in row order, pos = its batch position under transform t.
+template <class Body>
+__device__ __forceinline__ void walk_track_windows(const StreamParams& S, const int* __restrict__ win, int n, int n_win, int q0, int t,
+                                                   Body body) {
+    const int slot = win[5 * q0];
+    if (slot < 0 || slot >= S.n_slots) return;
+    if (q0 > 0 && win[5 * (q0 - 1)] == slot) return;           // not the track's first window: the thread of that one walks on
+    for (int q = q0; q < n && win[5 * q] == slot; ++q) {
+        const int r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
+        const long long pos = (long long)pos0 + (long long)t * ne;
+        if (r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos >= n_win || w < 0 || w >= n) continue;
+        body(slot, r_last, pos, w);
+    }
+}
+
 __global__ __launch_bounds__(256) void stream_frame_scores_group_kernel(StreamParams S, const float* __restrict__ scores,
                                                                         const int* __restrict__ win, int n, int n_win,
                                                                         float* __restrict__ final_out) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n * S.nt) return;
     const int q0 = u / S.nt, t = u - q0 * S.nt;
-    const int slot = win[5 * q0];
-    if (slot < 0 || slot >= S.n_slots) return;
-    if (q0 > 0 && win[5 * (q0 - 1)] == slot) return;           // not the track's first window: the thread of that one walks on
-    float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
-    for (int q = q0; q < n && win[5 * q] == slot; ++q) {
-        const int r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
-        const long long pos = (long long)pos0 + (long long)t * ne;
-        if (r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos >= n_win || w < 0 || w >= n) continue;
+    walk_track_windows(S, win, n, n_win, q0, t, [&](int slot, int r_last, long long pos, int w) {
+        float* row = S.fs + ((size_t)slot * S.nt + t) * S.L;
         const float sc = fmaxf(scores[pos], 0.f);
         const int first = r_last - S.seg_len + 1;
         for (int k = S.seg_len - 1; k >= 0; --k) {
@@ -422,7 +413,7 @@ __global__ __launch_bounds__(256) void stream_frame_scores_group_kernel(StreamPa
             *c = m;
             if (k == 0) final_out[(size_t)w * S.nt + t] = m;
         }
-    }
+    });
 }
 
 // Per-joint frame scores of a stream (mcd_stream_joint_state_t): ring (n_slots, nt, L, 17).  tx_of[k] = the index among the corrupt
@@ -435,21 +426,15 @@ struct StreamJointParams {
 // The walk of stream_frame_scores_group_kernel, per joint: one thread per (track's FIRST window, transform, joint).  The window
 // ending at row r_last INITIALISES that row's cell (its value there if it forecasts the row, else 0) -- the track's first window
 // (r_last = seg_len - 1) all seg_len cells, which is what lets a reused slot or a wrapped ring start clean without the push kernel
-// -- and takes the maximum into the older rows it forecasts; its oldest row is then final.  max(value, 0) as joint_scatter_max_kernel.
+// -- and takes the maximum into the older rows it forecasts; its oldest row is then final.  max(value, 0) as scatter_max_kernel.
 __global__ __launch_bounds__(256) void stream_joint_scores_group_kernel(StreamParams S, StreamJointParams J, const float* __restrict__ maps,
                                                                         const int* __restrict__ win, int n, int n_win,
                                                                         float* __restrict__ final_out) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n * S.nt * 17) return;
     const int v = u % 17, qt = u / 17, q0 = qt / S.nt, t = qt - q0 * S.nt;
-    const int slot = win[5 * q0];
-    if (slot < 0 || slot >= S.n_slots) return;
-    if (q0 > 0 && win[5 * (q0 - 1)] == slot) return;           // not the track's first window: the thread of that one walks on
-    float* cells = J.js + ((size_t)slot * S.nt + t) * S.L * 17 + v;
-    for (int q = q0; q < n && win[5 * q] == slot; ++q) {
-        const int r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
-        const long long pos = (long long)pos0 + (long long)t * ne;
-        if (r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos >= n_win || w < 0 || w >= n) continue;
+    walk_track_windows(S, win, n, n_win, q0, t, [&](int slot, int r_last, long long pos, int w) {
+        float* cells = J.js + ((size_t)slot * S.nt + t) * S.L * 17 + v;
         const float* m = maps + (size_t)pos * J.Tx * 17 + v;
         const int first = r_last - S.seg_len + 1;
         const bool init_all = first == 0;
@@ -461,21 +446,8 @@ __global__ __launch_bounds__(256) void stream_joint_scores_group_kernel(StreamPa
             *c = cur;
             if (k == 0) final_out[((size_t)w * S.nt + t) * 17 + v] = cur;
         }
-    }
+    });
 }
-
-// one thread per (closed track i, pending row k, transform t, joint v), as stream_flush_kernel
-__global__ __launch_bounds__(256) void stream_joint_flush_kernel(StreamParams S, const float* __restrict__ js, const int* __restrict__ win,
-                                                                 int n, float* __restrict__ out) {
-    const int pend = S.seg_len - 1;
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n * pend * S.nt * 17) return;
-    const int v = u % 17, t = (u / 17) % S.nt, k = (u / (17 * S.nt)) % pend, i = u / (17 * S.nt * pend);
-    const int slot = win[2 * i], r_last = win[2 * i + 1];
-    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
-    out[u] = js[(((size_t)slot * S.nt + t) * S.L + (r_last - S.seg_len + 2 + k) % S.L) * 17 + v];
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // Frame-score assembly after the path (mocodad.py:362-425; eval_utils.py:27-34,100-106,133-149), on device, in float64
@@ -544,8 +516,7 @@ __global__ void frame_scatter_kernel(const FrameParams Q) {
     if (f < 0 || f >= Q.clip_n[lo]) return;
     const long long row = ((long long)tr * Q.n_clips + lo) * Q.P + person;
     Q.used[row] = 1;
-    // non-negative floats order like their bit patterns (np.nanmax over the windows covering the frame; 0 = absent)
-    atomicMax(reinterpret_cast<int*>(Q.mat + row * Q.F + f), __float_as_int(fmaxf(Q.scores[i], 0.f)));
+    atomic_max_nonneg(Q.mat + row * Q.F + f, Q.scores[i]);      // np.nanmax over the windows covering the frame; 0 = absent
 }
 
 __global__ __launch_bounds__(256) void frame_scores_kernel(const FrameParams Q) {

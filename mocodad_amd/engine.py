@@ -23,6 +23,10 @@ def _f32c(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _i32c(t: torch.Tensor, device) -> torch.Tensor:
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
 def _quantile_of(strategy: str) -> float:
     """'quantile:q' -> q, rejected outside [0, 1] like torch.quantile does (mocodad.py:513-516)."""
     try:
@@ -341,9 +345,7 @@ class HipScorer(_Scorer):
     def joint_scatter_max(self, maps: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
         """mcd_joint_scatter_max: maps (N,Tx,V), frames (N,Tx) 1-based frame id of each map row, row (N,) output row
         -> (n_rows, n_frames, V): per joint the maximum over the windows forecasting the frame; 0 where none does."""
-        maps = _f32c(maps, self.device)
-        frames = frames.to(self.device, torch.int32).contiguous()
-        row = row.to(self.device, torch.int32).contiguous()
+        maps, frames, row = _f32c(maps, self.device), _i32c(frames, self.device), _i32c(row, self.device)
         n = int(row.numel())
         if maps.dim() != 3 or maps.shape[0] != n or maps.shape[2] != 17 or tuple(frames.shape) != (n, maps.shape[1]):
             raise ValueError(f"need maps (N, Tx, 17), frames (N, Tx) and row (N,), got {tuple(maps.shape)}, {tuple(frames.shape)}, {tuple(row.shape)}")
@@ -483,24 +485,18 @@ class HipScorer(_Scorer):
         if gives_pose and want_pose and poses_all is not None:
             pose = torch.empty(poses_all.shape[0], *poses_all.shape[2:], device=self.device, dtype=torch.float32)
         if cond_mask is not None:
-            cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
+            cond_mask = _i32c(cond_mask, self.device)
             if cond_mask.numel() != B:
                 raise ValueError(f"cond_mask must have {B} entries")
+        view = _window_view(None, cond_mask) if cond_mask is not None else None      # (no mask: a null view, cfg's corrupt_idx)
         with torch.cuda.device(self.device):
-            if cond_mask is None:
-                _lib.check(self.L.mcd_aggregate(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
-                                                _ptr(loss_all), _ptr(poses_all), _ptr(data), _ptr(out), _ptr(pose), _stream()))
-            else:
-                view = _window_view(None, cond_mask)
-                _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
-                                                     _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view), _ptr(out), _ptr(pose),
-                                                     _stream()))
+            _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
+                                                 _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None,
+                                                 _ptr(out), _ptr(pose), _stream()))
         return pose, out
 
     def scatter_max(self, scores: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
-        scores = _f32c(scores, self.device)
-        frames = frames.to(self.device, torch.int32).contiguous()
-        row = row.to(self.device, torch.int32).contiguous()
+        scores, frames, row = _f32c(scores, self.device), _i32c(frames, self.device), _i32c(row, self.device)
         out = torch.empty(n_rows, n_frames, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self.L.mcd_scatter_max(_ptr(scores), _ptr(frames), _ptr(row), scores.numel(), frames.shape[1],

@@ -422,6 +422,26 @@ def test_scatter_max():
     assert torch.equal(r["out"].cpu(), want)
 
 
+def test_scatter_max_ignores_rows_outside_the_output():
+    """Rows -1 and n_rows = 3 among valid ones, 7 frames: a store through such a row would land one 28-byte row before / behind the
+    interior -- inside the guard band, where it is reported -- and must not happen; the valid rows equal np.maximum.at.  (Only
+    inside the region: the call is not repeated on an unguarded buffer.)"""
+    sc, _, _ = _scorer("sk_inject6")
+    frames = torch.tensor([[1, 2, 3], [1, 2, 3], [5, 6, 7], [5, 6, 7], [3, 4, 5], [6, 7, 8], [2, 3, 4]], dtype=torch.int32)
+    row = torch.tensor([0, -1, 2, 3, 1, 3, -1], dtype=torch.int32)
+    scores = torch.tensor([0.5, 9.0, 0.75, 8.0, 1.5, 7.0, 6.0])
+    with guarded() as g:
+        out = sc.scatter_max(guarded_copy(scores.to(DEV), "nan"), frames, row, 3, 7)
+        torch.cuda.synchronize()
+        g.check()
+        assert g.registry and unwritten(out) == 0
+    want = np.zeros((3, 7), np.float32)
+    ok = ((row >= 0) & (row < 3)).numpy()
+    ii, kk = np.nonzero(ok[:, None] & (frames.numpy() >= 1) & (frames.numpy() <= 7))
+    np.maximum.at(want, (row.numpy()[ii], frames.numpy()[ii, kk] - 1), scores.numpy()[ii])
+    assert (want > 0).sum() == 9 and np.array_equal(out.cpu().numpy(), want)
+
+
 def test_frame_score_assembler():
     """The two-clip example of test_frame_scores_gpu.test_device_frame_scores_error_and_fallback, one window per clip: the float64
     `out` and the assembler's workspace."""

@@ -68,6 +68,10 @@ def _frames(L, c, scores=P, trans=P, meta=P, frames=P, n=4, ws=P, out=P):
     return L.mcd_frame_scores(C.byref(c) if c is not None else None, scores, trans, meta, frames, n, 6, ws, out, None)
 
 
+def _scatter(L, scores=P, frames=P, row=P, n=2, seg_len=3, n_rows=2, n_frames=4, out=P):
+    return L.mcd_scatter_max(scores, frames, row, n, seg_len, n_rows, n_frames, out, None)
+
+
 CASES = {
     # ---- mcd_aggregate / mcd_aggregate_view
     "aggregate_view: null cfg": lambda L: _agg(L, None),
@@ -119,6 +123,16 @@ CASES = {
     "normalize_poses: null raw": lambda L: L.mcd_normalize_poses(None, 4, 640.0, 360.0, None, None, P, None),
     "normalize_poses: null out": lambda L: L.mcd_normalize_poses(P, 4, 640.0, 360.0, None, None, None, None),
     "normalize_poses: 2^40 frames": lambda L: L.mcd_normalize_poses(P, 1 << 40, 640.0, 360.0, None, None, P, None),
+    # ---- mcd_scatter_max (the checks of mcd_joint_scatter_max, recorded when the two became one host function)
+    "scatter_max: null out": lambda L: _scatter(L, out=None),
+    "scatter_max: null scores": lambda L: _scatter(L, scores=None),
+    "scatter_max: null frames": lambda L: _scatter(L, frames=None),
+    "scatter_max: null row": lambda L: _scatter(L, row=None),
+    "scatter_max: n -1": lambda L: _scatter(L, n=-1),
+    "scatter_max: seg_len 0": lambda L: _scatter(L, seg_len=0),
+    "scatter_max: n_rows -1": lambda L: _scatter(L, n_rows=-1),
+    "scatter_max: n_frames -2": lambda L: _scatter(L, n_frames=-2),
+    "scatter_max: 2^40 windows": lambda L: _scatter(L, n=1 << 40),
     # ---- mcd_stream_*
     "stream_push_group: null state": lambda L: _push(L, None),
     "stream_push_group: null ring": lambda L: _push(L, state(ring=None)),
@@ -184,6 +198,12 @@ def test_rejected_before_any_device_call(name):
     code, msg = run_case(_lib.lib(), CASES[name])
     assert code < 0, "the case must be a rejected call"
     assert [code, msg] == expected("host")[name]
+
+
+def test_scatter_max_empty_output_is_ok_without_a_device_call():
+    L = _lib.lib()      # (there is no GPU here: a memset of zero bytes or a launch would not come back as MCD_OK)
+    assert _scatter(L, n_rows=0) == 0 and _scatter(L, n_frames=0) == 0
+    assert _scatter(L, scores=None, frames=None, row=None, n=0, n_rows=0) == 0      # the inputs may be null when n == 0
 
 
 def test_table_and_recording_agree():

@@ -299,3 +299,27 @@ def test_joint_scatter_max_is_np_maximum_at(n, Tx, n_rows, n_frames):
         assert (~ok).any() and ok.any() and (ref > 0).any()
     if n == 40:
         assert (ref == 0).any()              # cells that no window reaches stay 0
+
+
+def test_scatter_max_is_np_maximum_at():
+    """The scalar mcd_scatter_max (the same kernel at row width 1), exactly: 37 windows of 4 frames onto 3 rows x 11 frames, with
+    frame ids 0 and 12 (ignored), negative scores (clamped to 0) and NaN scores (a NaN adds 0)."""
+    n, T, n_rows, n_frames = 37, 4, 3, 11
+    rng = np.random.default_rng(37)
+    scores = rng.standard_normal(n).astype(np.float32)
+    scores[[5, 20]] = np.nan
+    first = rng.integers(-2, n_frames + 1, n)
+    first[:3] = (-3, 0, 9)                                              # frames -3 .. 0, 0 .. 3 and 9 .. 12
+    frames = (first[:, None] + np.arange(T)[None]).astype(np.int32)
+    row = rng.integers(0, n_rows, n).astype(np.int32)
+    assert (frames == 0).any() and (frames == 12).any() and (scores < 0).any()
+    ref = np.zeros((n_rows, n_frames), np.float32)
+    ii, tt = np.nonzero((frames >= 1) & (frames <= n_frames))
+    np.maximum.at(ref, (row[ii], frames[ii, tt] - 1), np.fmax(scores, np.float32(0))[ii])
+    L = _lib()
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    s, f, r = d(scores), d(frames), d(row)
+    out = torch.full((n_rows, n_frames), 3.0, device=DEV)               # (the callee zeroes it)
+    L.check(L.lib().mcd_scatter_max(_ptr(s), _ptr(f), _ptr(r), n, T, n_rows, n_frames, _ptr(out), _stream()))
+    assert np.array_equal(out.cpu().numpy().view(np.int32), ref.view(np.int32))
+    assert (ref > 0).any() and (ref == 0).any()

@@ -1,7 +1,7 @@
 """CPU: the host side of the error maps (ABI 15) -- every argument error of mcd_error_maps, mcd_joint_scatter_max and the two
 stream entries comes back as MCD_EINVAL before any device call (the buffers here are HOST memory: a call that got as far as a
 launch could not return MCD_EINVAL), the latent module's refusal, and a NumPy model of the joint ring's walk
-(stream_joint_scores_group_kernel / stream_joint_flush_kernel, restated below) held to a brute-force per-row maximum over seeded
+(stream_joint_scores_group_kernel / stream_flush_kernel<17>, restated below) held to a brute-force per-row maximum over seeded
 random interleavings with slot reuse, ring wrap and groups of K ticks.  The GPU tests (test_stream_joint_gpu.py) hold the kernels
 to the dataset path bit for bit."""
 import ctypes
@@ -182,7 +182,7 @@ def walk_group(ring, win, maps, tx_of, T, nt):
 
 
 def flush_model(ring, win, T):
-    """stream_joint_flush_kernel: win (n, 2) [slot, r_last] -> (n, T - 1, nt, 17)."""
+    """stream_flush_kernel<17>: win (n, 2) [slot, r_last] -> (n, T - 1, nt, 17)."""
     L = ring.shape[2]
     return np.stack([np.stack([ring[s, :, (r - T + 2 + k) % L] for k in range(T - 1)]) for s, r in win.tolist()]) if len(win) else \
         np.zeros((0, T - 1, ring.shape[1], 17), np.float32)
