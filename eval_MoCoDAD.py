@@ -29,8 +29,12 @@ from mocodad_amd.utils.argparser import load_config  # noqa: E402
 
 
 def model_class(args):
-    """MoCoDADlatent when the YAML says `diffusion_on_latent: true` (the reference's eval_MoCoDAD.py:45-46), else MoCoDAD."""
+    """MoCoDADlatent when the YAML says `diffusion_on_latent: true` (the reference's eval_MoCoDAD.py:45-46) -- its pretrain stage,
+    MoCoDADlatentPretrain, with `stage: 'pretrain'` -- else MoCoDAD."""
     if getattr(args, "diffusion_on_latent", False):
+        if getattr(args, "stage", "diffusion") == "pretrain":
+            from mocodad_amd.models.mocodad_latent_pretrain import MoCoDADlatentPretrain
+            return MoCoDADlatentPretrain
         from mocodad_amd.models.mocodad_latent import MoCoDADlatent
         return MoCoDADlatent
     return MoCoDAD
@@ -66,6 +70,9 @@ def main():
         if getattr(args, "aggregation_strategy", "best") in ("all", "random") or "random" in str(args.conditioning_strategy):
             raise SystemExit("eval_MoCoDAD.py: --joint-scores needs one map per window with the same forecast frames under every "
                              "transform: not aggregation_strategy all / random, not the random_imp strategy")
+    pretrain = bool(getattr(model_cls, "is_pretrain", False))
+    if pretrain and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("eval_MoCoDAD.py: stage 'pretrain' runs in one process (its result is one mean over all windows, not gathered scores)")
     if cli.device_masks:
         args.random_imp_draw = "device"
     if not cli.synthetic:
@@ -131,7 +138,7 @@ def main():
 
     n = len(tw) if tw is not None else data.shape[0]
     shard = WindowShard(n, rank, world)
-    if use_dist:
+    if use_dist and not pretrain:
         shard.host_meta = (trans.numpy(), meta.numpy(), frames.numpy())
         model.shard = shard
     model.save_tensors = False
@@ -162,7 +169,8 @@ def main():
     if rank == 0:
         # end to end (test_step loop + gather + frame-score assembly + AUC) beside the scoring loop alone (the kernels)
         print(f"windows: {n}  gpus: {world}  time: {dt:.3f}s  ({n / dt:.0f} clips/s end to end; scoring loop {t1 - t0:.3f}s = {n / (t1 - t0):.0f} clips/s "
-              f"+ epoch end {dt - (t1 - t0):.3f}s)  batch: {args.batch_size}  noise_steps: {args.noise_steps}  samples: {args.n_generated_samples}  AUC: {auc:.6f}")
+              f"+ epoch end {dt - (t1 - t0):.3f}s)  batch: {args.batch_size}  noise_steps: {args.noise_steps}  samples: {args.n_generated_samples}  "
+              + (f"pretrain_rec_loss: {auc:.6f}" if pretrain else f"AUC: {auc:.6f}"))
         if cli.dump_scores:
             import numpy as np
             np.savez(cli.dump_scores, scores=model.last_scores, auc=np.float64(auc))

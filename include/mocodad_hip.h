@@ -586,6 +586,41 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
                      int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,
                      void* stream);
 
+/* ---- MoCoDADlatent, stage 'pretrain': the bottleneck autoencoder (added without a change of MCD_ABI_VERSION: two new exports, no
+ * struct, enum or existing signature touched -- a caller built against version 15 without them runs unchanged, and a stale
+ * library shows as a missing symbol when the binding is made).
+ *
+ * Replaces: build_model, stage 'pretrain' (mocodad_latent.py:58-64): STSAE_Unet(use_bottleneck, inject_condition) + the condition
+ * encoder.  Reads 'model.{st_gcnnsp1a,st_gcnnsd1..3,down1,down2,to_time_dim}' as mcd_pack_latent_weights does, + 'model.{st_gcnnsu4,
+ * st_gcnnsu3,up3,up2,rev_to_time_dim}', + 'condition_encoder.*'; no 'denoiser.*'.  3 or 5 .. 12 corrupt frames, 1 .. 12 condition
+ * frames, latent_dim a multiple of 16 in 16 .. 128; anything else is MCD_EUNSUPPORTED by name, a missing tensor MCD_EMISSING with
+ * its name, both before the device is touched.  The handle is a mcd_latent_weights_t of the autoencoder kind: freed by
+ * mcd_free_latent_weights, sized by mcd_latent_workspace_bytes (cond_emb, z0, the condition encoder's scratch, and one region that
+ * holds H and then G = rev_to_time_dim(z), 640 floats per corrupt frame and window), taken by mcd_latent_encode and
+ * mcd_latent_reconstruct.  mcd_latent_score / mcd_latent_denoise on it, and mcd_latent_reconstruct on a diffusion-stage handle,
+ * return MCD_EUNSUPPORTED naming the kind the call needs. */
+int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
+                               int32_t device, mcd_latent_weights_t** out);
+
+/* Replaces: MoCoDADlatent.forward, stage 'pretrain' (mocodad_latent.py:93-100, 131: _unet_forward at t = -1 -> STSAE_Unet.forward,
+ * stsae_unet.py:406-438) and the per-window term of post_processing (mocodad_latent.py:218): launches [condition encoder] ->
+ * encode -> [project, 5 .. 12 corrupt frames] -> unproject (rev_to_time_dim, all windows as one MFMA product) -> decode (the up
+ * path with both skips, + X).  The decode launch forms the skips d1 / d2 again from the window's corrupt frames; nothing but G
+ * crosses the launch boundary.
+ *   z_in          NULL: the decoder takes the window's own code z0; else (B,D), 16-byte aligned: the caller's latents, decoded with
+ *                 the window's own skips and condition
+ *   pose_out      NULL or (B, 2, t_unet, 17): the reconstructed corrupt frames
+ *   loss_out      NULL or (B): mean over (c,t,v) of cfg->loss_fn(pose, corrupt frames), summed in a fixed order
+ *   cond_emb_out  NULL or (B,16);  z0_out  NULL or (B,D): the window's own code, also when z_in is given
+ * cfg: n_windows, seg_len, noise_steps (locates the table's row of t = -1), loss_fn and the frame lists; n_samples is not read.
+ * n_windows <= 0 returns MCD_OK before anything is touched.  Windows are independent: a non-finite pose or z_in row stays with
+ * its window, every other window's four outputs keep their bits.
+ * Alignment: workspace and z_in (when given) 16-byte aligned, else MCD_EINVAL before any launch; the outputs take any float
+ * alignment. */
+int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                           const float* step_table, void* workspace, const float* z_in, float* pose_out, float* loss_out,
+                           float* cond_emb_out, float* z0_out, void* stream);
+
 /* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
  * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121).
  * Alignment: noise_out must be 16-byte aligned (an element group of four floats is one store), else MCD_EINVAL. */

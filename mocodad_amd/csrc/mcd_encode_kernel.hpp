@@ -1,7 +1,7 @@
 // mcd_encode_kernel.hpp — the encoder family: the MFMA condition encoders of the pose model, cond_fast_kernel<T, NB> (shipped
 // channel list) and cond_unet_kernel<T, NB> ('E_unet'), and the latent model's encode launch latent_encode_kernel<T, NB,
-// COND_IN_KERNEL, PROJECT_IN_KERNEL>.  All three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear
-// over the (c,t,v) flattening; the shared pieces -- load_window_frames, unet_down_path, flatten_linear -- are stated here once
+// COND_IN_KERNEL, PROJECT_IN_KERNEL>, and the decode launch of its pretrain stage, latent_decode_kernel<T> (at the end of the file).
+// The first three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear over the (c,t,v) flattening; the shared pieces -- load_window_frames, unet_down_path, flatten_linear -- are stated here once
 // (DESIGN.md 2.1-2.2, 2.6).  cond_fast_body is also the trajectory kernel's prologue (score_kernel, P.cond_inkernel).
 #pragma once
 #include "mcd_device.hpp"
@@ -452,6 +452,136 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_encode_kernel(const float*
             latent_down_pass<T, NB, PROJECT_IN_KERNEL, true>(wbuf, dv, fi, seg_len, pe_row, z0_out, D, b0, B, smem, BAD, solo);
             __syncthreads();
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Decode launch of the latent autoencoder (stage 'pretrain': STSAE_Unet with use_bottleneck, stsae_unet.py:365-438, behind
+// rev_to_time_dim): ONE window per workgroup, so window isolation (top of this file) holds by construction.
+//   G (B, 640 T) = rev_to_time_dim(z) from latent_unproject_kernel, in H's order -> up3 + d2 -> layers 7, 8 -> up2 + d1 ->
+//   layers 9, 10 -> + X -> pose (B,2,T,17) and the window's mean loss against X (mocodad_latent.py:131, 218)
+// The skip tensors d1 / d2 do not cross the launch boundary: the kernel runs layers 0 .. 4 and down1 again on the window's corrupt
+// frames -- with the embedding rows the encode launch formed -- and keeps d1 / d2 in registers between the capturing down-samplers
+// and the adding up-samplers, as score_kernel does (resample_stage<.., CAPTURE> / <.., ADD>; DESIGN.md 2.6b says why).  Every
+// layer runs mix-first through layer_generic on Plan<T, 1>; layer 10's two output channels are one 16-channel m-tile whose other
+// rows the packer left zero.
+// Table of the packed buffer (pack_latent_ae_model): layers 0 .. 10 at l * F_STRIDE, W_e / b_e with all 530 rows, TAB_LAT_CAPW /
+// TAB_LAT_CAPB + 0, 1 = down1 / down2 in the capture k order, TAB_RSW / TAB_RSB + 2, 3 = up3 / up2.
+// ------------------------------------------------------------------------------------------------
+template <int T>
+struct LatentDecLds {
+    using PL = Plan<T, 1>;
+    static constexpr int G_IN = PL::s64b;                  // G [P10][68]: behind up3's output, where layer 7's z follows
+    static constexpr int L8_out = PL::s64b;                // [P12][36]
+    static constexpr int L10_z = 0, L10_out = 2 * PL::s32a;      // [P17][36] | [P17][20]
+    static constexpr int WORK = PL::R;
+    static constexpr int EMB = 560;                        // 530 rows; layer 10's m-tile reads 16 from emb_off(10) = 528: the rest zero
+    static constexpr int RED = NTHREADS / 16;              // loss partial sums, one per DPP row
+    static constexpr int FLOATS = WORK + EMB + EDIM + RED;
+    static_assert(G_IN + PL::P10 * 68 <= PL::R && L10_out + PL::s16 <= PL::R && PL::UP2_out + PL::s32a <= PL::R, "decode LDS plan");
+    static_assert(L8_out + PL::s32b <= PL::UP2_out, "decode LDS plan: layer 8's output under up2's");
+    static_assert(2 * T * 17 <= NTHREADS, "epilogue: one pose element per thread");
+};
+
+template <int T>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float* wbuf, const DataView dv, const FrameIdx fi, int seg_len,
+                                                                    const float* __restrict__ pe_row, const float* __restrict__ cond,
+                                                                    const float* __restrict__ G, float* __restrict__ pose_out,
+                                                                    float* __restrict__ loss_out, int loss_fn, int B) {
+    using PL = Plan<T, 1>;
+    using LD = LatentDecLds<T>;
+    constexpr int TV = T * 17, TV10 = T * 10, F = LAT_ENC_C * TV10;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const RG = smem;
+    float* const EMB = smem + LD::WORK;
+    float* const SEN = EMB + LD::EMB;
+    float* const RED = SEN + EDIM;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    Prof prof;
+    prof.off();
+    const float* wb = wbuf;
+    if (tid < EDIM) {
+        const float e = pe_row[tid] + cond[(size_t)b * EDIM + tid];
+        SEN[tid] = e / (1.f + expf(-e));
+    }
+    for (int u = tid; u < LD::WORK + LD::EMB; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
+    __syncthreads();
+    load_window_frames<T, 1>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b, B);
+    {
+        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
+        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
+        for (int o = tid; o < emb_off(10) + C0; o += NTHREADS) {      // the rows of all eleven layers, as latent_down_pass forms its 400
+            float a = be[o];
+#pragma unroll
+            for (int k = 0; k < EDIM; ++k) a = fmaf(we[o * EDIM + k], SEN[k], a);
+            EMB[o] = a;
+        }
+    }
+    __syncthreads();
+    // ---- layers 0 .. 4 once more, for the skips: d1 = layer 2's output, d2 = layer 4's, captured by the down-samplers' B reads
+    float skip1[RsCfg<32, 17, 12, T, 1, true>::PER * RsCfg<32, 17, 12, T, 1, true>::SK];
+    float skip2[RsCfg<64, 12, 10, T, 1, true>::PER * RsCfg<64, 12, 10, T, 1, true>::SK];
+    layer_generic<16, 16, 17, true, true, T, 1>(wb, layer_w(wb, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, EMB + emb_off(0), wave, lane, prof, 0);
+    layer_generic<16, 32, 17, true, true, T, 1>(wb, layer_w(wb, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, EMB + emb_off(1), wave, lane, prof, 0);
+    layer_generic<32, 32, 17, false, true, T, 1>(wb, layer_w(wb, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, EMB + emb_off(2), wave, lane, prof, 0);
+    {
+        RsCoef<32, 17, 12, T, 1, true> rc;
+        rc.load(wb + tab_i(wb, TAB_LAT_CAPW + 0), wb + tab_i(wb, TAB_LAT_CAPB + 0), lane);
+        resample_stage<32, 17, 12, T, 1, true, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, skip1, wave, lane);
+        __syncthreads();
+    }
+    layer_generic<32, 64, 12, true, true, T, 1>(wb, layer_w(wb, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, EMB + emb_off(3), wave, lane, prof, 0);
+    layer_generic<64, 64, 12, false, true, T, 1>(wb, layer_w(wb, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, EMB + emb_off(4), wave, lane, prof, 0);
+    {
+        // (down2's own output is not needed -- layers 5, 6 and the bottleneck ran in the launches before -- the stage is here for its reads)
+        RsCoef<64, 12, 10, T, 1, true> rc;
+        rc.load(wb + tab_i(wb, TAB_LAT_CAPW + 1), wb + tab_i(wb, TAB_LAT_CAPB + 1), lane);
+        resample_stage<64, 12, 10, T, 1, true, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, skip2, wave, lane);
+        __syncthreads();
+    }
+    // ---- G -> [P10][68]; the pad rows behind the last frame hold zeros (up3's trailing k-step reads two rows past a frame)
+    for (int u = tid; u < PL::P10 * 16; u += NTHREADS) {
+        const int col = u >> 4, q = u & 15;
+        const float4 v = col < TV10 ? load_global4(G + (size_t)b * F + col * LAT_ENC_C + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        lds_store4(lds_addr(RG + LD::G_IN + col * 68 + 4 * q), v.x, v.y, v.z, v.w);
+    }
+    __syncthreads();
+    {
+        RsCoef<64, 10, 12, T, 1, false> rc;
+        rc.load(wb + tab_i(wb, TAB_RSW + 2), wb + tab_i(wb, TAB_RSB + 2), lane);
+        resample_stage<64, 10, 12, T, 1, false, true>(RG + LD::G_IN, 68, RG + PL::UP3_out, 68, rc, skip2, wave, lane);      // up3 (+ d2)
+        __syncthreads();
+    }
+    layer_generic<64, 64, 12, false, true, T, 1>(wb, layer_w(wb, 7), RG + PL::L7_in, RG + PL::L7_z, RG + PL::L7_out, EMB + emb_off(7), wave, lane, prof, 0);
+    layer_generic<64, 32, 12, true, true, T, 1>(wb, layer_w(wb, 8), RG + PL::L8_in, RG + PL::L8_z, RG + LD::L8_out, EMB + emb_off(8), wave, lane, prof, 0);
+    {
+        RsCoef<32, 12, 17, T, 1, false> rc;
+        rc.load(wb + tab_i(wb, TAB_RSW + 3), wb + tab_i(wb, TAB_RSB + 3), lane);
+        resample_stage<32, 12, 17, T, 1, false, true>(RG + LD::L8_out, 36, RG + PL::UP2_out, 36, rc, skip1, wave, lane);     // up2 (+ d1)
+        __syncthreads();
+    }
+    layer_generic<32, 32, 17, false, true, T, 1>(wb, layer_w(wb, 9), RG + PL::L9_in, RG + PL::L9_z, RG + PL::L9_out, EMB + emb_off(9), wave, lane, prof, 0);
+    layer_generic<32, 16, 17, true, true, T, 1>(wb, layer_w(wb, 10), RG + PL::L10_in, RG + LD::L10_z, RG + LD::L10_out, EMB + emb_off(10), wave, lane, prof, 0);
+    // ---- + X, the pose, and the window's loss in a fixed order: one element per thread, the 16 lanes of a DPP row, then the 32
+    // row sums one after the other by one thread
+    float l = 0.f;
+    if (tid < C0 * TV) {
+        const int c = tid / TV, tv = tid - c * TV, t = tv / 17, v = tv - t * 17;
+        const float x = load_coord(dv, b, c, fi.idx[t], v, seg_len);
+        const float p = RG[LD::L10_out + tv * 20 + c] + x;
+        if (pose_out) pose_out[((size_t)b * C0 + c) * TV + tv] = p;
+        l = loss_elem(p, x, loss_fn);
+    }
+    l = row16_sum(l);
+    if ((lane & 15) == 0) RED[tid >> 4] = l;
+    __syncthreads();
+    if (tid == 0 && loss_out) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < LD::RED; ++i) s += RED[i];
+        loss_out[b] = s / (float)(C0 * TV);
     }
 }
 

@@ -14,6 +14,7 @@
 //   X(unit, TP, NB, LT)          score_tiled_kernel<TP, NB, LT>
 //   X(unit, TP, NB)              score_tiled_kernel<TP, NB, false, true>: the 'E_unet' condition encoder at 13 .. 32 condition frames
 //   X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL)   latent_encode_kernel (at the end of this file; its translation unit is mcd_latent.hip)
+//   X(unit, T)                   latent_decode_kernel<T> (likewise)
 #pragma once
 
 #ifndef MCD_FAST_T      // the shipped library
@@ -113,8 +114,14 @@
     X(0, 3, 2, true, true) X(0, 3, 2, false, true) \
     X(1, 5, 1, false, false) X(1, 12, 1, false, false) X(2, 6, 1, false, false) X(2, 11, 1, false, false) \
     X(3, 7, 1, false, false) X(3, 10, 1, false, false) X(4, 8, 1, false, false) X(4, 9, 1, false, false)
+// The decode launch of the latent autoencoder (stage 'pretrain'; latent_decode_kernel<T> of mcd_encode_kernel.hpp, one window per
+// workgroup), in units of mcd_latent.hip like the encode rows -- units of their own, so that no object of the rows above changes:
+//   X(unit, T)   latent_decode_kernel<T>: T corrupt frames, the frame counts of the encode rows
+// A developer build keeps the 3-frame row and the row of MCD_FAST_T, in unit 0.
+#define MCD_LATENT_DECODE_INSTANCES(X) \
+    X(5, 3) X(5, 5) X(5, 6) X(6, 7) X(6, 8) X(7, 9) X(7, 10) X(8, 11) X(8, 12)
 #ifndef MCD_FAST_T
-#define MCD_LATENT_UNITS 4
+#define MCD_LATENT_UNITS 8
 #else
 #define MCD_LATENT_UNITS 0
 #endif

@@ -2,7 +2,8 @@
 // mcd_encode_kernel.hpp, which mcd_launch.hpp brings) and their launchers; built with
 // the default eight waves per workgroup (the chain kernel has its own four).  Compiled once as it is (unit 0: the dispatch, the
 // chain, projection and Philox kernels, the encode kernels of the rows of unit 0) and once per unit n = 1 .. MCD_LATENT_UNITS
-// with -DMCD_LATENT_UNIT=n (the encode kernels of that unit's rows only); see MCD_LATENT_ENCODE_INSTANCES in mcd_instances.hpp.
+// with -DMCD_LATENT_UNIT=n (the encode / decode kernels of that unit's rows only); see MCD_LATENT_ENCODE_INSTANCES and
+// MCD_LATENT_DECODE_INSTANCES in mcd_instances.hpp.  Unit 0 also holds latent_unproject_kernel.
 #undef MCD_NWAVES      // (a developer build may name another wave count for its trajectory kernel)
 #ifndef MCD_LATENT_UNIT
 #define MCD_LATENT_UNIT 0
@@ -70,7 +71,71 @@ int launch_latent_encode_unit<MCD_LATENT_UNIT>(int t, bool cond_in_kernel, const
     return fail(MCD_EUNSUPPORTED, "latent encode: no such row");
 }
 
+// MCD_LATENT_DECODE_INSTANCES (mcd_instances.hpp): X(unit, T), the decode launch of the autoencoder, dispatched like the encode rows
+struct LatentDecodeArgs {
+    const float* wbuf; const DataView& dv; const FrameIdx& fi; int seg_len; const float* pe_row; const float* cond; const float* G;
+    float* pose_out; float* loss_out; int loss_fn, B; hipStream_t st;
+};
+
+template <int T>
+static int launch_latent_decode_t(const LatentDecodeArgs& a) {
+    static_assert(NWAVES == 8, "the latent decode launch ships with eight waves per workgroup");
+    constexpr size_t lds = (size_t)LatentDecLds<T>::FLOATS * 4;
+    static_assert(lds <= 160 * 1024, "latent decode: more than 160 KB of LDS");
+    LDS_LIMIT((&latent_decode_kernel<T>), lds);
+    hipLaunchKernelGGL((latent_decode_kernel<T>), dim3(a.B), dim3(NTHREADS), lds, a.st, a.wbuf, a.dv, a.fi, a.seg_len, a.pe_row, a.cond, a.G,
+                       a.pose_out, a.loss_out, a.loss_fn, a.B);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+template <bool HERE, int T>
+struct LatentDecodeRow {
+    static int go(const LatentDecodeArgs& a) { return launch_latent_decode_t<T>(a); }
+};
+template <int T>
+struct LatentDecodeRow<false, T> {
+    static int go(const LatentDecodeArgs&) { return fail(MCD_EUNSUPPORTED, "latent decode: the row is not part of this unit"); }
+};
+
+template <int U>
+int launch_latent_decode_unit(int t, const LatentDecodeArgs& a);
+#define MCD_ROW(unit, T) template <> int launch_latent_decode_unit<latent_row_unit(unit)>(int, const LatentDecodeArgs&);
+MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+
+template <>
+int launch_latent_decode_unit<MCD_LATENT_UNIT>(int t, const LatentDecodeArgs& a) {
+#define MCD_ROW(unit, T) if (t == (T)) return LatentDecodeRow<latent_row_held(T) && latent_row_unit(unit) == MCD_LATENT_UNIT, T>::go(a);
+    MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+    return fail(MCD_EUNSUPPORTED, "latent decode: no such row");
+}
+
 #if MCD_LATENT_UNIT == 0
+
+bool latent_decode_has_kernel(int t) {
+#define MCD_ROW(unit, T) if (latent_row_held(T) && t == (T)) return true;
+    MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+    return false;
+}
+
+int launch_latent_decode(int t, const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len, const float* pe_row,
+                         const float* cond, const float* G, float* pose_out, float* loss_out, int loss_fn, int B, hipStream_t st) {
+    const LatentDecodeArgs a{wbuf, dv, fi, seg_len, pe_row, cond, G, pose_out, loss_out, loss_fn, B, st};
+#define MCD_ROW(unit, T) if (latent_row_held(T) && t == (T)) return launch_latent_decode_unit<latent_row_unit(unit)>(t, a);
+    MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
+#undef MCD_ROW
+    return fail(MCD_EUNSUPPORTED, "the latent decode launch has no kernel for " + std::to_string(t) + " frames");
+}
+
+int launch_latent_unproject(int t, const float* wbuf, const float* z, float* G, int D, int B, hipStream_t st) {
+    hipLaunchKernelGGL(latent_unproject_kernel, dim3((B + UNPROJ_NC - 1) / UNPROJ_NC, t), dim3(UNPROJ_THREADS), 0, st, wbuf, z, G, D / 16,
+                       LAT_ENC_C * t * 10, B);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
 
 bool latent_encode_has_kernel(int t, bool cond_in_kernel) {
 #define MCD_ROW(unit, T, NB, CI, PIK) if (latent_row_held(T) && t == (T) && cond_in_kernel == (CI)) return true;

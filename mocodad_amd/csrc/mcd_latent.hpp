@@ -53,6 +53,12 @@ __host__ __device__ inline int latent_chain_lds_floats(int D, int chains_per_wg)
 
 // words of the packed buffer's offset table (mcd_device.hpp) that hold to_time_dim's weight / bias
 constexpr int TAB_LAT_LW = 100, TAB_LAT_LB = 101;
+// ... and, in an autoencoder handle (stage 'pretrain', pack_latent_ae_model) only: down1 / down2 once more in the CAPTURE k order
+// (fragments + 0, 1; biases + 0, 1), whose B operands are the skip tensors d1 / d2 (resample_stage); rev_to_time_dim's weight as
+// the A fragments of latent_unproject_kernel and its bias, both with the 640 t outputs in H's order [(t 10 + v) 64 + c].  The rows
+// of layers 7 .. 10 (l * F_STRIDE), up3 / up2 (TAB_RSW / TAB_RSB + 2, 3) and the embedding rows 400 .. 529 of W_e are filled there too.
+constexpr int TAB_LAT_CAPW = 102, TAB_LAT_CAPB = 104;
+constexpr int TAB_LAT_RW = 106, TAB_LAT_RB = 107;
 
 // launchers (mcd_latent.hip holds the kernels; mcd_api.hip only calls these)
 // The rows of MCD_LATENT_ENCODE_INSTANCES this library holds: is there an encode kernel for t corrupt frames (cond_in_kernel: the
@@ -66,6 +72,13 @@ int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const Da
                          int seg_len, const float* pe_row, float* cond_out, float* out, int D, int B, hipStream_t st);
 // H (B, 640 t) -> z0 (B,D): to_time_dim of the rows with PROJECT_IN_KERNEL = false
 int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_out, int D, int B, hipStream_t st);
+// The autoencoder's decoder half (mcd_latent_reconstruct).  z (B,D) -> G (B, 640 t) = rev_to_time_dim(z), in H's order
+int launch_latent_unproject(int t, const float* wbuf, const float* z, float* G, int D, int B, hipStream_t st);
+// is there a decode kernel for t corrupt frames (MCD_LATENT_DECODE_INSTANCES)
+bool latent_decode_has_kernel(int t);
+// G + the window's corrupt frames and cond_emb -> pose (B,2,t,17) and / or the window's mean loss against its corrupt frames (B)
+int launch_latent_decode(int t, const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len, const float* pe_row,
+                         const float* cond, const float* G, float* pose_out, float* loss_out, int loss_fn, int B, hipStream_t st);
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
 int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
 

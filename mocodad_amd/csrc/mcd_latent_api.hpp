@@ -1,6 +1,8 @@
 // mcd_latent_api.hpp — host side of the MoCoDADlatent entry points (include/mocodad_hip.h): the handle and the calls around the
 // launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose upload helper and condition-encoder routes it shares; the
-// front end of a call (view, checks, workspace layout, launch_cond) is mcd_call.hpp, the packer pack_latent_model of mcd_pack.hpp.
+// front end of a call (view, checks, workspace layout, launch_cond) is mcd_call.hpp, the packers pack_latent_model / pack_latent_ae_model
+// of mcd_pack.hpp.  A handle is of one of two kinds: diffusion stage (mcd_latent_score, mcd_latent_denoise) or autoencoder (stage
+// 'pretrain': mcd_latent_reconstruct); mcd_latent_encode, the workspace size, the options and the release take both.
 // It holds no device code.
 #pragma once
 #include "mcd_latent.hpp"
@@ -14,6 +16,8 @@ struct mcd_latent_weights {
     bool fused_ok;        // cond_fast_body's table is packed and t_cond = t_unet: the encode launch can run the condition encoder itself
     int h_floats;         // per window: the last encoder layer's output H that the encode launch leaves for latent_project_kernel; 0 = the
                           // encode launch computes z0 itself (3 corrupt frames)
+    bool ae;              // the autoencoder of stage 'pretrain' (mcd_pack_latent_ae_weights): decoder tables, no denoiser
+    int g_floats;         // ... per window: rev_to_time_dim's output G for latent_decode_kernel (it takes H's place once z0 is formed); else 0
     mcd_weights cw;       // the condition encoder as the pose model's launchers take it: dbuf, cond and the cond_* flags; nothing else is set
     int opt[MCD_LATENT_OPT_COUNT];
 };
@@ -75,6 +79,7 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
     memset(w->opt, 0, sizeof(w->opt));
     w->fused_ok = m.fused_ok != 0;
     w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
+    w->ae = false; w->g_floats = 0;
     w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
     memset(w->cw.opt, 0, sizeof(w->cw.opt));
     set_cond_weights(&w->cw, m, dbuf);
@@ -97,7 +102,7 @@ void mcd_free_latent_weights(mcd_latent_weights_t* w) {
 
 int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows) {
     if (!w || n_windows <= 0) return 0;
-    return latent_workspace(&w->cw, n_windows, w->net.D, w->h_floats).bytes;
+    return latent_workspace(&w->cw, n_windows, w->net.D, std::max(w->h_floats, w->g_floats)).bytes;
 }
 
 int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
@@ -111,7 +116,7 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     if (w->h_floats && !aligned16(z0_out)) return fail(MCD_EINVAL, "z0_out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     // no workspace argument here: the plain encoder's scratch and H come from the stream-ordered allocator
-    const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D, w->h_floats);
+    const LatentWorkspace lay = latent_workspace(&w->cw, cfg->n_windows, w->net.D, w->h_floats);      // (no G: nothing decodes here)
     const int64_t need = lay.bytes - lay.gather;
     char* scratch = nullptr;
     if (need > 0) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)need, st));
@@ -128,6 +133,7 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
 int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const float* cond, const float* step_table, int32_t t,
                        int32_t n_rows, float* eps_out, void* stream) {
     if (!w) return fail(MCD_EINVAL, "null argument");
+    if (w->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_denoise needs a diffusion-stage handle (mcd_pack_latent_weights): an autoencoder handle has no denoiser");
     if (n_rows <= 0) return MCD_OK;
     if (!x || !cond || !step_table || !eps_out) return fail(MCD_EINVAL, "null argument");
     if (t < 0) return fail(MCD_EINVAL, "t must be >= 0 (step_table needs at least t + 1 rows)");
@@ -144,6 +150,7 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
                      int32_t aggregation, float quantile, float* loss_agg, float* loss_all, float* latent_all, float* latent_code,
                      void* stream) {
     if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
+    if (w->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_score needs a diffusion-stage handle (mcd_pack_latent_weights): an autoencoder handle has no denoiser");
     const int B = cfg->n_windows, S = cfg->n_samples, D = w->net.D;
     if (B <= 0) return MCD_OK;
     if (!data || !step_table || !workspace) return fail(MCD_EINVAL, "null argument (the workspace of mcd_latent_workspace_bytes is required)");
@@ -174,6 +181,63 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
     P.B = B; P.S = S; P.ns = cfg->noise_steps; P.wpg = S >= LAT_NC ? 1 : LAT_NC / S;
     P.mode = 0; P.loss_fn = cfg->loss_fn; P.aggr = aggregation; P.aggr_q = quantile;
     return launch_latent_chain(P, st);
+}
+
+int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
+                               int32_t device, mcd_latent_weights_t** out) {
+    if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
+    PackedModel m;
+    int rc = pack_latent_ae_model(tensors, n_tensors, cfg, latent_dim, m);
+    if (rc != MCD_OK) return rc;
+    float* dbuf = nullptr;
+    rc = upload_packed(m.buf, device, &dbuf);
+    if (rc != MCD_OK) return rc;
+    mcd_latent_weights* w = new mcd_latent_weights();
+    w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
+    memset(w->opt, 0, sizeof(w->opt));
+    w->fused_ok = m.fused_ok != 0;
+    w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
+    w->ae = true; w->g_floats = LAT_ENC_C * cfg->t_unet * 10;
+    w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
+    memset(w->cw.opt, 0, sizeof(w->cw.opt));
+    set_cond_weights(&w->cw, m, dbuf);
+    *out = w;
+    return MCD_OK;
+}
+
+int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                           const float* step_table, void* workspace, const float* z_in, float* pose_out, float* loss_out,
+                           float* cond_emb_out, float* z0_out, void* stream) {
+    if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
+    if (!w->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_reconstruct needs an autoencoder handle (mcd_pack_latent_ae_weights): a diffusion-stage handle has no decoder");
+    const int B = cfg->n_windows, D = w->net.D, T = w->cfg.t_unet;
+    if (B <= 0) return MCD_OK;
+    if (!data || !step_table || !workspace) return fail(MCD_EINVAL, "null argument (the workspace of mcd_latent_workspace_bytes is required)");
+    if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
+    if (cfg->loss_fn < MCD_LOSS_SMOOTH_L1 || cfg->loss_fn > MCD_LOSS_MSE) return fail(MCD_EINVAL, "unknown loss_fn");
+    if (z_in && !aligned16(z_in)) return fail(MCD_EINVAL, "z_in must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const LatentWorkspace lay = latent_workspace(&w->cw, B, D, std::max(w->h_floats, w->g_floats));
+    char* wsb = reinterpret_cast<char*>(workspace);
+    float* cond = reinterpret_cast<float*>(wsb);
+    float* z0 = reinterpret_cast<float*>(wsb + lay.z0);
+    float* hg = reinterpret_cast<float*>(wsb + lay.h);      // H of the encode launch, then G of the unproject launch
+    if (int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, reinterpret_cast<float*>(wsb + lay.gather),
+                                    reinterpret_cast<float*>(wsb + lay.plain), hg, st)) return rc;
+    if (pose_out || loss_out) {
+        DataView dv;
+        if (int rc = window_view(data, view, cfg->seg_len, dv)) return rc;
+        FrameIdx fi;
+        memset(&fi, 0, sizeof(fi));
+        for (int k = 0; k < cfg->n_corrupt; ++k) fi.idx[k] = cfg->corrupt_idx[k];
+        const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
+        if (int rc = launch_latent_unproject(T, w->dbuf, z_in ? z_in : z0, hg, D, B, st)) return rc;
+        if (int rc = launch_latent_decode(T, w->dbuf, dv, fi, cfg->seg_len, pe_row, cond, hg, pose_out, loss_out, cfg->loss_fn, B, st)) return rc;
+    }
+    if (cond_emb_out) HIP_TRY(hipMemcpyAsync(cond_emb_out, cond, (size_t)B * EDIM * 4, hipMemcpyDeviceToDevice, st));
+    if (z0_out) HIP_TRY(hipMemcpyAsync(z0_out, z0, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+    return MCD_OK;
 }
 
 int mcd_latent_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,

@@ -6,6 +6,8 @@
 //   latent_philox_kernel          the perf mode's draws in the parity layout
 //   latent_project_kernel         to_time_dim for all windows of a call as MFMA products (5 .. 12 corrupt frames, whose encode launch
 //                                 stops at the last layer's output)
+//   latent_unproject_kernel       stage 'pretrain' (mcd_latent_reconstruct): rev_to_time_dim for all windows of a call as
+//                                 MFMA products, feeding latent_decode_kernel (mcd_encode_kernel.hpp)
 #pragma once
 #include "mcd_device.hpp"
 #include "mcd_latent.hpp"
@@ -249,6 +251,54 @@ __global__ __launch_bounds__(PROJ_THREADS) void latent_project_kernel(const floa
         }
         const float4 bb = load_global4(wbuf + tab_i(wbuf, TAB_LAT_LB) + c0);
         if (b < B) store_global4(z0_out + (size_t)b * D + c0, make_float4(s.x + bb.x, s.y + bb.y, s.z + bb.z, s.w + bb.w));
+    }
+}
+
+// rev_to_time_dim of the autoencoder (stsae_unet.py:433-434) for all windows of a call: G[b][r] = bias'[r] + sum_k W'[r][k] z[b][k]
+// with the 640 T outputs r in H's order [(t 10 + v) 64 + c] -- the rows of W' and bias' are permuted by the packer, so that
+// latent_decode_kernel copies a window's G into its LDS region with 16-byte loads -- and W' in pack_gemm_frags order (M = 640 T,
+// K = D).  Workgroup (x, y): windows 32 x .. 32 x + 31 as two n-tiles, the 40 m-tiles (one corrupt frame's 640 outputs) 40 y ..;
+// wave w takes the m-tiles w, w + 4, ...  A window is a column: its z stays in the wave's registers for all m-tiles, the k-chain of an
+// output starts from the bias and runs over k in ascending groups, and columns of an MFMA never mix -- a non-finite z row reaches
+// its own G row only.  The columns past the batch read the last window's z (inside the buffer), compute on zeros and store nothing.
+// Every workgroup streams its 40 D-wide row tiles of W' once per 32 windows.
+constexpr int UNPROJ_WAVES = 4, UNPROJ_THREADS = UNPROJ_WAVES * 64, UNPROJ_NC = 32, UNPROJ_MT = 40;
+__global__ __launch_bounds__(UNPROJ_THREADS) void latent_unproject_kernel(const float* __restrict__ wbuf, const float* __restrict__ z,
+                                                                          float* __restrict__ G, int KQ, int F, int B) {
+    const int tid = threadIdx.x, lane = tid & 63, n16 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int D = KQ * 16;
+    const int bA = blockIdx.x * UNPROJ_NC + n16, bB = bA + 16;
+    const float* zpA = z + (size_t)(bA < B ? bA : B - 1) * D + 4 * g;
+    const float* zpB = z + (size_t)(bB < B ? bB : B - 1) * D + 4 * g;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 zA[LAT_MAX_DIM / 16], zB[LAT_MAX_DIM / 16];
+#pragma unroll
+    for (int k = 0; k < LAT_MAX_DIM / 16; ++k) {
+        zA[k] = (k < KQ && bA < B) ? load_global4(zpA + k * 16) : zero;
+        zB[k] = (k < KQ && bB < B) ? load_global4(zpB + k * 16) : zero;
+    }
+    const float* wtab = wbuf + tab_i(wbuf, TAB_LAT_RW);
+    const float* btab = wbuf + tab_i(wbuf, TAB_LAT_RB);
+#pragma unroll 1
+    for (int i = 0; i < UNPROJ_MT / UNPROJ_WAVES; ++i) {
+        const int mt = blockIdx.y * UNPROJ_MT + wave + i * UNPROJ_WAVES;
+        const float* wp = wtab + ((size_t)mt * KQ * 64 + lane) * 4;
+        float4 a[LAT_MAX_DIM / 16];
+#pragma unroll
+        for (int k = 0; k < LAT_MAX_DIM / 16; ++k) a[k] = k < KQ ? load_global4(wp + k * 256) : zero;
+        const int c0 = mt * 16 + 4 * g;      // the lane's four output rows
+        const float4 bb = load_global4(btab + c0);
+        f32x4 accA = {bb.x, bb.y, bb.z, bb.w}, accB = accA;
+#pragma unroll
+        for (int k = 0; k < LAT_MAX_DIM / 16; ++k) {
+            if (k < KQ) {
+                accA = lat_mfma4(a[k], zA[k], accA);
+                accB = lat_mfma4(a[k], zB[k], accB);
+            }
+        }
+        if (bA < B) store_global4(G + (size_t)bA * F + c0, make_float4(accA[0], accA[1], accA[2], accA[3]));
+        if (bB < B) store_global4(G + (size_t)bB * F + c0, make_float4(accB[0], accB[1], accB[2], accB[3]));
     }
 }
 

@@ -2,7 +2,7 @@
 //   fold    BatchNorm folded into the 1x1 convolutions in double, once per layer (fold_layer) / resampler (fold_conv_bn) and handle
 //   emit    small emitters write a folded layer into the Builder in one of the layouts the kernels read: plain rows (GLayer, the
 //           runtime-shape kernels), MFMA fragments [W_t' | W_r'] or [W_t' ; W_r'], 16-padded biases, resampler fragments
-//   model   pack_pose_model / pack_latent_model call the emitters in the order the buffer is laid out in and return the host
+//   model   pack_pose_model / pack_latent_model / pack_latent_ae_model call the emitters in the order the buffer is laid out in and return the host
 //           buffer with every table the handle keeps (PackedModel); mcd_pack_weights / mcd_pack_latent_weights upload it.
 // The allocation ORDER of a call site is the buffer's layout: tests/test_pack_layout_host.py pins it (mcd_debug_pack_digest).
 #pragma once
@@ -461,6 +461,113 @@ int pack_pose_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_mo
 
 bool latent_dim_ok(int d) { return d >= 16 && d <= LAT_MAX_DIM && d % 16 == 0; }
 
+// The part both latent handles share, behind the offset table: the embedding table W_e / b_e with room for emb_rows rows (the rows
+// of layers 0 .. 6 filled), the down path's seven layers, every one mix-first, [W_t' | W_r'] (layer 6 too, as in cond_unet_kernel),
+// down1 / down2 (non-capturing fragments), to_time_dim for the encode launch's tail or for latent_project_kernel.
+int pack_latent_down(TensorMap& tm, int T, int D, int emb_rows, Builder& B, std::vector<int>& tab, int& we_off, int& be_off) {
+    we_off = B.alloc((size_t)emb_rows * EDIM); be_off = B.alloc(emb_rows);
+    for (int l = 0; l < LAT_DOWN_LAYERS; ++l) {
+        const LDesc Dl = layer_desc(l);
+        const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
+        int tq = 0, am = 0;
+        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
+        FoldedLayer f;
+        if (!fold_layer(tm, p, l == 0 ? C0 : Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
+        if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
+        const int bias = emit_bias16(f, B);
+        set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
+    }
+    tab[TAB_WE] = we_off; tab[TAB_BE] = be_off;
+    for (int r = 0; r < 2; ++r) {
+        Folded f;
+        if (!fold_resampler(tm, std::string("model.") + RS_NAMES[r], RS_IN[r], RS_OUT[r], f)) return fail(MCD_EMISSING, tm.missing);
+        tab[TAB_RSW + r] = emit_resampler(f, RS_IN[r], RS_OUT[r], false, B, &tab[TAB_RSB + r]);
+    }
+    const int64_t F = (int64_t)LAT_ENC_C * T * 10;
+    const float* lw = tm.get("model.to_time_dim.weight", F * D);
+    const float* lb = tm.get("model.to_time_dim.bias", D);
+    if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
+    if (latent_project_in_kernel(T)) {
+        tab[TAB_LAT_LW] = emit_copy(B, lw, F * D);
+    } else {
+        // latent_project_kernel: A fragments of W' [D][K], column k' = (t 10 + v) 64 + c of W' = column c T 10 + (t 10 + v) of the
+        // weight -- the order in which the encode launch leaves H
+        const int TV = T * 10;
+        tab[TAB_LAT_LW] = pack_gemm_frags(B, D, (int)F, [&](int r, int k) -> double { return lw[(size_t)r * F + (size_t)(k % LAT_ENC_C) * TV + k / LAT_ENC_C]; });
+    }
+    tab[TAB_LAT_LB] = emit_copy(B, lb, D);
+    return MCD_OK;
+}
+
+// MoCoDADlatent, stage 'pretrain' (mocodad_latent.py:59-64): STSAE_Unet with use_bottleneck -- the down path and to_time_dim as in
+// the diffusion stage's handle, then rev_to_time_dim and the up path (stsae_unet.py:365-438) for latent_unproject_kernel and
+// latent_decode_kernel -- and the condition encoder.  No denoiser.  The decoder tables exist in this kind of handle only.
+int pack_latent_ae_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int latent_dim, PackedModel& m) {
+    const int rc0 = check_common_cfg(cfg);
+    if (rc0 != MCD_OK) return rc0;
+    if (cfg->strategy != MCD_STRATEGY_INJECT) return fail(MCD_EINVAL, "the latent model conditions by 'inject' only (mocodad_latent.py:32)");
+    const int T = cfg->t_unet, D = latent_dim;
+    if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
+        return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
+    if (!latent_encode_has_kernel(T, false) || !latent_decode_has_kernel(T) || cfg->t_cond > 12)
+        return fail(MCD_EUNSUPPORTED, "the latent autoencoder has no kernels for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
+                                      " condition frames (instantiated: " + latent_encode_counts() + " corrupt frames with 1 .. 12 condition frames)");
+    if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
+        return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
+    if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
+        return fail(MCD_EUNSUPPORTED, "this library holds no cond_unet_kernel for " + std::to_string(cfg->t_cond) + " condition frames (MCD_COND_UNET_INSTANCES)");
+    if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
+
+    TensorMap tm = tensor_map(tensors, n_tensors);
+    Builder B;
+    B.alloc(TAB_FLOATS);
+    std::vector<int> tab(TAB_FLOATS, 0);
+    int we_off = 0, be_off = 0;
+    if (int rc = pack_latent_down(tm, T, D, EMB_TOTAL, B, tab, we_off, be_off)) return rc;
+    const bool fusable = cfg->t_cond == T && latent_encode_has_kernel(T, true);
+    const int rc = pack_cond_encoder(tm, cfg, B, m.cond, fusable);
+    if (rc != MCD_OK) return rc;
+    write_cond_table(tab.data(), m.cond);
+    m.fused_ok = m.cond.fast_table && fusable;
+    // ---- the up path: layers 7 .. 10 mix-first like the others (layer 10: its 2 output channels in one 16-row m-tile), their
+    // embedding rows behind those of the down path
+    for (int l = LAT_DOWN_LAYERS; l < NLAYERS; ++l) {
+        const LDesc Dl = layer_desc(l);
+        const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
+        int tq = 0, am = 0;
+        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
+        FoldedLayer f;
+        if (!fold_layer(tm, p, Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
+        if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
+        const int bias = emit_bias16(f, B);
+        set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
+    }
+    // up3 / up2, and down1 / down2 once more in the capture k order: the decode launch's down-samplers hold d1 / d2 in registers
+    for (int r = 0; r < 4; ++r) {
+        Folded f;
+        if (!fold_resampler(tm, std::string("model.") + RS_NAMES[r], RS_IN[r], RS_OUT[r], f)) return fail(MCD_EMISSING, tm.missing);
+        if (r < 2) tab[TAB_LAT_CAPW + r] = emit_resampler(f, RS_IN[r], RS_OUT[r], true, B, &tab[TAB_LAT_CAPB + r]);
+        else tab[TAB_RSW + r] = emit_resampler(f, RS_IN[r], RS_OUT[r], false, B, &tab[TAB_RSB + r]);
+    }
+    {
+        // latent_unproject_kernel: A fragments of W' [640 T][D] and bias', row r' = (t 10 + v) 64 + c = row c T 10 + (t 10 + v) of
+        // rev_to_time_dim (the view of stsae_unet.py:434) -- H's order, which the decode launch copies into its LDS region as it lies
+        const int TV = T * 10, F = LAT_ENC_C * TV;
+        const float* rw = tm.get("model.rev_to_time_dim.weight", (int64_t)F * D);
+        const float* rb = tm.get("model.rev_to_time_dim.bias", F);
+        if (!rw || !rb) return fail(MCD_EMISSING, tm.missing);
+        auto src_row = [&](int r) { return (size_t)(r % LAT_ENC_C) * TV + r / LAT_ENC_C; };
+        tab[TAB_LAT_RW] = pack_gemm_frags(B, F, D, [&](int r, int k) -> double { return rw[src_row(r) * D + k]; });
+        tab[TAB_LAT_RB] = B.alloc(F);
+        for (int r = 0; r < F; ++r) B.buf[tab[TAB_LAT_RB] + r] = rb[src_row(r)];
+    }
+    memset(&m.net, 0, sizeof(m.net));
+    m.net.D = D;
+    memcpy(B.buf.data(), tab.data(), sizeof(int) * TAB_FLOATS);
+    m.buf = std::move(B.buf);
+    return MCD_OK;
+}
+
 // MoCoDADlatent: the U-Net's down path (stsae_unet.py:182-219) with its embedding Linears, to_time_dim, the condition encoder,
 // the denoiser (components.py:228-241)
 int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* lcfg, PackedModel& m) {
@@ -488,40 +595,8 @@ int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_
     Builder B;
     B.alloc(TAB_FLOATS);
     std::vector<int> tab(TAB_FLOATS, 0);
-    // ---- the down path: every layer mix-first, [W_t' | W_r'] (layer 6 too, as in cond_unet_kernel)
-    const int we_off = B.alloc((size_t)LAT_EMB * EDIM), be_off = B.alloc(LAT_EMB);
-    for (int l = 0; l < LAT_DOWN_LAYERS; ++l) {
-        const LDesc Dl = layer_desc(l);
-        const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
-        int tq = 0, am = 0;
-        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-        FoldedLayer f;
-        if (!fold_layer(tm, p, l == 0 ? C0 : Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
-        if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
-        const int bias = emit_bias16(f, B);
-        set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
-    }
-    tab[TAB_WE] = we_off; tab[TAB_BE] = be_off;
-    for (int r = 0; r < 2; ++r) {
-        Folded f;
-        if (!fold_resampler(tm, std::string("model.") + RS_NAMES[r], RS_IN[r], RS_OUT[r], f)) return fail(MCD_EMISSING, tm.missing);
-        tab[TAB_RSW + r] = emit_resampler(f, RS_IN[r], RS_OUT[r], false, B, &tab[TAB_RSB + r]);
-    }
-    {
-        const int64_t F = (int64_t)LAT_ENC_C * T * 10;
-        const float* lw = tm.get("model.to_time_dim.weight", F * D);
-        const float* lb = tm.get("model.to_time_dim.bias", D);
-        if (!lw || !lb) return fail(MCD_EMISSING, tm.missing);
-        if (latent_project_in_kernel(T)) {
-            tab[TAB_LAT_LW] = emit_copy(B, lw, F * D);
-        } else {
-            // latent_project_kernel: A fragments of W' [D][K], column k' = (t 10 + v) 64 + c of W' = column c T 10 + (t 10 + v) of the
-            // weight -- the order in which the encode launch leaves H
-            const int TV = T * 10;
-            tab[TAB_LAT_LW] = pack_gemm_frags(B, D, (int)F, [&](int r, int k) -> double { return lw[(size_t)r * F + (size_t)(k % LAT_ENC_C) * TV + k / LAT_ENC_C]; });
-        }
-        tab[TAB_LAT_LB] = emit_copy(B, lb, D);
-    }
+    int we_off = 0, be_off = 0;
+    if (int rc = pack_latent_down(tm, T, D, LAT_EMB, B, tab, we_off, be_off)) return rc;
     // ---- the condition encoder, packed as the pose model's (the AE decoder is dead work at evaluation and is not read).  The fused
     // form runs cond_fast_body itself: its table is packed in every build, whatever cond_fast_kernel rows the library holds
     const bool fusable = cfg->t_cond == T && latent_encode_has_kernel(T, true);

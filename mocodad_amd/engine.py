@@ -617,6 +617,64 @@ class LatentScorer(_Scorer):
         return out
 
 
+class LatentReconstructor(_Scorer):
+    """One packed MoCoDADlatent model of stage 'pretrain' -- the bottleneck autoencoder -- on one GPU: mcd_pack_latent_ae_weights
+    and mcd_latent_reconstruct.
+
+    state_dict: the reference's keys ('model.*' with the up path and rev_to_time_dim, 'condition_encoder.*'; no 'denoiser.*').
+    The other arguments are LatentScorer's without hidden_sizes.  3 or 5 .. 12 corrupt frames, 1 .. 12 condition frames.  A call is
+    [condition encoder] -> encode -> [project] -> unproject -> decode; the workspace holds cond_emb, z0 and one
+    n_windows x 640 x corrupt-frames region (the encoder's last activation, then the decoder's first)."""
+
+    _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
+    _step_table = staticmethod(latent_step_table)
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
+                 cond_channels: Sequence[int] = (), latent_dim: int, cond_unet: bool = False, num_coords: int = 2, n_joints: int = 17,
+                 emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
+        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
+        self.latent_dim = int(latent_dim)
+        if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
+            raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
+        cfg = self._model_cfg("inject", len(self.corrupt_idx), len(self.cond_idx), cond_channels, cond_unet)
+        arr, n, keep = _pack_tensors(state_dict)
+        # sizes and tensor names are checked by the library before it touches a device: those errors need no GPU
+        have_gpu = torch.cuda.is_available()
+        self.device = torch.device(device if device is not None else (f"cuda:{torch.cuda.current_device()}" if have_gpu else "cuda:0"))
+        idx = self.device.index if self.device.index is not None else 0
+        handle = C.c_void_p()
+        _lib.check(self.L.mcd_pack_latent_ae_weights(arr, n, C.byref(cfg), self.latent_dim, idx, C.byref(handle)))
+        del keep
+        self._h = handle
+        self._set_options(options)
+
+    def reconstruct(self, data, z: Optional[torch.Tensor] = None, *, want_pose: bool = True, want_code: bool = False,
+                    loss_fn: str = "smooth_l1", noise_steps: int = 2):
+        """One pass of the autoencoder (mcd_latent_reconstruct) -> (pose (B,2,t_unet,17) | None, loss (B,), cond_emb (B,16),
+        z0 (B,D) | None).  z: (B,D) latents to decode in place of the windows' own codes (with the windows' own skips and
+        condition); z0 is the windows' own code either way.  loss: mean loss_fn(pose, corrupt frames) per window.  noise_steps
+        only sizes the step table, whose last row holds the constant time step -1.  Asynchronous on the current stream."""
+        data, view, B, keep = self._windows(data)
+        D, dev = self.latent_dim, self.device
+        if z is not None:
+            if z.dim() != 2 or tuple(z.shape) != (B, D):
+                raise ValueError(f"z must have shape ({B}, {D}), got {tuple(z.shape)}")
+            z = _f32c(z, dev)
+        pose = torch.empty(B, self.num_coords, len(self.corrupt_idx), self.n_joints, device=dev, dtype=torch.float32) if want_pose else None
+        loss = torch.empty(B, device=dev, dtype=torch.float32)
+        cond = torch.empty(B, self.emb_dim, device=dev, dtype=torch.float32)
+        code = torch.empty(B, D, device=dev, dtype=torch.float32) if want_code else None
+        cfg = self._score_cfg(B, 1, int(noise_steps), loss_fn)
+        with torch.cuda.device(dev):
+            ws = self._workspace(int(self.L.mcd_latent_workspace_bytes(self._h, B)))
+            if B:
+                _lib.check(self.L.mcd_latent_reconstruct(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
+                                                         _ptr(self.table(int(noise_steps))), _ptr(ws), _ptr(z), _ptr(pose), _ptr(loss),
+                                                         _ptr(cond), _ptr(code), _stream()))
+        del keep
+        return pose, loss, cond, code
+
+
 def _scaler_stats(center, scale, dev) -> list:
     """[center, scale] as (34,) float64 device tensors (the precision sklearn's transform runs in), or [] when both are None."""
     if (center is None) != (scale is None):

@@ -11,7 +11,8 @@ frames in front) for another channel list / h_dim.
 to_time_dim is one more launch between the encoder and the chain.
 
 Reference: models/mocodad_latent.py (forward :69-132), models/common/components.py:203-291 (Denoiser),
-models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` and training are outside the accelerated path.
+models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` is mocodad_latent_pretrain.MoCoDADlatentPretrain; training is outside
+the accelerated path.
 """
 import argparse
 from typing import List, Optional
@@ -69,7 +70,8 @@ class MoCoDADlatent(MoCoDAD):
         self.hidden_sizes = list(args.hidden_sizes)
         self.pretrained_model_ckpt_path = getattr(args, "pretrained_model_ckpt_path", None)
         if self.stage == "pretrain":
-            raise NotImplementedError("mocodad_amd scores the 'diffusion' stage of MoCoDADlatent; pretrain with the reference implementation")
+            raise NotImplementedError("MoCoDADlatent (mocodad_amd) is the 'diffusion' stage; a stage-1 checkpoint is evaluated by "
+                                      "mocodad_amd.models.mocodad_latent_pretrain.MoCoDADlatentPretrain (training: the reference implementation)")
         if self.stage != "diffusion":
             raise ValueError(f"Unknown stage {self.stage}")
         super().__init__(args)

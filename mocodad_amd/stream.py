@@ -798,6 +798,10 @@ class PoseStream:
                  clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False):
         from .engine import ClipRings, StreamRings
         from .utils.transforms import affine_table
+        if getattr(model, "is_pretrain", False):
+            raise NotImplementedError(f"PoseStream does not take {type(model).__name__}: the pretrain stage of the latent model "
+                                      "reconstructs poses and yields no anomaly score per window (score live streams with "
+                                      "MoCoDAD or the diffusion-stage MoCoDADlatent)")
         self.latent = bool(getattr(model, "is_latent", False))
         self.joint_scores = bool(joint_scores)
         if self.joint_scores and self.latent:

@@ -7,6 +7,8 @@
     python tools/latent_bench.py --split-encode                # the shipped configuration through the three-launch form
     python tools/latent_bench.py --corrupt-frames 12 --cond-frames 12     # seg_len 24: cond_fast_kernel + encode + projection + chain
                                                                # (default output: profiles/latent_bench_tx12.json)
+    python tools/latent_bench.py --stage pretrain --corrupt-frames 12 --cond-frames 12      # the autoencoder's call, mcd_latent_reconstruct
+                                                               # (default output: profiles/latent_recon_bench_tx12.json)
 
 Shipped configuration (configs/ubnormal_latent_test.yaml: D 64, hidden [64,128,128,64], noise_steps 10, 10 samples), seeded
 random-init weights, perf mode (in-kernel Philox), batch 1024 and a batch that fills the device.  Per batch, three legs alternate
@@ -17,6 +19,10 @@ inside one timed loop, each bracketed by device events:
                 same windows) -- the condition encoder and all 11 U-Net layers, against 7 here
 FLOPs are counted from the shapes (functions below), never copied.  Yardsticks of the chain launch: the MFMAs it issues at 32 cycles
 per SIMD each (v_mfma_f32_16x16x4_f32) on 256 CUs x 4 SIMDs at --clock-ghz, and the CPU restatement tests/latent_ref.py on 16 threads.
+--stage pretrain times mcd_latent_reconstruct (MoCoDADlatentPretrain) instead: the legs `reconstruct` (the whole call), `encode` (the
+diffusion stage's mcd_latent_encode on a model of the same frame split and latent size: the launches the two stages share, the
+yardstick) and their difference, the unproject + decode launches; the per-launch kernel averages come from a kernel trace of this
+command (rocprofv3 --kernel-trace --stats -- python tools/latent_bench.py --stage pretrain ...), not from this script.
 No GPU: fails (a CPU run says nothing about these times)."""
 import argparse
 import json
@@ -95,6 +101,59 @@ def timed(legs, reps, warmup):
     return {k: sorted(a.elapsed_time(b) for a, b in v) for k, v in ev.items()}
 
 
+def decoder_flops(T, D):
+    """rev_to_time_dim; the up path (layers 7 .. 10, up3, up2); the layers 0 .. 4 and down1 the decode launch runs again for the skips"""
+    up = sum(stgcn_flops(a, b, v, T) for a, b, v in UP) + 2 * 64 * T * 10 * 12 + 2 * 32 * T * 12 * 17
+    again = sum(stgcn_flops(a, b, v, T) for a, b, v in DOWN[:5]) + 2 * 32 * T * 17 * 12 + 2 * 64 * T * 12 * 10
+    return 2 * 64 * T * 10 * D, up, again
+
+
+def main_pretrain(a):
+    from mocodad_amd.models.mocodad_latent_pretrain import MoCoDADlatentPretrain
+    dev = torch.device("cuda:0")
+    Tc, Tx = int(a.cond_frames), int(a.corrupt_frames)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", f"latent_recon_bench_tx{Tx}.json")
+    cfgs = []
+    for name in ("ubnormal_latent_pretrain.yaml", "ubnormal_latent_test.yaml"):
+        cfg = load_config(os.path.join(ROOT, "configs", name))
+        if a.cond_arch:
+            cfg.conditioning_architecture = a.cond_arch
+        cfg.seg_len, cfg.conditioning_indices = Tc + Tx, list(range(Tc))
+        cfgs.append(cfg)
+    torch.manual_seed(0)
+    ae, lat = MoCoDADlatentPretrain(cfgs[0]).to(dev), MoCoDADlatent(cfgs[1]).to(dev)
+    sa, sl = ae.scorer(), lat.scorer()
+    D, T, ns = ae.latent_embedding_dim, ae.n_frames_corrupt, lat.noise_steps
+    assert D == lat.latent_embedding_dim
+    down_f, ttd_f = encoder_flops(T, D)
+    rev_f, up_f, again_f = decoder_flops(T, D)
+    cond_f = cond_flops(Tc, unet=cfgs[0].conditioning_architecture == "E_unet")
+    res = {"config": {"stage": "pretrain", "latent_dim": D, "frames": [T, Tc], "cond_arch": cfgs[0].conditioning_architecture,
+                      "launches_per_call": "[condition encoder] encode [project] unproject decode"},
+           "flops_per_window": {"condition_encoder": cond_f, "down_path": down_f, "to_time_dim": ttd_f, "rev_to_time_dim": rev_f,
+                                "up_path": up_f, "layers_0_4_again_for_the_skips": again_f,
+                                "total": cond_f + down_f + ttd_f + rev_f + up_f + again_f},
+           "bytes_per_window": {"H": 4 * 640 * T, "G": 4 * 640 * T, "skips_if_they_crossed_the_launch": 4 * (32 * T * 17 + 64 * T * 12)},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "batches": {}}
+    gen = torch.Generator().manual_seed(1)
+    for B in (a.batches or (1024,)):
+        data = torch.randn(B, 2, Tc + Tx, 17, generator=gen).clamp_(-3, 3).to(dev)
+        legs = {"reconstruct": lambda: sa.reconstruct(data), "reconstruct_loss_only": lambda: sa.reconstruct(data, want_pose=False),
+                "encode": lambda: sl.encode(data, noise_steps=ns)}
+        t = timed(legs, a.reps, a.warmup)
+        med = {k: v[len(v) // 2] for k, v in t.items()}
+        res["batches"][str(B)] = {
+            "ms_median": med, "ms_min": {k: v[0] for k, v in t.items()}, "ms_max": {k: v[-1] for k, v in t.items()},
+            "unproject_plus_decode_ms_derived": med["reconstruct"] - med["encode"], "windows_per_s": B / (med["reconstruct"] * 1e-3),
+            "reconstruct_gflops": B * res["flops_per_window"]["total"] / (med["reconstruct"] * 1e-3) / 1e9,
+            "reconstruct_over_encode": med["reconstruct"] / med["encode"]}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="default: profiles/latent_bench.json, profiles/latent_bench_tx<N>.json with --corrupt-frames N")
@@ -108,9 +167,12 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=None, help="window counts to time (default: 1024 and --fill-batch)")
     ap.add_argument("--split-encode", action="store_true", help="MCD_LATENT_OPT_SPLIT_ENCODE: the shipped configuration in three launches")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU restatement of the chain")
+    ap.add_argument("--stage", choices=["diffusion", "pretrain"], default="diffusion", help="pretrain: time mcd_latent_reconstruct")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("latent_bench.py needs an MI355X: nothing about these launches can be timed on a CPU")
+    if a.stage == "pretrain":
+        return main_pretrain(a)
     import latent_ref as R
     dev = torch.device("cuda:0")
     cfg = load_config(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml"))
