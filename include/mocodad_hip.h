@@ -643,6 +643,10 @@ int mcd_debug_poison_lds(void* stream);
 int mcd_debug_pack_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* latent_cfg,
                           int64_t* n_floats_out, uint64_t* digest_out);
 
+/* ... the same for the packer of mcd_pack_latent_ae_weights (the autoencoder of stage 'pretrain'). */
+int mcd_debug_pack_ae_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
+                             int64_t* n_floats_out, uint64_t* digest_out);
+
 const char* mcd_last_error(void);
 int32_t mcd_abi_version(void);
 

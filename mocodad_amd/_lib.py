@@ -78,6 +78,8 @@ _SIGS = {
     "mcd_debug_poison_lds": (C.c_int, [C.c_void_p]),
     "mcd_debug_pack_digest": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.POINTER(LatentCfg), C.POINTER(C.c_int64),
                                         C.POINTER(C.c_uint64)]),
+    "mcd_debug_pack_ae_digest": (C.c_int, [C.POINTER(Tensor), C.c_int32, C.POINTER(ModelCfg), C.c_int32, C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_uint64)]),
     "mcd_cond_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_score_workspace_bytes": (C.c_int64, [C.c_void_p, C.POINTER(ScoreCfg)]),

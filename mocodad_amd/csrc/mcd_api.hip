@@ -342,6 +342,17 @@ int mcd_debug_pack_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const 
     return MCD_OK;
 }
 
+int mcd_debug_pack_ae_digest(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
+                             int64_t* n_floats_out, uint64_t* digest_out) {
+    if (!tensors || !cfg || !n_floats_out || !digest_out) return fail(MCD_EINVAL, "null argument");
+    PackedModel m;
+    const int rc = pack_latent_ae_model(tensors, n_tensors, cfg, latent_dim, m);
+    if (rc != MCD_OK) return rc;
+    *n_floats_out = (int64_t)m.buf.size();
+    *digest_out = pack_digest(m);
+    return MCD_OK;
+}
+
 int mcd_set_option(mcd_weights_t* w, int32_t option, int32_t value) {
     if (!w) return fail(MCD_EINVAL, "null argument");
     if (option < 0 || option >= MCD_OPT_COUNT) return fail(MCD_EINVAL, "unknown option " + std::to_string(option));

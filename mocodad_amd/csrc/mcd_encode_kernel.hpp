@@ -1,8 +1,12 @@
 // mcd_encode_kernel.hpp — the encoder family: the MFMA condition encoders of the pose model, cond_fast_kernel<T, NB> (shipped
 // channel list) and cond_unet_kernel<T, NB> ('E_unet'), and the latent model's encode launch latent_encode_kernel<T, NB,
 // COND_IN_KERNEL, PROJECT_IN_KERNEL>, and the decode launch of its pretrain stage, latent_decode_kernel<T> (at the end of the file).
-// The first three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear over the (c,t,v) flattening; the shared pieces -- load_window_frames, unet_down_path, flatten_linear -- are stated here once
-// (DESIGN.md 2.1-2.2, 2.6).  cond_fast_body is also the trajectory kernel's prologue (score_kernel, P.cond_inkernel).
+// The first three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear over the (c,t,v) flattening;
+// the decode launch is the same loader and the same down stem, capturing the skips, in front of the up path.  The shared pieces are
+// stated here once: load_window_frames (all four), unet_down_stem (the 'E_unet' encoder, the encode and the decode launch; with layer
+// 5 it is unet_down_path), step_embedding (the encode and the decode launch), flatten_linear (the two encoders' tails)
+// (DESIGN.md 2.1-2.2, 2.6).  cond_fast_body, also the trajectory kernel's prologue (score_kernel, P.cond_inkernel), keeps its own
+// loader and tail.
 #pragma once
 #include "mcd_device.hpp"
 #include "mcd_latent.hpp"
@@ -76,35 +80,76 @@ __device__ __forceinline__ void load_window_frames(float* dst, const DataView& d
     }
 }
 
-// The U-Net's down path 2->16->32->32 | 17->12 | 32->64->64 | 12->10 | 64->128 on Plan<T, NB> (layers 0 .. 5 and the two
-// non-capturing down-samplers, each with its barrier), input at RG + L0_in, output at RG + L5_out.  tab: the layer table (layer l
-// at l * F_STRIDE); rs: the table words, relative to wb, of down1 / down2's fragments and biases.  HASEMB: the embedding
-// EMB + emb_off(l) is added in each layer's GEMM epilogue as in score_kernel.  The last layer differs per kernel: the caller's.
+// The U-Net's down stem 2->16->32->32 | 17->12 | 32->64->64 | 12->10 on Plan<T, NB> (layers 0 .. 4 and the two down-samplers, each
+// with its barrier), input at RG + L0_in, output at RG + DN2_out.  tab: the layer table (layer l at l * F_STRIDE); rs: the table
+// words, relative to wb, of down1 / down2's fragments and biases.  HASEMB: the embedding EMB + emb_off(l) is added in each layer's
+// GEMM epilogue as in score_kernel.  CAPTURE: the down-samplers keep their B operands -- the skip tensors d1 / d2 -- in the caller's
+// skip1 / skip2 (resample_stage; rs then names fragments in the capture k order); without it the two arrays are not touched.
 struct RsWords { int w1, b1, w2, b2; };
-template <int T, int NB, bool HASEMB>
-__device__ __forceinline__ void unet_down_path(const float* wb, const float* tab, const RsWords rs, float* RG, const float* EMB,
-                                               int wave, int lane, Prof& prof) {
+template <int T, int NB, bool HASEMB, bool CAPTURE, int NS1, int NS2>
+__device__ __forceinline__ void unet_down_stem(const float* wb, const float* tab, const RsWords rs, float* RG, const float* EMB,
+                                               float (&skip1)[NS1], float (&skip2)[NS2], int wave, int lane, Prof& prof) {
     using PL = Plan<T, NB>;
     auto emb = [&](int l) { return HASEMB ? EMB + emb_off(l) : nullptr; };
-    float nosk[1] = {0.f};
     layer_generic<16, 16, 17, true, HASEMB, T, NB>(wb, layer_w(tab, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, emb(0), wave, lane, prof, 0);
     layer_generic<16, 32, 17, true, HASEMB, T, NB>(wb, layer_w(tab, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, emb(1), wave, lane, prof, 0);
     layer_generic<32, 32, 17, false, HASEMB, T, NB>(wb, layer_w(tab, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, emb(2), wave, lane, prof, 0);
     {
-        RsCoef<32, 17, 12, T, NB, false> rc;
+        RsCoef<32, 17, 12, T, NB, CAPTURE> rc;
         rc.load(wb + tab_i(wb, rs.w1), wb + tab_i(wb, rs.b1), lane);
-        resample_stage<32, 17, 12, T, NB, false, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, nosk, wave, lane);
+        resample_stage<32, 17, 12, T, NB, CAPTURE, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, skip1, wave, lane);
         __syncthreads();
     }
     layer_generic<32, 64, 12, true, HASEMB, T, NB>(wb, layer_w(tab, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, emb(3), wave, lane, prof, 0);
     layer_generic<64, 64, 12, false, HASEMB, T, NB>(wb, layer_w(tab, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, emb(4), wave, lane, prof, 0);
     {
-        RsCoef<64, 12, 10, T, NB, false> rc;
+        RsCoef<64, 12, 10, T, NB, CAPTURE> rc;
         rc.load(wb + tab_i(wb, rs.w2), wb + tab_i(wb, rs.b2), lane);
-        resample_stage<64, 12, 10, T, NB, false, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, nosk, wave, lane);
+        resample_stage<64, 12, 10, T, NB, CAPTURE, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, skip2, wave, lane);
         __syncthreads();
     }
-    layer_generic<64, 128, 10, true, HASEMB, T, NB>(wb, layer_w(tab, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, emb(5), wave, lane, prof, 0);
+}
+// The down path of the encoders: the stem without capture, then 64->128 (layer 5), output at RG + L5_out.  The last layer differs
+// per kernel: the caller's.
+template <int T, int NB, bool HASEMB>
+__device__ __forceinline__ void unet_down_path(const float* wb, const float* tab, const RsWords rs, float* RG, const float* EMB,
+                                               int wave, int lane, Prof& prof) {
+    using PL = Plan<T, NB>;
+    float nosk[1] = {0.f};
+    unet_down_stem<T, NB, HASEMB, false>(wb, tab, rs, RG, EMB, nosk, nosk, wave, lane, prof);
+    layer_generic<64, 128, 10, true, HASEMB, T, NB>(wb, layer_w(tab, 5), RG + PL::L5_in, RG + PL::L5_z, RG + PL::L5_out, HASEMB ? EMB + emb_off(5) : nullptr, wave, lane, prof, 0);
+}
+
+// The step embedding of the latent U-Net at its constant time step: SEN[n][16] = SiLU(pe_row + ce[n]) for the workgroup's NB
+// windows (solo >= 0: the other slots hold zeros, so that their rows are the bias alone), then rows [0, n_rows) of W_e / b_e:
+// EMB[n * stride + o] = b_e[o] + sum_k W_e[o][k] SEN[n][k], one fmaf chain from the bias, k = 0 .. 15.  The barrier between
+// the two halves is also the one behind the caller's clearing of its region (in front of the call: the window is loaded behind it);
+// the rows are published by the caller's next barrier.  (With the caller's clearing and loading handed in as a callback between the
+// halves -- the order the two kernels had -- latent_encode_kernel<3, 2, true, true> spilled 13 SGPRs where it spills 3, and its
+// launch left the bar by 1 %: profiles/README.md, "Latent family".)
+template <int NB>
+__device__ __forceinline__ void step_embedding(const float* wb, const float* __restrict__ pe_row, const float* ce, float* SEN, float* EMB,
+                                               int stride, int n_rows, int tid, int solo) {
+    if (tid < NB * EDIM) {
+        const float e = pe_row[tid % EDIM] + ce[tid];
+        SEN[tid] = (solo >= 0 && tid / EDIM != solo) ? 0.f : e / (1.f + expf(-e));
+    }
+    __syncthreads();
+    gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
+    gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
+    for (int o = tid; o < n_rows; o += NTHREADS) {
+        float w[EDIM];
+#pragma unroll
+        for (int k = 0; k < EDIM; ++k) w[k] = we[o * EDIM + k];
+        const float bo = be[o];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            float a = bo;
+#pragma unroll
+            for (int k = 0; k < EDIM; ++k) a = fmaf(w[k], SEN[n * EDIM + k], a);
+            EMB[n * stride + o] = a;
+        }
+    }
 }
 
 // Linear over the (c, tv) flattening of H[(n TV + tv) CS + c]: out[n][j] = bias[j] + sum_k W[j][k] H[n][k], k = c TV + tv, for the
@@ -352,30 +397,9 @@ __device__ __forceinline__ void latent_down_pass(const float* wbuf, const DataVi
     prof.off();
     const float* wb = wbuf;
     if constexpr (OPAQUE) asm volatile("" : "+s"(wb));
-    if (tid < NB * EDIM) {
-        const float e = pe_row[tid % EDIM] + CE[tid];
-        SEN[tid] = (solo >= 0 && tid / EDIM != solo) ? 0.f : e / (1.f + expf(-e));
-    }
     for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
-    __syncthreads();
+    step_embedding<NB>(wb, pe_row, CE, SEN, EMB, EMB_STRIDE, LAT_EMB, tid, solo);
     load_window_frames<T, NB, OPAQUE>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b0, B, solo);
-    {
-        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
-        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
-        for (int o = tid; o < LAT_EMB; o += NTHREADS) {
-            float w[EDIM];
-#pragma unroll
-            for (int k = 0; k < EDIM; ++k) w[k] = we[o * EDIM + k];
-            const float bo = be[o];
-#pragma unroll
-            for (int n = 0; n < NB; ++n) {
-                float a = bo;
-#pragma unroll
-                for (int k = 0; k < EDIM; ++k) a = fmaf(w[k], SEN[n * EDIM + k], a);
-                EMB[n * EMB_STRIDE + o] = a;
-            }
-        }
-    }
     __syncthreads();
     unet_down_path<T, NB, true>(wb, wb, RsWords{TAB_RSW + 0, TAB_RSB + 0, TAB_RSW + 1, TAB_RSB + 1}, RG, EMB, wave, lane, prof);
     constexpr int F = LAT_ENC_C * TV10;
@@ -502,45 +526,17 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float*
     Prof prof;
     prof.off();
     const float* wb = wbuf;
-    if (tid < EDIM) {
-        const float e = pe_row[tid] + cond[(size_t)b * EDIM + tid];
-        SEN[tid] = e / (1.f + expf(-e));
-    }
+    // the rows of all eleven layers, as latent_down_pass forms its 400
     for (int u = tid; u < LD::WORK + LD::EMB; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
-    __syncthreads();
+    step_embedding<1>(wb, pe_row, cond + (size_t)b * EDIM, SEN, EMB, 0, emb_off(10) + C0, tid, -1);
     load_window_frames<T, 1>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b, B);
-    {
-        gfloat* we = as_global(wb + tab_i(wb, TAB_WE));
-        gfloat* be = as_global(wb + tab_i(wb, TAB_BE));
-        for (int o = tid; o < emb_off(10) + C0; o += NTHREADS) {      // the rows of all eleven layers, as latent_down_pass forms its 400
-            float a = be[o];
-#pragma unroll
-            for (int k = 0; k < EDIM; ++k) a = fmaf(we[o * EDIM + k], SEN[k], a);
-            EMB[o] = a;
-        }
-    }
     __syncthreads();
-    // ---- layers 0 .. 4 once more, for the skips: d1 = layer 2's output, d2 = layer 4's, captured by the down-samplers' B reads
+    // ---- the down stem once more, for the skips: d1 = layer 2's output, d2 = layer 4's, captured by the down-samplers' B reads.
+    // (down2's own output is not needed -- layers 5, 6 and the bottleneck ran in the launches before -- the stage is there for its reads)
     float skip1[RsCfg<32, 17, 12, T, 1, true>::PER * RsCfg<32, 17, 12, T, 1, true>::SK];
     float skip2[RsCfg<64, 12, 10, T, 1, true>::PER * RsCfg<64, 12, 10, T, 1, true>::SK];
-    layer_generic<16, 16, 17, true, true, T, 1>(wb, layer_w(wb, 0), RG + PL::L0_in, RG + PL::L0_z, RG + PL::L0_out, EMB + emb_off(0), wave, lane, prof, 0);
-    layer_generic<16, 32, 17, true, true, T, 1>(wb, layer_w(wb, 1), RG + PL::L1_in, RG + PL::L1_z, RG + PL::L1_out, EMB + emb_off(1), wave, lane, prof, 0);
-    layer_generic<32, 32, 17, false, true, T, 1>(wb, layer_w(wb, 2), RG + PL::L2_in, RG + PL::L2_z, RG + PL::L2_out, EMB + emb_off(2), wave, lane, prof, 0);
-    {
-        RsCoef<32, 17, 12, T, 1, true> rc;
-        rc.load(wb + tab_i(wb, TAB_LAT_CAPW + 0), wb + tab_i(wb, TAB_LAT_CAPB + 0), lane);
-        resample_stage<32, 17, 12, T, 1, true, false>(RG + PL::L2_out, 36, RG + PL::DN1_out, 36, rc, skip1, wave, lane);
-        __syncthreads();
-    }
-    layer_generic<32, 64, 12, true, true, T, 1>(wb, layer_w(wb, 3), RG + PL::L3_in, RG + PL::L3_z, RG + PL::L3_out, EMB + emb_off(3), wave, lane, prof, 0);
-    layer_generic<64, 64, 12, false, true, T, 1>(wb, layer_w(wb, 4), RG + PL::L4_in, RG + PL::L4_z, RG + PL::L4_out, EMB + emb_off(4), wave, lane, prof, 0);
-    {
-        // (down2's own output is not needed -- layers 5, 6 and the bottleneck ran in the launches before -- the stage is here for its reads)
-        RsCoef<64, 12, 10, T, 1, true> rc;
-        rc.load(wb + tab_i(wb, TAB_LAT_CAPW + 1), wb + tab_i(wb, TAB_LAT_CAPB + 1), lane);
-        resample_stage<64, 12, 10, T, 1, true, false>(RG + PL::L4_out, 68, RG + PL::DN2_out, 68, rc, skip2, wave, lane);
-        __syncthreads();
-    }
+    unet_down_stem<T, 1, true, true>(wb, wb, RsWords{TAB_LAT_CAPW + 0, TAB_LAT_CAPB + 0, TAB_LAT_CAPW + 1, TAB_LAT_CAPB + 1}, RG, EMB,
+                                     skip1, skip2, wave, lane, prof);
     // ---- G -> [P10][68]; the pad rows behind the last frame hold zeros (up3's trailing k-step reads two rows past a frame)
     for (int u = tid; u < PL::P10 * 16; u += NTHREADS) {
         const int col = u >> 4, q = u & 15;

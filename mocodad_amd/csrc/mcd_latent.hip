@@ -18,7 +18,8 @@ namespace mcd {
 static_assert(MCD_LATENT_UNIT >= 0 && MCD_LATENT_UNIT <= MCD_LATENT_UNITS, "compile with -DMCD_LATENT_UNIT=<n>, n = 1 .. MCD_LATENT_UNITS, or without");
 
 // MCD_LATENT_ENCODE_INSTANCES (mcd_instances.hpp): X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL).  A developer build holds the
-// 3-frame rows and the row of its frame count, in unit 0.
+// 3-frame rows and the row of its frame count, in unit 0.  (That rule compares a row's T with MCD_FAST_T, a value: the token-pasting
+// probe MCD_IN_UNIT of mcd_inst.hip cannot state it, so the rows reach their unit through one held-here / not-here template.)
 #ifdef MCD_FAST_T
 constexpr bool latent_row_held(int t) { return t == 3 || t == MCD_FAST_T; }
 constexpr int latent_row_unit(int) { return 0; }
@@ -27,90 +28,75 @@ constexpr bool latent_row_held(int) { return true; }
 constexpr int latent_row_unit(int unit) { return unit; }
 #endif
 
-struct LatentEncodeArgs {
-    const float* wbuf; const DataView& dv; const FrameIdx& cond_fi; const FrameIdx& fi; int seg_len; const float* pe_row;
-    float* cond_out; float* out; int D, B; hipStream_t st;
-};
-
+// A row of a table: its argument struct, which calls it serves, its launch.  Only launch() names the kernel, and only the unit that
+// holds the row calls it (RowIn below).
 template <int T, int NB, bool CI, bool PIK>
-static int launch_latent_encode_t(const LatentEncodeArgs& a) {
-    static_assert(NWAVES == 8, "the latent encode launch ships with eight waves per workgroup");
-    static_assert(PIK || !CI, "the rows that project in a launch of their own take cond_emb from a launch of its own as well");
-    constexpr size_t lds = (size_t)LatentEncLds<T, NB, PIK>::FLOATS * 4;
-    static_assert(lds <= 160 * 1024, "latent encode: more than 160 KB of LDS");
-    LDS_LIMIT((&latent_encode_kernel<T, NB, CI, PIK>), lds);
-    hipLaunchKernelGGL((latent_encode_kernel<T, NB, CI, PIK>), dim3((a.B + NB - 1) / NB), dim3(NTHREADS), lds, a.st, a.wbuf, a.dv, a.cond_fi, a.fi,
-                       a.seg_len, a.pe_row, a.cond_out, a.out, a.D, a.B);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
+struct EncodeRow {
+    using Args = LatentEncodeArgs;
+    static bool serves(int t, const Args& a) { return t == T && a.cond_in_kernel == CI; }
+    static int launch(const Args& a) {
+        static_assert(NWAVES == 8, "the latent encode launch ships with eight waves per workgroup");
+        static_assert(PIK || !CI, "the rows that project in a launch of their own take cond_emb from a launch of its own as well");
+        constexpr size_t lds = (size_t)LatentEncLds<T, NB, PIK>::FLOATS * 4;
+        static_assert(lds <= 160 * 1024, "latent encode: more than 160 KB of LDS");
+        LDS_LIMIT((&latent_encode_kernel<T, NB, CI, PIK>), lds);
+        hipLaunchKernelGGL((latent_encode_kernel<T, NB, CI, PIK>), dim3((a.B + NB - 1) / NB), dim3(NTHREADS), lds, a.st, a.wbuf, a.call.dv, a.call.cond_fi,
+                           a.call.fi, a.call.seg_len, a.call.pe_row, a.cond_out, a.out, a.D, a.B);
+        HIP_TRY(hipGetLastError());
+        return MCD_OK;
+    }
+};
+// MCD_LATENT_DECODE_INSTANCES (mcd_instances.hpp): X(unit, T), the decode launch of the autoencoder
+template <int T>
+struct DecodeRow {
+    using Args = LatentDecodeArgs;
+    static bool serves(int t, const Args&) { return t == T; }
+    static int launch(const Args& a) {
+        static_assert(NWAVES == 8, "the latent decode launch ships with eight waves per workgroup");
+        constexpr size_t lds = (size_t)LatentDecLds<T>::FLOATS * 4;
+        static_assert(lds <= 160 * 1024, "latent decode: more than 160 KB of LDS");
+        LDS_LIMIT((&latent_decode_kernel<T>), lds);
+        hipLaunchKernelGGL((latent_decode_kernel<T>), dim3(a.B), dim3(NTHREADS), lds, a.st, a.wbuf, a.call.dv, a.call.fi, a.call.seg_len, a.call.pe_row,
+                           a.cond, a.G, a.pose_out, a.loss_out, a.loss_fn, a.B);
+        HIP_TRY(hipGetLastError());
+        return MCD_OK;
+    }
+};
+// both tables as MCD_ROW(unit, T, row type)
+#define MCD_ENCODE_ROW(unit, T, NB, CI, PIK) MCD_ROW(unit, T, EncodeRow<T, NB, CI, PIK>)
+#define MCD_DECODE_ROW(unit, T) MCD_ROW(unit, T, DecodeRow<T>)
 
 // a row's launcher in the unit that holds the row; elsewhere nothing of it is instantiated
-template <bool HERE, int T, int NB, bool CI, bool PIK>
-struct LatentRow {
-    static int go(const LatentEncodeArgs& a) { return launch_latent_encode_t<T, NB, CI, PIK>(a); }
+template <bool HERE, class Row>
+struct RowIn {
+    static int go(const typename Row::Args& a) { return Row::launch(a); }
 };
-template <int T, int NB, bool CI, bool PIK>
-struct LatentRow<false, T, NB, CI, PIK> {
-    static int go(const LatentEncodeArgs&) { return fail(MCD_EUNSUPPORTED, "latent encode: the row is not part of this unit"); }
+template <class Row>
+struct RowIn<false, Row> {
+    static int go(const typename Row::Args&) { return fail(MCD_EUNSUPPORTED, "latent launch: the row is not part of this unit"); }
 };
 
-// the dispatch over the rows of unit U: defined by the translation unit compiled as that unit
-template <int U>
-int launch_latent_encode_unit(int t, bool cond_in_kernel, const LatentEncodeArgs& a);
-#define MCD_ROW(unit, T, NB, CI, PIK) template <> int launch_latent_encode_unit<latent_row_unit(unit)>(int, bool, const LatentEncodeArgs&);
-MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
+// the dispatch over the rows of unit U that take Args: defined by the translation unit compiled as that unit
+template <int U, class Args>
+int launch_latent_unit(int t, const Args& a);
+#define MCD_ROW(unit, T, ...) template <> int launch_latent_unit<latent_row_unit(unit), __VA_ARGS__::Args>(int, const __VA_ARGS__::Args&);
+MCD_LATENT_ENCODE_INSTANCES(MCD_ENCODE_ROW)
+MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
 #undef MCD_ROW
 
+#define MCD_ROW(unit, T, ...) \
+    if (__VA_ARGS__::serves(t, a)) return RowIn<latent_row_held(T) && latent_row_unit(unit) == MCD_LATENT_UNIT, __VA_ARGS__>::go(a);
 template <>
-int launch_latent_encode_unit<MCD_LATENT_UNIT>(int t, bool cond_in_kernel, const LatentEncodeArgs& a) {
-#define MCD_ROW(unit, T, NB, CI, PIK) \
-    if (t == (T) && cond_in_kernel == (CI)) return LatentRow<latent_row_held(T) && latent_row_unit(unit) == MCD_LATENT_UNIT, T, NB, CI, PIK>::go(a);
-    MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
-#undef MCD_ROW
+int launch_latent_unit<MCD_LATENT_UNIT, LatentEncodeArgs>(int t, const LatentEncodeArgs& a) {
+    MCD_LATENT_ENCODE_INSTANCES(MCD_ENCODE_ROW)
     return fail(MCD_EUNSUPPORTED, "latent encode: no such row");
 }
-
-// MCD_LATENT_DECODE_INSTANCES (mcd_instances.hpp): X(unit, T), the decode launch of the autoencoder, dispatched like the encode rows
-struct LatentDecodeArgs {
-    const float* wbuf; const DataView& dv; const FrameIdx& fi; int seg_len; const float* pe_row; const float* cond; const float* G;
-    float* pose_out; float* loss_out; int loss_fn, B; hipStream_t st;
-};
-
-template <int T>
-static int launch_latent_decode_t(const LatentDecodeArgs& a) {
-    static_assert(NWAVES == 8, "the latent decode launch ships with eight waves per workgroup");
-    constexpr size_t lds = (size_t)LatentDecLds<T>::FLOATS * 4;
-    static_assert(lds <= 160 * 1024, "latent decode: more than 160 KB of LDS");
-    LDS_LIMIT((&latent_decode_kernel<T>), lds);
-    hipLaunchKernelGGL((latent_decode_kernel<T>), dim3(a.B), dim3(NTHREADS), lds, a.st, a.wbuf, a.dv, a.fi, a.seg_len, a.pe_row, a.cond, a.G,
-                       a.pose_out, a.loss_out, a.loss_fn, a.B);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
-}
-
-template <bool HERE, int T>
-struct LatentDecodeRow {
-    static int go(const LatentDecodeArgs& a) { return launch_latent_decode_t<T>(a); }
-};
-template <int T>
-struct LatentDecodeRow<false, T> {
-    static int go(const LatentDecodeArgs&) { return fail(MCD_EUNSUPPORTED, "latent decode: the row is not part of this unit"); }
-};
-
-template <int U>
-int launch_latent_decode_unit(int t, const LatentDecodeArgs& a);
-#define MCD_ROW(unit, T) template <> int launch_latent_decode_unit<latent_row_unit(unit)>(int, const LatentDecodeArgs&);
-MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
-#undef MCD_ROW
-
 template <>
-int launch_latent_decode_unit<MCD_LATENT_UNIT>(int t, const LatentDecodeArgs& a) {
-#define MCD_ROW(unit, T) if (t == (T)) return LatentDecodeRow<latent_row_held(T) && latent_row_unit(unit) == MCD_LATENT_UNIT, T>::go(a);
-    MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
-#undef MCD_ROW
+int launch_latent_unit<MCD_LATENT_UNIT, LatentDecodeArgs>(int t, const LatentDecodeArgs& a) {
+    MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
     return fail(MCD_EUNSUPPORTED, "latent decode: no such row");
 }
+#undef MCD_ROW
 
 #if MCD_LATENT_UNIT == 0
 
@@ -119,15 +105,6 @@ bool latent_decode_has_kernel(int t) {
     MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
 #undef MCD_ROW
     return false;
-}
-
-int launch_latent_decode(int t, const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len, const float* pe_row,
-                         const float* cond, const float* G, float* pose_out, float* loss_out, int loss_fn, int B, hipStream_t st) {
-    const LatentDecodeArgs a{wbuf, dv, fi, seg_len, pe_row, cond, G, pose_out, loss_out, loss_fn, B, st};
-#define MCD_ROW(unit, T) if (latent_row_held(T) && t == (T)) return launch_latent_decode_unit<latent_row_unit(unit)>(t, a);
-    MCD_LATENT_DECODE_INSTANCES(MCD_ROW)
-#undef MCD_ROW
-    return fail(MCD_EUNSUPPORTED, "the latent decode launch has no kernel for " + std::to_string(t) + " frames");
 }
 
 int launch_latent_unproject(int t, const float* wbuf, const float* z, float* G, int D, int B, hipStream_t st) {
@@ -158,15 +135,19 @@ std::string latent_encode_counts() {
     return s;
 }
 
-int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
-                         int seg_len, const float* pe_row, float* cond_out, float* out, int D, int B, hipStream_t st) {
-    const LatentEncodeArgs a{wbuf, dv, cond_fi, fi, seg_len, pe_row, cond_out, out, D, B, st};
-#define MCD_ROW(unit, T, NB, CI, PIK) \
-    if (latent_row_held(T) && t == (T) && cond_in_kernel == (CI)) return launch_latent_encode_unit<latent_row_unit(unit)>(t, cond_in_kernel, a);
-    MCD_LATENT_ENCODE_INSTANCES(MCD_ROW)
-#undef MCD_ROW
+// the outer dispatch: a row this library holds -> the unit that holds it
+#define MCD_ROW(unit, T, ...) \
+    if (latent_row_held(T) && __VA_ARGS__::serves(t, a)) return launch_latent_unit<latent_row_unit(unit), __VA_ARGS__::Args>(t, a);
+int launch_latent_decode(int t, const LatentDecodeArgs& a) {
+    MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
+    return fail(MCD_EUNSUPPORTED, "the latent decode launch has no kernel for " + std::to_string(t) + " frames");
+}
+
+int launch_latent_encode(int t, const LatentEncodeArgs& a) {
+    MCD_LATENT_ENCODE_INSTANCES(MCD_ENCODE_ROW)
     return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(t) + " frames (instantiated: " + latent_encode_counts() + " corrupt frames)");
 }
+#undef MCD_ROW
 
 int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_out, int D, int B, hipStream_t st) {
     hipLaunchKernelGGL(latent_project_kernel, dim3((B + PROJ_NC - 1) / PROJ_NC, D / 16), dim3(PROJ_THREADS), 0, st, wbuf, H, z0_out,

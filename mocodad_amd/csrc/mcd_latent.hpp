@@ -67,9 +67,12 @@ constexpr int TAB_LAT_RW = 106, TAB_LAT_RB = 107;
 bool latent_encode_has_kernel(int t, bool cond_in_kernel);
 bool latent_project_in_kernel(int t);
 std::string latent_encode_counts();
+// What a latent call derives from its cfg, view and step table, once (latent_call of mcd_latent_api.hpp), for the encode launches
+// and the decode launch: the window view, the condition / corrupt frame lists, the table's row of the constant time step -1
+struct LatentCall { DataView dv; FrameIdx cond_fi, fi; int seg_len; const float* pe_row; };
 // cond_in_kernel = false: cond_out already holds cond_emb (B,16).  out: z0 (B,D), or H (B, 640 t) for a row that does not project
-int launch_latent_encode(int t, bool cond_in_kernel, const float* wbuf, const DataView& dv, const FrameIdx& cond_fi, const FrameIdx& fi,
-                         int seg_len, const float* pe_row, float* cond_out, float* out, int D, int B, hipStream_t st);
+struct LatentEncodeArgs { const float* wbuf; const LatentCall& call; bool cond_in_kernel; float* cond_out; float* out; int D, B; hipStream_t st; };
+int launch_latent_encode(int t, const LatentEncodeArgs& a);
 // H (B, 640 t) -> z0 (B,D): to_time_dim of the rows with PROJECT_IN_KERNEL = false
 int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_out, int D, int B, hipStream_t st);
 // The autoencoder's decoder half (mcd_latent_reconstruct).  z (B,D) -> G (B, 640 t) = rev_to_time_dim(z), in H's order
@@ -77,8 +80,8 @@ int launch_latent_unproject(int t, const float* wbuf, const float* z, float* G, 
 // is there a decode kernel for t corrupt frames (MCD_LATENT_DECODE_INSTANCES)
 bool latent_decode_has_kernel(int t);
 // G + the window's corrupt frames and cond_emb -> pose (B,2,t,17) and / or the window's mean loss against its corrupt frames (B)
-int launch_latent_decode(int t, const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len, const float* pe_row,
-                         const float* cond, const float* G, float* pose_out, float* loss_out, int loss_fn, int B, hipStream_t st);
+struct LatentDecodeArgs { const float* wbuf; const LatentCall& call; const float* cond; const float* G; float* pose_out; float* loss_out; int loss_fn, B; hipStream_t st; };
+int launch_latent_decode(int t, const LatentDecodeArgs& a);
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
 int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
 

@@ -28,37 +28,68 @@ using namespace mcd;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// gather / plain / hbuf: the scratch regions of latent_workspace() (null where the handle's route has none)
-int latent_encode_impl(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
-                       const float* step_table, float* cond_out, float* z0_out, float* gather, float* plain, float* hbuf, hipStream_t st) {
-    DataView dv;
-    if (int rc = window_view(data, view, cfg->seg_len, dv)) return rc;
+// The regions of a latent call's workspace (latent_workspace) from its base pointer: cond_emb, z0, the plain encoder's gather and
+// third buffer, H / G.  origin: the layout offset `base` stands for (mcd_latent_encode allocates the part from `gather` on); a
+// region in front of it, or any region of a null base, is null.
+struct LatentRegions { float *cond, *z0, *gather, *plain, *h; };
+LatentRegions latent_regions(void* base, const LatentWorkspace& lay, int64_t origin = 0) {
+    auto at = [&](int64_t off) { return base && off >= origin ? reinterpret_cast<float*>(static_cast<char*>(base) + (off - origin)) : nullptr; };
+    return {at(0), at(lay.z0), at(lay.gather), at(lay.plain), at(lay.h)};
+}
+
+// cfg, view and step_table of a call against the handle -> what the launches take
+int latent_call(const mcd_latent_weights* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                const float* step_table, LatentCall& c) {
+    if (int rc = window_view(data, view, cfg->seg_len, c.dv)) return rc;
     if (cfg->n_corrupt != w->cfg.t_unet || cfg->n_cond != w->cfg.t_cond) return fail(MCD_EINVAL, "frame split does not match the packed model (t_unet / t_cond)");
     if (int rc = check_frame_partition(cfg)) return rc;
     if (int rc = check_frame_lists(cfg)) return rc;
-    FrameIdx cond_fi, fi;
-    memset(&cond_fi, 0, sizeof(cond_fi));
-    memset(&fi, 0, sizeof(fi));
-    for (int k = 0; k < cfg->n_cond; ++k) cond_fi.idx[k] = cfg->cond_idx[k];
-    for (int k = 0; k < cfg->n_corrupt; ++k) fi.idx[k] = cfg->corrupt_idx[k];
+    memset(&c.cond_fi, 0, sizeof(c.cond_fi));
+    memset(&c.fi, 0, sizeof(c.fi));
+    for (int k = 0; k < cfg->n_cond; ++k) c.cond_fi.idx[k] = cfg->cond_idx[k];
+    for (int k = 0; k < cfg->n_corrupt; ++k) c.fi.idx[k] = cfg->corrupt_idx[k];
+    c.seg_len = cfg->seg_len;
     // row ns of the table: the constant time step -1 the encoder is given (mocodad_latent.py:95)
-    const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
-    const int B = cfg->n_windows;
+    c.pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
+    return MCD_OK;
+}
+
+// [condition encoder] -> encode -> [project]: cond_emb (B,16) and z0 (B,D) of B windows.  R: the scratch regions gather / plain / h
+// (null where the handle's route has none)
+int latent_encode_impl(const mcd_latent_weights* w, const LatentCall& c, int B, float* cond_out, float* z0_out, const LatentRegions& R,
+                       hipStream_t st) {
     // the pose model's routes: in the encode launch (shipped encoder at t_cond = t_unet), or a launch of its own in front of it
     const CondRoute route = cond_route(&w->cw, w->fused_ok && !w->opt[MCD_LATENT_OPT_SPLIT_ENCODE]);
     const bool plain_route = route == COND_PLAIN || route == COND_PLAIN_SCRATCH;
     if (route != COND_INKERNEL && route != COND_FAST && route != COND_UNET && !plain_route)      // (a developer build without the frame count)
         return fail(MCD_EUNSUPPORTED, "E_unet condition encoder: frame count not instantiated");
-    if (plain_route && !gather) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
+    if (plain_route && !R.gather) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this condition encoder");
     if (route != COND_INKERNEL)
-        if (int rc = launch_cond(&w->cw, route, dv, cond_fi, cfg->seg_len, cond_out, B, gather, plain, st)) return rc;
-    if (!w->h_floats)
-        return launch_latent_encode(w->cfg.t_unet, route == COND_INKERNEL, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, z0_out, w->net.D,
-                                    B, st);
+        if (int rc = launch_cond(&w->cw, route, c.dv, c.cond_fi, c.seg_len, cond_out, B, R.gather, R.plain, st)) return rc;
+    if (!w->h_floats) return launch_latent_encode(w->cfg.t_unet, {w->dbuf, c, route == COND_INKERNEL, cond_out, z0_out, w->net.D, B, st});
     // 5 .. 12 corrupt frames: the encode launch leaves H, one projection launch computes every window's z0
-    if (!hbuf) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this frame count");
-    if (int rc = launch_latent_encode(w->cfg.t_unet, false, w->dbuf, dv, cond_fi, fi, cfg->seg_len, pe_row, cond_out, hbuf, w->net.D, B, st)) return rc;
-    return launch_latent_project(w->cfg.t_unet, w->dbuf, hbuf, z0_out, w->net.D, B, st);
+    if (!R.h) return fail(MCD_EINVAL, "workspace required (mcd_latent_workspace_bytes) for this frame count");
+    if (int rc = launch_latent_encode(w->cfg.t_unet, {w->dbuf, c, false, cond_out, R.h, w->net.D, B, st})) return rc;
+    return launch_latent_project(w->cfg.t_unet, w->dbuf, R.h, z0_out, w->net.D, B, st);
+}
+
+// a packer's result (rc, m) -> the uploaded handle; ae: the autoencoder's kind
+int make_latent_weights(int rc, const PackedModel& m, const mcd_model_cfg_t* cfg, int32_t device, bool ae, mcd_latent_weights_t** out) {
+    if (rc != MCD_OK) return rc;
+    float* dbuf = nullptr;
+    rc = upload_packed(m.buf, device, &dbuf);
+    if (rc != MCD_OK) return rc;
+    mcd_latent_weights* w = new mcd_latent_weights();
+    w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
+    memset(w->opt, 0, sizeof(w->opt));
+    w->fused_ok = m.fused_ok != 0;
+    w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
+    w->ae = ae; w->g_floats = ae ? LAT_ENC_C * cfg->t_unet * 10 : 0;
+    w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
+    memset(w->cw.opt, 0, sizeof(w->cw.opt));
+    set_cond_weights(&w->cw, m, dbuf);
+    *out = w;
+    return MCD_OK;
 }
 
 }  // namespace
@@ -69,22 +100,14 @@ int mcd_pack_latent_weights(const mcd_tensor_t* tensors, int32_t n_tensors, cons
                             int32_t device, mcd_latent_weights_t** out) {
     if (!tensors || !cfg || !lcfg || !out) return fail(MCD_EINVAL, "null argument");
     PackedModel m;
-    int rc = pack_latent_model(tensors, n_tensors, cfg, lcfg, m);
-    if (rc != MCD_OK) return rc;
-    float* dbuf = nullptr;
-    rc = upload_packed(m.buf, device, &dbuf);
-    if (rc != MCD_OK) return rc;
-    mcd_latent_weights* w = new mcd_latent_weights();
-    w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
-    memset(w->opt, 0, sizeof(w->opt));
-    w->fused_ok = m.fused_ok != 0;
-    w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
-    w->ae = false; w->g_floats = 0;
-    w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
-    memset(w->cw.opt, 0, sizeof(w->cw.opt));
-    set_cond_weights(&w->cw, m, dbuf);
-    *out = w;
-    return MCD_OK;
+    return make_latent_weights(pack_latent_model(tensors, n_tensors, cfg, lcfg, m), m, cfg, device, false, out);
+}
+
+int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
+                               int32_t device, mcd_latent_weights_t** out) {
+    if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
+    PackedModel m;
+    return make_latent_weights(pack_latent_ae_model(tensors, n_tensors, cfg, latent_dim, m), m, cfg, device, true, out);
 }
 
 int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value) {
@@ -120,9 +143,9 @@ int mcd_latent_encode(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg,
     const int64_t need = lay.bytes - lay.gather;
     char* scratch = nullptr;
     if (need > 0) HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&scratch), (size_t)need, st));
-    const int rc = latent_encode_impl(w, cfg, data, view, step_table, cond_emb_out, z0_out, reinterpret_cast<float*>(scratch),
-                                      scratch ? reinterpret_cast<float*>(scratch + (lay.plain - lay.gather)) : nullptr,
-                                      scratch ? reinterpret_cast<float*>(scratch + (lay.h - lay.gather)) : nullptr, st);
+    LatentCall c;
+    int rc = latent_call(w, cfg, data, view, step_table, c);
+    if (rc == MCD_OK) rc = latent_encode_impl(w, c, cfg->n_windows, cond_emb_out, z0_out, latent_regions(scratch, lay, lay.gather), st);
     if (scratch) {
         const hipError_t e = hipFreeAsync(scratch, st);
         if (rc == MCD_OK && e != hipSuccess) return fail(MCD_EDEVICE, std::string("hipFreeAsync: ") + hipGetErrorString(e));
@@ -168,41 +191,18 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
     if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const LatentWorkspace lay = latent_workspace(&w->cw, B, D, w->h_floats);
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* cond = reinterpret_cast<float*>(wsb);
-    float* z0 = reinterpret_cast<float*>(wsb + lay.z0);
-    if (int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, reinterpret_cast<float*>(wsb + lay.gather),
-                                    reinterpret_cast<float*>(wsb + lay.plain), reinterpret_cast<float*>(wsb + lay.h), st)) return rc;
+    const LatentRegions R = latent_regions(workspace, lay);
+    LatentCall c;
+    if (int rc = latent_call(w, cfg, data, view, step_table, c)) return rc;
+    if (int rc = latent_encode_impl(w, c, B, R.cond, R.z0, R, st)) return rc;
     LatentChainParams P;
     memset(&P, 0, sizeof(P));
-    P.wbuf = w->dbuf; P.net = w->net; P.cond = cond; P.z0 = z0; P.noise = noise; P.step_table = step_table;
+    P.wbuf = w->dbuf; P.net = w->net; P.cond = R.cond; P.z0 = R.z0; P.noise = noise; P.step_table = step_table;
     P.loss_agg = aggregation == MCD_AGGR_ALL ? nullptr : loss_agg; P.loss_all = loss_all; P.latent_all = latent_all; P.latent_code = latent_code;
     P.seed = seed; P.first_window = first_window_id;
     P.B = B; P.S = S; P.ns = cfg->noise_steps; P.wpg = S >= LAT_NC ? 1 : LAT_NC / S;
     P.mode = 0; P.loss_fn = cfg->loss_fn; P.aggr = aggregation; P.aggr_q = quantile;
     return launch_latent_chain(P, st);
-}
-
-int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
-                               int32_t device, mcd_latent_weights_t** out) {
-    if (!tensors || !cfg || !out) return fail(MCD_EINVAL, "null argument");
-    PackedModel m;
-    int rc = pack_latent_ae_model(tensors, n_tensors, cfg, latent_dim, m);
-    if (rc != MCD_OK) return rc;
-    float* dbuf = nullptr;
-    rc = upload_packed(m.buf, device, &dbuf);
-    if (rc != MCD_OK) return rc;
-    mcd_latent_weights* w = new mcd_latent_weights();
-    w->cfg = *cfg; w->device = device; w->n_floats = m.buf.size(); w->net = m.net; w->dbuf = dbuf;
-    memset(w->opt, 0, sizeof(w->opt));
-    w->fused_ok = m.fused_ok != 0;
-    w->h_floats = latent_project_in_kernel(cfg->t_unet) ? 0 : LAT_ENC_C * cfg->t_unet * 10;
-    w->ae = true; w->g_floats = LAT_ENC_C * cfg->t_unet * 10;
-    w->cw.cfg = *cfg; w->cw.device = device; w->cw.dbuf = w->dbuf; w->cw.n_floats = w->n_floats;
-    memset(w->cw.opt, 0, sizeof(w->cw.opt));
-    set_cond_weights(&w->cw, m, dbuf);
-    *out = w;
-    return MCD_OK;
 }
 
 int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
@@ -219,24 +219,16 @@ int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t*
     if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const LatentWorkspace lay = latent_workspace(&w->cw, B, D, std::max(w->h_floats, w->g_floats));
-    char* wsb = reinterpret_cast<char*>(workspace);
-    float* cond = reinterpret_cast<float*>(wsb);
-    float* z0 = reinterpret_cast<float*>(wsb + lay.z0);
-    float* hg = reinterpret_cast<float*>(wsb + lay.h);      // H of the encode launch, then G of the unproject launch
-    if (int rc = latent_encode_impl(w, cfg, data, view, step_table, cond, z0, reinterpret_cast<float*>(wsb + lay.gather),
-                                    reinterpret_cast<float*>(wsb + lay.plain), hg, st)) return rc;
+    const LatentRegions R = latent_regions(workspace, lay);      // (R.h: H of the encode launch, then G of the unproject launch)
+    LatentCall c;
+    if (int rc = latent_call(w, cfg, data, view, step_table, c)) return rc;
+    if (int rc = latent_encode_impl(w, c, B, R.cond, R.z0, R, st)) return rc;
     if (pose_out || loss_out) {
-        DataView dv;
-        if (int rc = window_view(data, view, cfg->seg_len, dv)) return rc;
-        FrameIdx fi;
-        memset(&fi, 0, sizeof(fi));
-        for (int k = 0; k < cfg->n_corrupt; ++k) fi.idx[k] = cfg->corrupt_idx[k];
-        const float* pe_row = step_table + (size_t)cfg->noise_steps * (4 + EDIM) + 4;
-        if (int rc = launch_latent_unproject(T, w->dbuf, z_in ? z_in : z0, hg, D, B, st)) return rc;
-        if (int rc = launch_latent_decode(T, w->dbuf, dv, fi, cfg->seg_len, pe_row, cond, hg, pose_out, loss_out, cfg->loss_fn, B, st)) return rc;
+        if (int rc = launch_latent_unproject(T, w->dbuf, z_in ? z_in : R.z0, R.h, D, B, st)) return rc;
+        if (int rc = launch_latent_decode(T, {w->dbuf, c, R.cond, R.h, pose_out, loss_out, cfg->loss_fn, B, st})) return rc;
     }
-    if (cond_emb_out) HIP_TRY(hipMemcpyAsync(cond_emb_out, cond, (size_t)B * EDIM * 4, hipMemcpyDeviceToDevice, st));
-    if (z0_out) HIP_TRY(hipMemcpyAsync(z0_out, z0, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+    if (cond_emb_out) HIP_TRY(hipMemcpyAsync(cond_emb_out, R.cond, (size_t)B * EDIM * 4, hipMemcpyDeviceToDevice, st));
+    if (z0_out) HIP_TRY(hipMemcpyAsync(z0_out, R.z0, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
     return MCD_OK;
 }
 

@@ -461,22 +461,26 @@ int pack_pose_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_mo
 
 bool latent_dim_ok(int d) { return d >= 16 && d <= LAT_MAX_DIM && d % 16 == 0; }
 
+// layer l of the latent U-Net: its mix, its embedding rows into W_e / b_e, its bias, its fragments mix-first, its table row
+int pack_latent_layer(TensorMap& tm, int l, int T, Builder& B, std::vector<int>& tab, int we_off, int be_off) {
+    const LDesc Dl = layer_desc(l);
+    const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
+    int tq = 0, am = 0;
+    if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
+    FoldedLayer f;
+    if (!fold_layer(tm, p, l == 0 ? C0 : Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
+    if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
+    const int bias = emit_bias16(f, B);
+    set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
+    return MCD_OK;
+}
 // The part both latent handles share, behind the offset table: the embedding table W_e / b_e with room for emb_rows rows (the rows
 // of layers 0 .. 6 filled), the down path's seven layers, every one mix-first, [W_t' | W_r'] (layer 6 too, as in cond_unet_kernel),
 // down1 / down2 (non-capturing fragments), to_time_dim for the encode launch's tail or for latent_project_kernel.
 int pack_latent_down(TensorMap& tm, int T, int D, int emb_rows, Builder& B, std::vector<int>& tab, int& we_off, int& be_off) {
     we_off = B.alloc((size_t)emb_rows * EDIM); be_off = B.alloc(emb_rows);
-    for (int l = 0; l < LAT_DOWN_LAYERS; ++l) {
-        const LDesc Dl = layer_desc(l);
-        const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
-        int tq = 0, am = 0;
-        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-        FoldedLayer f;
-        if (!fold_layer(tm, p, l == 0 ? C0 : Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
-        if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
-        const int bias = emit_bias16(f, B);
-        set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
-    }
+    for (int l = 0; l < LAT_DOWN_LAYERS; ++l)
+        if (int rc = pack_latent_layer(tm, l, T, B, tab, we_off, be_off)) return rc;
     tab[TAB_WE] = we_off; tab[TAB_BE] = be_off;
     for (int r = 0; r < 2; ++r) {
         Folded f;
@@ -499,24 +503,42 @@ int pack_latent_down(TensorMap& tm, int T, int D, int emb_rows, Builder& B, std:
     return MCD_OK;
 }
 
-// MoCoDADlatent, stage 'pretrain' (mocodad_latent.py:59-64): STSAE_Unet with use_bottleneck -- the down path and to_time_dim as in
-// the diffusion stage's handle, then rev_to_time_dim and the up path (stsae_unet.py:365-438) for latent_unproject_kernel and
-// latent_decode_kernel -- and the condition encoder.  No denoiser.  The decoder tables exist in this kind of handle only.
-int pack_latent_ae_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int latent_dim, PackedModel& m) {
+// The configurations both latent handles refuse.  rows_ok: the handle's launches have kernels for t_unet corrupt frames; head: how
+// its message for the frame counts opens
+int check_latent_cfg(const mcd_model_cfg_t* cfg, int D, bool rows_ok, const char* head) {
     const int rc0 = check_common_cfg(cfg);
     if (rc0 != MCD_OK) return rc0;
     if (cfg->strategy != MCD_STRATEGY_INJECT) return fail(MCD_EINVAL, "the latent model conditions by 'inject' only (mocodad_latent.py:32)");
-    const int T = cfg->t_unet, D = latent_dim;
+    const int T = cfg->t_unet;
     if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
         return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    if (!latent_encode_has_kernel(T, false) || !latent_decode_has_kernel(T) || cfg->t_cond > 12)
-        return fail(MCD_EUNSUPPORTED, "the latent autoencoder has no kernels for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
+    if (!rows_ok || cfg->t_cond > 12)
+        return fail(MCD_EUNSUPPORTED, std::string(head) + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
                                       " condition frames (instantiated: " + latent_encode_counts() + " corrupt frames with 1 .. 12 condition frames)");
     if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
         return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
     if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
         return fail(MCD_EUNSUPPORTED, "this library holds no cond_unet_kernel for " + std::to_string(cfg->t_cond) + " condition frames (MCD_COND_UNET_INSTANCES)");
     if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
+    return MCD_OK;
+}
+// The condition encoder of a latent handle, packed as the pose model's (the AE decoder is dead work at evaluation and is not read).
+// The fused form runs cond_fast_body itself: its table is packed in every build, whatever cond_fast_kernel rows the library holds
+int pack_latent_cond(TensorMap& tm, const mcd_model_cfg_t* cfg, Builder& B, std::vector<int>& tab, PackedModel& m) {
+    const bool fusable = cfg->t_cond == cfg->t_unet && latent_encode_has_kernel(cfg->t_unet, true);
+    const int rc = pack_cond_encoder(tm, cfg, B, m.cond, fusable);
+    if (rc != MCD_OK) return rc;
+    write_cond_table(tab.data(), m.cond);
+    m.fused_ok = m.cond.fast_table && fusable;
+    return MCD_OK;
+}
+
+// MoCoDADlatent, stage 'pretrain' (mocodad_latent.py:59-64): STSAE_Unet with use_bottleneck -- the down path and to_time_dim as in
+// the diffusion stage's handle, then rev_to_time_dim and the up path (stsae_unet.py:365-438) for latent_unproject_kernel and
+// latent_decode_kernel -- and the condition encoder.  No denoiser.  The decoder tables exist in this kind of handle only.
+int pack_latent_ae_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int latent_dim, PackedModel& m) {
+    const int T = cfg->t_unet, D = latent_dim;
+    if (int rc = check_latent_cfg(cfg, D, latent_encode_has_kernel(T, false) && latent_decode_has_kernel(T), "the latent autoencoder has no kernels for ")) return rc;
 
     TensorMap tm = tensor_map(tensors, n_tensors);
     Builder B;
@@ -524,24 +546,11 @@ int pack_latent_ae_model(const mcd_tensor_t* tensors, int32_t n_tensors, const m
     std::vector<int> tab(TAB_FLOATS, 0);
     int we_off = 0, be_off = 0;
     if (int rc = pack_latent_down(tm, T, D, EMB_TOTAL, B, tab, we_off, be_off)) return rc;
-    const bool fusable = cfg->t_cond == T && latent_encode_has_kernel(T, true);
-    const int rc = pack_cond_encoder(tm, cfg, B, m.cond, fusable);
-    if (rc != MCD_OK) return rc;
-    write_cond_table(tab.data(), m.cond);
-    m.fused_ok = m.cond.fast_table && fusable;
+    if (int rc = pack_latent_cond(tm, cfg, B, tab, m)) return rc;
     // ---- the up path: layers 7 .. 10 mix-first like the others (layer 10: its 2 output channels in one 16-row m-tile), their
     // embedding rows behind those of the down path
-    for (int l = LAT_DOWN_LAYERS; l < NLAYERS; ++l) {
-        const LDesc Dl = layer_desc(l);
-        const std::string p = std::string("model.") + UNET_LAYER_NAMES[l];
-        int tq = 0, am = 0;
-        if (!pack_mix_mfma(tm, p, T, Dl.V, B, tq, am)) return fail(MCD_EMISSING, tm.missing);
-        FoldedLayer f;
-        if (!fold_layer(tm, p, Dl.cin, Dl.cout, Dl.res != 0, f)) return fail(MCD_EMISSING, tm.missing);
-        if (!copy_emb_linear(tm, p, l, Dl.cout, B, we_off, be_off)) return fail(MCD_EMISSING, tm.missing);
-        const int bias = emit_bias16(f, B);
-        set_layer_row(&tab[l * F_STRIDE], tq, am, emit_mix_first(f, Dl.cin, B), bias, f.slope);
-    }
+    for (int l = LAT_DOWN_LAYERS; l < NLAYERS; ++l)
+        if (int rc = pack_latent_layer(tm, l, T, B, tab, we_off, be_off)) return rc;
     // up3 / up2, and down1 / down2 once more in the capture k order: the decode launch's down-samplers hold d1 / d2 in registers
     for (int r = 0; r < 4; ++r) {
         Folded f;
@@ -571,21 +580,8 @@ int pack_latent_ae_model(const mcd_tensor_t* tensors, int32_t n_tensors, const m
 // MoCoDADlatent: the U-Net's down path (stsae_unet.py:182-219) with its embedding Linears, to_time_dim, the condition encoder,
 // the denoiser (components.py:228-241)
 int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, const mcd_latent_cfg_t* lcfg, PackedModel& m) {
-    const int rc0 = check_common_cfg(cfg);
-    if (rc0 != MCD_OK) return rc0;
-    if (cfg->strategy != MCD_STRATEGY_INJECT) return fail(MCD_EINVAL, "the latent model conditions by 'inject' only (mocodad_latent.py:32)");
-    const int T = cfg->t_unet;
-    if (T < 1 || T > MCD_MAX_FRAMES || cfg->t_cond < 1 || cfg->t_cond > MCD_MAX_FRAMES)
-        return fail(MCD_EUNSUPPORTED, "frame counts must be in 1.." + std::to_string(MCD_MAX_FRAMES));
-    if (!latent_encode_has_kernel(T, false) || cfg->t_cond > 12)
-        return fail(MCD_EUNSUPPORTED, "the latent encode launch has no kernel for " + std::to_string(T) + " corrupt + " + std::to_string(cfg->t_cond) +
-                                      " condition frames (instantiated: " + latent_encode_counts() + " corrupt frames with 1 .. 12 condition frames)");
-    if (cfg->cond_layers != MCD_COND_UNET && (cfg->cond_layers < 1 || cfg->cond_layers > MCD_MAX_COND_LAYERS))
-        return fail(MCD_EINVAL, "cond_layers must be 1 .. " + std::to_string(MCD_MAX_COND_LAYERS) + " or MCD_COND_UNET");
-    if (cfg->cond_layers == MCD_COND_UNET && !cond_unet_has_kernel(cfg->t_cond))
-        return fail(MCD_EUNSUPPORTED, "this library holds no cond_unet_kernel for " + std::to_string(cfg->t_cond) + " condition frames (MCD_COND_UNET_INSTANCES)");
-    const int D = lcfg->latent_dim, NL = lcfg->n_layers;
-    if (!latent_dim_ok(D)) return fail(MCD_EUNSUPPORTED, "latent_embedding_dim " + std::to_string(D) + ": must be a multiple of 16 in 16..128");
+    const int T = cfg->t_unet, D = lcfg->latent_dim, NL = lcfg->n_layers;
+    if (int rc = check_latent_cfg(cfg, D, latent_encode_has_kernel(T, false), "the latent encode launch has no kernel for ")) return rc;
     if (NL < 1 || NL > LAT_MAX_LAYERS) return fail(MCD_EUNSUPPORTED, "the denoiser has " + std::to_string(NL) + " layers: 1.." + std::to_string(LAT_MAX_LAYERS) + " are supported");
     for (int l = 0; l < NL; ++l)
         if (!latent_dim_ok(lcfg->hidden[l])) return fail(MCD_EUNSUPPORTED, "denoiser hidden size " + std::to_string(lcfg->hidden[l]) + ": must be a multiple of 16 in 16..128");
@@ -597,13 +593,7 @@ int pack_latent_model(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_
     std::vector<int> tab(TAB_FLOATS, 0);
     int we_off = 0, be_off = 0;
     if (int rc = pack_latent_down(tm, T, D, LAT_EMB, B, tab, we_off, be_off)) return rc;
-    // ---- the condition encoder, packed as the pose model's (the AE decoder is dead work at evaluation and is not read).  The fused
-    // form runs cond_fast_body itself: its table is packed in every build, whatever cond_fast_kernel rows the library holds
-    const bool fusable = cfg->t_cond == T && latent_encode_has_kernel(T, true);
-    const int rc = pack_cond_encoder(tm, cfg, B, m.cond, fusable);
-    if (rc != MCD_OK) return rc;
-    write_cond_table(tab.data(), m.cond);
-    m.fused_ok = m.cond.fast_table && fusable;
+    if (int rc = pack_latent_cond(tm, cfg, B, tab, m)) return rc;
     // ---- the denoiser: Linear -> BatchNorm1d -> ReLU, the last layer a plain Linear; cond_layers apart
     LatentNet& N = m.net;
     N.D = D; N.n_layers = NL;

@@ -504,7 +504,36 @@ class HipScorer(_Scorer):
         return out
 
 
-class LatentScorer(_Scorer):
+class _LatentHandle(_Scorer):
+    """What the two kinds of latent handle share: the library entries, the step table, and the packing of a state_dict -- the
+    model configuration ('inject' only), the device choice, the call of the subclass's pack entry _PACK with its own arguments
+    (_pack_args, between the configuration and the device index)."""
+
+    _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
+    _step_table = staticmethod(latent_step_table)
+    _PACK = ""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
+                 cond_channels: Sequence[int] = (), latent_dim: int, cond_unet: bool = False, num_coords: int = 2, n_joints: int = 17,
+                 emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
+        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
+        self.latent_dim = int(latent_dim)
+        if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
+            raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
+        cfg = self._model_cfg("inject", len(self.corrupt_idx), len(self.cond_idx), cond_channels, cond_unet)
+        arr, n, keep = _pack_tensors(state_dict)
+        # sizes and tensor names are checked by the library before it touches a device: those errors need no GPU
+        have_gpu = torch.cuda.is_available()
+        self.device = torch.device(device if device is not None else (f"cuda:{torch.cuda.current_device()}" if have_gpu else "cuda:0"))
+        idx = self.device.index if self.device.index is not None else 0
+        handle = C.c_void_p()
+        _lib.check(getattr(self.L, self._PACK)(arr, n, C.byref(cfg), *self._pack_args(), idx, C.byref(handle)))
+        del keep
+        self._h = handle
+        self._set_options(options)
+
+
+class LatentScorer(_LatentHandle):
     """One packed MoCoDADlatent model (stage 'diffusion') on one GPU: the mcd_latent_* entry points.
 
     state_dict: the reference's keys ('model.*' without an up path, 'condition_encoder.*', 'denoiser.*').
@@ -515,32 +544,18 @@ class LatentScorer(_Scorer):
     workspace also holds the encoder's last activation (n_windows x 640 x corrupt frames floats); `encode`, `score` and the
     workspace size are used the same way."""
 
-    _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
-    _step_table = staticmethod(latent_step_table)
+    _PACK = "mcd_pack_latent_weights"
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
-                 cond_channels: Sequence[int] = (), latent_dim: int, hidden_sizes: Sequence[int], cond_unet: bool = False,
-                 num_coords: int = 2, n_joints: int = 17, emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
-        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
-        self.latent_dim = int(latent_dim)
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, hidden_sizes: Sequence[int], **model):
         self.hidden_sizes = [int(h) for h in hidden_sizes]
-        if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
-            raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
-        cfg = self._model_cfg("inject", len(self.corrupt_idx), len(self.cond_idx), cond_channels, cond_unet)
+        super().__init__(state_dict, **model)
+
+    def _pack_args(self):
         lcfg = _lib.LatentCfg()
         lcfg.latent_dim, lcfg.n_layers = self.latent_dim, len(self.hidden_sizes)
         for i, h in enumerate(self.hidden_sizes[:8]):       # (more than 8 layers: the library refuses n_layers)
             lcfg.hidden[i] = h
-        arr, n, keep = _pack_tensors(state_dict)
-        # sizes and tensor names are checked by the library before it touches a device: those errors need no GPU
-        have_gpu = torch.cuda.is_available()
-        self.device = torch.device(device if device is not None else (f"cuda:{torch.cuda.current_device()}" if have_gpu else "cuda:0"))
-        idx = self.device.index if self.device.index is not None else 0
-        handle = C.c_void_p()
-        _lib.check(self.L.mcd_pack_latent_weights(arr, n, C.byref(cfg), C.byref(lcfg), idx, C.byref(handle)))
-        del keep
-        self._h = handle
-        self._set_options(options)
+        return [C.byref(lcfg)]
 
     def encode(self, data, *, noise_steps: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
         """windows -> (cond_emb (B,16), z0 (B,D)): condition encoder + down path at t = -1 + to_time_dim (mcd_latent_encode)."""
@@ -617,7 +632,7 @@ class LatentScorer(_Scorer):
         return out
 
 
-class LatentReconstructor(_Scorer):
+class LatentReconstructor(_LatentHandle):
     """One packed MoCoDADlatent model of stage 'pretrain' -- the bottleneck autoencoder -- on one GPU: mcd_pack_latent_ae_weights
     and mcd_latent_reconstruct.
 
@@ -626,27 +641,10 @@ class LatentReconstructor(_Scorer):
     [condition encoder] -> encode -> [project] -> unproject -> decode; the workspace holds cond_emb, z0 and one
     n_windows x 640 x corrupt-frames region (the encoder's last activation, then the decoder's first)."""
 
-    _OPTIONS, _SET_OPTION, _FREE = _lib.LATENT_OPT, "mcd_latent_set_option", "mcd_free_latent_weights"
-    _step_table = staticmethod(latent_step_table)
+    _PACK = "mcd_pack_latent_ae_weights"
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], *, seg_len: int, cond_idx: Sequence[int], corrupt_idx: Sequence[int],
-                 cond_channels: Sequence[int] = (), latent_dim: int, cond_unet: bool = False, num_coords: int = 2, n_joints: int = 17,
-                 emb_dim: int = 16, device=None, options: Optional[Dict[str, int]] = None):
-        self._init_model(seg_len, cond_idx, corrupt_idx, num_coords, n_joints, emb_dim)
-        self.latent_dim = int(latent_dim)
-        if len(cond_channels) > _lib.MCD_MAX_COND_LAYERS:
-            raise ValueError(f"at most {_lib.MCD_MAX_COND_LAYERS} condition-encoder layers")
-        cfg = self._model_cfg("inject", len(self.corrupt_idx), len(self.cond_idx), cond_channels, cond_unet)
-        arr, n, keep = _pack_tensors(state_dict)
-        # sizes and tensor names are checked by the library before it touches a device: those errors need no GPU
-        have_gpu = torch.cuda.is_available()
-        self.device = torch.device(device if device is not None else (f"cuda:{torch.cuda.current_device()}" if have_gpu else "cuda:0"))
-        idx = self.device.index if self.device.index is not None else 0
-        handle = C.c_void_p()
-        _lib.check(self.L.mcd_pack_latent_ae_weights(arr, n, C.byref(cfg), self.latent_dim, idx, C.byref(handle)))
-        del keep
-        self._h = handle
-        self._set_options(options)
+    def _pack_args(self):
+        return [self.latent_dim]
 
     def reconstruct(self, data, z: Optional[torch.Tensor] = None, *, want_pose: bool = True, want_code: bool = False,
                     loss_fn: str = "smooth_l1", noise_steps: int = 2):

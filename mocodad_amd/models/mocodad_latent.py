@@ -61,21 +61,44 @@ class DenoiserParams(nn.Module):
                 input_size = nxt
 
 
-class MoCoDADlatent(MoCoDAD):
+LOSS_FNS = {"smooth_l1": F.smooth_l1_loss, "l1": F.l1_loss, "mse": F.mse_loss}
+
+
+class LatentStage(MoCoDAD):
+    """What the two stages of the latent model share (MoCoDADlatent here, mocodad_latent_pretrain.MoCoDADlatentPretrain): the
+    constructor keys on top of MoCoDAD's, 'inject' as the only conditioning, and the arguments of their engine handle.  A stage
+    checks `args.stage` and sets `hidden_sizes` before it calls this constructor."""
     is_latent = True
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.stage = args.stage
         self.latent_embedding_dim = args.latent_embedding_dim
-        self.hidden_sizes = list(args.hidden_sizes)
         self.pretrained_model_ckpt_path = getattr(args, "pretrained_model_ckpt_path", None)
-        if self.stage == "pretrain":
-            raise NotImplementedError("MoCoDADlatent (mocodad_amd) is the 'diffusion' stage; a stage-1 checkpoint is evaluated by "
-                                      "mocodad_amd.models.mocodad_latent_pretrain.MoCoDADlatentPretrain (training: the reference implementation)")
-        if self.stage != "diffusion":
-            raise ValueError(f"Unknown stage {self.stage}")
         super().__init__(args)
         assert self.conditioning_strategy == 'inject', 'Conditioning strategy must be inject. Other strategies are not supported for the latent space'
+
+    def _scorer_kwargs(self, device) -> dict:
+        """The keyword arguments engine.LatentScorer and engine.LatentReconstructor share, from this module."""
+        if self.conditioning_strategy != "inject":
+            raise NotImplementedError("the latent model conditions by 'inject' only")
+        ci, xi = self._frame_split()
+        # (the class as the pose module holds it NOW: build_model, inherited, takes it from that module's globals, and a reload
+        # of mocodad_amd.models.mocodad rebinds it there -- a name imported into this module would be the class of before)
+        unet = isinstance(self.condition_encoder, _pose.CondUNetParams)
+        return dict(seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi, cond_unet=unet,
+                    cond_channels=[] if unet else list(self.condition_encoder.channels), latent_dim=self.latent_embedding_dim,
+                    num_coords=self.num_coords, n_joints=self.n_joints, emb_dim=self.embedding_dim, device=device)
+
+
+class MoCoDADlatent(LatentStage):
+    def __init__(self, args: argparse.Namespace) -> None:
+        self.hidden_sizes = list(args.hidden_sizes)
+        if args.stage == "pretrain":
+            raise NotImplementedError("MoCoDADlatent (mocodad_amd) is the 'diffusion' stage; a stage-1 checkpoint is evaluated by "
+                                      "mocodad_amd.models.mocodad_latent_pretrain.MoCoDADlatentPretrain (training: the reference implementation)")
+        if args.stage != "diffusion":
+            raise ValueError(f"Unknown stage {args.stage}")
+        super().__init__(args)
 
     def build_model(self) -> None:
         super().build_model()
@@ -86,21 +109,11 @@ class MoCoDADlatent(MoCoDAD):
     def build_scorer(self, device):
         """engine.LatentScorer with this module's weights (MoCoDAD.scorer() caches it per device)."""
         from ..engine import LatentScorer
-        if self.conditioning_strategy != "inject":
-            raise NotImplementedError("the latent model conditions by 'inject' only")
-        ci, xi = self._frame_split()
-        # (the class as the pose module holds it NOW: build_model, inherited, takes it from that module's globals, and a reload
-        # of mocodad_amd.models.mocodad rebinds it there -- a name imported into this module would be the class of before)
-        unet = isinstance(self.condition_encoder, _pose.CondUNetParams)
-        return LatentScorer(self.state_dict(), seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi, cond_unet=unet,
-                            cond_channels=[] if unet else list(self.condition_encoder.channels), latent_dim=self.latent_embedding_dim,
-                            hidden_sizes=self.hidden_sizes, num_coords=self.num_coords, n_joints=self.n_joints,
-                            emb_dim=self.embedding_dim, device=device)
+        return LatentScorer(self.state_dict(), hidden_sizes=self.hidden_sizes, **self._scorer_kwargs(device))
 
     # -------------------------------------------------------------- forward
     def _loss(self, x: torch.Tensor, z0: torch.Tensor) -> torch.Tensor:
-        fn = {"smooth_l1": F.smooth_l1_loss, "l1": F.l1_loss, "mse": F.mse_loss}[self.loss_name]
-        return fn(x, z0.expand_as(x), reduction="none").mean(dim=-1)
+        return LOSS_FNS[self.loss_name](x, z0.expand_as(x), reduction="none").mean(dim=-1)
 
     def forward(self, input_data: List[torch.Tensor], condition_data: torch.Tensor = None, aggr_strategy: str = 'best', *,
                 return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,

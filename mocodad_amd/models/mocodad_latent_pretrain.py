@@ -16,10 +16,9 @@ from typing import List, Optional
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from . import mocodad as _pose
-from .mocodad import MoCoDAD, UNetParams
+from .mocodad import UNetParams
+from .mocodad_latent import LOSS_FNS, LatentStage
 
 
 class LatentAEParams(UNetParams):
@@ -33,23 +32,15 @@ class LatentAEParams(UNetParams):
         self.rev_to_time_dim = nn.Linear(latent_dim, f)
 
 
-_LOSS = {"smooth_l1": F.smooth_l1_loss, "l1": F.l1_loss, "mse": F.mse_loss}
-
-
-class MoCoDADlatentPretrain(MoCoDAD):
-    is_latent = True
+class MoCoDADlatentPretrain(LatentStage):
     is_pretrain = True
 
     def __init__(self, args: argparse.Namespace) -> None:
-        self.stage = args.stage
-        self.latent_embedding_dim = args.latent_embedding_dim
         self.hidden_sizes = list(getattr(args, "hidden_sizes", None) or [])      # (a key of the YAML; the stage builds no denoiser)
-        self.pretrained_model_ckpt_path = getattr(args, "pretrained_model_ckpt_path", None)
-        if self.stage != "pretrain":
-            raise ValueError(f"MoCoDADlatentPretrain is the 'pretrain' stage of the latent model, got stage {self.stage!r}: "
+        if args.stage != "pretrain":
+            raise ValueError(f"MoCoDADlatentPretrain is the 'pretrain' stage of the latent model, got stage {args.stage!r}: "
                              "the 'diffusion' stage is mocodad_amd.models.mocodad_latent.MoCoDADlatent")
         super().__init__(args)
-        assert self.conditioning_strategy == 'inject', 'Conditioning strategy must be inject. Other strategies are not supported for the latent space'
         self.model_return_value = "pose"      # (mocodad_latent.py:33)
 
     def build_model(self) -> None:
@@ -60,14 +51,7 @@ class MoCoDADlatentPretrain(MoCoDAD):
     def build_scorer(self, device):
         """engine.LatentReconstructor with this module's weights (MoCoDAD.scorer() caches it per device)."""
         from ..engine import LatentReconstructor
-        if self.conditioning_strategy != "inject":
-            raise NotImplementedError("the latent model conditions by 'inject' only")
-        ci, xi = self._frame_split()
-        unet = isinstance(self.condition_encoder, _pose.CondUNetParams)
-        return LatentReconstructor(self.state_dict(), seg_len=self.n_frames, cond_idx=ci, corrupt_idx=xi, cond_unet=unet,
-                                   cond_channels=[] if unet else list(self.condition_encoder.channels),
-                                   latent_dim=self.latent_embedding_dim, num_coords=self.num_coords, n_joints=self.n_joints,
-                                   emb_dim=self.embedding_dim, device=device)
+        return LatentReconstructor(self.state_dict(), **self._scorer_kwargs(device))
 
     # -------------------------------------------------------------- forward
     def _corrupt_frames(self, tensor_data) -> torch.Tensor:
@@ -122,4 +106,4 @@ class MoCoDADlatentPretrain(MoCoDAD):
     def post_processing(self, out, gt_data, trans=None, meta=None, frames=None) -> float:
         """mocodad_latent.py:217-218 on host arrays (saved tensors): mean loss_fn(out, gt_data)."""
         t = lambda a: a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
-        return torch.mean(_LOSS[self.loss_name](t(out), t(gt_data), reduction="none")).item()
+        return torch.mean(LOSS_FNS[self.loss_name](t(out), t(gt_data), reduction="none")).item()

@@ -136,6 +136,66 @@ def test_case_list_holds_the_configurations_it_names():
     assert set(recorded()["cases"]) == set(IDS)
 
 
+# The autoencoder of stage 'pretrain' (pack_latent_ae_model, behind mcd_debug_pack_ae_digest): (name, corrupt frames, settings).
+# The shipped encoder at 3 + 3 (fused table); 5 corrupt + 3 condition frames (fast, not fused; to_time_dim as fragments); 'E_unet' at
+# 12 + 12; another channel list at 6 + 3.  Their digests ("ae_cases" of pack_digests.json, "ae_recorded_from") were recorded the same
+# way from the commit that added the stage, patched with this export alone.
+AE_CASES = [
+    ("ae_3_3", 3, dict(_inject(3, **SHIPPED), latent_embedding_dim=32)),
+    ("ae_5_3", 5, dict(_inject(3, **SHIPPED), latent_embedding_dim=32)),
+    ("ae_eunet_12_12", 12, dict(_inject(12, conditioning_architecture="E_unet"), latent_embedding_dim=64)),
+    ("ae_other_list_6_3", 6, dict(_inject(3, **OTHER), latent_embedding_dim=16)),
+]
+AE_IDS = [c[0] for c in AE_CASES]
+
+
+def build_ae_inputs(index):
+    """-> (state_dict drawn from default_rng(1000 + index), ModelCfg, latent_dim) of AE_CASES[index]"""
+    import latentp_ref
+    from mocodad_amd.models.mocodad_latent_pretrain import MoCoDADlatentPretrain
+    _, t_corrupt, over = AE_CASES[index]
+    t_cond = len(over["conditioning_indices"])
+    base = dict(latentp_ref.load_fixture("P6")[2], stage="pretrain")
+    with torch.no_grad():
+        m = MoCoDADlatentPretrain(make_args(base, **dict(over, seg_len=t_cond + t_corrupt)))
+    rng = np.random.default_rng(1000 + index)
+    sd = {}
+    for k, v in m.state_dict().items():
+        if not v.dtype.is_floating_point:
+            continue
+        a = rng.standard_normal(tuple(v.shape))
+        if k.endswith("running_var"):
+            a = np.abs(a) + 0.5
+        sd[k] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(tuple(v.shape)))
+    ci, xi = m._frame_split()
+    unet_enc = m.conditioning_architecture == "E_unet"
+    chans = [] if unet_enc else list(m.condition_encoder.channels)
+    cfg = _lib.ModelCfg(num_coords=2, n_joints=17, emb_dim=16, strategy=_lib.STRATEGY["inject"])
+    cfg.t_cond, cfg.t_unet = len(ci), len(xi)
+    cfg.cond_layers = _lib.COND_UNET if unet_enc else len(chans)
+    for i, c in enumerate(chans):
+        cfg.cond_channels[i] = c
+    return sd, cfg, m.latent_embedding_dim
+
+
+@pytest.mark.parametrize("index", range(len(AE_CASES)), ids=AE_IDS)
+def test_autoencoder_packed_layout_matches_the_recorded_digest(index):
+    L = _lib.lib()
+    sd, cfg, D = build_ae_inputs(index)
+    name, t_corrupt, over = AE_CASES[index]
+    assert (cfg.t_unet, cfg.t_cond, D) == (t_corrupt, len(over["conditioning_indices"]), over["latent_embedding_dim"])
+    arr, n, keep = _pack_tensors(sd)
+    nf, dg = C.c_int64(0), C.c_uint64(0)
+    rc = L.mcd_debug_pack_ae_digest(arr, n, C.byref(cfg), D, C.byref(nf), C.byref(dg))
+    del keep
+    assert rc == 0, L.mcd_last_error()
+    want = recorded()["ae_cases"][name]
+    print(f"{name}: n_floats {nf.value} digest {dg.value:016x}  recorded {want['n_floats']} {want['digest']}")
+    assert int(nf.value) == want["n_floats"]
+    assert f"{dg.value:016x}" == want["digest"]
+    assert set(recorded()["ae_cases"]) == set(AE_IDS)
+
+
 def _without(sd, key):
     assert key in sd
     return {k: v for k, v in sd.items() if k != key}
