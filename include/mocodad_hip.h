@@ -190,9 +190,25 @@ int32_t mcd_plan_split(const mcd_weights_t* w, const mcd_score_cfg_t* cfg);
  *   MCD_OPT_SPLIT         0 (default): the library chooses how many workgroups share a window's samples (1 = a workgroup
  *                         runs all samples of its windows: condition encoder and aggregation fused into the ONE launch;
  *                         n_samples = one trajectory per workgroup, better fill for odd batch sizes); n > 0 forces it
- *                         (tests). */
+ *                         (tests).
+ *   MCD_OPT_PHASE         tuning experiments on when co-resident workgroups of a scoring call start and take priority
+ *                         (bench.py --phase).  0 (default): the library's behaviour.  The runtime-shape kernels ignore it; the
+ *                         two MFMA trajectory-kernel families read it as follows:
+ *                           value    1 .. 12 U-Net frames (score_kernel)            13 .. 32 frames (score_tiled_kernel)
+ *                           n > 0    the second half of the grid starts             as 0
+ *                                    n x 1024 clock cycles late
+ *                           -1       no priority time slices                        no priority time slices (16-frame form;
+ *                                                                                   the others never have them)
+ *                           -2       slices from the host's estimate alone:         as 0 (this family has no self-calibration)
+ *                                    the kernel's measurement of its previous
+ *                                    launch is not used
+ *                           n < -15  every workgroup starts at its own hashed       the slice length is forced to
+ *                                    offset of 0 .. 63 x |n| x 16 cycles;           2^(-n - 16) ticks of the 100 MHz clock,
+ *                                    slices as at 0                                 clamped to 2^10 .. 2^26 (16-frame form)
+ *                           -3 .. -15  as 0                                         as 0
+ *                         (n < -15 means different things to the two families: a start offset there, a slice length here.) */
 enum { MCD_OPT_VARIANT = 0, MCD_OPT_COND_GENERIC = 1, MCD_OPT_GENERIC_UNET = 2, MCD_OPT_SPLIT = 3,
-       MCD_OPT_PHASE = 4, /* tuning experiment: start the second half of the grid `value` x 1024 clock cycles late */
+       MCD_OPT_PHASE = 4, /* tuning experiments: the table above */
        MCD_OPT_COUNT = 5 };
 int mcd_set_option(mcd_weights_t* w, int32_t option, int32_t value);
 

@@ -34,7 +34,6 @@ namespace {
 int launch_score(const mcd_weights* w, int T, ScoreParams& P, hipStream_t st, bool* fused = nullptr, bool layer_test = false) {
     if (!layer_test) {
         P.force_split = w->opt[MCD_OPT_SPLIT];
-        P.phase = w->opt[MCD_OPT_PHASE];
         const int variant = w->opt[MCD_OPT_VARIANT];
         if (variant != 0 && !score_has_variants()) return fail(MCD_EUNSUPPORTED, "MCD_OPT_VARIANT needs a -DMCD_TUNING_VARIANTS build");
 #define MCD_CASE(unit, V, T_, NB, MINW) if (T == T_ && variant == V) return launch_score_t<T_, NB, MINW>(P, st, fused);
@@ -79,7 +78,7 @@ int64_t gen_scratch_bytes(int64_t units, int T) {
 int launch_score_generic(const mcd_weights* w, const ScoreParams& P, const FrameMaps& M, float* scratch, hipStream_t st) {
     const int T = w->cfg.t_unet;
     const int wgs = P.n_chains < GEN_MAX_WGS ? P.n_chains : GEN_MAX_WGS;
-    const size_t lds = ((size_t)3 * C0 * T * 17 + EMB_TOTAL + 4 + EDIM + GEN_THREADS) * 4;
+    const size_t lds = (size_t)GenericLds(T).floats() * 4;
     hipLaunchKernelGGL(score_generic_kernel, dim3(wgs), dim3(GEN_THREADS), lds, st, P, M, w->gen, T, scratch);
     HIP_TRY(hipGetLastError());
     return MCD_OK;
@@ -111,7 +110,7 @@ constexpr int CE_MAX_WGS = 512;
 int launch_cond_plain(const mcd_weights* w, const float* cond_data, int B, float* emb, float* scratch, hipStream_t st) {
     const bool g = w->cond.gmode != 0;
     if (g && !scratch) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes) for this many condition frames");
-    const size_t lds = ((size_t)(g ? 2 : 3) * w->cond.cmax * w->cond.Tc * 17 + CE_THREADS) * 4;
+    const size_t lds = w->cond.lds_floats() * 4;
     LDS_LIMIT(&cond_encode_kernel, (size_t)160 * 1024);
     const int wgs = g && B > CE_MAX_WGS ? CE_MAX_WGS : B;
     hipLaunchKernelGGL(cond_encode_kernel, dim3(wgs), dim3(CE_THREADS), lds, st, w->cond, cond_data, emb, B, g ? scratch : nullptr);
@@ -161,7 +160,7 @@ int64_t cond_scratch_bytes(const mcd_weights* w, CondRoute r, int64_t B) {
         case COND_TILED: return w->cond_unet && w->tiled_cond_tp ? tiled_scratch_bytes(w, B, w->tiled_cond_tp) : 0;
         case COND_UNET_GENERIC: return w->cond_unet ? gen_scratch_bytes(B, w->cond.Tc) : 0;
         case COND_PLAIN_SCRATCH:
-            return w->has_cond && !w->cond_unet && w->cond.gmode ? (B < CE_MAX_WGS ? B : CE_MAX_WGS) * (int64_t)w->cond.cmax * w->cond.Tc * 17 * 4 : 0;
+            return w->has_cond && !w->cond_unet && w->cond.gmode ? (B < CE_MAX_WGS ? B : CE_MAX_WGS) * (int64_t)w->cond.buf_floats() * 4 : 0;
         default: return 0;
     }
 }
@@ -178,6 +177,7 @@ int64_t cond_ws_bytes(const mcd_weights* w, int64_t B) {
 }
 
 int launch_unet(const mcd_weights* w, UnetRoute r, ScoreParams& P, const FrameMaps& M, float* scratch, hipStream_t st, bool* fused = nullptr) {
+    P.phase = w->opt[MCD_OPT_PHASE];      // (the launchers decode it: decode_phase; score_kernel reads it raw)
     switch (r) {
         case UNET_KERNEL: return launch_score(w, w->cfg.t_unet, P, st, fused);
         case UNET_TILED: return launch_score_tiled(w, P, M, scratch, st);
@@ -510,7 +510,7 @@ static int score_impl(const mcd_weights_t* w, const mcd_score_cfg_t* cfg, const 
     ScoreParams P;
     memset(&P, 0, sizeof(P));
     P.wbuf = w->dbuf; P.prof = g_prof;
-    P.tune = w->opt[MCD_OPT_PHASE] == -2 ? nullptr : w->tune;      // (phase -2: the host's estimate only -- A/B of the self-calibration)
+    P.tune = decode_phase(w->opt[MCD_OPT_PHASE]).self_tune ? w->tune : nullptr;      // (off: the host's estimate only -- A/B of the self-calibration)
     if (int rc = window_view(data, view, cfg->seg_len, P.dv)) return rc;
     if (rnd) P.win_mask = view->cond_mask;
     P.noise = noise; P.step_table = step_table; P.pose_out = pose_out;

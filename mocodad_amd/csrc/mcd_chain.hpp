@@ -56,7 +56,7 @@ struct ScoreParams {
     int force_split;          // host only (MCD_OPT_SPLIT): 0 = choose
     int loss_out_optional;    // host only: loss_out is the library's own scratch, not wanted when the aggregation is fused
     int plan_only;            // host only: choose `split`, do not launch
-    int phase;                // tuning experiment (MCD_OPT_PHASE): the second half of the grid starts `phase` x 1024 cycles late
+    int phase;                // MCD_OPT_PHASE, raw (its table: mocodad_hip.h; the host's reading: decode_phase, mcd_launch.hpp)
     int prio_shift;           // host: log2 of the priority time slice in 100 MHz ticks (see the top of the step loop); 0 = off
                               // (an ESTIMATE from the shapes; the kernel replaces it by a sixth of the measured duration of the
                               // previous launch of the same grid when `tune` holds one)

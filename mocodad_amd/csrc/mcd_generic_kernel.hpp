@@ -14,6 +14,18 @@ constexpr int GEN_THREADS = 256;     // block size of the two generic kernels (C
 constexpr int GEN_BUF = 1280;        // floats per frame of the three rotating buffers: 128 ch x 10 joints (>= 32 x 17, 64 x 12)
 constexpr int GEN_D1 = 32 * 17, GEN_D2 = 64 * 12;
 constexpr int GEN_SLAB = 3 * GEN_BUF + GEN_D1 + GEN_D2;      // per frame and workgroup
+// LDS plan of score_generic_kernel at T U-Net frames, offsets in floats (the kernel carves at them, the launcher asks for floats())
+struct GenericLds {
+    int CTV;                                                          // C0 x T x 17: one [c][t][v] tensor over the U-Net frames
+    __host__ __device__ explicit GenericLds(int T) : CTV(C0 * T * 17) {}
+    __host__ __device__ int xt() const { return 0; }                  // chain state
+    __host__ __device__ int eps() const { return xt() + CTV; }        // layer 10's output (+ x)
+    __host__ __device__ int zn() const { return eps() + CTV; }        // this step's noise at the U-Net frames
+    __host__ __device__ int emb() const { return zn() + CTV; }        // [EMB_TOTAL + 4]
+    __host__ __device__ int se() const { return emb() + EMB_TOTAL + 4; }   // [16]
+    __host__ __device__ int red() const { return se() + EDIM; }       // [GEN_THREADS]
+    __host__ __device__ int floats() const { return red() + GEN_THREADS; }
+};
 
 // one ST-GCN layer (stsgcn.py:94-116, BatchNorm folded): X [cin][T][V] -> O [cout][T][V]; Y (>= cin T V floats, may be O) and
 // Z are scratch.  THREADS: the caller's block size; VC: the joint count when the caller knows it (its joint-mix loop is then
@@ -142,13 +154,14 @@ __device__ void g_resample(const float* wb, int wo, int bo, int C, int T, int vi
 __global__ __launch_bounds__(GEN_THREADS) void score_generic_kernel(const ScoreParams P, const FrameMaps M, const GenNet N, int T,
                                                                     float* __restrict__ scratch) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];
-    const int TV = T * 17, CTV = C0 * TV, tid = threadIdx.x;
-    float* XT = gsm;                  // chain state [c][t][v] over the U-Net frames
-    float* EPS = XT + CTV;            // layer 10's output (+ x)
-    float* ZN = EPS + CTV;            // this step's noise at the U-Net frames
-    float* EMB = ZN + CTV;            // [EMB_TOTAL + 4]
-    float* SE = EMB + EMB_TOTAL + 4;  // [16]
-    float* RED = SE + EDIM;           // [GEN_THREADS]
+    const GenericLds LD(T);
+    const int TV = T * 17, CTV = LD.CTV, tid = threadIdx.x;
+    float* XT = gsm + LD.xt();
+    float* EPS = gsm + LD.eps();
+    float* ZN = gsm + LD.zn();
+    float* EMB = gsm + LD.emb();
+    float* SE = gsm + LD.se();
+    float* RED = gsm + LD.red();
     float* slab = scratch + (size_t)blockIdx.x * GEN_SLAB * T;
     float* A = slab;
     float* Bb = A + GEN_BUF * T;
@@ -308,11 +321,12 @@ __global__ __launch_bounds__(CE_THREADS) void cond_encode_kernel(const CondW W, 
                                                                  float* __restrict__ emb_out, int B, float* __restrict__ gbuf) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Tc = W.Tc, TV = Tc * 17, tid = threadIdx.x;
-    float* RED = smem + (gbuf ? 2 : 3) * W.cmax * TV;  // CE_THREADS partial sums
+    const int BF = (int)W.buf_floats();
+    float* RED = smem + (int)W.red_offset();           // CE_THREADS partial sums
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
     float* X = smem;
-    float* Z = X + W.cmax * TV;
-    float* O = gbuf ? gbuf + (size_t)blockIdx.x * W.cmax * TV : Z + W.cmax * TV;
+    float* Z = X + BF;
+    float* O = W.gmode ? gbuf + (size_t)blockIdx.x * BF : Z + BF;      // (the launcher passes gbuf exactly when W.gmode is set)
     __syncthreads();
     for (int u = tid; u < C0 * TV; u += CE_THREADS) X[u] = cond[(size_t)b * C0 * TV + u];  // (c, t, v) row-major
     __syncthreads();

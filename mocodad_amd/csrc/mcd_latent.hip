@@ -158,7 +158,7 @@ int launch_latent_project(int t, const float* wbuf, const float* H, float* z0_ou
 
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st) {
     const int per_wg = P.mode == 1 ? LAT_NC : P.wpg * P.S;
-    const size_t lds = (size_t)latent_chain_lds_floats(P.net.D, per_wg) * 4;
+    const size_t lds = (size_t)LatentChainLds(P.net.D, per_wg).floats() * 4;
     LDS_LIMIT((&latent_chain_kernel), 160 * 1024);
     const int grid = P.mode == 1 ? (P.B + LAT_NC - 1) / LAT_NC : (P.B + P.wpg - 1) / P.wpg;
     hipLaunchKernelGGL(latent_chain_kernel, dim3(grid), dim3(LAT_THREADS), lds, st, P);

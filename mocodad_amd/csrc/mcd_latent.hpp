@@ -46,10 +46,23 @@ struct LatentChainParams {
     float aggr_q;
 };
 
-__host__ __device__ inline int latent_chain_lds_floats(int D, int chains_per_wg) {
-    // HA | HB | X | Z0 | E | CE | RED | column tables | per-sample losses
-    return 2 * LAT_NC * LAT_HS + 2 * LAT_NC * (D + 4) + LAT_NC * 20 + LAT_NC * 16 + LAT_NC * 8 + 2 * LAT_NC + chains_per_wg;
-}
+// LDS plan of latent_chain_kernel for latent size D and chains_per_wg chains of a workgroup, offsets in floats: the kernel carves
+// at them, launch_latent_chain asks for floats()
+struct LatentChainLds {
+    int XS, per_wg;           // row stride of X and Z0; per-sample losses kept
+    __host__ __device__ LatentChainLds(int D, int chains_per_wg) : XS(D + 4), per_wg(chains_per_wg) {}
+    __host__ __device__ int ha() const { return 0; }                              // activations, ping
+    __host__ __device__ int hb() const { return ha() + LAT_NC * LAT_HS; }         // ... pong
+    __host__ __device__ int x() const { return hb() + LAT_NC * LAT_HS; }          // chain state x[col][D]
+    __host__ __device__ int z0() const { return x() + LAT_NC * XS; }              // latent code of the column's window
+    __host__ __device__ int e() const { return z0() + LAT_NC * XS; }              // pos_encoding(i) + cond_emb [col][20]
+    __host__ __device__ int ce() const { return e() + LAT_NC * 20; }              // cond_emb [col][16]
+    __host__ __device__ int red() const { return ce() + LAT_NC * 16; }            // loss partial sums [col][8]
+    __host__ __device__ int colb() const { return red() + LAT_NC * 8; }           // ints: window (mode 1: row) of a column, -1 = empty
+    __host__ __device__ int cols() const { return colb() + LAT_NC; }              // ints: its sample
+    __host__ __device__ int loss() const { return cols() + LAT_NC; }              // [window of the workgroup][S]
+    __host__ __device__ int floats() const { return loss() + per_wg; }
+};
 
 // words of the packed buffer's offset table (mcd_device.hpp) that hold to_time_dim's weight / bias
 constexpr int TAB_LAT_LW = 100, TAB_LAT_LB = 101;

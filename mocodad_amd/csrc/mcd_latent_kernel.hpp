@@ -24,18 +24,20 @@ __device__ __forceinline__ f32x4 lat_mfma4(const float4 a, const float4 b, f32x4
 
 __global__ __launch_bounds__(LAT_THREADS) void latent_chain_kernel(const LatentChainParams P) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int D = P.net.D, XS = D + 4, L = P.net.n_layers;
+    const int D = P.net.D, L = P.net.n_layers;
     const int per_wg = P.mode == 1 ? LAT_NC : P.wpg * P.S;      // chains of this workgroup
-    float* const HA = smem;
-    float* const HB = HA + LAT_NC * LAT_HS;
-    float* const X = HB + LAT_NC * LAT_HS;        // chain state x[col][D]
-    float* const Z0 = X + LAT_NC * XS;            // latent code of the column's window
-    float* const E = Z0 + LAT_NC * XS;            // pos_encoding(i) + cond_emb [col][20]
-    float* const CE = E + LAT_NC * 20;            // cond_emb [col][16]
-    float* const RED = CE + LAT_NC * 16;          // loss partial sums [col][8]
-    int* const COLB = reinterpret_cast<int*>(RED + LAT_NC * 8);      // window (mode 1: row) of a column, -1 = empty
-    int* const COLS = COLB + LAT_NC;                                 // its sample
-    float* const LOSS = reinterpret_cast<float*>(COLS + LAT_NC);     // [window of the workgroup][S]
+    const LatentChainLds LD(D, per_wg);           // (what each region holds: at the struct)
+    const int XS = LD.XS;
+    float* const HA = smem + LD.ha();
+    float* const HB = smem + LD.hb();
+    float* const X = smem + LD.x();
+    float* const Z0 = smem + LD.z0();
+    float* const E = smem + LD.e();
+    float* const CE = smem + LD.ce();
+    float* const RED = smem + LD.red();
+    int* const COLB = reinterpret_cast<int*>(smem + LD.colb());
+    int* const COLS = reinterpret_cast<int*>(smem + LD.cols());
+    float* const LOSS = smem + LD.loss();
     const int tid = threadIdx.x, lane = tid & 63, n16 = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int K = P.ns > 2 ? P.ns - 1 : 1;

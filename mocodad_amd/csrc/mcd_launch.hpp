@@ -16,6 +16,11 @@ struct CondW {
     int gmode;       // 1: three LDS buffers of cmax x Tc x 17 do not fit (25 .. 31 condition frames of the shipped encoder): the third one lives in global scratch
     GLayer L[MCD_MAX_COND_LAYERS];
     int lw, lb;
+    // cond_encode_kernel's memory plan: three rotating activation buffers of buf_floats() -- all in LDS, or under gmode two of
+    // them and one per workgroup in global scratch -- and behind the LDS buffers RED, CE_THREADS partial sums
+    __host__ __device__ size_t buf_floats() const { return (size_t)cmax * Tc * 17; }
+    __host__ __device__ size_t red_offset() const { return (gmode ? 2 : 3) * buf_floats(); }
+    __host__ __device__ size_t lds_floats() const { return red_offset() + CE_THREADS; }
 };
 
 struct GenNet { GLayer L[NLAYERS]; int rs_w[4], rs_b[4], we, be; };
@@ -105,6 +110,25 @@ constexpr int shipped_waves_tiled(int tp) { return tp > 16 ? 12 : 8; }
 #define MCD_WAVES_CHECK(expected) static_assert(NWAVES == (expected), "this unit's MCD_NWAVES is not the wave count the kernel ships with (MCD_UNIT_FLAGS_<n> in mcd_instances.hpp)")
 #endif
 
+// MCD_OPT_PHASE (a tuning option; the table of its values is at the enum in mocodad_hip.h), decoded for the host here and nowhere
+// else.  The kernels read the raw value (ScoreParams::phase): score_kernel for start_delay and hashed_start.
+struct PhaseOpt {
+    int start_delay;      // > 0: score_kernel starts the second half of its grid that many x 1024 cycles late (the kernel's own read)
+    bool slices;          // the launchers give co-resident workgroups their priority time slices (-1: off)
+    bool self_tune;       // score_kernel corrects the host's slice estimate by its previous launch's measurement (-2: off)
+    int forced_shift;     // < -15, score_tiled_kernel: slice length 2^(-value - 16) ticks instead of the estimate; -1: none
+    bool hashed_start;    // < -15, score_kernel: every workgroup starts at its own hashed offset (the kernel's own read)
+};
+inline PhaseOpt decode_phase(int phase) {
+    return PhaseOpt{phase > 0 ? phase : 0, phase != -1, phase != -2, phase < -15 ? -phase - 16 : -1, phase < -15};
+}
+// log2 of the priority time slice of co-resident workgroups in ticks of the 100 MHz clock: about a sixth of the launch's
+// expected duration `ticks` (or the length the option forces), within 2^10 .. 2^26
+inline int prio_slice_shift(double ticks, int forced_shift = -1) {
+    const int sh = forced_shift >= 0 ? forced_shift : (int)floor(log2(ticks / 6.0) + 0.5);
+    return sh < 10 ? 10 : (sh > 26 ? 26 : sh);
+}
+
 template <int T, int NB, int MINW, bool LT = false>
 int launch_score_t(ScoreParams& P, hipStream_t st, bool* fused) {
     MCD_WAVES_CHECK(shipped_waves_score(T));
@@ -126,14 +150,13 @@ int launch_score_t(ScoreParams& P, hipStream_t st, bool* fused) {
     if (P.loss_agg && P.loss_out_optional) P.loss_out = nullptr;
     if (P.mode == 0 && !P.loss_agg && !P.loss_out) return fail(MCD_EINVAL, "workspace required (mcd_score_workspace_bytes): per-sample losses of an unfused aggregation");
     P.prio_shift = 0;
-    if (MINW >= 4 && P.mode == 0 && P.phase != -1) {
+    if (MINW >= 4 && P.mode == 0 && decode_phase(P.phase).slices) {
         // priority time slice of the co-resident workgroups (see score_kernel): about 1/6 of the launch's expected duration --
         // rounds of workgroups x trajectories per workgroup x passes x ~7.5 us per (chain, frame) of a pass
         const double rounds = (double)(((long long)groups * P.split + slots - 1) / slots);
         const double traj = (double)((P.S + P.split - 1) / P.split);
         const double ticks = rounds * traj * (double)(P.ns > 2 ? P.ns - 1 : 1) * 7.5 * NB * T * 100.0;
-        int sh = (int)floor(log2(ticks / 6.0) + 0.5);
-        P.prio_shift = sh < 10 ? 10 : (sh > 26 ? 26 : sh);
+        P.prio_shift = prio_slice_shift(ticks);
         P.prio_rounds = (int)rounds;
     }
     hipLaunchKernelGGL((score_kernel<T, NB, MINW, LT>), dim3(groups * P.split), dim3(NTHREADS), PL::BYTES, st, P);
@@ -170,20 +193,21 @@ constexpr int tl_wgs_per_cu(int TP) { return TP * tl_nb(TP) <= 16 ? 2 : 1; }
 template <int TP, int NB, bool LT = false, bool COND = false>
 int launch_score_tiled_t(const mcd_weights* w, const ScoreParams& P, const FrameMaps& M, float* scratch, int wgs, hipStream_t st) {
     MCD_WAVES_CHECK(COND ? NWAVES : shipped_waves_tiled(TP));      // (the COND form -- the 'E_unet' encoder on the tiled stages -- runs on eight or twelve)
-    constexpr int TF = TP * NB;
-    constexpr size_t lds = ((size_t)tl_ra_floats(TF) + (TF * 17 + 16) * 4 + NB * (EMB_TOTAL + 4 + EDIM) + TF * 17 * 2 * 2 + (TF * 17 + 16) * 4 + NTHREADS + 128 + 32 + tl_ex_floats(TF)) * 4;
+    using LD = TiledLds<TP, NB>;
+    // the three shipped shapes (one chain, the shipped wave count), pinned: a change of the plan shows up here
+    static_assert(NB != 1 || NTHREADS != 64 * shipped_waves_tiled(TP) || LD::BYTES == (TP == 16 ? 81824 : TP == 24 ? 148704 : 154656),
+                  "TiledLds: the LDS of a shipped shape changed");
+    constexpr size_t lds = LD::BYTES;
     LDS_LIMIT((&score_tiled_kernel<TP, NB, LT, COND>), lds);
     ScoreParams Q = P;
     Q.prio_shift = 0;
-    const int phase = w->opt[MCD_OPT_PHASE];      // (-1: no slices; -(16 + shift): a given slice length, tuning)
-    if (TF <= 16 && !LT && !COND && P.mode == 0 && phase != -1 && wgs > 0) {
+    const PhaseOpt ph = decode_phase(P.phase);
+    if (LD::TF <= 16 && !LT && !COND && P.mode == 0 && ph.slices && wgs > 0) {
         // priority time slice of the two co-resident workgroups: about 1/6 of the launch -- chains per workgroup x passes x
         // ~190 us per pass of a 16-frame chain sharing its CU (2.4 GHz), in ticks of the 100 MHz clock
         const double per_wg = (double)((P.n_chains + (long long)wgs * NB - 1) / ((long long)wgs * NB));
         const double ticks = per_wg * (double)(P.ns > 2 ? P.ns - 1 : 1) * 190.0 * 100.0;
-        const int sh = (int)floor(log2(ticks / 6.0) + 0.5);
-        Q.prio_shift = sh < 10 ? 10 : (sh > 26 ? 26 : sh);
-        if (phase < -15) Q.prio_shift = -phase - 16 > 26 ? 26 : (-phase - 16 < 10 ? 10 : -phase - 16);
+        Q.prio_shift = prio_slice_shift(ticks, ph.forced_shift);
     }
     hipLaunchKernelGGL((score_tiled_kernel<TP, NB, LT, COND>), dim3(wgs), dim3(NTHREADS), lds, st, Q, M, COND ? w->tiled_cond : w->tiled,
                        COND ? w->cond.Tc : w->cfg.t_unet, scratch);

@@ -346,9 +346,9 @@ int pack_cond_encoder(TensorMap& tm, const mcd_model_cfg_t* cfg, Builder& B, Con
                 set_layer_row(cp.ctab[l], tq, am, wp, emit_bias16(fl[l], B), fl[l].slope);
             }
         }
-        const size_t lds = ((size_t)3 * Cw.cmax * Cw.Tc * 17 + CE_THREADS) * 4;
-        Cw.gmode = lds > 160 * 1024;
-        if (((size_t)2 * Cw.cmax * Cw.Tc * 17 + CE_THREADS) * 4 > 160 * 1024) return fail(MCD_EUNSUPPORTED, "condition encoder activations exceed LDS");
+        Cw.gmode = 0;      // three buffers in LDS if they fit, else two (CondW::lds_floats)
+        if (Cw.lds_floats() * 4 > 160 * 1024) Cw.gmode = 1;
+        if (Cw.lds_floats() * 4 > 160 * 1024) return fail(MCD_EUNSUPPORTED, "condition encoder activations exceed LDS");
     }
     return MCD_OK;
 }

@@ -49,9 +49,43 @@ __host__ __device__ constexpr int tl_ra_floats(int TP) {
 // (+ 4 pad rows: the 17-joint resampler's last k-step reads joints 16 .. 19 of the chunk's last frame -- zero coefficients on finite values)
 __host__ __device__ constexpr int tl_ex_floats(int TF) { return TF == 24 ? (tl_fc(TF) * 17 + 4) * 36 : 0; }
 __host__ __device__ constexpr int tl_qc(int TP) { return TP % 3 == 0 ? 3 : 4; }     // output frames per mix unit (6 at 24 frames: 108 coefficient registers, spills)
-__host__ __device__ constexpr long long tl_slab_floats(int TP) {
-    // A0, A1 (ping-pong, up to 128 ch x 10 joints), the skips D1, D2 -- each with 16 rows of padding behind it
-    return (long long)2 * (TP * 10 + 16) * 132 + (long long)(TP * 17 + 16) * 36 + (long long)(TP * 12 + 16) * 68;
+// LDS plan of score_tiled_kernel<TP, NB>, offsets in floats: the kernel carves at them, launch_score_tiled_t asks for BYTES.
+// (RED is NTHREADS long: like the kernel, the plan belongs to the translation unit that instantiates it.)
+template <int TP, int NB>
+struct TiledLds {
+    static constexpr int TF = TP * NB, R17 = TF * 17;
+    static constexpr int EMBS = EMB_TOTAL + 4;
+    static constexpr int RA_F = tl_ra_floats(TF), EX_F = tl_ex_floats(TF);
+    static constexpr int RA = 0;                           // work region (mix: 32 channels of all frames; GEMM: z chunk + x chunk)
+    static constexpr int XT = RA + RA_F;                   // [R17 + 16][4]  chain state (+ pad)
+    static constexpr int EMB = XT + (R17 + 16) * 4;        // [NB][EMB_TOTAL + 4]
+    static constexpr int SE = EMB + NB * EMBS;             // [NB][16]
+    static constexpr int ZN = SE + NB * EDIM;              // [R17][2]  this step's noise
+    static constexpr int ZO = ZN + R17 * C0;               // [R17][2]  layer 10's mixed output
+    static constexpr int P4 = ZO + R17 * C0;               // [R17 + 16][4]  layer 10's W-first product (+ zero pad rows: its mix reads 16-channel blocks)
+    static constexpr int RED = P4 + (R17 + 16) * 4;        // [NTHREADS]
+    static constexpr int W4L = RED + NTHREADS;             // [4][32]  layer 10's W-first weights [W_t; W_r] (constant over the launch)
+    static constexpr int UPDT = W4L + 128;                 // [32] ints: frame t -> frame whose chain state its prediction updates (pos_of[upd_of[t]]), or -1
+    static constexpr int EX = UPDT + 32;                   // [TL_FC * 17 + 4][36]  second hand-over chunk of layers 2 -> 3, 8 -> 9 (24 frames only)
+    static constexpr int FLOATS = EX + EX_F;
+    static constexpr int BYTES = FLOATS * 4;
+    static_assert(RA % 4 == 0 && XT % 4 == 0 && EMB % 4 == 0 && P4 % 4 == 0 && W4L % 4 == 0 && EX % 4 == 0,
+                  "tiled LDS plan: a region read or written as float4 starts on a 16-byte boundary");
+    static_assert(BYTES <= 160 * 1024, "tiled LDS plan exceeds the 160 KB of a CU");
+};
+// ... and of its slab in global memory: A0, A1 (ping-pong, up to 128 ch x 10 joints), the skips D1, D2 -- each with 16 rows of
+// padding behind it.  TF: the workgroup's frames (TP x NB)
+template <int TF>
+struct TiledSlab {
+    static constexpr int A0 = 0;
+    static constexpr int A1 = A0 + (TF * 10 + 16) * 132;
+    static constexpr int D1 = A1 + (TF * 10 + 16) * 132;
+    static constexpr int D2 = D1 + (TF * 17 + 16) * 36;
+    static constexpr int FLOATS = D2 + (TF * 12 + 16) * 68;
+};
+static_assert(TiledSlab<16>::FLOATS == 70976 && TiledSlab<24>::FLOATS == 103520 && TiledSlab<32>::FLOATS == 136064, "TiledSlab: a shipped slab changed");
+constexpr long long tl_slab_floats(int TF) {       // (the function form: the host sizes the workspace by the handle's padded frame count)
+    return TF == 16 ? TiledSlab<16>::FLOATS : TF == 24 ? TiledSlab<24>::FLOATS : TF == 32 ? TiledSlab<32>::FLOATS : 0;
 }
 
 // row stride of a C-channel tensor in the SLAB.  The + 4 of the LDS row strides (cs_of) serves the LDS banks; in global memory it
@@ -512,25 +546,24 @@ template <int TP, int NB, bool LT = false, bool COND = false>
 __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) void score_tiled_kernel(const ScoreParams P, const FrameMaps M, const TiledNet N, int T,
                                                                   float* __restrict__ slabs) {
     constexpr int TF = TP * NB;
-    constexpr int R17 = TF * 17, R12 = TF * 12, R10 = TF * 10;
+    constexpr int R17 = TF * 17;
     constexpr int TL_FC = tl_fc(TF), NFC = TF / TL_FC;
     static_assert(TP % TL_FC == 0, "a GEMM chunk lies inside one chain (its embedding rows are the chain's)");
-    constexpr int EMBS = EMB_TOTAL + 4;
+    using LD = TiledLds<TP, NB>;       // the LDS plan: work region, chain state, tables (what each region holds: at the struct)
+    using SL = TiledSlab<TF>;
+    constexpr int EMBS = LD::EMBS, RA_F = LD::RA_F, EXF = LD::EX_F;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // LDS: work region RA (mix: 32 channels of all frames; GEMM: z chunk + x chunk), chain state XT[col][4] (+ pad), tables
-    constexpr int RA_F = tl_ra_floats(TF);
-    float* const RA = smem;
-    float* const XT = RA + RA_F;                    // [R17 + 16][4]
-    float* const EMB = XT + (R17 + 16) * 4;         // [NB][EMB_TOTAL + 4]
-    float* const SE = EMB + NB * EMBS;              // [NB][16]
-    float* const ZN = SE + NB * EDIM;               // [R17][2]  this step's noise
-    float* const ZO = ZN + R17 * C0;                // [R17][2]  layer 10's mixed output
-    float* const P4 = ZO + R17 * C0;                // [R17 + 16][4]  layer 10's W-first product (+ zero pad rows: its mix reads 16-channel blocks)
-    float* const RED = P4 + (R17 + 16) * 4;         // [NTHREADS]
-    float* const W4L = RED + NTHREADS;              // [4][32]  layer 10's W-first weights [W_t; W_r] (constant over the launch)
-    constexpr int EXF = tl_ex_floats(TF);
-    int* const UPDT = reinterpret_cast<int*>(W4L + 128);   // [32]  frame t -> frame whose chain state its prediction updates (pos_of[upd_of[t]]), or -1
-    float* const EX = W4L + 128 + 32;                    // [TL_FC * 17][36]  second hand-over chunk of layers 2 -> 3, 8 -> 9 (24 frames only)
+    float* const RA = smem + LD::RA;
+    float* const XT = smem + LD::XT;
+    float* const EMB = smem + LD::EMB;
+    float* const SE = smem + LD::SE;
+    float* const ZN = smem + LD::ZN;
+    float* const ZO = smem + LD::ZO;
+    float* const P4 = smem + LD::P4;
+    float* const RED = smem + LD::RED;
+    float* const W4L = smem + LD::W4L;
+    int* const UPDT = reinterpret_cast<int*>(smem + LD::UPDT);
+    float* const EX = smem + LD::EX;
     const int tid0 = threadIdx.x;
     int tid = tid0, lane = tid & 63;
     int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -541,18 +574,18 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
     bool tl_tron = false;
     int tl_ev = 0, tl_pass = 0;
 #endif
-    float* slab = slabs + (size_t)blockIdx.x * tl_slab_floats(TF);
+    float* slab = slabs + (size_t)blockIdx.x * SL::FLOATS;
     const int Tx = P.n_corrupt, K = P.ns > 2 ? P.ns - 1 : 1, per = C0 * Tx * 17;
     // everything a chain leaves behind that the next chain of this workgroup reads before writing it (pad rows / pad frames meet
     // zero coefficients: they must hold finite values) -- cleared at the start, and again behind a chain that DIVERGED (see below)
     auto clear_state = [&](int t_id) {
-        for (int u = t_id; u < (int)tl_slab_floats(TF); u += NTHREADS) slab[u] = 0.f;
+        for (int u = t_id; u < SL::FLOATS; u += NTHREADS) slab[u] = 0.f;
         for (int u = t_id; u < (R17 + 16) * 4; u += NTHREADS) { XT[u] = 0.f; P4[u] = 0.f; }
         for (int u = t_id; u < R17 * C0; u += NTHREADS) { ZN[u] = 0.f; ZO[u] = 0.f; }
         for (int u = t_id; u < EXF; u += NTHREADS) EX[u] = 0.f;
         for (int u = t_id; u < RA_F; u += NTHREADS) RA[u] = 0.f;
     };
-    for (int u = tid; u < (int)tl_slab_floats(TF); u += NTHREADS) slab[u] = 0.f;      // pad rows / pad frames: finite values
+    for (int u = tid; u < SL::FLOATS; u += NTHREADS) slab[u] = 0.f;      // pad rows / pad frames: finite values
     for (int u = tid; u < (R17 + 16) * 4; u += NTHREADS) XT[u] = 0.f;
     if (tid < 64) P4[R17 * 4 + tid] = 0.f;
     if (!COND && tid < 128) W4L[tid] = P.wbuf[N.wp[10] + tid];
@@ -627,10 +660,10 @@ __global__ __launch_bounds__(NTHREADS, (TP * NB <= 16 ? 2 : 1) * NWAVES / 4) voi
             asm volatile("" : "+s"(sl));
             KTiledNet* Ns = (KTiledNet*)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TiledKernArgs, N));
             asm volatile("" : "+s"(Ns));
-            float* const A0 = sl;
-            float* const A1 = A0 + (R10 + 16) * 132;
-            float* const D1 = A1 + (R10 + 16) * 132;
-            float* const D2 = D1 + (R17 + 16) * 36;
+            float* const A0 = sl + SL::A0;
+            float* const A1 = sl + SL::A1;
+            float* const D1 = sl + SL::D1;
+            float* const D2 = sl + SL::D2;
             __syncthreads();
             if (!COND && tid < NB * EDIM) {
                 float e = srow[4 + tid % EDIM];
