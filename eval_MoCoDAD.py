@@ -40,6 +40,27 @@ def model_class(args):
     return MoCoDAD
 
 
+def load_latent_decoder(model, args, random_init: bool) -> None:
+    """latent_score_space 'pose': the stage-1 decoder from pretrained_model_ckpt_path; with --random-init and no such file, from a
+    seeded MoCoDADlatentPretrain whose shared tensors (down path, to_time_dim, condition encoder) are copied from the diffusion module."""
+    path = getattr(args, "pretrained_model_ckpt_path", None)
+    if path and os.path.exists(path):
+        model.load_decoder(path)
+        return
+    if not random_init:
+        raise SystemExit(f"stage-1 checkpoint {path} not found: latent_score_space 'pose' decodes with it (pass --random-init to decode "
+                         "with seeded random-init weights)")
+    import copy
+    from mocodad_amd.models.mocodad_latent_pretrain import MoCoDADlatentPretrain
+    a = copy.copy(args)
+    a.stage = "pretrain"
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(getattr(args, "seed", 0)) + 1)
+        sd = MoCoDADlatentPretrain(a).state_dict()
+    sd.update({k: v.detach().cpu() for k, v in model.state_dict().items() if k in sd})
+    model.load_decoder(sd)
+
+
 def main():
     ap = argparse.ArgumentParser(description="MoCoDAD (MI355X)")
     ap.add_argument("-c", "--config", type=str, required=True)
@@ -56,15 +77,23 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="'nccl' (= RCCL over xGMI) or 'gloo' (tests with several ranks on one GPU)")
     ap.add_argument("--dump-scores", type=str, default=None, help="rank 0 writes the gathered window scores + AUC to this .npz")
     ap.add_argument("--joint-scores", type=str, default=None, metavar="OUT.npz",
-                    help="pose model, one process: also write, per (scene, clip, person) row, the (n_frames, 17) per-joint frame "
+                    help="pose model, or the latent model scoring in pose space; one process: also write, per (scene, clip, person) row, the (n_frames, 17) per-joint frame "
                          "scores -- the scatter-max of the windows' error maps (which joints and forecast frames a score comes "
                          "from), averaged over the transforms -- with the row table and the joint names")
+    ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
+                    help="latent model, stage 'diffusion' (overrides the YAML's latent_score_space): 'pose' decodes the generated "
+                         "latents with the stage-1 decoder of pretrained_model_ckpt_path and scores the forecasts as the pose model does")
     cli = ap.parse_args()
     args = load_config(cli.config)
     model_cls = model_class(args)
+    if cli.latent_score_space is not None:
+        args.latent_score_space = cli.latent_score_space
+    pose_space = getattr(model_cls, "is_latent", False) and not getattr(model_cls, "is_pretrain", False) \
+        and getattr(args, "latent_score_space", None) == "pose"
     if cli.joint_scores:
-        if model_cls is not MoCoDAD:
-            raise SystemExit("eval_MoCoDAD.py: --joint-scores needs the pose model (a latent has no joints)")
+        if model_cls is not MoCoDAD and not pose_space:
+            raise SystemExit("eval_MoCoDAD.py: --joint-scores needs the pose model, or the latent model with latent_score_space: 'pose' "
+                             "(a latent has no joints)")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("eval_MoCoDAD.py: --joint-scores runs in one process (the maps are not gathered across ranks)")
         if getattr(args, "aggregation_strategy", "best") in ("all", "random") or "random" in str(args.conditioning_strategy):
@@ -135,6 +164,8 @@ def main():
         model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"])
     elif not cli.random_init:
         raise SystemExit(f"checkpoint {ckpt} not found (pass --random-init to score with seeded random-init weights)")
+    if pose_space:
+        load_latent_decoder(model, args, cli.random_init)
 
     n = len(tw) if tw is not None else data.shape[0]
     shard = WindowShard(n, rank, world)

@@ -287,7 +287,8 @@ int mcd_aggregate_view(const mcd_score_cfg_t* cfg, int32_t num_coords, int32_t n
 /* Error maps (ABI version 15): WHERE a window's score comes from -- which joints, which forecast frames.  Replaces what a caller
  * would otherwise redo in PyTorch from pose_out: the per-element loss of mocodad.py:484 before its mean over C*Tx*V, with the
  * sample selection, tie rules and NaN behaviour of _aggregation_strategy (mocodad.py:454-520) as mcd_aggregate implements them.
- * Pose model only (a latent has no joints); num_coords must be 2 and n_joints 17, the layout the window loader reads.
+ * It takes poses: mcd_score's, or for the latent model the decoded forecasts of mcd_latent_decode_samples (a latent itself has no
+ * joints); num_coords must be 2 and n_joints 17, the layout the window loader reads.
  *   E[b,s,t,v] = (1/C) sum_c loss_elem(pose_all[b,s,c,t,v], x[b,c,t,v])       mean_{t,v} E[b,s] = loss_all[b,s] up to rounding
  * x = the ground-truth corrupt frame t of window b, read through `view` with the affine transform applied -- by the device function
  * the trajectory kernels load it with, so its bits are the ones the loss was computed on.  With view->cond_mask the corrupt frames of
@@ -554,8 +555,14 @@ int64_t mcd_latent_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_wind
 
 /* Test and diagnostic aid in the style of mcd_set_option.
  *   MCD_LATENT_OPT_SPLIT_ENCODE  1: the shipped configuration takes the three-launch form too (cond_fast_kernel, then the encode
- *                                launch reading cond_emb), so the two forms can be compared on the same weights.  0: default. */
-enum { MCD_LATENT_OPT_SPLIT_ENCODE = 0, MCD_LATENT_OPT_COUNT = 1 };
+ *                                launch reading cond_emb), so the two forms can be compared on the same weights.  0: default.
+ *   MCD_LATENT_OPT_DECODE_SPW    n > 0: a workgroup of mcd_latent_decode_samples' decode launch takes n samples of its window (at
+ *                                most all of them) instead of what the launcher's rule gives.  0: the rule.  No result depends on it.
+ *   MCD_LATENT_OPT_DECODE_CHUNK  n > 0: mcd_latent_decode_samples walks the batch in chunks of at most n windows (and at most what
+ *                                its bound on G holds); mcd_latent_decode_workspace_bytes follows.  0: the bound alone.  No result
+ *                                depends on it.
+ * (The two decode options are new enumerators behind the existing one: no value a caller compiled against changes.) */
+enum { MCD_LATENT_OPT_SPLIT_ENCODE = 0, MCD_LATENT_OPT_DECODE_SPW = 1, MCD_LATENT_OPT_DECODE_CHUNK = 2, MCD_LATENT_OPT_COUNT = 3 };
 int mcd_latent_set_option(mcd_latent_weights_t* w, int32_t option, int32_t value);
 
 /* The latent step table: (noise_steps + 1, 4 + emb_dim) -- rows 0 .. ns-1 as for mcd_score (update coefficients of
@@ -587,7 +594,8 @@ int mcd_latent_denoise(const mcd_latent_weights_t* w, const float* x, const floa
  *                else (S, max(ns-1,1), B, D): slot 0 = x_T (torch.randn at mocodad_latent.py:109), slot k = the z of step
  *                i = ns - k (torch.randn_like at :121), in call order
  *   step_table   the latent step table above
- *   workspace    mcd_latent_workspace_bytes (required)
+ *   workspace    mcd_latent_workspace_bytes (required).  Behind the call (in stream order) its first n_windows x 16 floats hold
+ *                cond_emb (B,16), until the workspace is used again: what mcd_latent_decode_samples takes as cond_emb_in
  *   aggregation  MCD_AGGR_ALL (loss_all required, loss_agg unused) or BEST / WORST / MEAN / MEDIAN / QUANTILE -> loss_agg (B,)
  *   loss_all (B,S), latent_all (B,S,D) generated latents, latent_code (B,D) = z0: optional outputs (NULL = not wanted)
  * cfg->loss_fn is applied to (generated latent, z0) and averaged over D.  1 .. 1024 samples per call.  Chains are independent:
@@ -613,8 +621,9 @@ int mcd_latent_score(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, 
  * its name, both before the device is touched.  The handle is a mcd_latent_weights_t of the autoencoder kind: freed by
  * mcd_free_latent_weights, sized by mcd_latent_workspace_bytes (cond_emb, z0, the condition encoder's scratch, and one region that
  * holds H and then G = rev_to_time_dim(z), 640 floats per corrupt frame and window), taken by mcd_latent_encode and
- * mcd_latent_reconstruct.  mcd_latent_score / mcd_latent_denoise on it, and mcd_latent_reconstruct on a diffusion-stage handle,
- * return MCD_EUNSUPPORTED naming the kind the call needs. */
+ * mcd_latent_reconstruct (and by mcd_latent_decode_samples, which has a workspace size of its own).  mcd_latent_score /
+ * mcd_latent_denoise on it, and mcd_latent_reconstruct / mcd_latent_decode_samples on a diffusion-stage handle, return
+ * MCD_EUNSUPPORTED naming the kind the call needs. */
 int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, const mcd_model_cfg_t* cfg, int32_t latent_dim,
                                int32_t device, mcd_latent_weights_t** out);
 
@@ -636,6 +645,33 @@ int mcd_pack_latent_ae_weights(const mcd_tensor_t* tensors, int32_t n_tensors, c
 int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
                            const float* step_table, void* workspace, const float* z_in, float* pose_out, float* loss_out,
                            float* cond_emb_out, float* z0_out, void* stream);
+
+/* ---- Generated latents back to poses (added without a change of MCD_ABI_VERSION, as the pretrain stage was: two new exports).
+ *
+ * The diffusion stage scores in latent space; the stage-1 autoencoder's rev_to_time_dim and up path are the decoder of the latents
+ * it generates (the reference freezes the down path, to_time_dim and the condition encoder when it trains stage 2, so those
+ * tensors are the same in both checkpoints).  On an AUTOENCODER handle (a diffusion-stage handle: MCD_EUNSUPPORTED naming the kind
+ * the call needs):
+ *   latents      (B,S,D), 16-byte aligned: e.g. latent_all of mcd_latent_score
+ *   cond_emb_in  NULL: the handle's own condition encoder runs as a launch in front; else (B,16), what mcd_latent_encode /
+ *                mcd_latent_score produced for these windows
+ *   pose_all     NULL or (B,S,2,t_unet,17): sample s of window b decoded with the window's own skips and condition, + its corrupt frames
+ *   loss_all     (B,S): mean over (c,t,v) of cfg->loss_fn(pose, corrupt frames), summed in the fixed order of mcd_latent_reconstruct
+ *   workspace    mcd_latent_decode_workspace_bytes(w, n_windows, n_samples), 16-byte aligned
+ * pose_all[:, s] and loss_all[:, s] are bit for bit what mcd_latent_reconstruct(z_in = latents[:, s]) returns.  Both have the
+ * layout of mcd_score's outputs: mcd_aggregate, mcd_aggregate_view and mcd_error_maps take them as they take those.
+ * Launches: [condition encoder] -> per chunk of windows: latent_unproject_kernel over the chunk's latent rows -> the decode launch,
+ * one workgroup per window and range of its samples: the down stem for the skips runs once per workgroup, not once per sample.
+ * Cost: G = rev_to_time_dim of a row is 640 t_unet floats; the call walks the batch in chunks of windows so that G stays under
+ * 256 MB, and the workspace is cond_emb (B,16) + the condition encoder's scratch + that bounded G.  1 .. 1024 samples per call.
+ * Samples and windows are independent: a non-finite latent row gives that sample a non-finite loss and changes no other sample's
+ * or window's bits; neither do the chunking nor the split of a window's samples over workgroups.
+ * n_windows <= 0 returns MCD_OK before any device call; n_samples < 1, a NULL latents / loss_all / workspace, a misaligned latents or
+ * workspace are MCD_EINVAL before any launch. */
+int64_t mcd_latent_decode_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows, int32_t n_samples);
+int mcd_latent_decode_samples(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                              const float* step_table, void* workspace, const float* cond_emb_in, const float* latents, float* pose_all,
+                              float* loss_all, void* stream);
 
 /* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
  * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121).

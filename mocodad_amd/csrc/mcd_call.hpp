@@ -81,6 +81,20 @@ LatentWorkspace latent_workspace(const mcd_weights* cw, int64_t B, int D, int64_
     return L;
 }
 
+// latent, mcd_latent_decode_samples: [condition embeddings (B,16)][gathered condition frames][third buffer of the plain encoder][G];
+// the middle two as above, G = g_bytes: the rows of one window chunk (mcd_latent_api.hpp bounds it)
+struct LatentDecodeWorkspace { int64_t gather, plain, g, bytes; };
+LatentDecodeWorkspace latent_decode_workspace(const mcd_weights* cw, int64_t B, int64_t g_bytes) {
+    const CondRoute r = cond_route(cw);
+    const bool plain = r == COND_PLAIN || r == COND_PLAIN_SCRATCH;
+    LatentDecodeWorkspace L;
+    L.gather = round256(B * EDIM * 4);
+    L.plain = L.gather + (plain ? round256(B * C0 * cw->cfg.t_cond * 17 * 4) : 0);
+    L.g = L.plain + (plain ? round256(cond_scratch_bytes(cw, COND_PLAIN_SCRATCH, B)) : 0);
+    L.bytes = L.g + round256(g_bytes);
+    return L;
+}
+
 // One condition encoder launch (with its gather, for the plain routes) -> emb (B,16).  r: a route with a launch of its own (not
 // COND_NONE / COND_INKERNEL).  gather: where the plain encoder's dense (B,C,Tc,V) copy of the condition frames goes; NULL = dv.data
 // IS that copy (mcd_cond_encode).  scratch: cond_scratch_bytes(w, r, B) of device memory, NULL if that is 0.

@@ -1,6 +1,7 @@
 // mcd_encode_kernel.hpp — the encoder family: the MFMA condition encoders of the pose model, cond_fast_kernel<T, NB> (shipped
 // channel list) and cond_unet_kernel<T, NB> ('E_unet'), and the latent model's encode launch latent_encode_kernel<T, NB,
-// COND_IN_KERNEL, PROJECT_IN_KERNEL>, and the decode launch of its pretrain stage, latent_decode_kernel<T> (at the end of the file).
+// COND_IN_KERNEL, PROJECT_IN_KERNEL>, and the decode launches of its pretrain stage, latent_decode_kernel<T> and
+// latent_decode_samples_kernel<T> (at the end of the file; they share latent_decode_stem and latent_decode_row).
 // The first three are a window loader, stage functions of mcd_device.hpp on an LDS plan and a Linear over the (c,t,v) flattening;
 // the decode launch is the same loader and the same down stem, capturing the skips, in front of the up path.  The shared pieces are
 // stated here once: load_window_frames (all four), unet_down_stem (the 'E_unet' encoder, the encode and the decode launch; with layer
@@ -507,40 +508,56 @@ struct LatentDecLds {
     static_assert(2 * T * 17 <= NTHREADS, "epilogue: one pose element per thread");
 };
 
-template <int T>
-__global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float* wbuf, const DataView dv, const FrameIdx fi, int seg_len,
-                                                                    const float* __restrict__ pe_row, const float* __restrict__ cond,
-                                                                    const float* __restrict__ G, float* __restrict__ pose_out,
-                                                                    float* __restrict__ loss_out, int loss_fn, int B) {
+// The two pieces of a decode workgroup, stated once for latent_decode_kernel (one G row per window) and latent_decode_samples_kernel
+// (a range of a window's G rows, below).
+// (1) the region cleared, the rows of all eleven layers as latent_down_pass forms its 400, the window's corrupt frames, and the down
+// stem once more for the skips: d1 = layer 2's output, d2 = layer 4's, captured by the down-samplers' B reads.  (down2's own output is
+// not needed -- layers 5, 6 and the bottleneck ran in the launches before -- the stage is there for its reads.)  Ends behind a barrier.
+template <int T, int NS1, int NS2>
+__device__ __forceinline__ void latent_decode_stem(const float* wb, const DataView& dv, const FrameIdx& fi, int seg_len,
+                                                   const float* pe_row, const float* cond_row, int b, int B,
+                                                   float* smem, float (&skip1)[NS1], float (&skip2)[NS2], int tid, int wave, int lane,
+                                                   Prof& prof) {
     using PL = Plan<T, 1>;
     using LD = LatentDecLds<T>;
-    constexpr int TV = T * 17, TV10 = T * 10, F = LAT_ENC_C * TV10;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const RG = smem;
     float* const EMB = smem + LD::WORK;
     float* const SEN = EMB + LD::EMB;
-    float* const RED = SEN + EDIM;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.x;
-    Prof prof;
-    prof.off();
-    const float* wb = wbuf;
-    // the rows of all eleven layers, as latent_down_pass forms its 400
     for (int u = tid; u < LD::WORK + LD::EMB; u += NTHREADS) smem[u] = 0.f;      // pad columns / pad channels must hold finite values
-    step_embedding<1>(wb, pe_row, cond + (size_t)b * EDIM, SEN, EMB, 0, emb_off(10) + C0, tid, -1);
+    step_embedding<1>(wb, pe_row, cond_row, SEN, EMB, 0, emb_off(10) + C0, tid, -1);
     load_window_frames<T, 1>(RG + PL::L0_in, dv, [&](int t) { return fi.idx[t]; }, seg_len, b, B);
     __syncthreads();
-    // ---- the down stem once more, for the skips: d1 = layer 2's output, d2 = layer 4's, captured by the down-samplers' B reads.
-    // (down2's own output is not needed -- layers 5, 6 and the bottleneck ran in the launches before -- the stage is there for its reads)
-    float skip1[RsCfg<32, 17, 12, T, 1, true>::PER * RsCfg<32, 17, 12, T, 1, true>::SK];
-    float skip2[RsCfg<64, 12, 10, T, 1, true>::PER * RsCfg<64, 12, 10, T, 1, true>::SK];
     unet_down_stem<T, 1, true, true>(wb, wb, RsWords{TAB_LAT_CAPW + 0, TAB_LAT_CAPB + 0, TAB_LAT_CAPW + 1, TAB_LAT_CAPB + 1}, RG, EMB,
                                      skip1, skip2, wave, lane, prof);
+}
+// (2) row g_row of G (640 T floats each, H's order) -> up3 + d2 -> layers 7, 8 -> up2 + d1 -> layers 9, 10 -> + X -> row o_row of
+// pose_out (2, T, 17 each; null: not stored) and loss_out[o_row] (null: not stored).  The skips are read only (resample_stage<..,
+// ADD>).  On return RED holds the 32 row sums of the loss, published by the barrier in front of the one thread that adds them.
+// OPAQUE: the instance a caller runs in a loop (thread id and weight pointer made opaque per run, as the encoders' solo passes at
+// the top of this file); tid / wave / lane: the caller's, used as they are without OPAQUE.
+template <int T, bool OPAQUE, int NS1, int NS2>
+__device__ __forceinline__ void latent_decode_row(const float* wbuf, const DataView& dv, const FrameIdx& fi, int seg_len,
+                                                  const float* G, size_t g_row, float* pose_out, float* loss_out, size_t o_row,
+                                                  int loss_fn, int b, float* smem, float (&skip1)[NS1], float (&skip2)[NS2], int tid, int wave,
+                                                  int lane, Prof& prof) {
+    using PL = Plan<T, 1>;
+    using LD = LatentDecLds<T>;
+    constexpr int TV = T * 17, TV10 = T * 10, F = LAT_ENC_C * TV10;
+    float* const RG = smem;
+    float* const EMB = smem + LD::WORK;
+    float* const RED = EMB + LD::EMB + EDIM;
+    const float* wb = wbuf;
+    if constexpr (OPAQUE) {      // (the caller's ids serve the other instance: latent_decode_kernel's text stays what it was)
+        tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        asm volatile("" : "+s"(wb));
+    }
     // ---- G -> [P10][68]; the pad rows behind the last frame hold zeros (up3's trailing k-step reads two rows past a frame)
     for (int u = tid; u < PL::P10 * 16; u += NTHREADS) {
         const int col = u >> 4, q = u & 15;
-        const float4 v = col < TV10 ? load_global4(G + (size_t)b * F + col * LAT_ENC_C + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 v = col < TV10 ? load_global4(G + g_row * F + col * LAT_ENC_C + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
         lds_store4(lds_addr(RG + LD::G_IN + col * 68 + 4 * q), v.x, v.y, v.z, v.w);
     }
     __syncthreads();
@@ -560,14 +577,14 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float*
     }
     layer_generic<32, 32, 17, false, true, T, 1>(wb, layer_w(wb, 9), RG + PL::L9_in, RG + PL::L9_z, RG + PL::L9_out, EMB + emb_off(9), wave, lane, prof, 0);
     layer_generic<32, 16, 17, true, true, T, 1>(wb, layer_w(wb, 10), RG + PL::L10_in, RG + LD::L10_z, RG + LD::L10_out, EMB + emb_off(10), wave, lane, prof, 0);
-    // ---- + X, the pose, and the window's loss in a fixed order: one element per thread, the 16 lanes of a DPP row, then the 32
-    // row sums one after the other by one thread
+    // ---- + X, the pose, and the loss in a fixed order: one element per thread, the 16 lanes of a DPP row, then the 32 row sums one
+    // after the other by one thread
     float l = 0.f;
     if (tid < C0 * TV) {
         const int c = tid / TV, tv = tid - c * TV, t = tv / 17, v = tv - t * 17;
         const float x = load_coord(dv, b, c, fi.idx[t], v, seg_len);
         const float p = RG[LD::L10_out + tv * 20 + c] + x;
-        if (pose_out) pose_out[((size_t)b * C0 + c) * TV + tv] = p;
+        if (pose_out) pose_out[(o_row * C0 + c) * TV + tv] = p;
         l = loss_elem(p, x, loss_fn);
     }
     l = row16_sum(l);
@@ -577,7 +594,65 @@ __global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float*
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < LD::RED; ++i) s += RED[i];
-        loss_out[b] = s / (float)(C0 * TV);
+        loss_out[o_row] = s / (float)(C0 * TV);
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_decode_kernel(const float* wbuf, const DataView dv, const FrameIdx fi, int seg_len,
+                                                                    const float* __restrict__ pe_row, const float* __restrict__ cond,
+                                                                    const float* __restrict__ G, float* __restrict__ pose_out,
+                                                                    float* __restrict__ loss_out, int loss_fn, int B) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    Prof prof;
+    prof.off();
+    float skip1[RsCfg<32, 17, 12, T, 1, true>::PER * RsCfg<32, 17, 12, T, 1, true>::SK];
+    float skip2[RsCfg<64, 12, 10, T, 1, true>::PER * RsCfg<64, 12, 10, T, 1, true>::SK];
+    latent_decode_stem<T>(wbuf, dv, fi, seg_len, pe_row, cond + (size_t)b * EDIM, b, B, smem, skip1, skip2, tid, wave, lane, prof);
+    latent_decode_row<T, false>(wbuf, dv, fi, seg_len, G, (size_t)b, pose_out, loss_out, (size_t)b, loss_fn, b, smem, skip1, skip2, tid, wave, lane, prof);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Decode launch for the S generated latents of a window (mcd_latent_decode_samples): workgroup (x, y) = window
+// b0 + x of the call and its samples y spw .. min(S, (y + 1) spw) - 1.  The stem above runs ONCE per workgroup -- the skips depend on
+// the window alone and stay in registers -- then latent_decode_row once per sample on row x S + s of G (the chunk's rows, from
+// latent_unproject_kernel over the chunk's latent rows) -> pose_all[b, s] (B,S,2,T,17; null: not stored) and loss_all[b, s].
+// Samples are independent: a generated latent may be non-finite (a diverged chain), and the pad rows and pad channels of the region
+// meet zero coefficients (NaN x 0 = NaN).  A sample leaves the next one nothing but such pads -- every value a stage reads with a
+// non-zero coefficient was written by that sample's own stages -- so behind a sample whose loss is not finite the work region is
+// cleared again, as it is in front of the first; behind a finite one the pads hold finite values, as they do behind the stem.  (The
+// test is on the 32 row sums of the loss: every element of the pose is in one of them.)  The embedding rows are not written by a
+// sample and are not cleared.  A sample's bits therefore do not depend on spw, nor on the samples in front of it.
+// ------------------------------------------------------------------------------------------------
+template <int T>
+__global__ __launch_bounds__(NTHREADS, 1) void latent_decode_samples_kernel(const float* wbuf, const DataView dv, const FrameIdx fi, int seg_len,
+                                                                            const float* __restrict__ pe_row, const float* __restrict__ cond,
+                                                                            const float* __restrict__ G, float* __restrict__ pose_all,
+                                                                            float* __restrict__ loss_all, int loss_fn, int b0, int B,
+                                                                            int S, int spw) {
+    using LD = LatentDecLds<T>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const float* const RED = smem + LD::WORK + LD::EMB + EDIM;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = b0 + blockIdx.x;
+    const int s0 = blockIdx.y * spw, s1 = s0 + spw < S ? s0 + spw : S;
+    Prof prof;
+    prof.off();
+    float skip1[RsCfg<32, 17, 12, T, 1, true>::PER * RsCfg<32, 17, 12, T, 1, true>::SK];
+    float skip2[RsCfg<64, 12, 10, T, 1, true>::PER * RsCfg<64, 12, 10, T, 1, true>::SK];
+    latent_decode_stem<T>(wbuf, dv, fi, seg_len, pe_row, cond + (size_t)b * EDIM, b, B, smem, skip1, skip2, tid, wave, lane, prof);
+#pragma unroll 1
+    for (int s = s0; s < s1; ++s) {
+        latent_decode_row<T, true>(wbuf, dv, fi, seg_len, G, (size_t)blockIdx.x * S + s, pose_all, loss_all, (size_t)b * S + s, loss_fn, b, smem, skip1, skip2, tid, wave, lane, prof);
+        // every thread reads the same 32 row sums (behind the row's barrier; the next stores to RED lie behind the next row's): uniform
+        if (s + 1 < s1 && __ballot(not_finite(RED[lane & (LD::RED - 1)])) != 0ull) {
+            for (int u = tid; u < LD::WORK; u += NTHREADS) smem[u] = 0.f;
+            __syncthreads();
+        }
     }
 }
 

@@ -14,7 +14,7 @@
 //   X(unit, TP, NB, LT)          score_tiled_kernel<TP, NB, LT>
 //   X(unit, TP, NB)              score_tiled_kernel<TP, NB, false, true>: the 'E_unet' condition encoder at 13 .. 32 condition frames
 //   X(unit, T, NB, COND_IN_KERNEL, PROJECT_IN_KERNEL)   latent_encode_kernel (at the end of this file; its translation unit is mcd_latent.hip)
-//   X(unit, T)                   latent_decode_kernel<T> (likewise)
+//   X(unit, T)                   latent_decode_kernel<T>, latent_decode_samples_kernel<T> (likewise)
 #pragma once
 
 #ifndef MCD_FAST_T      // the shipped library
@@ -120,8 +120,13 @@
 // A developer build keeps the 3-frame row and the row of MCD_FAST_T, in unit 0.
 #define MCD_LATENT_DECODE_INSTANCES(X) \
     X(5, 3) X(5, 5) X(5, 6) X(6, 7) X(6, 8) X(7, 9) X(7, 10) X(8, 11) X(8, 12)
+// The decode launch for all generated latents of a window (mcd_latent_decode_samples; latent_decode_samples_kernel<T>, one window and
+// a range of its samples per workgroup), again in units of its own:
+//   X(unit, T)   latent_decode_samples_kernel<T>: the frame counts of the rows above
+#define MCD_LATENT_DECODE_SAMPLES_INSTANCES(X) \
+    X(9, 3) X(9, 5) X(9, 6) X(10, 7) X(10, 8) X(11, 9) X(11, 10) X(12, 11) X(12, 12)
 #ifndef MCD_FAST_T
-#define MCD_LATENT_UNITS 8
+#define MCD_LATENT_UNITS 12
 #else
 #define MCD_LATENT_UNITS 0
 #endif

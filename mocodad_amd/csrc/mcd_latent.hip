@@ -3,7 +3,7 @@
 // the default eight waves per workgroup (the chain kernel has its own four).  Compiled once as it is (unit 0: the dispatch, the
 // chain, projection and Philox kernels, the encode kernels of the rows of unit 0) and once per unit n = 1 .. MCD_LATENT_UNITS
 // with -DMCD_LATENT_UNIT=n (the encode / decode kernels of that unit's rows only); see MCD_LATENT_ENCODE_INSTANCES and
-// MCD_LATENT_DECODE_INSTANCES in mcd_instances.hpp.  Unit 0 also holds latent_unproject_kernel.
+// MCD_LATENT_DECODE_INSTANCES / MCD_LATENT_DECODE_SAMPLES_INSTANCES in mcd_instances.hpp.  Unit 0 also holds latent_unproject_kernel.
 #undef MCD_NWAVES      // (a developer build may name another wave count for its trajectory kernel)
 #ifndef MCD_LATENT_UNIT
 #define MCD_LATENT_UNIT 0
@@ -62,9 +62,38 @@ struct DecodeRow {
         return MCD_OK;
     }
 };
-// both tables as MCD_ROW(unit, T, row type)
+// How many of a window's S samples one workgroup of latent_decode_samples_kernel takes (the ONE statement of the rule; a heuristic,
+// measured at two batch sizes only: DESIGN.md 2.6c).  The stem is per workgroup, so a window's samples are split only while the
+// windows alone leave workgroup slots of the device empty: the fewest groups g <= S with nb g >= slots, spw = ceil(S / g).  nb >= slots:
+// g = 1, one workgroup per window and the stem once.
+inline int latent_samples_per_wg(int nb, int S, int slots) {
+    int g = (slots + nb - 1) / nb;
+    g = g < 1 ? 1 : (g > S ? S : g);
+    return (S + g - 1) / g;
+}
+// MCD_LATENT_DECODE_SAMPLES_INSTANCES (mcd_instances.hpp): X(unit, T), the decode launch for all samples of a window
+template <int T>
+struct DecodeSamplesRow {
+    using Args = LatentDecodeSamplesArgs;
+    static bool serves(int t, const Args&) { return t == T; }
+    static int launch(const Args& a) {
+        static_assert(NWAVES == 8, "the latent decode launch ships with eight waves per workgroup");
+        constexpr size_t lds = (size_t)LatentDecLds<T>::FLOATS * 4;
+        static_assert(lds <= 160 * 1024, "latent decode: more than 160 KB of LDS");
+        LDS_LIMIT((&latent_decode_samples_kernel<T>), lds);
+        static std::atomic<int> slots_cache[64];
+        const int slots = wg_slots(reinterpret_cast<const void*>(&latent_decode_samples_kernel<T>), lds, slots_cache, NTHREADS);
+        const int spw = a.force_spw > 0 ? (a.force_spw < a.S ? a.force_spw : a.S) : latent_samples_per_wg(a.nb, a.S, slots);
+        hipLaunchKernelGGL((latent_decode_samples_kernel<T>), dim3(a.nb, (a.S + spw - 1) / spw), dim3(NTHREADS), lds, a.st, a.wbuf, a.call.dv,
+                           a.call.fi, a.call.seg_len, a.call.pe_row, a.cond, a.G, a.pose_all, a.loss_all, a.loss_fn, a.b0, a.B, a.S, spw);
+        HIP_TRY(hipGetLastError());
+        return MCD_OK;
+    }
+};
+// the tables as MCD_ROW(unit, T, row type)
 #define MCD_ENCODE_ROW(unit, T, NB, CI, PIK) MCD_ROW(unit, T, EncodeRow<T, NB, CI, PIK>)
 #define MCD_DECODE_ROW(unit, T) MCD_ROW(unit, T, DecodeRow<T>)
+#define MCD_DECODE_SAMPLES_ROW(unit, T) MCD_ROW(unit, T, DecodeSamplesRow<T>)
 
 // a row's launcher in the unit that holds the row; elsewhere nothing of it is instantiated
 template <bool HERE, class Row>
@@ -82,6 +111,7 @@ int launch_latent_unit(int t, const Args& a);
 #define MCD_ROW(unit, T, ...) template <> int launch_latent_unit<latent_row_unit(unit), __VA_ARGS__::Args>(int, const __VA_ARGS__::Args&);
 MCD_LATENT_ENCODE_INSTANCES(MCD_ENCODE_ROW)
 MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
+MCD_LATENT_DECODE_SAMPLES_INSTANCES(MCD_DECODE_SAMPLES_ROW)
 #undef MCD_ROW
 
 #define MCD_ROW(unit, T, ...) \
@@ -95,6 +125,11 @@ template <>
 int launch_latent_unit<MCD_LATENT_UNIT, LatentDecodeArgs>(int t, const LatentDecodeArgs& a) {
     MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
     return fail(MCD_EUNSUPPORTED, "latent decode: no such row");
+}
+template <>
+int launch_latent_unit<MCD_LATENT_UNIT, LatentDecodeSamplesArgs>(int t, const LatentDecodeSamplesArgs& a) {
+    MCD_LATENT_DECODE_SAMPLES_INSTANCES(MCD_DECODE_SAMPLES_ROW)
+    return fail(MCD_EUNSUPPORTED, "latent decode (samples): no such row");
 }
 #undef MCD_ROW
 
@@ -140,6 +175,11 @@ std::string latent_encode_counts() {
     if (latent_row_held(T) && __VA_ARGS__::serves(t, a)) return launch_latent_unit<latent_row_unit(unit), __VA_ARGS__::Args>(t, a);
 int launch_latent_decode(int t, const LatentDecodeArgs& a) {
     MCD_LATENT_DECODE_INSTANCES(MCD_DECODE_ROW)
+    return fail(MCD_EUNSUPPORTED, "the latent decode launch has no kernel for " + std::to_string(t) + " frames");
+}
+
+int launch_latent_decode_samples(int t, const LatentDecodeSamplesArgs& a) {
+    MCD_LATENT_DECODE_SAMPLES_INSTANCES(MCD_DECODE_SAMPLES_ROW)
     return fail(MCD_EUNSUPPORTED, "the latent decode launch has no kernel for " + std::to_string(t) + " frames");
 }
 

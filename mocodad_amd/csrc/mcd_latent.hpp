@@ -95,6 +95,12 @@ bool latent_decode_has_kernel(int t);
 // G + the window's corrupt frames and cond_emb -> pose (B,2,t,17) and / or the window's mean loss against its corrupt frames (B)
 struct LatentDecodeArgs { const float* wbuf; const LatentCall& call; const float* cond; const float* G; float* pose_out; float* loss_out; int loss_fn, B; hipStream_t st; };
 int launch_latent_decode(int t, const LatentDecodeArgs& a);
+// The same for the S generated latents of each window (mcd_latent_decode_samples): nb windows b0 .. b0 + nb - 1 of the call's B, G
+// (nb S, 640 t) = the chunk's rows, window-major -> pose_all (B,S,2,t,17) (null: not wanted) and loss_all (B,S), both indexed by
+// the call's window.  force_spw > 0: that many samples per workgroup (at most S) instead of the launcher's rule
+// (latent_samples_per_wg in mcd_latent.hip); no result depends on it.
+struct LatentDecodeSamplesArgs { const float* wbuf; const LatentCall& call; const float* cond; const float* G; float* pose_all; float* loss_all; int loss_fn, b0, nb, B, S, force_spw; hipStream_t st; };
+int launch_latent_decode_samples(int t, const LatentDecodeSamplesArgs& a);
 int launch_latent_chain(const LatentChainParams& P, hipStream_t st);
 int launch_latent_philox(unsigned long long seed, long long first_window, int B, int S, int K, int D, float* out, hipStream_t st);
 

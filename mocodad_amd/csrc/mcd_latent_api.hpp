@@ -2,7 +2,8 @@
 // launchers of mcd_latent.hip.  Included at the end of mcd_api.hip, whose upload helper and condition-encoder routes it shares; the
 // front end of a call (view, checks, workspace layout, launch_cond) is mcd_call.hpp, the packers pack_latent_model / pack_latent_ae_model
 // of mcd_pack.hpp.  A handle is of one of two kinds: diffusion stage (mcd_latent_score, mcd_latent_denoise) or autoencoder (stage
-// 'pretrain': mcd_latent_reconstruct); mcd_latent_encode, the workspace size, the options and the release take both.
+// 'pretrain': mcd_latent_reconstruct, mcd_latent_decode_samples); mcd_latent_encode, the workspace size, the options and the release
+// take both.
 // It holds no device code.
 #pragma once
 #include "mcd_latent.hpp"
@@ -90,6 +91,27 @@ int make_latent_weights(int rc, const PackedModel& m, const mcd_model_cfg_t* cfg
     set_cond_weights(&w->cw, m, dbuf);
     *out = w;
     return MCD_OK;
+}
+
+// ---- mcd_latent_decode_samples: G = rev_to_time_dim of every latent row is 640 t_unet floats per row (315 MB at 1024 windows x 10
+// samples x 12 frames), so the call walks the batch in chunks of windows -- unproject + decode per chunk, on the one stream -- and G
+// never exceeds LAT_DECODE_G_BYTES.  A row of G belongs to one window and one sample: the chunking changes no bit.
+constexpr int64_t LAT_DECODE_G_BYTES = 256ll << 20;
+// bytes of G per window (S rows)
+int64_t decode_window_bytes(const mcd_latent_weights* w, int64_t S) { return S * w->g_floats * 4; }
+// the most windows a chunk may hold (>= 1: S <= LAT_MAX_S rows of a window are 31 MB at 12 frames): what the bound holds, or the
+// value of MCD_LATENT_OPT_DECODE_CHUNK if that is smaller
+int64_t decode_chunk_max(const mcd_latent_weights* w, int64_t S) {
+    const int64_t n = std::max<int64_t>(1, LAT_DECODE_G_BYTES / decode_window_bytes(w, S));
+    const int forced = w->opt[MCD_LATENT_OPT_DECODE_CHUNK];
+    return forced > 0 ? std::min<int64_t>(n, forced) : n;
+}
+// the G region the size query reserves: every row while that stays under the bound (and under the forced chunk), else the bound --
+// monotone in both arguments, and never less than the largest chunk of the call
+int64_t decode_g_bytes(const mcd_latent_weights* w, int64_t B, int64_t S) {
+    const int forced = w->opt[MCD_LATENT_OPT_DECODE_CHUNK];
+    const int64_t rows_of = forced > 0 ? std::min<int64_t>(B, forced) : B;
+    return std::min(rows_of * decode_window_bytes(w, S), LAT_DECODE_G_BYTES);
 }
 
 }  // namespace
@@ -229,6 +251,55 @@ int mcd_latent_reconstruct(const mcd_latent_weights_t* w, const mcd_score_cfg_t*
     }
     if (cond_emb_out) HIP_TRY(hipMemcpyAsync(cond_emb_out, R.cond, (size_t)B * EDIM * 4, hipMemcpyDeviceToDevice, st));
     if (z0_out) HIP_TRY(hipMemcpyAsync(z0_out, R.z0, (size_t)B * D * 4, hipMemcpyDeviceToDevice, st));
+    return MCD_OK;
+}
+
+int64_t mcd_latent_decode_workspace_bytes(const mcd_latent_weights_t* w, int32_t n_windows, int32_t n_samples) {
+    if (!w || !w->ae || n_windows <= 0 || n_samples < 1 || n_samples > LAT_MAX_S) return 0;
+    return latent_decode_workspace(&w->cw, n_windows, decode_g_bytes(w, n_windows, n_samples)).bytes;
+}
+
+int mcd_latent_decode_samples(const mcd_latent_weights_t* w, const mcd_score_cfg_t* cfg, const float* data, const mcd_window_view_t* view,
+                              const float* step_table, void* workspace, const float* cond_emb_in, const float* latents, float* pose_all,
+                              float* loss_all, void* stream) {
+    if (!w || !cfg) return fail(MCD_EINVAL, "null argument");
+    if (!w->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_decode_samples needs an autoencoder handle (mcd_pack_latent_ae_weights): a diffusion-stage handle has no decoder");
+    const int B = cfg->n_windows, S = cfg->n_samples, D = w->net.D, T = w->cfg.t_unet;
+    if (B <= 0) return MCD_OK;
+    if (!data || !step_table || !workspace) return fail(MCD_EINVAL, "null argument (the workspace of mcd_latent_decode_workspace_bytes is required)");
+    if (!latents || !loss_all) return fail(MCD_EINVAL, "null argument (latents and loss_all are required)");
+    if (S < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
+    if (S > LAT_MAX_S) return fail(MCD_EUNSUPPORTED, "n_samples " + std::to_string(S) + ": at most " + std::to_string(LAT_MAX_S) + " per call");
+    if ((long long)B * S > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x n_samples exceeds 2^31 - 1: decode in smaller batches");
+    if (cfg->noise_steps < 2) return fail(MCD_EINVAL, "need noise_steps >= 2 (the table's row noise_steps holds t = -1)");
+    if (cfg->loss_fn < MCD_LOSS_SMOOTH_L1 || cfg->loss_fn > MCD_LOSS_MSE) return fail(MCD_EINVAL, "unknown loss_fn");
+    if (!aligned16(latents)) return fail(MCD_EINVAL, "latents must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    LatentCall c;
+    if (int rc = latent_call(w, cfg, data, view, step_table, c)) return rc;
+    const LatentDecodeWorkspace lay = latent_decode_workspace(&w->cw, B, decode_g_bytes(w, B, S));
+    auto at = [&](int64_t off) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + off); };
+    const float* cond = cond_emb_in;
+    if (!cond) {      // the handle's own condition encoder, as the launch in front of the encode launch (latent_encode_impl)
+        const CondRoute route = cond_route(&w->cw);
+        const bool plain_route = route == COND_PLAIN || route == COND_PLAIN_SCRATCH;
+        if (route != COND_FAST && route != COND_UNET && !plain_route)
+            return fail(MCD_EUNSUPPORTED, "E_unet condition encoder: frame count not instantiated");
+        if (int rc = launch_cond(&w->cw, route, c.dv, c.cond_fi, c.seg_len, at(0), B, plain_route ? at(lay.gather) : nullptr,
+                                 plain_route ? at(lay.plain) : nullptr, st)) return rc;
+        cond = at(0);
+    }
+    // chunks of equal size (the last one may be shorter), none above decode_chunk_max
+    const int64_t cmax = decode_chunk_max(w, S), n_chunks = (B + cmax - 1) / cmax;
+    const int chunk = (int)((B + n_chunks - 1) / n_chunks);
+    float* const G = at(lay.g);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = std::min(chunk, B - b0);
+        if (int rc = launch_latent_unproject(T, w->dbuf, latents + (size_t)b0 * S * D, G, D, nb * S, st)) return rc;
+        if (int rc = launch_latent_decode_samples(T, {w->dbuf, c, cond, G, pose_all, loss_all, cfg->loss_fn, b0, nb, B, S,
+                                                      w->opt[MCD_LATENT_OPT_DECODE_SPW], st})) return rc;
+    }
     return MCD_OK;
 }
 

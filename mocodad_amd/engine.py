@@ -135,7 +135,8 @@ class _Scorer:
     def set_option(self, name: str, value: int) -> None:
         """Per-handle switch of the library (include/mocodad_hip.h): MCD_OPT_* 'variant', 'cond_generic', 'generic_unet', 'split',
         'phase' on a HipScorer; MCD_LATENT_OPT_* 'split_encode' on a LatentScorer (1 makes the shipped configuration take the
-        three-launch form, condition encoder as its own launch, as well)."""
+        three-launch form, condition encoder as its own launch, as well); 'decode_spw' / 'decode_chunk' on a LatentReconstructor
+        (test aids of decode_samples: samples per workgroup, windows per chunk; 0 = the library's rules; no result depends on them)."""
         if name not in self._OPTIONS:
             raise ValueError(f"unknown option {name!r} (known: {sorted(self._OPTIONS)})")
         _lib.check(getattr(self.L, self._SET_OPTION)(self._h, self._OPTIONS[name], int(value)))
@@ -194,6 +195,105 @@ class _Scorer:
         if cond_mask is not None and cond_mask.numel() != out[2]:
             raise ValueError(f"cond_mask must have {out[2]} entries")
         return out
+
+
+    # ------------------------------------------------------------------ handle-free entries on poses: any scorer whose calls
+    # yield (loss_all (B,S), poses_all (B,S,C,Tx,V)) -- HipScorer.score, LatentReconstructor.decode_samples -- has them
+    def _scratch(self, kind: str, numel: int) -> torch.Tensor:
+        """`numel` floats of the current stream's scratch buffer `kind` (the poses / per-sample losses a maps launch reads when the
+        caller did not ask for them): grown on demand, reused by the next call.  Call inside `torch.cuda.device(self.device)`."""
+        key = (kind, torch.cuda.current_stream().cuda_stream)
+        buf = self._map_bufs.get(key)
+        if buf is None or buf.numel() < numel:
+            buf = self._map_bufs[key] = torch.empty(max(numel, 1), device=self.device, dtype=torch.float32)
+        return buf[:numel]
+
+    def error_maps(self, data, loss_all: Optional[torch.Tensor], poses_all: torch.Tensor, strategy: str, *, loss_fn: str = "smooth_l1",
+                   cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mcd_error_maps: which joints and forecast frames a window's score comes from.  data: the windows the poses were
+        scored on ((B,C,T,V) tensor or WindowBatch: the ground truth is read through the view, transform applied); loss_all (B,S)
+        (None for 'all', 'mean', 'mean_pose', 'median_pose', which do not read it); poses_all (B,S,C,Tx,V); strategy: 'all' |
+        'best' | 'worst' | 'mean' | 'median' | 'quantile:q' | 'mean_pose' | 'median_pose' -> M (B,Tx,V), for 'all' E (B,S,Tx,V).
+        cond_mask ('random_imp'): the batch's (B,) condition-frame bitmasks.  Asynchronous on the current stream."""
+        name, q = _aggregation_of(strategy, list(_lib.AGGR), f"Unknown aggregation strategy {strategy}")
+        if cond_mask is not None:
+            cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
+        data, view, B, keep = self._windows(data, cond_mask)
+        poses_all = _f32c(poses_all, self.device)
+        Tx = len(self.corrupt_idx)
+        if poses_all.dim() != 5 or poses_all.shape[0] != B or tuple(poses_all.shape[2:]) != (self.num_coords, Tx, self.n_joints):
+            raise ValueError(f"poses_all must have shape ({B}, S, {self.num_coords}, {Tx}, {self.n_joints}), got {tuple(poses_all.shape)}")
+        S = int(poses_all.shape[1])
+        if loss_all is not None:
+            loss_all = _f32c(loss_all, self.device)
+            if tuple(loss_all.shape) != (B, S):
+                raise ValueError(f"loss_all must have shape ({B}, {S}), got {tuple(loss_all.shape)}")
+        elif name not in ("all", "mean", "mean_pose", "median_pose"):
+            raise ValueError(f"the {name!r} maps select samples by their losses: loss_all is required")
+        with torch.cuda.device(self.device):
+            maps = self._maps_launch(data, view, B, S, name, q, loss_all, poses_all, loss_fn)
+        del keep
+        return maps
+
+    def _maps_launch(self, data, view, B, S, name, q, loss_all, poses_all, loss_fn) -> torch.Tensor:
+        Tx = len(self.corrupt_idx)
+        shape = (B, S, Tx, self.n_joints) if name == "all" else (B, Tx, self.n_joints)
+        maps = torch.empty(shape, device=self.device, dtype=torch.float32)
+        cfg = self._score_cfg(B, S, 2, loss_fn)
+        _lib.check(self.L.mcd_error_maps(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q), _ptr(loss_all),
+                                         _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None, _ptr(maps),
+                                         _stream()))
+        return maps
+
+    def joint_scatter_max(self, maps: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
+        """mcd_joint_scatter_max: maps (N,Tx,V), frames (N,Tx) 1-based frame id of each map row, row (N,) output row
+        -> (n_rows, n_frames, V): per joint the maximum over the windows forecasting the frame; 0 where none does."""
+        maps, frames, row = _f32c(maps, self.device), _i32c(frames, self.device), _i32c(row, self.device)
+        n = int(row.numel())
+        if maps.dim() != 3 or maps.shape[0] != n or maps.shape[2] != 17 or tuple(frames.shape) != (n, maps.shape[1]):
+            raise ValueError(f"need maps (N, Tx, 17), frames (N, Tx) and row (N,), got {tuple(maps.shape)}, {tuple(frames.shape)}, {tuple(row.shape)}")
+        out = torch.empty(int(n_rows), int(n_frames), 17, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_joint_scatter_max(_ptr(maps), _ptr(frames), _ptr(row), n, int(maps.shape[1]), int(n_rows), int(n_frames),
+                                                    _ptr(out), _stream()))
+        return out
+
+    def aggregate(self, data: torch.Tensor, loss_all: torch.Tensor, poses_all: Optional[torch.Tensor], strategy: str,
+                  *, noise_steps: int, loss_fn: str = "smooth_l1", want_pose: bool = True,
+                  out: Optional[torch.Tensor] = None, cond_mask: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """_aggregation_strategy of the reference on device -> (selected pose | None, loss (B,)).
+        out: optional preallocated contiguous fp32 (B,) device tensor receiving the loss.
+        cond_mask (random_imp): the batch's (B,) condition-frame bitmasks -- the *_pose strategies take each window's
+        ground-truth corrupt frames from it (mcd_aggregate_view)."""
+        B, S = loss_all.shape
+        # the C ABI takes dense (B,S) / (B,S,C,Tx,V) tensors: views with other strides (e.g. a transposed (S,B) stack) are copied
+        loss_all = _f32c(loss_all, self.device)
+        if poses_all is not None:
+            poses_all = _f32c(poses_all, self.device)
+        name, q = _aggregation_of(strategy, [a for a in _lib.AGGR if a != "all"], f"Unknown aggregation strategy {strategy}")
+        cfg = self._score_cfg(B, S, int(noise_steps), loss_fn)
+        needs_data = name in ("mean_pose", "median_pose")
+        if torch.is_tensor(data):
+            data = _f32c(data, self.device)
+        elif needs_data:
+            raise ValueError("the *_pose aggregation strategies need the materialised (B,C,T,V) windows")
+        else:
+            data = None
+        out = _out_vector(out, B, self.device)
+        gives_pose = name in ("best", "worst", "mean_pose", "median_pose")
+        pose = None
+        if gives_pose and want_pose and poses_all is not None:
+            pose = torch.empty(poses_all.shape[0], *poses_all.shape[2:], device=self.device, dtype=torch.float32)
+        if cond_mask is not None:
+            cond_mask = _i32c(cond_mask, self.device)
+            if cond_mask.numel() != B:
+                raise ValueError(f"cond_mask must have {B} entries")
+        view = _window_view(None, cond_mask) if cond_mask is not None else None      # (no mask: a null view, cfg's corrupt_idx)
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
+                                                 _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None,
+                                                 _ptr(out), _ptr(pose), _stream()))
+        return pose, out
 
 
 class HipScorer(_Scorer):
@@ -295,65 +395,6 @@ class HipScorer(_Scorer):
         r = self._score(data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask,
                         aggregation=aggregation, want_all=want_all, out=out, want_maps=want_maps)
         return r if want_maps else r[:3]
-
-    def _scratch(self, kind: str, numel: int) -> torch.Tensor:
-        """`numel` floats of the current stream's scratch buffer `kind` (the poses / per-sample losses a maps launch reads when the
-        caller did not ask for them): grown on demand, reused by the next call.  Call inside `torch.cuda.device(self.device)`."""
-        key = (kind, torch.cuda.current_stream().cuda_stream)
-        buf = self._map_bufs.get(key)
-        if buf is None or buf.numel() < numel:
-            buf = self._map_bufs[key] = torch.empty(max(numel, 1), device=self.device, dtype=torch.float32)
-        return buf[:numel]
-
-    def error_maps(self, data, loss_all: Optional[torch.Tensor], poses_all: torch.Tensor, strategy: str, *, loss_fn: str = "smooth_l1",
-                   cond_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """mcd_error_maps: which joints and forecast frames a window's score comes from.  data: the windows the poses were
-        scored on ((B,C,T,V) tensor or WindowBatch: the ground truth is read through the view, transform applied); loss_all (B,S)
-        (None for 'all', 'mean', 'mean_pose', 'median_pose', which do not read it); poses_all (B,S,C,Tx,V); strategy: 'all' |
-        'best' | 'worst' | 'mean' | 'median' | 'quantile:q' | 'mean_pose' | 'median_pose' -> M (B,Tx,V), for 'all' E (B,S,Tx,V).
-        cond_mask ('random_imp'): the batch's (B,) condition-frame bitmasks.  Asynchronous on the current stream."""
-        name, q = _aggregation_of(strategy, list(_lib.AGGR), f"Unknown aggregation strategy {strategy}")
-        if cond_mask is not None:
-            cond_mask = cond_mask.to(self.device, torch.int32).contiguous()
-        data, view, B, keep = self._windows(data, cond_mask)
-        poses_all = _f32c(poses_all, self.device)
-        Tx = len(self.corrupt_idx)
-        if poses_all.dim() != 5 or poses_all.shape[0] != B or tuple(poses_all.shape[2:]) != (self.num_coords, Tx, self.n_joints):
-            raise ValueError(f"poses_all must have shape ({B}, S, {self.num_coords}, {Tx}, {self.n_joints}), got {tuple(poses_all.shape)}")
-        S = int(poses_all.shape[1])
-        if loss_all is not None:
-            loss_all = _f32c(loss_all, self.device)
-            if tuple(loss_all.shape) != (B, S):
-                raise ValueError(f"loss_all must have shape ({B}, {S}), got {tuple(loss_all.shape)}")
-        elif name not in ("all", "mean", "mean_pose", "median_pose"):
-            raise ValueError(f"the {name!r} maps select samples by their losses: loss_all is required")
-        with torch.cuda.device(self.device):
-            maps = self._maps_launch(data, view, B, S, name, q, loss_all, poses_all, loss_fn)
-        del keep
-        return maps
-
-    def _maps_launch(self, data, view, B, S, name, q, loss_all, poses_all, loss_fn) -> torch.Tensor:
-        Tx = len(self.corrupt_idx)
-        shape = (B, S, Tx, self.n_joints) if name == "all" else (B, Tx, self.n_joints)
-        maps = torch.empty(shape, device=self.device, dtype=torch.float32)
-        cfg = self._score_cfg(B, S, 2, loss_fn)
-        _lib.check(self.L.mcd_error_maps(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q), _ptr(loss_all),
-                                         _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None, _ptr(maps),
-                                         _stream()))
-        return maps
-
-    def joint_scatter_max(self, maps: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
-        """mcd_joint_scatter_max: maps (N,Tx,V), frames (N,Tx) 1-based frame id of each map row, row (N,) output row
-        -> (n_rows, n_frames, V): per joint the maximum over the windows forecasting the frame; 0 where none does."""
-        maps, frames, row = _f32c(maps, self.device), _i32c(frames, self.device), _i32c(row, self.device)
-        n = int(row.numel())
-        if maps.dim() != 3 or maps.shape[0] != n or maps.shape[2] != 17 or tuple(frames.shape) != (n, maps.shape[1]):
-            raise ValueError(f"need maps (N, Tx, 17), frames (N, Tx) and row (N,), got {tuple(maps.shape)}, {tuple(frames.shape)}, {tuple(row.shape)}")
-        out = torch.empty(int(n_rows), int(n_frames), 17, device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_joint_scatter_max(_ptr(maps), _ptr(frames), _ptr(row), n, int(maps.shape[1]), int(n_rows), int(n_frames),
-                                                    _ptr(out), _stream()))
-        return out
 
     def _score(self, data, n_samples, noise_steps, noise, seed, first_window_id, loss_fn, want_poses, cond_mask, *, aggregation,
                want_all, out, want_maps=False):
@@ -458,43 +499,6 @@ class HipScorer(_Scorer):
                                                    len(self.cond_idx), _ptr(out), _stream()))
         return out
 
-    def aggregate(self, data: torch.Tensor, loss_all: torch.Tensor, poses_all: Optional[torch.Tensor], strategy: str,
-                  *, noise_steps: int, loss_fn: str = "smooth_l1", want_pose: bool = True,
-                  out: Optional[torch.Tensor] = None, cond_mask: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
-        """_aggregation_strategy of the reference on device -> (selected pose | None, loss (B,)).
-        out: optional preallocated contiguous fp32 (B,) device tensor receiving the loss.
-        cond_mask (random_imp): the batch's (B,) condition-frame bitmasks -- the *_pose strategies take each window's
-        ground-truth corrupt frames from it (mcd_aggregate_view)."""
-        B, S = loss_all.shape
-        # the C ABI takes dense (B,S) / (B,S,C,Tx,V) tensors: views with other strides (e.g. a transposed (S,B) stack) are copied
-        loss_all = _f32c(loss_all, self.device)
-        if poses_all is not None:
-            poses_all = _f32c(poses_all, self.device)
-        name, q = _aggregation_of(strategy, [a for a in _lib.AGGR if a != "all"], f"Unknown aggregation strategy {strategy}")
-        cfg = self._score_cfg(B, S, int(noise_steps), loss_fn)
-        needs_data = name in ("mean_pose", "median_pose")
-        if torch.is_tensor(data):
-            data = _f32c(data, self.device)
-        elif needs_data:
-            raise ValueError("the *_pose aggregation strategies need the materialised (B,C,T,V) windows")
-        else:
-            data = None
-        out = _out_vector(out, B, self.device)
-        gives_pose = name in ("best", "worst", "mean_pose", "median_pose")
-        pose = None
-        if gives_pose and want_pose and poses_all is not None:
-            pose = torch.empty(poses_all.shape[0], *poses_all.shape[2:], device=self.device, dtype=torch.float32)
-        if cond_mask is not None:
-            cond_mask = _i32c(cond_mask, self.device)
-            if cond_mask.numel() != B:
-                raise ValueError(f"cond_mask must have {B} entries")
-        view = _window_view(None, cond_mask) if cond_mask is not None else None      # (no mask: a null view, cfg's corrupt_idx)
-        with torch.cuda.device(self.device):
-            _lib.check(self.L.mcd_aggregate_view(C.byref(cfg), self.num_coords, self.n_joints, _lib.AGGR[name], C.c_float(q),
-                                                 _ptr(loss_all), _ptr(poses_all), _ptr(data), C.byref(view) if view is not None else None,
-                                                 _ptr(out), _ptr(pose), _stream()))
-        return pose, out
-
     def scatter_max(self, scores: torch.Tensor, frames: torch.Tensor, row: torch.Tensor, n_rows: int, n_frames: int) -> torch.Tensor:
         scores, frames, row = _f32c(scores, self.device), _i32c(frames, self.device), _i32c(row, self.device)
         out = torch.empty(n_rows, n_frames, device=self.device, dtype=torch.float32)
@@ -588,11 +592,13 @@ class LatentScorer(_LatentHandle):
 
     def score(self, data, *, n_samples: int, noise_steps: int, aggregation: str = "all", noise: Optional[torch.Tensor] = None,
               seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_all: bool = False, want_latents: bool = False,
-              want_code: bool = False, out: Optional[torch.Tensor] = None):
+              want_code: bool = False, out: Optional[torch.Tensor] = None, want_cond: bool = False):
         """One MoCoDADlatent.forward (mcd_latent_score) -> (loss_agg (B,) | None, loss_all (B,S) | None, latent_all (B,S,D) | None,
         latent_code (B,D) | None).  aggregation: 'all' (per-sample losses only) or best | worst | mean | median | quantile:q.
         noise: (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream.  out: optional preallocated (B,) tensor the
-        aggregated losses are written into (it is then the first result).  Asynchronous on the current stream."""
+        aggregated losses are written into (it is then the first result).  want_cond: a fifth result, cond_emb (B,16) as the call
+        computed it -- a view of the head of this stream's workspace (where mcd_latent_score leaves it), valid until the scorer's
+        next call on the stream.  Asynchronous on the current stream."""
         data, view, B, keep = self._windows(data)
         S, ns, D = int(n_samples), int(noise_steps), self.latent_dim
         if S < 1 or ns < 2:
@@ -620,6 +626,8 @@ class LatentScorer(_LatentHandle):
                                                    _ptr(self.table(ns)), _ptr(ws), _lib.AGGR[name], C.c_float(q), _ptr(agg), _ptr(loss),
                                                    _ptr(lat), _ptr(code), _stream()))
         del keep
+        if want_cond:
+            return agg, loss, lat, code, ws[:B * self.emb_dim * 4].view(torch.float32).view(B, self.emb_dim)
         return agg, loss, lat, code
 
     def philox_noise(self, n_windows: int, *, n_samples: int, noise_steps: int, seed: int = 0, first_window_id: int = 0) -> torch.Tensor:
@@ -639,7 +647,9 @@ class LatentReconstructor(_LatentHandle):
     state_dict: the reference's keys ('model.*' with the up path and rev_to_time_dim, 'condition_encoder.*'; no 'denoiser.*').
     The other arguments are LatentScorer's without hidden_sizes.  3 or 5 .. 12 corrupt frames, 1 .. 12 condition frames.  A call is
     [condition encoder] -> encode -> [project] -> unproject -> decode; the workspace holds cond_emb, z0 and one
-    n_windows x 640 x corrupt-frames region (the encoder's last activation, then the decoder's first)."""
+    n_windows x 640 x corrupt-frames region (the encoder's last activation, then the decoder's first).  decode_samples decodes the
+    (B,S,D) latents another model generated for the windows -- the diffusion stage's, whose decoder this handle is
+    (MoCoDADlatent.load_decoder) -- in one call; aggregate / error_maps / joint_scatter_max of the base class take its results."""
 
     _PACK = "mcd_pack_latent_ae_weights"
 
@@ -671,6 +681,36 @@ class LatentReconstructor(_LatentHandle):
                                                          _ptr(cond), _ptr(code), _stream()))
         del keep
         return pose, loss, cond, code
+
+    def decode_samples(self, data, latents: torch.Tensor, cond_emb: Optional[torch.Tensor] = None, *, want_poses: bool = True,
+                       loss_fn: str = "smooth_l1", noise_steps: int = 2):
+        """The decoder on all generated latents of each window (mcd_latent_decode_samples): latents (B,S,D) -- e.g. latent_all of
+        LatentScorer.score -- -> (pose_all (B,S,2,t_unet,17) | None, loss_all (B,S)): sample s of window b decoded with the window's
+        own skips and condition, and its mean loss_fn against the window's corrupt frames; column s is bit for bit
+        reconstruct(data, z=latents[:, s]).  cond_emb: (B,16) as LatentScorer.encode / score computed it for these windows (None:
+        this handle's condition encoder runs in front).  The results have the layout of HipScorer.score's: `aggregate` and
+        `error_maps` take them.  Asynchronous on the current stream."""
+        data, view, B, keep = self._windows(data)
+        D, dev = self.latent_dim, self.device
+        if latents.dim() != 3 or latents.shape[0] != B or latents.shape[1] < 1 or latents.shape[2] != D:
+            raise ValueError(f"latents must have shape ({B}, S >= 1, {D}), got {tuple(latents.shape)}")
+        latents = _f32c(latents, dev)
+        S = int(latents.shape[1])
+        if cond_emb is not None:
+            if tuple(cond_emb.shape) != (B, self.emb_dim):
+                raise ValueError(f"cond_emb must have shape ({B}, {self.emb_dim}), got {tuple(cond_emb.shape)}")
+            cond_emb = _f32c(cond_emb, dev)
+        poses = torch.empty(B, S, self.num_coords, len(self.corrupt_idx), self.n_joints, device=dev, dtype=torch.float32) if want_poses else None
+        loss = torch.empty(B, S, device=dev, dtype=torch.float32)
+        cfg = self._score_cfg(B, S, int(noise_steps), loss_fn)
+        with torch.cuda.device(dev):
+            ws = self._workspace(int(self.L.mcd_latent_decode_workspace_bytes(self._h, B, S)))
+            if B:
+                _lib.check(self.L.mcd_latent_decode_samples(self._h, C.byref(cfg), _ptr(data), C.byref(view) if view is not None else None,
+                                                            _ptr(self.table(int(noise_steps))), _ptr(ws), _ptr(cond_emb), _ptr(latents),
+                                                            _ptr(poses), _ptr(loss), _stream()))
+        del keep
+        return poses, loss
 
 
 def _scaler_stats(center, scale, dev) -> list:

@@ -13,8 +13,15 @@ to_time_dim is one more launch between the encoder and the chain.
 Reference: models/mocodad_latent.py (forward :69-132), models/common/components.py:203-291 (Denoiser),
 models/stsae/stsae_unet.py:8-251 (STSE_Unet).  `stage: pretrain` is mocodad_latent_pretrain.MoCoDADlatentPretrain; training is outside
 the accelerated path.
+
+Extension, pose space: the reference trains the diffusion stage with `model` and `condition_encoder` loaded from the stage-1
+checkpoint and frozen (mocodad_latent.py:223-228), so stage 1's rev_to_time_dim and up path decode the latents this stage
+generates.  `load_decoder` takes them from the stage-1 checkpoint (`pretrained_model_ckpt_path`); `latent_score_space: 'pose'`
+(or forward(space='pose')) then decodes the S generated latents of every window (mcd_latent_decode_samples), takes the loss against
+the window's corrupt frames and aggregates as the pose model does -- which is what `return_maps` and the *_pose aggregations need.
 """
 import argparse
+import os
 from typing import List, Optional
 
 import numpy as np
@@ -62,6 +69,10 @@ class DenoiserParams(nn.Module):
 
 
 LOSS_FNS = {"smooth_l1": F.smooth_l1_loss, "l1": F.l1_loss, "mse": F.mse_loss}
+SCORE_SPACES = ("latent", "pose")
+# the tensors the two stages' checkpoints share (frozen while stage 2 trains): everything of this module's `model` -- the down path
+# and to_time_dim -- and the condition encoder
+SHARED_PREFIXES = ("model.", "condition_encoder.")
 
 
 class LatentStage(MoCoDAD):
@@ -98,7 +109,17 @@ class MoCoDADlatent(LatentStage):
                                       "mocodad_amd.models.mocodad_latent_pretrain.MoCoDADlatentPretrain (training: the reference implementation)")
         if args.stage != "diffusion":
             raise ValueError(f"Unknown stage {args.stage}")
+        self.latent_score_space = self._check_space(getattr(args, "latent_score_space", None) or "latent")
         super().__init__(args)
+        self._decoder_sd = None       # load_decoder: the autoencoder's state_dict (a plain dict: no parameter of this module)
+        self._decoder = None          # ... its engine.LatentReconstructor, built lazily per device
+        self._decoder_key = None
+
+    @staticmethod
+    def _check_space(space: str) -> str:
+        if space not in SCORE_SPACES:
+            raise ValueError(f"latent_score_space must be one of {SCORE_SPACES}, got {space!r}")
+        return space
 
     def build_model(self) -> None:
         super().build_model()
@@ -111,23 +132,89 @@ class MoCoDADlatent(LatentStage):
         from ..engine import LatentScorer
         return LatentScorer(self.state_dict(), hidden_sizes=self.hidden_sizes, **self._scorer_kwargs(device))
 
+    # -------------------------------------------------------------- the stage-1 decoder
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        self._decoder_sd = self._decoder = None      # (its copies of the shared tensors are stale: call load_decoder again)
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def load_decoder(self, source=None, *, check: bool = True) -> None:
+        """Takes the decoder of the generated latents -- rev_to_time_dim and the up path -- from a stage-1 ('pretrain') checkpoint.
+        source: its state_dict, a checkpoint path, or None = `pretrained_model_ckpt_path`.  The autoencoder handle is packed from
+        the stage-1 tensors this module lacks plus this module's OWN down path, to_time_dim and condition encoder.
+        check: every tensor the two stages share must be torch.equal between the checkpoint and this module (they are when stage 2
+        was trained from that checkpoint with both frozen); ValueError naming the first key that is not.  check=False skips that.
+        Nothing is registered: state_dict() and loading a diffusion checkpoint are what they were (load_state_dict drops the
+        decoder: call this after it)."""
+        if source is None:
+            source = self.pretrained_model_ckpt_path
+            if not source:
+                raise ValueError("load_decoder: no source given and pretrained_model_ckpt_path is not set")
+        if isinstance(source, (str, os.PathLike)):
+            if not os.path.exists(source):
+                raise FileNotFoundError(f"load_decoder: stage-1 checkpoint {source} not found")
+            source = torch.load(source, map_location="cpu", weights_only=False)
+            source = source.get("state_dict", source)
+        own = self.state_dict()
+        shared = [k for k in own if k.startswith(SHARED_PREFIXES)]
+        if check:
+            for k in shared:
+                if k not in source:
+                    raise ValueError(f"load_decoder: the stage-1 checkpoint has no tensor {k!r}")
+                a, b = source[k].detach().cpu(), own[k].detach().cpu()
+                if a.shape != b.shape or not torch.equal(a, b):
+                    raise ValueError(f"load_decoder: tensor {k!r} differs between the stage-1 checkpoint and this module "
+                                     "(the stages share the down path, to_time_dim and the condition encoder; check=False decodes "
+                                     "with this module's own)")
+        for k in ("model.rev_to_time_dim.weight", "model.rev_to_time_dim.bias"):
+            if k not in source:
+                raise ValueError(f"load_decoder: the stage-1 checkpoint has no tensor {k!r} (not a 'pretrain' checkpoint?)")
+        # the decoder half of stage 1 (what `model` holds there and not here: the up path, rev_to_time_dim) + this module's own tensors
+        sd = {k: v.detach().clone().cpu() for k, v in source.items() if torch.is_tensor(v) and k.startswith("model.") and k not in own}
+        sd.update({k: own[k].detach().clone().cpu() for k in shared})
+        self._decoder_sd, self._decoder, self._decoder_key = sd, None, None
+
+    def decoder(self):
+        """engine.LatentReconstructor of the loaded decoder on the module's current device (packed lazily, like scorer())."""
+        if self._decoder_sd is None:
+            raise RuntimeError("MoCoDADlatent has no decoder: call load_decoder(stage-1 state_dict or checkpoint path) first")
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} (mocodad_amd) scores on an MI355X only: move the module to a cuda device "
+                               "(there is no CPU fallback)")
+        if self._decoder is None or self._decoder_key != str(dev):
+            from ..engine import LatentReconstructor
+            self._decoder = LatentReconstructor(self._decoder_sd, **self._scorer_kwargs(dev))
+            self._decoder_key = str(dev)
+        return self._decoder
+
     # -------------------------------------------------------------- forward
     def _loss(self, x: torch.Tensor, z0: torch.Tensor) -> torch.Tensor:
         return LOSS_FNS[self.loss_name](x, z0.expand_as(x), reduction="none").mean(dim=-1)
 
     def forward(self, input_data: List[torch.Tensor], condition_data: torch.Tensor = None, aggr_strategy: str = 'best', *,
                 return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,
-                return_maps: bool = False) -> List[torch.Tensor]:
+                return_maps: bool = False, space: Optional[str] = None) -> List[torch.Tensor]:
         """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or selected latent] + the inputs, as
         mocodad_latent.py:69-129 (`condition_data` is unused there too; `aggr_strategy` defaults to 'best', None = the module's).
 
         noise (extension, keyword only): (S, max(ns-1,1), B, D) replacing the in-kernel Philox stream -- slot 0 = the x_T of
         torch.randn (:109), slot k = the randn_like of step ns-k (:121), in call order.  window_offset keys the Philox stream.
-        return_maps: NotImplementedError -- the error maps of MoCoDAD.forward are per joint and forecast frame, and a latent has
-        no joints."""
-        if return_maps:
+        space (extension, keyword only; None = the module's `latent_score_space`): 'latent' -- the list above, the loss taken on
+        the latent -- or 'pose' (needs load_decoder): the S generated latents of every window are decoded to forecasts, the loss
+        is taken against the window's corrupt frames and aggregated as MoCoDAD.forward does, every strategy of the pose model
+        included (mean_pose / median_pose on poses); return_ 'pose' gives the selected decoded forecast (B,2,Tx,17).
+        return_maps: with a decoder it implies pose space and appends maps (B,Tx,V) and map_frames (B,Tx) exactly as
+        MoCoDAD.forward does (mcd_error_maps on the decoded forecasts).  Without one: NotImplementedError -- the error maps are
+        per joint and forecast frame, and a latent has no joints."""
+        if return_maps and self._decoder_sd is None:
             raise NotImplementedError("MoCoDADlatent has no error maps: its loss is taken on a latent code, and a latent has no joints "
-                                      "(return_maps is for the pose model, MoCoDAD)")
+                                      "(return_maps is for the pose model, MoCoDAD -- or call load_decoder first: the stage-1 "
+                                      "decoder turns the generated latents into forecasts)")
+        space = "pose" if return_maps else self._check_space(self.latent_score_space if space is None else space)
+        if space == "pose":
+            if self._decoder_sd is None:
+                raise RuntimeError("latent_score_space 'pose' needs the stage-1 decoder: call load_decoder first")
+            return self._forward_pose(input_data, aggr_strategy, return_, noise, window_offset, return_maps)
         tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         loss_based = aggr in ("mean", "median") or "quantile" in aggr
         if (loss_based or aggr in ("best", "worst")) and (ret == "loss" or loss_based):
@@ -137,6 +224,25 @@ class MoCoDADlatent(LatentStage):
             _, loss_all, lat, z0 = sc.score(tensor_data, aggregation="all", want_latents=True, want_code=True, **kw)
             selected, loss = self._aggregate_latents(lat, loss_all, z0, aggr)
         return self._pack_out_data(selected, loss, [tensor_data] + meta_out, return_=ret)
+
+    def _forward_pose(self, input_data, aggr_strategy, return_, noise, window_offset, return_maps) -> List[torch.Tensor]:
+        """forward in pose space: the chain call for the latents and cond_emb, the decoder on all samples, then the pose model's
+        aggregation (and error maps) on (loss_all, pose_all)."""
+        if return_maps and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
+            raise ValueError("return_maps: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
+        tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
+        dec = self.decoder()
+        want_pose = ret in ("pose", "all") or aggr in ("all", "random", "mean_pose", "median_pose")
+        if hasattr(tensor_data, "as_view") and aggr in ("mean_pose", "median_pose"):
+            tensor_data = tensor_data.materialize()      # the *_pose strategies compare against the windows themselves
+        _, _, lat, _, cond = sc.score(tensor_data, aggregation="all", want_latents=True, want_cond=True, **kw)
+        poses_all, loss_all = dec.decode_samples(tensor_data, lat, cond, want_poses=want_pose or return_maps, loss_fn=self.loss_name)
+        selected, loss = self._aggregate(dec, tensor_data, loss_all, poses_all, aggr, want_pose)
+        out = self._pack_out_data(selected, loss, [tensor_data] + meta_out, return_=ret)
+        if not return_maps:
+            return out
+        maps = dec.error_maps(tensor_data, loss_all, poses_all, aggr, loss_fn=self.loss_name)
+        return out + [maps, self.map_frames(None, maps.shape[0])]
 
     def _aggregate_latents(self, lat: torch.Tensor, loss_all: torch.Tensor, z0: torch.Tensor, aggr: str):
         """_aggregation_strategy (mocodad.py:454-520) on the (B,S,D) latents and (B,S) losses the chain launch wrote: device

@@ -9,6 +9,8 @@
                                                                # (default output: profiles/latent_bench_tx12.json)
     python tools/latent_bench.py --stage pretrain --corrupt-frames 12 --cond-frames 12      # the autoencoder's call, mcd_latent_reconstruct
                                                                # (default output: profiles/latent_recon_bench_tx12.json)
+    python tools/latent_bench.py --stage forecast --corrupt-frames 12 --cond-frames 12 --batches 1024 96   # generated latents -> poses
+                                                               # (default output: profiles/latent_forecast_bench_tx12.json)
 
 Shipped configuration (configs/ubnormal_latent_test.yaml: D 64, hidden [64,128,128,64], noise_steps 10, 10 samples), seeded
 random-init weights, perf mode (in-kernel Philox), batch 1024 and a batch that fills the device.  Per batch, three legs alternate
@@ -23,6 +25,11 @@ per SIMD each (v_mfma_f32_16x16x4_f32) on 256 CUs x 4 SIMDs at --clock-ghz, and 
 diffusion stage's mcd_latent_encode on a model of the same frame split and latent size: the launches the two stages share, the
 yardstick) and their difference, the unproject + decode launches; the per-launch kernel averages come from a kernel trace of this
 command (rocprofv3 --kernel-trace --stats -- python tools/latent_bench.py --stage pretrain ...), not from this script.
+--stage forecast times the pose-space scoring of the diffusion stage: the chain call (mcd_latent_score with latent_all) and
+mcd_latent_decode_samples on its latents and cond_emb, against the only way there was before that call: the chain call followed by
+S calls of mcd_latent_reconstruct(z_in = latents[:, s]).  Legs: `chain`, `decode_samples`, `decode_samples_one_wg_per_window`
+(MCD_LATENT_OPT_DECODE_SPW = S: no split of a window's samples), `reconstruct_loop` (the S calls), and the two whole sequences
+`forecast` and `baseline`; kernel averages again from a kernel trace of this command.
 No GPU: fails (a CPU run says nothing about these times)."""
 import argparse
 import json
@@ -154,6 +161,78 @@ def main_pretrain(a):
     print(json.dumps(res, indent=1))
 
 
+def main_forecast(a):
+    from mocodad_amd.models.mocodad_latent_pretrain import MoCoDADlatentPretrain
+    dev = torch.device("cuda:0")
+    Tc, Tx = int(a.cond_frames), int(a.corrupt_frames)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", f"latent_forecast_bench_tx{Tx}.json")
+    cfgs = []
+    for name in ("ubnormal_latent_pretrain.yaml", "ubnormal_latent_test.yaml"):
+        cfg = load_config(os.path.join(ROOT, "configs", name))
+        if a.cond_arch:
+            cfg.conditioning_architecture = a.cond_arch
+        cfg.seg_len, cfg.conditioning_indices = Tc + Tx, list(range(Tc))
+        cfgs.append(cfg)
+    torch.manual_seed(0)
+    ae, lat = MoCoDADlatentPretrain(cfgs[0]), MoCoDADlatent(cfgs[1]).to(dev)
+    sd = ae.state_dict()
+    sd.update({k: v.detach().cpu() for k, v in lat.state_dict().items() if k in sd})      # the tensors the two stages share
+    lat.load_decoder(sd)
+    sl, sa = lat.scorer(), lat.decoder()
+    D, T, ns, S = lat.latent_embedding_dim, lat.n_frames_corrupt, lat.noise_steps, lat.n_generated_samples
+    rev_f, up_f, again_f = decoder_flops(T, D)
+    res = {"config": {"stage": "forecast", "latent_dim": D, "frames": [T, Tc], "noise_steps": ns, "n_samples": S,
+                      "cond_arch": cfgs[0].conditioning_architecture,
+                      "launches": {"decode_samples": "per chunk of windows: unproject, decode", "reconstruct_loop": f"{S} x ([condition encoder] encode [project] unproject decode)"}},
+           "flops_per_window": {"rev_to_time_dim_per_sample": rev_f, "up_path_per_sample": up_f, "stem_for_the_skips": again_f,
+                                "decode_samples": S * (rev_f + up_f) + again_f, "decode_launches_of_the_loop": S * (rev_f + up_f + again_f)},
+           "bytes_per_window": {"G": 4 * 640 * T * S, "latents": 4 * D * S, "pose_all": 4 * 2 * T * 17 * S},
+           "device": torch.cuda.get_device_name(0), "reps": a.reps, "batches": {}}
+    gen = torch.Generator().manual_seed(1)
+    for B in (a.batches or (1024, 96)):
+        data = torch.randn(B, 2, Tc + Tx, 17, generator=gen).clamp_(-3, 3).to(dev)
+        chain = lambda: sl.score(data, n_samples=S, noise_steps=ns, aggregation="all", want_latents=True, want_cond=True, seed=1)
+        _, _, z, _, cond = chain()
+        z, cond = z.clone(), cond.clone()
+
+        def one_wg_per_window():
+            sa.set_option("decode_spw", S)
+            sa.decode_samples(data, z, cond)
+            sa.set_option("decode_spw", 0)
+
+        def loop(lat_all=z):
+            for s in range(S):
+                sa.reconstruct(data, z=lat_all[:, s])
+
+        def forecast():
+            _, _, l, _, c = chain()
+            return sa.decode_samples(data, l, c)
+
+        def baseline():
+            loop(chain()[2])
+        # the new call and the loop it replaces must agree bit for bit at the size that is timed
+        p, lo = sa.decode_samples(data, z, cond)
+        for s in (0, S - 1):
+            p1, l1, _, _ = sa.reconstruct(data, z=z[:, s])
+            assert torch.equal(p[:, s], p1) and torch.equal(lo[:, s], l1)
+        legs = {"chain": chain, "decode_samples": lambda: sa.decode_samples(data, z, cond), "decode_samples_one_wg_per_window": one_wg_per_window,
+                "reconstruct_loop": loop, "forecast": forecast, "baseline": baseline}
+        t = timed(legs, a.reps, a.warmup)
+        med = {k: v[len(v) // 2] for k, v in t.items()}
+        res["batches"][str(B)] = {
+            "ms_median": med, "ms_min": {k: v[0] for k, v in t.items()}, "ms_max": {k: v[-1] for k, v in t.items()},
+            "decode_samples_over_reconstruct_loop": med["decode_samples"] / med["reconstruct_loop"],
+            "forecast_over_baseline": med["forecast"] / med["baseline"],
+            "split_over_one_wg_per_window": med["decode_samples"] / med["decode_samples_one_wg_per_window"],
+            "windows_per_s_forecast": B / (med["forecast"] * 1e-3),
+            "decode_samples_gflops": B * res["flops_per_window"]["decode_samples"] / (med["decode_samples"] * 1e-3) / 1e9}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="default: profiles/latent_bench.json, profiles/latent_bench_tx<N>.json with --corrupt-frames N")
@@ -167,12 +246,15 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=None, help="window counts to time (default: 1024 and --fill-batch)")
     ap.add_argument("--split-encode", action="store_true", help="MCD_LATENT_OPT_SPLIT_ENCODE: the shipped configuration in three launches")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU restatement of the chain")
-    ap.add_argument("--stage", choices=["diffusion", "pretrain"], default="diffusion", help="pretrain: time mcd_latent_reconstruct")
+    ap.add_argument("--stage", choices=["diffusion", "pretrain", "forecast"], default="diffusion",
+                    help="pretrain: time mcd_latent_reconstruct; forecast: the chain call + mcd_latent_decode_samples against the loop of reconstruct calls")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("latent_bench.py needs an MI355X: nothing about these launches can be timed on a CPU")
     if a.stage == "pretrain":
         return main_pretrain(a)
+    if a.stage == "forecast":
+        return main_forecast(a)
     import latent_ref as R
     dev = torch.device("cuda:0")
     cfg = load_config(os.path.join(ROOT, "configs", "ubnormal_latent_test.yaml"))
