@@ -80,6 +80,14 @@ def main():
                     help="pose model, or the latent model scoring in pose space; one process: also write, per (scene, clip, person) row, the (n_frames, 17) per-joint frame "
                          "scores -- the scatter-max of the windows' error maps (which joints and forecast frames a score comes "
                          "from), averaged over the transforms -- with the row table and the joint names")
+    ap.add_argument("--forecast-tracks", type=str, default=None, metavar="OUT.npz",
+                    help="pose model, or the latent model scoring in pose space; one process: also write, per trajectory row (tracked "
+                         "person and video frame), the expected pose -- the forecasts of the windows covering the row collapsed into "
+                         "one, in image pixels next to the observed row -- with how many windows forecast it and how much they disagree")
+    ap.add_argument("--forecast-method", choices=("unique", "mean", "median"), default="median",
+                    help="--forecast-tracks: the pose of a row from its covering windows (extract_single_pose's `method`)")
+    ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean",
+                    help="--forecast-tracks: how the 34 per-feature standard deviations become one spread (its `std_method`)")
     ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
                     help="latent model, stage 'diffusion' (overrides the YAML's latent_score_space): 'pose' decodes the generated "
                          "latents with the stage-1 decoder of pretrained_model_ckpt_path and scores the forecasts as the pose model does")
@@ -99,6 +107,20 @@ def main():
         if getattr(args, "aggregation_strategy", "best") in ("all", "random") or "random" in str(args.conditioning_strategy):
             raise SystemExit("eval_MoCoDAD.py: --joint-scores needs one map per window with the same forecast frames under every "
                              "transform: not aggregation_strategy all / random, not the random_imp strategy")
+    if cli.forecast_tracks:      # (refusals by name, before any GPU call)
+        aggr = str(getattr(args, "aggregation_strategy", "best"))
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-tracks runs in one process (the forecasts are not gathered across ranks)")
+        if model_cls is not MoCoDAD and not pose_space:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-tracks needs the pose model, or the latent model with latent_score_space: 'pose' "
+                             "(in latent space the model forecasts a latent code, not a pose)")
+        if aggr in ("mean", "median") or "quantile" in aggr:
+            raise SystemExit(f"eval_MoCoDAD.py: --forecast-tracks needs an aggregation that selects a pose (best, worst, mean_pose, "
+                             f"median_pose): aggregation_strategy {aggr!r} aggregates losses and selects none")
+        if aggr in ("all", "random"):
+            raise SystemExit(f"eval_MoCoDAD.py: --forecast-tracks needs one forecast per window: not aggregation_strategy {aggr!r}")
+        if cli.joint_scores:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-tracks and --joint-scores are separate runs")
     pretrain = bool(getattr(model_cls, "is_pretrain", False))
     if pretrain and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("eval_MoCoDAD.py: stage 'pretrain' runs in one process (its result is one mean over all windows, not gathered scores)")
@@ -183,9 +205,19 @@ def main():
         batches = tw.batches(args.batch_size, shard.lo, shard.hi) if tw is not None else \
             synthetic.batches((data, trans, meta, frames), args.batch_size, shard.lo, shard.hi)
         maps, map_frames = [], []
+        forecasts, forecast_frames = [], []
         for i, batch in enumerate(batches):
             model._calls = shard.lo + i * args.batch_size     # global window id keys the noise stream
-            if cli.joint_scores:      # test_step with the error maps of the batch's windows beside its output
+            if cli.forecast_tracks:   # test_step with the selected forecast of the batch's windows beside its output
+                n_b, kw = int(batch[1].shape[0]), {}
+                if model.conditioning_strategy == "random_imp":      # the frame sets forward would draw, drawn here: they say which frames a window forecasts
+                    kw["cond_mask"] = model.random_imp_masks(n_b, model._calls) if model.random_imp_draw == "device" \
+                        else model.draw_random_imp_mask(n_b)
+                out = model.forward(batch, return_="all", **kw)
+                model._test_output_list.append(out[:1] + out[2:])
+                forecasts.append(out[1])
+                forecast_frames.append(model.map_frames(kw.get("cond_mask"), n_b))
+            elif cli.joint_scores:      # test_step with the error maps of the batch's windows beside its output
                 out = model.forward(batch, return_maps=True)
                 model._test_output_list.append(out[:-2])
                 maps.append(out[-2])
@@ -215,6 +247,26 @@ def main():
             np.savez(cli.joint_scores, joint_scores=js, rows=rows, row_columns=np.asarray(["scene", "clip", "person"]),
                      joint_names=np.asarray(JOINT_NAMES))
             print(f"joint scores: {js.shape[0]} (scene, clip, person) rows x {js.shape[1]} frames x {js.shape[2]} joints -> {cli.joint_scores}")
+        if cli.forecast_tracks:
+            import numpy as np
+            from mocodad_amd._lib import JOINT_NAMES
+            from mocodad_amd.engine import denormalize_poses, forecast_assemble
+            from mocodad_amd.utils.eval_utils import forecast_track_rows
+            t2 = time.perf_counter()
+            src = dict(windows=tw) if tw is not None else dict(meta=meta.numpy(), frames=frames.numpy())
+            pose, count, spread, rows, frame_ids = forecast_track_rows(
+                torch.cat(forecasts), trans.numpy(), torch.cat(forecast_frames).cpu().numpy(), forecast_assemble,
+                method=cli.forecast_method, spread_method=cli.forecast_spread, **src)
+            res = dict(rows=rows, row_columns=np.asarray(["scene", "clip", "person"]), frames=frame_ids,
+                       expected_norm=pose.cpu().numpy(), count=count.cpu().numpy(), spread=spread.cpu().numpy(),
+                       joint_names=np.asarray(JOINT_NAMES), method=np.asarray(cli.forecast_method), spread_method=np.asarray(cli.forecast_spread))
+            if getattr(tw, "raw", None) is not None:      # a dataset: row r of the buffer is CSV row r, back to its pixels
+                res["observed"] = tw.raw.poses
+                res["expected"] = denormalize_poses(pose, tw.raw.poses, tw.vid_res, *tw.scaler, count=count).cpu().numpy()
+            np.savez(cli.forecast_tracks, **res)
+            print(f"forecast tracks: {len(rows)} trajectory rows, {int((res['count'] > 0).sum())} with a forecast ({cli.forecast_method}, spread "
+                  f"{cli.forecast_spread}) -> {cli.forecast_tracks}  {time.perf_counter() - t2:.3f}s"
+                  + ("" if "expected" in res else "  (synthetic clips have no pixel rows: expected_norm only, no observed / expected)"))
     if use_dist:
         dist.destroy_process_group()
 

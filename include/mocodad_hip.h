@@ -336,6 +336,51 @@ int mcd_joint_scatter_max(const float* maps, const int32_t* frames, const int32_
 int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float vid_h,
                         const double* center, const double* scale, float* out, void* stream);
 
+/* ---- Forecast tracks: expected poses per person and frame, in pixels (added without a change of MCD_ABI_VERSION, as the pretrain
+ * stage was: two new exports and one new enum, no struct or existing signature touched).
+ *
+ * Replaces: compute_fig_matrix + extract_single_pose (utils/eval_utils.py:13-24, 37-72): the selected forecasts of many overlapping
+ * windows collapsed into ONE pose per output cell, with the disagreement of the windows covering it.
+ *   poses        (N, 2, Tx, 17) f32: the selected forecast of each window (pose_agg of mcd_aggregate)
+ *   cell         (N, Tx) i32: the output cell of every forecast frame; a value outside [0, n_cells) means "ignore" (the convention
+ *                mcd_scatter_max has for rows and frames).  A cell is whatever the caller numbers: a global trajectory row, or
+ *                row * n_frames + f - 1 for a dense (row, frame) matrix in the reference's layout
+ *   method       MCD_FORECAST_UNIQUE / MEAN / MEDIAN;  spread_method  MCD_FORECAST_MEAN / MEDIAN (over the 34 features)
+ *   max_cover    1 .. 32: the (window, frame) pairs a cell's list holds
+ *   workspace    n_cells * max_cover int32 words, caller-owned; it need not be initialised
+ *   pose_out     (n_cells, 34) f32 in the CSV's interleaved order x1,y1,...,x17,y17 (the feature order of compute_fig_matrix)
+ *   count_out    (n_cells,) i32: the pairs k covering the cell;  spread_out (n_cells,) f32
+ * All three are written for every cell by the callee; a cell no window forecasts is 0 with count 0, the convention of the frame
+ * scores.  Per cell, over its k pairs in ascending window index (within a window: ascending forecast frame), in float64, unfused,
+ * rounded to fp32 once on store:
+ *   UNIQUE  the pair of the lowest window index;  MEAN  the sum in that order / k;  MEDIAN  per feature the middle value, for an
+ *           even k the half-sum of the two middle values (np.median)
+ *   spread  per feature the population standard deviation in two passes -- the mean as above, then sqrt(sum((x - mean)^2) / k) --
+ *           then the mean of the 34 values, summed in feature order, or their median (the half-sum of ranks 16 and 17)
+ *   k > max_cover: count_out carries k, pose and spread are NaN.  (With fixed conditioning indices a frame is forecast by at most
+ *           Tx windows, under random_imp by at most seg_len <= 32.)
+ * A NaN in a forecast reaches only the cells that forecast covers.  The result does not depend on the order in which workgroups
+ * reach a cell: pairs claim list slots with int32 atomics, the reduction orders the claimed indices before it combines them.
+ * Two launches and one memset.  Argument errors (n, n_cells < 0, Tx outside 1 .. 32, max_cover outside 1 .. 32, an unknown method,
+ * n * Tx > 2^31 - 1, a null pointer -- the inputs only when n > 0) are MCD_EINVAL before any device call; n == 0 or n_cells == 0 is
+ * MCD_OK and launches nothing (n == 0: the outputs are zeroed, as mcd_scatter_max zeroes its own). */
+enum { MCD_FORECAST_UNIQUE = 0, MCD_FORECAST_MEAN = 1, MCD_FORECAST_MEDIAN = 2 };
+int mcd_forecast_assemble(const float* poses, const int32_t* cell, int64_t n, int32_t n_corrupt, int32_t n_cells, int32_t method,
+                          int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
+                          float* spread_out, void* stream);
+
+/* The inverse of mcd_normalize_poses: norm (n, 34) f32 interleaved (what mcd_forecast_assemble writes) back to image pixels in the
+ * bounding box of raw (n, 34) f32, the observed CSV row of the same person and frame -> out (n, 34) f32 interleaved.
+ * The box L, R, T, B is computed exactly as mcd_normalize_poses computes it (fp32 margin, clip, round-half-even); per element k,
+ * with s = R - L, c = (L + R) / 2 for an x feature and s = B - T, c = (T + B) / 2 for a y feature,
+ *   out = ((p * scale_k + center_k) * s + c)
+ * every operation in float64 and unfused, rounded to fp32 once (center / scale: device (34,) f64, or both NULL: p * s + c).
+ * A degenerate side (s = 0, where mcd_normalize_poses writes zeros) gives c.  count: NULL, or (n,) i32 -- a row with count 0 comes
+ * back all zero, the CSV's convention for "missing".  One thread per row.  Argument errors are MCD_EINVAL before any device call;
+ * n == 0 is MCD_OK and launches nothing.  PRECONDITION: `raw` is finite. */
+int mcd_denormalize_poses(const float* norm, const float* raw, const int32_t* count, int64_t n, float vid_w, float vid_h,
+                          const double* center, const double* scale, float* out, void* stream);
+
 /* Live pose streams: the state between two ticks of an online scorer (many tracked people, one new pose row per track per
  * video frame), in two CALLER-owned device rings.  Replaces, one tick at a time, what the dataset path does once per dataset: the
  * per-row normalisation of mcd_normalize_poses, the sliding windows over consecutive rows of a trajectory

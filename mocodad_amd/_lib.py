@@ -13,6 +13,7 @@ STRATEGY = {"inject": 0, "concat": 1, "no_condition": 2, "inbetween_imp": 3, "ra
 LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
 COND_UNET = -1  # MCD_COND_UNET
 AGGR = {"all": 0, "best": 1, "worst": 2, "mean": 3, "median": 4, "mean_pose": 5, "median_pose": 6, "quantile": 7}
+FORECAST = {"unique": 0, "mean": 1, "median": 2}      # MCD_FORECAST_*
 OPT = {"variant": 0, "cond_generic": 1, "generic_unet": 2, "split": 3, "phase": 4}     # MCD_OPT_*
 LATENT_OPT = {"split_encode": 0, "decode_spw": 1, "decode_chunk": 2}     # MCD_LATENT_OPT_*
 # the 17 joints of a pose row, in the trajectory CSVs' order (COCO keypoints): the joint axis of the error maps
@@ -106,6 +107,10 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_normalize_poses": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "mcd_forecast_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_denormalize_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "mcd_stream_flush": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_stream_push_group": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

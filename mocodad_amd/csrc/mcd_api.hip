@@ -690,6 +690,51 @@ int mcd_normalize_poses(const float* raw, int64_t n_frames, float vid_w, float v
     return MCD_OK;
 }
 
+int mcd_denormalize_poses(const float* norm, const float* raw, const int32_t* count, int64_t n, float vid_w, float vid_h,
+                          const double* center, const double* scale, float* out, void* stream) {
+    if (n < 0) return fail(MCD_EINVAL, "n < 0");
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    if (n == 0) return MCD_OK;
+    if (!norm || !raw || !out) return fail(MCD_EINVAL, "null argument");
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many rows for one launch");
+    hipLaunchKernelGGL(denormalize_poses_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, norm, raw, count,
+                       (long long)n, vid_w, vid_h, center, scale, out);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_forecast_assemble(const float* poses, const int32_t* cell, int64_t n, int32_t n_corrupt, int32_t n_cells, int32_t method,
+                          int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
+                          float* spread_out, void* stream) {
+    if (n < 0 || n_cells < 0) return fail(MCD_EINVAL, "need n, n_cells >= 0");
+    if (n_corrupt < 1 || n_corrupt > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "need 1 <= n_corrupt <= 32");
+    if (max_cover < 1 || max_cover > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "need 1 <= max_cover <= 32");
+    if (method != MCD_FORECAST_UNIQUE && method != MCD_FORECAST_MEAN && method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "method must be MCD_FORECAST_UNIQUE, MEAN or MEDIAN");
+    if (spread_method != MCD_FORECAST_MEAN && spread_method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "spread_method must be MCD_FORECAST_MEAN or MEDIAN");
+    if (n > 0x7fffffffll / n_corrupt) return fail(MCD_EINVAL, "n x n_corrupt exceeds 2^31 - 1: assemble in smaller batches");
+    if (n_cells == 0) return MCD_OK;
+    if (!workspace || !pose_out || !count_out || !spread_out) return fail(MCD_EINVAL, "null argument");
+    if (n > 0 && (!poses || !cell)) return fail(MCD_EINVAL, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ForecastParams F{poses, cell, workspace, pose_out, count_out, spread_out, (int)(n * n_corrupt), n_corrupt, n_cells, method,
+                     spread_method, max_cover};
+    HIP_TRY(hipMemsetAsync(count_out, 0, (size_t)n_cells * sizeof(int32_t), st));
+    if (n == 0) {      // nothing forecasts anything: the empty result, as mcd_scatter_max leaves it, without a launch
+        HIP_TRY(hipMemsetAsync(pose_out, 0, (size_t)n_cells * 34 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(spread_out, 0, (size_t)n_cells * sizeof(float), st));
+        return MCD_OK;
+    }
+    hipLaunchKernelGGL(forecast_claim_kernel, dim3((unsigned)((F.n_pairs + 255ll) / 256)), dim3(256), 0, st, F);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(forecast_reduce_kernel, dim3(n_cells < 65536 ? n_cells : 65536), dim3(64), 0, st, F);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 static int stream_params(const mcd_stream_state_t* s, StreamParams* P) {
     if (!s || !s->ring || !s->frame_scores) return fail(MCD_EINVAL, "null stream state");
     if (s->n_slots <= 0 || s->num_transform <= 0 || s->seg_len <= 0 || s->seg_len > MCD_MAX_FRAMES || s->ring_len < s->seg_len)

@@ -5,6 +5,9 @@
 //   scatter_max<W> / frame_scatter / frame_scores kernels   post_processing                    models/mocodad.py:362-425
 //                               (W = 1: window scores, W = 17: per-joint maps; atomic_max_nonneg is the one scatter-max idiom)
 //   normalize_poses_kernel      dataset loader: bbox-centre coordinates + RobustScaler      utils/data.py:11-43,165-186,350-359
+//   denormalize_poses_kernel    its inverse, back to image pixels in the observed row's bounding box (mcd_denormalize_poses)
+//   forecast_claim / forecast_reduce kernels   overlapping window forecasts -> one pose per (person, frame) cell + their spread
+//                               (mcd_forecast_assemble)                                         utils/eval_utils.py:13-24,37-72
 //   stream_push_group / stream_frame_scores_group / stream_flush<W> kernels   the same loader step + sliding windows + scatter-max,
 //                               one group of ticks at a time (a single tick is a group of one) on device rings
 //                                                               utils/preprocessing.py:14-86, models/mocodad.py:392-393
@@ -316,6 +319,171 @@ __global__ __launch_bounds__(256) void normalize_poses_kernel(const float* __res
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
     normalize_pose_row(raw + f * 34, vid_w, vid_h, center, scale, out + f * 34, nullptr);
+}
+
+// The inverse of normalize_pose_row (mcd_denormalize_poses): a normalised row p (34, interleaved) back to image pixels in the
+// bounding box of the observed row r.  The box L, R, T, B is normalize_pose_row's, restated operation for operation (fp32 margin,
+// clip, round-half-even) rather than shared, so that the forward kernels' code stays what it was; per element, in float64 and
+// unfused, rounded to fp32 once: ((p * scale_k + center_k) * s + c), s = w | h, c = cx | cy.  A side of the box that is
+// degenerate (s = 0, where the forward kernel writes zeros; also the box of a row without joints) gives c.
+__device__ __forceinline__ void denormalize_pose_row(const float* __restrict__ p, const float* __restrict__ r, float vid_w, float vid_h,
+                                                     const double* __restrict__ center, const double* __restrict__ scale,
+                                                     float* __restrict__ o) {
+#pragma clang fp contract(off)
+    float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+    for (int k = 0; k < 34; k += 2) {
+        const float x = r[k], y = r[k + 1];
+        if (x != 0.f) { xmin = fminf(xmin, x); xmax = fmaxf(xmax, x); }
+        if (y != 0.f) { ymin = fminf(ymin, y); ymax = fmaxf(ymax, y); }
+    }
+    double cx = 0.0, cy = 0.0, w = 0.0, h = 0.0;
+    if (!(xmin > xmax || ymin > ymax)) {
+        const float ew = 0.1f * ((xmax - xmin) + 1.f), eh = 0.1f * ((ymax - ymin) + 1.f);
+        const float wm1 = vid_w - 1.f, hm1 = vid_h - 1.f;
+        const int L = (int)rintf(fminf(fmaxf(xmin - ew, 0.f), wm1)), R = (int)rintf(fminf(fmaxf(xmax + ew, 0.f), wm1));
+        const int T = (int)rintf(fminf(fmaxf(ymin - eh, 0.f), hm1)), B = (int)rintf(fminf(fmaxf(ymax + eh, 0.f), hm1));
+        cx = 0.5 * (double)(L + R); cy = 0.5 * (double)(T + B);
+        w = (double)(R - L); h = (double)(B - T);
+    }
+    for (int k = 0; k < 34; ++k) {
+        const double s = (k & 1) ? h : w, c = (k & 1) ? cy : cx;
+        double t = (double)p[k];
+        if (center) {
+            t = t * scale[k];
+            t = t + center[k];
+        }
+        t = t * s;
+        o[k] = s != 0.0 ? (float)(t + c) : (float)c;
+    }
+}
+
+// one thread per row, like normalize_poses_kernel; count != nullptr: a row with count 0 is all zeros (the CSV's "missing")
+__global__ __launch_bounds__(256) void denormalize_poses_kernel(const float* __restrict__ norm, const float* __restrict__ raw,
+                                                                const int* __restrict__ count, long long n, float vid_w, float vid_h,
+                                                                const double* __restrict__ center, const double* __restrict__ scale,
+                                                                float* __restrict__ out) {
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    if (count && count[f] == 0) {
+        for (int k = 0; k < 34; ++k) out[f * 34 + k] = 0.f;
+        return;
+    }
+    denormalize_pose_row(norm + f * 34, raw + f * 34, vid_w, vid_h, center, scale, out + f * 34);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forecast tracks (mcd_forecast_assemble): the overlapping window forecasts of a (person, frame) cell collapsed into one pose
+// (utils/eval_utils.py:13-24 compute_fig_matrix + :37-72 extract_single_pose), in two launches on a caller-owned list workspace.
+//   forecast_claim_kernel : one thread per (window, forecast frame) PAIR; a pair whose cell is in range claims a slot of the
+//                           cell's list with an atomic on the cell's count and stores its pair index there.  Which slot a pair
+//                           gets depends on arrival order; nothing else does:
+//   forecast_reduce_kernel: one 64-lane wave per cell orders the claimed pair indices (ascending pair index = ascending window
+//                           index, and within a window ascending forecast frame) by rank counting, stages the k x 34 values in
+//                           LDS in that order, and lanes 0 .. 33 take one feature each -- float64, unfused, in list order.
+// Everything a lane indexes at run time lives in LDS: no per-thread array.
+// ------------------------------------------------------------------------------------------------
+struct ForecastParams {
+    const float* poses; const int* cell;      // (N, 2, Tx, 17), (N, Tx)
+    int* list;                                // workspace (n_cells, max_cover) pair indices
+    float* pose_out; int* count_out; float* spread_out;
+    int n_pairs, Tx, n_cells, method, spread_method, max_cover;
+};
+
+__global__ __launch_bounds__(256) void forecast_claim_kernel(const ForecastParams F) {
+    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= F.n_pairs) return;
+    const int c = F.cell[u];
+    if (c < 0 || c >= F.n_cells) return;
+    const int slot = atomicAdd(F.count_out + c, 1);
+    if (slot < F.max_cover) F.list[(size_t)c * F.max_cover + slot] = (int)u;
+}
+
+// the middle of the k values x[0], x[stride], ... (np.median: for even k the half-sum of the two middle values), by rank
+// counting as wave_select does: rank of j = #{m : x_m < x_j or (x_m == x_j and m < j)}; a NaN among them gives NaN
+__device__ __forceinline__ double forecast_median(const float* x, int stride, int k) {
+    const int r0 = (k - 1) / 2, r1 = k / 2;
+    double lo = 0.0, hi = 0.0;
+    bool nan = false;
+    for (int j = 0; j < k; ++j) {
+        const float xj = x[j * stride];
+        nan |= xj != xj;
+        int r = 0;
+        for (int m = 0; m < k; ++m) {
+            const float xm = x[m * stride];
+            r += (xm < xj || (xm == xj && m < j)) ? 1 : 0;
+        }
+        if (r == r0) lo = (double)xj;
+        if (r == r1) hi = (double)xj;
+    }
+    return nan ? (double)NAN : (lo + hi) / 2.0;
+}
+
+__global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParams F) {
+#pragma clang fp contract(off)      // sum((x - mean)^2) is a product, then a sum: never an FMA
+    __shared__ int claimed[MCD_MAX_FRAMES], ordered[MCD_MAX_FRAMES];
+    __shared__ float vals[MCD_MAX_FRAMES * 34];
+    __shared__ double sd[34], mid[2];         // per-feature standard deviations; their two middle values
+    const int lane = threadIdx.x;
+    for (int c = blockIdx.x; c < F.n_cells; c += gridDim.x) {
+        const int k = F.count_out[c];
+        float* po = F.pose_out + (size_t)c * 34;
+        if (k <= 0 || k > F.max_cover) {      // no forecast: zeros; more pairs than the list holds: NaN (count_out says how many)
+            const float v = k <= 0 ? 0.f : __builtin_nanf("");
+            if (lane < 34) po[lane] = v;
+            if (lane == 0) F.spread_out[c] = v;
+            continue;
+        }
+        __syncthreads();                       // the previous cell's readers are done with the LDS
+        if (lane < k) claimed[lane] = F.list[(size_t)c * F.max_cover + lane];
+        __syncthreads();
+        if (lane < k) {                        // pair indices are distinct: the ranks are a permutation of 0 .. k-1
+            const int mine = claimed[lane];
+            int r = 0;
+            for (int m = 0; m < k; ++m) r += claimed[m] < mine ? 1 : 0;
+            ordered[r] = mine;
+        }
+        __syncthreads();
+        for (int e = lane; e < k * 34; e += 64) {
+            const int j = e / 34, f = e - j * 34, pair = ordered[j], i = pair / F.Tx, tx = pair - i * F.Tx;
+            vals[e] = F.poses[(((size_t)i * 2 + (f & 1)) * F.Tx + tx) * 17 + (f >> 1)];
+        }
+        __syncthreads();
+        if (lane < 34) {
+            const float* x = vals + lane;
+            double sum = 0.0;
+            for (int j = 0; j < k; ++j) sum += (double)x[j * 34];
+            const double mean = sum / (double)k;
+            double ss = 0.0;
+            for (int j = 0; j < k; ++j) {
+                const double d = (double)x[j * 34] - mean;
+                ss += d * d;
+            }
+            sd[lane] = sqrt(ss / (double)k);
+            po[lane] = (float)(F.method == MCD_FORECAST_UNIQUE ? (double)x[0] : F.method == MCD_FORECAST_MEAN ? mean : forecast_median(x, 34, k));
+        }
+        __syncthreads();
+        if (F.spread_method == MCD_FORECAST_MEAN) {
+            if (lane == 0) {
+                double s = 0.0;
+                for (int f = 0; f < 34; ++f) s += sd[f];
+                F.spread_out[c] = (float)(s / 34.0);
+            }
+        } else {
+            // the half-sum of ranks 16 and 17 of the 34 values, by rank counting again; a NaN among them gives NaN
+            bool nan = false;
+            if (lane < 34) {
+                const double mine = sd[lane];
+                nan = mine != mine;
+                int r = 0;
+                for (int m = 0; m < 34; ++m) r += (sd[m] < mine || (sd[m] == mine && m < lane)) ? 1 : 0;
+                if (r == 16) mid[0] = mine;
+                if (r == 17) mid[1] = mine;
+            }
+            const bool any_nan = __ballot(nan) != 0ull;
+            __syncthreads();
+            if (lane == 0) F.spread_out[c] = any_nan ? __builtin_nanf("") : (float)((mid[0] + mid[1]) / 2.0);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

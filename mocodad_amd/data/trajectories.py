@@ -166,7 +166,9 @@ def check_supported(args) -> None:
 def load_dataset(args, device):
     """The test-time dataset of `args` (the reference's YAML keys) as a TrajectoryWindows on `device`: parse, upload the raw
     rows once, normalise them with mcd_normalize_poses into the trajectory buffer.  Returns (windows, timing) with timing =
-    {'parse': s, 'normalise': s} (the second includes the upload and, for a self-fitted validation scaler, the fit)."""
+    {'parse': s, 'normalise': s} (the second includes the upload and, for a self-fitted validation scaler, the fit).  The windows
+    keep what takes a normalised row back to pixels: `.raw` (the RawTrajectories: row r of the buffer is raw.poses[r]), `.scaler`
+    ((center, scale)) and `.vid_res`."""
     import torch
     from ..engine import normalize_poses
     from .windows import TrajectoryWindows
@@ -193,6 +195,8 @@ def load_dataset(args, device):
         buf = normalize_poses(raw.poses, vid_res, *stats, device=dev)
     tw = TrajectoryWindows.from_buffer(buf.reshape(-1), raw.offsets, raw.frames, raw.keys, seg_len,
                                        int(getattr(args, "num_transform", 1)))
+    # what takes a normalised row back to pixels (engine.denormalize_poses): row r of the buffer is raw.poses[r]
+    tw.raw, tw.scaler, tw.vid_res = raw, stats, vid_res
     torch.cuda.synchronize(dev)
     raw.timing["normalise"] = time.perf_counter() - t0
     return tw, raw.timing

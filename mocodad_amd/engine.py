@@ -769,6 +769,118 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
     return out
 
 
+def _call_device(device, *tensors) -> torch.device:
+    """The device of a handle-free call: `device` when given, else that of the first of `tensors` on a GPU, else the current one."""
+    if device is not None:
+        return torch.device(device)
+    for t in tensors:
+        if t is not None and t.device.type == "cuda":
+            return t.device
+    _need_gpu()
+    return torch.device(f"cuda:{torch.cuda.current_device()}")
+
+
+def _caller_buffer(name: str, t: Optional[torch.Tensor], shape: Tuple[int, ...], dtype, dev) -> Optional[torch.Tensor]:
+    """A caller's output buffer, checked (None: the wrapper allocates)."""
+    if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+        raise ValueError(f"{name} must be a contiguous {tuple(shape)} {str(dtype).replace('torch.', '')} tensor on {dev}")
+    return t
+
+
+def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, method: str = "median", spread_method: str = "mean",
+                      max_cover: int = _lib.MCD_MAX_FRAMES, device=None, out=None,
+                      workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mcd_forecast_assemble (utils/eval_utils.py:13-24, 37-72): the selected forecasts of overlapping windows, poses (N,2,Tx,17),
+    collapsed into one pose per output cell; cell (N,Tx) int32 names the cell of every forecast frame, a value outside
+    [0, n_cells) means "ignore".  method: 'unique' (the lowest window index) | 'mean' | 'median'; spread_method: 'mean' | 'median'
+    of the 34 per-feature standard deviations over the windows covering the cell; max_cover 1 .. 32: pairs a cell's list holds.
+    -> (pose (n_cells, 34) fp32 interleaved x1,y1,...,x17,y17, count (n_cells,) int32, spread (n_cells,) fp32); a cell nobody
+    forecasts is 0 with count 0, one with more than max_cover pairs is NaN with its true count.  out: the caller's three buffers
+    instead of new ones; workspace: the caller's int32 scratch of at least n_cells * max_cover words.  Asynchronous on the current
+    stream; arguments are checked before anything touches the device."""
+    if method not in _lib.FORECAST:
+        raise ValueError(f"method must be one of {tuple(_lib.FORECAST)}, got {method!r}")
+    if spread_method not in ("mean", "median"):
+        raise ValueError(f"spread_method must be 'mean' or 'median', got {spread_method!r}")
+    max_cover, n_cells = int(max_cover), int(n_cells)
+    if not 1 <= max_cover <= _lib.MCD_MAX_FRAMES:
+        raise ValueError(f"max_cover must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {max_cover}")
+    if n_cells < 0:
+        raise ValueError(f"n_cells must be >= 0, got {n_cells}")
+    if poses.dim() != 4 or poses.shape[1] != 2 or poses.shape[3] != 17 or not 1 <= poses.shape[2] <= _lib.MCD_MAX_FRAMES:
+        raise ValueError(f"poses must have shape (N, 2, Tx, 17) with 1 <= Tx <= {_lib.MCD_MAX_FRAMES}, got {tuple(poses.shape)}")
+    N, Tx = int(poses.shape[0]), int(poses.shape[2])
+    if tuple(cell.shape) != (N, Tx) or cell.dtype.is_floating_point:
+        raise ValueError(f"cell must be an integer ({N}, {Tx}) tensor, got {tuple(cell.shape)} {cell.dtype}")
+    if N * Tx > 2**31 - 1:
+        raise ValueError("N x Tx exceeds 2^31 - 1: assemble in smaller batches")
+    dev = _call_device(device, poses)
+    if out is not None and len(out) != 3:
+        raise ValueError("out must be the three buffers (pose, count, spread)")
+    o_pose, o_count, o_spread = out if out is not None else (None, None, None)
+    o_pose = _caller_buffer("out[0] (pose)", o_pose, (n_cells, 34), torch.float32, dev)
+    o_count = _caller_buffer("out[1] (count)", o_count, (n_cells,), torch.int32, dev)
+    o_spread = _caller_buffer("out[2] (spread)", o_spread, (n_cells,), torch.float32, dev)
+    if workspace is not None and (workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.device != dev
+                                  or workspace.numel() < n_cells * max_cover):
+        raise ValueError(f"workspace must be a contiguous int32 tensor of at least n_cells x max_cover = {n_cells * max_cover} words on {dev}")
+    L = _lib.lib()
+    _need_gpu()
+    poses, cell = _f32c(poses, dev), _i32c(cell, dev)
+    with torch.cuda.device(dev):
+        if o_pose is None:
+            o_pose = torch.empty(n_cells, 34, device=dev, dtype=torch.float32)
+        if o_count is None:
+            o_count = torch.empty(n_cells, device=dev, dtype=torch.int32)
+        if o_spread is None:
+            o_spread = torch.empty(n_cells, device=dev, dtype=torch.float32)
+        if workspace is None:
+            workspace = torch.empty(max(n_cells * max_cover, 1), device=dev, dtype=torch.int32)
+        _lib.check(L.mcd_forecast_assemble(_ptr(poses), _ptr(cell), N, Tx, n_cells, _lib.FORECAST[method], _lib.FORECAST[spread_method],
+                                           max_cover, _ptr(workspace), _ptr(o_pose), _ptr(o_count), _ptr(o_spread), _stream()))
+    return o_pose, o_count, o_spread
+
+
+def denormalize_poses(norm: torch.Tensor, raw, vid_res: Sequence[float], center=None, scale=None, count: Optional[torch.Tensor] = None, *,
+                      device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mcd_denormalize_poses, the inverse of normalize_poses: norm (n, 34) fp32 in the CSV's interleaved order (what
+    forecast_assemble writes) -> (n, 34) fp32 image pixels in the bounding box of raw (n, 34), the observed CSV row of the same
+    person and frame (host array or tensor; finite); center / scale (34,): the scaler statistics normalize_poses was given, or both
+    None.  count (n,) int32: rows with count 0 come back all zero, the CSV's "missing".  out: an (n, 34) fp32 device buffer to
+    write into.  Asynchronous on the current stream; arguments are checked before anything touches the device."""
+    if (center is None) != (scale is None):
+        raise ValueError("center and scale go together (both None = no robust scaling)")
+    if norm.dim() != 2 or norm.shape[1] != 34:
+        raise ValueError(f"norm must be (n, 34) = x1,y1,...,x17,y17, got {tuple(norm.shape)}")
+    n = int(norm.shape[0])
+    raw_t = raw if torch.is_tensor(raw) else torch.from_numpy(np.ascontiguousarray(raw, dtype=np.float32))
+    if tuple(raw_t.shape) != (n, 34):
+        raise ValueError(f"raw pose rows must be ({n}, 34) like norm, got {tuple(raw_t.shape)}")
+    if raw_t.numel() and not bool(torch.isfinite(raw_t).all().item()):
+        raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
+    if count is not None and (tuple(count.shape) != (n,) or count.dtype.is_floating_point):
+        raise ValueError(f"count must be an integer ({n},) tensor, got {tuple(count.shape)} {count.dtype}")
+    w, h = (float(np.float32(v)) for v in vid_res)
+    if not (np.isfinite(w) and np.isfinite(h)):
+        raise ValueError(f"vid_res must be finite, got {tuple(vid_res)}")
+    for name, a in (("center", center), ("scale", scale)):
+        if a is not None and tuple(np.shape(a) if not torch.is_tensor(a) else a.shape) != (34,):
+            raise ValueError(f"{name} must hold 34 features, got shape {tuple(np.shape(a) if not torch.is_tensor(a) else a.shape)}")
+    dev = _call_device(device, out, norm)
+    out = _caller_buffer("out", out, (n, 34), torch.float32, dev)
+    L = _lib.lib()
+    _need_gpu()
+    stats = _scaler_stats(center, scale, dev)
+    norm, raw_t = _f32c(norm, dev), _f32c(raw_t, dev)
+    count = _i32c(count, dev) if count is not None else None
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(n, 34, device=dev, dtype=torch.float32)
+        c, s = (stats[0], stats[1]) if stats else (None, None)
+        _lib.check(L.mcd_denormalize_poses(_ptr(norm), _ptr(raw_t), _ptr(count), n, w, h, _ptr(c), _ptr(s), _ptr(out), _stream()))
+    return out
+
+
 class StreamRings:
     """Device state of a live pose stream (mcd_stream_state_t) and the launches on it: flush, push_group and frame_scores_group
     per group of ticks (a single tick is a group of one); the host half -- which track owns which slot, row counts, frame

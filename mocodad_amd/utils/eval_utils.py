@@ -126,6 +126,79 @@ def joint_score_rows(maps, trans, meta, frames, gts, num_transform: int, joint_s
     return out.cpu().numpy(), row_keys
 
 
+# ------------------------------------------------------------------ forecast tracks (mcd_forecast_assemble)
+def forecast_cells_dense(row, frame_ids, trans, n_frames: int) -> np.ndarray:
+    """cell (N, Tx) int32 for a dense (row, frame) matrix in the reference's layout (compute_fig_matrix, eval_utils.py:13-24):
+    row * n_frames + f - 1 for the 1-based frame id f of every forecast frame; -1 (ignored) for a window of another transform
+    than 0, the identity -- their forecasts live in rotated or flipped coordinates --, a negative row, or a frame outside
+    [1, n_frames]."""
+    row, f, trans = np.asarray(row, np.int64).reshape(-1, 1), np.asarray(frame_ids, np.int64), np.asarray(trans).reshape(-1, 1)
+    ok = (trans == 0) & (row >= 0) & (f >= 1) & (f <= n_frames)
+    return np.where(ok, row * n_frames + f - 1, -1).astype(np.int32)
+
+
+def forecast_cells_aligned(base, map_frames, trans, row_stride: int = 34) -> np.ndarray:
+    """cell (N, Tx) int32 = the global trajectory row of every forecast frame: base // 34 + its 0-based window frame index
+    (TrajectoryWindows.base: a window's element offset into the frame-major buffer); -1 for a window of another transform than 0."""
+    base, mf, trans = np.asarray(base, np.int64).reshape(-1, 1), np.asarray(map_frames, np.int64), np.asarray(trans).reshape(-1, 1)
+    return np.where(trans == 0, base // row_stride + mf, -1).astype(np.int32)
+
+
+def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows=None, meta=None, frames=None, method: str = "median",
+                        spread_method: str = "mean", max_cover: int = 32):
+    """Forecast tracks of a dataset (eval_MoCoDAD.py --forecast-tracks): the selected forecast of every window, poses (N,2,Tx,17)
+    (forward(return_='all')), collapsed into one expected pose per trajectory row -- per tracked person and video frame.
+    trans (N,): only windows of transform 0, the identity, contribute.  map_frames (N,Tx): the 0-based window frame index of each
+    pose row (MoCoDAD.map_frames; per window under 'random_imp').  The trajectory rows come from `windows` (a TrajectoryWindows: a
+    row is a row of its buffer, cell = base // 34 + frame index) or from meta (N,4) / frames (N,seg_len) (a row is a distinct
+    (scene, clip, person, frame id) of the transform-0 windows, in lexicographic order).  assemble: engine.forecast_assemble (or a
+    restatement of it).
+    -> (pose (R,34), count (R,), spread (R,) as `assemble` returns them, rows (R,3) int64 = (scene, clip, person), frame_ids (R,)
+    int64); a row no window forecasts -- the first n_cond rows of a track under a tail forecast -- has count 0 and a zero pose."""
+    trans, mf = np.asarray(trans).reshape(-1), np.asarray(map_frames, np.int64)
+    if windows is not None:
+        meta, frames, base = np.asarray(windows.meta), np.asarray(windows.frames), np.asarray(windows.base)
+    elif meta is None or frames is None:
+        raise ValueError("forecast_track_rows needs a TrajectoryWindows or the windows' meta and frames")
+    else:
+        meta, frames, base = np.asarray(meta), np.asarray(frames), None
+    N, seg_len = frames.shape
+    if len(trans) != N or len(meta) != N or mf.shape[0] != N or poses.shape[0] != N or mf.shape[1] != poses.shape[2]:
+        raise ValueError(f"need one forecast, transform, meta row, frame row and map_frames row per window, got {tuple(poses.shape)}, "
+                         f"{trans.shape}, {meta.shape}, {frames.shape}, {mf.shape}")
+    ident = np.flatnonzero(trans == 0)
+    keys = np.concatenate([np.repeat(meta[ident, :3].astype(np.int64), seg_len, axis=0), frames[ident].reshape(-1, 1).astype(np.int64)], axis=1)
+    if base is not None:
+        n_rows = int(windows.buffer.numel()) // 34
+        cell = forecast_cells_aligned(base, mf, trans)
+        row_of = (base[ident, None] // 34 + np.arange(seg_len)).reshape(-1)         # trajectory row of every covered window frame
+        table = np.zeros((n_rows, 4), np.int64)
+        table[row_of] = keys
+    else:
+        table, inv = np.unique(keys, axis=0, return_inverse=True)
+        n_rows = len(table)
+        dense = np.full((N, seg_len), -1, np.int64)
+        dense[ident] = inv.reshape(len(ident), seg_len)
+        cell = np.where(trans[:, None] == 0, np.take_along_axis(dense, mf, axis=1), -1).astype(np.int32)
+    import torch
+    pose, count, spread = assemble(poses, torch.from_numpy(np.ascontiguousarray(cell)), n_rows, method=method, spread_method=spread_method,
+                                   max_cover=max_cover)
+    return pose, count, spread, table[:, :3], table[:, 3]
+
+
+def reference_std_score(spread, lift: float = 1e-7) -> np.ndarray:
+    """The reference's MinMax step on the dense per-person spread vector (extract_single_pose, eval_utils.py:66-69:
+    MinMaxScaler().fit_transform(std_vec + std_lift)), restated in float64 with sklearn's operations: scale = 1 / (max - min)
+    (1 for a constant vector), x * scale + (0 - min * scale).  Host code: not a hot path."""
+    x = np.asarray(spread, np.float64).reshape(-1) + lift
+    if not len(x):
+        return x
+    lo, hi = np.nanmin(x), np.nanmax(x)
+    rng = hi - lo
+    scale = 1.0 / (rng if rng >= 10 * np.finfo(np.float64).eps else 1.0)
+    return x * scale + (0.0 - lo * scale)
+
+
 def post_process_scores(out, trans, meta, frames, gts: Dict[Tuple[int, int], np.ndarray], *, num_transform: int,
                         pad_size: int, filter_kernel_size: float, frames_shift: int, masks: Optional[Dict] = None,
                         scatter_max: Optional[Callable] = None) -> Tuple[np.ndarray, np.ndarray]:
