@@ -141,7 +141,16 @@ int mcd_layer_forward(const mcd_weights_t* w, int32_t stage, const float* x, con
 /* The noise tensor the perf mode (noise == NULL) of mcd_score draws in-kernel, in mcd_score's `noise` layout
  * (S, max(ns-1,1), B, C=2, Tx, V=17): mcd_score(noise = this tensor) reproduces mcd_score(noise = NULL, seed,
  * first_window_id) bit for bit.  Replaces nothing in the reference (which draws torch.randn_like, mocodad.py:162,176);
- * it exists so that the in-kernel generator's distribution can be tested and the perf mode can be replayed by an oracle. */
+ * it exists so that the in-kernel generator's distribution can be tested and the perf mode can be replayed by an oracle.
+ * KEY LAYOUT (tests/draws_ref.py restates it in NumPy; tests/test_draws_gpu.py holds this tensor and every kernel's own draw to
+ * it).  One Philox4x32-10 call has the key (low, high 32 bits of seed) and the counter (c0, c1, c2, c3):
+ *   c1 = noise slot k (0 = x_T, k >= 1 = the z of step ns - k), c2 = sample s, c3 = (first_window_id + b) mod 2^32;
+ *   x_T (k = 0):       c0 = (c * Tx + tx) * 17 + v, one call per element: z = r(w0) cos(a(w1)) of its output words w0 .. w3;
+ *   step noise (k>=1): c0 = tx * 9 + v0 / 2, one call per joint pair (v0 even) of corrupt frame tx: (w0, w1) give the
+ *                      coordinates c = 0, 1 of joint v0 as (r cos a, r sin a), (w2, w3) the same of joint v0 + 1 (unused at
+ *                      v0 = 16);
+ *   u(w) = ((float)(w >> 8) + 0.5f) * 2^-24 in float (the largest word rounds to u = 1 and gives r = 0),
+ *   r(w) = sqrt(-1.38629436111989f * log2(u(w))), a(w) = 6.28318530717958647692f * u(w), on the hardware's log2, sqrt, sin, cos. */
 int mcd_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
                      int32_t n_corrupt, float* noise_out, void* stream);
 
@@ -720,6 +729,9 @@ int mcd_latent_decode_samples(const mcd_latent_weights_t* w, const mcd_score_cfg
 
 /* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
  * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121).
+ * KEY LAYOUT (key, c1 = slot k, c2 = sample s, c3 = window id, u, r and a as for mcd_philox_noise): for every slot c0 = d0 / 4,
+ * one call per group of four elements d0 .. d0 + 3, which are r(w0) cos(a(w1)), r(w0) sin(a(w1)), r(w2) cos(a(w3)),
+ * r(w2) sin(a(w3)) in this order.
  * Alignment: noise_out must be 16-byte aligned (an element group of four floats is one store), else MCD_EINVAL. */
 int mcd_latent_philox_noise(uint64_t seed, int64_t first_window_id, int32_t n_windows, int32_t n_samples, int32_t noise_steps,
                             int32_t latent_dim, float* noise_out, void* stream);

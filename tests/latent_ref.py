@@ -175,19 +175,20 @@ def chain_inputs(i: int, ns: int, S: int, B: int):
     return torch.randn(B, 2, 6, 17, generator=g), torch.randn(S, max(ns - 1, 1), B, LATENT_SHAPES[i][0], generator=g)
 
 
-def random_latent_model(D: int, hidden: Sequence[int], *, seed: int, ns: int, S: int, tame: bool):
+def random_latent_model(D: int, hidden: Sequence[int], *, seed: int, ns: int, S: int, tame: bool, **over):
     """-> (MoCoDADlatent on the CPU, cloned fp32 state_dict): fixture B's settings with latent_embedding_dim D and the denoiser
     widths `hidden`, seeded random-init weights, perturbed BatchNorm statistics and PReLU slopes.  tame: the last denoiser layer
     and its cond_layers entry scaled by 0.1, so that eps stays O(0.1) and a chain's size comes from the schedule alone.
+    over: further settings replacing fixture B's (seg_len, conditioning_indices: another frame split).
     Built once per argument set and session and shared: treat the state_dict as read-only."""
     from helpers import make_args
     from mocodad_amd.models.mocodad_latent import MoCoDADlatent
-    key = (D, tuple(hidden), seed, ns, S, tame)
+    key = (D, tuple(hidden), seed, ns, S, tame, tuple(sorted((k, str(v)) for k, v in over.items())))
     if key not in _models:
         cfg = load_fixture("B")[2]
         with torch.random.fork_rng(), torch.no_grad():
             torch.manual_seed(seed)
-            m = MoCoDADlatent(make_args(cfg, latent_embedding_dim=D, hidden_sizes=list(hidden), noise_steps=ns, n_generated_samples=S))
+            m = MoCoDADlatent(make_args(cfg, latent_embedding_dim=D, hidden_sizes=list(hidden), noise_steps=ns, n_generated_samples=S, **over))
             _perturb(m, torch.Generator().manual_seed(seed + 1))
             if tame:
                 last = len(hidden) - 1
