@@ -479,6 +479,56 @@ int mcd_stream_joint_scores_group(const mcd_stream_state_t* s, const mcd_stream_
 int mcd_stream_joint_flush(const mcd_stream_state_t* s, const mcd_stream_joint_state_t* js, const int32_t* win, int32_t n,
                            float* out, void* stream);
 
+/* Forecast ring of a live stream (added without a change of MCD_ABI_VERSION, as the forecast exports were: two new exports and a new
+ * struct, nothing existing touched): the EXPECTED POSE of a track row, leaving the device with the tick that makes the row final --
+ * what mcd_forecast_assemble + mcd_denormalize_poses give for the row on the dataset path, bit for bit.  A third CALLER-owned state
+ * beside mcd_stream_state_t and mcd_stream_joint_state_t, which stay as they are.
+ *   forecast  (n_slots, ring_len, n_corrupt, 34) f32: cell (r % ring_len, j) = row r of the track as corrupt frame j of its ONE
+ *             window, the window that ends at row r + seg_len - 1 - corrupt_idx[j]: that window's selected forecast of the row
+ *             (pose_agg of mcd_aggregate under MCD_AGGR_BEST / WORST, zeros when no sample passes), interleaved x1,y1,...,x17,y17.
+ *             Only windows of transform 0, the identity, are stored.
+ *   observed  (n_slots, ring_len, 34) f32: cell r % ring_len = the raw row r as pushed.
+ *   n_corrupt the model's number of forecast frames, 1 .. 32.
+ * Cell rule (nothing is stored about validity, and nothing needs initialising): a cell has exactly one writer; cell (r, j), seen
+ * from a track whose last row so far is r_hi, is valid iff its window exists -- corrupt_idx[j] <= r and
+ * r + seg_len - 1 - corrupt_idx[j] <= r_hi.  corrupt_idx must ascend, so ascending window order is descending j.  A reused slot and
+ * a wrapped ring start clean because an invalid cell is never read.
+ * The row's result, over its k valid cells in ascending window order, is mcd_forecast_assemble's per cell (float64, unfused, rounded
+ * once; UNIQUE / MEAN / MEDIAN, the two-pass population standard deviation per feature, its mean or median over the 34 features),
+ * then mcd_denormalize_poses' per row in the box of the observed row.  A row with k = 0 (the first rows of a track) is all zero in
+ * expected, norm and spread.  A row is final with the window whose oldest row it is: all k <= n_corrupt windows covering it are in.
+ *
+ * mcd_stream_forecast_group: behind the group's scoring call.  raw (n, 34), desc (n, 4): what mcd_stream_push_group was given;
+ * loss_all (num_transform * n_windows, n_samples) and poses_all (num_transform * n_windows, n_samples, 2, n_corrupt, 17): the
+ * per-sample losses and poses of that call, in the order of base_out; win (n_windows, 5): the table of
+ * mcd_stream_frame_scores_group; cfg: seg_len (the state's), n_corrupt (the forecast state's), corrupt_idx (ascending; n_cond +
+ * n_corrupt = seg_len), n_samples; aggregation: MCD_AGGR_BEST or MCD_AGGR_WORST; method / spread_method: MCD_FORECAST_*; vid_w,
+ * vid_h, center, scale: as for mcd_denormalize_poses.  Two launches: (1) one 64-lane wave per transform-0 window selects its sample
+ * and stores the n_corrupt x 34 values, further workgroups store the raw rows; (2) one wave per window reduces that window's oldest
+ * row.  Outputs, row w of each = the row window w (in (tick, j) order) finalised: expected_out (n_windows, 34) f32 image pixels,
+ * norm_out (n_windows, 34) f32 normalised, observed_out (n_windows, 34) f32 the raw row, count_out (n_windows,) i32 = k,
+ * spread_out (n_windows,) f32.  n == 0 launches nothing; n_windows == 0 stores the raw rows only (the outputs may be NULL).
+ * mcd_stream_forecast_flush: win (n, 2) = [slot, r_last] of tracks being closed, as for mcd_stream_flush -> the same five outputs
+ * with n * (seg_len - 1) rows: the pending rows r_last - seg_len + 2 .. r_last, which see only the windows that exist.
+ * Argument errors -- a null state, cfg or (where rows are produced) pointer, n_corrupt outside 1 .. 32 or not cfg's, a seg_len that is
+ * not the state's, corrupt_idx not ascending, an unknown method or spread_method, an aggregation other than best / worst, negative
+ * counts, n_windows > n, more rows than a group holds -- are MCD_EINVAL before any device call. */
+typedef struct {
+    float* forecast;
+    float* observed;
+    int32_t n_corrupt;
+} mcd_stream_forecast_state_t;
+
+int mcd_stream_forecast_group(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const float* raw, const int32_t* desc,
+                              int32_t n, const float* loss_all, const float* poses_all, const int32_t* win, int32_t n_windows,
+                              const mcd_score_cfg_t* cfg, int32_t aggregation, int32_t method, int32_t spread_method, float vid_w,
+                              float vid_h, const double* center, const double* scale, float* expected_out, float* norm_out,
+                              float* observed_out, int32_t* count_out, float* spread_out, void* stream);
+int mcd_stream_forecast_flush(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const int32_t* win, int32_t n,
+                              const mcd_score_cfg_t* cfg, int32_t method, int32_t spread_method, float vid_w, float vid_h,
+                              const double* center, const double* scale, float* expected_out, float* norm_out, float* observed_out,
+                              int32_t* count_out, float* spread_out, void* stream);
+
 /* Online clip scores of a live stream: the last stage of post_processing -- the person aggregation
  * mean_p s + (max_p log1p s - min_p log1p s) (mocodad.py:399-401), score_process = shift + gaussian_filter1d (eval_utils.py:100-106)
  * and the mean over the transforms (mocodad.py:424) -- incrementally, one value per video frame of a clip, from the final per-row

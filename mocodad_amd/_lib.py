@@ -63,6 +63,10 @@ class StreamJointState(C.Structure):
     _fields_ = [("joint_scores", C.c_void_p)]
 
 
+class StreamForecastState(C.Structure):
+    _fields_ = [("forecast", C.c_void_p), ("observed", C.c_void_p), ("n_corrupt", C.c_int32)]
+
+
 class ClipState(C.Structure):
     _fields_ = [("sum", C.c_void_p), ("lmax", C.c_void_p), ("lmin", C.c_void_p), ("n", C.c_void_p), ("n_clips", C.c_int32),
                 ("clip_ring_len", C.c_int32), ("num_transform", C.c_int32)]
@@ -119,6 +123,13 @@ _SIGS = {
                                                 C.POINTER(ScoreCfg), C.c_void_p, C.c_void_p]),
     "mcd_stream_joint_flush": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamJointState), C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p]),
+    "mcd_stream_forecast_group": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamForecastState), C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ScoreCfg), C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_stream_forecast_flush": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamForecastState), C.c_void_p, C.c_int32,
+                                            C.POINTER(ScoreCfg), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_stream_clip_update": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_int32, C.c_void_p]),
     "mcd_stream_clip_emit": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,

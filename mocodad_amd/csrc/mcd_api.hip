@@ -837,6 +837,88 @@ int mcd_stream_joint_flush(const mcd_stream_state_t* s, const mcd_stream_joint_s
     return stream_flush<17>(P, js->joint_scores, win, n, out, stream);
 }
 
+// the forecast rings beside a stream state: (n_slots, ring_len, n_corrupt, 34) and (n_slots, ring_len, 34) floats; everything the two
+// entries below share is checked here, before any device call
+static int stream_forecast_params(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const mcd_score_cfg_t* cfg,
+                                  int32_t method, int32_t spread_method, float vid_w, float vid_h, const double* center,
+                                  const double* scale, StreamParams* P, StreamForecastParams* F) {
+    if (int rc = stream_params(s, P)) return rc;
+    if (!fs || !fs->forecast || !fs->observed) return fail(MCD_EINVAL, "null stream forecast state");
+    if (fs->n_corrupt < 1 || fs->n_corrupt > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "stream forecast state: need 1 <= n_corrupt <= 32");
+    if (!cfg) return fail(MCD_EINVAL, "null argument");
+    if (cfg->seg_len != P->seg_len) return fail(MCD_EINVAL, "cfg->seg_len is not the stream state's seg_len");
+    if (cfg->n_corrupt != fs->n_corrupt) return fail(MCD_EINVAL, "cfg->n_corrupt is not the stream forecast state's n_corrupt");
+    if (int rc = check_frame_partition(cfg)) return rc;
+    for (int k = 0; k < cfg->n_corrupt; ++k)
+        if (cfg->corrupt_idx[k] < 0 || cfg->corrupt_idx[k] >= cfg->seg_len || (k > 0 && cfg->corrupt_idx[k] <= cfg->corrupt_idx[k - 1]))
+            return fail(MCD_EINVAL, "corrupt_idx must ascend inside [0, seg_len)");
+    if (method != MCD_FORECAST_UNIQUE && method != MCD_FORECAST_MEAN && method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "method must be MCD_FORECAST_UNIQUE, MEAN or MEDIAN");
+    if (spread_method != MCD_FORECAST_MEAN && spread_method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "spread_method must be MCD_FORECAST_MEAN or MEDIAN");
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    if ((int64_t)s->n_slots * s->ring_len > 0x7fffffffll / (34 * fs->n_corrupt))
+        return fail(MCD_EUNSUPPORTED, "stream forecast ring of more than 2^31 elements");
+    memset(F, 0, sizeof(*F));
+    F->fc = fs->forecast; F->obs = fs->observed; F->center = center; F->scale = scale; F->vid_w = vid_w; F->vid_h = vid_h;
+    F->Tx = fs->n_corrupt; F->method = method; F->spread_method = spread_method;
+    for (int k = 0; k < cfg->n_corrupt; ++k) F->cidx[k] = cfg->corrupt_idx[k];
+    return MCD_OK;
+}
+
+int mcd_stream_forecast_group(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const float* raw, const int32_t* desc,
+                              int32_t n, const float* loss_all, const float* poses_all, const int32_t* win, int32_t n_windows,
+                              const mcd_score_cfg_t* cfg, int32_t aggregation, int32_t method, int32_t spread_method, float vid_w,
+                              float vid_h, const double* center, const double* scale, float* expected_out, float* norm_out,
+                              float* observed_out, int32_t* count_out, float* spread_out, void* stream) {
+    StreamParams P;
+    StreamForecastParams F;
+    if (int rc = stream_forecast_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, &P, &F)) return rc;
+    if (aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST)
+        return fail(MCD_EINVAL, "a forecast is the pose of ONE sample: aggregation must be MCD_AGGR_BEST or MCD_AGGR_WORST");
+    if (n < 0 || n_windows < 0 || n_windows > n) return fail(MCD_EINVAL, "need 0 <= n_windows <= n");
+    if (n > stream_group_rows(s))
+        return fail(MCD_EINVAL, "more rows than n_slots * (ring_len - seg_len + 1): a group holds at most ring_len - seg_len + 1 rows per track");
+    long long total;
+    if (int rc = check_group_windows(s, n_windows, 1, &total)) return rc;
+    if (cfg->n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
+    if (n == 0) return MCD_OK;
+    if (!raw || !desc) return fail(MCD_EINVAL, "null argument");
+    if (n_windows > 0 && (!loss_all || !poses_all || !win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out))
+        return fail(MCD_EINVAL, "null argument");
+    F.loss_all = loss_all; F.poses_all = poses_all; F.S = cfg->n_samples; F.strategy = aggregation; F.in_lds = F.S <= AGG_LDS_MAX;
+    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
+    hipStream_t st = (hipStream_t)stream;
+    // the windows' forecasts and the raw rows in one launch; the final rows in a second one behind it (stream order)
+    const long long blocks = (long long)n_windows + ((long long)n * 34 + 63) / 64;
+    const size_t lds = (size_t)(SEL_LDS_WORDS + (F.in_lds ? F.S : 0)) * sizeof(float);
+    hipLaunchKernelGGL(stream_forecast_store_kernel, dim3((unsigned)blocks), dim3(64), lds, st, P, F, raw, desc, n, win, n_windows, (int)total);
+    HIP_TRY(hipGetLastError());
+    if (n_windows == 0) return MCD_OK;
+    hipLaunchKernelGGL(stream_forecast_emit_kernel, dim3((unsigned)n_windows), dim3(64), 0, st, P, F, win, n_windows, (int)total);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+int mcd_stream_forecast_flush(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const int32_t* win, int32_t n,
+                              const mcd_score_cfg_t* cfg, int32_t method, int32_t spread_method, float vid_w, float vid_h,
+                              const double* center, const double* scale, float* expected_out, float* norm_out, float* observed_out,
+                              int32_t* count_out, float* spread_out, void* stream) {
+    StreamParams P;
+    StreamForecastParams F;
+    if (int rc = stream_forecast_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, &P, &F)) return rc;
+    if (n < 0 || n > P.n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
+    const long long rows = (long long)n * (P.seg_len - 1);
+    if (rows == 0) return MCD_OK;
+    if (!win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out) return fail(MCD_EINVAL, "null argument");
+    if (rows > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
+    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
+    hipLaunchKernelGGL(stream_forecast_flush_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, P, F, win, n);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 static int clip_params(const mcd_clip_state_t* c, ClipParams* P) {
     if (!c || !c->sum || !c->lmax || !c->lmin || !c->n) return fail(MCD_EINVAL, "null clip state");
     if (c->n_clips <= 0 || c->num_transform <= 0 || c->clip_ring_len <= 0)

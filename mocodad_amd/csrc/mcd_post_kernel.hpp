@@ -15,11 +15,14 @@
 //                               post_processing, incrementally on a per-clip ring     models/mocodad.py:399-424, utils/eval_utils.py:100-106
 //   stream_joint_scores_group kernel   the per-joint sibling of the stream's score ring, fed by the error maps: the same walk over a
 //                               track's windows (walk_track_windows) with its own cell rule; flushed by stream_flush<17>
+//   stream_forecast_store / stream_forecast_emit / stream_forecast_flush kernels   the stream's forecast ring: per window the selected
+//                               forecast (wave_select) into the cells of the rows it forecasts, per final / pending row the
+//                               reduction of forecast_reduce_kernel (forecast_reduce_staged) and denormalize_pose_row
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
-// with the parameter blocks the host fills (SelectParams inside AggrParams and MapParams, StreamParams, StreamJointParams, FrameParams,
-// ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines API_THREADS and says `using namespace mcd`), in front
+// with the parameter blocks the host fills (SelectParams inside AggrParams and MapParams, StreamParams, StreamJointParams,
+// StreamForecastParams, FrameParams, ClipParams, ClipEmitParams).  Included once, by mcd_api.hip (which defines API_THREADS and says `using namespace mcd`), in front
 // of its host code.
 #pragma once
 
@@ -418,8 +421,51 @@ __device__ __forceinline__ double forecast_median(const float* x, int stride, in
     return nan ? (double)NAN : (lo + hi) / 2.0;
 }
 
-__global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParams F) {
+// The reduction of ONE cell, shared by forecast_reduce_kernel and the stream's forecast rows (forecast_emit_row): the k x 34 values
+// staged in LDS in list order (vals[j * 34 + f]) -> lanes 0 .. 33 store their feature's pose to po[lane], the spread goes to *so.
+// sd (34 doubles) and mid (2 doubles) are LDS.  Called by all 64 lanes of the one-wave workgroup, behind the barrier that makes
+// `vals` visible; 1 <= k <= MCD_MAX_FRAMES.
+__device__ __forceinline__ void forecast_reduce_staged(const float* vals, int k, int method, int spread_method, int lane, double* sd,
+                                                       double* mid, float* po, float* so) {
 #pragma clang fp contract(off)      // sum((x - mean)^2) is a product, then a sum: never an FMA
+    if (lane < 34) {
+        const float* x = vals + lane;
+        double sum = 0.0;
+        for (int j = 0; j < k; ++j) sum += (double)x[j * 34];
+        const double mean = sum / (double)k;
+        double ss = 0.0;
+        for (int j = 0; j < k; ++j) {
+            const double d = (double)x[j * 34] - mean;
+            ss += d * d;
+        }
+        sd[lane] = sqrt(ss / (double)k);
+        po[lane] = (float)(method == MCD_FORECAST_UNIQUE ? (double)x[0] : method == MCD_FORECAST_MEAN ? mean : forecast_median(x, 34, k));
+    }
+    __syncthreads();
+    if (spread_method == MCD_FORECAST_MEAN) {
+        if (lane == 0) {
+            double s = 0.0;
+            for (int f = 0; f < 34; ++f) s += sd[f];
+            *so = (float)(s / 34.0);
+        }
+    } else {
+        // the half-sum of ranks 16 and 17 of the 34 values, by rank counting again; a NaN among them gives NaN
+        bool nan = false;
+        if (lane < 34) {
+            const double mine = sd[lane];
+            nan = mine != mine;
+            int r = 0;
+            for (int m = 0; m < 34; ++m) r += (sd[m] < mine || (sd[m] == mine && m < lane)) ? 1 : 0;
+            if (r == 16) mid[0] = mine;
+            if (r == 17) mid[1] = mine;
+        }
+        const bool any_nan = __ballot(nan) != 0ull;
+        __syncthreads();
+        if (lane == 0) *so = any_nan ? __builtin_nanf("") : (float)((mid[0] + mid[1]) / 2.0);
+    }
+}
+
+__global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParams F) {
     __shared__ int claimed[MCD_MAX_FRAMES], ordered[MCD_MAX_FRAMES];
     __shared__ float vals[MCD_MAX_FRAMES * 34];
     __shared__ double sd[34], mid[2];         // per-feature standard deviations; their two middle values
@@ -448,41 +494,7 @@ __global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParam
             vals[e] = F.poses[(((size_t)i * 2 + (f & 1)) * F.Tx + tx) * 17 + (f >> 1)];
         }
         __syncthreads();
-        if (lane < 34) {
-            const float* x = vals + lane;
-            double sum = 0.0;
-            for (int j = 0; j < k; ++j) sum += (double)x[j * 34];
-            const double mean = sum / (double)k;
-            double ss = 0.0;
-            for (int j = 0; j < k; ++j) {
-                const double d = (double)x[j * 34] - mean;
-                ss += d * d;
-            }
-            sd[lane] = sqrt(ss / (double)k);
-            po[lane] = (float)(F.method == MCD_FORECAST_UNIQUE ? (double)x[0] : F.method == MCD_FORECAST_MEAN ? mean : forecast_median(x, 34, k));
-        }
-        __syncthreads();
-        if (F.spread_method == MCD_FORECAST_MEAN) {
-            if (lane == 0) {
-                double s = 0.0;
-                for (int f = 0; f < 34; ++f) s += sd[f];
-                F.spread_out[c] = (float)(s / 34.0);
-            }
-        } else {
-            // the half-sum of ranks 16 and 17 of the 34 values, by rank counting again; a NaN among them gives NaN
-            bool nan = false;
-            if (lane < 34) {
-                const double mine = sd[lane];
-                nan = mine != mine;
-                int r = 0;
-                for (int m = 0; m < 34; ++m) r += (sd[m] < mine || (sd[m] == mine && m < lane)) ? 1 : 0;
-                if (r == 16) mid[0] = mine;
-                if (r == 17) mid[1] = mine;
-            }
-            const bool any_nan = __ballot(nan) != 0ull;
-            __syncthreads();
-            if (lane == 0) F.spread_out[c] = any_nan ? __builtin_nanf("") : (float)((mid[0] + mid[1]) / 2.0);
-        }
+        forecast_reduce_staged(vals, k, F.method, F.spread_method, lane, sd, mid, po, F.spread_out + c);
     }
 }
 
@@ -615,6 +627,118 @@ __global__ __launch_bounds__(256) void stream_joint_scores_group_kernel(StreamPa
             if (k == 0) final_out[((size_t)w * S.nt + t) * 17 + v] = cur;
         }
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forecast ring of a stream (mcd_stream_forecast_state_t): the expected pose of a row, leaving with the tick that makes it final.
+//   forecast ring (n_slots, L, Tx, 34): cell (r % L, j) = row r as corrupt frame j of its ONE window, the window that ends at row
+//                 r + seg_len - 1 - corrupt_idx[j]: that window's selected forecast of the row (pose_agg of aggregate_kernel: the
+//                 best / worst sample by wave_select, zeros when no sample passes), interleaved x1,y1,...,x17,y17.
+//   observed ring (n_slots, L, 34): the raw row r as it was pushed.
+// Cell rule: a cell has exactly one writer, and nothing is stored about validity -- cell (r, j) is valid, seen from a track whose
+// last row so far is r_hi, iff its window exists: corrupt_idx[j] <= r (the window does not begin before row 0) and
+// r + seg_len - 1 - corrupt_idx[j] <= r_hi (it has been scored).  corrupt_idx ascends, so the valid j are ONE run [jb, ja) and
+// ascending window order is descending j.  A reused slot and a wrapped ring need no initialisation: an invalid cell is never read,
+// and a valid one was written by this track after any older content (a group holds at most L - seg_len + 1 rows per track, the
+// bound that keeps rows r0 - seg_len + 1 .. r0 + R - 1 at distinct positions).
+//   stream_forecast_store_kernel: workgroups 0 .. n_windows - 1, one 64-lane wave per transform-0 window of the group: select, then
+//                 the Tx x 34 values into their cells; the workgroups behind them copy the group's raw rows, one thread per element.
+//   stream_forecast_emit_kernel / stream_forecast_flush_kernel: one wave per final / pending row (forecast_emit_row): the k valid
+//                 cells staged in LDS in window order, forecast_reduce_staged, denormalize_pose_row in the box of the observed row.
+// Plain loads and stores; what a lane indexes at run time is LDS or global memory.
+// ------------------------------------------------------------------------------------------------
+struct StreamForecastParams {
+    float* fc; float* obs;
+    const float* loss_all; const float* poses_all;      // (n_win, S), (n_win, S, 2, Tx, 17) of the group's scoring call
+    float* expected; float* norm; float* observed; int* count; float* spread;
+    const double* center; const double* scale;
+    float vid_w, vid_h;
+    int Tx, S, strategy, in_lds, method, spread_method;
+    int cidx[MCD_MAX_FRAMES];
+};
+
+__global__ __launch_bounds__(64) void stream_forecast_store_kernel(StreamParams S, StreamForecastParams F, const float* __restrict__ raw,
+                                                                   const int* __restrict__ desc, int n, const int* __restrict__ win,
+                                                                   int n_windows, int n_win) {
+    extern __shared__ float sfc_lds[];      // [SEL_LDS_WORDS] wave_select's, [S] staged losses (in_lds)
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= n_windows) {     // the raw rows: desc (n, 4) = [slot, row index r, ...] as stream_push_group_kernel reads it
+        const long long u = (long long)((int)blockIdx.x - n_windows) * 64 + lane;
+        if (u >= (long long)n * 34) return;
+        const int i = (int)(u / 34), f = (int)(u - (long long)i * 34);
+        const int slot = desc[4 * i], r = desc[4 * i + 1];
+        if (slot < 0 || slot >= S.n_slots || r < 0) return;
+        F.obs[((size_t)slot * S.L + r % S.L) * 34 + f] = raw[u];
+        return;
+    }
+    const int q = blockIdx.x;               // win (n_windows, 5) = [slot, r_last, pos0, ne, w]: the window's transform-0 position is pos0
+    const int slot = win[5 * q], r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos0 >= n_win || w < 0 || w >= n_windows) return;
+    const SampleVals X = stage_samples(F.loss_all + (size_t)pos0 * F.S, 1, F.S, sfc_lds + SEL_LDS_WORDS, F.in_lds != 0, lane);
+    const Selection sel = wave_select(X, F.S, lane, F.strategy, 0.f, sfc_lds);
+    const float* p = F.poses_all + ((size_t)pos0 * F.S + (sel.i0 >= 0 ? sel.i0 : 0)) * 34 * F.Tx;
+    const int first = r_last - S.seg_len + 1;
+    for (int j = 0; j < F.Tx; ++j) {        // (j is wave-uniform: corrupt_idx is read from the kernel arguments)
+        const int r = first + F.cidx[j];
+        if (lane < 34)
+            F.fc[(((size_t)slot * S.L + r % S.L) * F.Tx + j) * 34 + lane] = sel.i0 >= 0 ? p[((lane & 1) * F.Tx + j) * 17 + (lane >> 1)] : 0.f;
+    }
+}
+
+// Row r of `slot`, seen with r_hi the track's last row so far, into row o of the five outputs.  vals [MCD_MAX_FRAMES * 34], pn [34],
+// sd [34], mid [2]: LDS.  One wave; every lane takes the same branches.
+__device__ __forceinline__ void forecast_emit_row(const StreamParams& S, const StreamForecastParams& F, int slot, int r, int r_hi, size_t o,
+                                                  int lane, float* vals, float* pn, double* sd, double* mid) {
+    int ja = 0, jb = 0;
+    for (int j = 0; j < F.Tx; ++j) {
+        const int c = F.cidx[j];
+        ja += c <= r ? 1 : 0;
+        jb += r + S.seg_len - 1 - c > r_hi ? 1 : 0;
+    }
+    const int k = ja > jb ? ja - jb : 0;
+    const size_t row = (size_t)slot * S.L + r % S.L;
+    const float* cell = F.fc + row * F.Tx * 34;
+    for (int e = lane; e < k * 34; e += 64) {      // window order: the m-th window of the row holds it as corrupt frame ja - 1 - m
+        const int m = e / 34, f = e - m * 34;
+        vals[e] = cell[(ja - 1 - m) * 34 + f];
+    }
+    if (lane < 34) F.observed[o * 34 + lane] = F.obs[row * 34 + lane];
+    if (lane == 0) F.count[o] = k;
+    if (k == 0) {                                   // no window forecasts the row: all zero
+        if (lane < 34) { F.norm[o * 34 + lane] = 0.f; F.expected[o * 34 + lane] = 0.f; }
+        if (lane == 0) F.spread[o] = 0.f;
+        return;
+    }
+    __syncthreads();
+    forecast_reduce_staged(vals, k, F.method, F.spread_method, lane, sd, mid, pn, F.spread + o);
+    __syncthreads();
+    if (lane < 34) F.norm[o * 34 + lane] = pn[lane];
+    if (lane == 0) denormalize_pose_row(pn, F.obs + row * 34, F.vid_w, F.vid_h, F.center, F.scale, F.expected + o * 34);
+}
+
+// one wave per window of the group's table: its oldest row r_last - seg_len + 1 is final, every window covering it is in
+__global__ __launch_bounds__(64) void stream_forecast_emit_kernel(StreamParams S, StreamForecastParams F, const int* __restrict__ win,
+                                                                  int n_windows, int n_win) {
+    __shared__ float vals[MCD_MAX_FRAMES * 34], pn[34];
+    __shared__ double sd[34], mid[2];
+    const int q = blockIdx.x;
+    if (q >= n_windows) return;
+    const int slot = win[5 * q], r_last = win[5 * q + 1], pos0 = win[5 * q + 2], ne = win[5 * q + 3], w = win[5 * q + 4];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1 || pos0 < 0 || ne < 1 || pos0 >= n_win || w < 0 || w >= n_windows) return;
+    forecast_emit_row(S, F, slot, r_last - S.seg_len + 1, r_last, (size_t)w, threadIdx.x, vals, pn, sd, mid);
+}
+
+// one wave per (closed track i, pending row k): win (n, 2) = [slot, r_last]; rows r_last - seg_len + 2 .. r_last see only the
+// windows that exist
+__global__ __launch_bounds__(64) void stream_forecast_flush_kernel(StreamParams S, StreamForecastParams F, const int* __restrict__ win, int n) {
+    __shared__ float vals[MCD_MAX_FRAMES * 34], pn[34];
+    __shared__ double sd[34], mid[2];
+    const int pend = S.seg_len - 1, u = blockIdx.x;
+    if (u >= n * pend) return;
+    const int i = u / pend, k = u - i * pend;
+    const int slot = win[2 * i], r_last = win[2 * i + 1];
+    if (slot < 0 || slot >= S.n_slots || r_last < S.seg_len - 1) return;
+    forecast_emit_row(S, F, slot, r_last - S.seg_len + 2 + k, r_last, (size_t)u, threadIdx.x, vals, pn, sd, mid);
 }
 
 // ------------------------------------------------------------------------------------------------

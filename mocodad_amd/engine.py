@@ -887,11 +887,13 @@ class StreamRings:
     ids -- is mocodad_amd.stream.TrackTable, the call that ties them together PoseStream.push / push_many.
       ring          flat (n_slots * 2 * ring_len * 34,) fp32: row r of slot s at positions r % L and r % L + L of its 2 L rows
       frame_scores  (n_slots, num_transform, ring_len) fp32 running maxima
+    and, opt-in, the joint ring (joint_scores=True: mcd_stream_joint_state_t) and the forecast and observed rings (forecasts=(method,
+    spread, n_corrupt): mcd_stream_forecast_state_t; forecast_group / forecast_flush).
     vid_res / center / scale: as for normalize_poses.  All calls are asynchronous on the current stream; one state is driven
     from one stream."""
 
     def __init__(self, n_slots: int, seg_len: int, ring_len: int, num_transform: int, vid_res: Sequence[float], center=None,
-                 scale=None, *, device=None, joint_scores: bool = False):
+                 scale=None, *, device=None, joint_scores: bool = False, forecasts: Optional[Tuple[str, str, int]] = None):
         self.L = _lib.lib()
         _need_gpu()
         self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -912,6 +914,58 @@ class StreamRings:
             with torch.cuda.device(dev):
                 self.joint_scores_ring = torch.zeros(self.n_slots, self.num_transform, self.ring_len, 17, device=dev, dtype=torch.float32)
             self._jstate = _lib.StreamJointState(joint_scores=self.joint_scores_ring.data_ptr())
+        # forecasts = (method, spread, n_corrupt): the forecast and observed rings (mcd_stream_forecast_state_t); without it nothing
+        # is allocated
+        self.forecast_ring, self.observed_ring, self._fstate, self._forecast = None, None, None, None
+        if forecasts is not None:
+            method, spread, n_corrupt = forecasts
+            if method not in _lib.FORECAST:
+                raise ValueError(f"forecast method must be one of {tuple(_lib.FORECAST)}, got {method!r}")
+            if spread not in ("mean", "median"):
+                raise ValueError(f"forecast spread must be 'mean' or 'median', got {spread!r}")
+            if not 1 <= int(n_corrupt) <= _lib.MCD_MAX_FRAMES:
+                raise ValueError(f"n_corrupt must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {n_corrupt}")
+            self._forecast = (_lib.FORECAST[method], _lib.FORECAST[spread])
+            with torch.cuda.device(dev):      # (zeros: the kernels need no initial value, two streams in one state compare equal)
+                self.forecast_ring = torch.zeros(self.n_slots, self.ring_len, int(n_corrupt), 34, device=dev, dtype=torch.float32)
+                self.observed_ring = torch.zeros(self.n_slots, self.ring_len, 34, device=dev, dtype=torch.float32)
+            self._fstate = _lib.StreamForecastState(forecast=self.forecast_ring.data_ptr(), observed=self.observed_ring.data_ptr(),
+                                                    n_corrupt=int(n_corrupt))
+
+    def _forecast_outputs(self, rows: int):
+        dev = self.device
+        return (torch.empty(rows, 34, device=dev, dtype=torch.float32), torch.empty(rows, 34, device=dev, dtype=torch.float32),
+                torch.empty(rows, 34, device=dev, dtype=torch.float32), torch.empty(rows, device=dev, dtype=torch.int32),
+                torch.empty(rows, device=dev, dtype=torch.float32))
+
+    def forecast_group(self, raw: torch.Tensor, desc: torch.Tensor, n: int, loss_all: Optional[torch.Tensor],
+                       poses_all: Optional[torch.Tensor], win: Optional[torch.Tensor], n_windows: int, cfg: "_lib.ScoreCfg",
+                       aggregation: str):
+        """mcd_stream_forecast_group, behind the group's scoring call: raw / desc as for push_group, loss_all (num_transform *
+        n_windows, S) and poses_all (num_transform * n_windows, S, 2, Tx, 17) of that call, win as for frame_scores_group, cfg: the
+        model's frame lists and sample count, aggregation 'best' | 'worst' -> (expected (n_windows, 34) pixels, expected_norm
+        (n_windows, 34), observed (n_windows, 34), count (n_windows,) int32, spread (n_windows,)) in (tick, j) order: the row each
+        window finalised.  A group without a window (n_windows = 0) only stores its raw rows."""
+        nw = int(n_windows)
+        with torch.cuda.device(self.device):
+            out = self._forecast_outputs(nw)
+            c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+            _lib.check(self.L.mcd_stream_forecast_group(
+                C.byref(self._state), C.byref(self._fstate), _ptr(raw), _ptr(desc), int(n), _ptr(loss_all) if nw else None,
+                _ptr(poses_all) if nw else None, _ptr(win) if nw else None, nw, C.byref(cfg), _lib.AGGR[aggregation], self._forecast[0],
+                self._forecast[1], self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), *(_ptr(o) if nw else None for o in out), _stream()))
+        return out
+
+    def forecast_flush(self, win: Optional[torch.Tensor], n: int, cfg: "_lib.ScoreCfg"):
+        """mcd_stream_forecast_flush: as `flush` -> the five tensors of forecast_group with n * (seg_len - 1) rows."""
+        with torch.cuda.device(self.device):
+            out = self._forecast_outputs(int(n) * (self.seg_len - 1))
+            if out[3].numel():
+                c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+                _lib.check(self.L.mcd_stream_forecast_flush(
+                    C.byref(self._state), C.byref(self._fstate), _ptr(win), int(n), C.byref(cfg), self._forecast[0], self._forecast[1],
+                    self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), *(_ptr(o) for o in out), _stream()))
+        return out
 
     def joint_scores_group(self, maps: torch.Tensor, win: torch.Tensor, n_windows: int, cfg: "_lib.ScoreCfg") -> torch.Tensor:
         """mcd_stream_joint_scores_group: maps (num_transform * n_windows, Tx, 17) error maps of the group's windows in the order

@@ -35,7 +35,14 @@ in the tick's one copy.  The definitions stand above `ClipScoreCfg`.
 Per-joint frame scores (opt-in, `PoseStream(joint_scores=True)`): the tick's scoring call also yields the error maps
 of its windows (mcd_error_maps: per forecast frame and joint, the loss behind the window's score), a second ring (max_tracks,
 num_transform, L, 17) takes their per-row maximum with the same window table (mcd_stream_joint_scores_group), and
-`Tick.joint_final` / `FrameScores.joints` carry them row for row with the frame scores."""
+`Tick.joint_final` / `FrameScores.joints` carry them row for row with the frame scores.
+
+Expected poses (opt-in, `PoseStream(forecasts=ForecastCfg(...))`): what the model expected to see at a row -- the
+selected forecasts of the windows covering it collapsed into one pose, in image pixels next to the observed row, with how many
+windows forecast it and how much they disagree; the dataset path's --forecast-tracks, bit for bit.  The tick's scoring call also
+yields the per-sample losses and poses, a forecast ring (max_tracks, L, n_corrupt, 34) and a ring of the raw rows (max_tracks, L,
+34) keep what the rows in flight need (mcd_stream_forecast_group, mcd_stream_forecast_flush), and `Tick.forecast` /
+`FrameScores.forecast` carry the rows with the frame scores.  `forecast_cover` is the definition as code."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -741,6 +748,58 @@ class ClipTable:
         return ClipTick([], [], outs.astype(np.int32).reshape(-1, 4), [clip] * len(fr), fr.astype(np.int32), 0, span)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# Expected poses (include/mocodad_hip.h: mcd_stream_forecast_state_t).  Definition, the dataset path's
+# (eval_MoCoDAD.py --forecast-tracks = mcd_forecast_assemble + mcd_denormalize_poses): for row r of a track take the windows of
+# transform 0 that FORECAST it -- row r is the window's corrupt frame j when the window ends at row r + seg_len - 1 - corrupt_idx[j]
+# -- each with its selected forecast (the pose of the model's best / worst sample; zeros when no sample passes); combine them in
+# ascending window order in float64 (unique / mean / median per feature, the population standard deviation per feature and its mean
+# or median over the 34 features), and take the result to pixels in the bounding box of the observed row.  A row is final with the
+# window whose oldest row it is: every window covering it is in by then.  At a close the pending rows see the windows that exist.
+# ----------------------------------------------------------------------------------------------------------------------
+FORECAST_METHODS = ("unique", "mean", "median")
+FORECAST_SPREADS = ("mean", "median")
+
+
+@dataclass
+class ForecastCfg:
+    """PoseStream(forecasts=ForecastCfg(...)): method / spread as eval_MoCoDAD.py's --forecast-method / --forecast-spread."""
+    method: str = "median"
+    spread: str = "mean"
+
+
+def forecast_cover(corrupt_idx: Sequence[int], seg_len: int, r: int, r_last: int) -> List[Tuple[int, int]]:
+    """The windows of a track that forecast its row r, the track's last row so far being r_last: [(window end row, j)] in window
+    order (ascending end row), j = the index among the corrupt frames at which the window holds the row.  A window ending at row e
+    covers rows e - seg_len + 1 .. e and exists when seg_len - 1 <= e <= r_last.  (At finality r_last = r + seg_len - 1.)"""
+    seg_len, r, r_last = int(seg_len), int(r), int(r_last)
+    out = []
+    for j, c in enumerate(corrupt_idx):
+        e = r + seg_len - 1 - int(c)
+        if int(c) <= r and e <= r_last:
+            out.append((e, j))
+    return sorted(out)
+
+
+@dataclass
+class ForecastRows:
+    """Expected poses, row for row with the FrameScores that carries them (device tensors): expected (n, 34) fp32 image pixels in
+    the CSV's order x1,y1,...,x17,y17; expected_norm (n, 34) fp32 the same pose in normalised coordinates; observed (n, 34) fp32
+    the raw row the track pushed for that frame; count (n,) int32 windows that forecast the row (0: expected, expected_norm and
+    spread are zero -- the first rows of a track); spread (n,) fp32 their disagreement."""
+    expected: "object"
+    expected_norm: "object"
+    observed: "object"
+    count: "object"
+    spread: "object"
+
+    def __len__(self):
+        return int(self.count.shape[0])
+
+    def rows(self, a: int, b: int) -> "ForecastRows":
+        return ForecastRows(self.expected[a:b], self.expected_norm[a:b], self.observed[a:b], self.count[a:b], self.spread[a:b])
+
+
 @dataclass
 class FrameScores:
     """Final per-row frame scores: row i belongs to track keys[i] at frame id frames[i]; values (n, num_transform) fp32 on the
@@ -749,6 +808,7 @@ class FrameScores:
     frames: np.ndarray
     values: "object"
     joints: "object" = None           # PoseStream(joint_scores=True): (n, num_transform, 17) fp32 device, the same rows per joint
+    forecast: Optional[ForecastRows] = None   # PoseStream(forecasts=...): the expected poses of the same rows
 
     def __len__(self):
         return len(self.keys)
@@ -771,6 +831,8 @@ class Tick:
     joint_final: "object" = None      # PoseStream(joint_scores=True): (n_emit, num_transform, 17) fp32 device, row for row with
     #                                   `final` (= final.joints): per joint the maximum over the windows FORECASTING the row; 0 for
     #                                   a row no window forecasts (the first n_cond rows of a track).  closed.joints: the tails
+    forecast: Optional[ForecastRows] = None   # PoseStream(forecasts=...): the expected poses, row for row with `final`
+    #                                   (= final.forecast).  closed.forecast: the tails
 
 
 class PoseStream:
@@ -789,13 +851,19 @@ class PoseStream:
     maximum (mcd_stream_joint_scores_group), and `Tick.joint_final`, `Tick.closed.joints` and the `joints` of what `close`
     returns carry them row for row with the frame scores -- bit for bit the dataset path's mcd_joint_scatter_max.  Off (the
     default): no extra launch, no poses requested, nothing allocated.
+    forecasts: None, or a ForecastCfg: the expected pose of every row (pose model with fixed conditioning indices and a
+    best / worst aggregation only; the definition stands above ForecastCfg).  Every scoring call then also writes the per-sample
+    losses and poses, mcd_stream_forecast_group keeps each transform-0 window's selected forecast and the raw rows in two more
+    rings and reduces the rows that became final, and `Tick.forecast`, `Tick.closed.forecast` and the `forecast` of what `close`
+    returns carry them row for row with the frame scores -- bit for bit eval_MoCoDAD.py's --forecast-tracks.  Off (the default):
+    no extra launch, no poses requested, nothing allocated.
 
     One PoseStream is driven from ONE stream (the current stream of the first push): its rings, staging buffers and the track
     table are per-tick state, and the launches of a tick are ordered only by that stream."""
 
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
                  num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
-                 clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False):
+                 clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False, forecasts: Optional[ForecastCfg] = None):
         from .engine import ClipRings, StreamRings
         from .utils.transforms import affine_table
         if getattr(model, "is_pretrain", False):
@@ -807,6 +875,18 @@ class PoseStream:
         if self.joint_scores and self.latent:
             raise NotImplementedError("PoseStream(joint_scores=True) needs the pose model: MoCoDADlatent takes its loss on a latent "
                                       "code, and a latent has no joints")
+        self.forecasts = forecasts
+        if forecasts is not None:
+            if self.latent:
+                raise NotImplementedError("PoseStream(forecasts=...) needs the pose model: MoCoDADlatent forecasts a latent code (pose-"
+                                          "space forecasts of the latent model on a stream belong with its joint_scores, not built)")
+            if forecasts.method not in FORECAST_METHODS:
+                raise ValueError(f"forecasts: method must be one of {FORECAST_METHODS}, got {forecasts.method!r}")
+            if forecasts.spread not in FORECAST_SPREADS:
+                raise ValueError(f"forecasts: spread must be one of {FORECAST_SPREADS}, got {forecasts.spread!r}")
+            if model.aggregation_strategy not in ("best", "worst"):
+                raise ValueError(f"PoseStream(forecasts=...) needs an aggregation that selects a pose, best or worst: aggregation_strategy "
+                                 f"{model.aggregation_strategy!r} aggregates losses and selects none")
         if self.latent and model.device.type != "cuda":
             raise ValueError("PoseStream scores the latent model (MoCoDADlatent) on a cuda device only: move the module to one "
                              "first (there is no CPU fallback)")
@@ -824,8 +904,10 @@ class PoseStream:
         self.num_transform = nt = max(1, int(model.num_transforms if num_transform is None else num_transform))
         self.table = TrackTable(max_tracks, self.seg_len, ring_len, max_idle)
         n = self.table.max_tracks
-        self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev,
-                                 **({"joint_scores": True} if self.joint_scores else {}))
+        extra = {"joint_scores": True} if self.joint_scores else {}
+        if forecasts is not None:
+            extra["forecasts"] = (forecasts.method, forecasts.spread, len(self.scorer.corrupt_idx))
+        self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev, **extra)
         self.ring = self.rings.ring
         self.clips, self.clip_rings, clip_words = None, None, 0
         if clip_scores is not None:
@@ -882,7 +964,12 @@ class PoseStream:
             win = self._upload([plan.win])[0] if n and pend else None
             out = self.rings.flush(win, n)
             joints = self.rings.joint_flush(win, n) if self.joint_scores else None
-        return FrameScores(keys, plan.frames.reshape(-1).copy(), out, joints)
+            fc = ForecastRows(*self.rings.forecast_flush(win, n, self._forecast_cfg(0))) if self.forecasts is not None else None
+        return FrameScores(keys, plan.frames.reshape(-1).copy(), out, joints, fc)
+
+    def _forecast_cfg(self, n_windows: int):
+        """The frame lists and the sample count the forecast entries read."""
+        return self.scorer._score_cfg(n_windows, int(self.model.n_generated_samples), 2)
 
     def _clip_launches(self, cticks: List[ClipTick], parts: list):
         """The launch pairs of a tick's / a group's ClipTicks (one, unless batch_clip_ticks has to cut) -> (launches, index in
@@ -989,14 +1076,21 @@ class PoseStream:
                 score = self.scorer.score if self.latent else self.scorer.score_fused
                 res = score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
                             noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores,
-                            **({"want_maps": True} if self.joint_scores else {}))
+                            **({"want_maps": True} if self.joint_scores else {}),
+                            # forecasts: the per-sample losses and the poses come back (the maps launch then reads these: written once)
+                            **({"want_all": True, "want_poses": True} if self.forecasts is not None else {}))
                 final = self.rings.frame_scores_group(scores, win_d, nw)
                 if self.joint_scores:       # the windows' error maps into the joint ring, by the same sorted window table
                     jfinal = self.rings.joint_scores_group(res[3], win_d, nw, self.scorer._score_cfg(nw, 1, 2))
             else:
+                res = (None, None, None)
                 final = torch.empty(0, nt, device=dev, dtype=torch.float32)
                 if self.joint_scores:
                     jfinal = torch.empty(0, nt, 17, device=dev, dtype=torch.float32)
+            if self.forecasts is not None:  # the raw rows and the windows' selected forecasts into their rings; the final rows out
+                fc = ForecastRows(*self.rings.forecast_group(raw_d if n else None, desc_d if n else None, n, res[1], res[2],
+                                                             win_d if nw else None, nw, self._forecast_cfg(nt * nw),
+                                                             self.model.aggregation_strategy))
             clips = [None] * len(g.plans)
             if g.clip is not None:
                 clips = self._clip_run(g.clip, launches, views[at:at + 3] or None, final, closed.values)
@@ -1007,12 +1101,14 @@ class PoseStream:
             a, b = nt * w0, nt * (w0 + ne)
             wb = WindowBatch(self.ring, base[a:b], trans[a:b], self.affine, self.seg_len) if ne else None
             jf = jfinal[w0:w0 + ne] if self.joint_scores else None
+            ff = fc.rows(w0, w0 + ne) if self.forecasts is not None else None
             tail = FrameScores(closed.keys[c0 * pend:c1 * pend], closed.frames[c0 * pend:c1 * pend].copy(),
-                               closed.values[c0 * pend:c1 * pend], closed.joints[c0 * pend:c1 * pend] if self.joint_scores else None)
+                               closed.values[c0 * pend:c1 * pend], closed.joints[c0 * pend:c1 * pend] if self.joint_scores else None,
+                               closed.forecast.rows(c0 * pend, c1 * pend) if self.forecasts is not None else None)
             out.append(Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                             trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores[a:b], windows=wb,
-                            final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne], jf), closed=tail,
-                            first_window_id=first + a, clip=clips[i], joint_final=jf))
+                            final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne], jf, ff), closed=tail,
+                            first_window_id=first + a, clip=clips[i], joint_final=jf, forecast=ff))
             c0 = c1
         return out
 

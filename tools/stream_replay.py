@@ -31,6 +31,11 @@ with a score at that frame, not the clip's whole roster, and neither pad_size no
 asserted against the other.
 --joint-scores: per-joint frame scores in every tick (PoseStream(joint_scores=True)): "tick" then includes the error
 maps launch behind the scoring call and mcd_stream_joint_scores_group; pose model only.
+--forecasts [--forecast-method M] [--forecast-spread S]: the expected pose of every row in every tick (PoseStream(forecasts=
+ForecastCfg(M, S))): "tick" then includes the scoring call writing its per-sample losses and poses and the two launches
+of mcd_stream_forecast_group (closes: mcd_stream_forecast_flush); pose model with a best / worst aggregation only.
+--forecasts-out OUT.npz: the rows of the warm-up replay in the layout of eval_MoCoDAD.py --forecast-tracks (rows, frames, observed,
+expected, expected_norm, count, spread, joint_names), sorted by (scene, clip, person, frame); not timed.
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
 emitted windows, the range of the per-replay medians (the spread), and the same for the baseline."""
 import argparse
@@ -50,7 +55,7 @@ from mocodad_amd.data.windows import TrajectoryWindows, WindowBatch  # noqa: E40
 from mocodad_amd.engine import normalize_poses  # noqa: E402
 from mocodad_amd.models.mocodad import MoCoDAD  # noqa: E402
 from mocodad_amd.models.mocodad_latent import MoCoDADlatent  # noqa: E402
-from mocodad_amd.stream import ClipScoreCfg, PoseStream, ticks_by_frame  # noqa: E402
+from mocodad_amd.stream import ClipScoreCfg, ForecastCfg, PoseStream, ticks_by_frame  # noqa: E402
 from mocodad_amd.utils.argparser import load_config  # noqa: E402
 
 
@@ -89,6 +94,10 @@ def main():
     ap.add_argument("--clip-scores", action="store_true", help="online per-clip frame scores in every tick (Tick.clip)")
     ap.add_argument("--sigma", type=float, default=None, help="Gaussian sigma of the clip scores (default: the model's filter_kernel_size)")
     ap.add_argument("--joint-scores", action="store_true", help="per-joint frame scores in every tick (Tick.joint_final)")
+    ap.add_argument("--forecasts", action="store_true", help="expected poses in every tick (Tick.forecast)")
+    ap.add_argument("--forecast-method", choices=("unique", "mean", "median"), default="median")
+    ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean")
+    ap.add_argument("--forecasts-out", default=None, metavar="OUT.npz", help="--forecasts: write the rows of the warm-up replay")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
     cli = ap.parse_args()
@@ -156,10 +165,21 @@ def main():
 
     clip_keys = sorted({k[:2] for k, _, _ in tracks})
     clip_cfg = ClipScoreCfg(sigma=cli.sigma, max_clips=len(clip_keys)) if cli.clip_scores else None
+    if cli.forecasts_out and not cli.forecasts:
+        raise SystemExit("--forecasts-out needs --forecasts")
+    extra = {"joint_scores": True} if cli.joint_scores else {}
+    if cli.forecasts:
+        extra["forecasts"] = ForecastCfg(cli.forecast_method, cli.forecast_spread)
+    FIELDS = ("observed", "expected", "expected_norm", "count", "spread")
 
-    def replay(collect=None, online=None):
+    def replay(collect=None, online=None, forecast_rows=None):
         stream = PoseStream(model, vid_res=vid_res, center=center, scale=scale, max_tracks=peak, ring_len=ring_len,
-                            num_transform=nt, clip_scores=clip_cfg, **({"joint_scores": True} if cli.joint_scores else {}))
+                            num_transform=nt, clip_scores=clip_cfg, **extra)
+
+        def keep(fs):       # (the warm-up replay only: copies to the host, outside the timed region)
+            if forecast_rows is not None and len(fs):
+                forecast_rows.append((np.asarray(fs.keys, np.int64).reshape(-1, 3), np.asarray(fs.frames, np.int64))
+                                     + tuple(getattr(fs.forecast, name).cpu().numpy() for name in FIELDS))
         times, counts, rows, spent = [], [], 0, 0.0
         for call, done in calls:
             torch.cuda.synchronize()
@@ -180,8 +200,11 @@ def main():
                         collect[idx] = tick.scores.cpu().numpy()
             if online is not None:
                 online += [tick.clip for tick in out]
+            for tick in out if forecast_rows is not None else ():
+                keep(tick.closed)
+                keep(tick.final)
             if done:
-                stream.close(done)
+                keep(stream.close(done))
         if clip_cfg is not None:
             for clip in clip_keys:
                 _, tail = stream.close_clip(clip)
@@ -206,7 +229,16 @@ def main():
 
     scores = np.full(nt * n, np.nan, np.float32)
     online = [] if cli.clip_scores else None
-    _, counts, _ = replay(scores, online)        # warm-up replay (code objects, allocator pools); also the scores for the AUC
+    frows = [] if cli.forecasts_out else None
+    _, counts, _ = replay(scores, online, frows)        # warm-up replay (code objects, allocator pools); also the scores for the AUC
+    if frows is not None:
+        from mocodad_amd._lib import JOINT_NAMES
+        cols = [np.concatenate([r[i] for r in frows]) for i in range(2 + len(FIELDS))]
+        order = np.lexsort((cols[1], cols[0][:, 2], cols[0][:, 1], cols[0][:, 0]))
+        np.savez(cli.forecasts_out, rows=cols[0][order], row_columns=np.asarray(["scene", "clip", "person"]), frames=cols[1][order],
+                 joint_names=np.asarray(JOINT_NAMES), method=np.asarray(cli.forecast_method), spread_method=np.asarray(cli.forecast_spread),
+                 **{name: cols[2 + i][order] for i, name in enumerate(FIELDS)})
+        print(f"forecasts: {len(order)} track rows, {int((cols[2 + FIELDS.index('count')] > 0).sum())} with a forecast -> {cli.forecasts_out}")
     baseline(counts)
     assert not np.isnan(scores).any() and sum(counts) == nt * n, "the replay did not emit every window of the dataset path"
     auc = None
@@ -245,6 +277,7 @@ def main():
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
            "model": "MoCoDADlatent" if latent else "MoCoDAD", "clip_scores": clip_res, "joint_scores": bool(cli.joint_scores),
+           "forecasts": {"method": cli.forecast_method, "spread": cli.forecast_spread} if cli.forecasts else None,
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
