@@ -1,6 +1,6 @@
 """Builds libmocodad_hip.so for gfx950 from mocodad_amd/csrc: mcd_api.hip (C ABI, routes, launches; with its headers mcd_pack.hpp, the
-weight packer, mcd_call.hpp, the front end of a scoring call, mcd_post_kernel.hpp, its own kernels, and mcd_generic_kernel.hpp, the
-runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels; once
+weight packer, mcd_call.hpp, the front end of a scoring call, mcd_post_kernel.hpp, its own kernels, mcd_stream_kernel.hpp and
+mcd_stream_api.hpp, the kernels and entry points of a live stream, and mcd_generic_kernel.hpp, the runtime-shape kernels) plus mcd_inst.hip once per unit of kernel instantiations (csrc/mcd_instances.hpp) and mcd_latent.hip (the MoCoDADlatent kernels; once
 more per unit of its encode kernels), compiled in parallel and linked with hipcc.
 
     python -m mocodad_amd.build                       # the shipped library (mocodad_amd/libmocodad_hip.so)

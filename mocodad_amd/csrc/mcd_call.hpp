@@ -1,5 +1,5 @@
 // mcd_call.hpp — the front end of a scoring call, shared by the pose entry points (mcd_api.hip) and the latent ones
-// (mcd_latent_api.hpp): the window view, the checks of the frame lists and of the aggregation, the workspace layouts, the launch of
+// (mcd_latent_api.hpp): the window view, the checks of the frame lists, the aggregation, the pose geometry and the forecast methods, the workspace layouts, the launch of
 // a condition encoder for a route, and the condition-encoder fields of a handle.  Host code only, like mcd_pack.hpp.  Included by
 // mcd_api.hip behind its routes and launchers (cond_route, launch_cond_view, launch_cond_plain, the *_ws_bytes functions), which it
 // calls.  The ORDER in which an entry point applies the checks is part of its behaviour (the first failing check names the
@@ -46,6 +46,21 @@ int check_aggregation(int strategy, float quantile, unsigned allowed, const char
     if (strategy < 0 || strategy > 31 || !((allowed >> strategy) & 1u)) return fail(MCD_EINVAL, unknown);
     if (strategy == MCD_AGGR_QUANTILE && !(quantile >= 0.f && quantile <= 1.f))       // (also rejects NaN; torch.quantile raises)
         return fail(MCD_EINVAL, "quantile must be in [0, 1]");
+    return MCD_OK;
+}
+
+// the geometry of a pose row's (de)normalisation: the image size and the RobustScaler's statistics
+int check_pose_geometry(float vid_w, float vid_h, const double* center, const double* scale) {
+    if (!std::isfinite(vid_w) || !std::isfinite(vid_h)) return fail(MCD_EINVAL, "vid_res must be finite");
+    if (!center != !scale) return fail(MCD_EINVAL, "center and scale are both given or both NULL");
+    return MCD_OK;
+}
+// how the overlapping forecasts of a (person, frame) cell become one pose, and their spread one number
+int check_forecast_methods(int method, int spread_method) {
+    if (method != MCD_FORECAST_UNIQUE && method != MCD_FORECAST_MEAN && method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "method must be MCD_FORECAST_UNIQUE, MEAN or MEDIAN");
+    if (spread_method != MCD_FORECAST_MEAN && spread_method != MCD_FORECAST_MEDIAN)
+        return fail(MCD_EINVAL, "spread_method must be MCD_FORECAST_MEAN or MEDIAN");
     return MCD_OK;
 }
 

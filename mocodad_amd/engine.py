@@ -713,19 +713,38 @@ class LatentReconstructor(_LatentHandle):
         return poses, loss
 
 
-def _scaler_stats(center, scale, dev) -> list:
-    """[center, scale] as (34,) float64 device tensors (the precision sklearn's transform runs in), or [] when both are None."""
+def _scaler_stats(center, scale, dev) -> tuple:
+    """(center, scale) as (34,) float64 device tensors (the precision sklearn's transform runs in), or (None, None)."""
     if (center is None) != (scale is None):
         raise ValueError("center and scale go together (both None = no robust scaling)")
     stats = []
     for name, a in (("center", center), ("scale", scale)):
         if a is None:
-            continue
+            return None, None
         a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
         if a.shape != (34,):
             raise ValueError(f"{name} must hold 34 features, got shape {a.shape}")
         stats.append(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
-    return stats
+    return tuple(stats)
+
+
+def _vid_res(vid_res: Sequence[float], need: str = "finite") -> tuple:
+    """The image size as the fp32 values the kernels take; `need`: what the caller's error text asks for ('finite': the caller
+    unpacks the pair, and another length fails there)."""
+    res = tuple(float(np.float32(v)) for v in vid_res)
+    if (len(res) != 2 and need != "finite") or (len(res) == 2 and not all(np.isfinite(res))):
+        raise ValueError(f"vid_res must be {need}, got {tuple(vid_res)}")
+    return res
+
+
+def forecast_codes(method: str, spread: str, names: Tuple[str, str] = ("method", "spread_method"),
+                   spreads: str = "'mean' or 'median'") -> Tuple[int, int]:
+    """The names of a forecast method and spread -> their MCD_FORECAST_* codes; `names` and `spreads`: the caller's error text."""
+    if method not in _lib.FORECAST:
+        raise ValueError(f"{names[0]} must be one of {tuple(_lib.FORECAST)}, got {method!r}")
+    if spread not in ("mean", "median"):
+        raise ValueError(f"{names[1]} must be {spreads}, got {spread!r}")
+    return _lib.FORECAST[method], _lib.FORECAST[spread]
 
 
 def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, device=None,
@@ -752,10 +771,8 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
         raise ValueError(f"raw pose rows must be (n_frames, 34) = x1,y1,...,x17,y17, got {shape}")
     if not finite:
         raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
-    w, h = (float(np.float32(v)) for v in vid_res)
-    if not (np.isfinite(w) and np.isfinite(h)):
-        raise ValueError(f"vid_res must be finite, got {tuple(vid_res)}")
-    stats = _scaler_stats(center, scale, dev)
+    w, h = _vid_res(vid_res)
+    c, s = _scaler_stats(center, scale, dev)
     n = shape[0]
     if out is None:
         out = torch.empty(n, 2, 17, device=dev, dtype=torch.float32)
@@ -764,7 +781,6 @@ def normalize_poses(raw, vid_res: Sequence[float], center=None, scale=None, *, d
     with torch.cuda.device(dev):
         if raw is None:
             raw = torch.from_numpy(raw_h).to(dev)
-        c, s = (stats[0], stats[1]) if stats else (None, None)
         _lib.check(L.mcd_normalize_poses(_ptr(raw), n, w, h, _ptr(c), _ptr(s), _ptr(out), _stream()))
     return out
 
@@ -798,10 +814,7 @@ def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, 
     forecasts is 0 with count 0, one with more than max_cover pairs is NaN with its true count.  out: the caller's three buffers
     instead of new ones; workspace: the caller's int32 scratch of at least n_cells * max_cover words.  Asynchronous on the current
     stream; arguments are checked before anything touches the device."""
-    if method not in _lib.FORECAST:
-        raise ValueError(f"method must be one of {tuple(_lib.FORECAST)}, got {method!r}")
-    if spread_method not in ("mean", "median"):
-        raise ValueError(f"spread_method must be 'mean' or 'median', got {spread_method!r}")
+    codes = forecast_codes(method, spread_method)
     max_cover, n_cells = int(max_cover), int(n_cells)
     if not 1 <= max_cover <= _lib.MCD_MAX_FRAMES:
         raise ValueError(f"max_cover must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {max_cover}")
@@ -836,8 +849,8 @@ def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, 
             o_spread = torch.empty(n_cells, device=dev, dtype=torch.float32)
         if workspace is None:
             workspace = torch.empty(max(n_cells * max_cover, 1), device=dev, dtype=torch.int32)
-        _lib.check(L.mcd_forecast_assemble(_ptr(poses), _ptr(cell), N, Tx, n_cells, _lib.FORECAST[method], _lib.FORECAST[spread_method],
-                                           max_cover, _ptr(workspace), _ptr(o_pose), _ptr(o_count), _ptr(o_spread), _stream()))
+        _lib.check(L.mcd_forecast_assemble(_ptr(poses), _ptr(cell), N, Tx, n_cells, codes[0], codes[1], max_cover, _ptr(workspace),
+                                           _ptr(o_pose), _ptr(o_count), _ptr(o_spread), _stream()))
     return o_pose, o_count, o_spread
 
 
@@ -860,9 +873,7 @@ def denormalize_poses(norm: torch.Tensor, raw, vid_res: Sequence[float], center=
         raise ValueError("raw pose rows hold NaN / inf values (the trajectory CSVs hold finite coordinates only)")
     if count is not None and (tuple(count.shape) != (n,) or count.dtype.is_floating_point):
         raise ValueError(f"count must be an integer ({n},) tensor, got {tuple(count.shape)} {count.dtype}")
-    w, h = (float(np.float32(v)) for v in vid_res)
-    if not (np.isfinite(w) and np.isfinite(h)):
-        raise ValueError(f"vid_res must be finite, got {tuple(vid_res)}")
+    w, h = _vid_res(vid_res)
     for name, a in (("center", center), ("scale", scale)):
         if a is not None and tuple(np.shape(a) if not torch.is_tensor(a) else a.shape) != (34,):
             raise ValueError(f"{name} must hold 34 features, got shape {tuple(np.shape(a) if not torch.is_tensor(a) else a.shape)}")
@@ -870,13 +881,12 @@ def denormalize_poses(norm: torch.Tensor, raw, vid_res: Sequence[float], center=
     out = _caller_buffer("out", out, (n, 34), torch.float32, dev)
     L = _lib.lib()
     _need_gpu()
-    stats = _scaler_stats(center, scale, dev)
+    c, s = _scaler_stats(center, scale, dev)
     norm, raw_t = _f32c(norm, dev), _f32c(raw_t, dev)
     count = _i32c(count, dev) if count is not None else None
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty(n, 34, device=dev, dtype=torch.float32)
-        c, s = (stats[0], stats[1]) if stats else (None, None)
         _lib.check(L.mcd_denormalize_poses(_ptr(norm), _ptr(raw_t), _ptr(count), n, w, h, _ptr(c), _ptr(s), _ptr(out), _stream()))
     return out
 
@@ -898,9 +908,7 @@ class StreamRings:
         _need_gpu()
         self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.n_slots, self.seg_len, self.ring_len, self.num_transform = int(n_slots), int(seg_len), int(ring_len), int(num_transform)
-        self.vid_res = tuple(float(np.float32(v)) for v in vid_res)
-        if len(self.vid_res) != 2 or not all(np.isfinite(self.vid_res)):
-            raise ValueError(f"vid_res must be two finite numbers, got {tuple(vid_res)}")
+        self.vid_res = _vid_res(vid_res, "two finite numbers")
         self._stats = _scaler_stats(center, scale, dev)
         with torch.cuda.device(dev):
             self.ring = torch.zeros(self.n_slots * 2 * self.ring_len * 34, device=dev, dtype=torch.float32)
@@ -919,13 +927,9 @@ class StreamRings:
         self.forecast_ring, self.observed_ring, self._fstate, self._forecast = None, None, None, None
         if forecasts is not None:
             method, spread, n_corrupt = forecasts
-            if method not in _lib.FORECAST:
-                raise ValueError(f"forecast method must be one of {tuple(_lib.FORECAST)}, got {method!r}")
-            if spread not in ("mean", "median"):
-                raise ValueError(f"forecast spread must be 'mean' or 'median', got {spread!r}")
+            self._forecast = forecast_codes(method, spread, ("forecast method", "forecast spread"))
             if not 1 <= int(n_corrupt) <= _lib.MCD_MAX_FRAMES:
                 raise ValueError(f"n_corrupt must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {n_corrupt}")
-            self._forecast = (_lib.FORECAST[method], _lib.FORECAST[spread])
             with torch.cuda.device(dev):      # (zeros: the kernels need no initial value, two streams in one state compare equal)
                 self.forecast_ring = torch.zeros(self.n_slots, self.ring_len, int(n_corrupt), 34, device=dev, dtype=torch.float32)
                 self.observed_ring = torch.zeros(self.n_slots, self.ring_len, 34, device=dev, dtype=torch.float32)
@@ -949,7 +953,7 @@ class StreamRings:
         nw = int(n_windows)
         with torch.cuda.device(self.device):
             out = self._forecast_outputs(nw)
-            c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+            c, s = self._stats
             _lib.check(self.L.mcd_stream_forecast_group(
                 C.byref(self._state), C.byref(self._fstate), _ptr(raw), _ptr(desc), int(n), _ptr(loss_all) if nw else None,
                 _ptr(poses_all) if nw else None, _ptr(win) if nw else None, nw, C.byref(cfg), _lib.AGGR[aggregation], self._forecast[0],
@@ -961,7 +965,7 @@ class StreamRings:
         with torch.cuda.device(self.device):
             out = self._forecast_outputs(int(n) * (self.seg_len - 1))
             if out[3].numel():
-                c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+                c, s = self._stats
                 _lib.check(self.L.mcd_stream_forecast_flush(
                     C.byref(self._state), C.byref(self._fstate), _ptr(win), int(n), C.byref(cfg), self._forecast[0], self._forecast[1],
                     self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), *(_ptr(o) for o in out), _stream()))
@@ -995,7 +999,7 @@ class StreamRings:
         with torch.cuda.device(self.device):
             base = torch.empty(nw, device=self.device, dtype=torch.int64)
             trans = torch.empty(nw, device=self.device, dtype=torch.int32)
-            c, s = (self._stats[0], self._stats[1]) if self._stats else (None, None)
+            c, s = self._stats
             _lib.check(self.L.mcd_stream_push_group(C.byref(self._state), _ptr(raw), _ptr(desc), int(n), int(n_windows),
                                                     self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), _ptr(base), _ptr(trans),
                                                     _stream()))

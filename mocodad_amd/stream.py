@@ -813,6 +813,10 @@ class FrameScores:
     def __len__(self):
         return len(self.keys)
 
+    def rows(self, a: int, b: int) -> "FrameScores":
+        return FrameScores(self.keys[a:b], self.frames[a:b].copy(), self.values[a:b], None if self.joints is None else self.joints[a:b],
+                           None if self.forecast is None else self.forecast.rows(a, b))
+
 
 @dataclass
 class Tick:
@@ -864,7 +868,7 @@ class PoseStream:
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
                  num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
                  clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False, forecasts: Optional[ForecastCfg] = None):
-        from .engine import ClipRings, StreamRings
+        from .engine import ClipRings, StreamRings, forecast_codes
         from .utils.transforms import affine_table
         if getattr(model, "is_pretrain", False):
             raise NotImplementedError(f"PoseStream does not take {type(model).__name__}: the pretrain stage of the latent model "
@@ -880,10 +884,7 @@ class PoseStream:
             if self.latent:
                 raise NotImplementedError("PoseStream(forecasts=...) needs the pose model: MoCoDADlatent forecasts a latent code (pose-"
                                           "space forecasts of the latent model on a stream belong with its joint_scores, not built)")
-            if forecasts.method not in FORECAST_METHODS:
-                raise ValueError(f"forecasts: method must be one of {FORECAST_METHODS}, got {forecasts.method!r}")
-            if forecasts.spread not in FORECAST_SPREADS:
-                raise ValueError(f"forecasts: spread must be one of {FORECAST_SPREADS}, got {forecasts.spread!r}")
+            forecast_codes(forecasts.method, forecasts.spread, ("forecasts: method", "forecasts: spread"), f"one of {FORECAST_SPREADS}")
             if model.aggregation_strategy not in ("best", "worst"):
                 raise ValueError(f"PoseStream(forecasts=...) needs an aggregation that selects a pose, best or worst: aggregation_strategy "
                                  f"{model.aggregation_strategy!r} aggregates losses and selects none")
@@ -1102,9 +1103,7 @@ class PoseStream:
             wb = WindowBatch(self.ring, base[a:b], trans[a:b], self.affine, self.seg_len) if ne else None
             jf = jfinal[w0:w0 + ne] if self.joint_scores else None
             ff = fc.rows(w0, w0 + ne) if self.forecasts is not None else None
-            tail = FrameScores(closed.keys[c0 * pend:c1 * pend], closed.frames[c0 * pend:c1 * pend].copy(),
-                               closed.values[c0 * pend:c1 * pend], closed.joints[c0 * pend:c1 * pend] if self.joint_scores else None,
-                               closed.forecast.rows(c0 * pend, c1 * pend) if self.forecasts is not None else None)
+            tail = closed.rows(c0 * pend, c1 * pend)
             out.append(Tick(meta=np.tile(plan.meta, (nt, 1)), frames=np.tile(plan.frames, (nt, 1)),
                             trans=np.repeat(np.arange(nt, dtype=np.int64), ne), scores=scores[a:b], windows=wb,
                             final=FrameScores(list(plan.keys), plan.frames[:, 0].copy(), final[w0:w0 + ne], jf, ff), closed=tail,

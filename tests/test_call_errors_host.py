@@ -5,7 +5,10 @@ before the call front end (mcd_call.hpp) existed:
     python tests/test_call_errors_host.py --record      # rewrites the "host" key; see the file's "how" entry
 
 (the stream_push_group / stream_frame_scores_group pairs: from the library of the last commit that also had per-tick stream
-entries, whose state and argument rules they took over one to one -- `--record FILE` writes a copy of the JSON elsewhere)
+entries, whose state and argument rules they took over one to one; the pairs of mcd_denormalize_poses, mcd_forecast_assemble, the
+joint and forecast ring entries and the clip entries, with the pairs that fix the ORDER of two checks failing together: from the
+library of the last commit whose stream entry points stood in mcd_api.hip, each check written out per entry -- `--record FILE`
+writes a copy of the JSON elsewhere)
 
 Pointers that a rejected call never reads are the dummy address P."""
 import ctypes as C
@@ -70,6 +73,78 @@ def _frames(L, c, scores=P, trans=P, meta=P, frames=P, n=4, ws=P, out=P):
 
 def _scatter(L, scores=P, frames=P, row=P, n=2, seg_len=3, n_rows=2, n_frames=4, out=P):
     return L.mcd_scatter_max(scores, frames, row, n, seg_len, n_rows, n_frames, out, None)
+
+
+def _denorm(L, norm=P, raw=P, count=None, n=4, w=640.0, h=360.0, center=None, scale=None, out=P):
+    return L.mcd_denormalize_poses(norm, raw, count, n, w, h, center, scale, out, None)
+
+
+def _assemble(L, poses=P, cell=P, n=4, n_corrupt=3, n_cells=5, method=1, spread=1, max_cover=3, ws=P, pose=P, count=P, spread_out=P):
+    return L.mcd_forecast_assemble(poses, cell, n, n_corrupt, n_cells, method, spread, max_cover, ws, pose, count, spread_out, None)
+
+
+def jstate(js=0x1000):
+    return _lib.StreamJointState(joint_scores=js)
+
+
+def fstate(fc=0x1000, obs=0x1000, n_corrupt=3):
+    return _lib.StreamForecastState(forecast=fc, observed=obs, n_corrupt=n_corrupt)
+
+
+def cfg_idx(corrupt_idx, **kw):
+    """score_cfg with the corrupt frame list replaced"""
+    c = score_cfg(**kw)
+    for i, v in enumerate(corrupt_idx):
+        c.corrupt_idx[i] = v
+    return c
+
+
+BIG_JOINT = dict(n_slots=1 << 19, ring_len=32, nt=16)      # pose and score rings below 2^31 elements, 17 per score cell above
+BIG_FORECAST = dict(n_slots=1 << 19, ring_len=48)           # 2^19 * 48 * 3 * 34 forecast elements
+
+
+def _joint(L, s="state", js="jstate", maps=P, win=P, n_windows=1, cfg="cfg", final=P):
+    s, js, cfg = state() if s == "state" else s, jstate() if js == "jstate" else js, score_cfg() if cfg == "cfg" else cfg
+    return L.mcd_stream_joint_scores_group(C.byref(s) if s is not None else None, C.byref(js) if js is not None else None, maps, win,
+                                           n_windows, C.byref(cfg) if cfg is not None else None, final, None)
+
+
+def _jflush(L, s="state", js="jstate", win=P, n=1, out=P):
+    s, js = state() if s == "state" else s, jstate() if js == "jstate" else js
+    return L.mcd_stream_joint_flush(C.byref(s) if s is not None else None, C.byref(js) if js is not None else None, win, n, out, None)
+
+
+def _fgroup(L, s="state", fs="fstate", raw=P, desc=P, n=2, loss_all=P, poses_all=P, win=P, n_windows=1, cfg="cfg", aggregation=1,
+            method=1, spread=1, w=640.0, h=360.0, center=None, scale=None, expected=P, norm=P, observed=P, count=P, spread_out=P):
+    s, fs, cfg = state() if s == "state" else s, fstate() if fs == "fstate" else fs, score_cfg() if cfg == "cfg" else cfg
+    return L.mcd_stream_forecast_group(C.byref(s) if s is not None else None, C.byref(fs) if fs is not None else None, raw, desc, n,
+                                       loss_all, poses_all, win, n_windows, C.byref(cfg) if cfg is not None else None, aggregation,
+                                       method, spread, w, h, center, scale, expected, norm, observed, count, spread_out, None)
+
+
+def _fflush(L, s="state", fs="fstate", win=P, n=1, cfg="cfg", method=1, spread=1, w=640.0, h=360.0, center=None, scale=None,
+            expected=P, norm=P, observed=P, count=P, spread_out=P):
+    s, fs, cfg = state() if s == "state" else s, fstate() if fs == "fstate" else fs, score_cfg() if cfg == "cfg" else cfg
+    return L.mcd_stream_forecast_flush(C.byref(s) if s is not None else None, C.byref(fs) if fs is not None else None, win, n,
+                                       C.byref(cfg) if cfg is not None else None, method, spread, w, h, center, scale, expected, norm,
+                                       observed, count, spread_out, None)
+
+
+def clip(**over):
+    d = dict(sum=0x1000, lmax=0x1000, lmin=0x1000, n=0x1000, n_clips=2, clip_ring_len=8, num_transform=2)
+    d.update(over)
+    return _lib.ClipState(**d)
+
+
+def _cupdate(L, c="clip", runs=P, n_runs=1, contrib=P, n_contrib=1, finals=P, n_finals=1, tails=P, n_tails=1):
+    c = clip() if c == "clip" else c
+    return L.mcd_stream_clip_update(C.byref(c) if c is not None else None, runs, n_runs, contrib, n_contrib, finals, n_finals, tails,
+                                    n_tails, None)
+
+
+def _cemit(L, c="clip", outs=P, n_out=1, gauss=P, radius=2, shift=1, out=P):
+    c = clip() if c == "clip" else c
+    return L.mcd_stream_clip_emit(C.byref(c) if c is not None else None, outs, n_out, gauss, radius, shift, out, None)
 
 
 CASES = {
@@ -167,6 +242,168 @@ CASES = {
     "stream_flush: n -1": lambda L: L.mcd_stream_flush(C.byref(state()), P, -1, P, None),
     "stream_flush: null win": lambda L: L.mcd_stream_flush(C.byref(state()), None, 1, P, None),
     "stream_flush: null out": lambda L: L.mcd_stream_flush(C.byref(state()), P, 1, None, None),
+    # (order of the checks: the counts before the bound on a group)
+    "stream_push_group: n_windows > n, n = 29": lambda L: _push(L, state(), n=29, n_windows=30),
+    # ---- mcd_denormalize_poses
+    "denormalize_poses: n -1": lambda L: _denorm(L, n=-1),
+    "denormalize_poses: vid_w inf": lambda L: _denorm(L, w=INF),
+    "denormalize_poses: vid_h nan": lambda L: _denorm(L, h=NAN),
+    "denormalize_poses: center without scale": lambda L: _denorm(L, center=P),
+    "denormalize_poses: scale without center": lambda L: _denorm(L, scale=P),
+    "denormalize_poses: vid_w inf, center without scale": lambda L: _denorm(L, w=INF, center=P),
+    "denormalize_poses: null norm": lambda L: _denorm(L, norm=None),
+    "denormalize_poses: null raw": lambda L: _denorm(L, raw=None),
+    "denormalize_poses: null out": lambda L: _denorm(L, out=None),
+    "denormalize_poses: 2^40 rows": lambda L: _denorm(L, n=1 << 40),
+    # ---- mcd_forecast_assemble
+    "forecast_assemble: n -1": lambda L: _assemble(L, n=-1),
+    "forecast_assemble: n_cells -1": lambda L: _assemble(L, n_cells=-1),
+    "forecast_assemble: n_corrupt 0": lambda L: _assemble(L, n_corrupt=0),
+    "forecast_assemble: n_corrupt 33": lambda L: _assemble(L, n_corrupt=33),
+    "forecast_assemble: max_cover 0": lambda L: _assemble(L, max_cover=0),
+    "forecast_assemble: max_cover 33": lambda L: _assemble(L, max_cover=33),
+    "forecast_assemble: method 3": lambda L: _assemble(L, method=3),
+    "forecast_assemble: method -1": lambda L: _assemble(L, method=-1),
+    "forecast_assemble: spread unique": lambda L: _assemble(L, spread=0),
+    "forecast_assemble: spread 3": lambda L: _assemble(L, spread=3),
+    "forecast_assemble: method 3, spread 3": lambda L: _assemble(L, method=3, spread=3),
+    "forecast_assemble: n x n_corrupt over 2^31": lambda L: _assemble(L, n=1 << 30),
+    "forecast_assemble: null workspace": lambda L: _assemble(L, ws=None),
+    "forecast_assemble: null pose_out": lambda L: _assemble(L, pose=None),
+    "forecast_assemble: null count_out": lambda L: _assemble(L, count=None),
+    "forecast_assemble: null spread_out": lambda L: _assemble(L, spread_out=None),
+    "forecast_assemble: null poses": lambda L: _assemble(L, poses=None),
+    "forecast_assemble: null cell": lambda L: _assemble(L, cell=None),
+    # ---- mcd_stream_joint_scores_group / mcd_stream_joint_flush
+    "stream_joint_scores_group: null state": lambda L: _joint(L, s=None),
+    "stream_joint_scores_group: ring_len < seg_len": lambda L: _joint(L, s=state(ring_len=5)),
+    "stream_joint_scores_group: null joint state": lambda L: _joint(L, js=None),
+    "stream_joint_scores_group: null joint_scores": lambda L: _joint(L, js=jstate(None)),
+    "stream_joint_scores_group: joint ring over 2^31": lambda L: _joint(L, s=state(**BIG_JOINT)),
+    "stream_joint_scores_group: null joint state, joint ring over 2^31": lambda L: _joint(L, s=state(**BIG_JOINT), js=None),
+    "stream_joint_scores_group: null cfg": lambda L: _joint(L, cfg=None),
+    "stream_joint_scores_group: cfg seg_len 5": lambda L: _joint(L, cfg=score_cfg(seg_len=5, n_cond=2)),
+    "stream_joint_scores_group: n_cond + n_corrupt != seg_len": lambda L: _joint(L, cfg=score_cfg(n_cond=2)),
+    "stream_joint_scores_group: n_corrupt 0": lambda L: _joint(L, cfg=score_cfg(n_cond=6, n_corrupt=0)),
+    "stream_joint_scores_group: corrupt_idx 6": lambda L: _joint(L, cfg=cfg_idx([3, 4, 6])),
+    "stream_joint_scores_group: corrupt_idx -1": lambda L: _joint(L, cfg=cfg_idx([-1, 4, 5])),
+    "stream_joint_scores_group: corrupt_idx twice": lambda L: _joint(L, cfg=cfg_idx([3, 4, 4])),
+    "stream_joint_scores_group: cfg seg_len 5, corrupt_idx descending": lambda L: _joint(L, cfg=cfg_idx([4, 3, 2], seg_len=5, n_cond=2)),
+    "stream_joint_scores_group: n_windows -1": lambda L: _joint(L, n_windows=-1),
+    "stream_joint_scores_group: n_windows = 29": lambda L: _joint(L, n_windows=29),
+    "stream_joint_scores_group: null maps": lambda L: _joint(L, maps=None),
+    "stream_joint_scores_group: null win": lambda L: _joint(L, win=None),
+    "stream_joint_scores_group: null final_out": lambda L: _joint(L, final=None),
+    "stream_joint_flush: null state": lambda L: _jflush(L, s=None),
+    "stream_joint_flush: null joint state": lambda L: _jflush(L, js=None),
+    "stream_joint_flush: null joint_scores": lambda L: _jflush(L, js=jstate(None)),
+    "stream_joint_flush: joint ring over 2^31": lambda L: _jflush(L, s=state(**BIG_JOINT)),
+    "stream_joint_flush: null joint state, joint ring over 2^31": lambda L: _jflush(L, s=state(**BIG_JOINT), js=None),
+    "stream_joint_flush: n -1": lambda L: _jflush(L, n=-1),
+    "stream_joint_flush: n > n_slots": lambda L: _jflush(L, n=5),
+    "stream_joint_flush: null win": lambda L: _jflush(L, win=None),
+    "stream_joint_flush: null out": lambda L: _jflush(L, out=None),
+    # ---- mcd_stream_forecast_group / mcd_stream_forecast_flush
+    "stream_forecast_group: null state": lambda L: _fgroup(L, s=None),
+    "stream_forecast_group: seg_len 33": lambda L: _fgroup(L, s=state(seg_len=33, ring_len=40)),
+    "stream_forecast_group: null forecast state": lambda L: _fgroup(L, fs=None),
+    "stream_forecast_group: null forecast": lambda L: _fgroup(L, fs=fstate(fc=None)),
+    "stream_forecast_group: null observed": lambda L: _fgroup(L, fs=fstate(obs=None)),
+    "stream_forecast_group: null forecast state, method 3": lambda L: _fgroup(L, fs=None, method=3),
+    "stream_forecast_group: state n_corrupt 0": lambda L: _fgroup(L, fs=fstate(n_corrupt=0)),
+    "stream_forecast_group: state n_corrupt 33": lambda L: _fgroup(L, fs=fstate(n_corrupt=33)),
+    "stream_forecast_group: null cfg": lambda L: _fgroup(L, cfg=None),
+    "stream_forecast_group: cfg seg_len 5": lambda L: _fgroup(L, cfg=score_cfg(seg_len=5, n_cond=2)),
+    "stream_forecast_group: cfg n_corrupt 2": lambda L: _fgroup(L, cfg=score_cfg(n_cond=4, n_corrupt=2)),
+    "stream_forecast_group: n_cond + n_corrupt != seg_len": lambda L: _fgroup(L, cfg=score_cfg(n_cond=2)),
+    "stream_forecast_group: corrupt_idx descending": lambda L: _fgroup(L, cfg=cfg_idx([5, 4, 3])),
+    "stream_forecast_group: corrupt_idx twice": lambda L: _fgroup(L, cfg=cfg_idx([3, 4, 4])),
+    "stream_forecast_group: corrupt_idx 6": lambda L: _fgroup(L, cfg=cfg_idx([3, 4, 6])),
+    "stream_forecast_group: corrupt_idx -1": lambda L: _fgroup(L, cfg=cfg_idx([-1, 4, 5])),
+    "stream_forecast_group: cfg seg_len 5, corrupt_idx descending": lambda L: _fgroup(L, cfg=cfg_idx([4, 3, 2], seg_len=5, n_cond=2)),
+    "stream_forecast_group: method 3": lambda L: _fgroup(L, method=3),
+    "stream_forecast_group: spread unique": lambda L: _fgroup(L, spread=0),
+    "stream_forecast_group: method -1, spread 3": lambda L: _fgroup(L, method=-1, spread=3),
+    "stream_forecast_group: corrupt_idx descending, method 3": lambda L: _fgroup(L, cfg=cfg_idx([5, 4, 3]), method=3),
+    "stream_forecast_group: spread 3, vid_h nan": lambda L: _fgroup(L, spread=3, h=NAN),
+    "stream_forecast_group: vid_w inf": lambda L: _fgroup(L, w=INF),
+    "stream_forecast_group: vid_h nan": lambda L: _fgroup(L, h=NAN),
+    "stream_forecast_group: center without scale": lambda L: _fgroup(L, center=P),
+    "stream_forecast_group: scale without center": lambda L: _fgroup(L, scale=P),
+    "stream_forecast_group: vid_w inf, center without scale": lambda L: _fgroup(L, w=INF, center=P),
+    "stream_forecast_group: forecast ring over 2^31": lambda L: _fgroup(L, s=state(**BIG_FORECAST)),
+    "stream_forecast_group: center without scale, forecast ring over 2^31": lambda L: _fgroup(L, s=state(**BIG_FORECAST), center=P),
+    "stream_forecast_group: aggregation mean": lambda L: _fgroup(L, aggregation=3),
+    "stream_forecast_group: aggregation all": lambda L: _fgroup(L, aggregation=0),
+    "stream_forecast_group: aggregation mean, n -1": lambda L: _fgroup(L, aggregation=3, n=-1, n_windows=0),
+    "stream_forecast_group: n -1": lambda L: _fgroup(L, n=-1, n_windows=0),
+    "stream_forecast_group: n_windows -1": lambda L: _fgroup(L, n_windows=-1),
+    "stream_forecast_group: n_windows > n": lambda L: _fgroup(L, n=1, n_windows=2),
+    "stream_forecast_group: n = 29": lambda L: _fgroup(L, n=29),
+    "stream_forecast_group: n_windows > n, n = 29": lambda L: _fgroup(L, n=29, n_windows=30),
+    "stream_forecast_group: n_samples 0": lambda L: _fgroup(L, cfg=score_cfg(S=0)),
+    "stream_forecast_group: n = 29, n_samples 0": lambda L: _fgroup(L, n=29, cfg=score_cfg(S=0)),
+    "stream_forecast_group: null raw": lambda L: _fgroup(L, raw=None),
+    "stream_forecast_group: null desc": lambda L: _fgroup(L, desc=None),
+    "stream_forecast_group: null loss_all": lambda L: _fgroup(L, loss_all=None),
+    "stream_forecast_group: null poses_all": lambda L: _fgroup(L, poses_all=None),
+    "stream_forecast_group: null win": lambda L: _fgroup(L, win=None),
+    "stream_forecast_group: null expected_out": lambda L: _fgroup(L, expected=None),
+    "stream_forecast_group: null spread_out": lambda L: _fgroup(L, spread_out=None),
+    "stream_forecast_flush: null state": lambda L: _fflush(L, s=None),
+    "stream_forecast_flush: null forecast state": lambda L: _fflush(L, fs=None),
+    "stream_forecast_flush: null forecast state, method 3": lambda L: _fflush(L, fs=None, method=3),
+    "stream_forecast_flush: state n_corrupt 33": lambda L: _fflush(L, fs=fstate(n_corrupt=33)),
+    "stream_forecast_flush: null cfg": lambda L: _fflush(L, cfg=None),
+    "stream_forecast_flush: cfg seg_len 5": lambda L: _fflush(L, cfg=score_cfg(seg_len=5, n_cond=2)),
+    "stream_forecast_flush: cfg n_corrupt 2": lambda L: _fflush(L, cfg=score_cfg(n_cond=4, n_corrupt=2)),
+    "stream_forecast_flush: n_cond + n_corrupt != seg_len": lambda L: _fflush(L, cfg=score_cfg(n_cond=2)),
+    "stream_forecast_flush: corrupt_idx descending": lambda L: _fflush(L, cfg=cfg_idx([5, 4, 3])),
+    "stream_forecast_flush: cfg seg_len 5, corrupt_idx descending": lambda L: _fflush(L, cfg=cfg_idx([4, 3, 2], seg_len=5, n_cond=2)),
+    "stream_forecast_flush: method 3": lambda L: _fflush(L, method=3),
+    "stream_forecast_flush: spread unique": lambda L: _fflush(L, spread=0),
+    "stream_forecast_flush: vid_w inf": lambda L: _fflush(L, w=INF),
+    "stream_forecast_flush: center without scale": lambda L: _fflush(L, center=P),
+    "stream_forecast_flush: vid_w inf, center without scale": lambda L: _fflush(L, w=INF, center=P),
+    "stream_forecast_flush: forecast ring over 2^31": lambda L: _fflush(L, s=state(**BIG_FORECAST)),
+    "stream_forecast_flush: n -1": lambda L: _fflush(L, n=-1),
+    "stream_forecast_flush: n > n_slots": lambda L: _fflush(L, n=5),
+    "stream_forecast_flush: null win": lambda L: _fflush(L, win=None),
+    "stream_forecast_flush: null norm_out": lambda L: _fflush(L, norm=None),
+    "stream_forecast_flush: null count_out": lambda L: _fflush(L, count=None),
+    # ---- mcd_stream_clip_update / mcd_stream_clip_emit
+    "stream_clip_update: null state": lambda L: _cupdate(L, c=None),
+    "stream_clip_update: null sum": lambda L: _cupdate(L, c=clip(sum=None)),
+    "stream_clip_update: null lmax": lambda L: _cupdate(L, c=clip(lmax=None)),
+    "stream_clip_update: null lmin": lambda L: _cupdate(L, c=clip(lmin=None)),
+    "stream_clip_update: null n": lambda L: _cupdate(L, c=clip(n=None)),
+    "stream_clip_update: n_clips 0": lambda L: _cupdate(L, c=clip(n_clips=0)),
+    "stream_clip_update: num_transform 0": lambda L: _cupdate(L, c=clip(num_transform=0)),
+    "stream_clip_update: clip_ring_len 0": lambda L: _cupdate(L, c=clip(clip_ring_len=0)),
+    "stream_clip_update: 257 transforms": lambda L: _cupdate(L, c=clip(num_transform=257)),
+    "stream_clip_update: cells over 2^31": lambda L: _cupdate(L, c=clip(n_clips=1 << 16, clip_ring_len=1 << 15)),
+    "stream_clip_update: n_runs -1": lambda L: _cupdate(L, n_runs=-1),
+    "stream_clip_update: n_runs = 17": lambda L: _cupdate(L, n_runs=17),        # (clip(): 2 * 8 = 16 cells)
+    "stream_clip_update: n_runs = 17, null runs": lambda L: _cupdate(L, n_runs=17, runs=None),
+    "stream_clip_update: n_runs = 17, n_contrib -1": lambda L: _cupdate(L, n_runs=17, n_contrib=-1),
+    "stream_clip_update: n_contrib -1": lambda L: _cupdate(L, n_contrib=-1),
+    "stream_clip_update: n_finals -1": lambda L: _cupdate(L, n_finals=-1),
+    "stream_clip_update: n_tails -1": lambda L: _cupdate(L, n_tails=-1),
+    "stream_clip_update: null runs": lambda L: _cupdate(L, runs=None),
+    "stream_clip_update: null contrib": lambda L: _cupdate(L, contrib=None),
+    "stream_clip_update: null finals": lambda L: _cupdate(L, finals=None),
+    "stream_clip_update: null tails": lambda L: _cupdate(L, tails=None),
+    "stream_clip_emit: null state": lambda L: _cemit(L, c=None),
+    "stream_clip_emit: 257 transforms": lambda L: _cemit(L, c=clip(num_transform=257)),
+    "stream_clip_emit: n_out -1": lambda L: _cemit(L, n_out=-1),
+    "stream_clip_emit: n_out = 17": lambda L: _cemit(L, n_out=17),
+    "stream_clip_emit: radius -1": lambda L: _cemit(L, radius=-1),
+    "stream_clip_emit: radius 2^24 + 1": lambda L: _cemit(L, radius=(1 << 24) + 1),
+    "stream_clip_emit: shift -1": lambda L: _cemit(L, shift=-1),
+    "stream_clip_emit: n_out = 17, radius -1": lambda L: _cemit(L, n_out=17, radius=-1),
+    "stream_clip_emit: null outs": lambda L: _cemit(L, outs=None),
+    "stream_clip_emit: null gauss": lambda L: _cemit(L, gauss=None),
+    "stream_clip_emit: null out": lambda L: _cemit(L, out=None),
     # ---- mcd_frame_scores
     "frame_scores: null cfg": lambda L: _frames(L, None),
     "frame_scores: null workspace": lambda L: _frames(L, frame_cfg(), ws=None),
@@ -215,9 +452,10 @@ def record(key, results, path=JSON):
     if os.path.exists(path):
         with open(path) as f:
             d = json.load(f)
-    d["how"] = ("host: `python tests/test_call_errors_host.py --record` on a machine without a GPU; "
-                "gpu: `python tests/test_call_errors_gpu.py --record` on the MI355X; both with the library built from the commit "
-                "before the call front end (mcd_call.hpp), so the pairs are what callers saw until then")
+    # (an existing "how" stays: it also says where the later pairs came from)
+    d.setdefault("how", "host: `python tests/test_call_errors_host.py --record` on a machine without a GPU; "
+                        "gpu: `python tests/test_call_errors_gpu.py --record` on the MI355X; both with the library built from the commit "
+                        "before the call front end (mcd_call.hpp), so the pairs are what callers saw until then")
     d[key] = results
     with open(path, "w") as f:
         json.dump(d, f, indent=1, sort_keys=True)
