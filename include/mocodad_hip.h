@@ -777,6 +777,39 @@ int mcd_latent_decode_samples(const mcd_latent_weights_t* w, const mcd_score_cfg
                               const float* step_table, void* workspace, const float* cond_emb_in, const float* latents, float* pose_all,
                               float* loss_all, void* stream);
 
+/* ---- The latent model scored in pose space, one call (added without a change of MCD_ABI_VERSION, as the decode exports were: two
+ * new exports, no struct, enum or existing signature touched).
+ *
+ * Replaces: the caller's sequence mcd_latent_score(MCD_AGGR_ALL, latent_all) -> mcd_latent_decode_samples(cond_emb_in = the head of
+ * the first call's workspace) -> mcd_aggregate_view -> [mcd_error_maps] -- what MoCoDADlatent.forward does in pose space
+ * (latent_score_space 'pose'; of the reference: mocodad_latent.py:93-127 for the latents, stsae_unet.py:406-438 for the decoder,
+ * mocodad.py:454-520 for the aggregation).  On the caller's stream it makes exactly the launches of those entries, in that order, so
+ * every output is bit for bit theirs; what changes is that cond_emb, the latents and (where nobody asked for them) the per-sample
+ * losses and poses never leave the one workspace, whose layout the library owns.
+ *   w / ae       the diffusion-stage handle (mcd_pack_latent_weights) and its decoder, an autoencoder handle
+ *                (mcd_pack_latent_ae_weights); swapped or of one kind: MCD_EUNSUPPORTED naming the kind needed.  They must agree
+ *                on t_unet, t_cond, latent_dim and the device (MCD_EINVAL naming the field); cfg's seg_len and frame lists serve both
+ *   noise, seed, first_window_id, step_table     as for mcd_latent_score
+ *   workspace    mcd_latent_pose_workspace_bytes(w, ae, n_windows, n_samples), 16-byte aligned: [mcd_latent_score's workspace, cond_emb
+ *                at its head][loss_all (B,S)][latent_all (B,S,D)][pose_all (B,S,2,t_unet,17)][mcd_latent_decode_samples's workspace];
+ *                the size does not depend on which outputs are passed (0 for a NULL or wrong-kind handle or sizes out of range)
+ *   aggregation  BEST / WORST / MEAN / MEDIAN / QUANTILE (with `quantile`) -> loss_agg (B,), required
+ *   optional outputs (NULL = not wanted): loss_all (B,S) the pose-space losses; pose_all (B,S,2,t_unet,17); pose_agg (B,2,t_unet,17) the
+ *                selected forecast (BEST / WORST only, else MCD_EINVAL); maps (B,t_unet,17) as mcd_error_maps writes them under the
+ *                aggregation; latent_all (B,S,D) the generated latents, 16-byte aligned (the decode launches read it).  pose_all is
+ *                written into the workspace when it is NULL but pose_agg or maps is asked for; when none of the three is, the
+ *                decode launches write losses only
+ * Checks come before any launch and name what failed: the handles' kinds and agreement, NULL data / step_table / workspace /
+ * loss_agg, the sizes and alignment rules of mcd_latent_score and mcd_latent_decode_samples, the frame lists, a view with a
+ * cond_mask (the latent model has fixed frame lists).  n_windows <= 0 returns MCD_OK before anything is touched.  Windows and
+ * samples are independent as in the four entries. */
+int64_t mcd_latent_pose_workspace_bytes(const mcd_latent_weights_t* w, const mcd_latent_weights_t* ae, int32_t n_windows,
+                                        int32_t n_samples);
+int mcd_latent_score_pose(const mcd_latent_weights_t* w, const mcd_latent_weights_t* ae, const mcd_score_cfg_t* cfg, const float* data,
+                          const mcd_window_view_t* view, const float* noise, uint64_t seed, int64_t first_window_id,
+                          const float* step_table, void* workspace, int32_t aggregation, float quantile, float* loss_agg,
+                          float* loss_all, float* pose_all, float* pose_agg, float* maps, float* latent_all, void* stream);
+
 /* The draws of mcd_latent_score's perf mode in its `noise` layout (S, max(ns-1,1), B, D): feeding them back reproduces the perf
  * mode bit for bit.  Replaces nothing in the reference (torch.randn / randn_like, mocodad_latent.py:109,121).
  * KEY LAYOUT (key, c1 = slot k, c2 = sample s, c3 = window id, u, r and a as for mcd_philox_noise): for every slot c0 = d0 / 4,

@@ -151,6 +151,10 @@ _SIGS = {
     "mcd_latent_decode_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32]),
     "mcd_latent_decode_samples": (C.c_int, [C.c_void_p, C.POINTER(ScoreCfg), C.c_void_p, C.POINTER(WindowView), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_latent_pose_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "mcd_latent_score_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ScoreCfg), C.c_void_p, C.POINTER(WindowView), C.c_void_p,
+                                        C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_latent_philox_noise": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "mcd_last_error": (C.c_char_p, []),
     "mcd_abi_version": (C.c_int32, []),

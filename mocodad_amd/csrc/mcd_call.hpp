@@ -110,6 +110,22 @@ LatentDecodeWorkspace latent_decode_workspace(const mcd_weights* cw, int64_t B, 
     return L;
 }
 
+// latent, mcd_latent_score_pose: [the chain call's workspace: latent_workspace of the diffusion-stage handle, cond_emb (B,16) at its
+// head][per-sample losses (B,S)][generated latents (B,S,D)][decoded poses (B,S,2,Tx,17)][the decode call's workspace:
+// latent_decode_workspace of the autoencoder handle, of which only G is used -- cond_emb is the chain call's].  The three middle
+// regions are reserved whatever the caller asks for (the size does not depend on the outputs); one the caller passes a buffer for
+// stays unused.  score_bytes / decode_bytes: the `bytes` of the two layouts above
+struct LatentPoseWorkspace { int64_t loss, latent, pose, decode, bytes; };      // (the chain call's workspace is at offset 0)
+LatentPoseWorkspace latent_pose_workspace(int64_t score_bytes, int64_t decode_bytes, int64_t B, int64_t S, int D, int Tx) {
+    LatentPoseWorkspace L;
+    L.loss = round256(score_bytes);
+    L.latent = L.loss + round256(B * S * 4);
+    L.pose = L.latent + round256(B * S * D * 4);
+    L.decode = L.pose + round256(B * S * C0 * Tx * 17 * 4);
+    L.bytes = L.decode + round256(decode_bytes);
+    return L;
+}
+
 // One condition encoder launch (with its gather, for the plain routes) -> emb (B,16).  r: a route with a launch of its own (not
 // COND_NONE / COND_INKERNEL).  gather: where the plain encoder's dense (B,C,Tc,V) copy of the condition frames goes; NULL = dv.data
 // IS that copy (mcd_cond_encode).  scratch: cond_scratch_bytes(w, r, B) of device memory, NULL if that is 0.

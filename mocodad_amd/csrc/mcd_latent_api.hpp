@@ -114,6 +114,13 @@ int64_t decode_g_bytes(const mcd_latent_weights* w, int64_t B, int64_t S) {
     return std::min(rows_of * decode_window_bytes(w, S), LAT_DECODE_G_BYTES);
 }
 
+// ---- mcd_latent_score_pose: the workspace of a diffusion-stage handle w and its decoder ae (latent_pose_workspace): the size query
+// and the call read this one function
+LatentPoseWorkspace latent_pose_layout(const mcd_latent_weights* w, const mcd_latent_weights* ae, int64_t B, int64_t S) {
+    return latent_pose_workspace(latent_workspace(&w->cw, B, w->net.D, w->h_floats).bytes,
+                                 latent_decode_workspace(&ae->cw, B, decode_g_bytes(ae, B, S)).bytes, B, S, w->net.D, w->cfg.t_unet);
+}
+
 }  // namespace
 
 extern "C" {
@@ -300,6 +307,62 @@ int mcd_latent_decode_samples(const mcd_latent_weights_t* w, const mcd_score_cfg
         if (int rc = launch_latent_decode_samples(T, {w->dbuf, c, cond, G, pose_all, loss_all, cfg->loss_fn, b0, nb, B, S,
                                                       w->opt[MCD_LATENT_OPT_DECODE_SPW], st})) return rc;
     }
+    return MCD_OK;
+}
+
+int64_t mcd_latent_pose_workspace_bytes(const mcd_latent_weights_t* w, const mcd_latent_weights_t* ae, int32_t n_windows, int32_t n_samples) {
+    if (n_windows <= 0 || n_samples < 1 || n_samples > LAT_MAX_S || !w || !ae || w->ae || !ae->ae) return 0;
+    return latent_pose_layout(w, ae, n_windows, n_samples).bytes;
+}
+
+int mcd_latent_score_pose(const mcd_latent_weights_t* w, const mcd_latent_weights_t* ae, const mcd_score_cfg_t* cfg, const float* data,
+                          const mcd_window_view_t* view, const float* noise, uint64_t seed, int64_t first_window_id,
+                          const float* step_table, void* workspace, int32_t aggregation, float quantile, float* loss_agg,
+                          float* loss_all, float* pose_all, float* pose_agg, float* maps, float* latent_all, void* stream) {
+    // every check of the four calls below comes here, before the first launch
+    if (!cfg) return fail(MCD_EINVAL, "null argument");
+    if (cfg->n_windows <= 0) return MCD_OK;      // (before anything else is read, the handles included)
+    if (!w || !ae) return fail(MCD_EINVAL, "null argument (two handles: the diffusion stage and its autoencoder)");
+    if (w->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_score_pose needs a diffusion-stage handle (mcd_pack_latent_weights) as its first handle: an autoencoder handle has no denoiser");
+    if (!ae->ae) return fail(MCD_EUNSUPPORTED, "mcd_latent_score_pose needs an autoencoder handle (mcd_pack_latent_ae_weights) as its second handle: a diffusion-stage handle has no decoder");
+    const int B = cfg->n_windows, S = cfg->n_samples, D = w->net.D;
+    if (!data || !step_table || !workspace) return fail(MCD_EINVAL, "null argument (the workspace of mcd_latent_pose_workspace_bytes is required)");
+    if (!loss_agg) return fail(MCD_EINVAL, "null argument (loss_agg is required)");
+    if (int rc = check_aggregation(aggregation, quantile, AGGR_LOSSES, "mcd_latent_score_pose aggregates losses (best, worst, mean, median, quantile)")) return rc;
+    if (pose_agg && aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST)
+        return fail(MCD_EINVAL, "pose_agg: only best and worst select a pose");
+    if (S < 1 || cfg->noise_steps < 2) return fail(MCD_EINVAL, "need n_samples >= 1 and noise_steps >= 2");
+    if (S > LAT_MAX_S) return fail(MCD_EUNSUPPORTED, "n_samples " + std::to_string(S) + ": at most " + std::to_string(LAT_MAX_S) + " per call");
+    if ((long long)B * S > 0x7fffffffll) return fail(MCD_EINVAL, "n_windows x n_samples exceeds 2^31 - 1: score in smaller batches");
+    if (cfg->loss_fn < MCD_LOSS_SMOOTH_L1 || cfg->loss_fn > MCD_LOSS_MSE) return fail(MCD_EINVAL, "unknown loss_fn");
+    // the two handles are the two stages of one model
+    if (ae->cfg.t_unet != w->cfg.t_unet || ae->cfg.t_cond != w->cfg.t_cond)
+        return fail(MCD_EINVAL, "the two handles differ in their frame split (t_unet / t_cond)");
+    if (ae->net.D != D) return fail(MCD_EINVAL, "the two handles differ in latent_dim");
+    if (ae->device != w->device) return fail(MCD_EINVAL, "the two handles are on different devices");
+    if (noise && !aligned16(noise)) return fail(MCD_EINVAL, "noise must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(MCD_EINVAL, "workspace must be 16-byte aligned");
+    if (latent_all && !aligned16(latent_all)) return fail(MCD_EINVAL, "latent_all must be 16-byte aligned (the decode launches read it)");
+    if (view && view->cond_mask) return fail(MCD_EINVAL, "cond_mask: the latent model has fixed frame lists");
+    {   // the frame lists and the view, against both handles (seg_len and the lists are the call's: one cfg serves both)
+        LatentCall c;
+        if (int rc = latent_call(w, cfg, data, view, step_table, c)) return rc;
+        if (int rc = latent_call(ae, cfg, data, view, step_table, c)) return rc;
+    }
+    const LatentPoseWorkspace lay = latent_pose_layout(w, ae, B, S);
+    auto at = [&](int64_t off) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + off); };
+    float* const la = loss_all ? loss_all : at(lay.loss);
+    float* const lat = latent_all ? latent_all : at(lay.latent);
+    float* const pa = pose_all ? pose_all : (pose_agg || maps) ? at(lay.pose) : nullptr;
+    // 1. the chain call: latents into `lat`, cond_emb at the head of the workspace (`la` takes the latent-space losses until step 2)
+    if (int rc = mcd_latent_score(w, cfg, data, view, noise, seed, first_window_id, step_table, workspace, MCD_AGGR_ALL, 0.f, nullptr, la,
+                                  lat, nullptr, stream)) return rc;
+    // 2. the decoder on every sample, with that cond_emb: the pose-space losses, and the poses where something reads them
+    if (int rc = mcd_latent_decode_samples(ae, cfg, data, view, step_table, at(lay.decode), at(0), lat, pa, la, stream)) return rc;
+    // 3. the pose model's aggregation (losses only: no ground truth is read)
+    if (int rc = mcd_aggregate_view(cfg, C0, 17, aggregation, quantile, la, pa, nullptr, nullptr, loss_agg, pose_agg, stream)) return rc;
+    // 4. the error maps under that aggregation
+    if (maps) return mcd_error_maps(cfg, C0, 17, aggregation, quantile, la, pa, data, view, maps, stream);
     return MCD_OK;
 }
 

@@ -713,6 +713,88 @@ class LatentReconstructor(_LatentHandle):
         return poses, loss
 
 
+class LatentPoseScorer:
+    """MoCoDADlatent scored in pose space in ONE library call (mcd_latent_score_pose) over two handles: a LatentScorer (the diffusion
+    stage) and the LatentReconstructor that decodes its latents (MoCoDADlatent.load_decoder).  The call makes the launches of
+    LatentScorer.score('all', want_latents) -> LatentReconstructor.decode_samples -> aggregate -> [error_maps] in that order, so
+    every result is bit for bit theirs; cond_emb, the latents and whatever per-sample result nobody asked for stay in this object's
+    per-stream workspace.  The results have HipScorer.score_fused's layout, and `corrupt_idx` / `_score_cfg` are the decoder
+    handle's: a live stream drives this object exactly as it drives a HipScorer.  It owns no handle (the two scorers do)."""
+
+    def __init__(self, scorer: "LatentScorer", decoder: "LatentReconstructor"):
+        if not isinstance(scorer, LatentScorer) or not isinstance(decoder, LatentReconstructor):
+            raise TypeError("LatentPoseScorer takes a LatentScorer (diffusion stage) and a LatentReconstructor (its decoder), in this order")
+        for name in ("seg_len", "cond_idx", "corrupt_idx", "latent_dim", "device"):
+            if getattr(scorer, name) != getattr(decoder, name):
+                raise ValueError(f"LatentPoseScorer: the two handles differ in {name}: {getattr(scorer, name)} / {getattr(decoder, name)}")
+        self.scorer, self.decoder = scorer, decoder
+        self.L, self.device = scorer.L, scorer.device
+        self.seg_len, self.latent_dim = scorer.seg_len, scorer.latent_dim
+        self.num_coords, self.n_joints, self.emb_dim = decoder.num_coords, decoder.n_joints, decoder.emb_dim
+        self._ws: Dict[int, torch.Tensor] = {}      # one workspace per stream, as _Scorer keeps them
+
+    _workspace = _Scorer._workspace
+
+    @property
+    def corrupt_idx(self):
+        return self.decoder.corrupt_idx
+
+    @property
+    def cond_idx(self):
+        return self.decoder.cond_idx
+
+    def _score_cfg(self, B: int, S: int, ns: int, loss_fn: str = "smooth_l1") -> "_lib.ScoreCfg":
+        return self.decoder._score_cfg(B, S, ns, loss_fn)
+
+    def philox_noise(self, n_windows: int, **kw) -> torch.Tensor:
+        """The draws the perf mode of `score` makes in-kernel: LatentScorer.philox_noise."""
+        return self.scorer.philox_noise(n_windows, **kw)
+
+    def score(self, data, *, n_samples: int, noise_steps: int, aggregation: str = "best", noise: Optional[torch.Tensor] = None,
+              seed: int = 0, first_window_id: int = 0, loss_fn: str = "smooth_l1", want_all: bool = False, want_poses: bool = False,
+              want_maps: bool = False, out: Optional[torch.Tensor] = None, want_selected: bool = False, want_latents: bool = False):
+        """data ((B,C,T,V) tensor or WindowBatch) -> (loss_agg (B,), loss_all (B,S) | None, poses_all (B,S,2,Tx,17) | None,
+        maps (B,Tx,17) | None), as HipScorer.score_fused with want_maps returns them -- the losses taken on the decoded forecasts
+        against the window's corrupt frames.  aggregation: best | worst | mean | median | quantile:q.  noise: (S, max(ns-1,1), B, D)
+        replacing the in-kernel Philox draws of the chain.  out: optional preallocated (B,) result.  want_selected: a fifth result,
+        the selected forecast (B,2,Tx,17) under best / worst (None under the others); want_latents: one more, the generated
+        latents (B,S,D).  Asynchronous on the current stream."""
+        data, view, B, keep = self.scorer._windows(data)
+        S, ns, D, dev = int(n_samples), int(noise_steps), self.latent_dim, self.device
+        if S < 1 or ns < 2:
+            raise ValueError("need n_samples >= 1 and noise_steps >= 2")
+        name, q = _aggregation_of(aggregation, LOSS_AGGREGATIONS,
+                                  f"the pose-space scoring call aggregates losses (best, worst, mean, median, quantile:q), not {aggregation!r}")
+        if noise is not None:
+            noise = _f32c(noise, dev)
+            exp = (S, max(ns - 1, 1), B, D)
+            if tuple(noise.shape) != exp:
+                raise ValueError(f"noise must have shape {exp}, got {tuple(noise.shape)}")
+        Tx, C_, V = len(self.corrupt_idx), self.num_coords, self.n_joints
+        agg = _out_vector(out, B, dev)
+        loss = torch.empty(B, S, device=dev, dtype=torch.float32) if want_all else None
+        poses = torch.empty(B, S, C_, Tx, V, device=dev, dtype=torch.float32) if want_poses else None
+        maps = torch.empty(B, Tx, V, device=dev, dtype=torch.float32) if want_maps else None
+        sel = torch.empty(B, C_, Tx, V, device=dev, dtype=torch.float32) if want_selected and name in ("best", "worst") else None
+        lat = torch.empty(B, S, D, device=dev, dtype=torch.float32) if want_latents else None
+        cfg = self._score_cfg(B, S, ns, loss_fn)
+        with torch.cuda.device(dev):
+            ws = self._workspace(int(self.L.mcd_latent_pose_workspace_bytes(self.scorer._h, self.decoder._h, B, S)))
+            if B:
+                _lib.check(self.L.mcd_latent_score_pose(self.scorer._h, self.decoder._h, C.byref(cfg), _ptr(data),
+                                                        C.byref(view) if view is not None else None, _ptr(noise), _seed64(seed),
+                                                        C.c_int64(first_window_id), _ptr(self.scorer.table(ns)), _ptr(ws), _lib.AGGR[name],
+                                                        C.c_float(q), _ptr(agg), _ptr(loss), _ptr(poses), _ptr(sel), _ptr(maps), _ptr(lat),
+                                                        _stream()))
+        del keep
+        res = (agg, loss, poses, maps)
+        if want_selected:
+            res += (sel,)
+        if want_latents:
+            res += (lat,)
+        return res
+
+
 def _scaler_stats(center, scale, dev) -> tuple:
     """(center, scale) as (34,) float64 device tensors (the precision sklearn's transform runs in), or (None, None)."""
     if (center is None) != (scale is None):

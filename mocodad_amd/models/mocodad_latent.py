@@ -114,6 +114,7 @@ class MoCoDADlatent(LatentStage):
         self._decoder_sd = None       # load_decoder: the autoencoder's state_dict (a plain dict: no parameter of this module)
         self._decoder = None          # ... its engine.LatentReconstructor, built lazily per device
         self._decoder_key = None
+        self._pose_scorer = None      # engine.LatentPoseScorer over the two, rebuilt when either is
 
     @staticmethod
     def _check_space(space: str) -> str:
@@ -134,7 +135,7 @@ class MoCoDADlatent(LatentStage):
 
     # -------------------------------------------------------------- the stage-1 decoder
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        self._decoder_sd = self._decoder = None      # (its copies of the shared tensors are stale: call load_decoder again)
+        self._decoder_sd = self._decoder = self._pose_scorer = None      # (its copies of the shared tensors are stale: call load_decoder again)
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def load_decoder(self, source=None, *, check: bool = True) -> None:
@@ -171,7 +172,7 @@ class MoCoDADlatent(LatentStage):
         # the decoder half of stage 1 (what `model` holds there and not here: the up path, rev_to_time_dim) + this module's own tensors
         sd = {k: v.detach().clone().cpu() for k, v in source.items() if torch.is_tensor(v) and k.startswith("model.") and k not in own}
         sd.update({k: own[k].detach().clone().cpu() for k in shared})
-        self._decoder_sd, self._decoder, self._decoder_key = sd, None, None
+        self._decoder_sd, self._decoder, self._decoder_key, self._pose_scorer = sd, None, None, None
 
     def decoder(self):
         """engine.LatentReconstructor of the loaded decoder on the module's current device (packed lazily, like scorer())."""
@@ -186,6 +187,15 @@ class MoCoDADlatent(LatentStage):
             self._decoder = LatentReconstructor(self._decoder_sd, **self._scorer_kwargs(dev))
             self._decoder_key = str(dev)
         return self._decoder
+
+    def pose_scorer(self):
+        """engine.LatentPoseScorer over scorer() and decoder(): pose-space scoring as one library call (built lazily, like both)."""
+        sc, dec = self.scorer(), self.decoder()
+        ps = self._pose_scorer
+        if ps is None or ps.scorer is not sc or ps.decoder is not dec:
+            from ..engine import LatentPoseScorer
+            ps = self._pose_scorer = LatentPoseScorer(sc, dec)
+        return ps
 
     # -------------------------------------------------------------- forward
     def _loss(self, x: torch.Tensor, z0: torch.Tensor) -> torch.Tensor:
@@ -227,11 +237,17 @@ class MoCoDADlatent(LatentStage):
 
     def _forward_pose(self, input_data, aggr_strategy, return_, noise, window_offset, return_maps) -> List[torch.Tensor]:
         """forward in pose space: the chain call for the latents and cond_emb, the decoder on all samples, then the pose model's
-        aggregation (and error maps) on (loss_all, pose_all)."""
+        aggregation (and error maps) on (loss_all, pose_all) -- for the loss-based aggregations as ONE library call (pose_scorer()),
+        for mean_pose / median_pose / all / random as the sequence of engine calls."""
         if return_maps and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
             raise ValueError("return_maps: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
         tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         dec = self.decoder()
+        if aggr in ("best", "worst", "mean", "median") or "quantile" in aggr:
+            # the loss-based aggregations: ONE library call (mcd_latent_score_pose), the bits of the sequence below
+            r = self.pose_scorer().score(tensor_data, aggregation=aggr, want_maps=return_maps, want_selected=ret in ("pose", "all"), **kw)
+            out = self._pack_out_data(r[4] if len(r) > 4 else None, r[0], [tensor_data] + meta_out, return_=ret)
+            return out + [r[3], self.map_frames(None, r[3].shape[0])] if return_maps else out
         want_pose = ret in ("pose", "all") or aggr in ("all", "random", "mean_pose", "median_pose")
         if hasattr(tensor_data, "as_view") and aggr in ("mean_pose", "median_pose"):
             tensor_data = tensor_data.materialize()      # the *_pose strategies compare against the windows themselves

@@ -861,13 +861,19 @@ class PoseStream:
     rings and reduces the rows that became final, and `Tick.forecast`, `Tick.closed.forecast` and the `forecast` of what `close`
     returns carry them row for row with the frame scores -- bit for bit eval_MoCoDAD.py's --forecast-tracks.  Off (the default):
     no extra launch, no poses requested, nothing allocated.
+    space (MoCoDADlatent only): None = the module's `latent_score_space`, or 'latent' / 'pose'.  In pose space (needs
+    load_decoder; RuntimeError with forward's message otherwise) the tick's scoring call is engine.LatentPoseScorer.score
+    (mcd_latent_score_pose): `Tick.scores` are the losses of the decoded forecasts against the corrupt frames, the numbers
+    eval_MoCoDAD.py gives for the same module, and joint_scores / forecasts work as for the pose model (the decoder handle's frame
+    lists).  In latent space both stay refused, and no decoder is packed.
 
     One PoseStream is driven from ONE stream (the current stream of the first push): its rings, staging buffers and the track
     table are per-tick state, and the launches of a tick are ordered only by that stream."""
 
     def __init__(self, model, *, vid_res, center=None, scale=None, max_tracks: int = 1024, ring_len: Optional[int] = None,
                  num_transform: Optional[int] = None, max_idle: Optional[int] = None, max_group_rows: Optional[int] = None,
-                 clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False, forecasts: Optional[ForecastCfg] = None):
+                 clip_scores: Optional[ClipScoreCfg] = None, joint_scores: bool = False, forecasts: Optional[ForecastCfg] = None,
+                 space: Optional[str] = None):
         from .engine import ClipRings, StreamRings, forecast_codes
         from .utils.transforms import affine_table
         if getattr(model, "is_pretrain", False):
@@ -875,15 +881,23 @@ class PoseStream:
                                       "reconstructs poses and yields no anomaly score per window (score live streams with "
                                       "MoCoDAD or the diffusion-stage MoCoDADlatent)")
         self.latent = bool(getattr(model, "is_latent", False))
+        if space is not None and space not in ("latent", "pose"):
+            raise ValueError(f"space must be None, 'latent' or 'pose', got {space!r}")
+        if space is not None and not self.latent:
+            raise ValueError("space= is for the latent model (MoCoDADlatent): the pose model has one score space")
+        # the space a latent module is scored in: the module's own (what forward and eval_MoCoDAD.py use) unless `space` says otherwise
+        self.space = (getattr(model, "latent_score_space", "latent") if space is None else space) if self.latent else None
+        self.pose_space = self.space == "pose"
         self.joint_scores = bool(joint_scores)
-        if self.joint_scores and self.latent:
+        if self.joint_scores and self.latent and not self.pose_space:
             raise NotImplementedError("PoseStream(joint_scores=True) needs the pose model: MoCoDADlatent takes its loss on a latent "
-                                      "code, and a latent has no joints")
+                                      "code, and a latent has no joints (latent_score_space 'pose' / space='pose' with a loaded "
+                                      "decoder scores decoded forecasts, which have)")
         self.forecasts = forecasts
         if forecasts is not None:
-            if self.latent:
-                raise NotImplementedError("PoseStream(forecasts=...) needs the pose model: MoCoDADlatent forecasts a latent code (pose-"
-                                          "space forecasts of the latent model on a stream belong with its joint_scores, not built)")
+            if self.latent and not self.pose_space:
+                raise NotImplementedError("PoseStream(forecasts=...) needs the pose model: MoCoDADlatent forecasts a latent code "
+                                          "(latent_score_space 'pose' / space='pose' with a loaded decoder decodes it to poses)")
             forecast_codes(forecasts.method, forecasts.spread, ("forecasts: method", "forecasts: spread"), f"one of {FORECAST_SPREADS}")
             if model.aggregation_strategy not in ("best", "worst"):
                 raise ValueError(f"PoseStream(forecasts=...) needs an aggregation that selects a pose, best or worst: aggregation_strategy "
@@ -898,8 +912,12 @@ class PoseStream:
         if not (aggr in ("best", "worst", "mean", "median") or "quantile" in aggr) or model.model_return_value != "loss":
             raise ValueError(f"PoseStream needs one loss per window: model_return_value 'loss' and a loss-based aggregation "
                              f"(best, worst, mean, median, quantile:q), not {aggr!r} / {model.model_return_value!r}")
+        if self.pose_space and getattr(model, "_decoder_sd", None) is None:       # (forward's message; before any device call)
+            raise RuntimeError("latent_score_space 'pose' needs the stage-1 decoder: call load_decoder first")
         self.model = model
-        self.scorer = model.scorer()
+        # pose space: engine.LatentPoseScorer, whose results have HipScorer.score_fused's layout and whose frame lists are the
+        # decoder handle's -- from here on the stream treats it as it treats the pose model's scorer
+        self.scorer = model.pose_scorer() if self.pose_space else model.scorer()
         self.device = dev = self.scorer.device
         self.seg_len = int(model.n_frames)
         self.num_transform = nt = max(1, int(model.num_transforms if num_transform is None else num_transform))
@@ -1073,7 +1091,8 @@ class PoseStream:
             if nw:
                 m = self.model
                 wb = WindowBatch(self.ring, base, trans, self.affine, self.seg_len)
-                # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches; else HipScorer.score_fused)
+                # (a MoCoDADlatent module: engine.LatentScorer.score, the encode + chain launches -- in pose space
+                # engine.LatentPoseScorer.score, + the decode, aggregate and maps launches; else HipScorer.score_fused)
                 score = self.scorer.score if self.latent else self.scorer.score_fused
                 res = score(wb, n_samples=m.n_generated_samples, noise_steps=m.noise_steps, aggregation=m.aggregation_strategy,
                             noise=noise, seed=m.seed, first_window_id=first, loss_fn=m.loss_name, out=scores,

@@ -7,6 +7,8 @@
     python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 256 --rows 120
     python tools/stream_replay.py -c configs/ubnormal_latent_test.yaml --random-init --synthetic-tracks 64    # the latent model
     python tools/stream_replay.py -c configs/hr_avenue_test.yaml --random-init --synthetic-tracks 64 --ticks-per-call 8
+    python tools/stream_replay.py -c configs/ubnormal_latent_test.yaml --random-init --synthetic-tracks 64 \\
+           --latent-score-space pose --joint-scores --forecasts                               # the latent model in pose space
 
 On-disk split: the trajectory CSVs are replayed in frame order, one tick = one frame id across all clips; a track is closed
 after its last row.  The window scores, put back into dataset order, go through the model's own post_processing: the AUC is
@@ -30,10 +32,14 @@ masks without an emitted score are excluded and counted).  The two differ by def
 with a score at that frame, not the clip's whole roster, and neither pad_size nor the HR masks are applied -- so neither is
 asserted against the other.
 --joint-scores: per-joint frame scores in every tick (PoseStream(joint_scores=True)): "tick" then includes the error
-maps launch behind the scoring call and mcd_stream_joint_scores_group; pose model only.
+maps launch behind the scoring call and mcd_stream_joint_scores_group; the pose model, or a latent config in pose space.
 --forecasts [--forecast-method M] [--forecast-spread S]: the expected pose of every row in every tick (PoseStream(forecasts=
 ForecastCfg(M, S))): "tick" then includes the scoring call writing its per-sample losses and poses and the two launches
-of mcd_stream_forecast_group (closes: mcd_stream_forecast_flush); pose model with a best / worst aggregation only.
+of mcd_stream_forecast_group (closes: mcd_stream_forecast_flush); a best / worst aggregation only; the pose model, or a latent config
+in pose space.
+--latent-score-space pose (a latent config): the stage-1 decoder is loaded as eval_MoCoDAD.py loads it (--random-init: a seeded one
+sharing the module's frozen tensors), the tick's scoring call is LatentPoseScorer.score (mcd_latent_score_pose: + the unproject,
+decode, aggregate and maps launches), and the baseline is that call alone, asked for the same outputs.
 --forecasts-out OUT.npz: the rows of the warm-up replay in the layout of eval_MoCoDAD.py --forecast-tracks (rows, frames, observed,
 expected, expected_norm, count, spread, joint_names), sorted by (scene, clip, person, frame); not timed.
 Prints one JSON line and writes it to --out (default profiles/stream_replay.json): median and p99 over all timed ticks that
@@ -98,10 +104,15 @@ def main():
     ap.add_argument("--forecast-method", choices=("unique", "mean", "median"), default="median")
     ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean")
     ap.add_argument("--forecasts-out", default=None, metavar="OUT.npz", help="--forecasts: write the rows of the warm-up replay")
+    ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
+                    help="latent model (overrides the YAML's latent_score_space): 'pose' loads the stage-1 decoder as eval_MoCoDAD.py "
+                         "does and scores the decoded forecasts (then --joint-scores and --forecasts work)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_replay.json"))
     cli = ap.parse_args()
     args = load_config(cli.config)
+    if cli.latent_score_space is not None:
+        args.latent_score_space = cli.latent_score_space
     if cli.data_dir:
         args.data_dir = cli.data_dir
         args.test_path = args.gt_path = os.path.join(cli.data_dir, "testing", "test_frame_mask")
@@ -121,6 +132,14 @@ def main():
         model.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=False)["state_dict"])
     elif not cli.random_init:
         raise SystemExit(f"checkpoint {ckpt} not found (pass --random-init to score with seeded random-init weights)")
+    pose_space = latent and model.latent_score_space == "pose"
+    if cli.latent_score_space is not None and not latent:
+        raise SystemExit("--latent-score-space is for a latent config (diffusion_on_latent: true)")
+    if pose_space:                                  # the stage-1 decoder, as eval_MoCoDAD.py loads it (--random-init included)
+        from eval_MoCoDAD import load_latent_decoder
+        load_latent_decoder(model, args, cli.random_init)
+    elif latent and (cli.joint_scores or cli.forecasts):
+        raise SystemExit("--joint-scores / --forecasts with a latent config need --latent-score-space pose (a latent has no joints)")
     center, scale = (None, None) if cli.no_scaler or cli.synthetic_tracks else T.load_scaler_stats(args.ckpt_dir)
 
     if cli.synthetic_tracks:
@@ -159,7 +178,7 @@ def main():
     n = tw.n_samples
     sample_of = {tuple(int(v) for v in r): i for i, r in enumerate(tw.meta[:n].numpy())}
     base_d, trans_d = tw.base.to(dev), tw.trans.to(dev)
-    sc = model.scorer()
+    sc = model.pose_scorer() if pose_space else model.scorer()
     kw = dict(n_samples=model.n_generated_samples, noise_steps=model.noise_steps, aggregation=model.aggregation_strategy,
               seed=model.seed, loss_fn=model.loss_name)
 
@@ -170,6 +189,10 @@ def main():
     extra = {"joint_scores": True} if cli.joint_scores else {}
     if cli.forecasts:
         extra["forecasts"] = ForecastCfg(cli.forecast_method, cli.forecast_spread)
+    # the baseline asks its scoring call for what the tick's asks (PoseStream._run_group): maps, per-sample losses and poses
+    base_extra = {}
+    if pose_space:
+        base_extra = dict(**({"want_maps": True} if cli.joint_scores else {}), **({"want_all": True, "want_poses": True} if cli.forecasts else {}))
     FIELDS = ("observed", "expected", "expected_norm", "count", "spread")
 
     def replay(collect=None, online=None, forecast_rows=None):
@@ -222,7 +245,7 @@ def main():
                 raise SystemExit("baseline: the tick holds more windows than the dataset path built")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            (sc.score if latent else sc.score_fused)(wb, first_window_id=lo, out=out[:c], **kw)
+            (sc.score if latent else sc.score_fused)(wb, first_window_id=lo, out=out[:c], **kw, **base_extra)
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
         return np.asarray(times)
@@ -276,7 +299,7 @@ def main():
            "windows_per_tick_median": int(np.median(counts)), "windows_per_tick_max": int(max(counts)),
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
-           "model": "MoCoDADlatent" if latent else "MoCoDAD", "clip_scores": clip_res, "joint_scores": bool(cli.joint_scores),
+           "model": "MoCoDADlatent" if latent else "MoCoDAD", "score_space": model.latent_score_space if latent else None, "clip_scores": clip_res, "joint_scores": bool(cli.joint_scores),
            "forecasts": {"method": cli.forecast_method, "spread": cli.forecast_spread} if cli.forecasts else None,
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
