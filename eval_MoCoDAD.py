@@ -88,6 +88,10 @@ def main():
                     help="--forecast-tracks: the pose of a row from its covering windows (extract_single_pose's `method`)")
     ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean",
                     help="--forecast-tracks: how the 34 per-feature standard deviations become one spread (its `std_method`)")
+    ap.add_argument("--forecast-transforms", choices=("identity", "all"), default="identity",
+                    help="--forecast-tracks: which windows forecast a row -- those of transform 0 only, or those of every test-time "
+                         "transform, each forecast mapped back through the inverse of its transform (more forecasts per row: larger "
+                         "counts, nothing else changes in the output)")
     ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
                     help="latent model, stage 'diffusion' (overrides the YAML's latent_score_space): 'pose' decodes the generated "
                          "latents with the stage-1 decoder of pretrained_model_ckpt_path and scores the forecasts as the pose model does")
@@ -121,6 +125,19 @@ def main():
             raise SystemExit(f"eval_MoCoDAD.py: --forecast-tracks needs one forecast per window: not aggregation_strategy {aggr!r}")
         if cli.joint_scores:
             raise SystemExit("eval_MoCoDAD.py: --forecast-tracks and --joint-scores are separate runs")
+        forecast_cover = 32
+        if cli.forecast_transforms == "all":      # the forecasts a row can collect: per transform one per forecast frame of a window
+            from types import SimpleNamespace
+            from mocodad_amd.utils.eval_utils import forecast_max_cover
+            split = SimpleNamespace(n_frames=args.seg_len, conditioning_indices=args.conditioning_indices,
+                                    conditioning_strategy=MoCoDAD.conditioning_strategies.get(args.conditioning_strategy, args.conditioning_strategy))
+            per_window = args.seg_len if split.conditioning_strategy == "random_imp" else len(MoCoDAD._frame_split(split)[1])
+            try:
+                forecast_cover = forecast_max_cover(args.num_transform, per_window, "all")
+            except ValueError as e:
+                raise SystemExit(f"eval_MoCoDAD.py: --forecast-transforms all: {e}") from None
+    elif cli.forecast_transforms != "identity":
+        raise SystemExit("eval_MoCoDAD.py: --forecast-transforms goes with --forecast-tracks")
     pretrain = bool(getattr(model_cls, "is_pretrain", False))
     if pretrain and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("eval_MoCoDAD.py: stage 'pretrain' runs in one process (its result is one mean over all windows, not gathered scores)")
@@ -256,7 +273,8 @@ def main():
             src = dict(windows=tw) if tw is not None else dict(meta=meta.numpy(), frames=frames.numpy())
             pose, count, spread, rows, frame_ids = forecast_track_rows(
                 torch.cat(forecasts), trans.numpy(), torch.cat(forecast_frames).cpu().numpy(), forecast_assemble,
-                method=cli.forecast_method, spread_method=cli.forecast_spread, **src)
+                method=cli.forecast_method, spread_method=cli.forecast_spread, max_cover=forecast_cover,
+                transforms=cli.forecast_transforms, num_transform=args.num_transform, **src)
             res = dict(rows=rows, row_columns=np.asarray(["scene", "clip", "person"]), frames=frame_ids,
                        expected_norm=pose.cpu().numpy(), count=count.cpu().numpy(), spread=spread.cpu().numpy(),
                        joint_names=np.asarray(JOINT_NAMES), method=np.asarray(cli.forecast_method), spread_method=np.asarray(cli.forecast_spread))

@@ -378,6 +378,26 @@ int mcd_forecast_assemble(const float* poses, const int32_t* cell, int64_t n, in
                           int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
                           float* spread_out, void* stream);
 
+/* Forecasts from EVERY test-time transform (added without a change of MCD_ABI_VERSION: one new export, nothing existing touched):
+ * mcd_forecast_assemble with the forecast of window i first mapped back through the inverse of its transform trans[i], so that the
+ * windows of all transforms forecast a cell in the coordinates of transform 0.
+ *   trans        (N,) i32 device: the transform of every window; a value outside [0, n_transform) makes the window's pairs ignored,
+ *                as a cell outside [0, n_cells) is.  NULL: the call IS mcd_forecast_assemble (inv_affine and n_transform are not read,
+ *                max_cover 1 .. 32)
+ *   inv_affine   (n_transform, 6) f64 device rows [i00 i01 i02 i10 i11 i12]: the inverse of the 2 x 3 affine map of each transform
+ *   max_cover    1 .. 64 (MCD_FORECAST_VIEW_COVER): 5 transforms x 12 forecast frames put 60 pairs on a cell
+ * Per joint (x', y') of a forecast:  x = fp32((i00 x' + i01 y') + i02),  y = fp32((i10 x' + i11 y') + i12) -- products and sums in
+ * float64, unfused, in that order, rounded to fp32 once.  A table row that equals (1,0,0,0,1,0) copies the value unchanged (a -0.0
+ * keeps its sign, a NaN y' does not reach x).  The mapped fp32 values enter the reduction of mcd_forecast_assemble as they are, in
+ * ascending pair index: with the dataset's transform-major window order that is transform, then window, then forecast frame.
+ * Argument errors are those of mcd_forecast_assemble, plus trans without inv_affine and n_transform < 1 (MCD_EINVAL before any device
+ * call). */
+#define MCD_FORECAST_VIEW_COVER 64
+int mcd_forecast_assemble_view(const float* poses, const int32_t* cell, const int32_t* trans, const double* inv_affine,
+                               int32_t n_transform, int64_t n, int32_t n_corrupt, int32_t n_cells, int32_t method,
+                               int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
+                               float* spread_out, void* stream);
+
 /* The inverse of mcd_normalize_poses: norm (n, 34) f32 interleaved (what mcd_forecast_assemble writes) back to image pixels in the
  * bounding box of raw (n, 34) f32, the observed CSV row of the same person and frame -> out (n, 34) f32 interleaved.
  * The box L, R, T, B is computed exactly as mcd_normalize_poses computes it (fp32 margin, clip, round-half-even); per element k,
@@ -528,6 +548,40 @@ int mcd_stream_forecast_flush(const mcd_stream_state_t* s, const mcd_stream_fore
                               const mcd_score_cfg_t* cfg, int32_t method, int32_t spread_method, float vid_w, float vid_h,
                               const double* center, const double* scale, float* expected_out, float* norm_out, float* observed_out,
                               int32_t* count_out, float* spread_out, void* stream);
+
+/* Forecast ring of a live stream over EVERY transform (added without a change of MCD_ABI_VERSION: two new exports and a new struct,
+ * nothing existing touched): what mcd_forecast_assemble_view + mcd_denormalize_poses give for a row on the dataset path, bit for
+ * bit.  A fourth CALLER-owned state; the three above stay as they are.
+ *   forecast      (n_slots, ring_len, num_transform, n_corrupt, 34) f32: cell (r % ring_len, t, j) = row r as corrupt frame j of its
+ *                 ONE window under transform t, ALREADY mapped back through the inverse of that transform (the per-joint map of
+ *                 mcd_forecast_assemble_view; when no sample passes, the zeros are mapped)
+ *   observed      (n_slots, ring_len, 34) f32: the raw row r as pushed
+ *   n_corrupt     the model's number of forecast frames;  num_transform  the stream state's;  num_transform * n_corrupt <= 64
+ * The cell rule is that of mcd_stream_forecast_state_t; it does not depend on t, and nothing needs initialising.  A row's k valid
+ * cells (k <= num_transform * n_corrupt) are combined in the dataset's order: transform ascending, within a transform ascending
+ * window (= descending j).
+ * mcd_stream_forecast_group_tta / mcd_stream_forecast_flush_tta: the arguments, outputs and checks of mcd_stream_forecast_group /
+ * mcd_stream_forecast_flush, plus inv_affine (num_transform, 6) f64 device, the table of mcd_forecast_assemble_view (read by the group
+ * entry's store launch; the cells the flush entry reads are already mapped).  Store launch: one 64-lane wave per window of every
+ * transform.  Plain loads and stores, no atomics.  Further argument errors: a null inv_affine, a num_transform that is not the
+ * stream state's, num_transform * n_corrupt > 64 (MCD_EINVAL before any device call). */
+typedef struct {
+    float* forecast;
+    float* observed;
+    int32_t n_corrupt;
+    int32_t num_transform;
+} mcd_stream_forecast_tta_state_t;
+
+int mcd_stream_forecast_group_tta(const mcd_stream_state_t* s, const mcd_stream_forecast_tta_state_t* fs, const float* raw,
+                                  const int32_t* desc, int32_t n, const float* loss_all, const float* poses_all, const int32_t* win,
+                                  int32_t n_windows, const mcd_score_cfg_t* cfg, int32_t aggregation, int32_t method,
+                                  int32_t spread_method, float vid_w, float vid_h, const double* center, const double* scale,
+                                  const double* inv_affine, float* expected_out, float* norm_out, float* observed_out,
+                                  int32_t* count_out, float* spread_out, void* stream);
+int mcd_stream_forecast_flush_tta(const mcd_stream_state_t* s, const mcd_stream_forecast_tta_state_t* fs, const int32_t* win, int32_t n,
+                                  const mcd_score_cfg_t* cfg, int32_t method, int32_t spread_method, float vid_w, float vid_h,
+                                  const double* center, const double* scale, const double* inv_affine, float* expected_out,
+                                  float* norm_out, float* observed_out, int32_t* count_out, float* spread_out, void* stream);
 
 /* Online clip scores of a live stream: the last stage of post_processing -- the person aggregation
  * mean_p s + (max_p log1p s - min_p log1p s) (mocodad.py:399-401), score_process = shift + gaussian_filter1d (eval_utils.py:100-106)

@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("MCD_LIB", os.path.join(_HERE, "libmocodad_hip.so"))  
 
 MCD_MAX_FRAMES = 32
 MCD_MAX_COND_LAYERS = 8
+MCD_FORECAST_VIEW_COVER = 64     # pairs on a forecast cell with every transform (mcd_forecast_assemble_view, the stream's tta state)
 
 STRATEGY = {"inject": 0, "concat": 1, "no_condition": 2, "inbetween_imp": 3, "random_imp": 4}
 LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
@@ -67,6 +68,10 @@ class StreamForecastState(C.Structure):
     _fields_ = [("forecast", C.c_void_p), ("observed", C.c_void_p), ("n_corrupt", C.c_int32)]
 
 
+class StreamForecastTtaState(C.Structure):
+    _fields_ = [("forecast", C.c_void_p), ("observed", C.c_void_p), ("n_corrupt", C.c_int32), ("num_transform", C.c_int32)]
+
+
 class ClipState(C.Structure):
     _fields_ = [("sum", C.c_void_p), ("lmax", C.c_void_p), ("lmin", C.c_void_p), ("n", C.c_void_p), ("n_clips", C.c_int32),
                 ("clip_ring_len", C.c_int32), ("num_transform", C.c_int32)]
@@ -113,6 +118,8 @@ _SIGS = {
                                       C.c_void_p]),
     "mcd_forecast_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_forecast_assemble_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_denormalize_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "mcd_stream_flush": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -130,6 +137,13 @@ _SIGS = {
     "mcd_stream_forecast_flush": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamForecastState), C.c_void_p, C.c_int32,
                                             C.POINTER(ScoreCfg), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_stream_forecast_group_tta": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamForecastTtaState), C.c_void_p, C.c_void_p,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ScoreCfg), C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_stream_forecast_flush_tta": (C.c_int, [C.POINTER(StreamState), C.POINTER(StreamForecastTtaState), C.c_void_p, C.c_int32,
+                                                C.POINTER(ScoreCfg), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_stream_clip_update": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_int32, C.c_void_p]),
     "mcd_stream_clip_emit": (C.c_int, [C.POINTER(ClipState), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,

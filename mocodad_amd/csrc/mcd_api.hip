@@ -720,6 +720,39 @@ int mcd_forecast_assemble(const float* poses, const int32_t* cell, int64_t n, in
     return MCD_OK;
 }
 
+int mcd_forecast_assemble_view(const float* poses, const int32_t* cell, const int32_t* trans, const double* inv_affine,
+                               int32_t n_transform, int64_t n, int32_t n_corrupt, int32_t n_cells, int32_t method,
+                               int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
+                               float* spread_out, void* stream) {
+    if (!trans)      // no transforms: the call is mcd_forecast_assemble, its checks and its kernels
+        return mcd_forecast_assemble(poses, cell, n, n_corrupt, n_cells, method, spread_method, max_cover, workspace, pose_out, count_out,
+                                     spread_out, stream);
+    if (n < 0 || n_cells < 0) return fail(MCD_EINVAL, "need n, n_cells >= 0");
+    if (n_corrupt < 1 || n_corrupt > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "need 1 <= n_corrupt <= 32");
+    if (max_cover < 1 || max_cover > MCD_FORECAST_VIEW_COVER) return fail(MCD_EINVAL, "need 1 <= max_cover <= 64");
+    if (int rc = check_forecast_methods(method, spread_method)) return rc;
+    if (n > 0x7fffffffll / n_corrupt) return fail(MCD_EINVAL, "n x n_corrupt exceeds 2^31 - 1: assemble in smaller batches");
+    if (!inv_affine) return fail(MCD_EINVAL, "trans needs inv_affine, the inverse table of its transforms");
+    if (n_transform < 1) return fail(MCD_EINVAL, "need n_transform >= 1");
+    if (n_cells == 0) return MCD_OK;
+    if (!workspace || !pose_out || !count_out || !spread_out) return fail(MCD_EINVAL, "null argument");
+    if (n > 0 && (!poses || !cell)) return fail(MCD_EINVAL, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ForecastViewParams V{{poses, cell, workspace, pose_out, count_out, spread_out, (int)(n * n_corrupt), n_corrupt, n_cells, method,
+                          spread_method, max_cover}, trans, inv_affine, n_transform};
+    HIP_TRY(hipMemsetAsync(count_out, 0, (size_t)n_cells * sizeof(int32_t), st));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(pose_out, 0, (size_t)n_cells * 34 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(spread_out, 0, (size_t)n_cells * sizeof(float), st));
+        return MCD_OK;
+    }
+    hipLaunchKernelGGL(forecast_claim_view_kernel, dim3((unsigned)((V.f.n_pairs + 255ll) / 256)), dim3(256), 0, st, V);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(forecast_reduce_view_kernel, dim3(n_cells < 65536 ? n_cells : 65536), dim3(64), 0, st, V);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* c) {
     if (!c || c->n_clips <= 0 || c->num_transform <= 0 || c->n_persons <= 0 || c->max_frames <= 0) return 0;
     const int64_t rows = (int64_t)c->num_transform * c->n_clips * c->n_persons;

@@ -9,13 +9,15 @@
 //                               -- both in ONE statement of that box: pose_box
 //   forecast_claim / forecast_reduce kernels   overlapping window forecasts -> one pose per (person, frame) cell + their spread
 //                               (mcd_forecast_assemble)                                         utils/eval_utils.py:13-24,37-72
+//   forecast_claim_view / forecast_reduce_view kernels   the same over the windows of EVERY test-time transform, each forecast
+//                               mapped back by inverse_affine_coord (mcd_forecast_assemble_view)
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
 // with the parameter blocks the host fills (SelectParams inside AggrParams and MapParams, ForecastParams, FrameParams).  Included
 // once, by mcd_api.hip (which defines API_THREADS and says `using namespace mcd`), in front of its host code.  The kernels of a live
 // stream are mcd_stream_kernel.hpp, included behind this file: they share normalize_pose_row / denormalize_pose_row, wave_select,
-// forecast_reduce_staged and the pieces of frame_scores_kernel (person_aggr_*, reflect_index, gauss_taps) defined here.
+// forecast_reduce_staged, inverse_affine_coord and the pieces of frame_scores_kernel (person_aggr_*, reflect_index, gauss_taps) defined here.
 #pragma once
 
 namespace {
@@ -386,6 +388,33 @@ __global__ __launch_bounds__(256) void forecast_claim_kernel(const ForecastParam
     if (slot < F.max_cover) F.list[(size_t)c * F.max_cover + slot] = (int)u;
 }
 
+// Forecasts from every test-time transform (mcd_forecast_assemble_view; the stream's store kernel): coordinate c (0 = x, 1 = y) of
+// the joint (xp, yp) forecast under a transform, mapped back by the row m = [i00 i01 i02 i10 i11 i12] of the inverse table:
+// (i_c0 xp + i_c1 yp) + i_c2 in float64, unfused, rounded to fp32 once.  A row equal to (1,0,0,0,1,0) copies the value: a -0.0
+// keeps its sign and a NaN in the other coordinate stays where it is, so the identity's pairs carry the bits they carry without a map.
+constexpr int FORECAST_VIEW_COVER = MCD_FORECAST_VIEW_COVER;      // pairs on a cell with all transforms
+__device__ __forceinline__ float inverse_affine_coord(const double* __restrict__ m, float xp, float yp, int c) {
+#pragma clang fp contract(off)
+    if (m[0] == 1.0 && m[1] == 0.0 && m[2] == 0.0 && m[3] == 0.0 && m[4] == 1.0 && m[5] == 0.0) return c ? yp : xp;
+    const double px = m[3 * c] * (double)xp, py = m[3 * c + 1] * (double)yp;
+    return (float)((px + py) + m[3 * c + 2]);
+}
+struct ForecastViewParams {
+    ForecastParams f;
+    const int* trans; const double* inv;      // (N,), (n_transform, 6)
+    int n_transform;
+};
+// forecast_claim_kernel with one more reason to ignore a pair: its window's transform is not in the table
+__global__ __launch_bounds__(256) void forecast_claim_view_kernel(const ForecastViewParams V) {
+    const ForecastParams& F = V.f;
+    const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= F.n_pairs) return;
+    const int c = F.cell[u], t = V.trans[u / F.Tx];
+    if (c < 0 || c >= F.n_cells || t < 0 || t >= V.n_transform) return;
+    const int slot = atomicAdd(F.count_out + c, 1);
+    if (slot < F.max_cover) F.list[(size_t)c * F.max_cover + slot] = (int)u;
+}
+
 // the middle of the k values x[0], x[stride], ... (np.median: for even k the half-sum of the two middle values), by rank
 // counting as wave_select does: rank of j = #{m : x_m < x_j or (x_m == x_j and m < j)}; a NaN among them gives NaN
 __device__ __forceinline__ double forecast_median(const float* x, int stride, int k) {
@@ -409,7 +438,7 @@ __device__ __forceinline__ double forecast_median(const float* x, int stride, in
 // The reduction of ONE cell, shared by forecast_reduce_kernel and the stream's forecast rows (forecast_emit_row): the k x 34 values
 // staged in LDS in list order (vals[j * 34 + f]) -> lanes 0 .. 33 store their feature's pose to po[lane], the spread goes to *so.
 // sd (34 doubles) and mid (2 doubles) are LDS.  Called by all 64 lanes of the one-wave workgroup, behind the barrier that makes
-// `vals` visible; 1 <= k <= MCD_MAX_FRAMES.
+// `vals` visible; 1 <= k <= the rows `vals` holds (MCD_MAX_FRAMES, or FORECAST_VIEW_COVER with all transforms).
 __device__ __forceinline__ void forecast_reduce_staged(const float* vals, int k, int method, int spread_method, int lane, double* sd,
                                                        double* mid, float* po, float* so) {
 #pragma clang fp contract(off)      // sum((x - mean)^2) is a product, then a sum: never an FMA
@@ -450,9 +479,12 @@ __device__ __forceinline__ void forecast_reduce_staged(const float* vals, int k,
     }
 }
 
-__global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParams F) {
-    __shared__ int claimed[MCD_MAX_FRAMES], ordered[MCD_MAX_FRAMES];
-    __shared__ float vals[MCD_MAX_FRAMES * 34];
+// The cells of a launch, for forecast_reduce_kernel (COVER = MCD_MAX_FRAMES, value = the pose element as it lies) and
+// forecast_reduce_view_kernel (COVER = FORECAST_VIEW_COVER, value = it mapped back): value(window i, forecast frame tx, feature f).
+template <int COVER, class Value>
+__device__ __forceinline__ void forecast_reduce_cells(const ForecastParams& F, Value value) {
+    __shared__ int claimed[COVER], ordered[COVER];
+    __shared__ float vals[COVER * 34];
     __shared__ double sd[34], mid[2];         // per-feature standard deviations; their two middle values
     const int lane = threadIdx.x;
     for (int c = blockIdx.x; c < F.n_cells; c += gridDim.x) {
@@ -476,11 +508,25 @@ __global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParam
         __syncthreads();
         for (int e = lane; e < k * 34; e += 64) {
             const int j = e / 34, f = e - j * 34, pair = ordered[j], i = pair / F.Tx, tx = pair - i * F.Tx;
-            vals[e] = F.poses[(((size_t)i * 2 + (f & 1)) * F.Tx + tx) * 17 + (f >> 1)];
+            vals[e] = value(i, tx, f);
         }
         __syncthreads();
         forecast_reduce_staged(vals, k, F.method, F.spread_method, lane, sd, mid, po, F.spread_out + c);
     }
+}
+
+__global__ __launch_bounds__(64) void forecast_reduce_kernel(const ForecastParams F) {
+    forecast_reduce_cells<MCD_MAX_FRAMES>(F, [&](int i, int tx, int f) -> float {
+        return F.poses[(((size_t)i * 2 + (f & 1)) * F.Tx + tx) * 17 + (f >> 1)];
+    });
+}
+
+__global__ __launch_bounds__(64) void forecast_reduce_view_kernel(const ForecastViewParams V) {
+    const ForecastParams& F = V.f;
+    forecast_reduce_cells<FORECAST_VIEW_COVER>(F, [&](int i, int tx, int f) -> float {
+        const float* p = F.poses + ((size_t)i * 2 * F.Tx + tx) * 17 + (f >> 1);      // a claimed pair's transform is in the table
+        return inverse_affine_coord(V.inv + 6 * V.trans[i], p[0], p[(size_t)F.Tx * 17], f & 1);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

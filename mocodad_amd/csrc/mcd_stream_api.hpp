@@ -96,6 +96,75 @@ static int stream_forecast_params(const mcd_stream_state_t* s, const mcd_stream_
     return MCD_OK;
 }
 
+// the forecast rings of every transform: (n_slots, ring_len, num_transform, n_corrupt, 34) and (n_slots, ring_len, 34) floats.  What is
+// new is checked here, the rest by stream_forecast_params on the same three fields
+static int stream_forecast_tta_params(const mcd_stream_state_t* s, const mcd_stream_forecast_tta_state_t* fs, const mcd_score_cfg_t* cfg,
+                                      int32_t method, int32_t spread_method, float vid_w, float vid_h, const double* center,
+                                      const double* scale, const double* inv_affine, StreamParams* P, StreamForecastParams* F) {
+    memset(F, 0, sizeof(*F));
+    if (int rc = stream_params(s, P)) return rc;
+    if (!fs || !fs->forecast || !fs->observed) return fail(MCD_EINVAL, "null stream forecast state");
+    if (fs->num_transform != P->nt) return fail(MCD_EINVAL, "stream forecast state: num_transform is not the stream state's");
+    if (fs->n_corrupt < 1 || fs->n_corrupt > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "stream forecast state: need 1 <= n_corrupt <= 32");
+    if ((int64_t)fs->num_transform * fs->n_corrupt > MCD_FORECAST_VIEW_COVER)
+        return fail(MCD_EINVAL, "stream forecast state: num_transform * n_corrupt exceeds 64, the pairs one row's reduction holds");
+    if ((int64_t)s->n_slots * s->ring_len > 0x7fffffffll / (34ll * fs->n_corrupt * fs->num_transform))
+        return fail(MCD_EUNSUPPORTED, "stream forecast ring of more than 2^31 elements");
+    const mcd_stream_forecast_state_t one{fs->forecast, fs->observed, fs->n_corrupt};
+    if (int rc = stream_forecast_params(s, &one, cfg, method, spread_method, vid_w, vid_h, center, scale, P, F)) return rc;
+    if (!inv_affine) return fail(MCD_EINVAL, "null inv_affine");
+    return MCD_OK;
+}
+
+// What the forecast entries of one transform and of every transform share behind their state's checks: the checks of a group (a
+// flush), then the launches.  inv == nullptr: the ring of transform 0 (mcd_stream_forecast_state_t); else the ring of every transform
+// and its inverse table.
+static int stream_forecast_group_run(const mcd_stream_state_t* s, const StreamParams& P, StreamForecastParams& F, const double* inv,
+                                     const float* raw, const int32_t* desc, int32_t n, const float* loss_all, const float* poses_all,
+                                     const int32_t* win, int32_t n_windows, const mcd_score_cfg_t* cfg, int32_t aggregation,
+                                     float* expected_out, float* norm_out, float* observed_out, int32_t* count_out, float* spread_out,
+                                     void* stream) {
+    if (aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST)
+        return fail(MCD_EINVAL, "a forecast is the pose of ONE sample: aggregation must be MCD_AGGR_BEST or MCD_AGGR_WORST");
+    if (int rc = check_group_rows(s, n, n_windows)) return rc;
+    long long total;
+    if (int rc = check_group_windows(s, n_windows, 1, &total)) return rc;
+    if (cfg->n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
+    if (n == 0) return MCD_OK;
+    if (!raw || !desc) return fail(MCD_EINVAL, "null argument");
+    if (n_windows > 0 && (!loss_all || !poses_all || !win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out))
+        return fail(MCD_EINVAL, "null argument");
+    F.loss_all = loss_all; F.poses_all = poses_all; F.S = cfg->n_samples; F.strategy = aggregation; F.in_lds = F.S <= AGG_LDS_MAX;
+    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
+    hipStream_t st = (hipStream_t)stream;
+    // the windows' forecasts and the raw rows in one launch; the final rows in a second one behind it (stream order)
+    const long long blocks = (inv ? total : (long long)n_windows) + ((long long)n * 34 + 63) / 64;
+    const size_t lds = (size_t)(SEL_LDS_WORDS + (F.in_lds ? F.S : 0)) * sizeof(float);
+    if (inv) hipLaunchKernelGGL(stream_forecast_store_tta_kernel, dim3((unsigned)blocks), dim3(64), lds, st, P, F, inv, raw, desc, n, win, n_windows, (int)total);
+    else hipLaunchKernelGGL(stream_forecast_store_kernel, dim3((unsigned)blocks), dim3(64), lds, st, P, F, raw, desc, n, win, n_windows, (int)total);
+    HIP_TRY(hipGetLastError());
+    if (n_windows == 0) return MCD_OK;
+    if (inv) hipLaunchKernelGGL(stream_forecast_emit_tta_kernel, dim3((unsigned)n_windows), dim3(64), 0, st, P, F, win, n_windows, (int)total);
+    else hipLaunchKernelGGL(stream_forecast_emit_kernel, dim3((unsigned)n_windows), dim3(64), 0, st, P, F, win, n_windows, (int)total);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
+static int stream_forecast_flush_run(const StreamParams& P, StreamForecastParams& F, bool tta, const int32_t* win, int32_t n,
+                                     float* expected_out, float* norm_out, float* observed_out, int32_t* count_out, float* spread_out,
+                                     void* stream) {
+    if (n < 0 || n > P.n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
+    const long long rows = (long long)n * (P.seg_len - 1);
+    if (rows == 0) return MCD_OK;
+    if (!win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out) return fail(MCD_EINVAL, "null argument");
+    if (rows > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
+    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
+    if (tta) hipLaunchKernelGGL(stream_forecast_flush_tta_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, P, F, win, n);
+    else hipLaunchKernelGGL(stream_forecast_flush_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, P, F, win, n);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 static int clip_params(const mcd_clip_state_t* c, ClipParams* P) {
     if (!c || !c->sum || !c->lmax || !c->lmin || !c->n) return fail(MCD_EINVAL, "null clip state");
     if (c->n_clips <= 0 || c->num_transform <= 0 || c->clip_ring_len <= 0)
@@ -182,28 +251,8 @@ int mcd_stream_forecast_group(const mcd_stream_state_t* s, const mcd_stream_fore
     StreamParams P;
     StreamForecastParams F;
     if (int rc = stream_forecast_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, &P, &F)) return rc;
-    if (aggregation != MCD_AGGR_BEST && aggregation != MCD_AGGR_WORST)
-        return fail(MCD_EINVAL, "a forecast is the pose of ONE sample: aggregation must be MCD_AGGR_BEST or MCD_AGGR_WORST");
-    if (int rc = check_group_rows(s, n, n_windows)) return rc;
-    long long total;
-    if (int rc = check_group_windows(s, n_windows, 1, &total)) return rc;
-    if (cfg->n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
-    if (n == 0) return MCD_OK;
-    if (!raw || !desc) return fail(MCD_EINVAL, "null argument");
-    if (n_windows > 0 && (!loss_all || !poses_all || !win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out))
-        return fail(MCD_EINVAL, "null argument");
-    F.loss_all = loss_all; F.poses_all = poses_all; F.S = cfg->n_samples; F.strategy = aggregation; F.in_lds = F.S <= AGG_LDS_MAX;
-    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
-    hipStream_t st = (hipStream_t)stream;
-    // the windows' forecasts and the raw rows in one launch; the final rows in a second one behind it (stream order)
-    const long long blocks = (long long)n_windows + ((long long)n * 34 + 63) / 64;
-    const size_t lds = (size_t)(SEL_LDS_WORDS + (F.in_lds ? F.S : 0)) * sizeof(float);
-    hipLaunchKernelGGL(stream_forecast_store_kernel, dim3((unsigned)blocks), dim3(64), lds, st, P, F, raw, desc, n, win, n_windows, (int)total);
-    HIP_TRY(hipGetLastError());
-    if (n_windows == 0) return MCD_OK;
-    hipLaunchKernelGGL(stream_forecast_emit_kernel, dim3((unsigned)n_windows), dim3(64), 0, st, P, F, win, n_windows, (int)total);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return stream_forecast_group_run(s, P, F, nullptr, raw, desc, n, loss_all, poses_all, win, n_windows, cfg, aggregation, expected_out,
+                                     norm_out, observed_out, count_out, spread_out, stream);
 }
 
 int mcd_stream_forecast_flush(const mcd_stream_state_t* s, const mcd_stream_forecast_state_t* fs, const int32_t* win, int32_t n,
@@ -213,15 +262,30 @@ int mcd_stream_forecast_flush(const mcd_stream_state_t* s, const mcd_stream_fore
     StreamParams P;
     StreamForecastParams F;
     if (int rc = stream_forecast_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, &P, &F)) return rc;
-    if (n < 0 || n > P.n_slots) return fail(MCD_EINVAL, "need 0 <= n <= n_slots");
-    const long long rows = (long long)n * (P.seg_len - 1);
-    if (rows == 0) return MCD_OK;
-    if (!win || !expected_out || !norm_out || !observed_out || !count_out || !spread_out) return fail(MCD_EINVAL, "null argument");
-    if (rows > 0x7fffffffll) return fail(MCD_EUNSUPPORTED, "too many tracks for one launch");
-    F.expected = expected_out; F.norm = norm_out; F.observed = observed_out; F.count = count_out; F.spread = spread_out;
-    hipLaunchKernelGGL(stream_forecast_flush_kernel, dim3((unsigned)rows), dim3(64), 0, (hipStream_t)stream, P, F, win, n);
-    HIP_TRY(hipGetLastError());
-    return MCD_OK;
+    return stream_forecast_flush_run(P, F, false, win, n, expected_out, norm_out, observed_out, count_out, spread_out, stream);
+}
+
+int mcd_stream_forecast_group_tta(const mcd_stream_state_t* s, const mcd_stream_forecast_tta_state_t* fs, const float* raw,
+                                  const int32_t* desc, int32_t n, const float* loss_all, const float* poses_all, const int32_t* win,
+                                  int32_t n_windows, const mcd_score_cfg_t* cfg, int32_t aggregation, int32_t method,
+                                  int32_t spread_method, float vid_w, float vid_h, const double* center, const double* scale,
+                                  const double* inv_affine, float* expected_out, float* norm_out, float* observed_out,
+                                  int32_t* count_out, float* spread_out, void* stream) {
+    StreamParams P;
+    StreamForecastParams F;
+    if (int rc = stream_forecast_tta_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, inv_affine, &P, &F)) return rc;
+    return stream_forecast_group_run(s, P, F, inv_affine, raw, desc, n, loss_all, poses_all, win, n_windows, cfg, aggregation,
+                                     expected_out, norm_out, observed_out, count_out, spread_out, stream);
+}
+
+int mcd_stream_forecast_flush_tta(const mcd_stream_state_t* s, const mcd_stream_forecast_tta_state_t* fs, const int32_t* win, int32_t n,
+                                  const mcd_score_cfg_t* cfg, int32_t method, int32_t spread_method, float vid_w, float vid_h,
+                                  const double* center, const double* scale, const double* inv_affine, float* expected_out,
+                                  float* norm_out, float* observed_out, int32_t* count_out, float* spread_out, void* stream) {
+    StreamParams P;
+    StreamForecastParams F;
+    if (int rc = stream_forecast_tta_params(s, fs, cfg, method, spread_method, vid_w, vid_h, center, scale, inv_affine, &P, &F)) return rc;
+    return stream_forecast_flush_run(P, F, true, win, n, expected_out, norm_out, observed_out, count_out, spread_out, stream);
 }
 
 int mcd_stream_clip_update(const mcd_clip_state_t* c, const int32_t* runs, int32_t n_runs, const int32_t* contrib,

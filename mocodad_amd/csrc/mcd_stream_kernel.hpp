@@ -1,10 +1,12 @@
 // mcd_stream_kernel.hpp — the device code of a live stream (launched by mcd_stream_api.hpp): the loader step, sliding windows and
 // scatter-max of the dataset path (utils/preprocessing.py:14-86, models/mocodad.py:392-393) one group of ticks at a time on device
 // rings -- stream_push_group / stream_frame_scores_group / stream_joint_scores_group / stream_flush<W>, the forecast ring's
-// stream_forecast_store / _emit / _flush -- and the online clip scores stream_clip_update / stream_clip_emit, with their parameter
+// stream_forecast_store / _emit / _flush and, over every transform, stream_forecast_store_tta / _emit_tta / _flush_tta -- and the online
+// clip scores stream_clip_update / stream_clip_emit, with their parameter
 // blocks and the three table rows the host hands them, each decoded and validated ONCE: WindowRow, ClosedRow, PushedRow.
 // Included once, by mcd_api.hip, behind mcd_post_kernel.hpp, whose pieces it shares: normalize_pose_row / denormalize_pose_row,
-// wave_select and stage_samples, forecast_reduce_staged, and person_aggr_* / reflect_index / gauss_taps of frame_scores_kernel.
+// wave_select and stage_samples, forecast_reduce_staged, inverse_affine_coord, and person_aggr_* / reflect_index / gauss_taps of
+// frame_scores_kernel.
 #pragma once
 
 namespace {
@@ -225,6 +227,9 @@ __global__ __launch_bounds__(64) void stream_forecast_store_kernel(StreamParams 
 
 // Row r of `slot`, seen with r_hi the track's last row so far, into row o of the five outputs.  vals [MCD_MAX_FRAMES * 34], pn [34],
 // sd [34], mid [2]: LDS.  One wave; every lane takes the same branches.
+// TTA (the ring of every transform, below): the row's cells are (S.nt, Tx, 34), its pairs the k1 windows of transform 0, then those
+// of transform 1, ...: k = S.nt * k1 <= FORECAST_VIEW_COVER rows of vals.
+template <bool TTA = false>
 __device__ __forceinline__ void forecast_emit_row(const StreamParams& S, const StreamForecastParams& F, int slot, int r, int r_hi, size_t o,
                                                   int lane, float* vals, float* pn, double* sd, double* mid) {
     int ja = 0, jb = 0;
@@ -233,12 +238,12 @@ __device__ __forceinline__ void forecast_emit_row(const StreamParams& S, const S
         ja += c <= r ? 1 : 0;
         jb += r + S.seg_len - 1 - c > r_hi ? 1 : 0;
     }
-    const int k = ja > jb ? ja - jb : 0;
+    const int k1 = ja > jb ? ja - jb : 0, k = TTA ? k1 * S.nt : k1;
     const size_t row = (size_t)slot * S.L + r % S.L;
-    const float* cell = F.fc + row * F.Tx * 34;
+    const float* cell = F.fc + row * (TTA ? S.nt : 1) * F.Tx * 34;
     for (int e = lane; e < k * 34; e += 64) {      // window order: the m-th window of the row holds it as corrupt frame ja - 1 - m
-        const int m = e / 34, f = e - m * 34;
-        vals[e] = cell[(ja - 1 - m) * 34 + f];
+        const int p = e / 34, f = e - p * 34, t = TTA ? p / k1 : 0, m = p - t * k1;
+        vals[e] = cell[(t * F.Tx + ja - 1 - m) * 34 + f];
     }
     if (lane < 34) F.observed[o * 34 + lane] = F.obs[row * 34 + lane];
     if (lane == 0) F.count[o] = k;
@@ -276,6 +281,67 @@ __global__ __launch_bounds__(64) void stream_forecast_flush_kernel(StreamParams 
     const ClosedRow c = load_closed_row(win, i);
     if (!c.valid(S)) return;
     forecast_emit_row(S, F, c.slot, c.r_last - S.seg_len + 2 + k, c.r_last, (size_t)u, threadIdx.x, vals, pn, sd, mid);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The forecast ring over EVERY transform (mcd_stream_forecast_tta_state_t): ring (n_slots, L, nt, Tx, 34), cell (r % L, t, j) = row r
+// as corrupt frame j of its one window under transform t, already mapped back by inverse_affine_coord (mcd_post_kernel.hpp) with row t
+// of the inverse table -- what forecast_reduce_view_kernel stages on the dataset path.  The cell rule above does not depend on t.
+//   stream_forecast_store_tta_kernel: workgroups 0 .. n_windows * nt - 1, one wave per (window of the table, transform); behind them
+//                 the raw rows, as stream_forecast_store_kernel copies them.
+//   stream_forecast_emit_tta_kernel / _flush_tta_kernel: forecast_emit_row<true>: transform ascending, then window order.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void stream_forecast_store_tta_kernel(StreamParams S, StreamForecastParams F, const double* __restrict__ inv,
+                                                                       const float* __restrict__ raw, const int* __restrict__ desc, int n,
+                                                                       const int* __restrict__ win, int n_windows, int n_win) {
+    extern __shared__ float sft_lds[];      // [SEL_LDS_WORDS] wave_select's, [S] staged losses (in_lds)
+    const int lane = threadIdx.x, n_wt = n_windows * S.nt;
+    if ((int)blockIdx.x >= n_wt) {
+        const long long u = (long long)((int)blockIdx.x - n_wt) * 64 + lane;
+        if (u >= (long long)n * 34) return;
+        const int i = (int)(u / 34), f = (int)(u - (long long)i * 34);
+        const PushedRow d = load_pushed_row(desc, i);
+        if (!d.valid(S)) return;
+        F.obs[((size_t)d.slot * S.L + d.r % S.L) * 34 + f] = raw[u];
+        return;
+    }
+    const int q = blockIdx.x / S.nt, t = blockIdx.x - q * S.nt;
+    const WindowRow w = load_window_row(win, q);
+    if (!w.valid(S, t, n_win, n_windows)) return;
+    const size_t pos = (size_t)w.pos(t);    // the window's batch position under transform t (trans_out[pos] = t)
+    const SampleVals X = stage_samples(F.loss_all + pos * F.S, 1, F.S, sft_lds + SEL_LDS_WORDS, F.in_lds != 0, lane);
+    const Selection sel = wave_select(X, F.S, lane, F.strategy, 0.f, sft_lds);
+    const float* p = F.poses_all + (pos * F.S + (sel.i0 >= 0 ? sel.i0 : 0)) * 34 * F.Tx;
+    const int first = w.r_last - S.seg_len + 1;
+    for (int j = 0; j < F.Tx; ++j) {
+        const int r = first + F.cidx[j];
+        if (lane < 34) {                    // no sample passes: the zeros of pose_agg, mapped like any forecast
+            const float xp = sel.i0 >= 0 ? p[j * 17 + (lane >> 1)] : 0.f, yp = sel.i0 >= 0 ? p[(F.Tx + j) * 17 + (lane >> 1)] : 0.f;
+            F.fc[((((size_t)w.slot * S.L + r % S.L) * S.nt + t) * F.Tx + j) * 34 + lane] = inverse_affine_coord(inv + 6 * t, xp, yp, lane & 1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void stream_forecast_emit_tta_kernel(StreamParams S, StreamForecastParams F, const int* __restrict__ win,
+                                                                      int n_windows, int n_win) {
+    __shared__ float vals[FORECAST_VIEW_COVER * 34], pn[34];
+    __shared__ double sd[34], mid[2];
+    const int q = blockIdx.x;
+    if (q >= n_windows) return;
+    const WindowRow w = load_window_row(win, q);
+    if (!w.valid(S, 0, n_win, n_windows)) return;
+    forecast_emit_row<true>(S, F, w.slot, w.r_last - S.seg_len + 1, w.r_last, (size_t)w.w, threadIdx.x, vals, pn, sd, mid);
+}
+
+__global__ __launch_bounds__(64) void stream_forecast_flush_tta_kernel(StreamParams S, StreamForecastParams F, const int* __restrict__ win, int n) {
+    __shared__ float vals[FORECAST_VIEW_COVER * 34], pn[34];
+    __shared__ double sd[34], mid[2];
+    const int pend = S.seg_len - 1, u = blockIdx.x;
+    if (u >= n * pend) return;
+    const int i = u / pend, k = u - i * pend;
+    const ClosedRow c = load_closed_row(win, i);
+    if (!c.valid(S)) return;
+    forecast_emit_row<true>(S, F, c.slot, c.r_last - S.seg_len + 2 + k, c.r_last, (size_t)u, threadIdx.x, vals, pn, sd, mid);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -887,19 +887,27 @@ def _caller_buffer(name: str, t: Optional[torch.Tensor], shape: Tuple[int, ...],
 
 def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, method: str = "median", spread_method: str = "mean",
                       max_cover: int = _lib.MCD_MAX_FRAMES, device=None, out=None,
-                      workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                      workspace: Optional[torch.Tensor] = None, trans: Optional[torch.Tensor] = None,
+                      inv_affine=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """mcd_forecast_assemble (utils/eval_utils.py:13-24, 37-72): the selected forecasts of overlapping windows, poses (N,2,Tx,17),
     collapsed into one pose per output cell; cell (N,Tx) int32 names the cell of every forecast frame, a value outside
     [0, n_cells) means "ignore".  method: 'unique' (the lowest window index) | 'mean' | 'median'; spread_method: 'mean' | 'median'
     of the 34 per-feature standard deviations over the windows covering the cell; max_cover 1 .. 32: pairs a cell's list holds.
     -> (pose (n_cells, 34) fp32 interleaved x1,y1,...,x17,y17, count (n_cells,) int32, spread (n_cells,) fp32); a cell nobody
     forecasts is 0 with count 0, one with more than max_cover pairs is NaN with its true count.  out: the caller's three buffers
-    instead of new ones; workspace: the caller's int32 scratch of at least n_cells * max_cover words.  Asynchronous on the current
+    instead of new ones; workspace: the caller's int32 scratch of at least n_cells * max_cover words.
+    trans (N,) integer + inv_affine (n_transform, 6) float64 (utils.transforms.inverse_affine_table): mcd_forecast_assemble_view --
+    the forecast of window i is first mapped back through row trans[i] of the inverse table, so the windows of every test-time
+    transform forecast a cell in the coordinates of transform 0; a window whose transform is outside the table is ignored;
+    max_cover 1 .. 64 then.  Both None (the default): mcd_forecast_assemble.  Asynchronous on the current
     stream; arguments are checked before anything touches the device."""
     codes = forecast_codes(method, spread_method)
     max_cover, n_cells = int(max_cover), int(n_cells)
-    if not 1 <= max_cover <= _lib.MCD_MAX_FRAMES:
-        raise ValueError(f"max_cover must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {max_cover}")
+    if (trans is None) != (inv_affine is None):
+        raise ValueError("trans and inv_affine go together (both None = no transforms)")
+    cover_max = _lib.MCD_MAX_FRAMES if trans is None else _lib.MCD_FORECAST_VIEW_COVER
+    if not 1 <= max_cover <= cover_max:
+        raise ValueError(f"max_cover must be in 1 .. {cover_max}, got {max_cover}")
     if n_cells < 0:
         raise ValueError(f"n_cells must be >= 0, got {n_cells}")
     if poses.dim() != 4 or poses.shape[1] != 2 or poses.shape[3] != 17 or not 1 <= poses.shape[2] <= _lib.MCD_MAX_FRAMES:
@@ -909,6 +917,13 @@ def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, 
         raise ValueError(f"cell must be an integer ({N}, {Tx}) tensor, got {tuple(cell.shape)} {cell.dtype}")
     if N * Tx > 2**31 - 1:
         raise ValueError("N x Tx exceeds 2^31 - 1: assemble in smaller batches")
+    if trans is not None:
+        if tuple(trans.shape) != (N,) or trans.dtype.is_floating_point:
+            raise ValueError(f"trans must be an integer ({N},) tensor, got {tuple(trans.shape)} {trans.dtype}")
+        if not torch.is_tensor(inv_affine):      # (a list through torch.as_tensor would pass through float32)
+            inv_affine = torch.from_numpy(np.ascontiguousarray(inv_affine, dtype=np.float64))
+        if inv_affine.dim() != 2 or inv_affine.shape[0] < 1 or inv_affine.shape[1] != 6:
+            raise ValueError(f"inv_affine must be (n_transform, 6) with n_transform >= 1, got {tuple(inv_affine.shape)}")
     dev = _call_device(device, poses)
     if out is not None and len(out) != 3:
         raise ValueError("out must be the three buffers (pose, count, spread)")
@@ -931,8 +946,16 @@ def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, 
             o_spread = torch.empty(n_cells, device=dev, dtype=torch.float32)
         if workspace is None:
             workspace = torch.empty(max(n_cells * max_cover, 1), device=dev, dtype=torch.int32)
-        _lib.check(L.mcd_forecast_assemble(_ptr(poses), _ptr(cell), N, Tx, n_cells, codes[0], codes[1], max_cover, _ptr(workspace),
-                                           _ptr(o_pose), _ptr(o_count), _ptr(o_spread), _stream()))
+        if trans is None:
+            _lib.check(L.mcd_forecast_assemble(_ptr(poses), _ptr(cell), N, Tx, n_cells, codes[0], codes[1], max_cover, _ptr(workspace),
+                                               _ptr(o_pose), _ptr(o_count), _ptr(o_spread), _stream()))
+        else:
+            # (an empty tensor has no address, and a NULL trans would mean "no transforms": one word stands in, no window reads it)
+            trans = _i32c(trans, dev) if N else torch.zeros(1, device=dev, dtype=torch.int32)
+            inv = inv_affine.to(dev, torch.float64).contiguous()
+            _lib.check(L.mcd_forecast_assemble_view(_ptr(poses), _ptr(cell), _ptr(trans), _ptr(inv), int(inv.shape[0]), N, Tx, n_cells,
+                                                    codes[0], codes[1], max_cover, _ptr(workspace), _ptr(o_pose), _ptr(o_count),
+                                                    _ptr(o_spread), _stream()))
     return o_pose, o_count, o_spread
 
 
@@ -985,7 +1008,7 @@ class StreamRings:
     from one stream."""
 
     def __init__(self, n_slots: int, seg_len: int, ring_len: int, num_transform: int, vid_res: Sequence[float], center=None,
-                 scale=None, *, device=None, joint_scores: bool = False, forecasts: Optional[Tuple[str, str, int]] = None):
+                 scale=None, *, device=None, joint_scores: bool = False, forecasts: Optional[Tuple] = None):
         self.L = _lib.lib()
         _need_gpu()
         self.device = dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -1005,18 +1028,35 @@ class StreamRings:
                 self.joint_scores_ring = torch.zeros(self.n_slots, self.num_transform, self.ring_len, 17, device=dev, dtype=torch.float32)
             self._jstate = _lib.StreamJointState(joint_scores=self.joint_scores_ring.data_ptr())
         # forecasts = (method, spread, n_corrupt): the forecast and observed rings (mcd_stream_forecast_state_t); without it nothing
-        # is allocated
+        # is allocated.  (method, spread, n_corrupt, 'all'): the forecast ring of EVERY transform instead, (n_slots, ring_len,
+        # num_transform, n_corrupt, 34), and the inverse table of the transforms (mcd_stream_forecast_tta_state_t); the ring of
+        # transform 0 alone is not allocated then, nor this one under 'identity'
         self.forecast_ring, self.observed_ring, self._fstate, self._forecast = None, None, None, None
+        self.forecast_tta_ring, self.inv_affine, self._tstate = None, None, None
         if forecasts is not None:
-            method, spread, n_corrupt = forecasts
+            method, spread, n_corrupt = forecasts[:3]
+            transforms = forecasts[3] if len(forecasts) > 3 else "identity"
             self._forecast = forecast_codes(method, spread, ("forecast method", "forecast spread"))
             if not 1 <= int(n_corrupt) <= _lib.MCD_MAX_FRAMES:
                 raise ValueError(f"n_corrupt must be in 1 .. {_lib.MCD_MAX_FRAMES}, got {n_corrupt}")
+            if transforms not in ("identity", "all"):
+                raise ValueError(f"forecast transforms must be 'identity' or 'all', got {transforms!r}")
+            if transforms == "all" and self.num_transform * int(n_corrupt) > _lib.MCD_FORECAST_VIEW_COVER:
+                raise ValueError(f"forecast transforms 'all': num_transform * n_corrupt = {self.num_transform} * {int(n_corrupt)} exceeds "
+                                 f"{_lib.MCD_FORECAST_VIEW_COVER}, the forecasts one row's reduction holds")
             with torch.cuda.device(dev):      # (zeros: the kernels need no initial value, two streams in one state compare equal)
-                self.forecast_ring = torch.zeros(self.n_slots, self.ring_len, int(n_corrupt), 34, device=dev, dtype=torch.float32)
                 self.observed_ring = torch.zeros(self.n_slots, self.ring_len, 34, device=dev, dtype=torch.float32)
-            self._fstate = _lib.StreamForecastState(forecast=self.forecast_ring.data_ptr(), observed=self.observed_ring.data_ptr(),
-                                                    n_corrupt=int(n_corrupt))
+                if transforms == "all":
+                    from .utils.transforms import inverse_affine_table
+                    self.forecast_tta_ring = torch.zeros(self.n_slots, self.ring_len, self.num_transform, int(n_corrupt), 34, device=dev,
+                                                         dtype=torch.float32)
+                    self.inv_affine = inverse_affine_table(self.num_transform).to(dev)
+                    self._tstate = _lib.StreamForecastTtaState(forecast=self.forecast_tta_ring.data_ptr(), observed=self.observed_ring.data_ptr(),
+                                                               n_corrupt=int(n_corrupt), num_transform=self.num_transform)
+                else:
+                    self.forecast_ring = torch.zeros(self.n_slots, self.ring_len, int(n_corrupt), 34, device=dev, dtype=torch.float32)
+                    self._fstate = _lib.StreamForecastState(forecast=self.forecast_ring.data_ptr(), observed=self.observed_ring.data_ptr(),
+                                                            n_corrupt=int(n_corrupt))
 
     def _forecast_outputs(self, rows: int):
         dev = self.device
@@ -1036,6 +1076,13 @@ class StreamRings:
         with torch.cuda.device(self.device):
             out = self._forecast_outputs(nw)
             c, s = self._stats
+            if self._tstate is not None:      # every transform: mcd_stream_forecast_group_tta, the same call plus the inverse table
+                _lib.check(self.L.mcd_stream_forecast_group_tta(
+                    C.byref(self._state), C.byref(self._tstate), _ptr(raw), _ptr(desc), int(n), _ptr(loss_all) if nw else None,
+                    _ptr(poses_all) if nw else None, _ptr(win) if nw else None, nw, C.byref(cfg), _lib.AGGR[aggregation], self._forecast[0],
+                    self._forecast[1], self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), _ptr(self.inv_affine),
+                    *(_ptr(o) if nw else None for o in out), _stream()))
+                return out
             _lib.check(self.L.mcd_stream_forecast_group(
                 C.byref(self._state), C.byref(self._fstate), _ptr(raw), _ptr(desc), int(n), _ptr(loss_all) if nw else None,
                 _ptr(poses_all) if nw else None, _ptr(win) if nw else None, nw, C.byref(cfg), _lib.AGGR[aggregation], self._forecast[0],
@@ -1046,7 +1093,12 @@ class StreamRings:
         """mcd_stream_forecast_flush: as `flush` -> the five tensors of forecast_group with n * (seg_len - 1) rows."""
         with torch.cuda.device(self.device):
             out = self._forecast_outputs(int(n) * (self.seg_len - 1))
-            if out[3].numel():
+            if out[3].numel() and self._tstate is not None:
+                c, s = self._stats
+                _lib.check(self.L.mcd_stream_forecast_flush_tta(
+                    C.byref(self._state), C.byref(self._tstate), _ptr(win), int(n), C.byref(cfg), self._forecast[0], self._forecast[1],
+                    self.vid_res[0], self.vid_res[1], _ptr(c), _ptr(s), _ptr(self.inv_affine), *(_ptr(o) for o in out), _stream()))
+            elif out[3].numel():
                 c, s = self._stats
                 _lib.check(self.L.mcd_stream_forecast_flush(
                     C.byref(self._state), C.byref(self._fstate), _ptr(win), int(n), C.byref(cfg), self._forecast[0], self._forecast[1],

@@ -759,13 +759,18 @@ class ClipTable:
 # ----------------------------------------------------------------------------------------------------------------------
 FORECAST_METHODS = ("unique", "mean", "median")
 FORECAST_SPREADS = ("mean", "median")
+FORECAST_TRANSFORMS = ("identity", "all")
 
 
 @dataclass
 class ForecastCfg:
-    """PoseStream(forecasts=ForecastCfg(...)): method / spread as eval_MoCoDAD.py's --forecast-method / --forecast-spread."""
+    """PoseStream(forecasts=ForecastCfg(...)): method / spread as eval_MoCoDAD.py's --forecast-method / --forecast-spread;
+    transforms as its --forecast-transforms: 'identity' -- the windows of transform 0 forecast a row -- or 'all' -- the windows of
+    every transform do, each forecast mapped back through the inverse of its transform and combined transform-major, then in window
+    order (up to num_transform * n_corrupt <= 64 forecasts per row; forecast_track_rows(transforms='all') bit for bit)."""
     method: str = "median"
     spread: str = "mean"
+    transforms: str = "identity"
 
 
 def forecast_cover(corrupt_idx: Sequence[int], seg_len: int, r: int, r_last: int) -> List[Tuple[int, int]]:
@@ -902,6 +907,8 @@ class PoseStream:
             if model.aggregation_strategy not in ("best", "worst"):
                 raise ValueError(f"PoseStream(forecasts=...) needs an aggregation that selects a pose, best or worst: aggregation_strategy "
                                  f"{model.aggregation_strategy!r} aggregates losses and selects none")
+            if forecasts.transforms not in FORECAST_TRANSFORMS:
+                raise ValueError(f"forecasts: transforms must be one of {FORECAST_TRANSFORMS}, got {forecasts.transforms!r}")
         if self.latent and model.device.type != "cuda":
             raise ValueError("PoseStream scores the latent model (MoCoDADlatent) on a cuda device only: move the module to one "
                              "first (there is no CPU fallback)")
@@ -926,6 +933,11 @@ class PoseStream:
         extra = {"joint_scores": True} if self.joint_scores else {}
         if forecasts is not None:
             extra["forecasts"] = (forecasts.method, forecasts.spread, len(self.scorer.corrupt_idx))
+            if forecasts.transforms == "all":      # the ring of every transform in place of transform 0's (refused here beyond 64 per row)
+                if nt * len(self.scorer.corrupt_idx) > 64:
+                    raise ValueError(f"forecasts: transforms='all' puts num_transform * n_corrupt = {nt} * {len(self.scorer.corrupt_idx)} "
+                                     "forecasts on a row; the reduction holds 64")
+                extra["forecasts"] += ("all",)
         self.rings = StreamRings(n, self.seg_len, self.table.ring_len, nt, vid_res, center, scale, device=dev, **extra)
         self.ring = self.rings.ring
         self.clips, self.clip_rings, clip_words = None, None, 0

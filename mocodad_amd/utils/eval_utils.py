@@ -127,25 +127,49 @@ def joint_score_rows(maps, trans, meta, frames, gts, num_transform: int, joint_s
 
 
 # ------------------------------------------------------------------ forecast tracks (mcd_forecast_assemble)
-def forecast_cells_dense(row, frame_ids, trans, n_frames: int) -> np.ndarray:
+FORECAST_TRANSFORMS = ("identity", "all")
+
+
+def _forecast_transforms(transforms: str) -> bool:
+    """'identity' | 'all' -> whether the windows of every transform contribute."""
+    if transforms not in FORECAST_TRANSFORMS:
+        raise ValueError(f"transforms must be one of {FORECAST_TRANSFORMS}, got {transforms!r}")
+    return transforms == "all"
+
+
+def forecast_max_cover(num_transform: int, n_corrupt: int, transforms: str = "identity") -> int:
+    """The pairs a trajectory row can collect with fixed conditioning indices: n_corrupt windows of transform 0, under 'all' of
+    each of the num_transform transforms -- at most 64 (MCD_FORECAST_VIEW_COVER), more is refused by name."""
+    if not _forecast_transforms(transforms):
+        return int(n_corrupt)
+    cover = max(1, int(num_transform)) * int(n_corrupt)
+    if cover > 64:
+        raise ValueError(f"transforms='all' puts num_transform * n_corrupt = {int(num_transform)} * {int(n_corrupt)} = {cover} forecasts "
+                         "on a row; the reduction holds 64 (use fewer transforms, or transforms='identity')")
+    return cover
+
+
+def forecast_cells_dense(row, frame_ids, trans, n_frames: int, transforms: str = "identity") -> np.ndarray:
     """cell (N, Tx) int32 for a dense (row, frame) matrix in the reference's layout (compute_fig_matrix, eval_utils.py:13-24):
     row * n_frames + f - 1 for the 1-based frame id f of every forecast frame; -1 (ignored) for a window of another transform
     than 0, the identity -- their forecasts live in rotated or flipped coordinates --, a negative row, or a frame outside
-    [1, n_frames]."""
+    [1, n_frames].  transforms='all': the windows of every transform keep their cells (mcd_forecast_assemble_view maps their
+    forecasts back)."""
     row, f, trans = np.asarray(row, np.int64).reshape(-1, 1), np.asarray(frame_ids, np.int64), np.asarray(trans).reshape(-1, 1)
-    ok = (trans == 0) & (row >= 0) & (f >= 1) & (f <= n_frames)
+    ok = ((trans == 0) | _forecast_transforms(transforms)) & (row >= 0) & (f >= 1) & (f <= n_frames)
     return np.where(ok, row * n_frames + f - 1, -1).astype(np.int32)
 
 
-def forecast_cells_aligned(base, map_frames, trans, row_stride: int = 34) -> np.ndarray:
+def forecast_cells_aligned(base, map_frames, trans, row_stride: int = 34, transforms: str = "identity") -> np.ndarray:
     """cell (N, Tx) int32 = the global trajectory row of every forecast frame: base // 34 + its 0-based window frame index
-    (TrajectoryWindows.base: a window's element offset into the frame-major buffer); -1 for a window of another transform than 0."""
+    (TrajectoryWindows.base: a window's element offset into the frame-major buffer); -1 for a window of another transform than 0,
+    unless transforms='all'."""
     base, mf, trans = np.asarray(base, np.int64).reshape(-1, 1), np.asarray(map_frames, np.int64), np.asarray(trans).reshape(-1, 1)
-    return np.where(trans == 0, base // row_stride + mf, -1).astype(np.int32)
+    return np.where((trans == 0) | _forecast_transforms(transforms), base // row_stride + mf, -1).astype(np.int32)
 
 
 def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows=None, meta=None, frames=None, method: str = "median",
-                        spread_method: str = "mean", max_cover: int = 32):
+                        spread_method: str = "mean", max_cover: int = 32, transforms: str = "identity", num_transform: Optional[int] = None):
     """Forecast tracks of a dataset (eval_MoCoDAD.py --forecast-tracks): the selected forecast of every window, poses (N,2,Tx,17)
     (forward(return_='all')), collapsed into one expected pose per trajectory row -- per tracked person and video frame.
     trans (N,): only windows of transform 0, the identity, contribute.  map_frames (N,Tx): the 0-based window frame index of each
@@ -153,8 +177,14 @@ def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows
     row is a row of its buffer, cell = base // 34 + frame index) or from meta (N,4) / frames (N,seg_len) (a row is a distinct
     (scene, clip, person, frame id) of the transform-0 windows, in lexicographic order).  assemble: engine.forecast_assemble (or a
     restatement of it).
+    transforms='all' (eval_MoCoDAD.py --forecast-transforms all): the windows of EVERY transform contribute -- their cells are the
+    trajectory row of their forecast frame like transform 0's, and `assemble` is also given trans= and inv_affine= (the inverse
+    table of the transforms 0 .. num_transform - 1, default max(trans) + 1, utils.transforms.inverse_affine_table), with which it
+    maps each forecast back before combining; a row's forecasts are combined transform-major in the order of the windows.  The
+    rows themselves are still those the transform-0 windows cover.  max_cover may be up to 64 then.
     -> (pose (R,34), count (R,), spread (R,) as `assemble` returns them, rows (R,3) int64 = (scene, clip, person), frame_ids (R,)
     int64); a row no window forecasts -- the first n_cond rows of a track under a tail forecast -- has count 0 and a zero pose."""
+    every = _forecast_transforms(transforms)
     trans, mf = np.asarray(trans).reshape(-1), np.asarray(map_frames, np.int64)
     if windows is not None:
         meta, frames, base = np.asarray(windows.meta), np.asarray(windows.frames), np.asarray(windows.base)
@@ -170,19 +200,33 @@ def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows
     keys = np.concatenate([np.repeat(meta[ident, :3].astype(np.int64), seg_len, axis=0), frames[ident].reshape(-1, 1).astype(np.int64)], axis=1)
     if base is not None:
         n_rows = int(windows.buffer.numel()) // 34
-        cell = forecast_cells_aligned(base, mf, trans)
+        cell = forecast_cells_aligned(base, mf, trans, transforms=transforms)
         row_of = (base[ident, None] // 34 + np.arange(seg_len)).reshape(-1)         # trajectory row of every covered window frame
         table = np.zeros((n_rows, 4), np.int64)
         table[row_of] = keys
     else:
         table, inv = np.unique(keys, axis=0, return_inverse=True)
         n_rows = len(table)
-        dense = np.full((N, seg_len), -1, np.int64)
-        dense[ident] = inv.reshape(len(ident), seg_len)
-        cell = np.where(trans[:, None] == 0, np.take_along_axis(dense, mf, axis=1), -1).astype(np.int32)
+        if not every:
+            dense = np.full((N, seg_len), -1, np.int64)
+            dense[ident] = inv.reshape(len(ident), seg_len)
+            cell = np.where(trans[:, None] == 0, np.take_along_axis(dense, mf, axis=1), -1).astype(np.int32)
+        else:       # the row of every window's forecast frames, looked up in the table of the transform-0 rows (absent: ignored)
+            fkeys = np.concatenate([np.repeat(meta[:, :3].astype(np.int64), mf.shape[1], axis=0),
+                                    np.take_along_axis(frames.astype(np.int64), mf, axis=1).reshape(-1, 1)], axis=1)
+            both, back = np.unique(np.concatenate([table, fkeys]), axis=0, return_inverse=True)
+            row_of_key = np.full(len(both), -1, np.int64)
+            back = back.reshape(-1)
+            row_of_key[back[:n_rows]] = np.arange(n_rows)
+            cell = row_of_key[back[n_rows:]].reshape(N, mf.shape[1]).astype(np.int32)
     import torch
+    extra = {}
+    if every:
+        from .transforms import inverse_affine_table
+        nt = int(num_transform) if num_transform is not None else (int(trans.max()) + 1 if N else 1)
+        extra = {"trans": torch.from_numpy(np.ascontiguousarray(trans, dtype=np.int32)), "inv_affine": inverse_affine_table(nt)}
     pose, count, spread = assemble(poses, torch.from_numpy(np.ascontiguousarray(cell)), n_rows, method=method, spread_method=spread_method,
-                                   max_cover=max_cover)
+                                   max_cover=max_cover, **extra)
     return pose, count, spread, table[:, :3], table[:, 3]
 
 

@@ -36,7 +36,8 @@ maps launch behind the scoring call and mcd_stream_joint_scores_group; the pose 
 --forecasts [--forecast-method M] [--forecast-spread S]: the expected pose of every row in every tick (PoseStream(forecasts=
 ForecastCfg(M, S))): "tick" then includes the scoring call writing its per-sample losses and poses and the two launches
 of mcd_stream_forecast_group (closes: mcd_stream_forecast_flush); a best / worst aggregation only; the pose model, or a latent config
-in pose space.
+in pose space.  --forecast-transforms all: the windows of every transform forecast a row, each mapped back through the inverse of
+its transform (ForecastCfg(M, S, 'all'): mcd_stream_forecast_group_tta, one store wave per window of every transform).
 --latent-score-space pose (a latent config): the stage-1 decoder is loaded as eval_MoCoDAD.py loads it (--random-init: a seeded one
 sharing the module's frozen tensors), the tick's scoring call is LatentPoseScorer.score (mcd_latent_score_pose: + the unproject,
 decode, aggregate and maps launches), and the baseline is that call alone, asked for the same outputs.
@@ -103,6 +104,8 @@ def main():
     ap.add_argument("--forecasts", action="store_true", help="expected poses in every tick (Tick.forecast)")
     ap.add_argument("--forecast-method", choices=("unique", "mean", "median"), default="median")
     ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean")
+    ap.add_argument("--forecast-transforms", choices=("identity", "all"), default="identity",
+                    help="--forecasts: forecasts of transform 0 only, or of every transform mapped back (ForecastCfg(transforms=...))")
     ap.add_argument("--forecasts-out", default=None, metavar="OUT.npz", help="--forecasts: write the rows of the warm-up replay")
     ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
                     help="latent model (overrides the YAML's latent_score_space): 'pose' loads the stage-1 decoder as eval_MoCoDAD.py "
@@ -188,7 +191,7 @@ def main():
         raise SystemExit("--forecasts-out needs --forecasts")
     extra = {"joint_scores": True} if cli.joint_scores else {}
     if cli.forecasts:
-        extra["forecasts"] = ForecastCfg(cli.forecast_method, cli.forecast_spread)
+        extra["forecasts"] = ForecastCfg(cli.forecast_method, cli.forecast_spread, cli.forecast_transforms)
     # the baseline asks its scoring call for what the tick's asks (PoseStream._run_group): maps, per-sample losses and poses
     base_extra = {}
     if pose_space:
@@ -300,7 +303,7 @@ def main():
            "windows_total": int(sum(counts)), "seg_len": seg_len, "num_transform": nt, "noise_steps": int(model.noise_steps),
            "n_samples": int(model.n_generated_samples), "ring_len": ring_len or seg_len, "reps": cli.reps, "auc": auc,
            "model": "MoCoDADlatent" if latent else "MoCoDAD", "score_space": model.latent_score_space if latent else None, "clip_scores": clip_res, "joint_scores": bool(cli.joint_scores),
-           "forecasts": {"method": cli.forecast_method, "spread": cli.forecast_spread} if cli.forecasts else None,
+           "forecasts": {"method": cli.forecast_method, "spread": cli.forecast_spread, "transforms": cli.forecast_transforms} if cli.forecasts else None,
            "tick": stats(t_stream), "baseline_score_fused": stats(t_base), "device": torch.cuda.get_device_name(0)}
     if auc is not None:
         print(f"AUC: {auc:.6f}")
