@@ -89,9 +89,16 @@ def main():
     ap.add_argument("--forecast-spread", choices=("mean", "median"), default="mean",
                     help="--forecast-tracks: how the 34 per-feature standard deviations become one spread (its `std_method`)")
     ap.add_argument("--forecast-transforms", choices=("identity", "all"), default="identity",
-                    help="--forecast-tracks: which windows forecast a row -- those of transform 0 only, or those of every test-time "
+                    help="--forecast-tracks / --forecast-fan: which windows forecast a row -- those of transform 0 only, or those of every test-time "
                          "transform, each forecast mapped back through the inverse of its transform (more forecasts per row: larger "
                          "counts, nothing else changes in the output)")
+    ap.add_argument("--forecast-fan", type=str, default=None, metavar="OUT.npz",
+                    help="pose model, or the latent model scoring in pose space; one process: also write, per trajectory row, the "
+                         "distribution of ALL generated futures covering the row (every sample of every covering window) -- quantile "
+                         "bands in image pixels and in normalised coordinates, mean, standard deviation, and where the observed "
+                         "coordinate falls among them (mid-rank in [0, 1]); works with every aggregation strategy but 'random'")
+    ap.add_argument("--forecast-levels", type=str, default="0.1,0.5,0.9", metavar="Q,Q,...",
+                    help="--forecast-fan: 1 .. 8 quantile levels in [0, 1], strictly ascending")
     ap.add_argument("--latent-score-space", choices=("latent", "pose"), default=None,
                     help="latent model, stage 'diffusion' (overrides the YAML's latent_score_space): 'pose' decodes the generated "
                          "latents with the stage-1 decoder of pretrained_model_ckpt_path and scores the forecasts as the pose model does")
@@ -111,6 +118,8 @@ def main():
         if getattr(args, "aggregation_strategy", "best") in ("all", "random") or "random" in str(args.conditioning_strategy):
             raise SystemExit("eval_MoCoDAD.py: --joint-scores needs one map per window with the same forecast frames under every "
                              "transform: not aggregation_strategy all / random, not the random_imp strategy")
+    if cli.forecast_tracks and cli.forecast_fan:
+        raise SystemExit("eval_MoCoDAD.py: --forecast-tracks and --forecast-fan are separate runs")
     if cli.forecast_tracks:      # (refusals by name, before any GPU call)
         aggr = str(getattr(args, "aggregation_strategy", "best"))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -136,8 +145,29 @@ def main():
                 forecast_cover = forecast_max_cover(args.num_transform, per_window, "all")
             except ValueError as e:
                 raise SystemExit(f"eval_MoCoDAD.py: --forecast-transforms all: {e}") from None
+    elif cli.forecast_fan:      # (refusals by name, before any GPU call)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-fan runs in one process (the forecasts are not gathered across ranks)")
+        if model_cls is not MoCoDAD and not pose_space:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-fan needs the pose model, or the latent model with latent_score_space: 'pose' "
+                             "(in latent space the model forecasts a latent code, not a pose)")
+        if cli.joint_scores:
+            raise SystemExit("eval_MoCoDAD.py: --forecast-fan and --joint-scores are separate runs")
+        if str(getattr(args, "aggregation_strategy", "best")) == "random":
+            raise SystemExit("eval_MoCoDAD.py: --forecast-fan: not aggregation_strategy 'random' (it keeps no record of the sample it drew)")
+        from types import SimpleNamespace
+        from mocodad_amd.engine import forecast_levels
+        from mocodad_amd.utils.eval_utils import forecast_fan_cover, forecast_max_cover
+        try:
+            fan_levels = forecast_levels([float(q) for q in cli.forecast_levels.split(",") if q.strip()], "--forecast-levels")
+            split = SimpleNamespace(n_frames=args.seg_len, conditioning_indices=args.conditioning_indices,
+                                    conditioning_strategy=MoCoDAD.conditioning_strategies.get(args.conditioning_strategy, args.conditioning_strategy))
+            per_window = args.seg_len if split.conditioning_strategy == "random_imp" else len(MoCoDAD._frame_split(split)[1])
+            forecast_cover = forecast_fan_cover(args.n_generated_samples, forecast_max_cover(args.num_transform, per_window, cli.forecast_transforms))
+        except ValueError as e:
+            raise SystemExit(f"eval_MoCoDAD.py: --forecast-fan: {e}") from None
     elif cli.forecast_transforms != "identity":
-        raise SystemExit("eval_MoCoDAD.py: --forecast-transforms goes with --forecast-tracks")
+        raise SystemExit("eval_MoCoDAD.py: --forecast-transforms goes with --forecast-tracks or --forecast-fan")
     pretrain = bool(getattr(model_cls, "is_pretrain", False))
     if pretrain and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("eval_MoCoDAD.py: stage 'pretrain' runs in one process (its result is one mean over all windows, not gathered scores)")
@@ -234,6 +264,15 @@ def main():
                 model._test_output_list.append(out[:1] + out[2:])
                 forecasts.append(out[1])
                 forecast_frames.append(model.map_frames(kw.get("cond_mask"), n_b))
+            elif cli.forecast_fan:      # test_step with EVERY sample of the batch's windows beside its output
+                n_b, kw = int(batch[1].shape[0]), {}
+                if model.conditioning_strategy == "random_imp":      # drawn here, as for --forecast-tracks
+                    kw["cond_mask"] = model.random_imp_masks(n_b, model._calls) if model.random_imp_draw == "device" \
+                        else model.draw_random_imp_mask(n_b)
+                out = model.forward(batch, return_samples=True, **kw)
+                model._test_output_list.append(out[:-2])
+                forecasts.append(out[-2])
+                forecast_frames.append(out[-1])
             elif cli.joint_scores:      # test_step with the error maps of the batch's windows beside its output
                 out = model.forward(batch, return_maps=True)
                 model._test_output_list.append(out[:-2])
@@ -285,6 +324,37 @@ def main():
             print(f"forecast tracks: {len(rows)} trajectory rows, {int((res['count'] > 0).sum())} with a forecast ({cli.forecast_method}, spread "
                   f"{cli.forecast_spread}) -> {cli.forecast_tracks}  {time.perf_counter() - t2:.3f}s"
                   + ("" if "expected" in res else "  (synthetic clips have no pixel rows: expected_norm only, no observed / expected)"))
+        if cli.forecast_fan:
+            import numpy as np
+            from mocodad_amd._lib import JOINT_NAMES
+            from mocodad_amd.engine import denormalize_poses, forecast_fan
+            from mocodad_amd.utils.eval_utils import forecast_fan_rows, forecast_observed_rows
+            t2 = time.perf_counter()
+            src = dict(windows=tw) if tw is not None else dict(meta=meta.numpy(), frames=frames.numpy(), data=data)
+            poses_all = torch.cat(forecasts)
+            quant, mean, std, rank, count, rows, frame_ids = forecast_fan_rows(
+                poses_all, trans.numpy(), torch.cat(forecast_frames).cpu().numpy(), forecast_fan, levels=fan_levels,
+                max_cover=forecast_cover, transforms=cli.forecast_transforms, num_transform=args.num_transform, **src)
+            observed = forecast_observed_rows(trans.numpy(), **src)      # (R,2,17) as the fan was given them
+            obs_norm = observed.reshape(len(rows), 2, 17).transpose(1, 2).reshape(len(rows), 34).cpu().numpy()      # interleaved x1,y1,...
+            res = dict(rows=rows, row_columns=np.asarray(["scene", "clip", "person"]), frames=frame_ids, levels=np.asarray(fan_levels),
+                       observed_norm=obs_norm, bands_norm=quant.cpu().numpy(), mean_norm=mean.cpu().numpy(), std_norm=std.cpu().numpy(),
+                       rank=rank.cpu().numpy(), count=count.cpu().numpy(), n_samples=np.int64(poses_all.shape[1]),
+                       joint_names=np.asarray(JOINT_NAMES))
+            if getattr(tw, "raw", None) is not None:      # a dataset: row r of the buffer is CSV row r, each level back to its pixels
+                res["observed"] = tw.raw.poses
+                res["bands"] = np.stack([denormalize_poses(quant[l], tw.raw.poses, tw.vid_res, *tw.scaler, count=count).cpu().numpy()
+                                         for l in range(len(fan_levels))])
+            np.savez(cli.forecast_fan, **res)
+            has = res["count"] > 0
+            lo, hi, ob = res["bands_norm"][0][has], res["bands_norm"][-1][has], obs_norm[has]
+            outside = ((ob < lo) | (ob > hi)).any(axis=1)
+            print(f"forecast fan: {len(rows)} trajectory rows, {int(has.sum())} with a forecast, "
+                  f"{100.0 * float(outside.mean()) if len(outside) else 0.0:.1f}% of those with a coordinate outside "
+                  f"[{fan_levels[0]:g}, {fan_levels[-1]:g}]; {poses_all.shape[1]} samples per window, "
+                  f"{poses_all.numel() * poses_all.element_size()} device bytes held for poses_all -> {cli.forecast_fan}  "
+                  f"{time.perf_counter() - t2:.3f}s"
+                  + ("" if "bands" in res else "  (synthetic clips have no pixel rows: the _norm outputs only, no observed / bands)"))
     if use_dist:
         dist.destroy_process_group()
 

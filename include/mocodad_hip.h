@@ -398,6 +398,43 @@ int mcd_forecast_assemble_view(const float* poses, const int32_t* cell, const in
                                int32_t spread_method, int32_t max_cover, int32_t* workspace, float* pose_out, int32_t* count_out,
                                float* spread_out, void* stream);
 
+/* Forecast fan: the distribution of ALL generated futures of a cell (added without a change of MCD_ABI_VERSION: one new export and two
+ * constants, nothing existing touched).  Where mcd_forecast_assemble[_view] combines ONE selected forecast per covering pair, this
+ * entry takes every sample of every covering pair and gives, per cell and coordinate, quantile bands, mean and standard deviation of
+ * them all, and where the observed coordinate falls among them.
+ *   poses_all    (N, S, 2, Tx, 17) f32: every sample of every window (pose_out of mcd_score, the poses of mcd_latent_decode_samples)
+ *   cell, trans, inv_affine, n_transform, max_cover, workspace: exactly as in mcd_forecast_assemble_view (trans NULL: no map, max_cover
+ *                1 .. 32; else 1 .. 64); the pairs of a cell are claimed by the same kernels and ordered by ascending pair index
+ *   levels       HOST pointer: n_levels in 1 .. 8 (MCD_FORECAST_FAN_LEVELS) doubles in [0, 1], strictly ascending; read before the
+ *                launch (they travel in the kernel's parameter block)
+ *   observed     (n_cells, 2, 17) f32, the frame-major layout of mcd_window_view_t's buffer (a trajectory buffer can be passed as it
+ *                lies), or NULL together with rank_out
+ * The VALUE LIST of a cell and feature: for each of its k pairs in ascending pair index the samples s = 0 .. S-1 in order -- K = k S
+ * values, each first mapped back by the rule of mcd_forecast_assemble_view when trans is given.  Outputs, all written for every cell by
+ * the callee, every operation a float64 operation, unfused, rounded to fp32 once on store:
+ *   count_out    (n_cells,) i32: k
+ *   mean_out, std_out   (n_cells, 34) f32 interleaved x1,y1,...: the sum in list order / K, then sqrt(sum((x - mean)^2) / K) in a second
+ *                pass (the definitions of mcd_forecast_assemble's spread)
+ *   quant_out    (n_levels, n_cells, 34) f32, level-major: each level is an (n_cells, 34) block mcd_denormalize_poses takes as it is.
+ *                With x the list sorted ascending, ties by list position (-0.0 == +0.0; np.sort(kind='stable')) and a level q:
+ *                h = q (K - 1), i = floor(h), g = h - i; the value is x[i] when g == 0, else (1 - g) x[i] + g x[i + 1].  (q = 0.5 is
+ *                np.median's half-sum; with S = 1 it is MCD_FORECAST_MEDIAN bit for bit.)
+ *   rank_out     (n_cells, 34) f32: (below + equal / 2) / K, below = #{x < observed}, equal = #{x == observed} over the list
+ * k = 0: every output of the cell is 0.  k > max_cover or K > 1024 (MCD_FORECAST_FAN_VALUES): count_out carries k, every other output
+ * of the cell is NaN.  A NaN among a feature's values makes that feature's outputs NaN and no others (under a transform that is no
+ * identity row a NaN reaches both coordinates of its joint, as in mcd_forecast_assemble_view); a NaN observed makes only its rank NaN.
+ * The result depends neither on the order in which workgroups claim list slots nor on the workspace's prior contents.  One workgroup
+ * per cell sorts (value, list position) keys in LDS, the joints in groups.  Two launches and one memset.  Argument errors -- those of
+ * mcd_forecast_assemble_view, n_samples < 1, n_levels outside 1 .. 8, a level outside [0, 1] or not above its predecessor, observed
+ * and rank_out not both NULL or both non-NULL -- are MCD_EINVAL before any device call; n_cells == 0 is MCD_OK and launches nothing,
+ * n == 0 zeroes the outputs. */
+#define MCD_FORECAST_FAN_VALUES 1024
+#define MCD_FORECAST_FAN_LEVELS 8
+int mcd_forecast_fan(const float* poses_all, const int32_t* cell, const int32_t* trans, const double* inv_affine, int32_t n_transform,
+                     int64_t n, int32_t n_samples, int32_t n_corrupt, int32_t n_cells, const double* levels, int32_t n_levels,
+                     int32_t max_cover, const float* observed, int32_t* workspace, float* quant_out, float* mean_out, float* std_out,
+                     float* rank_out, int32_t* count_out, void* stream);
+
 /* The inverse of mcd_normalize_poses: norm (n, 34) f32 interleaved (what mcd_forecast_assemble writes) back to image pixels in the
  * bounding box of raw (n, 34) f32, the observed CSV row of the same person and frame -> out (n, 34) f32 interleaved.
  * The box L, R, T, B is computed exactly as mcd_normalize_poses computes it (fp32 margin, clip, round-half-even); per element k,

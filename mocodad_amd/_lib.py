@@ -9,6 +9,8 @@ LIB_PATH = os.environ.get("MCD_LIB", os.path.join(_HERE, "libmocodad_hip.so"))  
 MCD_MAX_FRAMES = 32
 MCD_MAX_COND_LAYERS = 8
 MCD_FORECAST_VIEW_COVER = 64     # pairs on a forecast cell with every transform (mcd_forecast_assemble_view, the stream's tta state)
+MCD_FORECAST_FAN_VALUES = 1024   # values k * S the list of a cell's feature may hold (mcd_forecast_fan)
+MCD_FORECAST_FAN_LEVELS = 8      # quantile levels of one mcd_forecast_fan call
 
 STRATEGY = {"inject": 0, "concat": 1, "no_condition": 2, "inbetween_imp": 3, "random_imp": 4}
 LOSS = {"smooth_l1": 0, "l1": 1, "mse": 2}
@@ -120,6 +122,9 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_forecast_assemble_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mcd_forecast_fan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "mcd_denormalize_poses": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "mcd_stream_flush": (C.c_int, [C.POINTER(StreamState), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

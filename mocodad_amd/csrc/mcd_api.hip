@@ -753,6 +753,61 @@ int mcd_forecast_assemble_view(const float* poses, const int32_t* cell, const in
     return MCD_OK;
 }
 
+int mcd_forecast_fan(const float* poses_all, const int32_t* cell, const int32_t* trans, const double* inv_affine,
+                     int32_t n_transform, int64_t n, int32_t n_samples, int32_t n_corrupt, int32_t n_cells, const double* levels,
+                     int32_t n_levels, int32_t max_cover, const float* observed, int32_t* workspace, float* quant_out, float* mean_out,
+                     float* std_out, float* rank_out, int32_t* count_out, void* stream) {
+    const int cover_max = trans ? MCD_FORECAST_VIEW_COVER : MCD_MAX_FRAMES;
+    if (n < 0 || n_cells < 0) return fail(MCD_EINVAL, "need n, n_cells >= 0");
+    if (n_corrupt < 1 || n_corrupt > MCD_MAX_FRAMES) return fail(MCD_EINVAL, "need 1 <= n_corrupt <= 32");
+    if (max_cover < 1 || max_cover > cover_max) return fail(MCD_EINVAL, trans ? "need 1 <= max_cover <= 64" : "need 1 <= max_cover <= 32");
+    if (n_samples < 1) return fail(MCD_EINVAL, "need n_samples >= 1");
+    if (n > 0x7fffffffll / n_corrupt) return fail(MCD_EINVAL, "n x n_corrupt exceeds 2^31 - 1: assemble in smaller batches");
+    if (trans && !inv_affine) return fail(MCD_EINVAL, "trans needs inv_affine, the inverse table of its transforms");
+    if (trans && n_transform < 1) return fail(MCD_EINVAL, "need n_transform >= 1");
+    if (n_levels < 1 || n_levels > MCD_FORECAST_FAN_LEVELS) return fail(MCD_EINVAL, "need 1 <= n_levels <= 8");
+    if (!levels) return fail(MCD_EINVAL, "null argument");
+    for (int l = 0; l < n_levels; ++l) {
+        if (!(levels[l] >= 0.0 && levels[l] <= 1.0)) return fail(MCD_EINVAL, "levels outside [0, 1]");
+        if (l && !(levels[l] > levels[l - 1])) return fail(MCD_EINVAL, "levels must be strictly ascending");
+    }
+    if ((observed == nullptr) != (rank_out == nullptr)) return fail(MCD_EINVAL, "observed and rank_out go together (both NULL: no rank)");
+    if (n_cells == 0) return MCD_OK;
+    if (!workspace || !quant_out || !mean_out || !std_out || !count_out) return fail(MCD_EINVAL, "null argument");
+    if (n > 0 && (!poses_all || !cell)) return fail(MCD_EINVAL, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ForecastFanParams Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.v = ForecastViewParams{{poses_all, cell, workspace, nullptr, count_out, nullptr, (int)(n * n_corrupt), n_corrupt, n_cells, 0, 0, max_cover},
+                             trans, inv_affine, n_transform};
+    Q.observed = observed; Q.quant_out = quant_out; Q.mean_out = mean_out; Q.std_out = std_out; Q.rank_out = rank_out;
+    for (int l = 0; l < n_levels; ++l) Q.levels[l] = levels[l];
+    Q.n_samples = n_samples; Q.n_levels = n_levels;
+    HIP_TRY(hipMemsetAsync(count_out, 0, (size_t)n_cells * sizeof(int32_t), st));
+    if (n == 0) {      // nothing forecasts anything: the empty result, without a launch
+        const size_t plane = (size_t)n_cells * 34 * sizeof(float);
+        HIP_TRY(hipMemsetAsync(quant_out, 0, plane * n_levels, st));
+        HIP_TRY(hipMemsetAsync(mean_out, 0, plane, st));
+        HIP_TRY(hipMemsetAsync(std_out, 0, plane, st));
+        if (rank_out) HIP_TRY(hipMemsetAsync(rank_out, 0, plane, st));
+        return MCD_OK;
+    }
+    // the longest list a cell of this launch reduces -> the stride of its keys, and the joints 60 KB of LDS hold at that stride
+    const long long most = (long long)max_cover * n_samples;
+    Q.kp = 1;
+    while (Q.kp < most && Q.kp < MCD_FORECAST_FAN_VALUES) Q.kp <<= 1;
+    Q.jg = 17;
+    while (Q.jg > 1 && forecast_fan_lds_bytes(Q.kp, Q.jg) > (size_t)FORECAST_FAN_LDS) --Q.jg;
+    const dim3 claim_grid((unsigned)((Q.v.f.n_pairs + 255ll) / 256));
+    if (trans) hipLaunchKernelGGL(forecast_claim_view_kernel, claim_grid, dim3(256), 0, st, Q.v);
+    else hipLaunchKernelGGL(forecast_claim_kernel, claim_grid, dim3(256), 0, st, Q.v.f);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(forecast_fan_kernel, dim3(n_cells < 65536 ? n_cells : 65536), dim3(FORECAST_FAN_THREADS),
+                       forecast_fan_lds_bytes(Q.kp, Q.jg), st, Q);
+    HIP_TRY(hipGetLastError());
+    return MCD_OK;
+}
+
 int64_t mcd_frame_scores_workspace_bytes(const mcd_frame_cfg_t* c) {
     if (!c || c->n_clips <= 0 || c->num_transform <= 0 || c->n_persons <= 0 || c->max_frames <= 0) return 0;
     const int64_t rows = (int64_t)c->num_transform * c->n_clips * c->n_persons;

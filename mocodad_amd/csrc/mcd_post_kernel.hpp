@@ -11,6 +11,8 @@
 //                               (mcd_forecast_assemble)                                         utils/eval_utils.py:13-24,37-72
 //   forecast_claim_view / forecast_reduce_view kernels   the same over the windows of EVERY test-time transform, each forecast
 //                               mapped back by inverse_affine_coord (mcd_forecast_assemble_view)
+//   forecast_fan_kernel         behind the same claim kernels: quantile bands, mean, deviation and observed mid-rank over ALL
+//                               samples of the pairs covering a cell (mcd_forecast_fan)
 //   philox_noise / random_imp_masks kernels   the perf mode's draws, exported (mcd_philox_noise, mcd_random_imp_masks)
 //   gather_frames_kernel        the dense copy of the condition frames cond_encode_kernel reads
 //   poison_lds_kernel           test aid (mcd_debug_poison_lds)
@@ -527,6 +529,175 @@ __global__ __launch_bounds__(64) void forecast_reduce_view_kernel(const Forecast
         const float* p = F.poses + ((size_t)i * 2 * F.Tx + tx) * 17 + (f >> 1);      // a claimed pair's transform is in the table
         return inverse_affine_coord(V.inv + 6 * V.trans[i], p[0], p[(size_t)F.Tx * 17], f & 1);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Forecast fan (mcd_forecast_fan): per cell and feature the distribution of ALL S samples of every covering pair -- quantile bands,
+// mean, standard deviation and the mid-rank of the observed coordinate.  The pairs are claimed by forecast_claim_kernel /
+// forecast_claim_view_kernel as they are; then one 256-lane workgroup per cell:
+//   - the claimed pair indices are ordered by rank counting (k <= 64), as forecast_reduce_cells orders them;
+//   - the 17 joints are walked in groups of `jg` (the launcher's choice: what 60 KB of LDS hold at the launch's largest list).  Per
+//     group the K = k * S values of each feature are staged in list order (vals, row stride kp + 1 words: in the summing pass below
+//     lane f walks row f, and the odd stride puts the lanes on banks of their own) beside one 64-bit key per value, (order-preserving
+//     image of the value) << 32 | list position, padded to the cell's power of two with all-ones keys (keys, row stride kp: the
+//     lanes of a sort stage take consecutive positions of a row, never one position of many rows, so this stride needs no pad);
+//   - one lane per feature sums in list order (mean, two-pass deviation, NaN flag) -- float64, unfused.  At most 34 of the 256
+//     lanes work in this pass, 2 K dependent additions each, while the others wait at the next barrier: the definition fixes the
+//     order of the sum, not who computes it, and overlapping this pass with the sort is open;
+//   - a bitonic network sorts each feature's keys: the keys are distinct, so ANY network gives the stable order (ties by position;
+//     -0.0 and +0.0 share an image and a NaN feature's order is never read);
+//   - one lane per (feature, level) interpolates between two sorted values, read from `vals` through the key's position (a -0.0
+//     keeps its sign); one lane per feature finds the observed coordinate's rank by two lower bounds in the sorted keys.
+// Everything a lane indexes at run time lives in LDS or global memory: no per-thread array, no scratch.
+// ------------------------------------------------------------------------------------------------
+constexpr int FORECAST_FAN_VALUES = MCD_FORECAST_FAN_VALUES;
+constexpr int FORECAST_FAN_LEVELS = MCD_FORECAST_FAN_LEVELS;
+constexpr int FORECAST_FAN_THREADS = 256;
+constexpr int FORECAST_FAN_LDS = 60 * 1024;      // dynamic LDS of a launch, at most (with the static lists: inside 64 KB)
+struct ForecastFanParams {
+    ForecastViewParams v;                     // f.poses: (N, S, 2, Tx, 17); f.count_out: the claimed counts; v.trans == nullptr: no map
+    const float* observed;                    // (n_cells, 2, 17) frame-major, or nullptr with rank_out
+    float* quant_out; float* mean_out; float* std_out; float* rank_out;
+    double levels[FORECAST_FAN_LEVELS];
+    int n_samples, n_levels;
+    int kp, jg;                               // row stride of the keys (a power of two >= every list the launch reduces); joints per group
+};
+// bytes of dynamic LDS for groups of jg joints at key stride kp: per feature kp keys and kp + 1 staged values
+__host__ __device__ constexpr size_t forecast_fan_lds_bytes(int kp, int jg) {
+    return (size_t)2 * jg * ((size_t)kp * sizeof(unsigned long long) + (size_t)(kp + 1) * sizeof(float));
+}
+// fp32 -> u32 whose unsigned order is the order of the values, -0.0 == +0.0; every non-NaN image is below 0xffffffff
+__device__ __forceinline__ unsigned forecast_fan_image(float x) {
+    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// the first position of the ascending keys[0 .. n) that is not below `key`
+__device__ __forceinline__ int forecast_fan_lower_bound(const unsigned long long* keys, int n, unsigned long long key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(FORECAST_FAN_THREADS) void forecast_fan_kernel(const ForecastFanParams Q) {
+#pragma clang fp contract(off)      // (1 - g) x[i] + g x[i + 1] and sum((x - mean)^2): products, then sums -- never an FMA
+    extern __shared__ unsigned long long fan_lds[];
+    __shared__ int claimed[FORECAST_VIEW_COVER], ordered[FORECAST_VIEW_COVER];
+    __shared__ int fnan[34];                  // per feature of the group: a NaN among its values
+    const ForecastParams& F = Q.v.f;
+    const int tid = threadIdx.x, S = Q.n_samples, kp = Q.kp, vstride = kp + 1, nl = Q.n_levels;
+    unsigned long long* keys = fan_lds;                                            // [2 jg][kp]
+    float* vals = reinterpret_cast<float*>(fan_lds + (size_t)2 * Q.jg * kp);      // [2 jg][kp + 1]
+    for (int c = blockIdx.x; c < F.n_cells; c += gridDim.x) {
+        const int k = F.count_out[c];
+        const int K = k > 0 && k <= F.max_cover && (long long)k * S <= FORECAST_FAN_VALUES ? k * S : 0;
+        if (K == 0) {                              // no forecast: zeros; more pairs or values than a list holds: NaN (count_out says how many)
+            const float v = k <= 0 ? 0.f : __builtin_nanf("");
+            if (tid < 34) {
+                const size_t o = (size_t)c * 34 + tid;
+                Q.mean_out[o] = v;
+                Q.std_out[o] = v;
+                if (Q.rank_out) Q.rank_out[o] = v;
+                for (int l = 0; l < nl; ++l) Q.quant_out[(size_t)l * F.n_cells * 34 + o] = v;
+            }
+            continue;
+        }
+        int Kp = 1;
+        while (Kp < K) Kp <<= 1;                   // <= kp
+        const int half = Kp >> 1, lg_half = half ? __builtin_ctz(half) : 0;
+        __syncthreads();                           // the previous cell's readers are done with the lists
+        if (tid < k) claimed[tid] = F.list[(size_t)c * F.max_cover + tid];
+        __syncthreads();
+        if (tid < k) {                             // pair indices are distinct: the ranks are a permutation of 0 .. k-1
+            const int mine = claimed[tid];
+            int r = 0;
+            for (int m = 0; m < k; ++m) r += claimed[m] < mine ? 1 : 0;
+            ordered[r] = mine;
+        }
+        for (int j0 = 0; j0 < 17; j0 += Q.jg) {
+            const int nj = 17 - j0 < Q.jg ? 17 - j0 : Q.jg, nf = 2 * nj;
+            __syncthreads();                       // `ordered` is complete; the previous group's readers are done with keys / vals
+            for (int e = tid; e < nj * K; e += FORECAST_FAN_THREADS) {      // stage: list position p of joint j0 + jj, x and y
+                const int jj = e / K, p = e - jj * K, j = p / S, s = p - j * S, pair = ordered[j], i = pair / F.Tx, tx = pair - i * F.Tx;
+                const float* ptr = F.poses + ((((size_t)i * S + s) * 2) * F.Tx + tx) * 17 + (j0 + jj);
+                float x = ptr[0], y = ptr[(size_t)F.Tx * 17];
+                if (Q.v.trans) {                   // a claimed pair's transform is in the table
+                    const double* m = Q.v.inv + 6 * Q.v.trans[i];
+                    const float xp = x, yp = y;
+                    x = inverse_affine_coord(m, xp, yp, 0);
+                    y = inverse_affine_coord(m, xp, yp, 1);
+                }
+                vals[(2 * jj) * vstride + p] = x;
+                vals[(2 * jj + 1) * vstride + p] = y;
+                keys[(size_t)(2 * jj) * kp + p] = ((unsigned long long)forecast_fan_image(x) << 32) | (unsigned)p;
+                keys[(size_t)(2 * jj + 1) * kp + p] = ((unsigned long long)forecast_fan_image(y) << 32) | (unsigned)p;
+            }
+            for (int e = tid; e < nf * (Kp - K); e += FORECAST_FAN_THREADS) {      // the padding sorts behind every value
+                const int f = e / (Kp - K), p = K + (e - f * (Kp - K));
+                keys[(size_t)f * kp + p] = ~0ull;
+            }
+            __syncthreads();
+            if (tid < nf) {                        // mean and deviation in list order (forecast_reduce_staged's definitions)
+                const float* x = vals + tid * vstride;
+                double sum = 0.0;
+                bool nan = false;
+                for (int p = 0; p < K; ++p) {
+                    const float xv = x[p];
+                    nan |= xv != xv;
+                    sum += (double)xv;
+                }
+                const double mean = sum / (double)K;
+                double ss = 0.0;
+                for (int p = 0; p < K; ++p) {
+                    const double d = (double)x[p] - mean;
+                    ss += d * d;
+                }
+                const size_t o = (size_t)c * 34 + 2 * j0 + tid;
+                Q.mean_out[o] = (float)mean;
+                Q.std_out[o] = (float)sqrt(ss / (double)K);
+                fnan[tid] = nan ? 1 : 0;
+            }
+            for (int size = 2; size <= Kp; size <<= 1)                             // bitonic network on every feature's Kp keys
+                for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                    for (int e = tid; e < nf * half; e += FORECAST_FAN_THREADS) {
+                        const int f = e >> lg_half, t = e & (half - 1), lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                        unsigned long long* row = keys + (size_t)f * kp;
+                        const unsigned long long a = row[lo], b = row[hi];
+                        if ((a > b) == ((lo & size) == 0)) { row[lo] = b; row[hi] = a; }
+                    }
+                    __syncthreads();
+                }
+            __syncthreads();                       // (K == 1: no stage ran; fnan is visible either way)
+            for (int e = tid; e < nf * (nl + 1); e += FORECAST_FAN_THREADS) {
+                const int f = e / (nl + 1), l = e - f * (nl + 1);
+                const unsigned long long* row = keys + (size_t)f * kp;
+                const float* x = vals + f * vstride;
+                const size_t o = (size_t)c * 34 + 2 * j0 + f;
+                if (l < nl) {                      // level l: h = q (K - 1), between the sorted values floor(h) and floor(h) + 1
+                    double q = Q.levels[0];
+#pragma unroll
+                    for (int m = 1; m < FORECAST_FAN_LEVELS; ++m) q = l == m ? Q.levels[m] : q;      // (no lane-indexed kernel argument)
+                    const double h = q * (double)(K - 1), fl = floor(h), g = h - fl;
+                    const int i = (int)fl;
+                    double v = (double)x[(unsigned)row[i]];
+                    if (g != 0.0) {
+                        const double a = (1.0 - g) * v, b = g * (double)x[(unsigned)row[i + 1]];
+                        v = a + b;
+                    }
+                    Q.quant_out[(size_t)l * F.n_cells * 34 + o] = fnan[f] ? __builtin_nanf("") : (float)v;
+                } else if (Q.rank_out) {           // (below + equal / 2) / K of the observed coordinate
+                    const float obs = Q.observed[(size_t)c * 34 + (size_t)(f & 1) * 17 + j0 + (f >> 1)];
+                    const unsigned long long img = (unsigned long long)forecast_fan_image(obs) << 32;
+                    const int below = forecast_fan_lower_bound(row, K, img);
+                    const int upto = forecast_fan_lower_bound(row, K, img + (1ull << 32));
+                    const double r = ((double)below + (double)(upto - below) / 2.0) / (double)K;
+                    Q.rank_out[o] = (fnan[f] || obs != obs) ? __builtin_nanf("") : (float)r;
+                }
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -959,6 +959,107 @@ def forecast_assemble(poses: torch.Tensor, cell: torch.Tensor, n_cells: int, *, 
     return o_pose, o_count, o_spread
 
 
+def forecast_levels(levels, name: str = "levels") -> Tuple[float, ...]:
+    """The quantile levels of a forecast fan as floats: 1 .. 8 (MCD_FORECAST_FAN_LEVELS) values in [0, 1], strictly ascending."""
+    try:
+        lv = tuple(float(q) for q in levels)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a sequence of numbers, got {levels!r}") from None
+    if not 1 <= len(lv) <= _lib.MCD_FORECAST_FAN_LEVELS:
+        raise ValueError(f"{name} must hold 1 .. {_lib.MCD_FORECAST_FAN_LEVELS} values, got {len(lv)}")
+    if not all(0.0 <= q <= 1.0 for q in lv):
+        raise ValueError(f"{name} must lie in [0, 1], got {lv}")
+    if any(b <= a for a, b in zip(lv, lv[1:])):
+        raise ValueError(f"{name} must be strictly ascending, got {lv}")
+    return lv
+
+
+def forecast_fan(poses_all: torch.Tensor, cell: torch.Tensor, n_cells: int, *, levels=(0.1, 0.5, 0.9), observed: Optional[torch.Tensor] = None,
+                 max_cover: int = _lib.MCD_MAX_FRAMES, trans: Optional[torch.Tensor] = None, inv_affine=None, device=None, out=None,
+                 workspace: Optional[torch.Tensor] = None):
+    """mcd_forecast_fan: the distribution of ALL generated futures of a cell.  poses_all (N,S,2,Tx,17): every sample of every
+    window (HipScorer.score's poses, forward(return_samples=True)); cell (N,Tx), max_cover, trans, inv_affine, workspace: as for
+    forecast_assemble.  The value list of a cell's feature holds the S samples of each of its k covering pairs in ascending pair
+    index, K = k * S values (at most 1024), mapped back when trans is given.  levels: 1 .. 8 quantile levels in [0, 1], strictly
+    ascending.  observed (n_cells,2,17) fp32 in the trajectory buffer's frame-major layout (TrajectoryWindows.buffer viewed so), or
+    None: no rank.
+    -> (quant (n_levels, n_cells, 34) fp32, level-major, interleaved x1,y1,...; mean, std (n_cells, 34) fp32; rank (n_cells, 34)
+    fp32 = (below + equal / 2) / K of the observed coordinate, or None; count (n_cells,) int32 = k).  A cell nobody forecasts is 0
+    with count 0; one with k > max_cover or K > 1024 is NaN with its true count.  out: the caller's five buffers (the fourth None
+    without `observed`) instead of new ones.  Asynchronous on the current stream; arguments are checked before anything touches the
+    device."""
+    lv = forecast_levels(levels)
+    max_cover, n_cells = int(max_cover), int(n_cells)
+    if (trans is None) != (inv_affine is None):
+        raise ValueError("trans and inv_affine go together (both None = no transforms)")
+    cover_max = _lib.MCD_MAX_FRAMES if trans is None else _lib.MCD_FORECAST_VIEW_COVER
+    if not 1 <= max_cover <= cover_max:
+        raise ValueError(f"max_cover must be in 1 .. {cover_max}, got {max_cover}")
+    if n_cells < 0:
+        raise ValueError(f"n_cells must be >= 0, got {n_cells}")
+    if poses_all.dim() != 5 or poses_all.shape[1] < 1 or poses_all.shape[2] != 2 or poses_all.shape[4] != 17 \
+            or not 1 <= poses_all.shape[3] <= _lib.MCD_MAX_FRAMES:
+        raise ValueError(f"poses_all must have shape (N, S, 2, Tx, 17) with S >= 1 and 1 <= Tx <= {_lib.MCD_MAX_FRAMES}, got {tuple(poses_all.shape)}")
+    N, S, Tx = int(poses_all.shape[0]), int(poses_all.shape[1]), int(poses_all.shape[3])
+    if tuple(cell.shape) != (N, Tx) or cell.dtype.is_floating_point:
+        raise ValueError(f"cell must be an integer ({N}, {Tx}) tensor, got {tuple(cell.shape)} {cell.dtype}")
+    if N * Tx > 2**31 - 1:
+        raise ValueError("N x Tx exceeds 2^31 - 1: assemble in smaller batches")
+    if trans is not None:
+        if tuple(trans.shape) != (N,) or trans.dtype.is_floating_point:
+            raise ValueError(f"trans must be an integer ({N},) tensor, got {tuple(trans.shape)} {trans.dtype}")
+        if not torch.is_tensor(inv_affine):      # (a list through torch.as_tensor would pass through float32)
+            inv_affine = torch.from_numpy(np.ascontiguousarray(inv_affine, dtype=np.float64))
+        if inv_affine.dim() != 2 or inv_affine.shape[0] < 1 or inv_affine.shape[1] != 6:
+            raise ValueError(f"inv_affine must be (n_transform, 6) with n_transform >= 1, got {tuple(inv_affine.shape)}")
+    if observed is not None and (tuple(observed.shape) != (n_cells, 2, 17) or observed.dtype != torch.float32):
+        raise ValueError(f"observed must be a float32 ({n_cells}, 2, 17) tensor, got {tuple(observed.shape)} {observed.dtype}")
+    dev = _call_device(device, poses_all)
+    if out is not None and len(out) != 5:
+        raise ValueError("out must be the five buffers (quant, mean, std, rank, count)")
+    o_quant, o_mean, o_std, o_rank, o_count = out if out is not None else (None,) * 5
+    if observed is None and o_rank is not None:
+        raise ValueError("out[3] (rank) must be None without observed")
+    o_quant = _caller_buffer("out[0] (quant)", o_quant, (len(lv), n_cells, 34), torch.float32, dev)
+    o_mean = _caller_buffer("out[1] (mean)", o_mean, (n_cells, 34), torch.float32, dev)
+    o_std = _caller_buffer("out[2] (std)", o_std, (n_cells, 34), torch.float32, dev)
+    o_rank = _caller_buffer("out[3] (rank)", o_rank, (n_cells, 34), torch.float32, dev)
+    o_count = _caller_buffer("out[4] (count)", o_count, (n_cells,), torch.int32, dev)
+    if workspace is not None and (workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.device != dev
+                                  or workspace.numel() < n_cells * max_cover):
+        raise ValueError(f"workspace must be a contiguous int32 tensor of at least n_cells x max_cover = {n_cells * max_cover} words on {dev}")
+    L = _lib.lib()
+    _need_gpu()
+    poses_all, cell = _f32c(poses_all, dev), _i32c(cell, dev)
+    c_levels = (C.c_double * len(lv))(*lv)
+    with torch.cuda.device(dev):
+        if o_quant is None:
+            o_quant = torch.empty(len(lv), n_cells, 34, device=dev, dtype=torch.float32)
+        if o_mean is None:
+            o_mean = torch.empty(n_cells, 34, device=dev, dtype=torch.float32)
+        if o_std is None:
+            o_std = torch.empty(n_cells, 34, device=dev, dtype=torch.float32)
+        if observed is not None:
+            observed = _f32c(observed, dev)
+            if o_rank is None:
+                o_rank = torch.empty(n_cells, 34, device=dev, dtype=torch.float32)
+        if o_count is None:
+            o_count = torch.empty(n_cells, device=dev, dtype=torch.int32)
+        if workspace is None:
+            workspace = torch.empty(max(n_cells * max_cover, 1), device=dev, dtype=torch.int32)
+        inv, n_t = None, 0
+        if trans is not None:
+            # (an empty tensor has no address, and a NULL trans would mean "no transforms": one word stands in, no window reads it)
+            trans = _i32c(trans, dev) if N else torch.zeros(1, device=dev, dtype=torch.int32)
+            inv = inv_affine.to(dev, torch.float64).contiguous()
+            n_t = int(inv.shape[0])
+        # (n_cells == 0: observed and rank are both empty, both without an address, and the entry returns before it reads a pointer)
+        _lib.check(L.mcd_forecast_fan(_ptr(poses_all), _ptr(cell), _ptr(trans), _ptr(inv), n_t, N, S, Tx, n_cells, c_levels, len(lv),
+                                      max_cover, _ptr(observed), _ptr(workspace), _ptr(o_quant), _ptr(o_mean), _ptr(o_std), _ptr(o_rank),
+                                      _ptr(o_count), _stream()))
+    return o_quant, o_mean, o_std, o_rank, o_count
+
+
 def denormalize_poses(norm: torch.Tensor, raw, vid_res: Sequence[float], center=None, scale=None, count: Optional[torch.Tensor] = None, *,
                       device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """mcd_denormalize_poses, the inverse of normalize_poses: norm (n, 34) fp32 in the CSV's interleaved order (what

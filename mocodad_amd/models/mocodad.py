@@ -322,7 +322,8 @@ class MoCoDAD(_Base):
     # -------------------------------------------------------------- forward
     def forward(self, input_data: List[torch.Tensor], aggr_strategy: str = None, return_: str = None, *,
                 noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,
-                cond_mask: Optional[torch.Tensor] = None, return_maps: bool = False) -> List[torch.Tensor]:
+                cond_mask: Optional[torch.Tensor] = None, return_maps: bool = False,
+                return_samples: bool = False) -> List[torch.Tensor]:
         """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or pose] + the inputs.
 
         noise (extension, keyword only): (S, max(ns-1,1), B, C, Tx, V) tensor replacing the in-kernel Philox
@@ -334,9 +335,14 @@ class MoCoDAD(_Base):
         return_maps (extension, keyword only; off: exactly the list above): two more entries at the END of the list -- maps
         (B,Tx,V), which joints and forecast frames the window's score comes from (mean_{t,v} maps[b] = loss[b] up to rounding,
         under the aggregation's own sample selection: mcd_error_maps; 'all': the per-sample maps (B,S,Tx,V)), and map_frames
-        (B,Tx) int64, the 0-based window frame index of each map row."""
-        if return_maps and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
-            raise ValueError("return_maps: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
+        (B,Tx) int64, the 0-based window frame index of each map row.
+        return_samples (extension, keyword only; off: exactly the list above): two more entries at the END of the list, behind those
+        of return_maps -- poses_all (B,S,2,Tx,V), EVERY generated sample of every window (what aggr_strategy='all' returns as its
+        pose; the input of engine.forecast_fan), and map_frames (B,Tx) as above.  The call takes the non-fused path; the loss is what
+        the aggregation gives there, under every aggregation ('mean' / 'median' included, which select no pose)."""
+        for kw_name, on in (("return_maps", return_maps), ("return_samples", return_samples)):
+            if on and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
+                raise ValueError(f"{kw_name}: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
         tensor_data, meta_out, aggr, ret, sc, window_offset, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         pose_aggr = aggr in ("all", "random", "mean_pose", "median_pose")
         want_pose = ret in ("pose", "all") or pose_aggr
@@ -350,7 +356,7 @@ class MoCoDAD(_Base):
         kw["cond_mask"] = cond_mask
         fusable = aggr in ("best", "worst", "mean", "median") or "quantile" in aggr
         maps = None
-        if fusable and not want_pose:
+        if fusable and not want_pose and not return_samples:
             # loss-only output: trajectories, condition encoder and the aggregation over the samples in ONE launch
             if return_maps:
                 loss, _, _, maps = sc.score_fused(tensor_data, aggregation=aggr, want_maps=True, **kw)
@@ -358,12 +364,14 @@ class MoCoDAD(_Base):
                 loss, _, _ = sc.score_fused(tensor_data, aggregation=aggr, **kw)
             selected_x = None
         else:
-            loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose or return_maps, **kw)
+            loss_all, poses_all = sc.score(tensor_data, want_poses=want_pose or return_maps or return_samples, **kw)
             selected_x, loss = self._aggregate(sc, tensor_data, loss_all, poses_all, aggr, want_pose, cond_mask)
             if return_maps:
                 maps = sc.error_maps(tensor_data, loss_all, poses_all, aggr, loss_fn=self.loss_name, cond_mask=cond_mask)
         out = self._pack_out_data(selected_x, loss, [tensor_data] + meta_out, return_=ret)
-        return out + [maps, self.map_frames(cond_mask, maps.shape[0])] if return_maps else out
+        if return_maps:
+            out = out + [maps, self.map_frames(cond_mask, maps.shape[0])]
+        return out + [poses_all, self.map_frames(cond_mask, poses_all.shape[0])] if return_samples else out
 
     def map_frames(self, cond_mask: Optional[torch.Tensor], n_windows: int) -> torch.Tensor:
         """(B,Tx) int64: the 0-based window frame index of each row of an error map -- the corrupt frames, for 'random_imp' the

@@ -203,7 +203,7 @@ class MoCoDADlatent(LatentStage):
 
     def forward(self, input_data: List[torch.Tensor], condition_data: torch.Tensor = None, aggr_strategy: str = 'best', *,
                 return_: str = None, noise: Optional[torch.Tensor] = None, window_offset: Optional[int] = None,
-                return_maps: bool = False, space: Optional[str] = None) -> List[torch.Tensor]:
+                return_maps: bool = False, space: Optional[str] = None, return_samples: bool = False) -> List[torch.Tensor]:
         """[data (B,C,T,V), transformation_idx, metadata, actual_frames] -> [loss and/or selected latent] + the inputs, as
         mocodad_latent.py:69-129 (`condition_data` is unused there too; `aggr_strategy` defaults to 'best', None = the module's).
 
@@ -215,7 +215,10 @@ class MoCoDADlatent(LatentStage):
         included (mean_pose / median_pose on poses); return_ 'pose' gives the selected decoded forecast (B,2,Tx,17).
         return_maps: with a decoder it implies pose space and appends maps (B,Tx,V) and map_frames (B,Tx) exactly as
         MoCoDAD.forward does (mcd_error_maps on the decoded forecasts).  Without one: NotImplementedError -- the error maps are
-        per joint and forecast frame, and a latent has no joints."""
+        per joint and forecast frame, and a latent has no joints.
+        return_samples (pose space only; off: exactly the list above): appends poses_all (B,S,2,Tx,V), every decoded sample of every
+        window (what aggr_strategy 'all' returns as its pose), and map_frames (B,Tx), behind the entries of return_maps; the call
+        runs as the sequence of engine calls, whose losses the one-call path reproduces bit for bit."""
         if return_maps and self._decoder_sd is None:
             raise NotImplementedError("MoCoDADlatent has no error maps: its loss is taken on a latent code, and a latent has no joints "
                                       "(return_maps is for the pose model, MoCoDAD -- or call load_decoder first: the stage-1 "
@@ -224,7 +227,9 @@ class MoCoDADlatent(LatentStage):
         if space == "pose":
             if self._decoder_sd is None:
                 raise RuntimeError("latent_score_space 'pose' needs the stage-1 decoder: call load_decoder first")
-            return self._forward_pose(input_data, aggr_strategy, return_, noise, window_offset, return_maps)
+            return self._forward_pose(input_data, aggr_strategy, return_, noise, window_offset, return_maps, return_samples)
+        if return_samples:
+            raise ValueError("return_samples: in latent space the model generates latent codes, not poses (space='pose' decodes them)")
         tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         loss_based = aggr in ("mean", "median") or "quantile" in aggr
         if (loss_based or aggr in ("best", "worst")) and (ret == "loss" or loss_based):
@@ -235,15 +240,16 @@ class MoCoDADlatent(LatentStage):
             selected, loss = self._aggregate_latents(lat, loss_all, z0, aggr)
         return self._pack_out_data(selected, loss, [tensor_data] + meta_out, return_=ret)
 
-    def _forward_pose(self, input_data, aggr_strategy, return_, noise, window_offset, return_maps) -> List[torch.Tensor]:
+    def _forward_pose(self, input_data, aggr_strategy, return_, noise, window_offset, return_maps, return_samples=False) -> List[torch.Tensor]:
         """forward in pose space: the chain call for the latents and cond_emb, the decoder on all samples, then the pose model's
         aggregation (and error maps) on (loss_all, pose_all) -- for the loss-based aggregations as ONE library call (pose_scorer()),
         for mean_pose / median_pose / all / random as the sequence of engine calls."""
-        if return_maps and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
-            raise ValueError("return_maps: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
+        for kw_name, on in (("return_maps", return_maps), ("return_samples", return_samples)):
+            if on and (self.aggregation_strategy if aggr_strategy is None else aggr_strategy) == "random":
+                raise ValueError(f"{kw_name}: the 'random' aggregation keeps no record of the sample it drew; use 'all' and index it")
         tensor_data, meta_out, aggr, ret, sc, _, kw = self._begin_forward(input_data, aggr_strategy, return_, noise, window_offset)
         dec = self.decoder()
-        if aggr in ("best", "worst", "mean", "median") or "quantile" in aggr:
+        if not return_samples and (aggr in ("best", "worst", "mean", "median") or "quantile" in aggr):
             # the loss-based aggregations: ONE library call (mcd_latent_score_pose), the bits of the sequence below
             r = self.pose_scorer().score(tensor_data, aggregation=aggr, want_maps=return_maps, want_selected=ret in ("pose", "all"), **kw)
             out = self._pack_out_data(r[4] if len(r) > 4 else None, r[0], [tensor_data] + meta_out, return_=ret)
@@ -252,13 +258,14 @@ class MoCoDADlatent(LatentStage):
         if hasattr(tensor_data, "as_view") and aggr in ("mean_pose", "median_pose"):
             tensor_data = tensor_data.materialize()      # the *_pose strategies compare against the windows themselves
         _, _, lat, _, cond = sc.score(tensor_data, aggregation="all", want_latents=True, want_cond=True, **kw)
-        poses_all, loss_all = dec.decode_samples(tensor_data, lat, cond, want_poses=want_pose or return_maps, loss_fn=self.loss_name)
+        poses_all, loss_all = dec.decode_samples(tensor_data, lat, cond, want_poses=want_pose or return_maps or return_samples,
+                                                 loss_fn=self.loss_name)
         selected, loss = self._aggregate(dec, tensor_data, loss_all, poses_all, aggr, want_pose)
         out = self._pack_out_data(selected, loss, [tensor_data] + meta_out, return_=ret)
-        if not return_maps:
-            return out
-        maps = dec.error_maps(tensor_data, loss_all, poses_all, aggr, loss_fn=self.loss_name)
-        return out + [maps, self.map_frames(None, maps.shape[0])]
+        if return_maps:
+            maps = dec.error_maps(tensor_data, loss_all, poses_all, aggr, loss_fn=self.loss_name)
+            out = out + [maps, self.map_frames(None, maps.shape[0])]
+        return out + [poses_all, self.map_frames(None, poses_all.shape[0])] if return_samples else out
 
     def _aggregate_latents(self, lat: torch.Tensor, loss_all: torch.Tensor, z0: torch.Tensor, aggr: str):
         """_aggregation_strategy (mocodad.py:454-520) on the (B,S,D) latents and (B,S) losses the chain launch wrote: device

@@ -168,33 +168,23 @@ def forecast_cells_aligned(base, map_frames, trans, row_stride: int = 34, transf
     return np.where((trans == 0) | _forecast_transforms(transforms), base // row_stride + mf, -1).astype(np.int32)
 
 
-def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows=None, meta=None, frames=None, method: str = "median",
-                        spread_method: str = "mean", max_cover: int = 32, transforms: str = "identity", num_transform: Optional[int] = None):
-    """Forecast tracks of a dataset (eval_MoCoDAD.py --forecast-tracks): the selected forecast of every window, poses (N,2,Tx,17)
-    (forward(return_='all')), collapsed into one expected pose per trajectory row -- per tracked person and video frame.
-    trans (N,): only windows of transform 0, the identity, contribute.  map_frames (N,Tx): the 0-based window frame index of each
-    pose row (MoCoDAD.map_frames; per window under 'random_imp').  The trajectory rows come from `windows` (a TrajectoryWindows: a
-    row is a row of its buffer, cell = base // 34 + frame index) or from meta (N,4) / frames (N,seg_len) (a row is a distinct
-    (scene, clip, person, frame id) of the transform-0 windows, in lexicographic order).  assemble: engine.forecast_assemble (or a
-    restatement of it).
-    transforms='all' (eval_MoCoDAD.py --forecast-transforms all): the windows of EVERY transform contribute -- their cells are the
-    trajectory row of their forecast frame like transform 0's, and `assemble` is also given trans= and inv_affine= (the inverse
-    table of the transforms 0 .. num_transform - 1, default max(trans) + 1, utils.transforms.inverse_affine_table), with which it
-    maps each forecast back before combining; a row's forecasts are combined transform-major in the order of the windows.  The
-    rows themselves are still those the transform-0 windows cover.  max_cover may be up to 64 then.
-    -> (pose (R,34), count (R,), spread (R,) as `assemble` returns them, rows (R,3) int64 = (scene, clip, person), frame_ids (R,)
-    int64); a row no window forecasts -- the first n_cond rows of a track under a tail forecast -- has count 0 and a zero pose."""
+def _forecast_rows_and_cells(forecast_shape, trans, map_frames, *, windows=None, meta=None, frames=None, transforms: str = "identity",
+                             num_transform: Optional[int] = None, caller: str = "forecast_track_rows"):
+    """The trajectory rows of a dataset's windows and the cell of every forecast frame, for forecast_track_rows and forecast_fan_rows;
+    forecast_shape: (N, ..., Tx, 17), the shape of the forecasts.
+    -> (cell (N,Tx) int32, table (R,4) int64 = (scene, clip, person, frame id), extra: the trans= / inv_affine= keywords of the device
+    call under transforms='all' (else empty))."""
     every = _forecast_transforms(transforms)
     trans, mf = np.asarray(trans).reshape(-1), np.asarray(map_frames, np.int64)
     if windows is not None:
         meta, frames, base = np.asarray(windows.meta), np.asarray(windows.frames), np.asarray(windows.base)
     elif meta is None or frames is None:
-        raise ValueError("forecast_track_rows needs a TrajectoryWindows or the windows' meta and frames")
+        raise ValueError(f"{caller} needs a TrajectoryWindows or the windows' meta and frames")
     else:
         meta, frames, base = np.asarray(meta), np.asarray(frames), None
     N, seg_len = frames.shape
-    if len(trans) != N or len(meta) != N or mf.shape[0] != N or poses.shape[0] != N or mf.shape[1] != poses.shape[2]:
-        raise ValueError(f"need one forecast, transform, meta row, frame row and map_frames row per window, got {tuple(poses.shape)}, "
+    if len(trans) != N or len(meta) != N or mf.shape[0] != N or forecast_shape[0] != N or mf.shape[1] != forecast_shape[-2]:
+        raise ValueError(f"need one forecast, transform, meta row, frame row and map_frames row per window, got {tuple(forecast_shape)}, "
                          f"{trans.shape}, {meta.shape}, {frames.shape}, {mf.shape}")
     ident = np.flatnonzero(trans == 0)
     keys = np.concatenate([np.repeat(meta[ident, :3].astype(np.int64), seg_len, axis=0), frames[ident].reshape(-1, 1).astype(np.int64)], axis=1)
@@ -225,9 +215,83 @@ def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows
         from .transforms import inverse_affine_table
         nt = int(num_transform) if num_transform is not None else (int(trans.max()) + 1 if N else 1)
         extra = {"trans": torch.from_numpy(np.ascontiguousarray(trans, dtype=np.int32)), "inv_affine": inverse_affine_table(nt)}
-    pose, count, spread = assemble(poses, torch.from_numpy(np.ascontiguousarray(cell)), n_rows, method=method, spread_method=spread_method,
-                                   max_cover=max_cover, **extra)
+    return torch.from_numpy(np.ascontiguousarray(cell)), table, extra
+
+
+def forecast_track_rows(poses, trans, map_frames, assemble: Callable, *, windows=None, meta=None, frames=None, method: str = "median",
+                        spread_method: str = "mean", max_cover: int = 32, transforms: str = "identity", num_transform: Optional[int] = None):
+    """Forecast tracks of a dataset (eval_MoCoDAD.py --forecast-tracks): the selected forecast of every window, poses (N,2,Tx,17)
+    (forward(return_='all')), collapsed into one expected pose per trajectory row -- per tracked person and video frame.
+    trans (N,): only windows of transform 0, the identity, contribute.  map_frames (N,Tx): the 0-based window frame index of each
+    pose row (MoCoDAD.map_frames; per window under 'random_imp').  The trajectory rows come from `windows` (a TrajectoryWindows: a
+    row is a row of its buffer, cell = base // 34 + frame index) or from meta (N,4) / frames (N,seg_len) (a row is a distinct
+    (scene, clip, person, frame id) of the transform-0 windows, in lexicographic order).  assemble: engine.forecast_assemble (or a
+    restatement of it).
+    transforms='all' (eval_MoCoDAD.py --forecast-transforms all): the windows of EVERY transform contribute -- their cells are the
+    trajectory row of their forecast frame like transform 0's, and `assemble` is also given trans= and inv_affine= (the inverse
+    table of the transforms 0 .. num_transform - 1, default max(trans) + 1, utils.transforms.inverse_affine_table), with which it
+    maps each forecast back before combining; a row's forecasts are combined transform-major in the order of the windows.  The
+    rows themselves are still those the transform-0 windows cover.  max_cover may be up to 64 then.
+    -> (pose (R,34), count (R,), spread (R,) as `assemble` returns them, rows (R,3) int64 = (scene, clip, person), frame_ids (R,)
+    int64); a row no window forecasts -- the first n_cond rows of a track under a tail forecast -- has count 0 and a zero pose."""
+    cell, table, extra = _forecast_rows_and_cells(tuple(poses.shape), trans, map_frames, windows=windows, meta=meta, frames=frames,
+                                                  transforms=transforms, num_transform=num_transform)
+    pose, count, spread = assemble(poses, cell, len(table), method=method, spread_method=spread_method, max_cover=max_cover, **extra)
     return pose, count, spread, table[:, :3], table[:, 3]
+
+
+def forecast_fan_cover(n_samples: int, cover: int) -> int:
+    """The values one row's list collects for a forecast fan: n_samples per covering pair -- at most MCD_FORECAST_FAN_VALUES (1024),
+    more is refused by name.  -> cover."""
+    from .._lib import MCD_FORECAST_FAN_VALUES as most
+    if int(n_samples) * int(cover) > most:
+        raise ValueError(f"a forecast fan puts n_samples * cover = {int(n_samples)} * {int(cover)} = {int(n_samples) * int(cover)} values on a "
+                         f"row; the reduction holds {most} (use fewer samples, fewer transforms, or transforms='identity')")
+    return int(cover)
+
+
+def forecast_observed_rows(trans, *, windows=None, meta=None, frames=None, data=None):
+    """The observed pose of every trajectory row, (R,2,17) fp32 in the frame-major layout, row for row with the tables of
+    forecast_track_rows / forecast_fan_rows: a view of windows.buffer as it lies, or, without a TrajectoryWindows, scattered on the
+    host from the transform-0 windows' own frames in data (N,2,seg_len,17) (overlapping windows hold the same row)."""
+    import torch
+    if windows is not None:
+        return windows.buffer.view(-1, 2, 17)
+    if meta is None or frames is None or data is None:
+        raise ValueError("forecast_observed_rows needs a TrajectoryWindows, or the windows' meta and frames and the windows themselves (data)")
+    trans, meta, frames = np.asarray(trans).reshape(-1), np.asarray(meta), np.asarray(frames)
+    N, seg_len = frames.shape
+    d = data.detach().cpu().numpy() if torch.is_tensor(data) else np.asarray(data)
+    if d.shape != (N, 2, seg_len, 17) or len(trans) != N or len(meta) != N:
+        raise ValueError(f"data must be the windows ({N}, 2, {seg_len}, 17) with one transform and meta row each, got {d.shape}, "
+                         f"{trans.shape}, {meta.shape}")
+    ident = np.flatnonzero(trans == 0)
+    keys = np.concatenate([np.repeat(meta[ident, :3].astype(np.int64), seg_len, axis=0), frames[ident].reshape(-1, 1).astype(np.int64)], axis=1)
+    table, inv = np.unique(keys, axis=0, return_inverse=True)      # (the row numbering of _forecast_rows_and_cells)
+    obs = np.zeros((len(table), 2, 17), np.float32)
+    obs[inv.reshape(-1)] = d[ident].astype(np.float32).transpose(0, 2, 1, 3).reshape(-1, 2, 17)
+    return torch.from_numpy(obs)
+
+
+def forecast_fan_rows(poses_all, trans, map_frames, fan: Callable, *, windows=None, meta=None, frames=None, data=None,
+                      levels=(0.1, 0.5, 0.9), transforms: str = "identity", num_transform: Optional[int] = None, max_cover: int = 32):
+    """The forecast fan of a dataset (eval_MoCoDAD.py --forecast-fan): ALL S samples of every window, poses_all (N,S,2,Tx,17)
+    (forward(return_samples=True)), as per-row quantile bands, mean, standard deviation and the mid-rank of the observed row among
+    them.  Rows, cells, transforms, num_transform and max_cover: as forecast_track_rows.  The observed rows are those of
+    forecast_observed_rows: windows.buffer, or without a TrajectoryWindows the transform-0 windows' own frames in `data`.
+    fan: engine.forecast_fan (or a restatement of it).  S * max_cover may not exceed 1024.
+    -> (quant (n_levels,R,34), mean (R,34), std (R,34), rank (R,34), count (R,) as `fan` returns them, rows (R,3) int64 = (scene,
+    clip, person), frame_ids (R,) int64)."""
+    if poses_all.ndim != 5:
+        raise ValueError(f"poses_all must be (N, S, 2, Tx, 17), got {tuple(poses_all.shape)}")
+    forecast_fan_cover(poses_all.shape[1], max_cover)
+    cell, table, extra = _forecast_rows_and_cells(tuple(poses_all.shape), trans, map_frames, windows=windows, meta=meta, frames=frames,
+                                                  transforms=transforms, num_transform=num_transform, caller="forecast_fan_rows")
+    if windows is None and data is None:
+        raise ValueError("forecast_fan_rows needs the windows themselves (data) for the observed rows when there is no TrajectoryWindows")
+    observed = forecast_observed_rows(trans, windows=windows, meta=meta, frames=frames, data=data)
+    quant, mean, std, rank, count = fan(poses_all, cell, len(table), levels=levels, observed=observed, max_cover=max_cover, **extra)
+    return quant, mean, std, rank, count, table[:, :3], table[:, 3]
 
 
 def reference_std_score(spread, lift: float = 1e-7) -> np.ndarray:
